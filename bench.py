@@ -21,6 +21,12 @@ master block).  At N>1 every rank compresses its own 100 MB shard of an N x 100 
 on master blocks [100 r, 100 r + 100) with the preceding 32 KiB as dictionary, the chunk blobs
 are gathered to rank 0 over RCCL and merged into one gzip stream.
 
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it sets up, warms up,
+times the K steps, writes the last step's output if `--dump-outputs DIR` is given and prints the line with `metric`,
+`value`, `unit`, `ms_per_step`, `dtype` and `higher_is_better`.  Everything else — `value_resident` and the check that
+both entries give the same stream, round-trip and golden-SHA checks, `roofline` / `roofline_match`, the `blocksplitting1`
+line, `small_files`, the CPU baselines, the `weak` and `in_process` lines at N > 1 — runs with `--full`.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -95,6 +101,25 @@ def _ref_piece(task):
     t0 = time.perf_counter()
     out, _bp = ol.ref_deflate_part(data, start, end, 2, 0, n, split)
     return len(out), time.perf_counter() - t0
+
+
+# --dump-outputs: bytes of the gzip stream kept as float32 values (60 MB, under the 64 MB a dump may hold)
+DUMP_CAP = 15000000
+
+
+def dump_outputs(d, stream):
+    """What the timed path returned in its last step, as DIR/<name>.npy: the gzip stream, one float32 value (0 - 255) per
+    byte — all of it up to DUMP_CAP bytes, else DUMP_CAP positions drawn with a fixed seed (numpy default_rng(0), in stream
+    order) — and, as float64, its size and the CRC-32 of the whole stream.  The input is the same from run to run, so two
+    builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    b = np.frombuffer(stream, dtype=np.uint8)
+    if b.size > DUMP_CAP:
+        b = b[np.sort(np.random.default_rng(0).choice(b.size, DUMP_CAP, replace=False))]
+    np.save(os.path.join(d, "gzip_stream.npy"), b.astype(np.float32))
+    np.save(os.path.join(d, "gzip_stream_size.npy"), np.array([len(stream)], dtype=np.float64))
+    np.save(os.path.join(d, "gzip_stream_crc32.npy"), np.array([zlib.crc32(stream)], dtype=np.float64))
 
 
 def usable_cpus():
@@ -224,7 +249,7 @@ def small_files_line(lib, api, generate, ZopfliOptions, numiterations, sets, cal
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", type=int, default=100 * MB, help="bytes per GPU (default: the 100 MB workload)")
     ap.add_argument("--blocksplitting", type=int, default=None, help="0 = configs[1] (the default at N = 1), 1 = configs[2] "
@@ -259,7 +284,14 @@ def main():
     ap.add_argument("--small-files-only", action="store_true", help="N = 1: only the `small_files` measurement, on a bigger set")
     ap.add_argument("--no-in-process", action="store_true", help="N > 1: skip the extra measurement of the same total input "
                     "through ZopfliCompress in rank 0's process with ZOPFLI_AMD_DEVICES = N (what a drop-in caller gets)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: value_resident (--entry both), the "
+                    "output checks, roofline figures, the blocksplitting1 / small_files / CPU baseline lines and, at N > 1, "
+                    "the weak and in_process lines (the --no-* options above leave parts of it out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's output to DIR/*.npy "
+                    "(dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.devices:
         os.environ["ZOPFLI_AMD_DEVICES"] = args.devices
 
@@ -354,6 +386,8 @@ def main():
         a = copy.copy(args)
         a.scaling = a.scaling or "weak"
         a.blocksplitting = 0 if a.blocksplitting is None else a.blocksplitting
+        if not a.full and a.entry == "both":
+            a.entry = "zopfli_compress"     # (the headline's entry; the resident one beside it is part of --full)
         line = run_one(a)
     else:
         # N > 1 as the driver types it: BASELINE configs[2] is the headline — ONE stream of --size bytes, the reference's
@@ -363,6 +397,7 @@ def main():
         a.scaling = "strong"
         a.blocksplitting = 1 if a.blocksplitting is None else a.blocksplitting
         line = run_one(a)
+    if world > 1 and args.scaling is None and args.full:
         w = copy.copy(args)
         w.scaling = "weak"
         w.blocksplitting = 0
@@ -427,8 +462,10 @@ def _run_one(args, rank, world, dev_index, device, torch, dist, lib, cdist, gath
         total_bytes = size * world
         last_rank = world - 1
     resident = prefix + shard
-    ctx = Context(dev_index, lib)
-    ctx.set_input(resident)  # H2D, outside the timed region
+    ctx = None
+    if world > 1 or args.entry != "zopfli_compress":
+        ctx = Context(dev_index, lib)
+        ctx.set_input(resident)  # H2D, outside the timed region
     instart, inend = len(prefix), len(resident)
     final = 1 if rank == last_rank else 0
     header = bytes([31, 139, 8, 0, 0, 0, 0, 0, 2, 3])
@@ -536,8 +573,9 @@ def _run_one(args, rank, world, dev_index, device, torch, dist, lib, cdist, gath
     if world == 1 and args.entry in ("both", "zopfli_compress"):
         # (the resident run's context gives its cached table arrays back first: what the contexts of a device keep
         #  cached counts against ONE budget per device, and the entry point's own contexts are about to want it)
-        lib.zmx_ctx_trim_cache.argtypes = [ctypes.c_void_p]
-        lib.zmx_ctx_trim_cache(ctx.handle)
+        if ctx is not None:
+            lib.zmx_ctx_trim_cache.argtypes = [ctypes.c_void_p]
+            lib.zmx_ctx_trim_cache(ctx.handle)
         entry_dt, entry_out = run_entry(options, args.steps, args.warmup)   # (timing_acc / seg_acc now hold the entry point's)
         if args.entry == "zopfli_compress":
             dt, out = entry_dt, None
@@ -554,7 +592,7 @@ def _run_one(args, rank, world, dev_index, device, torch, dist, lib, cdist, gath
     #      RCCL measurement while the other ranks wait; its stream must equal the gathered one.
     line = None
     in_process = None
-    if world > 1 and not args.no_in_process:
+    if world > 1 and args.full and not args.no_in_process:
         if rank == 0:
             try:
                 os.environ["ZOPFLI_AMD_DEVICES"] = args.devices or str(world)    # (this process has not used the entry points yet)
@@ -605,6 +643,28 @@ def _run_one(args, rank, world, dev_index, device, torch, dist, lib, cdist, gath
         else:
             ms, value = ms_resident, value_resident
             out = resident_out
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
+        line = {
+            "metric": "input MB/s at numiterations=15 (gzip, bit-exact vs reference)",
+            "value": round(value, 4), "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms, 2), "higher_is_better": True, "scaling": "strong" if strong else "weak",
+            "entry": ("ZopfliCompress(options, ZOPFLI_FORMAT_GZIP, host buffer, size, &out, &outsize) of libzopfli_amd.so: host "
+                      "to device copy and context reuse inside the clock" if entry_dt is not None else
+                      "resident input: zmx_deflate_range + zmx_chunks_merge (H2D outside the clock)"),
+            "dtype": "u8 (f32/f64 cost DP)", "data": "synthetic" if corpus is None else "file:" + os.path.basename(args.file),
+            "config": {"workload": (f"class-{args.cls} synthetic ({CLASS_NAMES.get(args.cls, 'class ' + args.cls)})" if corpus is None
+                                    else "file " + os.path.basename(args.file)) +
+                                   f" {size} B {'in total' if strong else 'per GPU'}, numiterations="
+                                   f"{args.numiterations}, blocksplitting={args.blocksplitting}, gzip, "
+                                   + baseline_config_name(args.cls if corpus is None else None, size, args.numiterations,
+                                                          args.blocksplitting),
+                       "total_bytes": total, "master_blocks": (total + MB - 1) // MB,
+                       "sharding": "master blocks, contiguous per rank (strong scaling: ranges balanced by the estimated cost of their bytes, zmx_master_block_costs; weak: a fixed size per rank), gather of bit chunks to rank 0",
+                       "gather": gather_kind},
+            "output_bytes": len(out),
+        }
+    if rank == 0 and args.full:
         # ---- correctness of the measured output (outside the timed region)
         bitexact = None
         roundtrip = None
@@ -697,27 +757,11 @@ def _run_one(args, rank, world, dev_index, device, torch, dist, lib, cdist, gath
                     "note": "entries in flight = lanes with an entry's loads outstanding, summed over the wave iterations (an "
                             "entry longer than 15 bytes in common takes one more iteration per 16 bytes); the reference's walk "
                             "visits 100 (text) to 2 200 (two-symbol data) chain entries per position, counted here from ranks"}
-        line = {
-            "metric": "input MB/s at numiterations=15 (gzip, bit-exact vs reference)",
-            "value": round(value, 4), "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms, 2), "higher_is_better": True, "scaling": "strong" if strong else "weak",
-            "entry": ("ZopfliCompress(options, ZOPFLI_FORMAT_GZIP, host buffer, size, &out, &outsize) of libzopfli_amd.so: host "
-                      "to device copy and context reuse inside the clock" if entry_dt is not None else
-                      "resident input: zmx_deflate_range + zmx_chunks_merge (H2D outside the clock)"),
+        line.update({
             "value_resident": None if value_resident is None else round(value_resident, 4),
             "ms_per_step_resident": None if ms_resident is None else round(ms_resident, 2),
             "vs_baseline": None,
-            "dtype": "u8 (f32/f64 cost DP)", "data": "synthetic" if corpus is None else "file:" + os.path.basename(args.file),
-            "config": {"workload": (f"class-{args.cls} synthetic ({CLASS_NAMES.get(args.cls, 'class ' + args.cls)})" if corpus is None
-                                    else "file " + os.path.basename(args.file)) +
-                                   f" {size} B {'in total' if strong else 'per GPU'}, numiterations="
-                                   f"{args.numiterations}, blocksplitting={args.blocksplitting}, gzip, "
-                                   + baseline_config_name(args.cls if corpus is None else None, size, args.numiterations,
-                                                          args.blocksplitting),
-                       "total_bytes": total, "master_blocks": (total + MB - 1) // MB,
-                       "sharding": "master blocks, contiguous per rank (strong scaling: ranges balanced by the estimated cost of their bytes, zmx_master_block_costs; weak: a fixed size per rank), gather of bit chunks to rank 0",
-                       "gather": gather_kind},
-            "output_bytes": len(out), "roundtrip_ok": roundtrip, "bitexact_vs_reference": bitexact,
+            "roundtrip_ok": roundtrip, "bitexact_vs_reference": bitexact,
             "roofline": roofline,
             "roofline_match": roofline_match,
             "chain_tasks_per_step": {k: round(v / args.steps, 1) for k, v in seg_acc.items()},
@@ -732,7 +776,7 @@ def _run_one(args, rank, world, dev_index, device, torch, dist, lib, cdist, gath
             "breakdown_s_per_step_resident": None if resident_timing is None else {
                 k: round(v / args.steps, 4) for k, v in resident_timing.items()
                 if k not in ("squeeze_launches", "table_builds", "positions_matched")},
-        }
+        })
         if roofline is not None and entry_dt is not None and timing_acc.get("squeeze_launches"):
             roofline["avg_launch_ms_entry_summed_over_contexts"] = round(
                 timing_acc.get("dp_kernel", 0.0) / timing_acc["squeeze_launches"] * 1e3, 3)
@@ -784,7 +828,8 @@ def _run_one(args, rank, world, dev_index, device, torch, dist, lib, cdist, gath
             allc = cpu_baseline_all_cores(shard, options) if world == 1 else None
             if allc:
                 line["cpu_baseline_all_cores"] = allc
-    ctx.close()
+    if ctx is not None:
+        ctx.close()
     return line if rank == 0 else None
 
 

@@ -20,11 +20,11 @@ def test_exports_match_header():
 def test_png_library_exports_the_reference_abi():
     """libzopflipng_amd.so has the C entry points of the reference's zopflipng_lib.h (:76-85) and its defaults
     (zopflipng_lib.cc:33-43); the C++ ones are checked by linking the reference's own command line against it
-    (_build.build_png_tests).  No device call."""
+    (oracle/Makefile).  No device call."""
     import pytest
     from zopfli_amd._build import PNG_LIB
     if not os.path.exists(PNG_LIB):
-        pytest.skip("libzopflipng_amd.so not built (LodePNG's sources were not at hand)")
+        pytest.skip("oracle/_ref/libzopflipng_amd.so not built (LodePNG's sources were not at hand)")
     lib = ctypes.CDLL(PNG_LIB)
 
     class COpts(ctypes.Structure):    # zopflipng_lib.h:51-72

@@ -754,7 +754,7 @@ def test_reference_cli_linked_against_libzopfli_amd(tmp_path):
     import subprocess
     from zopfli_amd._build import REF_CLI
     if not os.path.exists(REF_CLI):
-        pytest.skip("tests/_build/zopfli_ref_cli_amd not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/zopfli_ref_cli_amd not built (needs the reference's sources at build time)")
     data = generate("X", 300000, 5)
     src = tmp_path / "input.xml"
     src.write_bytes(data)
@@ -775,7 +775,7 @@ def test_dynamic_user_of_libzopfli_so_1_switches_by_library_path(tmp_path):
     import subprocess
     from zopfli_amd._build import LIB_SONAME, REF_CLI_DYN, REF_SO_DIR
     if not (os.path.exists(REF_CLI_DYN) and os.path.exists(LIB_SONAME)):
-        pytest.skip("tests/_build/zopfli_ref_cli_dyn not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/zopfli_ref_cli_dyn not built (needs the reference's sources at build time)")
     data = generate("M", 250000, 3)
     outs = {}
     for name, libdir in (("ref", REF_SO_DIR), ("amd", os.path.dirname(LIB_SONAME))):
@@ -905,7 +905,8 @@ def test_bench_gpus_2_as_typed():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device-index", "0",
-                        "--size", "4000000", "--steps", "1", "--warmup", "0", "--cpu-sample", "200000", "--devices", "0,0"],
+                        "--size", "4000000", "--steps", "1", "--warmup", "0", "--cpu-sample", "200000", "--devices", "0,0",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -916,6 +917,28 @@ def test_bench_gpus_2_as_typed():
     assert d["roofline"] and d["cpu_baseline"]["cores"] == 1
     assert d["weak"]["scaling"] == "weak" and d["weak"]["config"]["total_bytes"] == 8000000 and d["weak"]["roundtrip_ok"] is True
     assert d["in_process"].get("same_stream_as_gathered") is True, d["in_process"]
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) times the headline only, --steps sets the timed steps, and
+    --dump-outputs writes the last timed step's gzip stream (one float32 per byte, with its size and CRC-32 as float64):
+    it decompresses to the seeded input."""
+    import subprocess
+    import sys
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "3000000", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "MB/s" and d["higher_is_better"] is True
+    assert "ZopfliCompress" in d["entry"] and not {"roofline", "cpu_baseline", "small_files", "blocksplitting1"} & set(d)
+    s = np.load(dump / "gzip_stream.npy")
+    assert s.dtype == np.float32 and s.size == d["output_bytes"] == int(np.load(dump / "gzip_stream_size.npy")[0])
+    stream = s.astype(np.uint8).tobytes()
+    assert zlib.crc32(stream) == int(np.load(dump / "gzip_stream_crc32.npy")[0])
+    assert gzip.decompress(stream) == generate("T", 3000000)
 
 
 def _write_png(path, width, height, seed):
@@ -945,7 +968,7 @@ def test_zopflipng_linked_against_libzopfli_amd(tmp_path):
     import subprocess
     from zopfli_amd._build import PNG_AMD, PNG_REF
     if not (os.path.exists(PNG_AMD) and os.path.exists(PNG_REF)):
-        pytest.skip("tests/_build/zopflipng_* not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/zopflipng_* not built (needs the reference's sources at build time)")
     src = str(tmp_path / "in.png")
     _write_png(src, 384, 256, 7)
     outs = {}

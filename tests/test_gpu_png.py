@@ -21,7 +21,7 @@ LCT_GREY, LCT_RGB, LCT_PALETTE, LCT_GREY_ALPHA, LCT_RGBA = 0, 2, 3, 4, 6
 def _filter_ref():
     from zopfli_amd._build import PNG_FILTER_REF
     if not os.path.exists(PNG_FILTER_REF):
-        pytest.skip("tests/_build/libpng_filter_ref.so not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/libpng_filter_ref.so not built (needs the reference's sources at build time)")
     lib = ctypes.CDLL(PNG_FILTER_REF)
     lib.ref_png_filter.argtypes = [ctypes.c_char_p, ctypes.c_char_p] + [ctypes.c_uint] * 5
     lib.ref_png_filter.restype = ctypes.c_uint
@@ -156,7 +156,7 @@ def test_libzopflipng_amd_vs_reference(tmp_path, which, args):
     (zopflipng_lib.cc:160-470)."""
     from zopfli_amd._build import PNG_AMD2, PNG_REF
     if not (os.path.exists(PNG_AMD2) and os.path.exists(PNG_REF)):
-        pytest.skip("tests/_build/zopflipng_amd2 / zopflipng_ref not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/zopflipng_amd2 / zopflipng_ref not built (needs the reference's sources at build time)")
     src = _make_inputs(tmp_path)[which]
     outs = {}
     for name, exe in (("amd", PNG_AMD2), ("ref", PNG_REF)):
@@ -173,7 +173,7 @@ def test_device_filters_are_used(tmp_path):
     the LFS_PREDEFINED hand-over changes nothing but who searched."""
     from zopfli_amd._build import PNG_AMD2
     if not os.path.exists(PNG_AMD2):
-        pytest.skip("tests/_build/zopflipng_amd2 not built")
+        pytest.skip("oracle/_ref/zopflipng_amd2 not built")
     src = _make_inputs(tmp_path)["rgba"]
     outs = []
     for env in ({}, {"ZOPFLIPNG_AMD_HOST_FILTERS": "1"}):
@@ -211,7 +211,7 @@ def test_png_at_size_vs_reference_golden(tmp_path, width):
     import json
     from zopfli_amd._build import PNG_AMD2
     if not os.path.exists(PNG_AMD2):
-        pytest.skip("tests/_build/zopflipng_amd2 not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/zopflipng_amd2 not built (needs the reference's sources at build time)")
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "png_at_size.json")) as f:
         gold = json.load(f)[str(width)]
     src, dst = str(tmp_path / "in.png"), str(tmp_path / "out.png")

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/${TAG:-profile_run}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="${BENCH_ARGS:---steps 1 --warmup 0 --no-cpu-baseline}"
+ARGS="--full ${BENCH_ARGS:---steps 1 --warmup 0 --no-cpu-baseline}"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o r -- python $REPO/bench.py $ARGS > $OUT/stats.log 2>&1
 grep '^{"metric"' $OUT/stats.log | tail -1 > $OUT/bench_line.json
 i=0

@@ -10,10 +10,10 @@ for scaling in weak strong; do
   for n in 1 2 4 8; do
     [ $n -gt $MAXG ] && continue
     if [ $n -eq 1 ]; then
-      python bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --scaling $scaling
+      python bench.py --gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline --scaling $scaling
     else
       python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-        bench.py --gpus $n --steps 3 --warmup 1 --no-cpu-baseline --scaling $scaling
+        bench.py --gpus $n --steps 3 --warmup 1 --full --no-cpu-baseline --scaling $scaling
     fi
   done
 done
