@@ -124,7 +124,8 @@ typedef struct zmx_ctx zmx_ctx;       /* one HIP device + stream + resident inpu
 typedef struct zmx_tables zmx_tables; /* match tables + LZ77 stores of a batch of blocks */
 
 /* One deflate block: bytes [instart, inend) of the resident input.  Matches may
- * reach back to max(0, instart-32768) and never extend past inend
+ * reach back to max(0, instart-32768) — or to the start of the block's segment, when
+ * zmx_set_input_segments declared some — and never extend past inend
  * (lz77.c:551-552, squeeze.c:229-230). */
 typedef struct zmx_block {
   uint64_t instart;
@@ -163,6 +164,14 @@ void zmx_ctx_destroy(zmx_ctx* ctx);
  * blocks): `in` must stay valid and unchanged until the next zmx_set_input or zmx_ctx_destroy on
  * this context.  The calling thread's current HIP device is left as it was. */
 int zmx_set_input(zmx_ctx* ctx, const unsigned char* in, size_t insize);
+
+/* Declares the resident input (the last zmx_set_input, which resets it to one segment) to be the concatenation of nseg
+ * independent inputs: segment i is bytes [starts[i], starts[i + 1]), the last one ends at the input's end; starts[0] = 0,
+ * the starts never decrease and none lies past the end (empty segments are allowed).  From this call on the window of a
+ * block built by zmx_tables_build* reaches back to max(start of its segment, instart - 32768) instead of
+ * max(0, instart - 32768): each input is compressed as if it were alone.  A block that spans two segments is refused
+ * (ZMX_ERR_REFUSED). */
+int zmx_set_input_segments(zmx_ctx* ctx, const uint64_t* starts, size_t nseg);
 
 /* Kernel A.  For every block: the static hash arrays (hash.c:100-137 val/same/
  * prev links as pure functions of the data and inend) and, for every position,
@@ -249,6 +258,10 @@ int zmx_encode_blocks(zmx_ctx* ctx, zmx_tables* tables, size_t njobs, const zmx_
 #define ZMX_CRC32 0
 #define ZMX_ADLER32 1
 int zmx_checksum(zmx_ctx* ctx, int kind, size_t begin, size_t end, uint32_t* value);
+/* The same for n ranges [begin[i], end[i]) at once (one launch set, one synchronisation): values[i] = the checksum of
+ * range i on its own; an empty range gives the initial value (CRC-32 0, Adler-32 1).  For the containers of a batch of
+ * inputs (zmx_compress_batch). */
+int zmx_checksums(zmx_ctx* ctx, int kind, size_t n, const uint64_t* begin, const uint64_t* end, uint32_t* values);
 uint32_t zmx_checksum_combine(int kind, uint32_t a, uint32_t b, uint64_t len_b);
 
 /* Parity probe: the ZopfliFindLongestMatch result for one position of one
@@ -276,6 +289,7 @@ int zmx_png_filter_types_pooled(const unsigned char* image, size_t linebytes, si
 int zmx_match_digest(zmx_ctx* ctx, zmx_tables* tables, uint64_t* out2);
 
 /* Parity probe: the static hash arrays of one block for positions max(0, instart - 32768) .. inend - 1
+ * (from the start of the block's segment instead, when that is later: zmx_set_input_segments)
  * (inend - windowstart entries each): same[] (hash.c:116-126) and the distances to the previous
  * position of the same hash / of the same second hash (hash.c:110-114, 129-135; 0 = none).
  * Fails for tables built with zmx_tables_build_from and a parent: those hold the hash arrays only
@@ -313,6 +327,19 @@ int zmx_block_costs(zmx_ctx* ctx, zmx_cost_stores* stores, size_t n, const uint3
 /* ZopfliLZ77GetByteRange (lz77.c:160-166) from the start of a sequence: bytes[i] = the input bytes that symbols
  * [0, pairs[2 i + 1]) of sequence pairs[2 i] stand for — where a split point lies (blocksplitter.c:303-314). */
 int zmx_cost_positions(zmx_ctx* ctx, zmx_cost_stores* stores, size_t n, const uint32_t* pairs, uint64_t* bytes);
+
+/* -------- many independent inputs in one call
+ *
+ * n independent ZopfliCompress calls in one: out[i], outsize[i] end as ZopfliCompress(options, output_type, in[i],
+ * insize[i], &out[i], &outsize[i]) leaves them (appended to, reference convention; the caller frees) — byte for byte,
+ * whatever the other inputs and their order.  The inputs' master blocks are dealt over the contexts and devices of the
+ * Zopfli* entry points together, so small files share the table builds, squeeze runs and bit writes of one large call
+ * (zmx_set_input_segments keeps each input's window inside it).  With options->verbose stderr carries the lines of the
+ * n calls, in input order.  0 on success (n = 0 included); -1 with zmx_last_error / zmx_last_error_class, and no out[i]
+ * changed, on failure. */
+int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
+                       const unsigned char* const* in, const size_t* insize,
+                       unsigned char** out, size_t* outsize);
 
 /* -------- whole-stream entry points on a resident input (bench, multi-GPU) */
 

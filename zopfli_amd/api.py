@@ -149,6 +149,27 @@ def compress(data, fmt=FORMAT_GZIP, options=None, lib=None):
     return _take(out, size)
 
 
+def compress_batch(datas, fmt=FORMAT_GZIP, options=None, lib=None):
+    """zmx_compress_batch: one ZopfliCompress output per input (a list of bytes), computed in one pass over the
+    devices.  Raises RuntimeError with the library's message on failure."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    n = len(datas)
+    keep = [bytes(d) for d in datas]
+    ins = (ctypes.c_char_p * max(n, 1))(*keep)
+    sizes = (ctypes.c_size_t * max(n, 1))(*[len(d) for d in keep])
+    outs = (_u8p * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    # (bound here, not in bind(): a library without the batch entry point — the CPU test library — still loads)
+    fn = lib.zmx_compress_batch
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p),
+                   ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), fmt, n, ins, sizes, outs, outsizes) != 0:
+        raise RuntimeError("zmx_compress_batch: " + (lib.zmx_last_error() or b"").decode())
+    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+
+
 def deflate(data, btype=2, final=1, options=None, lib=None):
     """ZopfliDeflate (deflate.c:908) from bp = 0; returns (bytes, bp)."""
     lib = lib or library()
@@ -206,6 +227,7 @@ class Context:
         self.lib = lib or library()
         self.handle = ctypes.c_void_p()
         self._input = None
+        self._segments = None
         if self.lib.zmx_ctx_create(device, ctypes.byref(self.handle)) != 0:
             raise RuntimeError("zmx_ctx_create: " + self.error())
 
@@ -223,7 +245,39 @@ class Context:
 
     def set_input(self, data):
         self._input = data
+        self._segments = None
         self._check(self.lib.zmx_set_input(self.handle, data, len(data)), "zmx_set_input")
+
+    def set_input_segments(self, starts):
+        """zmx_set_input_segments: the resident input is the concatenation of independent inputs starting at
+        `starts` (starts[0] = 0, non-decreasing); a block's window stops at the start of its own input."""
+        n = len(starts)
+        arr = (ctypes.c_uint64 * max(n, 1))(*starts)
+        fn = self.lib.zmx_set_input_segments
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, arr, n), "zmx_set_input_segments")
+        self._segments = list(starts)
+
+    def window_start(self, instart):
+        """Where the window of a block starting at `instart` begins: max(start of its segment, instart - 32768)."""
+        floor = 0
+        if self._segments:
+            floor = max(x for x in self._segments if x <= instart)
+        return max(floor, instart - 32768)
+
+    def checksums(self, kind, ranges):
+        """zmx_checksums: CRC-32 / Adler-32 of every resident range (begin, end), in one launch set."""
+        n = len(ranges)
+        b = (ctypes.c_uint64 * max(n, 1))(*[r[0] for r in ranges])
+        e = (ctypes.c_uint64 * max(n, 1))(*[r[1] for r in ranges])
+        v = (ctypes.c_uint32 * max(n, 1))()
+        fn = self.lib.zmx_checksums
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
+                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, kind, n, b, e, v), "zmx_checksums")
+        return [int(v[i]) for i in range(n)]
 
     def build_tables(self, blocks, parent=None, matches_only=False):
         """zmx_tables_build, zmx_tables_build_matches (no DP rows: for the greedy pass and as a parent), or
@@ -521,7 +575,7 @@ class Tables:
         """same[], prev1[], prev2[] of the block's positions from windowstart on (zmx_hash_links_download)."""
         import numpy as np
         s, e = self.blocks[block]
-        n = e - max(0, s - 32768)
+        n = e - self.ctx.window_start(s)
         arrs = [np.zeros(max(n, 1), dtype=np.uint16) for _ in range(3)]
         ptrs = [a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)) for a in arrs]
         self.ctx._check(self.ctx.lib.zmx_hash_links_download(self.ctx.handle, self.handle, block, *ptrs),

@@ -30,7 +30,8 @@ __device__ __forceinline__ u32 ck_mulmod(u32 a, u32 b) {
   return p;
 }
 
-__global__ __launch_bounds__(256) void k_checksum(ChecksumParams P) {
+// One piece: the 256 KiB (or less, for the leftmost piece of a range) that end at wg_end, clipped to begin.
+__device__ __forceinline__ void ck_piece(const u8* in, long long begin, long long wg_end, const u32* xpow, u32* out) {
   constexpr long long LANE = zamd::kChecksumLaneBytes;
   constexpr u32 BASE = zamd::kAdlerBase;
   static_assert(zamd::kChecksumLanes == 256, "one lane per table entry");
@@ -48,12 +49,10 @@ __global__ __launch_bounds__(256) void k_checksum(ChecksumParams P) {
     }
     __syncthreads();
   }
-  const long long wg_end = P.end - static_cast<long long>(blockIdx.x) * (LANE * 256);
   const long long hi = wg_end - static_cast<long long>(255 - t) * LANE;
   long long p = hi - LANE;
-  if (p < P.begin) p = P.begin;
+  if (p < begin) p = begin;
   u32 crc = 0, sum = 0, wsum = 0;
-  const u8* in = P.in;
   for (; p < hi && (p & 3); ++p) {
     const u32 d = in[p];
     crc = s_t[0][(crc ^ d) & 255] ^ (crc >> 8);
@@ -83,16 +82,35 @@ __global__ __launch_bounds__(256) void k_checksum(ChecksumParams P) {
     if ((t & (2 * s - 1)) == 0) {
       const u32 right_bytes = (s * static_cast<u32>(LANE)) % BASE;
       const u32 la = s_a[t];
-      s_c[t] = ck_mulmod(s_c[t], P.xpow[k]) ^ s_c[t + s];
+      s_c[t] = ck_mulmod(s_c[t], xpow[k]) ^ s_c[t + s];
       s_b[t] = static_cast<u32>((s_b[t] + static_cast<unsigned long long>(right_bytes) * la + s_b[t + s]) % BASE);
       s_a[t] = (la + s_a[t + s]) % BASE;
     }
   }
   if (t == 0) {
-    P.out[3 * blockIdx.x + 0] = s_c[0];
-    P.out[3 * blockIdx.x + 1] = s_a[0];
-    P.out[3 * blockIdx.x + 2] = s_b[0];
+    out[0] = s_c[0];
+    out[1] = s_a[0];
+    out[2] = s_b[0];
   }
+}
+
+__global__ __launch_bounds__(256) void k_checksum(ChecksumParams P) {
+  ck_piece(P.in, P.begin, P.end - static_cast<long long>(blockIdx.x) * (zamd::kChecksumLaneBytes * 256ll), P.xpow,
+           P.out + 3 * blockIdx.x);
+}
+
+// Pieces of many ranges in one launch (zmx_checksums): workgroup i takes the piece that ends at pieces[2 i + 1] of the
+// range that begins at pieces[2 i]; the host lists each range's pieces from its end, as k_checksum numbers them.
+struct ChecksumsParams {
+  const u8* in;
+  const long long* pieces;   // [pieces][2]: range begin, piece end
+  u32* out;                  // [pieces][3], as k_checksum
+  u32 xpow[8];
+};
+
+__global__ __launch_bounds__(256) void k_checksums(ChecksumsParams P) {
+  const long long begin = P.pieces[2 * blockIdx.x], wg_end = P.pieces[2 * blockIdx.x + 1];
+  ck_piece(P.in, begin, wg_end, P.xpow, P.out + 3 * blockIdx.x);
 }
 
 #endif  // ZMX_CHECKSUM_H_

@@ -145,6 +145,7 @@ struct zmx_ctx {
   u8* d_in = nullptr;
   size_t insize = 0, in_cap = 0;
   const unsigned char* h_in = nullptr;  // caller's buffer (borrowed until the next zmx_set_input)
+  std::vector<u64> seg_starts;          // zmx_set_input_segments: first byte of each independent input (empty: one input)
   u32* d_scratch = nullptr;  // k_match2 per-lane overflow change points
   u32* d_scratch5 = nullptr; // k_match5's (it may run beside k_match2)
   // table arrays are recycled between batches and calls: hipMalloc/hipFree of multi-GB arrays
@@ -554,6 +555,7 @@ int zmx_set_match_kernel(int kernel) {
 size_t zmx_internal_input_size(zmx_ctx* ctx) { return ctx->insize; }
 int zmx_internal_device(zmx_ctx* ctx) { return ctx->device; }
 void zmx_internal_set_error(const char* msg) { g_err = msg; g_err_class = ZMX_ERR_DEVICE; }
+void zmx_internal_set_error_class(const char* msg, int cls) { g_err = msg; g_err_class = cls; }
 const unsigned char* zmx_internal_input_host(zmx_ctx* ctx) { return ctx->h_in; }
 
 void zmx_internal_seg_stats(double* out8, int reset) {
@@ -717,6 +719,22 @@ int zmx_set_input(zmx_ctx* c, const unsigned char* in, size_t insize) {
   HIPCHK(hipStreamSynchronize(c->stream));
   c->insize = insize;
   c->h_in = in;
+  c->seg_starts.clear();
+  return 0;
+}
+
+// The resident input is the concatenation of independent inputs: a block's window stops at the first byte of its own
+// input instead of reaching 32 KiB into the one before it (BuildTables).  Every kernel works on [ws, inend) with link
+// indices relative to ws, so a floor on ws is all the rest needs.
+int zmx_set_input_segments(zmx_ctx* c, const uint64_t* starts, size_t nseg) {
+  if (nseg == 0 || starts == nullptr) return FailMsg("zmx_set_input_segments: no segments");
+  if (starts[0] != 0) return FailMsg("zmx_set_input_segments: the first segment must start at 0");
+  for (size_t i = 0; i < nseg; ++i) {
+    if (starts[i] > c->insize) return FailMsg("zmx_set_input_segments: a segment starts past the end of the input");
+    if (i && starts[i] < starts[i - 1]) return FailMsg("zmx_set_input_segments: segment starts must not decrease");
+  }
+  c->seg_starts.assign(starts, starts + nseg);
+  if (nseg == 1) c->seg_starts.clear();
   return 0;
 }
 
@@ -859,6 +877,14 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
     d.instart = blocks[b].instart;
     d.inend = blocks[b].inend;
     d.ws = d.instart > ZMX_WINDOW ? d.instart - ZMX_WINDOW : 0;
+    if (!c->seg_starts.empty()) {
+      // the segment of the block's first byte (the last of several that start there: the empty ones hold no block)
+      const size_t k = static_cast<size_t>(std::upper_bound(c->seg_starts.begin(), c->seg_starts.end(), d.instart) -
+                                           c->seg_starts.begin()) - 1;
+      const u64 seg_end = k + 1 < c->seg_starts.size() ? c->seg_starts[k + 1] : c->insize;
+      if (d.inend > seg_end) return FailMsg("zmx_tables_build: block spans two input segments (zmx_set_input_segments)");
+      d.ws = std::max<u64>(d.ws, c->seg_starts[k]);
+    }
     d.pos_off = pos_off;
     d.reg_off = reg_off;
     d.la_off = la_off;
@@ -2181,6 +2207,56 @@ int zmx_checksum(zmx_ctx* c, int kind, size_t begin, size_t end, uint32_t* value
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   *value = kind == ZMX_CRC32 ? zamd::FinishCrc32(pieces.data(), npieces, n) : zamd::FinishAdler32(pieces.data(), npieces, n);
+  return 0;
+}
+
+// zmx_checksum of n ranges in one launch: the 256 KiB pieces of every range, each range's listed from its end, go through
+// k_checksums together and are put together per range on the host.
+int zmx_checksums(zmx_ctx* c, int kind, size_t n, const uint64_t* begin, const uint64_t* end, uint32_t* values) {
+  if (kind != ZMX_CRC32 && kind != ZMX_ADLER32) return FailMsg("zmx_checksums: unknown kind");
+  if (n == 0) return 0;
+  if (!begin || !end || !values) return FailMsg("zmx_checksums: null array");
+  std::vector<size_t> first(n + 1, 0);
+  for (size_t r = 0; r < n; ++r) {
+    if (begin[r] > end[r] || end[r] > c->insize) return FailMsg("zmx_checksums: range outside the resident input");
+    first[r + 1] = first[r] + (end[r] - begin[r] + zamd::kChecksumPieceBytes - 1) / zamd::kChecksumPieceBytes;
+  }
+  const size_t npieces = first[n];
+  if (npieces > 0x7fffffffull) return FailMsg("zmx_checksums: too many pieces for one launch");
+  std::vector<zamd::ChecksumPiece> pieces(npieces);
+  if (npieces) {
+    std::vector<long long> tab(2 * npieces);
+    for (size_t r = 0; r < n; ++r) {
+      for (size_t j = first[r]; j < first[r + 1]; ++j) {
+        tab[2 * j] = static_cast<long long>(begin[r]);
+        tab[2 * j + 1] = static_cast<long long>(end[r]) - static_cast<long long>((j - first[r]) * zamd::kChecksumPieceBytes);
+      }
+    }
+    DeviceGuard dev_guard(c->device);
+    HIPCHK(dev_guard.err);
+    PoolScope tmp(c);
+    u32* d_out = nullptr;
+    long long* d_tab = nullptr;
+    HIPCHK(tmp.AllocT(&d_out, 3 * npieces, "d_out"));
+    HIPCHK(tmp.AllocT(&d_tab, 2 * npieces, "d_tab"));
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    ChecksumsParams P;
+    P.in = c->d_in;
+    P.pieces = d_tab;
+    P.out = d_out;
+    zamd::ChecksumTreePowers(P.xpow);
+    hipLaunchKernelGGL(k_checksums, dim3(static_cast<unsigned>(npieces)), dim3(256), 0, c->stream, P);
+    KCHK(c, "k_checksums");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(pieces.data(), d_out, npieces * sizeof(zamd::ChecksumPiece), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  for (size_t r = 0; r < n; ++r) {
+    const zamd::ChecksumPiece* pc = pieces.data() + first[r];
+    const size_t np = first[r + 1] - first[r];
+    const uint64_t len = end[r] - begin[r];
+    values[r] = kind == ZMX_CRC32 ? zamd::FinishCrc32(pc, np, len) : zamd::FinishAdler32(pc, np, len);
+  }
   return 0;
 }
 

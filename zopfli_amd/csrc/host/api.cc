@@ -22,6 +22,7 @@
 #include "lz77_optimal.h"
 #include "symbols.h"
 #include "deal.h"
+#include "dealing.h"
 #include "thread_pool.h"
 #include "zopfli_amd.h"
 
@@ -335,16 +336,30 @@ std::vector<zamd::Part> MasterBlocks(size_t insize, bool final) {
   return parts;
 }
 
+// `group_bytes` (batches of many small inputs, zamd::ShardHooks): a DeflateParts call takes parts up to that many bytes
+// instead of PartsPerBatch() parts — 256 parts of 64 KiB would leave the device idle — and at most 2048 of them (a part
+// may become 15 blocks or more, and the blocks of a table build are one launch dimension).
+// `part_chunks` (optional): the number of chunks of every part, in part order.
 int RunParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const std::vector<zamd::Part>& parts,
-             std::vector<zamd::Chunk>* chunks) {
+             std::vector<zamd::Chunk>* chunks, std::vector<size_t>* part_chunks = nullptr, size_t group_bytes = 0) {
   size_t step = PartsPerBatch();
+  size_t step_bytes = group_bytes;
   for (size_t a = 0; a < parts.size();) {
-    const size_t b = a + step < parts.size() ? a + step : parts.size();
+    size_t b = a + step < parts.size() ? a + step : parts.size();
+    if (group_bytes) {
+      b = a + 1;
+      size_t bytes = parts[a].inend - parts[a].instart;
+      while (b < parts.size() && b - a < 2048 && bytes + (parts[b].inend - parts[b].instart) <= step_bytes) {
+        bytes += parts[b].inend - parts[b].instart;
+        ++b;
+      }
+    }
     std::vector<zamd::Part> group(parts.begin() + static_cast<long>(a), parts.begin() + static_cast<long>(b));
     std::vector<zamd::Chunk> got;
-    const int rc = zamd::DeflateParts(ctx, options, btype, group, &got);
+    const int rc = zamd::DeflateParts(ctx, options, btype, group, &got, part_chunks);
     if (rc == -2 && b - a > 1) {   // the DP edges of the batch do not fit the device layer's budget: smaller batches
       step = (b - a + 1) / 2;
+      step_bytes = std::max<size_t>(step_bytes / 2, 1);
       continue;
     }
     if (rc) return rc;
@@ -367,9 +382,13 @@ struct ChecksumRequest {
   uint32_t value;
 };
 
+// `hooks` (zmx_compress_batch): `in` is the concatenation of independent inputs — a shard's upload starts no lower than
+// the first byte of its first part's input, the hooks tell the context its segments after the upload, the parts are
+// grouped by bytes; `part_chunks` (optional) gets the number of chunks of every part, in part order.
 int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned char* in,
                         const std::vector<zamd::Part>& parts, std::vector<zamd::Chunk>* chunks,
-                        ChecksumRequest* sum = nullptr) {
+                        ChecksumRequest* sum = nullptr, std::vector<size_t>* part_chunks = nullptr,
+                        zamd::ShardHooks* hooks = nullptr) {
   // (ZOPFLI_AMD_SPLIT_MB: from this many master blocks on, a request is dealt over ZOPFLI_AMD_SPLIT_WAYS = 3 contexts of
   //  each device — measured on 100 MB of text: 2 ways 123.2 ms, 3 ways 121.1, 4 ways 140; with block splitting 225 / 197 / 231;
   //  0 = never.  The GPU idles while the host computes a hundred cost models between two squeeze runs — 6 % of a
@@ -429,6 +448,7 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
   struct Shard {
     size_t first = 0, last = 0, base = 0;
     std::vector<zamd::Chunk> chunks;
+    std::vector<size_t> part_chunks;
     int rc = 0;
     std::string err;
     int err_class = ZMX_ERR_NONE;   // zmx_last_error_class() of the failure
@@ -563,6 +583,7 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
     sh.err.clear();
     sh.err_class = ZMX_ERR_NONE;
     sh.chunks.clear();
+    sh.part_chunks.clear();
     sh.sum = 0;
     sh.sum_bytes = 0;
     if (!retry && fail_shard == static_cast<long>(d)) {
@@ -573,13 +594,14 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
     }
     const size_t start = parts[sh.first].instart, end = parts[sh.last - 1].inend;
     sh.base = start > zamd::kWindow ? start - zamd::kWindow : 0;
+    if (hooks) sh.base = std::max(sh.base, hooks->floor(parts[sh.first].instart));
     const double tr0 = WallMs();
     if (!retry) turn.Wait();
     const double tr1 = WallMs();
     const int up = zmx_set_input(ctx, in + sh.base, end - sh.base);
     turn.Release();
     const double tr2 = WallMs();
-    if (up != 0) {
+    if (up != 0 || (hooks && hooks->uploaded(d, ctx, sh.base, sh.first, sh.last) != 0)) {
       sh.rc = -1;
       sh.err = zmx_last_error();
       sh.err_class = zmx_last_error_class();
@@ -597,7 +619,13 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
     std::vector<zamd::Part> mine(parts.begin() + static_cast<long>(sh.first), parts.begin() + static_cast<long>(sh.last));
     for (auto& p : mine) { p.instart -= sh.base; p.inend -= sh.base; }
     const double tr3 = WallMs();
-    sh.rc = RunParts(ctx, options, btype, mine, &sh.chunks);
+    struct SplitOnDevice {
+      bool was;
+      explicit SplitOnDevice(bool on) : was(zamd::g_split_on_device) { zamd::g_split_on_device = on || was; }
+      ~SplitOnDevice() { zamd::g_split_on_device = was; }
+    } split_on_device(hooks && hooks->split_on_device);
+    sh.rc = RunParts(ctx, options, btype, mine, &sh.chunks, part_chunks ? &sh.part_chunks : nullptr,
+                     hooks ? hooks->group_bytes : 0);
     if (sh.rc) { sh.err = zmx_last_error(); sh.err_class = zmx_last_error_class(); }
     if (TraceCall()) {
       std::fprintf(stderr, "  shard %zu (%zu parts): start +%.2f ms, wait for turn %.2f, upload %.2f, checksum %.2f, parts %.2f, end +%.2f\n",
@@ -645,9 +673,11 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
   for (auto& sh : shards) {
     if (sh.rc) {
       std::fprintf(stderr, "zopfli_amd: device error: %s\n", sh.err.c_str());
+      if (hooks) { hooks->error = sh.err; hooks->error_class = sh.err_class; }
       return sh.rc;
     }
     for (auto& c : sh.chunks) chunks->push_back(std::move(c));
+    if (part_chunks) part_chunks->insert(part_chunks->end(), sh.part_chunks.begin(), sh.part_chunks.end());
   }
   if (TraceCall()) {
     std::fprintf(stderr, "RunPartsSharded: lease %.2f ms, shards done +%.2f, chunks moved +%.2f\n", tr_lease - tr_begin,
@@ -713,6 +743,18 @@ void PushByte(unsigned v, unsigned char** out, size_t* outsize) {
 }
 
 }  // namespace
+
+// dealing.h: what zmx_compress_batch (batch.cc) shares with the calls above
+namespace zamd {
+std::vector<Part> InputMasterBlocks(size_t insize, bool final) { return MasterBlocks(insize, final); }
+int RunPartsDealt(const ZopfliOptions& options, int btype, const unsigned char* in, const std::vector<Part>& parts,
+                  std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks, ShardHooks* hooks) {
+  return RunPartsShardedOnce(options, btype, in, parts, chunks, nullptr, part_chunks, hooks);
+}
+void ResetCallStats() { ResetTiming(); }
+bool TraceCallOn() { return TraceCall(); }
+double CallWallMs() { return WallMs(); }
+}  // namespace zamd
 
 extern "C" {
 

@@ -1,0 +1,45 @@
+// What the batch entry point (batch.cc, zmx_compress_batch) shares with the single-call path of api.cc: the master
+// blocks of an input and the dealing of parts over the context pool — contexts, cost dealing, ordered uploads, stream
+// priorities, the retry of a failed shard on another context.  api.cc itself calls no device function that the batch
+// added: the hooks below are where batch.cc tells a context about its segments and takes its checksums.
+#pragma once
+#include <cstddef>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "deflate.h"
+#include "zopfli_amd.h"
+
+namespace zamd {
+
+// A request whose input is the concatenation of independent inputs (zmx_set_input_segments).
+struct ShardHooks {
+  // the first byte of the input that position `pos` lies in: a shard's upload starts at max(this, start - 32 KiB)
+  std::function<size_t(size_t pos)> floor;
+  // called on the shard's thread once its bytes in[base, ...) are resident on `ctx`, the shard holding parts
+  // [first, last) of the request: tells the context its segments (and takes what else the caller needs of the
+  // resident bytes); non-zero = failure, with zmx_last_error / zmx_last_error_class set
+  std::function<int(size_t shard, zmx_ctx* ctx, size_t base, size_t first, size_t last)> uploaded;
+  // a DeflateParts call takes parts up to this many bytes (halved when the device layer asks for fewer)
+  size_t group_bytes = 0;
+  // the block-split search's rounds on the device (g_split_on_device, deflate.h)
+  bool split_on_device = false;
+  // the failure of the request, when it fails
+  std::string error;
+  int error_class = ZMX_ERR_NONE;
+};
+
+// ZopfliDeflate's master blocks of an input of `insize` bytes (deflate.c:916-923): at least one, even when empty
+std::vector<Part> InputMasterBlocks(size_t insize, bool final);
+// the parts of a request dealt over the pool's contexts (one round: the request's bytes plus a window stay below 2^32);
+// `part_chunks` gets the number of chunks of every part, in part order
+int RunPartsDealt(const ZopfliOptions& options, int btype, const unsigned char* in, const std::vector<Part>& parts,
+                  std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks, ShardHooks* hooks);
+// the per-call timing and statistics of the calling thread start again (zmx_last_timing ...)
+void ResetCallStats();
+// ZOPFLI_AMD_TRACE_CALL=1, and the clock of its lines
+bool TraceCallOn();
+double CallWallMs();
+
+}  // namespace zamd

@@ -36,7 +36,7 @@ bool DeviceSplit(size_t nseq, size_t from_default, size_t symbols, size_t bytes)
   static const long from_env = [] { const char* e = std::getenv("ZOPFLI_AMD_DEVICE_SPLIT_FROM"); return e ? std::atol(e) : -1L; }();
   const size_t from = from_env >= 0 ? static_cast<size_t>(from_env) : from_default;
   if (on == 0 || nseq < from || nseq == 0) return false;
-  return on >= 2 || 20 * symbols >= 9 * bytes;
+  return on >= 2 || g_split_on_device || 20 * symbols >= 9 * bytes;
 }
 size_t DeviceSplitMin() {
   static const size_t v = [] { const char* e = std::getenv("ZOPFLI_AMD_DEVICE_SPLIT_MIN"); return e ? static_cast<size_t>(std::atoll(e)) : static_cast<size_t>(128); }();
@@ -132,7 +132,7 @@ Chunk BitsChunk(BitWriter* w) {
 }  // namespace
 
 int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const std::vector<Part>& parts,
-                 std::vector<Chunk>* chunks) {
+                 std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks) {
   const size_t np = parts.size();
   std::vector<PartState> st(np);
   for (size_t p = 0; p < np; ++p) st[p].part = parts[p];
@@ -146,6 +146,7 @@ int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const st
       c.end = parts[p].inend;
       c.final_block = parts[p].final_part;
       chunks->push_back(std::move(c));
+      if (part_chunks) part_chunks->push_back(1);
     }
     return 0;
   }
@@ -168,6 +169,7 @@ int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const st
     });
     for (size_t p = 0; p < np; ++p) {
       for (auto& c : st[p].chunks) chunks->push_back(std::move(c));
+      if (part_chunks) part_chunks->push_back(st[p].chunks.size());
     }
     return 0;
   }
@@ -600,6 +602,7 @@ int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const st
   const double tp4 = Now();
   for (size_t p = 0; p < np; ++p) {
     for (auto& c : st[p].chunks) chunks->push_back(std::move(c));
+    if (part_chunks) part_chunks->push_back(st[p].chunks.size());
   }
   if (trace_phases) {
     std::fprintf(stderr, "DeflateParts: optimal batch %.1f ms, join/split %.1f ms, fixed batch %.1f ms (%zu requests), "

@@ -48,10 +48,17 @@ struct Part {
   bool final_part;  // last deflate block of this part carries BFINAL
 };
 
+// Set on a thread whose DeflateParts calls take many small parts (the inputs of zmx_compress_batch): the block-split
+// search's rounds then run on the device wherever there are enough sequences, whatever the symbol density — the
+// host's search costs per part, and a thousand 64 KiB parts spend 0.7 s in it against 0.1 s on the device.  Both
+// give the same integers.
+inline thread_local bool g_split_on_device = false;
+
 // Compresses each part independently (one ZopfliDeflatePart each); chunks come
-// out in stream order.  Positions refer to the input resident in `ctx`.
+// out in stream order.  Positions refer to the input resident in `ctx`.  `part_chunks` (optional): the
+// number of chunks of every part is appended, in part order.
 int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const std::vector<Part>& parts,
-                 std::vector<Chunk>* chunks);
+                 std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks = nullptr);
 
 // Appends chunks at (*out, *outsize, *bp), reference conventions (deflate.h:50-53, util.h:135-155);
 // `in` is the base of the resident input (stored chunks that still refer to it).
