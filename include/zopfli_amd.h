@@ -283,6 +283,17 @@ int zmx_png_filter_types(zmx_ctx* ctx, const unsigned char* image, size_t lineby
 int zmx_png_filter_types_pooled(const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
                                 unsigned char* minsum_types, unsigned char* entropy_types);
 
+/* The filter type LodePNG's LFS_BRUTE_FORCE strategy picks for each scanline (lodepng.cpp:5585-5632): every row is
+ * filtered the five ways, each version zlib-compressed alone by LodePNG's fixed-tree deflate (window `windowsize`,
+ * minmatch 3, nicematch 128, lazy matching) and the first smallest in bytes wins.  zopflipng's `b` strategy deflates
+ * with window 32768; LodePNG's default is 2048.  Geometry as zmx_png_filter_types; `types` gets `height` bytes.  A
+ * window that is 0, not a power of two or above 32768 is refused (ZMX_ERR_REFUSED; LodePNG's errors 60 / 90);
+ * height 0 returns 0.  zmx_png_filter_types_brute_pooled is the same on one of the entry points' contexts. */
+int zmx_png_filter_types_brute(zmx_ctx* ctx, const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
+                               unsigned windowsize, unsigned char* types);
+int zmx_png_filter_types_brute_pooled(const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
+                                      unsigned windowsize, unsigned char* types);
+
 /* Parity probe over whole tables: two 64-bit sums over all positions of a hash of the logical content of the match
  * records (block, position, length, distance, same, literal, every change point of sublen).  Equal digests of two
  * table sets over the same blocks = the same ZopfliFindLongestMatch results at every position. */

@@ -34,6 +34,7 @@
 #include "zmx_trace.h"
 #include "zmx_greedy.h"
 #include "zmx_png.h"
+#include "zmx_png_brute.h"
 #include "zmx_blockcost.h"
 #include "zopfli_amd.h"
 #include "../host/thread_pool.h"
@@ -2371,6 +2372,66 @@ int zmx_png_filter_types(zmx_ctx* c, const unsigned char* image, size_t linebyte
   KCHK(c, "k_png_filter_types");
   if (minsum_types) HIPCHK(hipMemcpyAsync(minsum_types, d_types, height, hipMemcpyDeviceToHost, c->stream));
   if (entropy_types) HIPCHK(hipMemcpyAsync(entropy_types, d_types + height, height, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// LodePNG's brute-force row search (zmx_png_brute.h): the filter type LFS_BRUTE_FORCE picks for every scanline when the
+// rows are deflated with a window of `windowsize`.
+int zmx_png_filter_types_brute(zmx_ctx* c, const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
+                               unsigned windowsize, unsigned char* types) {
+  if (!c) return FailMsg("zmx_png_filter_types_brute: no context");
+  if (windowsize == 0 || windowsize > 32768u || (windowsize & (windowsize - 1u)) != 0) {   // LodePNG's errors 60 / 90
+    return FailMsg("zmx_png_filter_types_brute: the window must be a power of two of at most 32768");
+  }
+  if (height == 0) return 0;
+  if (!types) return FailMsg("zmx_png_filter_types_brute: no output");
+  if (linebytes == 0 || bytewidth == 0 || linebytes > 0x7fffffffu || height > 0x7fffffffu / 5u || bytewidth > 8) {
+    return FailMsg("zmx_png_filter_types_brute: bad geometry");
+  }
+  DeviceGuard dev_guard(c->device);
+  HIPCHK(dev_guard.err);
+  const u32 n = static_cast<u32>(linebytes), jobs = static_cast<u32>(5 * height);
+  // the per-position arrays in the dynamic LDS when they fit, else in the scratch beside the head table and the results
+  const u64 row_bytes = pngb_row_bytes(n);
+  const bool in_lds = row_bytes <= PNGB_LDS_MAX;
+  const u64 stride = (PNGB_HEAD_BYTES + 4ull * n + (in_lds ? 0 : row_bytes) + 255u) & ~255ull;
+  // two 1024-lane workgroups fill a CU's 32 waves; the LDS may allow fewer
+  const u64 per_cu = in_lds ? std::max<u64>(1, std::min<u64>(2, (160u * 1024u) / (row_bytes + 12u * 1024u))) : 1;
+  const u64 budget = 1ull << 30;
+  const u32 grid = static_cast<u32>(std::max<u64>(1, std::min<u64>({static_cast<u64>(jobs), 256 * per_cu, budget / stride})));
+  if (in_lds && row_bytes > 64u * 1024u) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_png_brute), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(PNGB_LDS_MAX)));
+  }
+  PoolScope tmp(c);
+  u8* d_img = nullptr;
+  u8* d_scratch = nullptr;
+  u8* d_types = nullptr;
+  u64* d_sizes = nullptr;
+  const size_t bytes = linebytes * height;
+  HIPCHK(tmp.AllocT(&d_img, bytes, "d_png_image"));
+  HIPCHK(tmp.AllocT(&d_scratch, static_cast<size_t>(stride) * grid, "d_png_brute_scratch"));
+  HIPCHK(tmp.AllocT(&d_sizes, static_cast<size_t>(jobs), "d_png_brute_sizes"));
+  HIPCHK(tmp.AllocT(&d_types, height, "d_png_types"));
+  HIPCHK(hipMemcpyAsync(d_img, image, bytes, hipMemcpyHostToDevice, c->stream));
+  PngBruteParams pp;
+  pp.image = d_img;
+  pp.linebytes = n;
+  pp.height = static_cast<u32>(height);
+  pp.bytewidth = static_cast<u32>(bytewidth);
+  pp.window = windowsize;
+  pp.jobs = jobs;
+  pp.scratch = d_scratch;
+  pp.scratch_stride = stride;
+  pp.in_lds = in_lds ? 1u : 0u;
+  pp.sizes = d_sizes;
+  hipLaunchKernelGGL(k_png_brute, dim3(grid), dim3(PNGB_THREADS), in_lds ? static_cast<unsigned>(row_bytes) : 0u, c->stream, pp);
+  KCHK(c, "k_png_brute");
+  hipLaunchKernelGGL(k_png_brute_pick, dim3(static_cast<unsigned>((height + 255) / 256)), dim3(256), 0, c->stream,
+                     static_cast<const u64*>(d_sizes), static_cast<u32>(height), d_types);
+  KCHK(c, "k_png_brute_pick");
+  HIPCHK(hipMemcpyAsync(types, d_types, height, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }

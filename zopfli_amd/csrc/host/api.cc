@@ -754,6 +754,10 @@ int RunPartsDealt(const ZopfliOptions& options, int btype, const unsigned char* 
 void ResetCallStats() { ResetTiming(); }
 bool TraceCallOn() { return TraceCall(); }
 double CallWallMs() { return WallMs(); }
+int OnPooledContext(const std::function<int(zmx_ctx*)>& fn) {
+  Lease lease(1);
+  return fn(lease.ctxs[0]);
+}
 }  // namespace zamd
 
 extern "C" {

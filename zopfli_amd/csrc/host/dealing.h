@@ -1,4 +1,4 @@
-// What the batch entry point (batch.cc, zmx_compress_batch) shares with the single-call path of api.cc: the master
+// What the batch entry point (batch.cc, zmx_compress_batch) and png.cc share with the single-call path of api.cc: the master
 // blocks of an input and the dealing of parts over the context pool — contexts, cost dealing, ordered uploads, stream
 // priorities, the retry of a failed shard on another context.  api.cc itself calls no device function that the batch
 // added: the hooks below are where batch.cc tells a context about its segments and takes its checksums.
@@ -41,5 +41,7 @@ void ResetCallStats();
 // ZOPFLI_AMD_TRACE_CALL=1, and the clock of its lines
 bool TraceCallOn();
 double CallWallMs();
+// `fn` on one of the pool's contexts, held for the call (what the *_pooled entry points outside api.cc use)
+int OnPooledContext(const std::function<int(zmx_ctx*)>& fn);
 
 }  // namespace zamd

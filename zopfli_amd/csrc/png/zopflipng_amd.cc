@@ -13,6 +13,9 @@
 //     chooses), the device returns the filter type of every row for both strategies, and the trial (and the final
 //     encode) hands them to LodePNG as LFS_PREDEFINED — the scanlines it writes are the ones its own search would
 //     have written;
+//   * so does the BRUTE_FORCE strategy's search (lodepng.cpp:5585-5632, zmx_png_filter_types_brute: every row deflated
+//     five ways with LodePNG's fixed-tree deflate on the device), once per image and only when that strategy is
+//     enabled, with window 32768 — the window of the final encode, the only one that runs it (the trials leave it out);
 //   * the final deflate is ZopfliDeflate of libzopfli_amd.so (the LZ77 optimal parse on the MI355X).
 // LodePNG itself (decoder, colour conversion, chunk writer, the trials' deflate) is the third-party library the
 // reference vendors; it is compiled from wherever LODEPNG_DIR points (zopfli_amd/_build.py), not part of this source.
@@ -135,7 +138,8 @@ class Image {
     }
     state.encoder.filter_strategy = lfs;
     if (lfs == LFS_PREDEFINED) state.encoder.predefined_filters = filters.data();
-    const std::vector<unsigned char>* searched = lfs == LFS_MINSUM ? &minsum_ : lfs == LFS_ENTROPY ? &entropy_ : nullptr;
+    const std::vector<unsigned char>* searched = lfs == LFS_MINSUM ? &minsum_ : lfs == LFS_ENTROPY ? &entropy_
+                                               : (lfs == LFS_BRUTE_FORCE && windowsize == brute_window_) ? &brute_ : nullptr;
     if (searched && searched->size() == h) {          // the device's search: the same rows, as predefined types
       state.encoder.filter_strategy = LFS_PREDEFINED;
       state.encoder.predefined_filters = searched->data();
@@ -168,16 +172,19 @@ class Image {
     return error;
   }
 
-  // The filter type of every scanline under MINSUM and under ENTROPY, searched on the device.  The scanlines are
+  // The filter type of every scanline under MINSUM and under ENTROPY (and under BRUTE_FORCE with window 32768 when
+  // `brute`), searched on the device.  The scanlines are
   // LodePNG's: one encode with filter type 0 and stored deflate blocks is the raw (colour-converted, bit-padded) rows
   // behind a zero byte each.  An image LodePNG would lay out differently than assumed here (interlaced; a header that
   // does not match) leaves the vectors empty and the rows to LodePNG's own search — the same rows by definition.  A
   // DEVICE failure is not papered over that way: it is an error of the optimisation (returns false, message on
   // stderr), like a failing ZopfliDeflate.
-  bool SearchFiltersOnDevice() {
+  bool SearchFiltersOnDevice(bool heuristics, bool brute) {
     minsum_.clear();
     entropy_.clear();
+    brute_.clear();
     if (getenv("ZOPFLIPNG_AMD_HOST_FILTERS")) return true;     // (A/B and test hook)
+    if (!heuristics && !brute) return true;
     lodepng::State state;
     Configure(&state, 32768);
     state.encoder.filter_strategy = LFS_ZERO;
@@ -200,13 +207,23 @@ class Image {
     if (lodepng::decompress(rows, idat) != 0 || rows.size() != static_cast<size_t>(h) * (linebytes + 1)) return true;
     std::vector<unsigned char> raw(static_cast<size_t>(h) * linebytes);
     for (size_t y = 0; y < h; ++y) memcpy(raw.data() + y * linebytes, rows.data() + y * (linebytes + 1) + 1, linebytes);
-    std::vector<unsigned char> a(h), b(h);
-    if (zmx_png_filter_types_pooled(raw.data(), linebytes, h, bytewidth, a.data(), b.data()) != 0) {
-      fprintf(stderr, "zopflipng_amd: the row-filter search on the device failed: %s\n", zmx_last_error());
-      return false;
+    if (heuristics) {
+      std::vector<unsigned char> a(h), b(h);
+      if (zmx_png_filter_types_pooled(raw.data(), linebytes, h, bytewidth, a.data(), b.data()) != 0) {
+        fprintf(stderr, "zopflipng_amd: the row-filter search on the device failed: %s\n", zmx_last_error());
+        return false;
+      }
+      minsum_.swap(a);
+      entropy_.swap(b);
     }
-    minsum_.swap(a);
-    entropy_.swap(b);
+    if (brute) {
+      std::vector<unsigned char> t(h);
+      if (zmx_png_filter_types_brute_pooled(raw.data(), linebytes, h, bytewidth, brute_window_, t.data()) != 0) {
+        fprintf(stderr, "zopflipng_amd: the brute-force row search on the device failed: %s\n", zmx_last_error());
+        return false;
+      }
+      brute_.swap(t);
+    }
     return true;
   }
 
@@ -229,6 +246,8 @@ class Image {
     state->encoder.text_compression = 1;
   }
   std::vector<unsigned char> minsum_, entropy_;
+  std::vector<unsigned char> brute_;             // LFS_BRUTE_FORCE's types at brute_window_
+  static const int brute_window_ = 32768;        // the final encode's window (zopflipng_lib.cc:360, :446)
 };
 
 // chunk names of `keep` that the file has, per place (before PLTE, before IDAT, after IDAT): zopflipng_lib.cc:309-352
@@ -290,7 +309,9 @@ int ZopfliPNGOptimize(const std::vector<unsigned char>& origpng, const ZopfliPNG
   if (!error) {
     // which strategies will be encoded at all decides whether the device's row search is wanted
     const bool trials = png_options.auto_filter_strategy;
-    if ((trials || enable[kStrategyMinSum] || enable[kStrategyEntropy]) && !img.SearchFiltersOnDevice()) error = 1;
+    // (brute force: only when asked for by name — the trials leave it out, zopflipng_lib.cc:434)
+    const bool heuristics = trials || enable[kStrategyMinSum] || enable[kStrategyEntropy];
+    if (!img.SearchFiltersOnDevice(heuristics, enable[kStrategyBruteForce])) error = 1;
     if (trials && !error) {
       // zopflipng_lib.cc:270-305: every strategy but brute force with LodePNG's fast deflate (window 8192: the winner
       // depends on the window), the smallest file's strategy wins (the first of equals) — the encodes side by side
