@@ -324,7 +324,10 @@ int zmx_length_array_download(zmx_ctx* ctx, zmx_tables* tables, size_t block, ui
  *                                `tables` for p in [piece_first[s], piece_first[s + 1]) — the greedy store of a master
  *                                block (blocksplitter.c:296), or the optimal parses of its blocks joined
  *                                (deflate.c:866); nothing crosses the bus
- *   zmx_cost_stores_create_host  the same from host arrays (lz77.h:44-49 convention)
+ *   zmx_cost_stores_create_host  the same from host arrays (lz77.h:44-49 convention).  Every pair must be a symbol:
+ *                                dist == 0 with litlen <= 255, or 3 <= litlen <= 258 with 1 <= dist <= 32768 (what the
+ *                                reference asserts); anything else is refused on the host, before any allocation or
+ *                                launch (ZMX_ERR_REFUSED, the message names the sequence and the symbol)
  *   zmx_block_costs              cost[i] = ZopfliCalculateBlockSizeAutoType(sequence ranges[3 i], lstart = ranges[3 i + 1],
  *                                lend = ranges[3 i + 2])
  * A sequence holds fewer than 2^22 symbols (a master block has at most 1 000 000). */

@@ -18,6 +18,7 @@
 #include "checksum.h"
 #include "huffman.h"
 #include "lz77_store.h"
+#include "symbol_check.h"
 extern "C" {
 #include "zopfli_oracle.h"
 }
@@ -39,6 +40,7 @@ struct zmx_tables {
 };
 
 static thread_local std::string g_err;
+static thread_local std::string g_refused;   // the message of the last refusal: the error is one while g_err still holds it
 
 extern "C" {
 
@@ -50,7 +52,7 @@ int zmx_device_count(void) {
 const char* zmx_last_error(void) { return g_err.c_str(); }
 int zmx_has_experiments(void) { return 0; }
 void zmx_set_kernel_timing(int) {}
-int zmx_last_error_class(void) { return g_err.empty() ? ZMX_ERR_NONE : ZMX_ERR_DEVICE; }
+int zmx_last_error_class(void) { return g_err.empty() ? ZMX_ERR_NONE : g_err == g_refused ? ZMX_ERR_REFUSED : ZMX_ERR_DEVICE; }
 void zmx_internal_set_error(const char* msg) { g_err = msg; }
 
 int zmx_ctx_create(int, zmx_ctx** ctx) {
@@ -285,10 +287,13 @@ int zmx_cost_stores_create(zmx_ctx*, zmx_tables* t, size_t nstores, const size_t
   zmx_cost_stores* s = new zmx_cost_stores();
   s->stores.resize(nstores);
   for (size_t q = 0; q < nstores; ++q) {
+    // (a sequence counts its own bytes, as on the device: its pieces may be prefixes of stores, in any order of the input)
+    size_t pos = 0;
     for (size_t p = piece_first[q]; p < piece_first[q + 1]; ++p) {
       const BlockData& d = t->blocks[block[p]];
       if (nsym[p] > d.nsym[slot[p]]) { delete s; g_err = "zmx_cost_stores_create: nsym exceeds the store"; return -1; }
-      s->stores[q].Append(d.litlens[slot[p]].data(), d.dists[slot[p]].data(), nsym[p], d.blk.instart);
+      s->stores[q].Append(d.litlens[slot[p]].data(), d.dists[slot[p]].data(), nsym[p], pos);
+      pos = s->stores[q].ByteRange(0, s->stores[q].size());
     }
   }
   *out = s;
@@ -296,6 +301,15 @@ int zmx_cost_stores_create(zmx_ctx*, zmx_tables* t, size_t nstores, const size_t
 }
 int zmx_cost_stores_create_host(zmx_ctx*, size_t nstores, const uint16_t* const* litlens, const uint16_t* const* dists,
                                 const size_t* nsym, zmx_cost_stores** out) {
+  *out = nullptr;
+  // (the device layer's refusal, by the same rule: symbol_check.h)
+  for (size_t q = 0; q < nstores; ++q) {
+    const size_t bad = zamd::FirstInvalidSymbol(litlens[q], dists[q], nsym[q]);
+    if (bad < nsym[q]) {
+      g_err = g_refused = "zmx_cost_stores_create_host: sequence " + std::to_string(q) + ", symbol " + std::to_string(bad) + " is no LZ77 symbol";
+      return -1;
+    }
+  }
   zmx_cost_stores* s = new zmx_cost_stores();
   s->stores.resize(nstores);
   for (size_t q = 0; q < nstores; ++q) s->stores[q].Append(litlens[q], dists[q], nsym[q], 0);

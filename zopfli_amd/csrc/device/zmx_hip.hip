@@ -37,6 +37,7 @@
 #include "zmx_png_brute.h"
 #include "zmx_blockcost.h"
 #include "zopfli_amd.h"
+#include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
 
 namespace {
@@ -2755,6 +2756,15 @@ int zmx_cost_stores_create_host(zmx_ctx* c, size_t nstores, const uint16_t* cons
                                 const size_t* nsym, zmx_cost_stores** out) {
   *out = nullptr;
   if (nstores == 0) return FailMsg("zmx_cost_stores_create_host: no sequence");
+  // (a symbol is an index into a wave's histogram in LDS: what is no symbol is refused here, before anything is
+  // allocated or launched — symbol_check.h)
+  for (size_t q = 0; q < nstores; ++q) {
+    const size_t bad = zamd::FirstInvalidSymbol(litlens[q], dists[q], nsym[q]);
+    if (bad < nsym[q]) {
+      return FailMsg("zmx_cost_stores_create_host: sequence " + std::to_string(q) + ", symbol " + std::to_string(bad) + ": litlen " +
+                     std::to_string(litlens[q][bad]) + ", dist " + std::to_string(dists[q][bad]) + " is no LZ77 symbol");
+    }
+  }
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   zmx_cost_stores* s = new zmx_cost_stores();
