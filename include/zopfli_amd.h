@@ -151,9 +151,7 @@ int zmx_last_error_class(void);
  * between calls (at most ZOPFLI_AMD_HOST_CACHE_MB, default 1024; zopfli_amd/csrc/host/block_cache.h) instead of changing
  * the host process's malloc settings.  This frees everything cached and returns the number of bytes given back. */
 size_t zmx_host_cache_trim(void);
-/* 1 in a build with -DZMX_EXPERIMENTS: the kernels that lost their measurement (k_bucket + k_match3 / k_match4, the four-wave
- * run task k_dp6_spec) are compiled in and selectable (zmx_set_match_kernel 3 / 4, ZOPFLI_AMD_COOP=1); 0 in the shipped
- * library, which does not contain them. */
+/* always 0; kept for ABI */
 int zmx_has_experiments(void);
 
 int zmx_ctx_create(int device, zmx_ctx** ctx);
@@ -431,8 +429,8 @@ void zmx_set_kernel_timing(int on);
 int zmx_last_host_timing(double* out2);
 
 /* Match-table builds since the last Zopfli* / zmx_deflate_range call started (HIP events):
- * [0] seconds in the match kernel (k_match2; ZOPFLI_AMD_MATCH = 3 / 4: k_match3 / k_match4) [1] seconds in k_same +
- * k_chain (or k_bucket) [2] table builds [3] positions whose record
+ * [0] seconds in the match kernel (k_match2 / k_match5) [1] seconds in k_same +
+ * k_chain [2] table builds [3] positions whose record
  * the match kernel computed (the others were copied from the parent tables). */
 int zmx_last_match_timing(double* out4);
 /* The skip-walk (k_match5) of the table builds since the last Zopfli* call started / zmx_deflate_range: out3 = entries in
@@ -458,8 +456,9 @@ int zmx_ctx_set_priority(zmx_ctx* ctx, int level);
 
 /* Which match-table kernel the table builds that START after this call use (the ZOPFLI_AMD_MATCH environment
  * variable sets the initial choice): 0 = per block, k_match5 where k_hits estimates long chains, k_match2 elsewhere
- * (the default), 2 = k_chain + k_match2, 3 / 4 = k_bucket + k_match3 / k_match4, 5 = k_chain + k_levels + k_rank2 +
- * k_match5 (the exact skip-walk) for every block.  All produce the same records; an A/B and test hook. */
+ * (the default), 2 = k_chain + k_match2, 5 = k_chain + k_levels + k_rank2 + k_match5 (the exact skip-walk) for every
+ * block.  All produce the same records; an A/B and test hook.  3 and 4 named kernels that were removed: the call fails
+ * (as for any other value), and ZOPFLI_AMD_MATCH=3 or 4 falls back to 2. */
 int zmx_set_match_kernel(int kernel);
 
 /* The chain's tasks (GetBestLengths cut into verified stretches, zmx_dp4.h) since the last Zopfli* /

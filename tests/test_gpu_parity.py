@@ -108,14 +108,14 @@ def test_match_digests_at_size(gpu_ctx, cls):
     blocks = [(s, min(s + 1000000, n)) for s in range(0, n, 1000000)]
     dig = {}
     try:
-        kernels = (2, 5, 0) + ((3, 4) if _has_experiments() else ())
-        for kern in kernels:
+        for kern in (2, 5, 0):
             assert gpu_ctx.lib.zmx_set_match_kernel(kern) == 0
             t = gpu_ctx.build_tables(blocks, matches_only=True)
             dig[kern] = t.match_digest()
             t.free()
-        if not _has_experiments():      # the shipped library refuses the kernels it does not contain
-            assert gpu_ctx.lib.zmx_set_match_kernel(3) != 0 and gpu_ctx.lib.zmx_set_match_kernel(4) != 0
+        # the kernels that were removed are refused
+        assert gpu_ctx.lib.zmx_set_match_kernel(3) != 0 and gpu_ctx.lib.zmx_set_match_kernel(4) != 0
+        assert gpu_ctx.lib.zmx_has_experiments() == 0
     finally:
         gpu_ctx.lib.zmx_set_match_kernel(0)
     assert len(set(dig.values())) == 1, dig
@@ -181,13 +181,12 @@ def test_change_point_pool_overflow_and_retry():
 
 
 def test_match_kernels_agree():
-    """The match-table kernels (ZOPFLI_AMD_MATCH: 2 = k_chain + k_match2 on prev links, 3 = k_bucket + k_match3,
-    a wave per position on sorted candidate slices, 4 = k_bucket + k_match4, the slices streamed by a lane per position,
-    5 = k_match5, the exact skip-walk on level links with counted hits, 0 = the default: k_match5 or k_match2 per block)
-    produce the same records — (length, distance, sublen) at every position of every class, blocks with a window in
-    front, tables built from a parent, and a change-point pool that overflows — and the same hash arrays
-    (zmx_hash_links_download reads k_bucket's sorted / rank / bucket arrays back as prev links).  Kernel 2 is the one
-    test_match_table checks against the oracle position by position."""
+    """The match-table kernels (ZOPFLI_AMD_MATCH: 2 = k_chain + k_match2 on prev links, 5 = k_match5, the exact
+    skip-walk on level links with counted hits, 0 = the default: k_match5 or k_match2 per block; 3 and 4, removed
+    kernels, fall back to 2) produce the same records — (length, distance, sublen) at every position of every class,
+    blocks with a window in front, tables built from a parent, and a change-point pool that overflows — and the same
+    hash arrays (zmx_hash_links_download).  Kernel 2 is the one test_match_table checks against the oracle position by
+    position."""
     import subprocess
     import sys
     code = (
@@ -386,19 +385,6 @@ CHAIN_ENVS = [
     ({"ZOPFLI_AMD_SHORTCUT_CHAIN": "0"}, lambda st: st["accepted"] > 0),
     ({"ZOPFLI_AMD_RUN_CODES": "1"}, lambda st: st["accepted"] > 0),                             # codes for wide run rows too (round 5's layout)                        # long-run shortcuts window by window (no chain in a fixed frame)                               # no mid snapshots: a task that leaves its binade is re-run whole
 ]
-
-
-def _has_experiments():
-    """-DZMX_EXPERIMENTS builds (tools/build_variant.py exp -DZMX_EXPERIMENTS, ZOPFLI_AMD_LIB=...) carry the kernels that
-    lost their measurement; the shipped library does not (zmx_has_experiments)."""
-    try:
-        return bool(api.library().zmx_has_experiments())
-    except Exception:
-        return False
-
-
-if _has_experiments():
-    CHAIN_ENVS.append(({"ZOPFLI_AMD_COOP": "1"}, lambda st: st["accepted"] > 0))   # run tasks by four waves each (zmx_dp6.h: exact, 10 % slower)
 
 
 @pytest.mark.parametrize("env,expect", CHAIN_ENVS, ids=lambda v: "-".join(f"{k[15:]}{x}" for k, x in v.items()) if isinstance(v, dict) else "")

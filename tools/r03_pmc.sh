@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes (one rocprofv3 run per line of tools/pmc_sets.txt) over ONE bench step of a class: counters of one kernel,
-# per launch.   CLS=P SIZE=20000000 KERNEL=k_match3 ZOPFLI_AMD_MATCH=3 TAG=pmc_p3 bash tools/r03_pmc.sh
+# per launch.   CLS=P SIZE=20000000 KERNEL=k_match5 ZOPFLI_AMD_MATCH=5 TAG=pmc_p5 bash tools/r03_pmc.sh
 set -u
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/${TAG:-pmc}

@@ -4,7 +4,7 @@ import os
 
 from ._build import LIB
 
-# (a variant build for A/B measurements and the -DZMX_EXPERIMENTS suite: tools/build_variant.py)
+# (a variant build for A/B measurements: tools/build_variant.py)
 if os.environ.get("ZOPFLI_AMD_LIB"):
     LIB = os.environ["ZOPFLI_AMD_LIB"]
 

@@ -596,7 +596,7 @@ __device__ __forceinline__ void d5_run_job(const Dp4Params& P, const D4Job& J, u
               reinterpret_cast<void*>(rb_), (short)0, (int)(2u * ke8[u]), 0x00020000);
           // (each offset ONE register of its own, the instruction's offset field 0 — see the note at lane2 above; the empty asm
           //  keeps the compiler from sharing a register between rows and putting the differences into the offset field, which
-          //  it does in some builds: zmx_dp6.h has the case)
+          //  it does in some builds)
           int vo = (int)(lane2 - 2u * (u32)(8 * h + u + 1));
           int vo2 = vo + 128;
           asm("" : "+v"(vo), "+v"(vo2));
@@ -689,7 +689,7 @@ __device__ __forceinline__ void d5_run_job(const Dp4Params& P, const D4Job& J, u
             st_ok = true;
           }
           // (the region that comes in replaces the one two below it: this wave's reads of that one must have been served
-          //  — zmx_dp6.h has the case that showed it; here the reads were always consumed before, this makes it explicit)
+          //  — here the reads were always consumed before, this makes it explicit)
           if (st_iss < rg0 + 2u) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           while (st_iss < rg0 + 2u) {
             const u16* src_ = rows + 1024u * st_iss + 8u * lane;
@@ -1324,7 +1324,6 @@ __global__ __launch_bounds__(64 * D5_WG, WAVES) void k_dp5_spec(Dp4Params P) {
   if (P.redo_pass && blockIdx.x >= *P.redo_count) return;
   const u32* wg = (P.redo_pass ? P.redo_wg : P.wg_tasks) + (u64)(P.task0 + blockIdx.x) * D5_WG;
   const u32 t0 = wg[0];
-  if (P.redo_pass && P.coop && P.kind[t0] != 0) return;      // a run task: k_dp6_spec's (zmx_dp6.h)
   const u32 b0 = P.tasks[t0].block;
   for (u32 i = threadIdx.x; i < ZMX_WTAB; i += 64 * D5_WG) s_wtab[i] = P.wtab[(u64)b0 * ZMX_WTAB + i];
   if (threadIdx.x == 0) s_rmax = 0;
@@ -1391,12 +1390,6 @@ __global__ __launch_bounds__(64 * D5_WG, WAVES) void k_dp5_spec(Dp4Params P) {
   d5_run_job<PROF, RUNS>(P, J, T.block, bd, s_wtab, reinterpret_cast<float*>(s_buf[wave]), reinterpret_cast<u16*>(s_buf[wave] + 4u * DP_XN),
                    reinterpret_cast<u16*>(s_buf[wave]), s_itab, IT, s_w1, s_sym1, s_ri[wave], s_rk[RUNS ? wave : 0u]);
 }
-
-// the cooperative run-task job (four waves a task): d6_run_job, k_dp6_spec — measured 10 % slower than the one-wave job
-// (round 5), so only in -DZMX_EXPERIMENTS builds
-#ifdef ZMX_EXPERIMENTS
-#include "zmx_dp6.h"
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // FIX: one workgroup per block walks the block's tasks in order, accepts every task whose entry

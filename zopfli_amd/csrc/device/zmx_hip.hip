@@ -17,18 +17,9 @@
 
 #include "zmx_kernels.h"
 #include "zmx_match2.h"
-// The kernels that lost their measurement — k_bucket + k_match3 / k_match4 (sorted candidate slices, round 3) and the
-// four-wave run task k_dp6_spec (round 5) — are NOT in the shipped library: they are compiled in with -DZMX_EXPERIMENTS
-// only (tools/build_variant.py --experiments), for the comparison and stress scripts under tools/.
-#ifdef ZMX_EXPERIMENTS
-#include "zmx_match3.h"
-#include "zmx_match4.h"
-#else
-#define BK_CH 32768u      // (the chunk size the chunk_base bookkeeping below shares with the experiments)
-#endif
 #include "zmx_match5.h"
 #include "zmx_dp4.h"
-#include "zmx_dp5.h"     // (includes zmx_dp6.h: the cooperative run-task job)
+#include "zmx_dp5.h"
 #include "zmx_encode.h"
 #include "zmx_checksum.h"
 #include "zmx_trace.h"
@@ -107,7 +98,6 @@ struct DeviceGuard {
 
 constexpr int kTooLarge = -2;   // zmx_tables_build*: the batch does not fit the code budget, try fewer blocks
 constexpr u32 kMatchGrid = 1024;  // persistent workgroups: 256 CUs x 4 (LDS-limited)
-constexpr u32 kMatchGrid3 = 768;  // k_match3: 256 CUs x 3
 constexpr int kMatchDefault = 0;   // ZOPFLI_AMD_MATCH when unset: per block, k_match5 where k_hits says the chains are long, else k_match2
 constexpr u32 kMatchGrid5 = 1536; // k_match5: 256 CUs x 6 workgroups of 4 waves (its scratch is k_match2's: 1536 x 256 <= 1024 x 512 lanes)
 constexpr size_t kInputPad = 4096;
@@ -187,18 +177,9 @@ struct zmx_tables {
   u16* d_same16 = nullptr;
   ushort4* d_links = nullptr;
   bool links_partial = false;     // built from a parent: the hash arrays exist only where the match kernel read them
-  // k_bucket's order of every 32768-position chunk by (hash value, position), per hash (zmx_match3.h)
-  u16* d_sorted_alloc = nullptr;
-  u16* d_sorted[2] = {nullptr, nullptr};   // (inside d_sorted_alloc)
-  u16* d_rank[2] = {nullptr, nullptr};
-  u32* d_bucket[2] = {nullptr, nullptr};
-  u8* d_ssame = nullptr;
-  u32* d_chunk_base = nullptr;
-  std::vector<u32> chunk_base;    // [nb + 1] first chunk of each block
   size_t merged_tasks = 0;        // tasks merged into their predecessors (BuildTables): the set has long tasks
   bool matches_only = false;      // built by zmx_tables_build_matches: no DP rows, codes, windows or tasks
   bool trimmed = false;           // zmx_tables_trim: only the stores are left
-  bool buckets = false;           // the hash arrays are k_bucket's (k_match3), not k_chain's links (k_match2)
   u32* d_recs = nullptr;
   u32* d_pool = nullptr;
   u32 pool_cap = 0;
@@ -224,7 +205,7 @@ struct zmx_tables {
   std::vector<u32> seg_off;
   std::vector<u64> block_edges;
   std::vector<u32> tile_off;
-  u32* d_counters = nullptr;  // 48 words, see MatchParams (16 .. 21: k_match3's profile counts; 24 .. 31: k_match5's tile cursors, 32 .. 39: its watchdog's dump)
+  u32* d_counters = nullptr;  // 48 words, see MatchParams (24 .. 31: k_match5's tile cursors, 32 .. 39: its watchdog's dump)
   u32* d_flags = nullptr;     // 4 words
   // what a squeeze run takes and gives, each side ONE array on the device and one pinned mirror on the host, so
   // that a run has one copy down and one up (eight small copies a run were 3 ms of copy kernels per 15 runs):
@@ -244,9 +225,6 @@ struct zmx_tables {
   u32* d_wg_tasks = nullptr;       // k_dp5_spec's workgroups: four tasks of one block each
   u32 n_wg = 0;
   u32 n_wg_runs = 0;               // ... of which the last n_wg_runs hold run tasks (k_taskkind): k_dp5_spec<.., true>
-  u32* d_task_kind = nullptr;      // [tasks] k_taskkind: 1 = a run task
-  u32* d_run_list = nullptr;       // the run tasks, longest first: k_dp6_spec's workgroups (zmx_dp6.h)
-  u32 n_run_list = 0;
   u32* d_wmeta = nullptr;          // per 32-position window: 40 words, what k_dp5_spec needs to fetch its rows (k_mkdesc)
   u32* d_winroff = nullptr;        // per 32-position window: offset of its first row in the block's codes (k_mkdesc)
   u32* d_winflag = nullptr;        // per 32-position window: fast path possible (k_mkdesc)
@@ -365,8 +343,6 @@ bool MatchFilter() {
 //       ZOPFLI_AMD_MATCH_HITS (300) take the exact skip-walk k_match5 (level links + counted hits, zmx_match5.h: 5 - 9 x
 //       faster on PNG-like and two-symbol data, profiles/r04_match.txt), the others k_match2, side by side on two streams
 //   2 = k_chain + k_match2 everywhere (prev links, a lane per position)
-//   3 = k_bucket + k_match3 (sorted candidate slices, a wave per position, 64 candidates per coalesced load)
-//   4 = k_bucket + k_match4 (the same slices streamed by a lane per position, four candidates per step)
 //   5 = k_match5 everywhere
 // All produce the same records (test_match_kernels_agree).  Tables built from a parent recompute their few tiles with
 // k_match2 either way.
@@ -376,11 +352,7 @@ int MatchKernel() {
   if (v < 0) {
     const char* e = std::getenv("ZOPFLI_AMD_MATCH");
     const int k = e ? std::atoi(e) : kMatchDefault;
-#ifdef ZMX_EXPERIMENTS
-    v = k == 0 || k == 3 || k == 4 || k == 5 ? k : 2;
-#else
-    v = k == 0 || k == 5 ? k : 2;      // (3 and 4 exist in -DZMX_EXPERIMENTS builds only)
-#endif
+    v = k == 0 || k == 5 ? k : 2;      // (3 and 4 were removed: they fall back to 2)
     g_match_kernel.store(v, std::memory_order_relaxed);
   }
   return v;
@@ -512,13 +484,7 @@ static bool KernelTiming() {
 }
 void zmx_set_kernel_timing(int on) { g_kernel_timing.store(on ? 1 : 0, std::memory_order_relaxed); }
 
-int zmx_has_experiments(void) {
-#ifdef ZMX_EXPERIMENTS
-  return 1;
-#else
-  return 0;
-#endif
-}
+int zmx_has_experiments(void) { return 0; }   // (always 0; kept for ABI)
 
 void zmx_set_oom_hook(zmx_oom_hook_t hook) { g_oom_hook.store(hook, std::memory_order_release); }
 
@@ -544,12 +510,8 @@ int zmx_ctx_trim_cache(zmx_ctx* c) {
 }
 
 int zmx_set_match_kernel(int kernel) {
-#ifdef ZMX_EXPERIMENTS
-  if (kernel != 0 && kernel != 2 && kernel != 3 && kernel != 4 && kernel != 5) return FailMsg("zmx_set_match_kernel: 0, 2, 3, 4 or 5");
-#else
-  if (kernel == 3 || kernel == 4) return FailMsg("zmx_set_match_kernel: kernels 3 and 4 are in -DZMX_EXPERIMENTS builds only");
+  if (kernel == 3 || kernel == 4) return FailMsg("zmx_set_match_kernel: kernels 3 and 4 were removed");
   if (kernel != 0 && kernel != 2 && kernel != 5) return FailMsg("zmx_set_match_kernel: 0, 2 or 5");
-#endif
   g_match_kernel.store(kernel, std::memory_order_relaxed);
   return 0;
 }
@@ -650,10 +612,6 @@ int zmx_ctx_create(int device, zmx_ctx** out) {
 
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain), hipFuncAttributeMaxDynamicSharedMemorySize,
                              CH_LDS_BYTES));
-#ifdef ZMX_EXPERIMENTS
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bucket), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             BK_LDS_BYTES));
-#endif
   *out = c;
   return 0;
 }
@@ -747,9 +705,6 @@ static void ReleaseTableArrays(zmx_ctx* c, zmx_tables* t, bool keep_stores) {
   rel(t->d_tile_off);
   rel(t->d_same16);
   rel(t->d_links);
-  rel(t->d_sorted_alloc);
-  rel(t->d_ssame);
-  rel(t->d_chunk_base);
   rel(t->d_recs);
   rel(t->d_pool);
   rel(t->d_la);
@@ -768,8 +723,6 @@ static void ReleaseTableArrays(zmx_ctx* c, zmx_tables* t, bool keep_stores) {
   rel(t->d_tasks);
   rel(t->d_task_off);
   rel(t->d_wg_tasks);
-  rel(t->d_task_kind);
-  rel(t->d_run_list);
   rel(t->d_wmeta);
   rel(t->d_runin);
   rel(t->d_runout);
@@ -783,8 +736,6 @@ static void ReleaseTableArrays(zmx_ctx* c, zmx_tables* t, bool keep_stores) {
   rel(t->d_chk);
   rel(t->d_over);
   rel(t->d_redo);
-  for (int h = 0; h < 2; ++h) { rel(t->d_rank[h]); rel(t->d_bucket[h]); }
-  t->d_sorted[0] = t->d_sorted[1] = nullptr;
   PinnedGive(c, &t->h_runin, t->h_runin_cap);
   PinnedGive(c, &t->h_runout, t->h_runout_cap);
   if (!keep_stores) { rel(t->d_store[0]); rel(t->d_store[1]); }
@@ -861,9 +812,14 @@ static unsigned SegHead(size_t nb) {
 }
 static unsigned SegWarm() { static const unsigned v = (EnvU32("ZOPFLI_AMD_SEG_WARM", 512, 64, 1u << 20) + 63u) & ~63u; return v; }
 
-static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_tables* t, zmx_tables* parent = nullptr, bool with_dp = true) {
-  const int mk = MatchKernel();   // (one choice per build: zmx_set_match_kernel may be called meanwhile)
-  t->matches_only = !with_dp;
+// ---------------------------------------------------------------------------------------------
+// BuildTables, phase by phase.  Every phase works on `c->stream` and returns 0, or what BuildTables returns for the
+// failure (-1 with the error set: HIPCHK).
+// ---------------------------------------------------------------------------------------------
+
+// Phase 1: where each block's window, positions and length-array entries lie, and the totals (t->total_b positions,
+// t->total_l window entries, t->tile_off); *la_total = length-array entries, *max_window = the longest window.
+static int LayoutBlocks(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_tables* t, u64* la_total, u64* max_window) {
   t->nb = nb;
   t->blocks.resize(nb);
   t->bsize.resize(nb);
@@ -902,17 +858,28 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
   t->total_b = pos_off;
   t->total_l = reg_off;
   t->tile_off = tile_off;
-  if (nb == 0) return 0;
+  *la_total = la_off;
+  *max_window = max_l;
+  return 0;
+}
 
-  // ---- reuse of the parent's records
-  std::vector<u64> src_pos;
+// Phase 2 (host only): what a table set over sub-blocks of `parent`'s blocks takes from the parent.
+struct ReusePlan {
+  bool reuse = false;
+  std::vector<u64> src_pos;       // per block: its first record in the parent's d_recs
   std::vector<u64> link_lo;       // per block: first links[] index the recomputed tiles read (its L: none)
-  std::vector<u32> tile_list;
+  std::vector<u32> tile_list;     // the tiles whose records are computed again
+};
+static ReusePlan PlanReuse(const zmx_ctx* c, const zmx_tables* t, const zmx_tables* parent) {
+  const size_t nb = t->nb;
+  const u64 pos_off = t->total_b;
+  const std::vector<u32>& tile_off = t->tile_off;
+  ReusePlan plan;
   bool reuse = parent != nullptr && parent->nb > 0 && c->h_in != nullptr && parent->d_recs != nullptr &&
                parent->total_b + pos_off < (3ull << 30);
   if (reuse) {
-    src_pos.resize(nb);
-    link_lo.resize(nb);
+    plan.src_pos.resize(nb);
+    plan.link_lo.resize(nb);
     size_t pb = 0;
     for (size_t b = 0; b < nb && reuse; ++b) {
       const BlockDesc& d = t->blocks[b];
@@ -922,9 +889,9 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
         break;
       }
       const BlockDesc& pd = parent->blocks[pb];
-      src_pos[b] = pd.pos_off + (d.instart - pd.instart);
+      plan.src_pos[b] = pd.pos_off + (d.instart - pd.instart);
       const u64 B = d.inend - d.instart;
-      link_lo[b] = d.inend - d.ws;
+      plan.link_lo[b] = d.inend - d.ws;
       if (B == 0 || d.inend == pd.inend) continue;   // same end: every record is the same
       // first position whose record may differ
       u64 t0 = B > ZMX_MAX_MATCH ? d.inend - ZMX_MAX_MATCH : d.instart;
@@ -934,46 +901,27 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
       if (r < t0) t0 = r;
       const u32 tile_first = static_cast<u32>((t0 - d.instart) / MT);
       for (u32 tile = tile_first; tile < tile_off[b + 1] - tile_off[b]; ++tile) {
-        tile_list.push_back(tile_off[b] + tile);
+        plan.tile_list.push_back(tile_off[b] + tile);
       }
       // the walks of those tiles stay inside the 32 KiB before them (lz77.c:464)
       const u64 first_index = d.instart + static_cast<u64>(tile_first) * MT - d.ws;
-      link_lo[b] = first_index > ZMX_WINDOW ? first_index - ZMX_WINDOW : 0;
+      plan.link_lo[b] = first_index > ZMX_WINDOW ? first_index - ZMX_WINDOW : 0;
     }
   }
+  plan.reuse = reuse;
+  return plan;
+}
 
+// Phase 3: the table set's arrays and the mirrors of a squeeze run's input and output.
+static int AllocTableArrays(zmx_ctx* c, zmx_tables* t, u64 la_off) {
+  const size_t nb = t->nb;
+  const u64 pos_off = t->total_b;
+  const u64 reg_off = t->total_l;
+  const std::vector<u32>& tile_off = t->tile_off;
   HIPCHK(PoolAlloc(c, &t->d_blocks, nb));
   HIPCHK(PoolAlloc(c, &t->d_tile_off, nb + 1));
   HIPCHK(PoolAlloc(c, &t->d_same16, reg_off));
-#ifdef ZMX_EXPERIMENTS
-  t->buckets = mk == 3 || mk == 4;
-#else
-  t->buckets = false;
-#endif
-  t->chunk_base.assign(nb + 1, 0);
-  for (size_t b = 0; b < nb; ++b) {
-    const u64 L = t->blocks[b].inend - t->blocks[b].ws;
-    t->chunk_base[b + 1] = t->chunk_base[b] + static_cast<u32>((L + BK_CH - 1) / BK_CH);
-  }
-#ifdef ZMX_EXPERIMENTS
-  if (t->buckets) {
-    // (the two orders in one allocation, M4_PAD entries in front: k_match4 reads 16 bytes at a time, from up to 15 entries
-    //  below a chunk's first one, and takes the second order as an offset from the first)
-    HIPCHK(PoolAlloc(c, &t->d_sorted_alloc, 2 * reg_off + 2 * M4_PAD));
-    t->d_sorted[0] = t->d_sorted_alloc + M4_PAD;
-    t->d_sorted[1] = t->d_sorted[0] + reg_off + M4_PAD;
-    for (int h = 0; h < 2; ++h) {
-      HIPCHK(PoolAlloc(c, &t->d_rank[h], reg_off));
-      HIPCHK(PoolAlloc(c, &t->d_bucket[h], static_cast<size_t>(t->chunk_base[nb]) * 32768u));
-    }
-    HIPCHK(PoolAlloc(c, &t->d_ssame, reg_off));
-    HIPCHK(PoolAlloc(c, &t->d_chunk_base, nb + 1));
-    HIPCHK(hipMemcpyAsync(t->d_chunk_base, t->chunk_base.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-  } else
-#endif
-  {
-    HIPCHK(PoolAlloc(c, &t->d_links, reg_off));
-  }
+  HIPCHK(PoolAlloc(c, &t->d_links, reg_off));
   HIPCHK(PoolAlloc(c, &t->d_recs, pos_off * 8));
   HIPCHK(PoolAlloc(c, &t->d_la, la_off));
   HIPCHK(PoolAlloc(c, &t->d_store[0], pos_off));
@@ -1010,9 +958,12 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
   HIPCHK(hipMemcpyAsync(t->d_blocks, t->blocks.data(), nb * sizeof(BlockDesc), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(t->d_tile_off, tile_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(t->d_flags, 0, 4 * sizeof(u32), c->stream));
+  return 0;
+}
 
-  HIPCHK(hipEventRecord(c->ev[0], c->stream));
-  PoolScope hash_tmp(c);
+// What the hash-link phase leaves for the match phase (temporaries of one build: back to the pool when it ends).
+struct MatchBuild {
+  PoolScope hash_tmp;
   u16* d_lev = nullptr;    // k_levels / k_rank2 (ZOPFLI_AMD_MATCH=5), alive until the match kernel has run
   u16* d_tot2 = nullptr;
   u16* d_rank2 = nullptr;
@@ -1024,223 +975,191 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
   double skip_positions = 0;                // positions of those blocks
   unsigned long long* d_m5stats = nullptr;  // k_match5's per-wave sums
   bool join_stream2 = false;
-  auto launch_hash = [&](const u64* d_link_lo) -> int {
-    if (max_l == 0) return 0;
-    const dim3 g1(static_cast<unsigned>((max_l + 256 * SAME_CH - 1) / (256 * SAME_CH)), static_cast<unsigned>(nb));
-    hipLaunchKernelGGL(k_same, g1, dim3(256), 0, c->stream, c->d_in, t->d_blocks, t->d_same16, d_link_lo);
-    KCHK(c, "k_same");
-    HIPCHK(hipGetLastError());
-    const dim3 g2(static_cast<unsigned>((max_l + CH_EMIT - 1) / CH_EMIT), static_cast<unsigned>(nb), 2);
-#ifdef ZMX_EXPERIMENTS
-    if (t->buckets) {
-      BucketParams kp;
-      kp.in = c->d_in;
-      kp.blocks = t->d_blocks;
-      kp.same16 = t->d_same16;
-      kp.chunk_base = t->d_chunk_base;
-      kp.link_lo = d_link_lo;
-      for (int h = 0; h < 2; ++h) { kp.sorted[h] = t->d_sorted[h]; kp.rank[h] = t->d_rank[h]; kp.bucket[h] = t->d_bucket[h]; }
-      kp.ssame = t->d_ssame;
-      hipLaunchKernelGGL(k_bucket, g2, dim3(BK_THREADS), BK_LDS_BYTES, c->stream, kp);
-      KCHK(c, "k_bucket");
-    } else
-#endif
+  explicit MatchBuild(zmx_ctx* c) : hash_tmp(c) {}
+};
+
+// Phase 4: hash links (k_same, k_chain) and, for the blocks that take it, what the skip-walk k_match5 reads.
+// d_link_lo = null: whole blocks.
+static int LaunchHash(zmx_ctx* c, zmx_tables* t, int mk, u64 max_l, const u64* d_link_lo, MatchBuild& m) {
+  const size_t nb = t->nb;
+  const u64 reg_off = t->total_l;
+  if (max_l == 0) return 0;
+  const dim3 g1(static_cast<unsigned>((max_l + 256 * SAME_CH - 1) / (256 * SAME_CH)), static_cast<unsigned>(nb));
+  hipLaunchKernelGGL(k_same, g1, dim3(256), 0, c->stream, c->d_in, t->d_blocks, t->d_same16, d_link_lo);
+  KCHK(c, "k_same");
+  HIPCHK(hipGetLastError());
+  const dim3 g2(static_cast<unsigned>((max_l + CH_EMIT - 1) / CH_EMIT), static_cast<unsigned>(nb), 2);
+  hipLaunchKernelGGL(k_chain, g2, dim3(64), CH_LDS_BYTES, c->stream, c->d_in, t->d_blocks, t->d_same16, t->d_links, d_link_lo);
+  KCHK(c, "k_chain");
+  if ((mk == 5 || mk == 0) && d_link_lo == nullptr) {
+    // The skip-walk (k_match5) for the blocks whose chains are long: k_hits estimates the hits per position the
+    // reference's walk would make, block by block; kernel 5 forces it for every block.  (Whole blocks only: a
+    // table built from a parent recomputes a few tiles with k_match2.)
+    m.skip_any = mk == 5;
+    if (mk == 5) for (size_t b = 0; b < nb; ++b) m.skip_positions += static_cast<double>(t->blocks[b].inend - t->blocks[b].instart);
+    const unsigned hits_chunks = static_cast<unsigned>((max_l + RK_CH - 1) / RK_CH);
     {
-      hipLaunchKernelGGL(k_chain, g2, dim3(64), CH_LDS_BYTES, c->stream, c->d_in, t->d_blocks, t->d_same16, t->d_links, d_link_lo);
-      KCHK(c, "k_chain");
-      if ((mk == 5 || mk == 0) && d_link_lo == nullptr) {
-        // The skip-walk (k_match5) for the blocks whose chains are long: k_hits estimates the hits per position the
-        // reference's walk would make, block by block; kernel 5 forces it for every block.  (Whole blocks only: a
-        // table built from a parent recomputes a few tiles with k_match2.)
-        skip_any = mk == 5;
-        if (mk == 5) for (size_t b = 0; b < nb; ++b) skip_positions += static_cast<double>(t->blocks[b].inend - t->blocks[b].instart);
-        const unsigned hits_chunks = static_cast<unsigned>((max_l + RK_CH - 1) / RK_CH);
-        {
-          // k_hits: the blocks' hit estimates (kernel 0: which walk a block gets) and the chunks' largest classes (k_rank2:
-          // where the 8192-hit cap can bind; ZOPFLI_AMD_RANK_ALL=1: ranks everywhere, as in round 4)
-          static const bool rank_all = [] { const char* e = std::getenv("ZOPFLI_AMD_RANK_ALL"); return e && std::atoi(e) != 0; }();
-          if (!d_energy) HIPCHK(hash_tmp.AllocT(&d_energy, nb, "d_energy"));
-          if (!d_cmax && !rank_all) HIPCHK(hash_tmp.AllocT(&d_cmax, nb * static_cast<size_t>(hits_chunks) + 1, "d_cmax"));
-          HIPCHK(hipMemsetAsync(d_energy, 0, nb * sizeof(unsigned long long), c->stream));
-          if (d_cmax) HIPCHK(hipMemsetAsync(d_cmax, 0, (nb * static_cast<size_t>(hits_chunks) + 1) * sizeof(u32), c->stream));
-          HitsParams hp;
-          hp.in = c->d_in;
-          hp.blocks = t->d_blocks;
-          hp.same16 = t->d_same16;
-          hp.energy = d_energy;
-          hp.cmax = d_cmax;
-          const dim3 g5(hits_chunks, static_cast<unsigned>(nb));
-          hipLaunchKernelGGL(k_hits, g5, dim3(RK_THREADS), 0, c->stream, hp);
-          KCHK(c, "k_hits");
-        }
-        if (mk == 0) {
-          std::vector<unsigned long long> energy(nb);
-          HIPCHK(hipMemcpyAsync(energy.data(), d_energy, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-          HIPCHK(hipStreamSynchronize(c->stream));
-          size_t on = 0;
-          for (size_t b = 0; b < nb; ++b) {
-            if (energy[b] > MatchAutoHits() * (t->blocks[b].inend - t->blocks[b].ws)) {
-              ++on;
-              skip_positions += static_cast<double>(t->blocks[b].inend - t->blocks[b].instart);
-            }
-          }
-          skip_any = on != 0;
-          skip_all = on == nb;
-        }
-        if (skip_any) {
-          if (!d_lev) HIPCHK(hash_tmp.AllocT(&d_lev, static_cast<size_t>(LV_N) * reg_off, "d_lev"));
-          if (!d_tot2) HIPCHK(hash_tmp.AllocT(&d_tot2, 2 * reg_off, "d_tot"));
-          if (!d_rank2) HIPCHK(hash_tmp.AllocT(&d_rank2, 2 * reg_off, "d_rank"));
-          if (!d_tot12) HIPCHK(hash_tmp.AllocT(&d_tot12, reg_off, "d_tot12"));
-          if (!d_xrec) HIPCHK(hash_tmp.AllocT(&d_xrec, 2 * reg_off, "d_xrec"));
-          LevelParams lp;
-          lp.in = c->d_in;
-          lp.blocks = t->d_blocks;
-          lp.lev = d_lev;
-          lp.total_l = reg_off;
-          lp.energy = mk == 0 ? d_energy : nullptr;
-          lp.thr = MatchAutoHits();
-          const dim3 g4(static_cast<unsigned>((max_l + LV_CH - 1) / LV_CH), static_cast<unsigned>(nb), LV_N);
-          hipLaunchKernelGGL(k_levels, g4, dim3(64), 0, c->stream, lp);
-          KCHK(c, "k_levels");
-          RankParams rp;
-          rp.in = c->d_in;
-          rp.blocks = t->d_blocks;
-          rp.links = t->d_links;
-          rp.same16 = t->d_same16;
-          rp.lev = d_lev;
-          rp.total_l = reg_off;
-          rp.tot = d_tot2;
-          rp.rank = d_rank2;
-          rp.xrec = d_xrec;
-          rp.tot12 = d_tot12;
-          rp.energy = lp.energy;
-          rp.thr = lp.thr;
-          rp.cmax = d_cmax;
-          rp.cmax_stride = hits_chunks;
-          const dim3 g3(static_cast<unsigned>((max_l + RK_CH - 1) / RK_CH), static_cast<unsigned>(nb));
-          hipLaunchKernelGGL(k_rank2, g3, dim3(RK_THREADS), 0, c->stream, rp);
-          KCHK(c, "k_rank2");
+      // k_hits: the blocks' hit estimates (kernel 0: which walk a block gets) and the chunks' largest classes (k_rank2:
+      // where the 8192-hit cap can bind)
+      if (!m.d_energy) HIPCHK(m.hash_tmp.AllocT(&m.d_energy, nb, "d_energy"));
+      if (!m.d_cmax) HIPCHK(m.hash_tmp.AllocT(&m.d_cmax, nb * static_cast<size_t>(hits_chunks) + 1, "d_cmax"));
+      HIPCHK(hipMemsetAsync(m.d_energy, 0, nb * sizeof(unsigned long long), c->stream));
+      HIPCHK(hipMemsetAsync(m.d_cmax, 0, (nb * static_cast<size_t>(hits_chunks) + 1) * sizeof(u32), c->stream));
+      HitsParams hp;
+      hp.in = c->d_in;
+      hp.blocks = t->d_blocks;
+      hp.same16 = t->d_same16;
+      hp.energy = m.d_energy;
+      hp.cmax = m.d_cmax;
+      const dim3 g5(hits_chunks, static_cast<unsigned>(nb));
+      hipLaunchKernelGGL(k_hits, g5, dim3(RK_THREADS), 0, c->stream, hp);
+      KCHK(c, "k_hits");
+    }
+    if (mk == 0) {
+      std::vector<unsigned long long> energy(nb);
+      HIPCHK(hipMemcpyAsync(energy.data(), m.d_energy, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      size_t on = 0;
+      for (size_t b = 0; b < nb; ++b) {
+        if (energy[b] > MatchAutoHits() * (t->blocks[b].inend - t->blocks[b].ws)) {
+          ++on;
+          m.skip_positions += static_cast<double>(t->blocks[b].inend - t->blocks[b].instart);
         }
       }
+      m.skip_any = on != 0;
+      m.skip_all = on == nb;
     }
-    return 0;
-  };
-  {
-    u64* d_link_lo = nullptr;
-    if (reuse) {
-      HIPCHK(hash_tmp.AllocT(&d_link_lo, nb, "d_link_lo"));
-      HIPCHK(hipMemcpyAsync(d_link_lo, link_lo.data(), nb * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    if (m.skip_any) {
+      if (!m.d_lev) HIPCHK(m.hash_tmp.AllocT(&m.d_lev, static_cast<size_t>(LV_N) * reg_off, "d_lev"));
+      if (!m.d_tot2) HIPCHK(m.hash_tmp.AllocT(&m.d_tot2, 2 * reg_off, "d_tot"));
+      if (!m.d_rank2) HIPCHK(m.hash_tmp.AllocT(&m.d_rank2, 2 * reg_off, "d_rank"));
+      if (!m.d_tot12) HIPCHK(m.hash_tmp.AllocT(&m.d_tot12, reg_off, "d_tot12"));
+      if (!m.d_xrec) HIPCHK(m.hash_tmp.AllocT(&m.d_xrec, 2 * reg_off, "d_xrec"));
+      LevelParams lp;
+      lp.in = c->d_in;
+      lp.blocks = t->d_blocks;
+      lp.lev = m.d_lev;
+      lp.total_l = reg_off;
+      lp.energy = mk == 0 ? m.d_energy : nullptr;
+      lp.thr = MatchAutoHits();
+      const dim3 g4(static_cast<unsigned>((max_l + LV_CH - 1) / LV_CH), static_cast<unsigned>(nb), LV_N);
+      hipLaunchKernelGGL(k_levels, g4, dim3(64), 0, c->stream, lp);
+      KCHK(c, "k_levels");
+      RankParams rp;
+      rp.in = c->d_in;
+      rp.blocks = t->d_blocks;
+      rp.links = t->d_links;
+      rp.same16 = t->d_same16;
+      rp.lev = m.d_lev;
+      rp.total_l = reg_off;
+      rp.tot = m.d_tot2;
+      rp.rank = m.d_rank2;
+      rp.xrec = m.d_xrec;
+      rp.tot12 = m.d_tot12;
+      rp.energy = lp.energy;
+      rp.thr = lp.thr;
+      rp.cmax = m.d_cmax;
+      rp.cmax_stride = hits_chunks;
+      const dim3 g3(static_cast<unsigned>((max_l + RK_CH - 1) / RK_CH), static_cast<unsigned>(nb));
+      hipLaunchKernelGGL(k_rank2, g3, dim3(RK_THREADS), 0, c->stream, rp);
+      KCHK(c, "k_rank2");
     }
-    if (launch_hash(d_link_lo) != 0) return -1;
-    t->links_partial = reuse;
   }
+  return 0;
+}
+static int BuildHashLinks(zmx_ctx* c, zmx_tables* t, int mk, u64 max_l, const ReusePlan& plan, MatchBuild& m) {
+  const size_t nb = t->nb;
+  HIPCHK(hipEventRecord(c->ev[0], c->stream));
+  u64* d_link_lo = nullptr;
+  if (plan.reuse) {
+    HIPCHK(m.hash_tmp.AllocT(&d_link_lo, nb, "d_link_lo"));
+    HIPCHK(hipMemcpyAsync(d_link_lo, plan.link_lo.data(), nb * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  }
+  if (LaunchHash(c, t, mk, max_l, d_link_lo, m) != 0) return -1;
+  t->links_partial = plan.reuse;
+  return 0;
+}
 
-  if (mk != 3 && !c->d_scratch) HIPCHK(PoolAllocT(c, &c->d_scratch, static_cast<size_t>(kMatchGrid) * M2_THREADS * SCRATCH_CPS, "d_scratch"));
+// Phase 5's match-table kernel over `total_tiles` tiles (all of them, or those of tile_list)
+static int LaunchMatch(zmx_ctx* c, zmx_tables* t, int mk, MatchBuild& m, u32* pool, u32 pool_cap, u32 total_tiles, const u32* d_tiles, bool prof) {
+  const size_t nb = t->nb;
+  if (total_tiles == 0) return 0;
+  MatchParams mp;
+  mp.in = c->d_in;
+  mp.blocks = t->d_blocks;
+  mp.tile_off = t->d_tile_off;
+  mp.nb = static_cast<u32>(nb);
+  mp.total_tiles = total_tiles;
+  mp.links = t->d_links;
+  mp.recs = t->d_recs;
+  mp.pool = pool;
+  mp.pool_cap = pool_cap;
+  mp.counters = t->d_counters;
+  mp.scratch = c->d_scratch;
+  mp.tile_list = d_tiles;
+  mp.skip_energy = nullptr;
+  mp.skip_thr = 0;
+  if ((mk == 5 || mk == 0) && d_tiles == nullptr && m.skip_any) {
+    if (!c->d_scratch5) HIPCHK(PoolAllocT(c, &c->d_scratch5, static_cast<size_t>(kMatchGrid5) * M5_THREADS * SCRATCH_CPS, "d_scratch5"));
+    Match5Params q;
+    q.m = mp;
+    q.m.scratch = c->d_scratch5;
+    q.xrec = m.d_xrec;
+    q.tot12 = m.d_tot12;
+    q.energy = mk == 0 ? m.d_energy : nullptr;
+    q.thr = MatchAutoHits();
+    const size_t m5_waves = static_cast<size_t>(kMatchGrid5) * (M5_THREADS / 64);
+    if (!m.d_m5stats) HIPCHK(m.hash_tmp.AllocT(&m.d_m5stats, 2 * m5_waves, "d_m5stats"));
+    HIPCHK(hipMemsetAsync(m.d_m5stats, 0, 2 * m5_waves * sizeof(unsigned long long), c->stream));
+    q.wave_stats = m.d_m5stats;
+    {
+      // positions a wave takes at a time: larger pieces keep the lanes busier (fewer ends of a piece, where lanes
+      // wait for the piece's longest walks), smaller ones the waves when there are few tiles.  100 MB, pieces of 512 /
+      // 1024 / 2048 positions: T 22.4 / 20.0 / 20.4 ms, P 30.1 / 27.9 / 29.5, B 97.1 / 93.1 / 100.0
+      const u64 waves = static_cast<u64>(kMatchGrid5) * (M5_THREADS / 64);
+      q.sub_shift = mp.total_tiles >= 4 * waves ? 1u : 2u;
+    }
+    if (mk == 5 || m.skip_all) {
+      hipLaunchKernelGGL(k_match5, dim3(kMatchGrid5), dim3(M5_THREADS), 0, c->stream, q);   // (no profile counts: tools/match_skip_model.c has the entries touched)
+      KCHK(c, "k_match5");
+      return 0;
+    }
+    // Some blocks each: k_match5 on the second stream beside k_match2 (which passes over k_match5's blocks) — the
+    // skip-walk of a few heavy blocks is a handful of long-running waves, the rest of the device is k_match2's.
+    HIPCHK(hipEventRecord(c->ev2[0], c->stream));
+    HIPCHK(hipStreamWaitEvent(c->stream2, c->ev2[0], 0));
+    hipLaunchKernelGGL(k_match5, dim3(kMatchGrid5), dim3(M5_THREADS), 0, c->stream2, q);
+    HIPCHK(hipGetLastError());
+    c->stream2_outstanding = true;
+    HIPCHK(hipEventRecord(c->ev2[1], c->stream2));
+    m.join_stream2 = true;
+    mp.skip_energy = m.d_energy;
+    mp.skip_thr = MatchAutoHits();
+  }
+  const bool filt = MatchFilter();
+  if (prof && filt) hipLaunchKernelGGL((k_match2<true, true>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
+  else if (prof) hipLaunchKernelGGL((k_match2<true, false>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
+  else if (filt) hipLaunchKernelGGL((k_match2<false, true>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
+  else hipLaunchKernelGGL((k_match2<false, false>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
+  if (m.join_stream2) {
+    m.join_stream2 = false;
+    HIPCHK(hipStreamWaitEvent(c->stream, c->ev2[1], 0));
+    c->stream2_outstanding = false;      // (whatever reuses the arrays does so in `stream`'s order, behind the kernel)
+  }
+  KCHK(c, "k_match2");
+  return 0;
+}
+
+// Phase 5: the match records: copied from the parent where the plan says so, else computed with a pool of their own.
+static int BuildMatchRecords(zmx_ctx* c, zmx_tables* t, zmx_tables* parent, int mk, u64 max_l, const ReusePlan& plan, MatchBuild& m) {
+  const size_t nb = t->nb;
+  const u64 pos_off = t->total_b;
+  const std::vector<u32>& tile_off = t->tile_off;
+  bool reuse = plan.reuse;
+  if (!c->d_scratch) HIPCHK(PoolAllocT(c, &c->d_scratch, static_cast<size_t>(kMatchGrid) * M2_THREADS * SCRATCH_CPS, "d_scratch"));
   HIPCHK(hipEventRecord(c->ev[1], c->stream));
   double match_positions = 0;
   double m5_lane_iters = 0, m5_iters = 0;   // k_match5's own counts
-  // the match-table kernel over `total_tiles` tiles (all of them, or those of tile_list)
-  auto launch_match = [&](u32* pool, u32 pool_cap, u32 total_tiles, const u32* d_tiles, bool prof) -> int {
-    if (total_tiles == 0) return 0;
-#ifdef ZMX_EXPERIMENTS
-    if (t->buckets) {
-      Match3Params mp;
-      mp.in = c->d_in;
-      mp.blocks = t->d_blocks;
-      mp.tile_off = t->d_tile_off;
-      mp.nb = static_cast<u32>(nb);
-      mp.total_tiles = total_tiles;
-      mp.same16 = t->d_same16;
-      mp.chunk_base = t->d_chunk_base;
-      for (int h = 0; h < 2; ++h) { mp.sorted[h] = t->d_sorted[h]; mp.rank[h] = t->d_rank[h]; mp.bucket[h] = t->d_bucket[h]; }
-      mp.ssame = t->d_ssame;
-      mp.recs = t->d_recs;
-      mp.pool = pool;
-      mp.pool_cap = pool_cap;
-      mp.counters = t->d_counters;
-      mp.tile_list = d_tiles;
-      mp.scratch = c->d_scratch;
-      if (mk == 3) {
-        if (prof) hipLaunchKernelGGL((k_match3<true>), dim3(kMatchGrid3), dim3(M3_THREADS), 0, c->stream, mp);
-        else hipLaunchKernelGGL((k_match3<false>), dim3(kMatchGrid3), dim3(M3_THREADS), 0, c->stream, mp);
-        KCHK(c, "k_match3");
-      } else {
-        if (prof) hipLaunchKernelGGL((k_match4<true>), dim3(kMatchGrid3), dim3(M4_THREADS), 0, c->stream, mp);
-        else hipLaunchKernelGGL((k_match4<false>), dim3(kMatchGrid3), dim3(M4_THREADS), 0, c->stream, mp);
-        KCHK(c, "k_match4");
-      }
-      return 0;
-    }
-#endif
-    MatchParams mp;
-    mp.in = c->d_in;
-    mp.blocks = t->d_blocks;
-    mp.tile_off = t->d_tile_off;
-    mp.nb = static_cast<u32>(nb);
-    mp.total_tiles = total_tiles;
-    mp.links = t->d_links;
-    mp.recs = t->d_recs;
-    mp.pool = pool;
-    mp.pool_cap = pool_cap;
-    mp.counters = t->d_counters;
-    mp.scratch = c->d_scratch;
-    mp.tile_list = d_tiles;
-    mp.skip_energy = nullptr;
-    mp.skip_thr = 0;
-    if ((mk == 5 || mk == 0) && d_tiles == nullptr && skip_any) {
-      if (!c->d_scratch5) HIPCHK(PoolAllocT(c, &c->d_scratch5, static_cast<size_t>(kMatchGrid5) * M5_THREADS * SCRATCH_CPS, "d_scratch5"));
-      Match5Params q;
-      q.m = mp;
-      q.m.scratch = c->d_scratch5;
-      q.xrec = d_xrec;
-      q.tot12 = d_tot12;
-      q.energy = mk == 0 ? d_energy : nullptr;
-      q.thr = MatchAutoHits();
-      const size_t m5_waves = static_cast<size_t>(kMatchGrid5) * (M5_THREADS / 64);
-      if (!d_m5stats) HIPCHK(hash_tmp.AllocT(&d_m5stats, 2 * m5_waves, "d_m5stats"));
-      HIPCHK(hipMemsetAsync(d_m5stats, 0, 2 * m5_waves * sizeof(unsigned long long), c->stream));
-      q.wave_stats = d_m5stats;
-      {
-        // positions a wave takes at a time: larger pieces keep the lanes busier (fewer ends of a piece, where lanes
-        // wait for the piece's longest walks), smaller ones the waves when there are few tiles.  100 MB, pieces of 512 /
-        // 1024 / 2048 positions: T 22.4 / 20.0 / 20.4 ms, P 30.1 / 27.9 / 29.5, B 97.1 / 93.1 / 100.0 (ZOPFLI_AMD_M5_UNIT =
-        // 2 / 1 / 0 forces one)
-        static const int forced = [] { const char* e = std::getenv("ZOPFLI_AMD_M5_UNIT"); return e ? std::atoi(e) : -1; }();
-        const u64 waves = static_cast<u64>(kMatchGrid5) * (M5_THREADS / 64);
-        q.sub_shift = forced >= 0 ? static_cast<u32>(forced > 2 ? 2 : forced) : (mp.total_tiles >= 4 * waves ? 1u : 2u);
-      }
-      if (mk == 5 || skip_all) {
-        hipLaunchKernelGGL(k_match5, dim3(kMatchGrid5), dim3(M5_THREADS), 0, c->stream, q);   // (no profile counts: tools/match_skip_model.c has the entries touched)
-        KCHK(c, "k_match5");
-        return 0;
-      }
-      // Some blocks each: k_match5 on the second stream beside k_match2 (which passes over k_match5's blocks) — the
-      // skip-walk of a few heavy blocks is a handful of long-running waves, the rest of the device is k_match2's.
-      HIPCHK(hipEventRecord(c->ev2[0], c->stream));
-      HIPCHK(hipStreamWaitEvent(c->stream2, c->ev2[0], 0));
-      hipLaunchKernelGGL(k_match5, dim3(kMatchGrid5), dim3(M5_THREADS), 0, c->stream2, q);
-      HIPCHK(hipGetLastError());
-      c->stream2_outstanding = true;
-      HIPCHK(hipEventRecord(c->ev2[1], c->stream2));
-      join_stream2 = true;
-      mp.skip_energy = d_energy;
-      mp.skip_thr = MatchAutoHits();
-    }
-    const bool filt = MatchFilter();
-    if (prof && filt) hipLaunchKernelGGL((k_match2<true, true>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
-    else if (prof) hipLaunchKernelGGL((k_match2<true, false>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
-    else if (filt) hipLaunchKernelGGL((k_match2<false, true>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
-    else hipLaunchKernelGGL((k_match2<false, false>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
-    if (join_stream2) {
-      join_stream2 = false;
-      HIPCHK(hipStreamWaitEvent(c->stream, c->ev2[1], 0));
-      c->stream2_outstanding = false;      // (whatever reuses the arrays does so in `stream`'s order, behind the kernel)
-    }
-    KCHK(c, "k_match2");
-    return 0;
-  };
-
   if (reuse) {
     // copy every record, adopt the parent's change-point pool (copied records point into it) and
     // recompute the listed tiles; on pool overflow fall through to the full build
@@ -1248,10 +1167,10 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
     u32* d_tile_list = nullptr;
     PoolScope tmp(c);
     HIPCHK(tmp.AllocT(&d_src_pos, nb, "d_src_pos"));
-    HIPCHK(tmp.AllocT(&d_tile_list, tile_list.size(), "d_tile_list"));
-    HIPCHK(hipMemcpyAsync(d_src_pos, src_pos.data(), nb * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    if (!tile_list.empty()) {
-      HIPCHK(hipMemcpyAsync(d_tile_list, tile_list.data(), tile_list.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(tmp.AllocT(&d_tile_list, plan.tile_list.size(), "d_tile_list"));
+    HIPCHK(hipMemcpyAsync(d_src_pos, plan.src_pos.data(), nb * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    if (!plan.tile_list.empty()) {
+      HIPCHK(hipMemcpyAsync(d_tile_list, plan.tile_list.data(), plan.tile_list.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
     }
     CopyRecsParams cp;
     cp.blocks = t->d_blocks;
@@ -1267,7 +1186,7 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
     // the pool cursor continues where the parent's stopped
     HIPCHK(hipMemsetAsync(t->d_counters, 0, 48 * sizeof(u32), c->stream));
     HIPCHK(hipMemcpyAsync(t->d_counters, parent->d_counters, sizeof(u32), hipMemcpyDeviceToDevice, c->stream));
-    if (launch_match(parent->d_pool, parent->pool_cap, static_cast<u32>(tile_list.size()), d_tile_list, false) != 0) return -1;
+    if (LaunchMatch(c, t, mk, m, parent->d_pool, parent->pool_cap, static_cast<u32>(plan.tile_list.size()), d_tile_list, false) != 0) return -1;
     u32 counters[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(counters, t->d_counters, sizeof(counters), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1278,7 +1197,7 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
       parent->pool_cap = 0;
     } else {
       reuse = false;                       // pool overflow: build everything with a pool of our own,
-      if (launch_hash(nullptr) != 0) return -1;   // which needs the hash arrays of whole blocks
+      if (LaunchHash(c, t, mk, max_l, nullptr, m) != 0) return -1;   // which needs the hash arrays of whole blocks
       t->links_partial = false;
     }
   }
@@ -1299,15 +1218,15 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
     t->pool_cap = static_cast<u32>(cap);
     HIPCHK(hipMemsetAsync(t->d_counters, 0, 48 * sizeof(u32), c->stream));
     static const bool match_prof = std::getenv("ZOPFLI_AMD_PROF") != nullptr;
-    if (launch_match(t->d_pool, t->pool_cap, tile_off[nb], nullptr, match_prof) != 0) return -1;
+    if (LaunchMatch(c, t, mk, m, t->d_pool, t->pool_cap, tile_off[nb], nullptr, match_prof) != 0) return -1;
     u32 counters[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(counters, t->d_counters, sizeof(counters), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     match_positions += static_cast<double>(pos_off);
-    if (d_m5stats) {      // (of the last attempt: the pool may grow and the kernel run again)
+    if (m.d_m5stats) {      // (of the last attempt: the pool may grow and the kernel run again)
       const size_t m5_waves = static_cast<size_t>(kMatchGrid5) * (M5_THREADS / 64);
       std::vector<unsigned long long> ws(2 * m5_waves);
-      HIPCHK(hipMemcpy(ws.data(), d_m5stats, ws.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(ws.data(), m.d_m5stats, ws.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
       m5_lane_iters = m5_iters = 0;
       for (size_t w = 0; w < m5_waves; ++w) { m5_lane_iters += static_cast<double>(ws[2 * w]); m5_iters += static_cast<double>(ws[2 * w + 1]); }
     }
@@ -1334,35 +1253,29 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
     g_match_stats[0] += ms_match * 1e-3;
     g_match_stats[1] += ms_hash * 1e-3;
     g_match_stats[2] += 1;
-    g_match_stats[3] += reuse ? static_cast<double>(tile_list.size()) * MT : match_positions;
-    if (skip_any && !reuse) {
+    g_match_stats[3] += reuse ? static_cast<double>(plan.tile_list.size()) * MT : match_positions;
+    if (m.skip_any && !reuse) {
       g_match5_stats[0] += m5_lane_iters;
       g_match5_stats[1] += m5_iters;
-      g_match5_stats[2] += skip_positions;
+      g_match5_stats[2] += m.skip_positions;
     }
     if (std::getenv("ZOPFLI_AMD_PROF") && !reuse) {
       unsigned long long hc[2] = {0, 0};
       HIPCHK(hipMemcpy(hc, t->d_counters + 4, sizeof(hc), hipMemcpyDeviceToHost));
       const double pos = static_cast<double>(pos_off);
       std::fprintf(stderr, "%s: %.2f ms for %.0f positions: %.1f chain hits per "
-                   "position, %.1f of 64 lanes with a hit per wave-loop iteration; %.1f SIMD cycles per hit (2.4 GHz, 1024 SIMDs)\n", mk == 5 || mk == 0 ? "k_match5 / k_match2 (hits = entries touched)" : mk == 4 ? "k_match4" : mk == 3 ? "k_match3" : "k_match2", ms_match, pos,
+                   "position, %.1f of 64 lanes with a hit per wave-loop iteration; %.1f SIMD cycles per hit (2.4 GHz, 1024 SIMDs)\n", mk == 5 || mk == 0 ? "k_match5 / k_match2 (hits = entries touched)" : "k_match2", ms_match, pos,
                    static_cast<double>(hc[0]) / pos, static_cast<double>(hc[0]) / static_cast<double>(hc[1] ? hc[1] : 1),
                    ms_match * 1e-3 * 2.4e9 * 1024 / static_cast<double>(hc[0] ? hc[0] : 1));
-      if (mk == 3) {
-        unsigned long long h3[3] = {0, 0, 0};
-        HIPCHK(hipMemcpy(h3, t->d_counters + 16, sizeof(h3), hipMemcpyDeviceToHost));
-        const double nbat = static_cast<double>(hc[1] ? hc[1] : 1);
-        std::fprintf(stderr, "k_match3: per batch of <= 64 candidates: %.2f pass the 4-byte filter, %.2f steps of the byte compare, "
-                     "%.1f %% of the batches change nothing; %.0f SIMD cycles per batch\n", static_cast<double>(h3[0]) / nbat,
-                     static_cast<double>(h3[1]) / nbat, 100.0 * static_cast<double>(h3[2]) / nbat, ms_match * 1e-3 * 2.4e9 * 1024 / nbat);
-      }
     }
   }
+  return 0;
+}
 
-  // (zmx_tables_build_matches: the greedy pass over master blocks that will be split wants the matches only; the codes
-  //  of its DP edges — two bytes for each of up to 258 edges a position, 52 GB for 100 MB of long runs — would be
-  //  written, never read, and held while the tables of the split blocks allocate their own)
-  if (with_dp) {
+// Phase 6: DP rows, the edges as codes and the window descriptors.  kTooLarge: come back with fewer blocks.
+static int BuildDpRows(zmx_ctx* c, zmx_tables* t) {
+  const size_t nb = t->nb;
+  const std::vector<u32>& tile_off = t->tile_off;
   // DP row layout (k_rowscan), then the edges as weight codes (k_codes) and a buffer descriptor per row
   RowScanParams rp;
   rp.blocks = t->d_blocks;
@@ -1435,172 +1348,161 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));   // (code_base is a local)
   }
-  // the chain's tasks (zmx_dp4.h): SEG_L positions each, the last one of a block takes the remainder
-  {
-    const u32 L = SegL(t->total_b), warm = SegWarm();
-    const u32 head = std::max(SegHead(nb), L);
-    t->task_off.assign(nb + 1, 0);
-    t->tasks.clear();
+  return 0;
+}
+
+// Phase 7: the chain's tasks (zmx_dp4.h): SEG_L positions each, the last one of a block takes the remainder
+static int BuildChainTasks(zmx_ctx* c, zmx_tables* t) {
+  const size_t nb = t->nb;
+  const u32 L = SegL(t->total_b), warm = SegWarm();
+  const u32 head = std::max(SegHead(nb), L);
+  t->task_off.assign(nb + 1, 0);
+  t->tasks.clear();
+  for (size_t b = 0; b < nb; ++b) {
+    const u32 B = t->bsize[b];
+    // the head [0, head), then tasks of L positions; the last one takes the remainder
+    const u32 n = (L == 0 || B < head + L) ? 1u : 1u + (B - head) / L;
+    for (u32 s = 0; s < n; ++s) {
+      SegTask k;
+      k.block = static_cast<u32>(b);
+      k.pout = s == 0 ? 0u : head + (s - 1) * L;
+      k.q = s == 0 ? 0u : k.pout - std::min(warm, k.pout);
+      k.pend = s + 1 == n ? B + 1 : head + s * L;
+      t->tasks.push_back(k);
+    }
+    t->task_off[b + 1] = static_cast<u32>(t->tasks.size());
+  }
+  const size_t nt = t->tasks.size();
+  HIPCHK(PoolAlloc(c, &t->d_tasks, nt));
+  HIPCHK(PoolAlloc(c, &t->d_task_off, nb + 1));
+  HIPCHK(PoolAlloc(c, &t->d_lvl, nt));
+  HIPCHK(PoolAlloc(c, &t->d_entry, nt));
+  HIPCHK(PoolAlloc(c, &t->d_exit, nt));
+  HIPCHK(PoolAlloc(c, &t->d_mid, nt));
+  HIPCHK(PoolAlloc(c, &t->d_chk, nt));
+  HIPCHK(PoolAlloc(c, &t->d_over, nt * SEG_OVER));
+  HIPCHK(PoolAlloc(c, &t->d_redo, 4 + nt * 4));
+  HIPCHK(hipMemcpyAsync(t->d_tasks, t->tasks.data(), nt * sizeof(SegTask), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(t->d_task_off, t->task_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(t->d_segstats, 0, 8 * sizeof(u32), c->stream));
+  // start the tasks at cut points of the DP where there is one close enough (zmx_dp5.h: k_cutpoints);
+  // ZOPFLI_AMD_SEG_CUTS = how far before a task's first owned position to look, 0 = every task warms up
+  // (the search costs 1.1 ms per 100 MB at 1024, the configuration the whole GPU suite ran with; 512 would halve
+  //  it and finds the same cut point for 99.8 % of the tasks of text)
+  static const u32 cut_depth = EnvU32("ZOPFLI_AMD_SEG_CUTS", 1024, 0, 1u << 16);
+  if (cut_depth && nt) {
+    PoolScope tmp(c);
+    u32* d_found = nullptr;
+    u32* d_wide = nullptr;
+    HIPCHK(tmp.AllocT(&d_found, 2, "d_found"));
+    HIPCHK(tmp.AllocT(&d_wide, nt, "d_wide"));
+    HIPCHK(hipMemsetAsync(d_found, 0, 2 * sizeof(u32), c->stream));
+    HIPCHK(hipMemsetAsync(d_wide, 0, nt * sizeof(u32), c->stream));
+    CutParams cp;
+    cp.blocks = t->d_blocks;
+    cp.dph = t->d_dph;
+    cp.tasks = t->d_tasks;
+    cp.depth = cut_depth;
+    cp.warm = warm;
+    cp.found = d_found;
+    cp.wide = d_wide;
+    hipLaunchKernelGGL(k_cutpoints, dim3(static_cast<unsigned>(nt)), dim3(64), 0, c->stream, cp);
+    KCHK(c, "k_cutpoints");
+    static const bool prof = std::getenv("ZOPFLI_AMD_PROF") != nullptr;
+    u32 found[2] = {0, 0};
+    std::vector<u32> wide(nt);
+    HIPCHK(hipMemcpyAsync(found, d_found, sizeof(found), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(wide.data(), d_wide, nt * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(t->tasks.data(), t->d_tasks, nt * sizeof(SegTask), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    // merge the tasks that must not speculate (k_cutpoints) into their predecessors: the predecessor walks on to
+    // the merged task's end.  (The head of a block is never merged: pout = 0.)
+    size_t merged = 0;
+    std::vector<SegTask> kept;
+    kept.reserve(nt);
+    std::vector<u32> off(nb + 1, 0);
     for (size_t b = 0; b < nb; ++b) {
-      const u32 B = t->bsize[b];
-      // the head [0, head), then tasks of L positions; the last one takes the remainder
-      const u32 n = (L == 0 || B < head + L) ? 1u : 1u + (B - head) / L;
-      for (u32 s = 0; s < n; ++s) {
-        SegTask k;
-        k.block = static_cast<u32>(b);
-        k.pout = s == 0 ? 0u : head + (s - 1) * L;
-        k.q = s == 0 ? 0u : k.pout - std::min(warm, k.pout);
-        k.pend = s + 1 == n ? B + 1 : head + s * L;
-        t->tasks.push_back(k);
+      for (u32 k = t->task_off[b]; k < t->task_off[b + 1]; ++k) {
+        if (k > t->task_off[b] && wide[k]) {
+          kept.back().pend = t->tasks[k].pend;
+          ++merged;
+        } else {
+          kept.push_back(t->tasks[k]);
+        }
       }
-      t->task_off[b + 1] = static_cast<u32>(t->tasks.size());
+      off[b + 1] = static_cast<u32>(kept.size());
     }
-    const size_t nt = t->tasks.size();
-    HIPCHK(PoolAlloc(c, &t->d_tasks, nt));
-    HIPCHK(PoolAlloc(c, &t->d_task_off, nb + 1));
-    HIPCHK(PoolAlloc(c, &t->d_lvl, nt));
-    HIPCHK(PoolAlloc(c, &t->d_entry, nt));
-    HIPCHK(PoolAlloc(c, &t->d_exit, nt));
-    HIPCHK(PoolAlloc(c, &t->d_mid, nt));
-    HIPCHK(PoolAlloc(c, &t->d_chk, nt));
-    HIPCHK(PoolAlloc(c, &t->d_over, nt * SEG_OVER));
-    HIPCHK(PoolAlloc(c, &t->d_redo, 4 + nt * 4));
-    HIPCHK(hipMemcpyAsync(t->d_tasks, t->tasks.data(), nt * sizeof(SegTask), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(t->d_task_off, t->task_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(t->d_segstats, 0, 8 * sizeof(u32), c->stream));
-    // start the tasks at cut points of the DP where there is one close enough (zmx_dp5.h: k_cutpoints);
-    // ZOPFLI_AMD_SEG_CUTS = how far before a task's first owned position to look, 0 = every task warms up
-    // (the search costs 1.1 ms per 100 MB at 1024, the configuration the whole GPU suite ran with; 512 would halve
-    //  it and finds the same cut point for 99.8 % of the tasks of text)
-    static const u32 cut_depth = EnvU32("ZOPFLI_AMD_SEG_CUTS", 1024, 0, 1u << 16);
-    // ZOPFLI_AMD_SEG_MERGE=0: never merge tasks (every task that finds no cut point warms up, as in round 2)
-    static const bool merge_on = EnvU32("ZOPFLI_AMD_SEG_MERGE", 1, 0, 1) != 0;
-    if (cut_depth && nt) {
-      PoolScope tmp(c);
-      u32* d_found = nullptr;
-      u32* d_wide = nullptr;
-      HIPCHK(tmp.AllocT(&d_found, 2, "d_found"));
-      HIPCHK(tmp.AllocT(&d_wide, nt, "d_wide"));
-      HIPCHK(hipMemsetAsync(d_found, 0, 2 * sizeof(u32), c->stream));
-      HIPCHK(hipMemsetAsync(d_wide, 0, nt * sizeof(u32), c->stream));
-      CutParams cp;
-      cp.blocks = t->d_blocks;
-      cp.dph = t->d_dph;
-      cp.tasks = t->d_tasks;
-      cp.depth = cut_depth;
-      cp.warm = warm;
-      cp.found = d_found;
-      cp.wide = d_wide;
-      hipLaunchKernelGGL(k_cutpoints, dim3(static_cast<unsigned>(nt)), dim3(64), 0, c->stream, cp);
-      KCHK(c, "k_cutpoints");
-      static const bool prof = std::getenv("ZOPFLI_AMD_PROF") != nullptr;
-      u32 found[2] = {0, 0};
-      std::vector<u32> wide(nt);
-      HIPCHK(hipMemcpyAsync(found, d_found, sizeof(found), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipMemcpyAsync(wide.data(), d_wide, nt * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipMemcpyAsync(t->tasks.data(), t->d_tasks, nt * sizeof(SegTask), hipMemcpyDeviceToHost, c->stream));
+    t->merged_tasks = merged;
+    if (merged) {
+      t->tasks.swap(kept);
+      t->task_off.swap(off);
+      HIPCHK(hipMemcpyAsync(t->d_tasks, t->tasks.data(), t->tasks.size() * sizeof(SegTask), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(t->d_task_off, t->task_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
-      // merge the tasks that must not speculate (k_cutpoints) into their predecessors: the predecessor walks on to
-      // the merged task's end.  (The head of a block is never merged: pout = 0.)
-      size_t merged = 0;
-      if (merge_on) {
-        std::vector<SegTask> kept;
-        kept.reserve(nt);
-        std::vector<u32> off(nb + 1, 0);
-        for (size_t b = 0; b < nb; ++b) {
-          for (u32 k = t->task_off[b]; k < t->task_off[b + 1]; ++k) {
-            if (k > t->task_off[b] && wide[k]) {
-              kept.back().pend = t->tasks[k].pend;
-              ++merged;
-            } else {
-              kept.push_back(t->tasks[k]);
-            }
-          }
-          off[b + 1] = static_cast<u32>(kept.size());
+    }
+    if (prof) {
+      std::fprintf(stderr, "k_cutpoints: %u of %zu tasks start at a cut point, %.1f positions before their first owned one on average; "
+                   "%zu tasks merged into their predecessors (long-run material in the warm-up stretch), %zu tasks left\n",
+                   found[0], nt, found[0] ? static_cast<double>(found[1]) / found[0] : 0.0, merged, t->tasks.size());
+    }
+  }
+  return 0;
+}
+
+// Phase 8: the workgroup lists.
+static int BuildWorkgroupLists(zmx_ctx* c, zmx_tables* t) {
+  const size_t nb = t->nb;
+  // k_dp5_spec's workgroups: four tasks of one block each (they share the block's weight table in
+  // LDS); the workgroups that hold a head (several times the length of the other tasks) go first.  Tasks that
+  // walk runs of equal bytes (k_taskkind) get workgroups of their own, listed after the others: they are run by the
+  // kernel's other variant, beside the rest.
+  const size_t ntk = t->tasks.size();
+  std::vector<u32> kind(ntk, 0);
+  if (ntk) {
+    PoolScope tmp(c);
+    u32* d_kind = nullptr;
+    HIPCHK(tmp.AllocT(&d_kind, ntk, "d_kind"));
+    TaskKindParams kp;
+    kp.tasks = t->d_tasks;
+    kp.blocks = t->d_blocks;
+    kp.winflag = t->d_winflag;
+    kp.win_off = t->d_win_off;
+    kp.kind = d_kind;
+    hipLaunchKernelGGL(k_taskkind, dim3(static_cast<unsigned>(ntk)), dim3(64), 0, c->stream, kp);
+    KCHK(c, "k_taskkind");
+    HIPCHK(hipMemcpyAsync(kind.data(), d_kind, ntk * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  std::vector<u32> wg, wg_runs;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (size_t b = 0; b < nb; ++b) {
+      const u32 a0 = t->task_off[b], a1 = t->task_off[b + 1];
+      // pass 0: the group that holds the block's head; pass 1: the others.  Inside a block the tasks of either kind
+      // are grouped four at a time in order.
+      std::vector<u32> grp[2];
+      for (u32 k = a0; k < a1; ++k) grp[kind[k] ? 1 : 0].push_back(k);
+      for (int kd = 0; kd < 2; ++kd) {
+        std::vector<u32>& dst = kd ? wg_runs : wg;
+        for (size_t i = 0; i < grp[kd].size(); i += D5_WG) {
+          const bool has_head = i == 0 && !grp[kd].empty() && grp[kd][0] == a0;
+          if ((pass == 0) != has_head) continue;
+          for (u32 w = 0; w < D5_WG; ++w) dst.push_back(i + w < grp[kd].size() ? grp[kd][i + w] : SEG_NONE);
         }
-        t->merged_tasks = merged;
-        if (merged) {
-          t->tasks.swap(kept);
-          t->task_off.swap(off);
-          HIPCHK(hipMemcpyAsync(t->d_tasks, t->tasks.data(), t->tasks.size() * sizeof(SegTask), hipMemcpyHostToDevice, c->stream));
-          HIPCHK(hipMemcpyAsync(t->d_task_off, t->task_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-          HIPCHK(hipStreamSynchronize(c->stream));
-        }
-      }
-      if (prof) {
-        std::fprintf(stderr, "k_cutpoints: %u of %zu tasks start at a cut point, %.1f positions before their first owned one on average; "
-                     "%zu tasks merged into their predecessors (long-run material in the warm-up stretch), %zu tasks left\n",
-                     found[0], nt, found[0] ? static_cast<double>(found[1]) / found[0] : 0.0, merged, t->tasks.size());
       }
     }
   }
-  {
-    // k_dp5_spec's workgroups: four tasks of one block each (they share the block's weight table in
-    // LDS); the workgroups that hold a head (several times the length of the other tasks) go first.  Tasks that
-    // walk runs of equal bytes (k_taskkind) get workgroups of their own, listed after the others: they are run by the
-    // kernel's other variant, beside the rest.
-    const size_t ntk = t->tasks.size();
-    std::vector<u32> kind(ntk, 0);
-    if (ntk) {
-      PoolScope tmp(c);
-      u32* d_kind = nullptr;
-      HIPCHK(tmp.AllocT(&d_kind, ntk, "d_kind"));
-      TaskKindParams kp;
-      kp.tasks = t->d_tasks;
-      kp.blocks = t->d_blocks;
-      kp.winflag = t->d_winflag;
-      kp.win_off = t->d_win_off;
-      kp.kind = d_kind;
-      hipLaunchKernelGGL(k_taskkind, dim3(static_cast<unsigned>(ntk)), dim3(64), 0, c->stream, kp);
-      KCHK(c, "k_taskkind");
-      HIPCHK(hipMemcpyAsync(kind.data(), d_kind, ntk * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    std::vector<u32> wg, wg_runs;
-    for (int pass = 0; pass < 2; ++pass) {
-      for (size_t b = 0; b < nb; ++b) {
-        const u32 a0 = t->task_off[b], a1 = t->task_off[b + 1];
-        // pass 0: the group that holds the block's head; pass 1: the others.  Inside a block the tasks of either kind
-        // are grouped four at a time in order.
-        std::vector<u32> grp[2];
-        for (u32 k = a0; k < a1; ++k) grp[kind[k] ? 1 : 0].push_back(k);
-        for (int kd = 0; kd < 2; ++kd) {
-          std::vector<u32>& dst = kd ? wg_runs : wg;
-          for (size_t i = 0; i < grp[kd].size(); i += D5_WG) {
-            const bool has_head = i == 0 && !grp[kd].empty() && grp[kd][0] == a0;
-            if ((pass == 0) != has_head) continue;
-            for (u32 w = 0; w < D5_WG; ++w) dst.push_back(i + w < grp[kd].size() ? grp[kd][i + w] : SEG_NONE);
-          }
-        }
-      }
-    }
-    t->n_wg = static_cast<u32>(wg.size() / D5_WG);
-    t->n_wg_runs = static_cast<u32>(wg_runs.size() / D5_WG);
-    // the cooperative kernel's list (zmx_dp6.h): a workgroup per run task, the longest first — a squeeze run waits for
-    // its longest task, and a giant started behind a queue of small ones ends that much later
-    {
-      std::vector<u32> runs;
-      for (size_t k = 0; k < ntk; ++k) if (kind[k]) runs.push_back(static_cast<u32>(k));
-      auto walked = [&](u32 k) {
-        const SegTask& T = t->tasks[k];
-        const u32 Bk = t->bsize[T.block];
-        return (T.pend < Bk ? T.pend : Bk) - T.q;
-      };
-      std::stable_sort(runs.begin(), runs.end(), [&](u32 a, u32 b2) { return walked(a) > walked(b2); });
-      t->n_run_list = static_cast<u32>(runs.size());
-      HIPCHK(PoolAlloc(c, &t->d_task_kind, ntk + 4));
-      HIPCHK(PoolAlloc(c, &t->d_run_list, runs.size() + 4));
-      if (ntk) HIPCHK(hipMemcpyAsync(t->d_task_kind, kind.data(), ntk * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-      if (!runs.empty()) HIPCHK(hipMemcpyAsync(t->d_run_list, runs.data(), runs.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));   // (locals)
-    }
-    wg.insert(wg.end(), wg_runs.begin(), wg_runs.end());
-    HIPCHK(PoolAlloc(c, &t->d_wg_tasks, wg.size() + 4));
-    if (!wg.empty()) HIPCHK(hipMemcpyAsync(t->d_wg_tasks, wg.data(), wg.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));   // `wg` is a local
-  }
-  }  // with_dp
-  // trace segments (zmx_trace.h)
+  t->n_wg = static_cast<u32>(wg.size() / D5_WG);
+  t->n_wg_runs = static_cast<u32>(wg_runs.size() / D5_WG);
+  wg.insert(wg.end(), wg_runs.begin(), wg_runs.end());
+  HIPCHK(PoolAlloc(c, &t->d_wg_tasks, wg.size() + 4));
+  if (!wg.empty()) HIPCHK(hipMemcpyAsync(t->d_wg_tasks, wg.data(), wg.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));   // `wg` is a local
+  return 0;
+}
+
+// Phase 9: trace segments (zmx_trace.h)
+static int BuildTraceSegments(zmx_ctx* c, zmx_tables* t) {
+  const size_t nb = t->nb;
   t->seg_off.assign(nb + 1, 0);
   for (size_t b = 0; b < nb; ++b) t->seg_off[b + 1] = t->seg_off[b] + (t->bsize[b] + TS_SEG - 1) / TS_SEG;
   HIPCHK(PoolAlloc(c, &t->d_seg_off, nb + 1));
@@ -1609,6 +1511,28 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
   HIPCHK(hipMemcpyAsync(t->d_seg_off, t->seg_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_tables* t, zmx_tables* parent = nullptr, bool with_dp = true) {
+  const int mk = MatchKernel();   // (one choice per build: zmx_set_match_kernel may be called meanwhile)
+  t->matches_only = !with_dp;
+  u64 la_off = 0, max_l = 0;
+  if (const int rc = LayoutBlocks(c, blocks, nb, t, &la_off, &max_l)) return rc;
+  if (nb == 0) return 0;
+  const ReusePlan plan = PlanReuse(c, t, parent);
+  if (const int rc = AllocTableArrays(c, t, la_off)) return rc;
+  MatchBuild m(c);
+  if (const int rc = BuildHashLinks(c, t, mk, max_l, plan, m)) return rc;
+  if (const int rc = BuildMatchRecords(c, t, parent, mk, max_l, plan, m)) return rc;
+  // (zmx_tables_build_matches: the greedy pass over master blocks that will be split wants the matches only; the codes
+  //  of its DP edges — two bytes for each of up to 258 edges a position, 52 GB for 100 MB of long runs — would be
+  //  written, never read, and held while the tables of the split blocks allocate their own)
+  if (with_dp) {
+    if (const int rc = BuildDpRows(c, t)) return rc;
+    if (const int rc = BuildChainTasks(c, t)) return rc;
+    if (const int rc = BuildWorkgroupLists(c, t)) return rc;
+  }
+  return BuildTraceSegments(c, t);
 }
 
 int zmx_tables_build(zmx_ctx* c, const zmx_block* blocks, size_t nblocks, zmx_tables** out) {
@@ -1760,6 +1684,49 @@ __attribute__((visibility("default"))) void zmx_internal_run_info(const double* 
   RunInfo(cost320, nullptr, 0, wmax, tiemask, &est);
 }
 
+// ZOPFLI_AMD_PROF: what the counters of the run that just ended say (t->d_prof), on stderr.
+static int ReportSqueezeProf(zmx_tables* t, const double* ksec, const u32* segstats) {
+  const size_t nb = t->nb;
+  std::vector<u64> pr(nb * ZMX_PROF_N);
+  HIPCHK(hipMemcpy(pr.data(), t->d_prof, pr.size() * sizeof(u64), hipMemcpyDeviceToHost));
+  double a[ZMX_PROF_N] = {};
+  for (size_t b = 0; b < nb; ++b)
+    for (unsigned k = 0; k < ZMX_PROF_N; ++k) a[k] += static_cast<double>(pr[b * ZMX_PROF_N + k]);
+  std::fprintf(stderr, "squeeze prof: edges %.2f ms chain %.2f ms trace %.2f ms; chain wave busy %.1f cycles/position, "
+               "%.0f steps, fast %.1f%% of %.0f positions walked (%zu in the blocks); tasks %u accepted %u re-run "
+               "state %u values %u level %u tie %u (%u positions, %u by the lean job)\n",
+               ksec[0] * 1e3, ksec[1] * 1e3, ksec[2] * 1e3, a[1] / a[4], a[0],
+               100.0 * a[2] / (a[2] + a[3] + 1e-9), a[4], t->total_b, segstats[0], segstats[1], segstats[2],
+               segstats[6], segstats[3], segstats[4], segstats[5], segstats[7]);
+  {
+    double mx = 0, hd = 0;
+    for (size_t b = 0; b < nb; ++b) { mx = std::max(mx, static_cast<double>(pr[b * ZMX_PROF_N + 7])); hd = std::max(hd, static_cast<double>(pr[b * ZMX_PROF_N + 8])); }
+    std::fprintf(stderr, "  k_dp5_spec: longest task %.0f cycles, longest head task %.0f cycles; %.1f%% of the positions walked by the integer step (cycles per position there: fetch issue %.1f, fetch wait %.1f, gather + chain %.1f)\n", mx, hd, 100.0 * a[10] / (a[4] + 1e-9), a[11] / (a[10] + 1e-9), a[12] / (a[10] + 1e-9), a[13] / (a[10] + 1e-9));
+  }
+  std::fprintf(stderr, "  k_dp5_spec integer windows, cycles per position: class decision %.1f, waiting for the prefetched record and codes %.1f, prefetch issue %.1f\n",
+               a[20] / (a[10] + 1e-9), a[21] / (a[10] + 1e-9), a[22] / (a[10] + 1e-9));
+  std::fprintf(stderr, "  k_dp5_spec windows: integer %.1f%% of positions at %.0f cycles each, class 1 in doubles %.1f%% at %.0f, class 2 %.1f%% at %.0f, generic %.1f%% at %.0f\n",
+               100.0 * a[28] / (a[4] + 1e-9), a[24] / (a[28] + 1e-9), 100.0 * a[29] / (a[4] + 1e-9), a[25] / (a[29] + 1e-9),
+               100.0 * a[30] / (a[4] + 1e-9), a[26] / (a[30] + 1e-9), 100.0 * a[31] / (a[4] + 1e-9), a[27] / (a[31] + 1e-9));
+  std::fprintf(stderr, "  k_dp5_spec generic windows, cycles each: shortcut %.0f (%.0f of them), run row integer %.0f (%.0f), run row doubles %.0f (%.0f), other row %.0f (%.0f), window header %.0f (%.0f)\n",
+               a[32] / (a[33] + 1e-9), a[33], a[34] / (a[35] + 1e-9), a[35], a[36] / (a[37] + 1e-9), a[37], a[38] / (a[39] + 1e-9), a[39], a[40] / (a[41] + 1e-9), a[41]);
+  std::fprintf(stderr, "  k_dp5_spec positions: run interior %.0f in unrolled windows, %.0f in loops with room, %.0f with checks; general step: %.0f run rows, %.0f other rows; class 2: %.0f rows that reach register 2\n",
+               a[42], a[43], a[44], a[45], a[46], a[47]);
+  {
+    const double gen = a[51] - a[49] - a[50] - a[52];     // (the loop over a window's positions, less its stretches)
+    std::fprintf(stderr, "  k_dp5_spec generic windows, cycles: headers %.3g, run stretches: whole windows %.3g (%.0f per position), others %.3g (%.0f); stretches of other rows %.3g (%.0f); the general step %.3g (%.0f per position incl. shortcuts)\n",
+                 a[48], a[49], a[49] / (a[42] + 1e-9), a[50], a[50] / (a[43] + a[44] + 1e-9), a[52], a[52] / (a[53] + 1e-9), gen, gen / (a[45] + a[46] + a[33] + 1e-9));
+  }
+  const char* nm[5] = {"32", "16", "8", "8 (two registers)", "generic"};
+  for (int i = 0; i < 5; ++i)
+    std::fprintf(stderr, "  path %-18s %5.1f%% of positions, %6.1f cycles/position\n", nm[i], 100.0 * a[6 + 2 * i] / a[4],
+                 a[5 + 2 * i] / (a[6 + 2 * i] + 1e-9));
+  for (int w = 0; w < 2; ++w)
+    std::fprintf(stderr, "  producer wave %d, cycles/step: walk %.0f ring %.0f tiles %.0f barrier %.0f\n", w + 1,
+                 a[16 + 8 * w] / a[0], a[17 + 8 * w] / a[0], a[18 + 8 * w] / a[0], a[19 + 8 * w] / a[0]);
+  return 0;
+}
+
 int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double* mincost, const int32_t* slot,
                     uint32_t* nsym, uint32_t* hist) {
   if (t && t->trimmed) return FailMsg("zmx_squeeze_run: these tables were trimmed to their stores (zmx_tables_trim)");
@@ -1854,16 +1821,6 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
   cp.redo_count = t->d_redo;
   cp.redo_wg = t->d_redo + 4;
   cp.redo_pass = 0;
-  // (ZOPFLI_AMD_COOP=1: run tasks by k_dp6_spec, four waves a task (zmx_dp6.h) — built and measured in round 5, NOT the
-  //  default: 52.6 ms of chain per run on class Z against 45.9 with one wave a task)
-#ifdef ZMX_EXPERIMENTS
-  static const int coop = [] { const char* e = std::getenv("ZOPFLI_AMD_COOP"); return e ? std::atoi(e) : 0; }();
-#else
-  constexpr int coop = 0;     // (k_dp6_spec is in -DZMX_EXPERIMENTS builds only)
-#endif
-  cp.coop = coop != 0 ? 1 : 0;
-  cp.kind = t->d_task_kind;
-  cp.run_list = t->d_run_list;
   cp.flags = t->d_flags;
   cp.wmeta = t->d_wmeta;
   cp.winroff = t->d_winroff;
@@ -1917,11 +1874,6 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
         HIPCHK(hipStreamWaitEvent(c->stream2, c->ev2[0], 0));
         Dp4Params cr = cp;
         cr.task0 = t->n_wg;
-#ifdef ZMX_EXPERIMENTS
-        if (cp.coop && cp.prof) hipLaunchKernelGGL((k_dp6_spec<2, true>), dim3(t->n_run_list), dim3(64 * D6_NW), 0, c->stream2, cr);
-        else if (cp.coop) hipLaunchKernelGGL((k_dp6_spec<2, false>), dim3(t->n_run_list), dim3(64 * D6_NW), 0, c->stream2, cr);
-        else
-#endif
         if (cp.prof) hipLaunchKernelGGL((k_dp5_spec<true, 2, true>), dim3(t->n_wg_runs), bdim, 0, c->stream2, cr);
         else hipLaunchKernelGGL((k_dp5_spec<false, 2, true>), dim3(t->n_wg_runs), bdim, 0, c->stream2, cr);
         HIPCHK(hipGetLastError());
@@ -1954,14 +1906,6 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
         // (one workgroup per listed task; the workgroups beyond the list have nothing to do)
         const unsigned cap = ntask;
         // (the variant for run tasks wherever the set has any: what is run again there is mostly theirs)
-#ifdef ZMX_EXPERIMENTS
-        if (t->n_wg_runs && cp.coop) {
-          // the listed run tasks by k_dp6_spec, the listed text tasks by the text variant (each passes over the other's)
-          hipLaunchKernelGGL((k_dp6_spec<2, false>), dim3(cap), dim3(64 * D6_NW), 0, c->stream, c2);
-          if (cp.prof) hipLaunchKernelGGL((k_dp5_spec<true, 4, false>), dim3(cap), dim3(64 * D5_WG), 0, c->stream, c2);
-          else hipLaunchKernelGGL((k_dp5_spec<false, 4, false>), dim3(cap), dim3(64 * D5_WG), 0, c->stream, c2);
-        } else
-#endif
         if (t->n_wg_runs) {
           if (cp.prof) hipLaunchKernelGGL((k_dp5_spec<true, 2, true>), dim3(cap), dim3(64 * D5_WG), 0, c->stream, c2);
           else hipLaunchKernelGGL((k_dp5_spec<false, 2, true>), dim3(cap), dim3(64 * D5_WG), 0, c->stream, c2);
@@ -2025,56 +1969,7 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
     g_seg_stats[7] += static_cast<double>(t->total_b);
   }
   for (size_t b = 0; b < nb; ++b) t->store_begin[slot[b]][b] = t->bsize[b] - nsym[b];
-  if (t->d_prof) {
-    std::vector<u64> pr(nb * ZMX_PROF_N);
-    HIPCHK(hipMemcpy(pr.data(), t->d_prof, pr.size() * sizeof(u64), hipMemcpyDeviceToHost));
-    double a[ZMX_PROF_N] = {};
-    for (size_t b = 0; b < nb; ++b)
-      for (unsigned k = 0; k < ZMX_PROF_N; ++k) a[k] += static_cast<double>(pr[b * ZMX_PROF_N + k]);
-    if (cp.coop && t->n_run_list) {
-      // k_dp6_spec's first pass (zmx_dp6.h): wave 0's cycles by activity, summed over the run tasks (the text tasks' counters
-      // of k_dp5_spec share the slots: read this line on long-run data only)
-      double mxj = 0;
-      for (size_t b = 0; b < nb; ++b) mxj = std::max(mxj, static_cast<double>(pr[b * ZMX_PROF_N + 16]));
-      std::fprintf(stderr, "coop prof (k_dp6_spec, first pass, wave 0): job cycles %.3g (longest job %.3g): token+flow %.3g, class 1 %.3g, class 2 %.3g, "
-                   "headers %.3g, other stretches %.3g (%.0f positions, %.0f each), run stretches %.3g (%.0f positions, %.0f each), general step %.3g (%.0f, %.0f each), "
-                   "shortcuts %.3g (%.0f, %.0f each), waiting for wave 1 at the rotation %.3g (%.0f windows, %.0f each); wave 1: %.3g of %.3g cycles inside get()\n",
-                   a[9], mxj, a[0], a[1], a[2], a[3], a[4], a[10], a[4] / (a[10] + 1e-9), a[5], a[11], a[5] / (a[11] + 1e-9), a[6], a[12], a[6] / (a[12] + 1e-9),
-                   a[7], a[13], a[7] / (a[13] + 1e-9), a[8], a[14], a[8] / (a[14] + 1e-9), a[15], a[17]);
-    }
-    std::fprintf(stderr, "squeeze prof: edges %.2f ms chain %.2f ms trace %.2f ms; chain wave busy %.1f cycles/position, "
-                 "%.0f steps, fast %.1f%% of %.0f positions walked (%zu in the blocks); tasks %u accepted %u re-run "
-                 "state %u values %u level %u tie %u (%u positions, %u by the lean job)\n",
-                 ksec[0] * 1e3, ksec[1] * 1e3, ksec[2] * 1e3, a[1] / a[4], a[0],
-                 100.0 * a[2] / (a[2] + a[3] + 1e-9), a[4], t->total_b, segstats[0], segstats[1], segstats[2],
-                 segstats[6], segstats[3], segstats[4], segstats[5], segstats[7]);
-    {
-      double mx = 0, hd = 0;
-      for (size_t b = 0; b < nb; ++b) { mx = std::max(mx, static_cast<double>(pr[b * ZMX_PROF_N + 7])); hd = std::max(hd, static_cast<double>(pr[b * ZMX_PROF_N + 8])); }
-      std::fprintf(stderr, "  k_dp5_spec: longest task %.0f cycles, longest head task %.0f cycles; %.1f%% of the positions walked by the integer step (cycles per position there: fetch issue %.1f, fetch wait %.1f, gather + chain %.1f)\n", mx, hd, 100.0 * a[10] / (a[4] + 1e-9), a[11] / (a[10] + 1e-9), a[12] / (a[10] + 1e-9), a[13] / (a[10] + 1e-9));
-    }
-    std::fprintf(stderr, "  k_dp5_spec integer windows, cycles per position: class decision %.1f, waiting for the prefetched record and codes %.1f, prefetch issue %.1f\n",
-                 a[20] / (a[10] + 1e-9), a[21] / (a[10] + 1e-9), a[22] / (a[10] + 1e-9));
-    std::fprintf(stderr, "  k_dp5_spec windows: integer %.1f%% of positions at %.0f cycles each, class 1 in doubles %.1f%% at %.0f, class 2 %.1f%% at %.0f, generic %.1f%% at %.0f\n",
-                 100.0 * a[28] / (a[4] + 1e-9), a[24] / (a[28] + 1e-9), 100.0 * a[29] / (a[4] + 1e-9), a[25] / (a[29] + 1e-9),
-                 100.0 * a[30] / (a[4] + 1e-9), a[26] / (a[30] + 1e-9), 100.0 * a[31] / (a[4] + 1e-9), a[27] / (a[31] + 1e-9));
-    std::fprintf(stderr, "  k_dp5_spec generic windows, cycles each: shortcut %.0f (%.0f of them), run row integer %.0f (%.0f), run row doubles %.0f (%.0f), other row %.0f (%.0f), window header %.0f (%.0f)\n",
-                 a[32] / (a[33] + 1e-9), a[33], a[34] / (a[35] + 1e-9), a[35], a[36] / (a[37] + 1e-9), a[37], a[38] / (a[39] + 1e-9), a[39], a[40] / (a[41] + 1e-9), a[41]);
-    std::fprintf(stderr, "  k_dp5_spec positions: run interior %.0f in unrolled windows, %.0f in loops with room, %.0f with checks; general step: %.0f run rows, %.0f other rows; class 2: %.0f rows that reach register 2\n",
-                 a[42], a[43], a[44], a[45], a[46], a[47]);
-    {
-      const double gen = a[51] - a[49] - a[50] - a[52];     // (the loop over a window's positions, less its stretches)
-      std::fprintf(stderr, "  k_dp5_spec generic windows, cycles: headers %.3g, run stretches: whole windows %.3g (%.0f per position), others %.3g (%.0f); stretches of other rows %.3g (%.0f); the general step %.3g (%.0f per position incl. shortcuts)\n",
-                   a[48], a[49], a[49] / (a[42] + 1e-9), a[50], a[50] / (a[43] + a[44] + 1e-9), a[52], a[52] / (a[53] + 1e-9), gen, gen / (a[45] + a[46] + a[33] + 1e-9));
-    }
-    const char* nm[5] = {"32", "16", "8", "8 (two registers)", "generic"};
-    for (int i = 0; i < 5; ++i)
-      std::fprintf(stderr, "  path %-18s %5.1f%% of positions, %6.1f cycles/position\n", nm[i], 100.0 * a[6 + 2 * i] / a[4],
-                   a[5 + 2 * i] / (a[6 + 2 * i] + 1e-9));
-    for (int w = 0; w < 2; ++w)
-      std::fprintf(stderr, "  producer wave %d, cycles/step: walk %.0f ring %.0f tiles %.0f barrier %.0f\n", w + 1,
-                   a[16 + 8 * w] / a[0], a[17 + 8 * w] / a[0], a[18 + 8 * w] / a[0], a[19 + 8 * w] / a[0]);
-  }
+  if (t->d_prof) return ReportSqueezeProf(t, ksec, segstats);
   return 0;
 }
 
@@ -2553,48 +2448,6 @@ int zmx_hash_links_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* s
   if (t->links_partial) return FailMsg("zmx_hash_links_download: tables built from a parent hold the hash arrays only near the block ends");
   const BlockDesc& d = t->blocks[block];
   const size_t n = static_cast<size_t>(d.inend - d.ws);
-  if (t->buckets) {
-    // k_bucket's arrays, read back as the reference's links: the previous position of the same hash value is the
-    // entry below in the chunk's order, or the last of that value's bucket in the previous chunk — if it is
-    // less than 32768 back (hash.c:110-114).  Every array of the structure is read here: sorted, rank, bucket.
-    if (n) HIPCHK(hipMemcpy(same, t->d_same16 + d.reg_off, n * sizeof(u16), hipMemcpyDeviceToHost));
-    const size_t nch = (n + BK_CH - 1) / BK_CH;
-    std::vector<u16> srt(n), rnk(n);
-    std::vector<u32> bkt(nch * 32768u);
-    for (int h = 0; h < 2; ++h) {
-      uint16_t* prev = h == 0 ? prev1 : prev2;
-      if (n) {
-        HIPCHK(hipMemcpy(srt.data(), t->d_sorted[h] + d.reg_off, n * sizeof(u16), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(rnk.data(), t->d_rank[h] + d.reg_off, n * sizeof(u16), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(bkt.data(), t->d_bucket[h] + static_cast<size_t>(t->chunk_base[block]) * 32768u, bkt.size() * sizeof(u32),
-                         hipMemcpyDeviceToHost));
-      }
-      for (size_t k = 0; k < n; ++k) {
-        const size_t cch = k / BK_CH, off = k % BK_CH;
-        const unsigned char* in = c->h_in + d.ws;
-        const u32 b0 = in[k], b1 = k + 1 < n ? in[k + 1] : 0u, b2 = k + 2 < n ? in[k + 2] : 0u;
-        u32 key = ((b0 << 10) ^ (b1 << 5) ^ b2) & 32767u;
-        if (h) key ^= (static_cast<u32>(same[k]) - 3u) & 255u;
-        const u32 e = bkt[cch * 32768u + key];
-        const u32 r = rnk[k];
-        if (srt[cch * BK_CH + r] != off || r < (e & 0xffffu) || r >= (e >> 16)) {
-          return FailMsg("zmx_hash_links_download: sorted / rank / bucket disagree at region position " + std::to_string(k));
-        }
-        u32 dist = 0;
-        if (r > (e & 0xffffu)) {
-          dist = static_cast<u32>(off) - srt[cch * BK_CH + r - 1];
-        } else if (cch > 0) {
-          const u32 ep = bkt[(cch - 1) * 32768u + key];
-          if ((ep >> 16) > (ep & 0xffffu)) {
-            const u32 offp = srt[(cch - 1) * BK_CH + (ep >> 16) - 1];
-            if (offp > off) dist = BK_CH + static_cast<u32>(off) - offp;
-          }
-        }
-        prev[k] = static_cast<uint16_t>(dist);
-      }
-    }
-    return 0;
-  }
   std::vector<ushort4> lk(n);
   if (n) HIPCHK(hipMemcpy(lk.data(), t->d_links + d.reg_off, n * sizeof(ushort4), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < n; ++i) {
