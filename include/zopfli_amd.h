@@ -207,7 +207,9 @@ int zmx_lz77_greedy(zmx_ctx* ctx, zmx_tables* tables, int slot, uint32_t* nsym, 
 /* One LZ77OptimalRun (squeeze.c:429): GetBestLengths (:217) forward DP with the
  * given per-block cost model, TraceBackwards (:317), FollowPath (:338).
  * cost[b*ZMX_HIST..] = ll_symbols[288] then d_symbols[32] in bits, mincost[b] =
- * GetCostModelMinCost (:163).  slot[b] selects the store written for block b. */
+ * GetCostModelMinCost (:163).  slot[b] selects the store written for block b.
+ * The oracle defines the meaning of any other mincost[b]: GetBestLengths with the mincost it is given (:293 skips an
+ * edge of length k at j when costs[j + k] <= mincost + costs[j], with exactly that value). */
 int zmx_squeeze_run(zmx_ctx* ctx, zmx_tables* tables, const double* cost, const double* mincost,
                     const int32_t* slot, uint32_t* nsym, uint32_t* hist);
 

@@ -1,6 +1,9 @@
 """Run by tests/test_gpu_parity.py::test_chain_task_paths in a subprocess (the task geometry of the chain
 kernels is read from the environment once per process): three chained squeeze runs per case against the
-CPU oracle, then one JSON line with how the chain's tasks fared (zmx_last_seg_stats)."""
+CPU oracle, then one JSON line with how the chain's tasks fared (zmx_last_seg_stats).
+SEG_PROBE_MINCOST=<delta> (tests/test_gpu_mincost_edges.py): two chained runs on a class T and a class Z case with
+mincost = GetCostModelMinCost + delta, so that match weights lie below it and the positions k_badscan marks go
+through whatever task geometry the environment sets."""
 import json
 import os
 import sys
@@ -42,9 +45,19 @@ CASES = [
 ]
 
 
+def mincost_cases(delta):
+    """(class, size, blocks, delta) of the SEG_PROBE_MINCOST mode; class Z shows no difference below delta 10."""
+    return [("T", 120000, [(0, 70000), (70000, 120000)], delta), ("Z", 150000, [(0, 150000)], max(delta, 10.0))]
+
+
 def main():
     global CASES
     dyadic = os.environ.get("SEG_PROBE_COSTS") == "dyadic"
+    inflate = {}
+    if os.environ.get("SEG_PROBE_MINCOST"):
+        mc = mincost_cases(float(os.environ["SEG_PROBE_MINCOST"]))
+        CASES = [c[:3] for c in mc]
+        inflate = {c[0]: c[3] for c in mc}
     if dyadic:   # one long block: its costs pass 2^20 bits, through every binade the weights can tie in
         CASES = [("T", 400000, [(0, 400000)]), ("X", 300000, [(10000, 300000)])]
     if os.environ.get("SEG_PROBE_CASES"):
@@ -58,13 +71,13 @@ def main():
         nb = len(blocks)
         nsym, hist = t.greedy(0)
         tables = [ol.OracleTable(data, s, e) for (s, e) in blocks]
-        for it in range(3):
+        for it in range(2 if inflate else 3):
             cost = np.zeros((nb, 320))
             mincost = np.zeros(nb)
             for b in range(nb):
                 ll, d = dyadic_costs(hist[b]) if dyadic else ol.entropy_costs(hist[b])
                 cost[b, :288], cost[b, 288:] = ll, d
-                mincost[b] = ol.model_min_cost(ll, d)
+                mincost[b] = ol.model_min_cost(ll, d) + inflate.get(cls, 0.0)
             nsym, hist = t.squeeze_run(cost, mincost, np.full(nb, it & 1, dtype=np.int32))
             for b, (s, e) in enumerate(blocks):
                 la, oll, odd = tables[b].squeeze_run(cost[b, :288], cost[b, 288:], mincost[b])

@@ -533,9 +533,10 @@ class Tables:
         self.ctx._check(fn(self.ctx.handle, self.handle, n, ctypes.cast(b, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
                            ctypes.cast(k, ctypes.c_void_p)), "zmx_verify_stores")
 
-    def encode_blocks(self, jobs, codes):
+    def encode_blocks(self, jobs, codes, slack=False):
         """zmx_encode_blocks: jobs = [(block, slot, nsym, bit_start, nbits)], codes = uint32 [njobs, 320]
-        (reversed code | length << 16).  Returns one bytes object per job (header bits zero)."""
+        (reversed code | length << 16).  Returns one bytes object per job (header bits zero); slack=True: with the 8
+        bytes allocated behind each output, which the library must leave alone."""
         import numpy as np
 
         class Job(ctypes.Structure):
@@ -551,6 +552,8 @@ class Tables:
         fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         self.ctx._check(fn(self.ctx.handle, self.handle, n, ctypes.cast(arr, ctypes.c_void_p),
                            codes.ctypes.data_as(ctypes.c_void_p), ctypes.cast(ptrs, ctypes.c_void_p)), "zmx_encode_blocks")
+        if slack:
+            return [bytes(b) for b in bufs]
         return [bytes(b[:(int(j[3]) + int(j[4]) + 7) // 8]) for b, j in zip(bufs, jobs)]
 
     def find_longest_match(self, block, pos):

@@ -193,8 +193,9 @@ struct VerifyParams {
   const VerifyJob* jobs;
   const u8* in;
   const u32* store[2];
-  u32* bad;         // [jobs][2]: 1 + index of a symbol that fails, and what was wrong (1: length / distance out of
-                    // range, 2: bytes differ, 3: the symbols do not add up to the block)
+  u32* bad;         // [jobs][2], word 0 set to all ones by the host: (1 + index) << 2 | reason of the FIRST symbol that
+                    // fails (1: length / distance out of range, 2: bytes differ, 3: the symbols do not add up to the
+                    // block, index = nsym: it comes after every symbol's own failure)
 };
 
 __global__ __launch_bounds__(256) void k_verify(VerifyParams P) {
@@ -231,11 +232,12 @@ __global__ __launch_bounds__(256) void k_verify(VerifyParams P) {
           if (P.in[pos + k] != P.in[pos + k - dist]) { why = 2; break; }
         }
       }
-      // (symbol and reason in ONE word, so that the reason reported is the reported symbol's: (i + 1) << 2 | why)
-      if (why) atomicMax(&P.bad[2 * blockIdx.x], ((i + 1) << 2) | why);
+      // (symbol and reason in ONE word, so that the reason reported is the reported symbol's: (i + 1) << 2 | why;
+      // the smallest one is the first symbol that fails, as the header promises)
+      if (why) atomicMin(&P.bad[2 * blockIdx.x], ((i + 1) << 2) | why);
     }
     base += tot;
     __syncthreads();
   }
-  if (threadIdx.x == 0 && base != J.inend) atomicMax(&P.bad[2 * blockIdx.x], ((J.nsym + 1) << 2) | 3u);
+  if (threadIdx.x == 0 && base != J.inend) atomicMin(&P.bad[2 * blockIdx.x], ((J.nsym + 1) << 2) | 3u);
 }

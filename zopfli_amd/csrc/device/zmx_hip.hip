@@ -2054,7 +2054,7 @@ int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, 
   HIPCHK(tmp.AllocT(&d_jobs, n, "d_jobs"));
   HIPCHK(tmp.AllocT(&d_bad, 2 * n, "d_bad"));
   HIPCHK(hipMemcpyAsync(d_jobs, vj.data(), n * sizeof(VerifyJob), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(d_bad, 0, 2 * n * sizeof(u32), c->stream));
+  HIPCHK(hipMemsetAsync(d_bad, 0xff, 2 * n * sizeof(u32), c->stream));    // k_verify keeps the minimum: the first failure
   VerifyParams P;
   P.jobs = d_jobs;
   P.in = c->d_in;
@@ -2068,7 +2068,7 @@ int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, 
   HIPCHK(hipMemcpyAsync(bad.data(), d_bad, 2 * n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (size_t i = 0; i < n; ++i) {
-    if (bad[2 * i] == 0) continue;
+    if (bad[2 * i] == 0xffffffffu) continue;
     static const char* why[4] = {"", "length or distance out of range", "the bytes it stands for are not the input's", "the symbols do not add up to the block"};
     char msg[200];
     std::snprintf(msg, sizeof(msg), "zmx_verify_stores: block %zu, symbol %u: %s", block[i], (bad[2 * i] >> 2) - 1, why[bad[2 * i] & 3]);
