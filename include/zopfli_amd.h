@@ -463,6 +463,12 @@ int zmx_ctx_set_priority(zmx_ctx* ctx, int level);
  * (as for any other value), and ZOPFLI_AMD_MATCH=3 or 4 falls back to 2. */
 int zmx_set_match_kernel(int kernel);
 
+/* k_match2 hands out a tile's 2048 positions longest walk first (on, the default, or ZOPFLI_AMD_MATCH_ORDER=1), by the
+ * estimate k_hits keeps for every position, or in ascending order (0).  The records are the same either way; with the
+ * order on, k_hits also runs when kernel 2 is forced.  Tables built from a parent are always built in ascending
+ * order.  An A/B and test hook; always returns 0. */
+int zmx_set_match_order(int on);
+
 /* The chain's tasks (GetBestLengths cut into verified stretches, zmx_dp4.h) since the last Zopfli* /
  * zmx_deflate_range call started: [0] tasks [1] accepted as computed [2] re-run because the entry
  * state differed [3] because the guessed level left the binade [4] because a weight could tie

@@ -108,6 +108,9 @@ def bind(lib):
     lib.zmx_last_seg_stats.argtypes = [P(ctypes.c_double)]
     lib.zmx_last_match_timing.argtypes = [P(ctypes.c_double)]
     lib.zmx_set_match_kernel.argtypes = [ctypes.c_int]
+    if hasattr(lib, "zmx_set_match_order"):   # (absent from an older build selected by ZOPFLI_AMD_LIB for an A/B)
+        lib.zmx_set_match_order.argtypes = [ctypes.c_int]
+        lib.zmx_set_match_order.restype = ctypes.c_int
     lib.zmx_dist_unique_id.argtypes = [ctypes.c_char_p]
     lib.zmx_dist_init.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, P(vp)]
     lib.zmx_dist_destroy.argtypes = [vp]

@@ -357,6 +357,19 @@ int MatchKernel() {
   }
   return v;
 }
+// k_match2 hands out a tile's positions longest walk first, by k_hits' estimates (ZOPFLI_AMD_MATCH_ORDER /
+// zmx_set_match_order; 0 = in ascending order).  Whole builds only: a table built from a parent recomputes a few
+// tiles, for which nobody runs k_hits.
+std::atomic<int> g_match_order{-1};
+bool MatchOrder() {
+  int v = g_match_order.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = std::getenv("ZOPFLI_AMD_MATCH_ORDER");
+    v = e ? (std::atoi(e) != 0 ? 1 : 0) : 1;
+    g_match_order.store(v, std::memory_order_relaxed);
+  }
+  return v != 0;
+}
 // kernel 0: blocks whose estimated hits per position (k_hits) exceed this take k_match5 (ZOPFLI_AMD_MATCH_HITS)
 u64 MatchAutoHits() {
   static const u64 v = [] { const char* e = std::getenv("ZOPFLI_AMD_MATCH_HITS"); return e ? static_cast<u64>(std::max<long>(0, std::atol(e))) : 300ull; }();
@@ -513,6 +526,11 @@ int zmx_set_match_kernel(int kernel) {
   if (kernel == 3 || kernel == 4) return FailMsg("zmx_set_match_kernel: kernels 3 and 4 were removed");
   if (kernel != 0 && kernel != 2 && kernel != 5) return FailMsg("zmx_set_match_kernel: 0, 2 or 5");
   g_match_kernel.store(kernel, std::memory_order_relaxed);
+  return 0;
+}
+
+int zmx_set_match_order(int on) {
+  g_match_order.store(on != 0 ? 1 : 0, std::memory_order_relaxed);
   return 0;
 }
 
@@ -971,6 +989,7 @@ struct MatchBuild {
   u32* d_tot12 = nullptr;
   unsigned long long* d_energy = nullptr;   // k_hits (kernel 0 = per block: k_match5 where the chains are long)
   u32* d_cmax = nullptr;                    // k_hits: the chunks' largest classes (k_rank2)
+  u8* d_est = nullptr;                      // k_hits: every position's class size as 32 - clz (k_match2's order), or null
   bool skip_any = false, skip_all = false;  // some / all blocks of this build take k_match5
   double skip_positions = 0;                // positions of those blocks
   unsigned long long* d_m5stats = nullptr;  // k_match5's per-wave sums
@@ -991,7 +1010,9 @@ static int LaunchHash(zmx_ctx* c, zmx_tables* t, int mk, u64 max_l, const u64* d
   const dim3 g2(static_cast<unsigned>((max_l + CH_EMIT - 1) / CH_EMIT), static_cast<unsigned>(nb), 2);
   hipLaunchKernelGGL(k_chain, g2, dim3(64), CH_LDS_BYTES, c->stream, c->d_in, t->d_blocks, t->d_same16, t->d_links, d_link_lo);
   KCHK(c, "k_chain");
-  if ((mk == 5 || mk == 0) && d_link_lo == nullptr) {
+  const bool walks = mk == 5 || mk == 0;     // k_hits decides or k_rank2 needs its maxima
+  const bool order = mk != 5 && MatchOrder();  // k_match2 runs and wants the estimates (kernel 2 too: its A/B with 0 stays like for like)
+  if ((walks || order) && d_link_lo == nullptr) {
     // The skip-walk (k_match5) for the blocks whose chains are long: k_hits estimates the hits per position the
     // reference's walk would make, block by block; kernel 5 forces it for every block.  (Whole blocks only: a
     // table built from a parent recomputes a few tiles with k_match2.)
@@ -1002,19 +1023,22 @@ static int LaunchHash(zmx_ctx* c, zmx_tables* t, int mk, u64 max_l, const u64* d
       // k_hits: the blocks' hit estimates (kernel 0: which walk a block gets) and the chunks' largest classes (k_rank2:
       // where the 8192-hit cap can bind)
       if (!m.d_energy) HIPCHK(m.hash_tmp.AllocT(&m.d_energy, nb, "d_energy"));
-      if (!m.d_cmax) HIPCHK(m.hash_tmp.AllocT(&m.d_cmax, nb * static_cast<size_t>(hits_chunks) + 1, "d_cmax"));
+      if (walks && !m.d_cmax) HIPCHK(m.hash_tmp.AllocT(&m.d_cmax, nb * static_cast<size_t>(hits_chunks) + 1, "d_cmax"));
+      if (order && !m.d_est) HIPCHK(m.hash_tmp.AllocT(&m.d_est, reg_off, "d_est"));
       HIPCHK(hipMemsetAsync(m.d_energy, 0, nb * sizeof(unsigned long long), c->stream));
-      HIPCHK(hipMemsetAsync(m.d_cmax, 0, (nb * static_cast<size_t>(hits_chunks) + 1) * sizeof(u32), c->stream));
+      if (m.d_cmax) HIPCHK(hipMemsetAsync(m.d_cmax, 0, (nb * static_cast<size_t>(hits_chunks) + 1) * sizeof(u32), c->stream));
       HitsParams hp;
       hp.in = c->d_in;
       hp.blocks = t->d_blocks;
       hp.same16 = t->d_same16;
       hp.energy = m.d_energy;
       hp.cmax = m.d_cmax;
+      hp.est = m.d_est;
       const dim3 g5(hits_chunks, static_cast<unsigned>(nb));
       hipLaunchKernelGGL(k_hits, g5, dim3(RK_THREADS), 0, c->stream, hp);
       KCHK(c, "k_hits");
     }
+    if (!walks) return 0;
     if (mk == 0) {
       std::vector<unsigned long long> energy(nb);
       HIPCHK(hipMemcpyAsync(energy.data(), m.d_energy, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -1099,6 +1123,7 @@ static int LaunchMatch(zmx_ctx* c, zmx_tables* t, int mk, MatchBuild& m, u32* po
   mp.tile_list = d_tiles;
   mp.skip_energy = nullptr;
   mp.skip_thr = 0;
+  mp.est = d_tiles == nullptr ? m.d_est : nullptr;
   if ((mk == 5 || mk == 0) && d_tiles == nullptr && m.skip_any) {
     if (!c->d_scratch5) HIPCHK(PoolAllocT(c, &c->d_scratch5, static_cast<size_t>(kMatchGrid5) * M5_THREADS * SCRATCH_CPS, "d_scratch5"));
     Match5Params q;
@@ -1267,6 +1292,14 @@ static int BuildMatchRecords(zmx_ctx* c, zmx_tables* t, zmx_tables* parent, int 
                    "position, %.1f of 64 lanes with a hit per wave-loop iteration; %.1f SIMD cycles per hit (2.4 GHz, 1024 SIMDs)\n", mk == 5 || mk == 0 ? "k_match5 / k_match2 (hits = entries touched)" : "k_match2", ms_match, pos,
                    static_cast<double>(hc[0]) / pos, static_cast<double>(hc[0]) / static_cast<double>(hc[1] ? hc[1] : 1),
                    ms_match * 1e-3 * 2.4e9 * 1024 / static_cast<double>(hc[0] ? hc[0] : 1));
+      if (mk != 5) {
+        // what the runtime says of the instantiation that ships (kMatchGrid counts on 4: the window and the order's 4 KB in LDS)
+        int wgs = 0;
+        if (MatchFilter()) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_match2<false, true>, M2_THREADS, 0));
+        else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_match2<false, false>, M2_THREADS, 0));
+        std::fprintf(stderr, "k_match2: %d workgroups of %u threads resident per CU; positions handed out %s\n", wgs, M2_THREADS,
+                     m.d_est ? "by k_hits' estimate, longest first" : "in ascending order");
+      }
     }
   }
   return 0;

@@ -271,12 +271,20 @@ __global__ __launch_bounds__(64) void k_chain(const u8* __restrict__ in, const B
 //     32 KiB window + tile + 258 bytes are staged in LDS; each lane walks the
 //     hash chain of one position at a time and refills from the tile queue as
 //     soon as its walk ends, so long walks do not idle the wave.
+//     The queue holds the tile's positions longest walk first when k_hits left
+//     its estimates (MatchParams::est, zmx_match2.h), else in ascending order.
 // ----------------------------------------------------------------------------
+#ifndef MT                                     // (-DMT=..., -DM_XCD_GROUP=..., -DMATCH_BATCH=...: tools/build_variant.py's A/B)
 #define MT 2048u
+#endif
 #define MWIN_BYTES (32768u + MT + 288u)     // + slack for 16-byte alignment and 4-byte compares
 #define SCRATCH_CPS 256u                      // per-lane overflow change points
+#ifndef M_XCD_GROUP
 #define M_XCD_GROUP 16u                        // consecutive tiles that go to one XCD (k_match*)
+#endif
+#ifndef MATCH_BATCH
 #define MATCH_BATCH 8u                        // lanes that wait for a record write / a new position before the wave serves them
+#endif
 
 struct MatchParams {
   const u8* in;
@@ -293,6 +301,8 @@ struct MatchParams {
   const u32* tile_list;  // optional: the tiles to do (total_tiles entries); null = all of them
   const unsigned long long* skip_energy;   // optional (k_hits): blocks whose estimate exceeds skip_thr x positions are k_match5's
   u64 skip_thr;
+  const u8* est = nullptr;   // optional (k_hits, indexed like the links): k_match2 hands out a tile's positions by descending
+                             // estimate of their walk; null = in ascending order
 };
 
 // (ds_read_u8: the byte itself, no shifting around a 32-bit read)

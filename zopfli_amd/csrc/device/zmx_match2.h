@@ -37,12 +37,47 @@ __device__ __forceinline__ u64 m2_lds_u64(const u32* win, u32 byte_off) {
   return x;
 }
 
+// ORDER (MatchParams::est set): the tile's positions are handed out longest walk first.  Hits per position spread
+// 25-fold inside a tile (median 22, p90 481 on text, tools/match_hits_study.c); in ascending order whoever draws a
+// 500-hit position late holds the workgroup and its window while the other lanes wait.  k_hits' estimate — the size
+// of the position's val2 class in its chunk, as 32 - clz — orders them as well as the true hit counts would.  A
+// counting sort by descending bucket into s_order[]: each wave adds the lanes of a bucket with one ballot and one
+// LDS atomic (the order of the waves inside a bucket is whatever the atomics make it: results do not depend on it).
+// Measured (ZOPFLI_AMD_PROF, class T): 58 instead of 36 of 64 lanes take a hit per iteration of the wave loop, and the
+// launch time follows the iterations ("Roofline bookkeeping"; profiles/o7_match_order.txt).
+// s_order[]'s 4 KB leave four workgroups resident per CU (39 364 B each of the CU's 160 KB), as before.
+#define M2_NBKT 17u                       // buckets 0 .. 16 (a class has at most 32768 members)
+#define M2_PER (MT / M2_THREADS)          // positions of a tile per thread of the sort
+static_assert(MT % M2_THREADS == 0 && M2_PER <= 8 && MT <= 65536, "s_order holds 16-bit indices of whole rounds of the workgroup");
+
+// The lanes with `valid` add themselves to ctr[b], one atomic per wave and distinct b: returns the lane's place.
+__device__ __forceinline__ u32 m2_wave_take(u32 b, bool valid, u32* ctr) {
+  u32 slot = 0;
+  u64 todo = __ballot(valid);
+  while (todo != 0) {
+    const u32 leader = (u32)__ffsll((unsigned long long)todo) - 1u;
+    const u32 v = (u32)__builtin_amdgcn_readlane((int)b, (int)leader);
+    const u64 m = __ballot(valid && b == v);
+    const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
+    u32 base = 0;
+    if (valid && b == v && rank == 0) base = atomicAdd(&ctr[v], (u32)__popcll(m));   // the leader: the first lane of m
+    base = (u32)__builtin_amdgcn_readlane((int)base, (int)leader);
+    if (valid && b == v) slot = base + rank;
+    todo &= ~m;
+  }
+  return slot;
+}
+
 template <bool PROF, bool FILT>
 __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match2(MatchParams P) {
   __shared__ __align__(16) u32 win[MWIN_BYTES / 4 + 4];
   __shared__ u32 s_next, s_tile;
+  // 4 KB beside the window's 35 120 B: four workgroups of a CU take 157.4 KB of its 160 KB
+  __shared__ u16 s_order[MT];
+  __shared__ u32 s_bkt[M2_NBKT], s_cur[M2_NBKT];
 
   const u32 tid = threadIdx.x;
+  const bool ordered = P.est != nullptr;
   const u32 xcd = blockIdx.x & 7;
   u32* my_scratch = P.scratch + ((u64)blockIdx.x * M2_THREADS + tid) * SCRATCH_CPS;
 
@@ -56,6 +91,7 @@ __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match
       s_tile = ((k / M_XCD_GROUP) * 8u + xcd) * M_XCD_GROUP + (k % M_XCD_GROUP);
       s_next = 0;
     }
+    if (ordered && tid < M2_NBKT) s_bkt[tid] = 0;
     __syncthreads();
     if (s_tile >= P.total_tiles) break;
     const u32 tile = P.tile_list ? P.tile_list[s_tile] : s_tile;
@@ -82,7 +118,34 @@ __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match
       if (a >= 0) x = *reinterpret_cast<const uint4*>(P.in + a);  // input is padded past its end
       reinterpret_cast<uint4*>(win)[v] = x;
     }
+    u64 bk = 0;      // the buckets of this thread's M2_PER positions, a byte each
+    if (ordered) {   // count the buckets (index of the estimate: reg_off + abs - ws, like the links)
+      const u8* est = P.est + bd.reg_off + (p0 - bd.ws);
+#pragma unroll 1   // (unrolled, the four indices are kept in registers through the walk, which has none to spare)
+      for (u32 k = 0; k < M2_PER; ++k) {
+        const u32 idx = k * M2_THREADS + tid;
+        const u32 e = idx < ntile ? (u32)est[idx] : 0u;
+        const u32 b = e < M2_NBKT ? e : M2_NBKT - 1u;
+        bk |= (u64)b << (8u * k);
+        (void)m2_wave_take(b, idx < ntile, s_bkt);
+      }
+    }
     __syncthreads();
+    if (ordered) {
+      if (tid < M2_NBKT) {   // descending: bucket b starts behind all the larger ones
+        u32 s = 0;
+        for (u32 u = tid + 1; u < M2_NBKT; ++u) s += s_bkt[u];
+        s_cur[tid] = s;
+      }
+      __syncthreads();
+#pragma unroll 1   // (unrolled, the four indices are kept in registers through the walk, which has none to spare)
+      for (u32 k = 0; k < M2_PER; ++k) {
+        const u32 idx = k * M2_THREADS + tid;
+        const u32 slot = m2_wave_take((u32)(bk >> (8u * k)) & 255u, idx < ntile, s_cur);
+        if (idx < ntile) s_order[slot] = (u16)idx;
+      }
+      __syncthreads();
+    }
 
     // index: abs - ws; {prev1 | prev2 << 16, same | ..}.  The base is the same for the whole workgroup: as a scalar
     // pair the walk's one dependent load takes a 32-bit lane offset instead of 64-bit address arithmetic per step.
@@ -151,10 +214,11 @@ __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match
           reinterpret_cast<uint4*>(rec)[1] = r1;
         }
         if (st == M2_IDLE) {
-          const u32 idx = atomicAdd(&s_next, 1u);
+          u32 idx = atomicAdd(&s_next, 1u);
           if (idx >= ntile) {
             st = M2_DONE;
           } else {
+            if (ordered) idx = s_order[idx];
             lp = lp0 + idx;
             li = li0 + idx;
             size_rem = rem0 - idx;               // saturated: only compared with 3 and 258

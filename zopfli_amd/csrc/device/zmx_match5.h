@@ -215,6 +215,7 @@ __global__ __launch_bounds__(64) void k_levels(LevelParams P) {
 // their second chain: per position that is the chain length the walk has in front of it — 100 on text, 186 on
 // markup, 2 000 on PNG-like and two-symbol data, 45 on long runs, within a few percent of the hits the
 // instrumented reference counts.  energy[b] > threshold x positions sends block b to the skip-walk.
+// The class sizes themselves are kept too (est, a byte per position) when k_match2 wants them for its order of service.
 // ----------------------------------------------------------------------------
 struct HitsParams {
   const u8* in;
@@ -222,6 +223,8 @@ struct HitsParams {
   const u16* same16;
   unsigned long long* energy;
   u32* cmax;          // [blocks][gridDim.x] the largest class of the chunk: of the 3-byte hash | of val2 << 16 (k_rank2: can the 8192-hit cap bind here?)
+  u8* est = nullptr;  // optional, indexed like same16: 32 - clz(size of the position's val2 class in its chunk), 1 .. 16 — the
+                      // walk the position has in front of it, to the power of two (k_match2 hands out a tile's longest first)
 };
 
 __device__ __forceinline__ u32 rk_val2(u32 bytes, u64 p, u64 L, u32 same) {
@@ -278,6 +281,28 @@ __global__ __launch_bounds__(RK_THREADS) void k_hits(HitsParams P) {
   }
   for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
   if ((tid & 63u) == 0) atomicAdd(&P.energy[blockIdx.y], sum);
+  if (P.est != nullptr) {
+    // every position's own class size, while the counts are still there (the chunk's bytes and runs come from L2)
+    u8* est = P.est + bd.reg_off;
+    for (u64 s = e0; s < e1; s += RK_THREADS * 4u) {
+      u32 by[4], sm[4];
+#pragma unroll
+      for (u32 u = 0; u < 4; ++u) {
+        const u64 p = s + RK_THREADS * u + tid;
+        by[u] = p < e1 ? rk_load_u32(base + p) : 0u;
+        sm[u] = p < e1 ? (u32)same[p] : 0u;
+      }
+#pragma unroll
+      for (u32 u = 0; u < 4; ++u) {
+        const u64 p = s + RK_THREADS * u + tid;
+        if (p < e1) {
+          const u32 key = rk_val2(by[u], p, L, sm[u]);
+          const u32 n = (cnt[key >> 1] >> (16u * (key & 1u))) & 0xffffu;   // >= 1: the position itself
+          est[p] = (u8)(32u - (u32)__clz((int)n));
+        }
+      }
+    }
+  }
   if (P.cmax == nullptr) return;
   // The same count for the 3-byte hash (the first chain's classes), and the largest class of either kind: a position's
   // walk visits at most the members of its two classes in its own chunk and the one before (a superset of its window),
