@@ -311,6 +311,18 @@ int zmx_hash_links_download(zmx_ctx* ctx, zmx_tables* tables, size_t block, uint
 /* Parity probe: length_array[0..blocksize] of the last zmx_squeeze_run. */
 int zmx_length_array_download(zmx_ctx* ctx, zmx_tables* tables, size_t block, uint16_t* out);
 
+/* Test entry: TraceBackwards + FollowPath (squeeze.c:317, :338) over length arrays the CALLER hands in — the tail of
+ * zmx_squeeze_run (k_trace_exits, k_trace_link, k_trace_emit and the result copy: the same code) without the DP in
+ * front of it.  length_arrays[b] has entries[b] = blocksize + 1 cells, as zmx_length_array_download returns them; they
+ * replace the tables' own; slot[b], nsym, hist and the stores are as after zmx_squeeze_run.  Refused on the host, before
+ * any launch (ZMX_ERR_REFUSED): trimmed or matches-only tables, nblocks or an entries[b] that is not the tables', a
+ * slot that is not 0 or 1, a cell h that holds 2 or more than min(h, 258).  A cell may hold 0 (GetBestLengths' "never
+ * reached"): the device judges whether the path meets one (flag 0x2) or takes a length the match record at its start
+ * does not hold (flag 0x4), and the call fails with "device consistency flags 0x..." (ZMX_ERR_DEVICE) as
+ * zmx_squeeze_run does; the next call on the same tables is not affected. */
+int zmx_trace_length_arrays(zmx_ctx* ctx, zmx_tables* tables, size_t nblocks, const uint16_t* const* length_arrays,
+                            const size_t* entries, const int32_t* slot, uint32_t* nsym, uint32_t* hist);
+
 /* -------- f-1 of SURVEY 8: the block-split search's cost function on the device
  *
  * ZopfliCalculateBlockSizeAutoType (deflate.c:610-621) of MANY ranges of LZ77 symbol sequences at once: what every

@@ -188,6 +188,20 @@ void zo_find_longest_match(const zo_table* t, size_t pos, unsigned short* sublen
   }
 }
 
+size_t zo_records(const zo_table* t, unsigned short* length, unsigned short* dist, size_t* cp_off) {
+  const size_t B = t->inend - t->instart;
+  memcpy(length, t->length, B * sizeof(unsigned short));
+  memcpy(dist, t->dist, B * sizeof(unsigned short));
+  memcpy(cp_off, t->cp_off, (B + 1) * sizeof(size_t));
+  return t->cp_n;
+}
+
+void zo_change_points(const zo_table* t, unsigned short* cp_len, unsigned short* cp_dist) {
+  if (t->cp_n == 0) return;
+  memcpy(cp_len, t->cp_len, t->cp_n * sizeof(unsigned short));
+  memcpy(cp_dist, t->cp_dist, t->cp_n * sizeof(unsigned short));
+}
+
 /* distance used to reach `len` at block position i = sublen[len] */
 static unsigned short zo_dist_for(const zo_table* t, size_t i, unsigned len) {
   size_t k;

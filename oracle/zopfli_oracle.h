@@ -38,6 +38,13 @@ unsigned short zo_same(const zo_table* t, size_t p);   /* hash.c:116-126 */
 unsigned short zo_prev1(const zo_table* t, size_t p);  /* distance to previous same-hash position, 0 = none */
 unsigned short zo_prev2(const zo_table* t, size_t p);  /* same for the second hash (hash.c:129-135) */
 
+/* The match records of the whole block at once: length[i], dist[i] (what zo_find_longest_match returns for position
+ * instart + i) and cp_off[0 .. B], the offsets of the positions' change points of sublen; returns their total number.
+ * zo_change_points copies those: sublen[l] at position i = cp_dist[k] for the first k in [cp_off[i], cp_off[i + 1])
+ * with cp_len[k] >= l (a first change point of length 2 is kept as the walk found it). */
+size_t zo_records(const zo_table* t, unsigned short* length, unsigned short* dist, size_t* cp_off);
+void zo_change_points(const zo_table* t, unsigned short* cp_len, unsigned short* cp_dist);
+
 /* ZopfliLZ77Greedy — lz77.c:544.  litlens/dists must hold inend-instart entries;
  * returns the number of symbols. */
 size_t zo_greedy(const zo_table* t, unsigned short* litlens, unsigned short* dists);

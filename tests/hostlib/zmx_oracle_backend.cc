@@ -7,6 +7,7 @@
 // libzopfli_amd.so never links this file: its zmx_* symbols come from the HIP
 // device layer only.
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -37,6 +38,7 @@ struct BlockData {
 
 struct zmx_tables {
   std::vector<BlockData> blocks;
+  bool matches_only = false, trimmed = false;   // (what zmx_trace_length_arrays refuses, as the device layer does)
 };
 
 static thread_local std::string g_err;
@@ -106,10 +108,12 @@ int zmx_tables_build(zmx_ctx* ctx, const zmx_block* blocks, size_t nblocks, zmx_
   return 0;
 }
 
-int zmx_tables_trim(zmx_ctx*, zmx_tables*) { return 0; }
+int zmx_tables_trim(zmx_ctx*, zmx_tables* t) { t->trimmed = true; return 0; }
 
 int zmx_tables_build_matches(zmx_ctx* ctx, const zmx_block* blocks, size_t nblocks, zmx_tables** tables) {
-  return zmx_tables_build(ctx, blocks, nblocks, tables);
+  const int rc = zmx_tables_build(ctx, blocks, nblocks, tables);
+  if (rc == 0) (*tables)->matches_only = true;
+  return rc;
 }
 
 int zmx_tables_build_from(zmx_ctx* ctx, zmx_tables*, const zmx_block* blocks, size_t nblocks, zmx_tables** tables) {
@@ -140,6 +144,60 @@ int zmx_squeeze_run(zmx_ctx*, zmx_tables* t, const double* cost, const double* m
     const double* ll = cost + b * ZMX_HIST;
     zo_get_best_lengths(d.table, ll, ll + ZMX_NUM_LL, mincost[b], d.length_array.data());
     d.nsym[s] = zo_trace_follow(d.table, d.length_array.data(), d.litlens[s].data(), d.dists[s].data());
+    nsym[b] = static_cast<uint32_t>(d.nsym[s]);
+    zo_histogram(d.litlens[s].data(), d.dists[s].data(), d.nsym[s], hist + b * ZMX_HIST);
+  }
+  return 0;
+}
+
+// (CPU stand-in for the trace kernels on given length arrays: the device layer's refusals by the same rule, then a plain
+// backward walk over the oracle's table.  Like the device it steps over a 0 as over a 1 and reports it (flag 2), and
+// reports a length the record at the symbol's start does not hold (flag 4).)
+int zmx_trace_length_arrays(zmx_ctx*, zmx_tables* t, size_t nblocks, const uint16_t* const* length_arrays,
+                            const size_t* entries, const int32_t* slot, uint32_t* nsym, uint32_t* hist) {
+  auto refuse = [](const std::string& m) { g_err = g_refused = "zmx_trace_length_arrays: " + m; return -1; };
+  if (t->trimmed) return refuse("these tables were trimmed to their stores (zmx_tables_trim)");
+  if (t->matches_only) return refuse("these tables hold matches only (zmx_tables_build_matches)");
+  if (nblocks != t->blocks.size()) return refuse("one length array per block of the tables");
+  for (size_t b = 0; b < nblocks; ++b) {
+    const size_t B = t->blocks[b].blk.inend - t->blocks[b].blk.instart;
+    if (slot[b] != 0 && slot[b] != 1) return refuse("slot must be 0 or 1");
+    if (entries[b] != B + 1) return refuse("block " + std::to_string(b) + " has " + std::to_string(B) + " + 1 cells, not " + std::to_string(entries[b]));
+    for (size_t h = 0; h <= B; ++h) {
+      const unsigned v = length_arrays[b][h];
+      if (v == 2 || v > (h < 258 ? h : 258)) {
+        return refuse("block " + std::to_string(b) + ", cell " + std::to_string(h) + " holds " + std::to_string(v) + ": no step of a path");
+      }
+    }
+  }
+  unsigned flags = 0;
+  std::vector<std::vector<uint16_t>> path(nblocks);
+  for (size_t b = 0; b < nblocks; ++b) {
+    BlockData& d = t->blocks[b];
+    const size_t B = d.blk.inend - d.blk.instart;
+    d.length_array.assign(length_arrays[b], length_arrays[b] + B + 1);
+    path[b] = d.length_array;
+    for (size_t h = B; h > 0;) {
+      unsigned len = path[b][h];
+      if (len == 0) { flags |= 2u; len = path[b][h] = 1; }
+      if (len >= 3) {
+        uint16_t sublen[259] = {0}, dist = 0, longest = 0;
+        zo_find_longest_match(d.table, d.blk.instart + h - len, sublen, &dist, &longest);
+        if (len > longest || sublen[len] == 0) flags |= 4u;
+      }
+      h -= len;
+    }
+  }
+  if (flags) {
+    char buf[96];
+    std::snprintf(buf, sizeof(buf), "zmx_trace_length_arrays: device consistency flags 0x%x", flags);
+    g_err = buf;
+    return -1;
+  }
+  for (size_t b = 0; b < nblocks; ++b) {
+    BlockData& d = t->blocks[b];
+    const int s = slot[b];
+    d.nsym[s] = zo_trace_follow(d.table, path[b].data(), d.litlens[s].data(), d.dists[s].data());
     nsym[b] = static_cast<uint32_t>(d.nsym[s]);
     zo_histogram(d.litlens[s].data(), d.dists[s].data(), d.nsym[s], hist + b * ZMX_HIST);
   }

@@ -40,6 +40,10 @@ def oracle():
         lib.zo_get_best_lengths.restype = ctypes.c_double
         lib.zo_trace_follow.argtypes = [vp, _u16p, _u16p, _u16p]
         lib.zo_trace_follow.restype = sz
+        lib.zo_records.argtypes = [vp, _u16p, _u16p, ctypes.POINTER(sz)]
+        lib.zo_records.restype = sz
+        lib.zo_change_points.argtypes = [vp, _u16p, _u16p]
+        lib.zo_change_points.restype = None
         lib.zo_histogram.argtypes = [_u16p, _u16p, sz, ctypes.POINTER(ctypes.c_uint32)]
         lib.zo_histogram.restype = None
         _oracle = lib
@@ -77,6 +81,20 @@ class OracleTable:
             for i, p in enumerate(range(ws, self.inend)):
                 a[i] = f(self.h, p)
         return out
+
+    def records(self):
+        """(length[B], dist[B], cp_off[B + 1], cp_len[], cp_dist[]): every position's match record at once; sublen[l]
+        at block position i is cp_dist[k] for the first k in [cp_off[i], cp_off[i + 1]) with cp_len[k] >= l."""
+        B = self.inend - self.instart
+        length = np.zeros(max(B, 1), dtype=np.uint16)
+        dist = np.zeros(max(B, 1), dtype=np.uint16)
+        off = np.zeros(B + 1, dtype=np.uint64)
+        n = self.lib.zo_records(self.h, length.ctypes.data_as(_u16p), dist.ctypes.data_as(_u16p),
+                                off.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
+        cp_len = np.zeros(max(n, 1), dtype=np.uint16)
+        cp_dist = np.zeros(max(n, 1), dtype=np.uint16)
+        self.lib.zo_change_points(self.h, cp_len.ctypes.data_as(_u16p), cp_dist.ctypes.data_as(_u16p))
+        return length[:B], dist[:B], off.astype(np.int64), cp_len[:n], cp_dist[:n]
 
     def greedy(self):
         B = self.inend - self.instart

@@ -514,6 +514,30 @@ class Tables:
                         "zmx_squeeze_run")
         return nsym, hist
 
+    def trace(self, length_arrays, slot):
+        """zmx_trace_length_arrays: the trace kernels of a squeeze run on the given length arrays (one per block,
+        blocksize + 1 cells each) -> (nsym, hist), the symbols in store slot[b] of block b."""
+        import numpy as np
+        nb = len(length_arrays)
+        las = [np.ascontiguousarray(a, dtype=np.uint16) for a in length_arrays]
+        ptrs = (ctypes.c_void_p * max(nb, 1))(*[a.ctypes.data for a in las])
+        entries = (ctypes.c_size_t * max(nb, 1))(*[a.size for a in las])
+        slot = np.ascontiguousarray(slot, dtype=np.int32)
+        if slot.size != nb:
+            raise ValueError("Tables.trace: one slot per length array")
+        nsym = np.zeros(max(nb, len(self.blocks)), dtype=np.uint32)
+        hist = np.zeros((max(nb, len(self.blocks)), ZMX_HIST), dtype=np.uint32)
+        # (bound here, not in bind(): an older build selected by ZOPFLI_AMD_LIB for an A/B still loads)
+        fn = self.ctx.lib.zmx_trace_length_arrays
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self.ctx._check(fn(self.ctx.handle, self.handle, nb, ctypes.cast(ptrs, ctypes.c_void_p),
+                           ctypes.cast(entries, ctypes.c_void_p), slot.ctypes.data_as(ctypes.c_void_p),
+                           nsym.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p)),
+                        "zmx_trace_length_arrays")
+        return nsym[:nb], hist[:nb]
+
     def store(self, block, slot, nsym):
         import numpy as np
         ll = np.zeros(max(int(nsym), 1), dtype=np.uint16)

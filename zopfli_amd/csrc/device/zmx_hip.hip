@@ -1760,6 +1760,65 @@ static int ReportSqueezeProf(zmx_tables* t, const double* ksec, const u32* segst
   return 0;
 }
 
+// The tail of a squeeze run, shared with zmx_trace_length_arrays: TraceBackwards + FollowPath (squeeze.c:317, :338) over
+// la[] as it stands on the device — k_trace_exits, k_trace_link, k_trace_emit (zmx_trace.h) — and the run's results.
+// ONE host round trip: the results travel behind the last kernel and the host waits for the copy (waiting for ev[3]
+// first and only then asking for the copy was two).  The task statistics come along (zeroed by the next run's k_wtab).
+// On success the stores of slot[b] are the blocks' (store_begin) and the histograms are kept for the next run's guess.
+static int TraceAndCollect(zmx_ctx* c, zmx_tables* t, const TraceSegParams& tp, const int32_t* slot, uint32_t* nsym,
+                           uint32_t* hist, bool timing, u32* segstats, const char* who) {
+  const size_t nb = t->nb;
+  const unsigned nblk = static_cast<unsigned>(nb);
+  const unsigned nseg = t->seg_off[nb];
+  if (nseg) hipLaunchKernelGGL(k_trace_exits, dim3(nseg), dim3(TS_THREADS), 0, c->stream, tp);
+  KCHK(c, "k_trace_exits");
+  hipLaunchKernelGGL(k_trace_link, dim3(nblk), dim3(64), 0, c->stream, tp);
+  KCHK(c, "k_trace_link");
+  if (nseg) hipLaunchKernelGGL(k_trace_emit, dim3(nseg), dim3(64), 0, c->stream, tp);
+  KCHK(c, "k_trace_emit");
+  HIPCHK(hipGetLastError());
+  if (timing) HIPCHK(hipEventRecord(c->ev[3], c->stream));
+  HIPCHK(hipMemcpyAsync(t->h_runout, t->d_runout, t->runout_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const u32* o_hist = reinterpret_cast<const u32*>(t->h_runout);
+  const u32* o_nsym = o_hist + nb * ZMX_HIST;
+  const u32* o_stats = o_nsym + nb;
+  const u32* o_flags = o_stats + 8;
+  std::memcpy(hist, o_hist, nb * ZMX_HIST * sizeof(u32));
+  std::memcpy(nsym, o_nsym, nb * sizeof(u32));
+  std::memcpy(segstats, o_stats, 8 * sizeof(u32));
+  if (o_flags[1]) {
+    char buf[128];
+    std::snprintf(buf, sizeof(buf), "%s: device consistency flags 0x%x", who, o_flags[1]);
+    return FailFault(buf);
+  }
+  t->h_hist.assign(hist, hist + nb * ZMX_HIST);
+  t->have_hist = true;
+  for (size_t b = 0; b < nb; ++b) t->store_begin[slot[b]][b] = t->bsize[b] - nsym[b];
+  return 0;
+}
+
+static TraceSegParams TraceParams(const zmx_tables* t) {
+  TraceSegParams tp;
+  tp.blocks = t->d_blocks;
+  tp.seg_off = t->d_seg_off;
+  tp.nb_total = static_cast<u32>(t->nb);
+  tp.recs = t->d_recs;
+  tp.pool = t->d_pool;
+  tp.la = t->d_la;
+  tp.slot = t->d_slot;
+  tp.store0 = t->d_store[0];
+  tp.store1 = t->d_store[1];
+  tp.hist_out = t->d_hist;
+  tp.nsym_out = t->d_nsym;
+  tp.flags = t->d_flags;
+  tp.extab = t->d_extab;
+  tp.seginfo = t->d_seginfo;
+  tp.block0 = 0;
+  tp.seg0 = 0;
+  return tp;
+}
+
 int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double* mincost, const int32_t* slot,
                     uint32_t* nsym, uint32_t* hist) {
   if (t && t->trimmed) return FailMsg("zmx_squeeze_run: these tables were trimmed to their stores (zmx_tables_trim)");
@@ -1865,23 +1924,7 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
   const bool scan_bad = any_below_mincost;
   if (scan_bad || !t->badpos_clean) HIPCHK(hipMemsetAsync(t->d_badpos, 0, t->badpos_words * sizeof(u32), c->stream));
   t->badpos_clean = !scan_bad;
-  TraceSegParams tp;
-  tp.blocks = t->d_blocks;
-  tp.seg_off = t->d_seg_off;
-  tp.nb_total = static_cast<u32>(nb);
-  tp.recs = t->d_recs;
-  tp.pool = t->d_pool;
-  tp.la = t->d_la;
-  tp.slot = t->d_slot;
-  tp.store0 = t->d_store[0];
-  tp.store1 = t->d_store[1];
-  tp.hist_out = t->d_hist;
-  tp.nsym_out = t->d_nsym;
-  tp.flags = t->d_flags;
-  tp.extab = t->d_extab;
-  tp.seginfo = t->d_seginfo;
-  tp.block0 = 0;
-  tp.seg0 = 0;
+  const TraceSegParams tp = TraceParams(t);
   double ksec[3] = {0, 0, 0};
   const bool timing = KernelTiming();
   const dim3 dpdim(64 * (D3_NB + 2));
@@ -1956,43 +1999,15 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
     }
     HIPCHK(hipGetLastError());
     if (timing) HIPCHK(hipEventRecord(c->ev[2], c->stream));
-    const unsigned nseg = t->seg_off[nb];
-    if (nseg) hipLaunchKernelGGL(k_trace_exits, dim3(nseg), dim3(TS_THREADS), 0, c->stream, tp);
-    KCHK(c, "k_trace_exits");
-    hipLaunchKernelGGL(k_trace_link, dim3(nblk), dim3(64), 0, c->stream, tp);
-    KCHK(c, "k_trace_link");
-    if (nseg) hipLaunchKernelGGL(k_trace_emit, dim3(nseg), dim3(64), 0, c->stream, tp);
-    KCHK(c, "k_trace_emit");
-    HIPCHK(hipGetLastError());
-    if (timing) HIPCHK(hipEventRecord(c->ev[3], c->stream));
   }
-  // ONE host round trip per run: the results travel behind the last kernel, the host waits for the copy and reads the
-  // phase times then (waiting for ev[3] first and only then asking for the copy was two).  The task statistics are
-  // zeroed by the next run's k_wtab.
+  // the walk back over length_array, the symbols, and the run's ONE host round trip (TraceAndCollect)
   u32 segstats[8];
-  HIPCHK(hipMemcpyAsync(t->h_runout, t->d_runout, t->runout_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (const int rc = TraceAndCollect(c, t, tp, slot, nsym, hist, timing, segstats, "zmx_squeeze_run")) return rc;
   for (int i = 0; i < 3 && timing; ++i) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
     ksec[i] += ms * 1e-3;
   }
-  {
-    const u32* o_hist = reinterpret_cast<const u32*>(t->h_runout);
-    const u32* o_nsym = o_hist + nb * ZMX_HIST;
-    const u32* o_stats = o_nsym + nb;
-    const u32* o_flags = o_stats + 8;
-    std::memcpy(hist, o_hist, nb * ZMX_HIST * sizeof(u32));
-    std::memcpy(nsym, o_nsym, nb * sizeof(u32));
-    std::memcpy(segstats, o_stats, sizeof(segstats));
-    if (o_flags[1]) {
-      char buf[128];
-      std::snprintf(buf, sizeof(buf), "zmx_squeeze_run: device consistency flags 0x%x", o_flags[1]);
-      return FailFault(buf);
-    }
-  }
-  t->h_hist.assign(hist, hist + nb * ZMX_HIST);
-  t->have_hist = true;
   ++t->squeeze_runs;
   {
     // (thread-local: no lock)
@@ -2001,9 +2016,53 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
     for (int i = 0; i < 7; ++i) g_seg_stats[i] += segstats[i];
     g_seg_stats[7] += static_cast<double>(t->total_b);
   }
-  for (size_t b = 0; b < nb; ++b) t->store_begin[slot[b]][b] = t->bsize[b] - nsym[b];
   if (t->d_prof) return ReportSqueezeProf(t, ksec, segstats);
   return 0;
+}
+
+// Test entry: the tail of a squeeze run on length arrays the caller hands in (tests/test_gpu_walk_edges.py).  What the
+// kernels cannot bound themselves is refused here, before any launch: a cell h may hold 0 (GetBestLengths never reached
+// it), 1 or a length 3 .. min(h, 258).  Whether the path meets a 0, or a length its record does not hold, is the
+// device's own business (flags 2 and 4 of k_trace_emit).
+int zmx_trace_length_arrays(zmx_ctx* c, zmx_tables* t, size_t nblocks, const uint16_t* const* length_arrays,
+                            const size_t* entries, const int32_t* slot, uint32_t* nsym, uint32_t* hist) {
+  if (t && t->trimmed) return FailMsg("zmx_trace_length_arrays: these tables were trimmed to their stores (zmx_tables_trim)");
+  if (t->matches_only) return FailMsg("zmx_trace_length_arrays: these tables hold matches only (zmx_tables_build_matches)");
+  if (nblocks != t->nb) return FailMsg("zmx_trace_length_arrays: one length array per block of the tables");
+  const size_t nb = t->nb;
+  if (nb == 0) return 0;
+  char buf[160];
+  for (size_t b = 0; b < nb; ++b) {
+    if (slot[b] != 0 && slot[b] != 1) return FailMsg("zmx_trace_length_arrays: slot must be 0 or 1");
+    if (entries[b] != static_cast<size_t>(t->bsize[b]) + 1) {
+      std::snprintf(buf, sizeof(buf), "zmx_trace_length_arrays: block %zu has %u + 1 cells, not %zu", b, t->bsize[b], entries[b]);
+      return FailMsg(buf);
+    }
+    for (size_t h = 0; h < entries[b]; ++h) {
+      const unsigned v = length_arrays[b][h];
+      if (v == 2 || v > (h < ZMX_MAX_MATCH ? h : ZMX_MAX_MATCH)) {
+        std::snprintf(buf, sizeof(buf), "zmx_trace_length_arrays: block %zu, cell %zu holds %u: no step of a path", b, h, v);
+        return FailMsg(buf);
+      }
+    }
+  }
+  DeviceGuard dev_guard(c->device);
+  HIPCHK(dev_guard.err);
+  // la[] rows as LayoutBlocks laid them out (padded to 8 entries), in one blocking copy
+  const BlockDesc& last = t->blocks[nb - 1];
+  std::vector<u16> rows(last.la_off + ((static_cast<u64>(t->bsize[nb - 1]) + 1 + 7) & ~7ull), 0);
+  for (size_t b = 0; b < nb; ++b) std::memcpy(rows.data() + t->blocks[b].la_off, length_arrays[b], entries[b] * sizeof(u16));
+  HIPCHK(hipMemcpy(t->d_la, rows.data(), rows.size() * sizeof(u16), hipMemcpyHostToDevice));
+  int* h_slot = reinterpret_cast<int*>(t->h_runin + (reinterpret_cast<unsigned char*>(t->d_slot) - t->d_runin));
+  std::memcpy(h_slot, slot, nb * sizeof(int));
+  HIPCHK(hipMemcpyAsync(t->d_slot, h_slot, nb * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  // (the flag words are zeroed when the tables are built and by nothing a squeeze run launches: this call judges its
+  //  own arrays alone, and what it reports must not fail the next call on these tables too)
+  HIPCHK(hipMemsetAsync(t->d_flags, 0, 4 * sizeof(u32), c->stream));
+  u32 segstats[8];
+  const int rc = TraceAndCollect(c, t, TraceParams(t), slot, nsym, hist, false, segstats, "zmx_trace_length_arrays");
+  if (rc) (void)hipMemsetAsync(t->d_flags, 0, 4 * sizeof(u32), c->stream);
+  return rc;
 }
 
 int zmx_store_download(zmx_ctx* c, zmx_tables* t, size_t block, int slot, uint16_t* litlens, uint16_t* dists,
