@@ -44,6 +44,23 @@ struct zmx_tables {
 static thread_local std::string g_err;
 static thread_local std::string g_refused;   // the message of the last refusal: the error is one while g_err still holds it
 
+// The device layer's entry checks (CheckTables, CheckStoreRef in zmx_hip.hip), with its texts.
+static int Refuse(const char* who, const std::string& m) {
+  g_err = g_refused = std::string(who) + ": " + m;
+  return -1;
+}
+static int CheckTables(const char* who, const zmx_tables* t, bool untrimmed, bool with_dp) {
+  if (!t) return Refuse(who, "no tables");
+  if ((untrimmed || with_dp) && t->trimmed) return Refuse(who, "these tables were trimmed to their stores (zmx_tables_trim)");
+  if (with_dp && t->matches_only) return Refuse(who, "these tables hold matches only (zmx_tables_build_matches)");
+  return 0;
+}
+static int CheckStoreRef(const char* who, const zmx_tables* t, size_t block, int slot, size_t nsym) {
+  if (block >= t->blocks.size() || (slot != 0 && slot != 1)) return Refuse(who, "bad block or slot");
+  if (nsym > t->blocks[block].nsym[slot]) return Refuse(who, "nsym exceeds the store");
+  return 0;
+}
+
 extern "C" {
 
 // (ZOPFLI_HOSTTEST_DEVICES pretends to that many devices: the multi-device sharding of api.cc on CPU)
@@ -127,6 +144,7 @@ void zmx_tables_free(zmx_ctx*, zmx_tables* t) {
 }
 
 int zmx_lz77_greedy(zmx_ctx*, zmx_tables* t, int slot, uint32_t* nsym, uint32_t* hist) {
+  if (const int rc = CheckTables("zmx_lz77_greedy", t, true, false)) return rc;
   for (size_t b = 0; b < t->blocks.size(); ++b) {
     BlockData& d = t->blocks[b];
     d.nsym[slot] = zo_greedy(d.table, d.litlens[slot].data(), d.dists[slot].data());
@@ -138,6 +156,7 @@ int zmx_lz77_greedy(zmx_ctx*, zmx_tables* t, int slot, uint32_t* nsym, uint32_t*
 
 int zmx_squeeze_run(zmx_ctx*, zmx_tables* t, const double* cost, const double* mincost, const int32_t* slot,
                     uint32_t* nsym, uint32_t* hist) {
+  if (const int rc = CheckTables("zmx_squeeze_run", t, true, !(t && t->blocks.empty()))) return rc;
   for (size_t b = 0; b < t->blocks.size(); ++b) {
     BlockData& d = t->blocks[b];
     const int s = slot[b];
@@ -155,9 +174,8 @@ int zmx_squeeze_run(zmx_ctx*, zmx_tables* t, const double* cost, const double* m
 // reports a length the record at the symbol's start does not hold (flag 4).)
 int zmx_trace_length_arrays(zmx_ctx*, zmx_tables* t, size_t nblocks, const uint16_t* const* length_arrays,
                             const size_t* entries, const int32_t* slot, uint32_t* nsym, uint32_t* hist) {
-  auto refuse = [](const std::string& m) { g_err = g_refused = "zmx_trace_length_arrays: " + m; return -1; };
-  if (t->trimmed) return refuse("these tables were trimmed to their stores (zmx_tables_trim)");
-  if (t->matches_only) return refuse("these tables hold matches only (zmx_tables_build_matches)");
+  auto refuse = [](const std::string& m) { return Refuse("zmx_trace_length_arrays", m); };
+  if (const int rc = CheckTables("zmx_trace_length_arrays", t, true, true)) return rc;
   if (nblocks != t->blocks.size()) return refuse("one length array per block of the tables");
   for (size_t b = 0; b < nblocks; ++b) {
     const size_t B = t->blocks[b].blk.inend - t->blocks[b].blk.instart;
@@ -206,8 +224,9 @@ int zmx_trace_length_arrays(zmx_ctx*, zmx_tables* t, size_t nblocks, const uint1
 
 int zmx_store_download(zmx_ctx*, zmx_tables* t, size_t block, int slot, uint16_t* litlens, uint16_t* dists,
                        size_t nsym) {
+  if (const int rc = CheckTables("zmx_store_download", t, false, false)) return rc;
+  if (const int rc = CheckStoreRef("zmx_store_download", t, block, slot, nsym)) return rc;
   BlockData& d = t->blocks[block];
-  if (nsym > d.nsym[slot]) return -1;
   std::memcpy(litlens, d.litlens[slot].data(), nsym * 2);
   std::memcpy(dists, d.dists[slot].data(), nsym * 2);
   return 0;
@@ -215,6 +234,10 @@ int zmx_store_download(zmx_ctx*, zmx_tables* t, size_t block, int slot, uint16_t
 
 int zmx_store_download_batch(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, const int32_t* slot,
                              const size_t* nsym, uint16_t* const* litlens, uint16_t* const* dists) {
+  if (const int rc = CheckTables("zmx_store_download_batch", t, false, false)) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    if (const int rc = CheckStoreRef("zmx_store_download_batch", t, block[i], slot[i], nsym[i])) return rc;
+  }
   for (size_t i = 0; i < n; ++i) {
     const int rc = zmx_store_download(c, t, block[i], slot[i], litlens[i], dists[i], nsym[i]);
     if (rc) return rc;
@@ -224,6 +247,10 @@ int zmx_store_download_batch(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* 
 
 // (CPU stand-in for the device's verify pass)
 int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, const int32_t* slot, const size_t* nsym) {
+  if (const int rc = CheckTables("zmx_verify_stores", t, true, false)) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    if (const int rc = CheckStoreRef("zmx_verify_stores", t, block[i], slot[i], nsym[i])) return rc;
+  }
   for (size_t i = 0; i < n; ++i) {
     const BlockData& d = t->blocks[block[i]];
     size_t pos = d.blk.instart;
@@ -288,10 +315,14 @@ int zmx_checksum(zmx_ctx* c, int kind, size_t begin, size_t end, uint32_t* value
 // (CPU stand-in for the device bit writer: the same contract, symbol by symbol)
 int zmx_encode_blocks(zmx_ctx*, zmx_tables* t, size_t njobs, const zmx_enc_job* jobs, const uint32_t* codes,
                       unsigned char* const* out) {
+  if (njobs == 0) return 0;
+  if (const int rc = CheckTables("zmx_encode_blocks", t, false, false)) return rc;
+  for (size_t j = 0; j < njobs; ++j) {
+    if (const int rc = CheckStoreRef("zmx_encode_blocks", t, jobs[j].block, jobs[j].slot, jobs[j].nsym)) return rc;
+  }
   for (size_t j = 0; j < njobs; ++j) {
     const zmx_enc_job& q = jobs[j];
     const BlockData& d = t->blocks[q.block];
-    if (q.nsym > d.nsym[q.slot]) return -1;
     const uint32_t* cd = codes + j * 320;
     unsigned char* o = out[j];
     uint64_t pos = q.bit_start;
@@ -325,11 +356,15 @@ int zmx_encode_blocks(zmx_ctx*, zmx_tables* t, size_t njobs, const zmx_enc_job* 
 
 int zmx_find_longest_match(zmx_ctx*, zmx_tables* t, size_t block, size_t pos, uint16_t* sublen,
                            uint16_t* distance, uint16_t* length) {
+  if (const int rc = CheckTables("zmx_find_longest_match", t, true, false)) return rc;
+  if (block >= t->blocks.size()) return Refuse("zmx_find_longest_match", "bad block");
   zo_find_longest_match(t->blocks[block].table, pos, sublen, distance, length);
   return 0;
 }
 
 int zmx_length_array_download(zmx_ctx*, zmx_tables* t, size_t block, uint16_t* out) {
+  if (const int rc = CheckTables("zmx_length_array_download", t, true, false)) return rc;
+  if (block >= t->blocks.size()) return Refuse("zmx_length_array_download", "bad block");
   const auto& la = t->blocks[block].length_array;
   std::memcpy(out, la.data(), la.size() * 2);
   return 0;
@@ -342,6 +377,12 @@ struct zmx_cost_stores {
 };
 int zmx_cost_stores_create(zmx_ctx*, zmx_tables* t, size_t nstores, const size_t* piece_first, const size_t* block,
                            const int32_t* slot, const size_t* nsym, zmx_cost_stores** out) {
+  *out = nullptr;
+  if (nstores == 0) return Refuse("zmx_cost_stores_create", "no sequence");
+  if (const int rc = CheckTables("zmx_cost_stores_create", t, false, false)) return rc;
+  for (size_t p = 0; p < piece_first[nstores]; ++p) {
+    if (const int rc = CheckStoreRef("zmx_cost_stores_create", t, block[p], slot[p], nsym[p])) return rc;
+  }
   zmx_cost_stores* s = new zmx_cost_stores();
   s->stores.resize(nstores);
   for (size_t q = 0; q < nstores; ++q) {
@@ -349,7 +390,6 @@ int zmx_cost_stores_create(zmx_ctx*, zmx_tables* t, size_t nstores, const size_t
     size_t pos = 0;
     for (size_t p = piece_first[q]; p < piece_first[q + 1]; ++p) {
       const BlockData& d = t->blocks[block[p]];
-      if (nsym[p] > d.nsym[slot[p]]) { delete s; g_err = "zmx_cost_stores_create: nsym exceeds the store"; return -1; }
       s->stores[q].Append(d.litlens[slot[p]].data(), d.dists[slot[p]].data(), nsym[p], pos);
       pos = s->stores[q].ByteRange(0, s->stores[q].size());
     }

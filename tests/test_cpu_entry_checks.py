@@ -1,0 +1,27 @@
+"""The entry checks of test_gpu_entry_checks.py against the host test library: its stand-in for the device layer
+(tests/hostlib/zmx_oracle_backend.cc) refuses the same requests with the same texts and class, for every entry it has
+(it has no hash links).  CPU only."""
+import pytest
+
+import oracle_lib as ol
+import test_gpu_entry_checks as ec
+
+
+@pytest.fixture(scope="module")
+def host_ctx():
+    from zopfli_amd import Context
+    ctx = Context(0, ol.hosttest_library())
+    yield ctx
+    ctx.close()
+
+
+def test_store_refs_checked_host_backend(host_ctx):
+    ec.store_refs_checked(host_ctx)
+
+
+def test_trimmed_tables_refuse_host_backend(host_ctx):
+    ec.trimmed_tables_refuse(host_ctx, hash_links=False)
+
+
+def test_matches_only_tables_refuse_host_backend(host_ctx):
+    ec.matches_only_tables_refuse(host_ctx)

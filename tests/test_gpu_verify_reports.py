@@ -155,3 +155,28 @@ def test_short_stores(gpu_ctx, verify_case):
     b = _flip(a, {int(pos[100])})
     assert sc.verify_len_dist(b, *BLOCKS[1], ll[:n - 300], dd[:n - 300]) == (100, 2)
     assert _report(gpu_ctx, t, a, b, [(1, 0, n - 300)]) == (1, 100, REASON[2])
+
+
+def test_error_class_of_a_failed_verification(gpu_ctx, verify_case):
+    """A refusal, then a failed verification on the same thread: the class is the verification's own (ZMX_ERR_DEVICE,
+    which the host layer tries again elsewhere), not the refusal's left behind; a passing call then returns 0."""
+    ZMX_ERR_DEVICE, ZMX_ERR_REFUSED = 1, 3
+    a, t, stores = verify_case
+    ll, dd = stores[(0, 0)]
+    pos, _ = _positions(0, ll, dd)
+    with pytest.raises(RuntimeError, match="zmx_store_download: bad block or slot"):
+        t.store(0, 2, 1)
+    assert gpu_ctx.lib.zmx_last_error_class() == ZMX_ERR_REFUSED
+    b = _flip(a, {int(pos[100])})
+    assert sc.verify_len_dist(b, *BLOCKS[0], ll, dd) == (100, 2)
+    gpu_ctx.set_input(b)
+    try:
+        with pytest.raises(RuntimeError) as e:
+            t.verify_stores([0], [0], [len(ll)])
+        cls = gpu_ctx.lib.zmx_last_error_class()
+    finally:
+        gpu_ctx.set_input(a)
+    m = MSG.search(str(e.value))
+    assert m and (int(m.group(1)), int(m.group(2)), m.group(3)) == (0, 100, REASON[2]), str(e.value)
+    assert cls == ZMX_ERR_DEVICE
+    t.verify_stores([0], [0], [len(ll)])                                   # passes: returns 0, raises nothing

@@ -27,11 +27,14 @@
 #include "zmx_png.h"
 #include "zmx_png_brute.h"
 #include "zmx_blockcost.h"
+#include "zmx_knobs.h"
 #include "zopfli_amd.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
 
 namespace {
+
+using zamd::Knobs;   // the ZOPFLI_AMD_* switches of this file (zmx_knobs.h)
 
 thread_local std::string g_err;   // per calling thread (zmx_last_error)
 // Kernel, match and task statistics: per calling THREAD (a Zopfli* call's shard threads hand theirs to the caller's
@@ -77,6 +80,12 @@ int FailFault(const std::string& m) {
   g_err_class = ZMX_ERR_DEVICE;
   return -1;
 }
+constexpr int kTooLarge = -2;   // zmx_tables_build*: the batch does not fit the code budget, try fewer blocks
+// refused as it is (this batch, anywhere), but the caller may come back with fewer blocks
+int FailTooLarge(const std::string& m) {
+  FailMsg(m);
+  return kTooLarge;
+}
 
 #define HIPCHK(expr)                                                  \
   do {                                                                \
@@ -96,9 +105,7 @@ struct DeviceGuard {
   ~DeviceGuard() { if (old >= 0) (void)hipSetDevice(old); }
 };
 
-constexpr int kTooLarge = -2;   // zmx_tables_build*: the batch does not fit the code budget, try fewer blocks
 constexpr u32 kMatchGrid = 1024;  // persistent workgroups: 256 CUs x 4 (LDS-limited)
-constexpr int kMatchDefault = 0;   // ZOPFLI_AMD_MATCH when unset: per block, k_match5 where k_hits says the chains are long, else k_match2
 constexpr u32 kMatchGrid5 = 1536; // k_match5: 256 CUs x 6 workgroups of 4 waves (its scratch is k_match2's: 1536 x 256 <= 1024 x 512 lanes)
 constexpr size_t kInputPad = 4096;
 
@@ -113,10 +120,7 @@ constexpr size_t kInputPad = 4096;
 // ---------------------------------------------------------------------------------------------
 constexpr size_t kGuardBytes = 4096;
 constexpr u32 kGuardMaxAllocs = 256;
-bool GuardOn() {
-  static const bool on = [] { const char* e = std::getenv("ZOPFLI_AMD_GUARD"); return e && std::atoi(e) != 0; }();
-  return on;
-}
+bool GuardOn() { return Knobs().guard; }
 
 }  // namespace
 
@@ -166,6 +170,51 @@ struct zmx_ctx {
   u64 guard_checks = 0;
 };
 
+// What a squeeze run takes and gives, each side ONE array on the device and one pinned mirror on the host, so that a run
+// has one copy down and one up (eight small copies a run were 3 ms of copy kernels per 15 runs).  This is the only place
+// that says where the parts lie: in = cost | mincost | wmax | tiemask | est | slot, out = hist | nsym | stats | flags.
+// The accessors take the base of either copy, the device's or the pinned one.
+struct RunLayout {
+  static constexpr size_t kStats = 8, kFlags = 4;   // words: the task statistics (k_wtab zeroes them), the consistency flags
+  size_t in_cost = 0, in_mincost = 0, in_wmax = 0, in_tiemask = 0, in_est = 0, in_slot = 0, in_bytes = 0;
+  size_t out_hist = 0, out_nsym = 0, out_stats = 0, out_flags = 0, out_bytes = 0;
+  RunLayout() = default;
+  explicit RunLayout(size_t nb) {
+    in_mincost = in_cost + nb * ZMX_HIST * sizeof(double);
+    in_wmax = in_mincost + nb * sizeof(double);
+    in_tiemask = in_wmax + nb * sizeof(float);
+    in_est = in_tiemask + nb * sizeof(u32);
+    in_slot = in_est + nb * sizeof(float);
+    in_bytes = in_slot + nb * sizeof(int);
+    out_nsym = out_hist + nb * ZMX_HIST * sizeof(u32);
+    out_stats = out_nsym + nb * sizeof(u32);
+    out_flags = out_stats + kStats * sizeof(u32);
+    out_bytes = out_flags + kFlags * sizeof(u32);
+  }
+  double* cost(unsigned char* in) const { return reinterpret_cast<double*>(in + in_cost); }         // [nb][ZMX_HIST]
+  double* mincost(unsigned char* in) const { return reinterpret_cast<double*>(in + in_mincost); }   // [nb]
+  float* wmax(unsigned char* in) const { return reinterpret_cast<float*>(in + in_wmax); }           // [nb] (RunInfo)
+  u32* tiemask(unsigned char* in) const { return reinterpret_cast<u32*>(in + in_tiemask); }         // [nb]
+  float* est(unsigned char* in) const { return reinterpret_cast<float*>(in + in_est); }             // [nb] estimated block cost
+  int* slot(unsigned char* in) const { return reinterpret_cast<int*>(in + in_slot); }               // [nb]
+  u32* hist(unsigned char* out) const { return reinterpret_cast<u32*>(out + out_hist); }            // [nb][ZMX_HIST]
+  u32* nsym(unsigned char* out) const { return reinterpret_cast<u32*>(out + out_nsym); }            // [nb]
+  u32* stats(unsigned char* out) const { return reinterpret_cast<u32*>(out + out_stats); }          // [kStats]
+  u32* flags(unsigned char* out) const { return reinterpret_cast<u32*>(out + out_flags); }          // [kFlags]
+  // the statistics and the flags behind them, as one range (out_flags = out_stats + stats_bytes above)
+  static constexpr size_t stats_and_flags_bytes() { return (kStats + kFlags) * sizeof(u32); }
+};
+
+// The kernel parameters that depend on the table set alone, filled when the set is built (FillTableParams).  A launch
+// copies its block and sets what varies per run.  Zeroed again when the arrays go (ReleaseTableArrays).
+struct TableParams {
+  GreedySegParams greedy;   // .store: per call
+  WtabParams wtab;          // (these four: sets with DP rows only)
+  BadScanParams badscan;
+  Dp4Params dp;             // per run: est_bits, prof, mid, task0, redo_pass and the switches' fields
+  TraceSegParams trace;
+};
+
 struct zmx_tables {
   size_t nb = 0;
   std::vector<BlockDesc> blocks;
@@ -185,11 +234,6 @@ struct zmx_tables {
   u32 pool_cap = 0;
   u16* d_la = nullptr;
   u32* d_store[2] = {nullptr, nullptr};
-  u32* d_hist = nullptr;
-  u32* d_nsym = nullptr;
-  double* d_cost = nullptr;
-  double* d_mincost = nullptr;
-  int* d_slot = nullptr;
   uint2* d_dph = nullptr;         // per position: DP row offset, kend | shortcut flag (k_rowscan)
   u64* d_block_edges = nullptr;   // per block: DP edges
   u32* d_badpos = nullptr;        // bit per position: it owns a match edge below mincost (k_badscan, per run)
@@ -206,16 +250,19 @@ struct zmx_tables {
   std::vector<u64> block_edges;
   std::vector<u32> tile_off;
   u32* d_counters = nullptr;  // 48 words, see MatchParams (24 .. 31: k_match5's tile cursors, 32 .. 39: its watchdog's dump)
-  u32* d_flags = nullptr;     // 4 words
-  // what a squeeze run takes and gives, each side ONE array on the device and one pinned mirror on the host, so
-  // that a run has one copy down and one up (eight small copies a run were 3 ms of copy kernels per 15 runs):
-  // d_runin = cost | mincost | runinfo | slot, d_runout = hist | nsym | segstats | flags (the d_* above point into them)
+  // a squeeze run's input and output, on the device and mirrored in pinned memory, laid out by `run`
+  RunLayout run;
   unsigned char* d_runin = nullptr;
   unsigned char* d_runout = nullptr;
   unsigned char* h_runin = nullptr;
   unsigned char* h_runout = nullptr;
   size_t h_runin_cap = 0, h_runout_cap = 0;
-  size_t runin_bytes = 0, runout_bytes = 0;
+  int* d_slot = nullptr;      // (these five point into d_runin / d_runout)
+  u32* d_hist = nullptr;
+  u32* d_nsym = nullptr;
+  u32* d_segstats = nullptr;
+  u32* d_flags = nullptr;
+  TableParams params = {};
   u64* d_prof = nullptr;      // nb * ZMX_PROF_N counters when ZOPFLI_AMD_PROF is set
   // the chain's tasks (zmx_dp4.h)
   std::vector<SegTask> tasks;
@@ -237,8 +284,6 @@ struct zmx_tables {
   SegCheck* d_chk = nullptr;
   u16* d_over = nullptr;      // [tasks][SEG_OVER]
   u32* d_redo = nullptr;      // [1 + 3 pad + tasks * 4]: k_dpscan's list of tasks to run a second time
-  float* d_runinfo = nullptr; // [3][nb]: wmax, tie mask (as bits), estimated block cost
-  u32* d_segstats = nullptr;  // 8 words
   std::vector<u32> h_hist;    // the histograms of the last greedy parse / squeeze run (host copy)
   bool have_hist = false;
   u32 squeeze_runs = 0;
@@ -272,8 +317,6 @@ std::atomic<zmx_oom_hook_t> g_oom_hook{nullptr};
 // ones share it, and idle ones are trimmed when another runs out (zmx_set_oom_hook).
 constexpr int kMaxDevices = 64;
 std::atomic<size_t> g_dev_cached[kMaxDevices];
-inline std::atomic<size_t>& DevCached(const zmx_ctx* c);
-
 inline std::atomic<size_t>& DevCached(const zmx_ctx* c) { return g_dev_cached[c->device >= 0 && c->device < kMaxDevices ? c->device : 0]; }
 
 hipError_t PoolAllocBytes(zmx_ctx* c, void** p, size_t bytes, const char* tag) {
@@ -331,13 +374,6 @@ hipError_t PoolAllocT(zmx_ctx* c, T** p, size_t n, const char* tag) {
 }
 #define PoolAlloc(c, p, n) PoolAllocT(c, p, n, #p)
 
-// Temporary arrays of one call: back to the pool when the call returns, whichever way (HIPCHK returns early).
-// k_match2's four-byte candidate filter (zmx_match2.h, FILT); ZOPFLI_AMD_MATCH_FILTER=0 keeps the one-byte test
-bool MatchFilter() {
-  static const bool on = [] { const char* e = std::getenv("ZOPFLI_AMD_MATCH_FILTER"); return e ? std::atoi(e) != 0 : true; }();
-  return on;
-}
-
 // Which match-table kernel (ZOPFLI_AMD_MATCH / zmx_set_match_kernel):
 //   0 (default) per block: k_hits estimates the hits per position of the reference's walk; blocks above
 //       ZOPFLI_AMD_MATCH_HITS (300) take the exact skip-walk k_match5 (level links + counted hits, zmx_match5.h: 5 - 9 x
@@ -348,34 +384,19 @@ bool MatchFilter() {
 // k_match2 either way.
 std::atomic<int> g_match_kernel{-1};
 int MatchKernel() {
-  int v = g_match_kernel.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = std::getenv("ZOPFLI_AMD_MATCH");
-    const int k = e ? std::atoi(e) : kMatchDefault;
-    v = k == 0 || k == 5 ? k : 2;      // (3 and 4 were removed: they fall back to 2)
-    g_match_kernel.store(v, std::memory_order_relaxed);
-  }
-  return v;
+  const int v = g_match_kernel.load(std::memory_order_relaxed);
+  return v < 0 ? Knobs().match : v;      // (the setter's choice, else the environment's)
 }
 // k_match2 hands out a tile's positions longest walk first, by k_hits' estimates (ZOPFLI_AMD_MATCH_ORDER /
 // zmx_set_match_order; 0 = in ascending order).  Whole builds only: a table built from a parent recomputes a few
 // tiles, for which nobody runs k_hits.
 std::atomic<int> g_match_order{-1};
 bool MatchOrder() {
-  int v = g_match_order.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = std::getenv("ZOPFLI_AMD_MATCH_ORDER");
-    v = e ? (std::atoi(e) != 0 ? 1 : 0) : 1;
-    g_match_order.store(v, std::memory_order_relaxed);
-  }
-  return v != 0;
-}
-// kernel 0: blocks whose estimated hits per position (k_hits) exceed this take k_match5 (ZOPFLI_AMD_MATCH_HITS)
-u64 MatchAutoHits() {
-  static const u64 v = [] { const char* e = std::getenv("ZOPFLI_AMD_MATCH_HITS"); return e ? static_cast<u64>(std::max<long>(0, std::atol(e))) : 300ull; }();
-  return v;
+  const int v = g_match_order.load(std::memory_order_relaxed);
+  return v < 0 ? Knobs().match_order : v != 0;
 }
 
+// Temporary arrays of one call: back to the pool when the call returns, whichever way (HIPCHK returns early).
 struct PoolScope {
   zmx_ctx* c;
   std::vector<void*> held;
@@ -422,7 +443,7 @@ int GuardVerify(zmx_ctx* c, const char* where) {
   if (c->guard_live.empty()) return 0;
   // (ZOPFLI_AMD_GUARD_SELFTEST=N: the N-th check finds a byte that this function itself just broke — the test that the
   //  mode reports what it is there to report)
-  static const u64 selftest = [] { const char* e = std::getenv("ZOPFLI_AMD_GUARD_SELFTEST"); return e ? static_cast<u64>(std::atoll(e)) : 0ull; }();
+  const u64 selftest = Knobs().guard_selftest;
   std::vector<std::pair<void*, zmx_ctx::GuardInfo>> live(c->guard_live.begin(), c->guard_live.end());
   if (!c->d_guard_tab) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_guard_tab), (2 * static_cast<size_t>(kGuardMaxAllocs) + 2) * sizeof(u64)));
   ++c->guard_checks;
@@ -487,13 +508,8 @@ int zmx_last_error_class(void) { return g_err_class; }
 // (bench.py, tools/latency.py and the tests' harness do).
 static std::atomic<int> g_kernel_timing{-1};
 static bool KernelTiming() {
-  int v = g_kernel_timing.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = std::getenv("ZOPFLI_AMD_KERNEL_TIMING");
-    v = (e ? std::atoi(e) != 0 : std::getenv("ZOPFLI_AMD_PROF") != nullptr) ? 1 : 0;
-    g_kernel_timing.store(v, std::memory_order_relaxed);
-  }
-  return v != 0;
+  const int v = g_kernel_timing.load(std::memory_order_relaxed);
+  return v < 0 ? Knobs().kernel_timing : v != 0;
 }
 void zmx_set_kernel_timing(int on) { g_kernel_timing.store(on ? 1 : 0, std::memory_order_relaxed); }
 
@@ -718,45 +734,18 @@ int zmx_set_input_segments(zmx_ctx* c, const uint64_t* starts, size_t nseg) {
 
 // Gives back the device arrays of a table set — all of them, or all but the two LZ77 stores (zmx_tables_trim).
 static void ReleaseTableArrays(zmx_ctx* c, zmx_tables* t, bool keep_stores) {
-  auto rel = [&](auto*& p) { PoolFree(c, p); p = nullptr; };
-  rel(t->d_blocks);
-  rel(t->d_tile_off);
-  rel(t->d_same16);
-  rel(t->d_links);
-  rel(t->d_recs);
-  rel(t->d_pool);
-  rel(t->d_la);
-  rel(t->d_dph);
-  rel(t->d_block_edges);
-  rel(t->d_badpos);
-  rel(t->d_code_base);
-  rel(t->d_codes);
-  rel(t->d_wtab);
-  rel(t->d_badcodes);
-  rel(t->d_seg_off);
-  rel(t->d_extab);
-  rel(t->d_seginfo);
-  rel(t->d_counters);
-  rel(t->d_prof);
-  rel(t->d_tasks);
-  rel(t->d_task_off);
-  rel(t->d_wg_tasks);
-  rel(t->d_wmeta);
-  rel(t->d_runin);
-  rel(t->d_runout);
-  rel(t->d_winroff);
-  rel(t->d_winflag);
-  rel(t->d_win_off);
-  rel(t->d_lvl);
-  rel(t->d_entry);
-  rel(t->d_exit);
-  rel(t->d_mid);
-  rel(t->d_chk);
-  rel(t->d_over);
-  rel(t->d_redo);
+  auto rel = [&](auto*&... p) { ((PoolFree(c, p), p = nullptr), ...); };
+  rel(t->d_blocks, t->d_tile_off, t->d_same16, t->d_links, t->d_recs, t->d_pool, t->d_la, t->d_dph, t->d_block_edges);
+  rel(t->d_badpos, t->d_code_base, t->d_codes, t->d_wtab, t->d_badcodes, t->d_seg_off, t->d_extab, t->d_seginfo);
+  rel(t->d_counters, t->d_prof, t->d_tasks, t->d_task_off, t->d_wg_tasks, t->d_wmeta, t->d_runin, t->d_runout);
+  rel(t->d_winroff, t->d_winflag, t->d_win_off, t->d_lvl, t->d_entry, t->d_exit, t->d_mid, t->d_chk, t->d_over, t->d_redo);
   PinnedGive(c, &t->h_runin, t->h_runin_cap);
   PinnedGive(c, &t->h_runout, t->h_runout_cap);
-  if (!keep_stores) { rel(t->d_store[0]); rel(t->d_store[1]); }
+  // nothing that pointed into those arrays stays behind (the entries refuse such tables: CheckTables)
+  t->d_slot = nullptr;
+  t->d_hist = t->d_nsym = t->d_segstats = t->d_flags = nullptr;
+  t->params = TableParams{};
+  if (!keep_stores) rel(t->d_store[0], t->d_store[1]);
 }
 
 void zmx_tables_free(zmx_ctx* c, zmx_tables* t) {
@@ -785,29 +774,13 @@ int zmx_tables_trim(zmx_ctx* c, zmx_tables* t) {
   return 0;
 }
 
-// `parent` (optional): a table set over blocks that contain the new ones.  The match record of a
-// position depends on its block only through the block end (SURVEY A.1): limit = min(258, end -
-// pos), same[] truncated at the end, zero bytes in the hashes of the last two positions.  So the
-// records of a sub-block equal the parent's except where pos + 258 > end or pos lies in the run
-// of equal bytes that reaches the end — only the tiles holding such positions are recomputed,
-// everything else is copied.  Hash links (k_same, k_chain) are rebuilt: they are cheap.
-static unsigned EnvU32(const char* name, unsigned dflt, unsigned lo, unsigned hi) {
-  const char* e = std::getenv(name);
-  if (!e) return dflt;
-  const long v = std::atol(e);
-  return v < static_cast<long>(lo) ? lo : v > static_cast<long>(hi) ? hi : static_cast<unsigned>(v);
-}
-// Task geometry of the chain (zmx_dp4.h): positions per task and warm-up positions before it.
-// ZOPFLI_AMD_SEG_L = 0 turns the cut off (one task per block: the serial chain).
-// Task length of the chain.  A task is one serial wave, and a run is at least a task, a second-pass task and the
+// Task length of the chain (zmx_dp4.h).  A task is one serial wave, and a run is at least a task, a second-pass task and the
 // serial re-runs long: with little to do (small calls: zopflipng's IDATs, files of a MB or less) short tasks cut
 // that latency (1 MB: 53 -> 47 ms, 64 KiB: 32 -> 24 ms) although every task pays its 512-position warm-up; with
 // a full batch 2048 and 4096 run alike and the longer tasks walk fewer positions.  ZOPFLI_AMD_SEG_L overrides
 // (0 = no tasks: the serial chain).
 static unsigned SegL(u64 total_positions) {
-  static const bool set = std::getenv("ZOPFLI_AMD_SEG_L") != nullptr;
-  static const unsigned v = EnvU32("ZOPFLI_AMD_SEG_L", 4096, 0, 1u << 24) & ~63u;
-  if (set) return v;
+  if (Knobs().seg_l_set) return Knobs().seg_l;
   // (with the tasks started at cut points, below, the warm-up is ~70 positions instead of 512 and 2048 beats 4096
   //  for a full batch too: half the positions re-run where a task crosses a binade, 4.17 -> 3.75 ms per run of 100 MB;
   //  1024 loses to the per-task set-up again: 4.2 ms)
@@ -818,17 +791,14 @@ static unsigned SegL(u64 total_positions) {
   //  100 MB: 2048 3.63 ms per run against 3.94 with 1024 — tools/r05_segl.sh)
   return total_positions <= (128u << 10) ? 256u : total_positions <= (16u << 20) ? 512u : total_positions <= (48u << 20) ? 1024u : 2048u;
 }
-// The first task of a block is exact by construction and runs beside the others: let it cover the
-// stretch where the costs double every few thousand positions and no guess would stay in its binade.
 // The exact head of a block (positions run from the true initial state; the values double every few hundred
 // positions there and speculative tasks would not stay inside a binade).  It is one serial wave: with few blocks in
 // the batch the whole run waits for it (short: 4096), with many it hides behind the other tasks and a long head
 // saves the serial re-runs of the early tasks (8192; 16384 and 4096 are within 1 %).  ZOPFLI_AMD_SEG_HEAD overrides.
 static unsigned SegHead(size_t nb) {
-  static const unsigned v = EnvU32("ZOPFLI_AMD_SEG_HEAD", 0, 0, 1u << 24) & ~63u;
+  const unsigned v = Knobs().seg_head;
   return v ? v : (nb >= 48 ? 8192u : 0u);       // (0: as long as a task)
 }
-static unsigned SegWarm() { static const unsigned v = (EnvU32("ZOPFLI_AMD_SEG_WARM", 512, 64, 1u << 20) + 63u) & ~63u; return v; }
 
 // ---------------------------------------------------------------------------------------------
 // BuildTables, phase by phase.  Every phase works on `c->stream` and returns 0, or what BuildTables returns for the
@@ -944,27 +914,17 @@ static int AllocTableArrays(zmx_ctx* c, zmx_tables* t, u64 la_off) {
   HIPCHK(PoolAlloc(c, &t->d_la, la_off));
   HIPCHK(PoolAlloc(c, &t->d_store[0], pos_off));
   HIPCHK(PoolAlloc(c, &t->d_store[1], pos_off));
-  {
-    const size_t in_cost = 0, in_min = in_cost + nb * ZMX_HIST * sizeof(double), in_info = in_min + nb * sizeof(double),
-                 in_slot = in_info + 3 * nb * sizeof(float);
-    t->runin_bytes = in_slot + nb * sizeof(int);
-    const size_t out_hist = 0, out_nsym = out_hist + nb * ZMX_HIST * sizeof(u32), out_stats = out_nsym + nb * sizeof(u32),
-                 out_flags = out_stats + 8 * sizeof(u32);
-    t->runout_bytes = out_flags + 4 * sizeof(u32);
-    HIPCHK(PoolAlloc(c, &t->d_runin, t->runin_bytes));
-    HIPCHK(PoolAlloc(c, &t->d_runout, t->runout_bytes));
-    HIPCHK(PinnedTake(c, &t->h_runin, t->runin_bytes, &t->h_runin_cap));
-    HIPCHK(PinnedTake(c, &t->h_runout, t->runout_bytes, &t->h_runout_cap));
-    t->d_cost = reinterpret_cast<double*>(t->d_runin + in_cost);
-    t->d_mincost = reinterpret_cast<double*>(t->d_runin + in_min);
-    t->d_runinfo = reinterpret_cast<float*>(t->d_runin + in_info);
-    t->d_slot = reinterpret_cast<int*>(t->d_runin + in_slot);
-    t->d_hist = reinterpret_cast<u32*>(t->d_runout + out_hist);
-    t->d_nsym = reinterpret_cast<u32*>(t->d_runout + out_nsym);
-    t->d_segstats = reinterpret_cast<u32*>(t->d_runout + out_stats);
-    t->d_flags = reinterpret_cast<u32*>(t->d_runout + out_flags);
-    HIPCHK(hipMemsetAsync(t->d_segstats, 0, 12 * sizeof(u32), c->stream));
-  }
+  t->run = RunLayout(nb);
+  HIPCHK(PoolAlloc(c, &t->d_runin, t->run.in_bytes));
+  HIPCHK(PoolAlloc(c, &t->d_runout, t->run.out_bytes));
+  HIPCHK(PinnedTake(c, &t->h_runin, t->run.in_bytes, &t->h_runin_cap));
+  HIPCHK(PinnedTake(c, &t->h_runout, t->run.out_bytes, &t->h_runout_cap));
+  t->d_slot = t->run.slot(t->d_runin);
+  t->d_hist = t->run.hist(t->d_runout);
+  t->d_nsym = t->run.nsym(t->d_runout);
+  t->d_segstats = t->run.stats(t->d_runout);
+  t->d_flags = t->run.flags(t->d_runout);
+  HIPCHK(hipMemsetAsync(t->d_segstats, 0, RunLayout::stats_and_flags_bytes(), c->stream));
   HIPCHK(PoolAlloc(c, &t->d_dph, pos_off));
   HIPCHK(PoolAlloc(c, &t->d_block_edges, nb));
   t->badpos_words = pos_off / 32 + 4;
@@ -975,7 +935,7 @@ static int AllocTableArrays(zmx_ctx* c, zmx_tables* t, u64 la_off) {
   HIPCHK(PoolAlloc(c, &t->d_counters, 48));
   HIPCHK(hipMemcpyAsync(t->d_blocks, t->blocks.data(), nb * sizeof(BlockDesc), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(t->d_tile_off, tile_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(t->d_flags, 0, 4 * sizeof(u32), c->stream));
+  HIPCHK(hipMemsetAsync(t->d_flags, 0, RunLayout::kFlags * sizeof(u32), c->stream));
   return 0;
 }
 
@@ -1045,7 +1005,7 @@ static int LaunchHash(zmx_ctx* c, zmx_tables* t, int mk, u64 max_l, const u64* d
       HIPCHK(hipStreamSynchronize(c->stream));
       size_t on = 0;
       for (size_t b = 0; b < nb; ++b) {
-        if (energy[b] > MatchAutoHits() * (t->blocks[b].inend - t->blocks[b].ws)) {
+        if (energy[b] > Knobs().match_hits * (t->blocks[b].inend - t->blocks[b].ws)) {
           ++on;
           m.skip_positions += static_cast<double>(t->blocks[b].inend - t->blocks[b].instart);
         }
@@ -1065,7 +1025,7 @@ static int LaunchHash(zmx_ctx* c, zmx_tables* t, int mk, u64 max_l, const u64* d
       lp.lev = m.d_lev;
       lp.total_l = reg_off;
       lp.energy = mk == 0 ? m.d_energy : nullptr;
-      lp.thr = MatchAutoHits();
+      lp.thr = Knobs().match_hits;
       const dim3 g4(static_cast<unsigned>((max_l + LV_CH - 1) / LV_CH), static_cast<unsigned>(nb), LV_N);
       hipLaunchKernelGGL(k_levels, g4, dim3(64), 0, c->stream, lp);
       KCHK(c, "k_levels");
@@ -1132,7 +1092,7 @@ static int LaunchMatch(zmx_ctx* c, zmx_tables* t, int mk, MatchBuild& m, u32* po
     q.xrec = m.d_xrec;
     q.tot12 = m.d_tot12;
     q.energy = mk == 0 ? m.d_energy : nullptr;
-    q.thr = MatchAutoHits();
+    q.thr = Knobs().match_hits;
     const size_t m5_waves = static_cast<size_t>(kMatchGrid5) * (M5_THREADS / 64);
     if (!m.d_m5stats) HIPCHK(m.hash_tmp.AllocT(&m.d_m5stats, 2 * m5_waves, "d_m5stats"));
     HIPCHK(hipMemsetAsync(m.d_m5stats, 0, 2 * m5_waves * sizeof(unsigned long long), c->stream));
@@ -1159,9 +1119,9 @@ static int LaunchMatch(zmx_ctx* c, zmx_tables* t, int mk, MatchBuild& m, u32* po
     HIPCHK(hipEventRecord(c->ev2[1], c->stream2));
     m.join_stream2 = true;
     mp.skip_energy = m.d_energy;
-    mp.skip_thr = MatchAutoHits();
+    mp.skip_thr = Knobs().match_hits;
   }
-  const bool filt = MatchFilter();
+  const bool filt = Knobs().match_filter;
   if (prof && filt) hipLaunchKernelGGL((k_match2<true, true>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
   else if (prof) hipLaunchKernelGGL((k_match2<true, false>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
   else if (filt) hipLaunchKernelGGL((k_match2<false, true>), dim3(kMatchGrid), dim3(M2_THREADS), 0, c->stream, mp);
@@ -1220,6 +1180,7 @@ static int BuildMatchRecords(zmx_ctx* c, zmx_tables* t, zmx_tables* parent, int 
       t->pool_cap = parent->pool_cap;
       parent->d_pool = nullptr;
       parent->pool_cap = 0;
+      parent->params.trace.pool = nullptr;
     } else {
       reuse = false;                       // pool overflow: build everything with a pool of our own,
       if (LaunchHash(c, t, mk, max_l, nullptr, m) != 0) return -1;   // which needs the hash arrays of whole blocks
@@ -1231,7 +1192,7 @@ static int BuildMatchRecords(zmx_ctx* c, zmx_tables* t, zmx_tables* parent, int 
   // position and grow on overflow (worst case 256 per position).
   // (ZOPFLI_AMD_POOL_ENTRIES: test hook, the first pool has that many entries in all, so that the
   // overflow / retry path and the fall-through from a reused parent pool run on small inputs)
-  static const u64 pool_entries = [] { const char* e = std::getenv("ZOPFLI_AMD_POOL_ENTRIES"); return e ? static_cast<u64>(std::atoll(e)) : 0ull; }();
+  const u64 pool_entries = Knobs().pool_entries;
   u64 per_pos = 4;
   for (bool first_try = true; !reuse; first_try = false) {
     u64 cap = std::max<u64>(pos_off * per_pos, 1u << 16);
@@ -1242,8 +1203,7 @@ static int BuildMatchRecords(zmx_ctx* c, zmx_tables* t, zmx_tables* parent, int 
     HIPCHK(PoolAlloc(c, &t->d_pool, cap));
     t->pool_cap = static_cast<u32>(cap);
     HIPCHK(hipMemsetAsync(t->d_counters, 0, 48 * sizeof(u32), c->stream));
-    static const bool match_prof = std::getenv("ZOPFLI_AMD_PROF") != nullptr;
-    if (LaunchMatch(c, t, mk, m, t->d_pool, t->pool_cap, tile_off[nb], nullptr, match_prof) != 0) return -1;
+    if (LaunchMatch(c, t, mk, m, t->d_pool, t->pool_cap, tile_off[nb], nullptr, Knobs().prof) != 0) return -1;
     u32 counters[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(counters, t->d_counters, sizeof(counters), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1284,7 +1244,7 @@ static int BuildMatchRecords(zmx_ctx* c, zmx_tables* t, zmx_tables* parent, int 
       g_match5_stats[1] += m5_iters;
       g_match5_stats[2] += m.skip_positions;
     }
-    if (std::getenv("ZOPFLI_AMD_PROF") && !reuse) {
+    if (Knobs().prof && !reuse) {
       unsigned long long hc[2] = {0, 0};
       HIPCHK(hipMemcpy(hc, t->d_counters + 4, sizeof(hc), hipMemcpyDeviceToHost));
       const double pos = static_cast<double>(pos_off);
@@ -1295,7 +1255,7 @@ static int BuildMatchRecords(zmx_ctx* c, zmx_tables* t, zmx_tables* parent, int 
       if (mk != 5) {
         // what the runtime says of the instantiation that ships (kMatchGrid counts on 4: the window and the order's 4 KB in LDS)
         int wgs = 0;
-        if (MatchFilter()) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_match2<false, true>, M2_THREADS, 0));
+        if (Knobs().match_filter) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_match2<false, true>, M2_THREADS, 0));
         else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, k_match2<false, false>, M2_THREADS, 0));
         std::fprintf(stderr, "k_match2: %d workgroups of %u threads resident per CU; positions handed out %s\n", wgs, M2_THREADS,
                      m.d_est ? "by k_hits' estimate, longest first" : "in ascending order");
@@ -1317,8 +1277,7 @@ static int BuildDpRows(zmx_ctx* c, zmx_tables* t) {
   rp.block_edges = t->d_block_edges;
   // (ZOPFLI_AMD_RUN_CODES=1: codes for every row, as in round 5; the serial chain — ZOPFLI_AMD_SEG_L=0, k_dp4's pipeline
   //  over whole blocks — needs them)
-  static const bool all_codes = [] { const char* e = std::getenv("ZOPFLI_AMD_RUN_CODES"); return e && std::atoi(e) != 0; }();
-  rp.codeless = !all_codes && SegL(t->total_b) != 0 ? 1u : 0u;
+  rp.codeless = !Knobs().run_codes && SegL(t->total_b) != 0 ? 1u : 0u;
   hipLaunchKernelGGL(k_rowscan, dim3(static_cast<unsigned>(nb)), dim3(1024), 0, c->stream, rp);
   KCHK(c, "k_rowscan");
   HIPCHK(hipGetLastError());
@@ -1328,10 +1287,7 @@ static int BuildDpRows(zmx_ctx* c, zmx_tables* t) {
   {
     // ZOPFLI_AMD_CODE_BUDGET_MB: what the codes of one batch may take (two bytes per DP edge; a position
     // has 1..258 edges).  Beyond it the caller is told to come back with fewer blocks (kTooLarge).
-    static const u64 env_mb = [] {
-      const char* e = std::getenv("ZOPFLI_AMD_CODE_BUDGET_MB");
-      return e ? static_cast<u64>(std::max<long>(1, std::atol(e))) : 0ull;
-    }();
+    const u64 env_mb = Knobs().code_budget_mb;
     const u64 budget = (env_mb ? env_mb * (1ull << 20) : static_cast<u64>(c->code_budget)) / sizeof(u16);
     std::vector<u64> code_base(nb, 0);
     u64 cur = 0;
@@ -1341,9 +1297,7 @@ static int BuildDpRows(zmx_ctx* c, zmx_tables* t) {
       cur += ((t->block_edges[b] + DP_PIECE - 1) & ~static_cast<u64>(DP_PIECE - 1)) + DP_PIECE;   // (the ring's DMA reads whole pieces)
     }
     if (cur > budget && nb > 1) {
-      g_err = "zmx_tables_build: the batch needs more room for its DP edges than ZOPFLI_AMD_CODE_BUDGET_MB allows";
-      g_err_class = ZMX_ERR_REFUSED;   // (this batch, anywhere; the caller comes back with fewer blocks)
-      return kTooLarge;
+      return FailTooLarge("zmx_tables_build: the batch needs more room for its DP edges than ZOPFLI_AMD_CODE_BUDGET_MB allows");
     }
     HIPCHK(PoolAlloc(c, &t->d_codes, cur + 2048));   // (k_dp5_spec stages whole KB: it reads a little past a window's rows)
     HIPCHK(hipMemcpyAsync(t->d_code_base, code_base.data(), nb * sizeof(u64), hipMemcpyHostToDevice, c->stream));
@@ -1387,7 +1341,7 @@ static int BuildDpRows(zmx_ctx* c, zmx_tables* t) {
 // Phase 7: the chain's tasks (zmx_dp4.h): SEG_L positions each, the last one of a block takes the remainder
 static int BuildChainTasks(zmx_ctx* c, zmx_tables* t) {
   const size_t nb = t->nb;
-  const u32 L = SegL(t->total_b), warm = SegWarm();
+  const u32 L = SegL(t->total_b), warm = Knobs().seg_warm;
   const u32 head = std::max(SegHead(nb), L);
   t->task_off.assign(nb + 1, 0);
   t->tasks.clear();
@@ -1417,12 +1371,12 @@ static int BuildChainTasks(zmx_ctx* c, zmx_tables* t) {
   HIPCHK(PoolAlloc(c, &t->d_redo, 4 + nt * 4));
   HIPCHK(hipMemcpyAsync(t->d_tasks, t->tasks.data(), nt * sizeof(SegTask), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(t->d_task_off, t->task_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(t->d_segstats, 0, 8 * sizeof(u32), c->stream));
+  HIPCHK(hipMemsetAsync(t->d_segstats, 0, RunLayout::kStats * sizeof(u32), c->stream));
   // start the tasks at cut points of the DP where there is one close enough (zmx_dp5.h: k_cutpoints);
   // ZOPFLI_AMD_SEG_CUTS = how far before a task's first owned position to look, 0 = every task warms up
   // (the search costs 1.1 ms per 100 MB at 1024, the configuration the whole GPU suite ran with; 512 would halve
   //  it and finds the same cut point for 99.8 % of the tasks of text)
-  static const u32 cut_depth = EnvU32("ZOPFLI_AMD_SEG_CUTS", 1024, 0, 1u << 16);
+  const u32 cut_depth = Knobs().seg_cuts;
   if (cut_depth && nt) {
     PoolScope tmp(c);
     u32* d_found = nullptr;
@@ -1441,7 +1395,6 @@ static int BuildChainTasks(zmx_ctx* c, zmx_tables* t) {
     cp.wide = d_wide;
     hipLaunchKernelGGL(k_cutpoints, dim3(static_cast<unsigned>(nt)), dim3(64), 0, c->stream, cp);
     KCHK(c, "k_cutpoints");
-    static const bool prof = std::getenv("ZOPFLI_AMD_PROF") != nullptr;
     u32 found[2] = {0, 0};
     std::vector<u32> wide(nt);
     HIPCHK(hipMemcpyAsync(found, d_found, sizeof(found), hipMemcpyDeviceToHost, c->stream));
@@ -1473,7 +1426,7 @@ static int BuildChainTasks(zmx_ctx* c, zmx_tables* t) {
       HIPCHK(hipMemcpyAsync(t->d_task_off, t->task_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
     }
-    if (prof) {
+    if (Knobs().prof) {
       std::fprintf(stderr, "k_cutpoints: %u of %zu tasks start at a cut point, %.1f positions before their first owned one on average; "
                    "%zu tasks merged into their predecessors (long-run material in the warm-up stretch), %zu tasks left\n",
                    found[0], nt, found[0] ? static_cast<double>(found[1]) / found[0] : 0.0, merged, t->tasks.size());
@@ -1546,7 +1499,83 @@ static int BuildTraceSegments(zmx_ctx* c, zmx_tables* t) {
   return 0;
 }
 
-static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_tables* t, zmx_tables* parent = nullptr, bool with_dp = true) {
+// Last: the kernels' parameter blocks, as far as they depend on the table set alone (TableParams).  No array of the set
+// moves after this (but its pool may go to a set built from it: BuildMatchRecords).
+static void FillTableParams(zmx_tables* t, bool with_dp) {
+  const u32 nb = static_cast<u32>(t->nb);
+  GreedySegParams& gp = t->params.greedy;
+  gp.blocks = t->d_blocks;
+  gp.seg_off = t->d_seg_off;
+  gp.nb = nb;
+  gp.recs = t->d_recs;
+  gp.hist_out = t->d_hist;
+  gp.nsym_out = t->d_nsym;
+  gp.extab = t->d_extab;
+  gp.seginfo = t->d_seginfo;
+  if (!with_dp) return;
+  const RunLayout& run = t->run;
+  WtabParams& wp = t->params.wtab;
+  wp.cost = run.cost(t->d_runin);
+  wp.mincost = run.mincost(t->d_runin);
+  wp.wtab = t->d_wtab;
+  wp.badcodes = t->d_badcodes;
+  wp.stats = t->d_segstats;
+  BadScanParams& bp = t->params.badscan;
+  bp.blocks = t->d_blocks;
+  bp.tile_off = t->d_tile_off;
+  bp.nb_total = nb;
+  bp.dph = t->d_dph;
+  bp.codes = t->d_codes;
+  bp.code_base = t->d_code_base;
+  bp.badcodes = t->d_badcodes;
+  bp.badpos = t->d_badpos;
+  Dp4Params& cp = t->params.dp;      // (block0, task0, redo_pass = 0, est_bits, prof, mid = null: per run)
+  cp.blocks = t->d_blocks;
+  cp.dph = t->d_dph;
+  cp.cost = wp.cost;
+  cp.mincost = wp.mincost;
+  cp.codes = t->d_codes;
+  cp.code_base = t->d_code_base;
+  cp.block_edges = t->d_block_edges;
+  cp.wtab = t->d_wtab;
+  cp.la = t->d_la;
+  cp.badpos = t->d_badpos;
+  cp.tasks = t->d_tasks;
+  cp.task_off = t->d_task_off;
+  cp.lvl = t->d_lvl;
+  cp.entry = t->d_entry;
+  cp.exit = t->d_exit;
+  cp.chk = t->d_chk;
+  cp.over = t->d_over;
+  cp.wmax = run.wmax(t->d_runin);
+  cp.tiemask = run.tiemask(t->d_runin);
+  cp.stats = t->d_segstats;
+  cp.wg_tasks = t->d_wg_tasks;
+  cp.redo_count = t->d_redo;
+  cp.redo_wg = t->d_redo + 4;
+  cp.flags = t->d_flags;
+  cp.wmeta = t->d_wmeta;
+  cp.winroff = t->d_winroff;
+  cp.winflag = t->d_winflag;
+  cp.win_off = t->d_win_off;
+  TraceSegParams& tp = t->params.trace;      // (block0, seg0 = 0)
+  tp.blocks = t->d_blocks;
+  tp.seg_off = t->d_seg_off;
+  tp.nb_total = nb;
+  tp.recs = t->d_recs;
+  tp.pool = t->d_pool;
+  tp.la = t->d_la;
+  tp.slot = t->d_slot;
+  tp.store0 = t->d_store[0];
+  tp.store1 = t->d_store[1];
+  tp.hist_out = t->d_hist;
+  tp.nsym_out = t->d_nsym;
+  tp.flags = t->d_flags;
+  tp.extab = t->d_extab;
+  tp.seginfo = t->d_seginfo;
+}
+
+static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_tables* t, zmx_tables* parent, bool with_dp) {
   const int mk = MatchKernel();   // (one choice per build: zmx_set_match_kernel may be called meanwhile)
   t->matches_only = !with_dp;
   u64 la_off = 0, max_l = 0;
@@ -1565,19 +1594,56 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
     if (const int rc = BuildChainTasks(c, t)) return rc;
     if (const int rc = BuildWorkgroupLists(c, t)) return rc;
   }
-  return BuildTraceSegments(c, t);
+  if (const int rc = BuildTraceSegments(c, t)) return rc;
+  FillTableParams(t, with_dp);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// What the entries check of their arguments before they touch anything.  `who` is the entry's name: the messages
+// start with it.
+// ---------------------------------------------------------------------------------------------
+enum TableNeeds {
+  kAnyTables,     // the stores are enough (they survive zmx_tables_trim)
+  kUntrimmed,     // ... the match records and what goes with them
+  kWithDp,        // ... and DP rows, codes, windows and tasks (not zmx_tables_build_matches)
+};
+static int CheckTables(const char* who, const zmx_tables* t, TableNeeds needs) {
+  const std::string w(who);
+  if (!t) return FailMsg(w + ": no tables");
+  if (needs >= kUntrimmed && t->trimmed) return FailMsg(w + ": these tables were trimmed to their stores (zmx_tables_trim)");
+  if (needs >= kWithDp && t->matches_only) return FailMsg(w + ": these tables hold matches only (zmx_tables_build_matches)");
+  return 0;
+}
+// symbols [0, nsym) of the store in `slot` of `block`
+static int CheckStoreRef(const char* who, const zmx_tables* t, size_t block, int slot, size_t nsym) {
+  if (block >= t->nb || (slot != 0 && slot != 1)) return FailMsg(std::string(who) + ": bad block or slot");
+  if (t->store_begin[slot][block] + nsym > t->bsize[block]) return FailMsg(std::string(who) + ": nsym exceeds the store");
+  return 0;
+}
+// The pinned staging buffer of a context holds at least `words` u32 (grow-only, with a quarter to spare).
+static int StageReserve(zmx_ctx* c, size_t words) {
+  if (words <= c->stage_cap) return 0;
+  if (c->h_stage) HIPCHK(hipHostFree(c->h_stage));
+  c->h_stage = nullptr;
+  c->stage_cap = 0;
+  const size_t cap = words + words / 4 + 16;
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), cap * sizeof(u32), hipHostMallocDefault));
+  c->stage_cap = cap;
+  return 0;
 }
 
 int zmx_tables_build(zmx_ctx* c, const zmx_block* blocks, size_t nblocks, zmx_tables** out) {
   return zmx_tables_build_from(c, nullptr, blocks, nblocks, out);
 }
 
-int zmx_tables_build_matches(zmx_ctx* c, const zmx_block* blocks, size_t nblocks, zmx_tables** out) {
+// A new table set over `blocks`: 0, -1 with the error set, or kTooLarge.
+static int BuildTablesEntry(zmx_ctx* c, zmx_tables* parent, const zmx_block* blocks, size_t nblocks, bool with_dp, zmx_tables** out) {
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   zmx_tables* t = new zmx_tables();
   g_last_oom = false;
-  const int rc = BuildTables(c, blocks, nblocks, t, nullptr, false);
+  const int rc = BuildTables(c, blocks, nblocks, t, parent, with_dp);
   if (rc) {
     zmx_tables_free(c, t);
     // out of device memory (other contexts of the device hold theirs): the caller may come back with fewer blocks,
@@ -1588,37 +1654,29 @@ int zmx_tables_build_matches(zmx_ctx* c, const zmx_block* blocks, size_t nblocks
   return 0;
 }
 
+int zmx_tables_build_matches(zmx_ctx* c, const zmx_block* blocks, size_t nblocks, zmx_tables** out) {
+  return BuildTablesEntry(c, nullptr, blocks, nblocks, false, out);
+}
+
+// `parent` (optional): a table set over blocks that contain the new ones.  The match record of a
+// position depends on its block only through the block end (SURVEY A.1): limit = min(258, end -
+// pos), same[] truncated at the end, zero bytes in the hashes of the last two positions.  So the
+// records of a sub-block equal the parent's except where pos + 258 > end or pos lies in the run
+// of equal bytes that reaches the end — only the tiles holding such positions are recomputed,
+// everything else is copied.  Hash links (k_same, k_chain) are rebuilt: they are cheap.
 int zmx_tables_build_from(zmx_ctx* c, zmx_tables* parent, const zmx_block* blocks, size_t nblocks, zmx_tables** out) {
-  if (parent && parent->trimmed) return FailMsg("zmx_tables_build_from: these tables were trimmed to their stores (zmx_tables_trim)");
-  DeviceGuard dev_guard(c->device);
-  HIPCHK(dev_guard.err);
-  zmx_tables* t = new zmx_tables();
-  g_last_oom = false;
-  const int rc = BuildTables(c, blocks, nblocks, t, parent);
-  if (rc) {
-    zmx_tables_free(c, t);
-    return rc == -1 && g_last_oom && nblocks > 1 ? kTooLarge : rc;
-  }
-  *out = t;
-  return 0;
+  if (parent != nullptr && CheckTables("zmx_tables_build_from", parent, kUntrimmed) != 0) return -1;
+  return BuildTablesEntry(c, parent, blocks, nblocks, true, out);
 }
 
 int zmx_lz77_greedy(zmx_ctx* c, zmx_tables* t, int slot, uint32_t* nsym, uint32_t* hist) {
-  if (t && t->trimmed) return FailMsg("zmx_lz77_greedy: these tables were trimmed to their stores (zmx_tables_trim)");
+  if (const int rc = CheckTables("zmx_lz77_greedy", t, kUntrimmed)) return rc;
   if (t->nb == 0) return 0;
   if (slot != 0 && slot != 1) return FailMsg("zmx_lz77_greedy: slot must be 0 or 1");
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
-  GreedySegParams gp;
-  gp.blocks = t->d_blocks;
-  gp.seg_off = t->d_seg_off;
-  gp.nb = static_cast<u32>(t->nb);
-  gp.recs = t->d_recs;
+  GreedySegParams gp = t->params.greedy;
   gp.store = t->d_store[slot];
-  gp.hist_out = t->d_hist;
-  gp.nsym_out = t->d_nsym;
-  gp.extab = t->d_extab;
-  gp.seginfo = t->d_seginfo;
   const unsigned nseg = t->seg_off[t->nb];
   if (nseg) hipLaunchKernelGGL(k_greedy_exits, dim3(nseg), dim3(GS_THREADS), 0, c->stream, gp);
   KCHK(c, "k_greedy_exits");
@@ -1778,15 +1836,12 @@ static int TraceAndCollect(zmx_ctx* c, zmx_tables* t, const TraceSegParams& tp, 
   KCHK(c, "k_trace_emit");
   HIPCHK(hipGetLastError());
   if (timing) HIPCHK(hipEventRecord(c->ev[3], c->stream));
-  HIPCHK(hipMemcpyAsync(t->h_runout, t->d_runout, t->runout_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(t->h_runout, t->d_runout, t->run.out_bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  const u32* o_hist = reinterpret_cast<const u32*>(t->h_runout);
-  const u32* o_nsym = o_hist + nb * ZMX_HIST;
-  const u32* o_stats = o_nsym + nb;
-  const u32* o_flags = o_stats + 8;
-  std::memcpy(hist, o_hist, nb * ZMX_HIST * sizeof(u32));
-  std::memcpy(nsym, o_nsym, nb * sizeof(u32));
-  std::memcpy(segstats, o_stats, 8 * sizeof(u32));
+  const u32* o_flags = t->run.flags(t->h_runout);
+  std::memcpy(hist, t->run.hist(t->h_runout), nb * ZMX_HIST * sizeof(u32));
+  std::memcpy(nsym, t->run.nsym(t->h_runout), nb * sizeof(u32));
+  std::memcpy(segstats, t->run.stats(t->h_runout), RunLayout::kStats * sizeof(u32));
   if (o_flags[1]) {
     char buf[128];
     std::snprintf(buf, sizeof(buf), "%s: device consistency flags 0x%x", who, o_flags[1]);
@@ -1798,51 +1853,48 @@ static int TraceAndCollect(zmx_ctx* c, zmx_tables* t, const TraceSegParams& tp, 
   return 0;
 }
 
-static TraceSegParams TraceParams(const zmx_tables* t) {
-  TraceSegParams tp;
-  tp.blocks = t->d_blocks;
-  tp.seg_off = t->d_seg_off;
-  tp.nb_total = static_cast<u32>(t->nb);
-  tp.recs = t->d_recs;
-  tp.pool = t->d_pool;
-  tp.la = t->d_la;
-  tp.slot = t->d_slot;
-  tp.store0 = t->d_store[0];
-  tp.store1 = t->d_store[1];
-  tp.hist_out = t->d_hist;
-  tp.nsym_out = t->d_nsym;
-  tp.flags = t->d_flags;
-  tp.extab = t->d_extab;
-  tp.seginfo = t->d_seginfo;
-  tp.block0 = 0;
-  tp.seg0 = 0;
-  return tp;
+// k_dp5_spec over `grid` workgroups of four tasks each: the variant for run tasks or the one for the others, with the
+// profile counters when the run has them
+static void LaunchSpec(hipStream_t stream, unsigned grid, bool run_tasks, const Dp4Params& p) {
+  const dim3 g(grid), b(64 * D5_WG);
+  if (run_tasks) {
+    if (p.prof) hipLaunchKernelGGL((k_dp5_spec<true, 2, true>), g, b, 0, stream, p);
+    else hipLaunchKernelGGL((k_dp5_spec<false, 2, true>), g, b, 0, stream, p);
+  } else {
+    if (p.prof) hipLaunchKernelGGL((k_dp5_spec<true, 4, false>), g, b, 0, stream, p);
+    else hipLaunchKernelGGL((k_dp5_spec<false, 4, false>), g, b, 0, stream, p);
+  }
+}
+// k_dp4_fix, a workgroup per block: the serial pass that accepts the tasks or runs them again
+static void LaunchFix(hipStream_t stream, unsigned nblk, const Dp4Params& p) {
+  const dim3 b(64 * (D3_NB + 2));
+  if (p.prof) hipLaunchKernelGGL(k_dp4_fix<true>, dim3(nblk), b, 0, stream, p);
+  else hipLaunchKernelGGL(k_dp4_fix<false>, dim3(nblk), b, 0, stream, p);
 }
 
 int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double* mincost, const int32_t* slot,
                     uint32_t* nsym, uint32_t* hist) {
-  if (t && t->trimmed) return FailMsg("zmx_squeeze_run: these tables were trimmed to their stores (zmx_tables_trim)");
+  if (const int rc = CheckTables("zmx_squeeze_run", t, kUntrimmed)) return rc;
   if (t->nb == 0) return 0;
-  if (t->matches_only) return FailMsg("zmx_squeeze_run: these tables hold matches only (zmx_tables_build_matches)");
+  if (const int rc = CheckTables("zmx_squeeze_run", t, kWithDp)) return rc;
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   for (size_t b = 0; b < t->nb; ++b) {
     if (slot[b] != 0 && slot[b] != 1) return FailMsg("zmx_squeeze_run: slot must be 0 or 1");
   }
   const size_t nb = t->nb;
+  const zamd::DeviceKnobs& knobs = Knobs();
   bool any_below_mincost = false;
   // the run's input in the pinned mirror: costs, mincosts, slots, and per block what the chain's acceptance test has
   // to know about this cost model (RunInfo)
   {
-    double* h_cost = reinterpret_cast<double*>(t->h_runin);
-    double* h_min = h_cost + nb * ZMX_HIST;
-    float* wmax = reinterpret_cast<float*>(h_min + nb);
-    u32* tiemask = reinterpret_cast<u32*>(wmax + nb);
-    float* est = wmax + 2 * nb;
-    int* h_slot = reinterpret_cast<int*>(wmax + 3 * nb);
-    std::memcpy(h_cost, cost, nb * ZMX_HIST * sizeof(double));
-    std::memcpy(h_min, mincost, nb * sizeof(double));
-    std::memcpy(h_slot, slot, nb * sizeof(int));
+    const RunLayout& run = t->run;
+    float* wmax = run.wmax(t->h_runin);
+    u32* tiemask = run.tiemask(t->h_runin);
+    float* est = run.est(t->h_runin);
+    std::memcpy(run.cost(t->h_runin), cost, nb * ZMX_HIST * sizeof(double));
+    std::memcpy(run.mincost(t->h_runin), mincost, nb * sizeof(double));
+    std::memcpy(run.slot(t->h_runin), slot, nb * sizeof(int));
     const u32* hh = t->have_hist ? t->h_hist.data() : nullptr;
     std::vector<char> below(nb, 0);
     zamd::ParallelFor(nb, [&](size_t b) {
@@ -1852,112 +1904,54 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
     });
     for (size_t b = 0; b < nb; ++b) any_below_mincost |= below[b] != 0;
   }
-  HIPCHK(hipMemcpyAsync(t->d_runin, t->h_runin, t->runin_bytes, hipMemcpyHostToDevice, c->stream));
-  static const bool want_prof = std::getenv("ZOPFLI_AMD_PROF") != nullptr;
-  if (want_prof && !t->d_prof) HIPCHK(PoolAlloc(c, &t->d_prof, nb * ZMX_PROF_N));
+  HIPCHK(hipMemcpyAsync(t->d_runin, t->h_runin, t->run.in_bytes, hipMemcpyHostToDevice, c->stream));
+  if (knobs.prof && !t->d_prof) HIPCHK(PoolAlloc(c, &t->d_prof, nb * ZMX_PROF_N));
   if (t->d_prof) HIPCHK(hipMemsetAsync(t->d_prof, 0, nb * ZMX_PROF_N * sizeof(u64), c->stream));
-  WtabParams wp;
-  wp.cost = t->d_cost;
-  wp.mincost = t->d_mincost;
-  wp.wtab = t->d_wtab;
-  wp.badcodes = t->d_badcodes;
-  wp.stats = t->d_segstats;
-  BadScanParams bp;
-  bp.blocks = t->d_blocks;
-  bp.tile_off = t->d_tile_off;
-  bp.nb_total = static_cast<u32>(nb);
-  bp.dph = t->d_dph;
-  bp.codes = t->d_codes;
-  bp.code_base = t->d_code_base;
-  bp.badcodes = t->d_badcodes;
-  bp.badpos = t->d_badpos;
-  Dp4Params cp;
-  cp.blocks = t->d_blocks;
-  cp.block0 = 0;
-  cp.task0 = 0;
-  cp.dph = t->d_dph;
-  cp.cost = t->d_cost;
-  cp.mincost = t->d_mincost;
-  cp.codes = t->d_codes;
-  cp.code_base = t->d_code_base;
-  cp.block_edges = t->d_block_edges;
-  cp.wtab = t->d_wtab;
-  cp.la = t->d_la;
+  // the chain's parameters: the table set's block and what this run adds
+  Dp4Params cp = t->params.dp;
+  cp.est_bits = t->squeeze_runs == 0 ? t->run.est(t->d_runin) : nullptr;
   cp.prof = t->d_prof;
-  cp.badpos = t->d_badpos;
-  cp.tasks = t->d_tasks;
-  cp.task_off = t->d_task_off;
-  cp.lvl = t->d_lvl;
-  cp.est_bits = t->squeeze_runs == 0 ? t->d_runinfo + 2 * nb : nullptr;
-  cp.entry = t->d_entry;
-  cp.exit = t->d_exit;
-  static const bool mid_on = EnvU32("ZOPFLI_AMD_SEG_MID", 1, 0, 1) != 0;   // 0: no mid snapshots (tasks that leave their binade are re-run whole)
-  cp.mid = mid_on ? t->d_mid : nullptr;
-  cp.chk = t->d_chk;
-  cp.over = t->d_over;
-  cp.wmax = t->d_runinfo;
-  cp.tiemask = reinterpret_cast<const u32*>(t->d_runinfo + nb);
-  cp.stats = t->d_segstats;
-  static const float level_scale = [] { const char* e = std::getenv("ZOPFLI_AMD_SEG_SCALE"); return e ? static_cast<float>(std::atof(e)) : 1.0f; }();
-  cp.level_scale = level_scale;
-  cp.wg_tasks = t->d_wg_tasks;
-  static const int seg_debug = [] { const char* e = std::getenv("ZOPFLI_AMD_SEG_DEBUG"); return e ? std::atoi(e) : 0; }();
-  cp.debug = seg_debug;
-  // (ZOPFLI_AMD_FIX_LEAN: 0 = every serial re-run by the lean one-wave job, large = none, unset = by the task's windows; zmx_dp5.h)
-  static const int fix_lean = [] { const char* e = std::getenv("ZOPFLI_AMD_FIX_LEAN"); return e ? std::atoi(e) : -1; }();
-  cp.fix_lean_min = fix_lean;
-  static const int int_path = [] { const char* e = std::getenv("ZOPFLI_AMD_INT_PATH"); return e ? std::atoi(e) : 1; }();
-  cp.int_path = int_path;
-  static const int chain_fast = [] { const char* e = std::getenv("ZOPFLI_AMD_SHORTCUT_CHAIN"); return e ? std::atoi(e) : 1; }();
-  cp.chain_fast = chain_fast;
-  cp.redo_count = t->d_redo;
-  cp.redo_wg = t->d_redo + 4;
-  cp.redo_pass = 0;
-  cp.flags = t->d_flags;
-  cp.wmeta = t->d_wmeta;
-  cp.winroff = t->d_winroff;
-  cp.winflag = t->d_winflag;
-  cp.win_off = t->d_win_off;
+  cp.mid = knobs.seg_mid ? t->d_mid : nullptr;
+  cp.level_scale = knobs.seg_scale;
+  cp.debug = knobs.seg_debug;
+  cp.fix_lean_min = knobs.fix_lean;
+  cp.int_path = knobs.int_path;
+  cp.chain_fast = knobs.shortcut_chain;
   // k_badscan's bitmap: all zero unless some block of this run has a match weight below mincost (RunInfo) — nearly never,
   // and then neither the memset nor the scan is launched (two of a run's ~20 stream operations; a small call is mostly
   // the gaps between them)
   const bool scan_bad = any_below_mincost;
   if (scan_bad || !t->badpos_clean) HIPCHK(hipMemsetAsync(t->d_badpos, 0, t->badpos_words * sizeof(u32), c->stream));
   t->badpos_clean = !scan_bad;
-  const TraceSegParams tp = TraceParams(t);
   double ksec[3] = {0, 0, 0};
   const bool timing = KernelTiming();
-  const dim3 dpdim(64 * (D3_NB + 2));
   {
     const unsigned nblk = static_cast<unsigned>(nb);
     const unsigned tiles = t->tile_off[nb];
     const unsigned ntask = t->task_off[nb];
     if (timing) HIPCHK(hipEventRecord(c->ev[0], c->stream));
     // the run's weights per block, and (rarely) the positions that own an edge below mincost
-    hipLaunchKernelGGL(k_wtab, dim3(nblk), dim3(256), 0, c->stream, wp);
+    hipLaunchKernelGGL(k_wtab, dim3(nblk), dim3(256), 0, c->stream, t->params.wtab);
     KCHK(c, "k_wtab");
-    if (tiles && scan_bad) hipLaunchKernelGGL(k_badscan, dim3(tiles), dim3(256), 0, c->stream, bp);
+    if (tiles && scan_bad) hipLaunchKernelGGL(k_badscan, dim3(tiles), dim3(256), 0, c->stream, t->params.badscan);
     KCHK(c, "k_badscan");
     HIPCHK(hipGetLastError());
     if (timing) HIPCHK(hipEventRecord(c->ev[1], c->stream));
     // the chain: every task speculatively on all CUs (four tasks of a block per workgroup, the workgroups
     // with a head first), then the per-block walk that accepts or re-runs
     {
-      const dim3 bdim(64 * D5_WG);
       // the run tasks on a second stream, beside the others: few and long (one wave may walk 100 000 positions)
       if (t->n_wg_runs) {
         HIPCHK(hipEventRecord(c->ev2[0], c->stream));
         HIPCHK(hipStreamWaitEvent(c->stream2, c->ev2[0], 0));
         Dp4Params cr = cp;
         cr.task0 = t->n_wg;
-        if (cp.prof) hipLaunchKernelGGL((k_dp5_spec<true, 2, true>), dim3(t->n_wg_runs), bdim, 0, c->stream2, cr);
-        else hipLaunchKernelGGL((k_dp5_spec<false, 2, true>), dim3(t->n_wg_runs), bdim, 0, c->stream2, cr);
+        LaunchSpec(c->stream2, t->n_wg_runs, true, cr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev2[1], c->stream2));
       }
       if (t->n_wg) {
-        if (cp.prof) hipLaunchKernelGGL((k_dp5_spec<true, 4, false>), dim3(t->n_wg), bdim, 0, c->stream, cp);
-        else hipLaunchKernelGGL((k_dp5_spec<false, 4, false>), dim3(t->n_wg), bdim, 0, c->stream, cp);
+        LaunchSpec(c->stream, t->n_wg, false, cp);
         HIPCHK(hipGetLastError());
       }
       if (t->n_wg_runs) HIPCHK(hipStreamWaitEvent(c->stream, c->ev2[1], 0));
@@ -1971,38 +1965,29 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
       // missed their level (ZOPFLI_AMD_SEG_REDO=0: leave them to the serial pass)
       // (ZOPFLI_AMD_SEG_REDO = how many such passes, default 1.  More settle more tasks before the serial pass — class Z:
       //  87 / 92 / 93 % accepted with 1 / 2 / 3 — but every pass waits for its longest task: 1 264 / 1 362 / 1 601 ms)
-      static const int redo = [] { const char* e = std::getenv("ZOPFLI_AMD_SEG_REDO"); return e ? std::atoi(e) : 1; }();
-      for (int pass = 0; pass < redo; ++pass) {
+      for (int pass = 0; pass < knobs.seg_redo; ++pass) {
         // (the list's counter was zeroed by the k_dpcheck before: zmx_dp4.h)
         hipLaunchKernelGGL(k_dpscan, dim3(nblk), dim3(64), 0, c->stream, cp);
         KCHK(c, "k_dpscan");
         Dp4Params c2 = cp;
         c2.redo_pass = 1;
         c2.est_bits = nullptr;
-        // (one workgroup per listed task; the workgroups beyond the list have nothing to do)
-        const unsigned cap = ntask;
-        // (the variant for run tasks wherever the set has any: what is run again there is mostly theirs)
-        if (t->n_wg_runs) {
-          if (cp.prof) hipLaunchKernelGGL((k_dp5_spec<true, 2, true>), dim3(cap), dim3(64 * D5_WG), 0, c->stream, c2);
-          else hipLaunchKernelGGL((k_dp5_spec<false, 2, true>), dim3(cap), dim3(64 * D5_WG), 0, c->stream, c2);
-        } else {
-          if (cp.prof) hipLaunchKernelGGL((k_dp5_spec<true, 4, false>), dim3(cap), dim3(64 * D5_WG), 0, c->stream, c2);
-          else hipLaunchKernelGGL((k_dp5_spec<false, 4, false>), dim3(cap), dim3(64 * D5_WG), 0, c->stream, c2);
-        }
+        // (one workgroup per listed task; the workgroups beyond the list have nothing to do.  The variant for run tasks
+        //  wherever the set has any: what is run again there is mostly theirs)
+        LaunchSpec(c->stream, ntask, t->n_wg_runs != 0, c2);
         KCHK(c, "k_dp5_spec");
         hipLaunchKernelGGL(k_dpcheck, dim3(ntask), dim3(64), 0, c->stream, cp);
         KCHK(c, "k_dpcheck");
       }
-      if (cp.prof) hipLaunchKernelGGL(k_dp4_fix<true>, dim3(nblk), dpdim, 0, c->stream, cp);
-      else hipLaunchKernelGGL(k_dp4_fix<false>, dim3(nblk), dpdim, 0, c->stream, cp);
+      LaunchFix(c->stream, nblk, cp);
       KCHK(c, "k_dp4_fix");
     }
     HIPCHK(hipGetLastError());
     if (timing) HIPCHK(hipEventRecord(c->ev[2], c->stream));
   }
   // the walk back over length_array, the symbols, and the run's ONE host round trip (TraceAndCollect)
-  u32 segstats[8];
-  if (const int rc = TraceAndCollect(c, t, tp, slot, nsym, hist, timing, segstats, "zmx_squeeze_run")) return rc;
+  u32 segstats[RunLayout::kStats];
+  if (const int rc = TraceAndCollect(c, t, t->params.trace, slot, nsym, hist, timing, segstats, "zmx_squeeze_run")) return rc;
   for (int i = 0; i < 3 && timing; ++i) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
@@ -2026,8 +2011,7 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
 // device's own business (flags 2 and 4 of k_trace_emit).
 int zmx_trace_length_arrays(zmx_ctx* c, zmx_tables* t, size_t nblocks, const uint16_t* const* length_arrays,
                             const size_t* entries, const int32_t* slot, uint32_t* nsym, uint32_t* hist) {
-  if (t && t->trimmed) return FailMsg("zmx_trace_length_arrays: these tables were trimmed to their stores (zmx_tables_trim)");
-  if (t->matches_only) return FailMsg("zmx_trace_length_arrays: these tables hold matches only (zmx_tables_build_matches)");
+  if (const int rc = CheckTables("zmx_trace_length_arrays", t, kWithDp)) return rc;
   if (nblocks != t->nb) return FailMsg("zmx_trace_length_arrays: one length array per block of the tables");
   const size_t nb = t->nb;
   if (nb == 0) return 0;
@@ -2053,24 +2037,24 @@ int zmx_trace_length_arrays(zmx_ctx* c, zmx_tables* t, size_t nblocks, const uin
   std::vector<u16> rows(last.la_off + ((static_cast<u64>(t->bsize[nb - 1]) + 1 + 7) & ~7ull), 0);
   for (size_t b = 0; b < nb; ++b) std::memcpy(rows.data() + t->blocks[b].la_off, length_arrays[b], entries[b] * sizeof(u16));
   HIPCHK(hipMemcpy(t->d_la, rows.data(), rows.size() * sizeof(u16), hipMemcpyHostToDevice));
-  int* h_slot = reinterpret_cast<int*>(t->h_runin + (reinterpret_cast<unsigned char*>(t->d_slot) - t->d_runin));
+  int* h_slot = t->run.slot(t->h_runin);
   std::memcpy(h_slot, slot, nb * sizeof(int));
   HIPCHK(hipMemcpyAsync(t->d_slot, h_slot, nb * sizeof(int), hipMemcpyHostToDevice, c->stream));
   // (the flag words are zeroed when the tables are built and by nothing a squeeze run launches: this call judges its
   //  own arrays alone, and what it reports must not fail the next call on these tables too)
-  HIPCHK(hipMemsetAsync(t->d_flags, 0, 4 * sizeof(u32), c->stream));
-  u32 segstats[8];
-  const int rc = TraceAndCollect(c, t, TraceParams(t), slot, nsym, hist, false, segstats, "zmx_trace_length_arrays");
-  if (rc) (void)hipMemsetAsync(t->d_flags, 0, 4 * sizeof(u32), c->stream);
+  HIPCHK(hipMemsetAsync(t->d_flags, 0, RunLayout::kFlags * sizeof(u32), c->stream));
+  u32 segstats[RunLayout::kStats];
+  const int rc = TraceAndCollect(c, t, t->params.trace, slot, nsym, hist, false, segstats, "zmx_trace_length_arrays");
+  if (rc) (void)hipMemsetAsync(t->d_flags, 0, RunLayout::kFlags * sizeof(u32), c->stream);
   return rc;
 }
 
 int zmx_store_download(zmx_ctx* c, zmx_tables* t, size_t block, int slot, uint16_t* litlens, uint16_t* dists,
                        size_t nsym) {
-  if (block >= t->nb || (slot != 0 && slot != 1)) return FailMsg("zmx_store_download: bad block or slot");
+  if (const int rc = CheckTables("zmx_store_download", t, kAnyTables)) return rc;
+  if (const int rc = CheckStoreRef("zmx_store_download", t, block, slot, nsym)) return rc;
   if (nsym == 0) return 0;
   const u32 begin = t->store_begin[slot][block];
-  if (begin + nsym > t->bsize[block]) return FailMsg("zmx_store_download: nsym exceeds the store");
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   std::vector<u32> tmp(nsym);
@@ -2086,24 +2070,16 @@ int zmx_store_download(zmx_ctx* c, zmx_tables* t, size_t block, int slot, uint16
 
 int zmx_store_download_batch(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, const int32_t* slot,
                              const size_t* nsym, uint16_t* const* litlens, uint16_t* const* dists) {
+  if (const int rc = CheckTables("zmx_store_download_batch", t, kAnyTables)) return rc;
   std::vector<size_t> off(n + 1, 0);
   for (size_t i = 0; i < n; ++i) {
-    if (block[i] >= t->nb || (slot[i] != 0 && slot[i] != 1)) return FailMsg("zmx_store_download_batch: bad block or slot");
-    if (t->store_begin[slot[i]][block[i]] + nsym[i] > t->bsize[block[i]])
-      return FailMsg("zmx_store_download_batch: nsym exceeds the store");
+    if (const int rc = CheckStoreRef("zmx_store_download_batch", t, block[i], slot[i], nsym[i])) return rc;
     off[i + 1] = off[i] + nsym[i];
   }
   if (off[n] == 0) return 0;
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
-  if (off[n] > c->stage_cap) {
-    if (c->h_stage) HIPCHK(hipHostFree(c->h_stage));
-    c->h_stage = nullptr;
-    c->stage_cap = 0;
-    const size_t cap = off[n] + off[n] / 4;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), cap * sizeof(u32), hipHostMallocDefault));
-    c->stage_cap = cap;
-  }
+  if (const int rc = StageReserve(c, off[n])) return rc;
   // every store in one go into pinned memory, one synchronisation, then the split into the
   // reference's two u16 arrays on the host workers
   for (size_t i = 0; i < n; ++i) {
@@ -2126,12 +2102,11 @@ int zmx_store_download_batch(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* 
 }
 
 int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, const int32_t* slot, const size_t* nsym) {
-  if (t && t->trimmed) return FailMsg("zmx_verify_stores: these tables were trimmed to their stores (zmx_tables_trim)");
+  if (const int rc = CheckTables("zmx_verify_stores", t, kUntrimmed)) return rc;
   if (n == 0) return 0;
   std::vector<VerifyJob> vj(n);
   for (size_t i = 0; i < n; ++i) {
-    if (block[i] >= t->nb || (slot[i] != 0 && slot[i] != 1)) return FailMsg("zmx_verify_stores: bad block or slot");
-    if (t->store_begin[slot[i]][block[i]] + nsym[i] > t->bsize[block[i]]) return FailMsg("zmx_verify_stores: nsym exceeds the store");
+    if (const int rc = CheckStoreRef("zmx_verify_stores", t, block[i], slot[i], nsym[i])) return rc;
     vj[i].sym_off = t->blocks[block[i]].pos_off + t->store_begin[slot[i]][block[i]];
     vj[i].instart = t->blocks[block[i]].instart;
     vj[i].inend = t->blocks[block[i]].inend;
@@ -2164,8 +2139,7 @@ int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, 
     static const char* why[4] = {"", "length or distance out of range", "the bytes it stands for are not the input's", "the symbols do not add up to the block"};
     char msg[200];
     std::snprintf(msg, sizeof(msg), "zmx_verify_stores: block %zu, symbol %u: %s", block[i], (bad[2 * i] >> 2) - 1, why[bad[2 * i] & 3]);
-    g_err = msg;
-    return -1;
+    return FailFault(msg);   // (the device found the parse wrong: another context may fare better)
   }
   return 0;
 }
@@ -2252,13 +2226,13 @@ int zmx_checksums(zmx_ctx* c, int kind, size_t n, const uint64_t* begin, const u
 int zmx_encode_blocks(zmx_ctx* c, zmx_tables* t, size_t njobs, const zmx_enc_job* jobs, const uint32_t* codes,
                       unsigned char* const* out) {
   if (njobs == 0) return 0;
+  if (const int rc = CheckTables("zmx_encode_blocks", t, kAnyTables)) return rc;
   std::vector<EncJob> ej(njobs);
   std::vector<u32> tile_job;
   std::vector<size_t> out_off(njobs + 1, 0);     // in the device / staging buffer, 8-byte aligned
   for (size_t j = 0; j < njobs; ++j) {
     const zmx_enc_job& q = jobs[j];
-    if (q.block >= t->nb || (q.slot != 0 && q.slot != 1)) return FailMsg("zmx_encode_blocks: bad block or slot");
-    if (t->store_begin[q.slot][q.block] + q.nsym > t->bsize[q.block]) return FailMsg("zmx_encode_blocks: nsym exceeds the store");
+    if (const int rc = CheckStoreRef("zmx_encode_blocks", t, q.block, q.slot, q.nsym)) return rc;
     out_off[j + 1] = out_off[j] + (((q.bit_start + q.nbits + 7) / 8 + 8 + 7) & ~static_cast<size_t>(7));
     EncJob& e = ej[j];
     e.sym_off = t->blocks[q.block].pos_off + t->store_begin[q.slot][q.block];
@@ -2311,14 +2285,7 @@ int zmx_encode_blocks(zmx_ctx* c, zmx_tables* t, size_t njobs, const zmx_enc_job
   KCHK(c, "k_enc_emit");
   HIPCHK(hipGetLastError());
   // down through the pinned staging buffer, then into the caller's memory on the host workers
-  if (out_words + 1 > c->stage_cap) {
-    if (c->h_stage) HIPCHK(hipHostFree(c->h_stage));
-    c->h_stage = nullptr;
-    c->stage_cap = 0;
-    const size_t cap = out_words + out_words / 4 + 16;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), cap * sizeof(u32), hipHostMallocDefault));
-    c->stage_cap = cap;
-  }
+  if (const int rc = StageReserve(c, out_words + 1)) return rc;
   u32 flag = 0;
   HIPCHK(hipMemcpyAsync(c->h_stage, d_out, out_words * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(&flag, d_flag, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
@@ -2488,7 +2455,7 @@ int zmx_match_digest(zmx_ctx* c, zmx_tables* t, uint64_t* out2) {
 
 int zmx_find_longest_match(zmx_ctx* c, zmx_tables* t, size_t block, size_t pos, uint16_t* sublen,
                            uint16_t* distance, uint16_t* length) {
-  if (t && t->trimmed) return FailMsg("zmx_find_longest_match: these tables were trimmed to their stores (zmx_tables_trim)");
+  if (const int rc = CheckTables("zmx_find_longest_match", t, kUntrimmed)) return rc;
   if (block >= t->nb) return FailMsg("zmx_find_longest_match: bad block");
   const BlockDesc& d = t->blocks[block];
   if (pos < d.instart || pos >= d.inend) return FailMsg("zmx_find_longest_match: pos outside the block");
@@ -2533,7 +2500,7 @@ int zmx_find_longest_match(zmx_ctx* c, zmx_tables* t, size_t block, size_t pos, 
 }
 
 int zmx_hash_links_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* same, uint16_t* prev1, uint16_t* prev2) {
-  if (t && t->trimmed) return FailMsg("zmx_hash_links_download: these tables were trimmed to their stores (zmx_tables_trim)");
+  if (const int rc = CheckTables("zmx_hash_links_download", t, kUntrimmed)) return rc;
   if (block >= t->nb) return FailMsg("zmx_hash_links_download: bad block");
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
@@ -2551,7 +2518,7 @@ int zmx_hash_links_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* s
 }
 
 int zmx_length_array_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* out) {
-  if (t && t->trimmed) return FailMsg("zmx_length_array_download: these tables were trimmed to their stores (zmx_tables_trim)");
+  if (const int rc = CheckTables("zmx_length_array_download", t, kUntrimmed)) return rc;
   if (block >= t->nb) return FailMsg("zmx_length_array_download: bad block");
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
@@ -2646,12 +2613,12 @@ int zmx_cost_stores_create(zmx_ctx* c, zmx_tables* t, size_t nstores, const size
                            const int32_t* slot, const size_t* nsym, zmx_cost_stores** out) {
   *out = nullptr;
   if (nstores == 0) return FailMsg("zmx_cost_stores_create: no sequence");
+  if (const int rc = CheckTables("zmx_cost_stores_create", t, kAnyTables)) return rc;
   const size_t np = piece_first[nstores];
   std::vector<size_t> total(nstores, 0);
   for (size_t s = 0; s < nstores; ++s) {
     for (size_t p = piece_first[s]; p < piece_first[s + 1]; ++p) {
-      if (block[p] >= t->nb || (slot[p] != 0 && slot[p] != 1)) return FailMsg("zmx_cost_stores_create: bad block or slot");
-      if (t->store_begin[slot[p]][block[p]] + nsym[p] > t->bsize[block[p]]) return FailMsg("zmx_cost_stores_create: nsym exceeds the store");
+      if (const int rc = CheckStoreRef("zmx_cost_stores_create", t, block[p], slot[p], nsym[p])) return rc;
       total[s] += nsym[p];
     }
   }
@@ -2786,7 +2753,7 @@ int zmx_block_costs(zmx_ctx* c, zmx_cost_stores* s, size_t n, const uint32_t* ra
   P.out = s->d_out;
   P.n = static_cast<u32>(n);
   P.prof = nullptr;
-  static const bool bc_prof = std::getenv("ZOPFLI_AMD_BC_PROF") != nullptr;
+  const bool bc_prof = Knobs().bc_prof;
   PoolScope tmp(c);
   if (bc_prof) {
     HIPCHK(tmp.AllocT(&P.prof, 16, "bc_prof"));
