@@ -1,7 +1,7 @@
 """Generates tests/golden/vectors.json from the REAL reference (oracle/_ref/libzopfli_ref.so,
 compiled from /root/reference by oracle/Makefile).  Run in the build container:
 
-    python tests/golden/make_golden.py [--big | --big2 | --big3 | --extra | --part]
+    python tests/golden/make_golden.py [--big | --big2 | --big3 | --extra | --part | --host-paths]
 
 Each vector: synthetic class / size / seed (zopfli_amd.datagen) or a literal input, the
 ZopfliOptions used, the format, and the SHA-256 + length of the reference's output.
@@ -170,7 +170,29 @@ def run_part(case):
     return case
 
 
+def host_paths_case():
+    """The mix on which every phase of the host layer has work (tests/test_gpu_host_paths.py, and the device-split case
+    of tests/test_cpu_host_stream.py): three master blocks; the first split finds points, the second split is tried, a
+    fixed-tree re-parse is requested (six; none wins), and dynamic and stored blocks are written."""
+    return dict(input=[dict(cls="M", size=1100000), dict(cls="R", size=400000), dict(cls="T", size=700000)],
+                format=0, numiterations=2, blocksplitting=1, blocksplittingmax=15)
+
+
+def run_host_paths(case):
+    import oracle_lib as ol
+    from zopfli_amd import generate
+    data = b"".join(generate(i["cls"], i["size"]) for i in case["input"])
+    out = ol.ref_compress(data, case["format"], case["numiterations"], case["blocksplitting"], case["blocksplittingmax"])
+    return dict(case, sha256=hashlib.sha256(out).hexdigest(), outsize=len(out))
+
+
 def main():
+    if "--host-paths" in sys.argv:
+        path = os.path.join(HERE, "host_paths.json")
+        with open(path, "w") as f:
+            json.dump(run_host_paths(host_paths_case()), f, indent=1)
+        print("wrote", path)
+        return
     if "--part" in sys.argv:
         done = [run_part(c) for c in part_cases()]
         path = os.path.join(HERE, "vectors_part.json")

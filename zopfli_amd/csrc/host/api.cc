@@ -57,9 +57,9 @@ using zamd::kMasterBlock;
 // measuring one against the other.
 void MaybeKeepHeap() {
   static const bool once = [] {
-    const char* e = std::getenv("ZOPFLI_AMD_KEEP_HEAP");
-    if (!e || std::atoi(e) == 0) return true;
-    if (std::atoi(e) == 2) {          // (for measuring: large blocks from the heap too — 32 MB is the most glibc takes; no better, nor is 1 MB)
+    const int mode = zamd::HostSwitches().keep_heap;
+    if (mode == 0) return true;
+    if (mode == 2) {          // (for measuring: large blocks from the heap too — 32 MB is the most glibc takes; no better, nor is 1 MB)
       mallopt(M_MMAP_THRESHOLD, 32 << 20);
       mallopt(M_TRIM_THRESHOLD, 1 << 30);
       mallopt(M_TOP_PAD, 64 << 20);
@@ -107,11 +107,7 @@ class ContextPool {
     // a context costs ~ 50 ms to set up and saves such a call 5 - 15 ms, which a program that compresses a few files
     // and exits never earns back (zopflipng on one 1024 x 1024 image: 0.62 -> 0.70 s when its calls set up two more
     // contexts); a long-lived caller pays once.  (The first context a call takes is created whenever none is free.)
-    static const size_t deal_after = [] {
-      const char* e = std::getenv("ZOPFLI_AMD_DEAL_AFTER");
-      return e ? static_cast<size_t>(std::max(0, std::atoi(e))) : static_cast<size_t>(8);
-    }();
-    const bool may_create_more = !polite || per_device <= 1 || ++polite_wishes_ >= deal_after;
+    const bool may_create_more = !polite || per_device <= 1 || ++polite_wishes_ >= zamd::HostSwitches().deal_after;
     for (;;) {
       if (polite && in_flight_ > 1) per_device = 1;
       std::vector<Slot*> slots;
@@ -234,33 +230,8 @@ class ContextPool {
     if (!devices_.empty()) return;
     MaybeKeepHeap();
     const int visible = zmx_device_count();
-    std::vector<int> list;
-    if (const char* e = std::getenv("ZOPFLI_AMD_DEVICES")) {
-      if (std::strcmp(e, "all") == 0) {
-        for (int i = 0; i < visible; ++i) list.push_back(i);
-      } else if (std::strchr(e, ',')) {
-        for (const char* p = e; *p;) {
-          list.push_back(std::atoi(p));
-          const char* q = std::strchr(p, ',');
-          if (!q) break;
-          p = q + 1;
-        }
-      } else {
-        const int n = std::atoi(e);
-        for (int i = 0; i < n && i < visible; ++i) list.push_back(i);
-        if (list.empty()) list.push_back(0);   // ("0": no count — device 0)
-      }
-    } else if (const char* e = std::getenv("ZOPFLI_AMD_DEVICE")) {
-      list.push_back(std::atoi(e));
-    } else if (const char* r = std::getenv("LOCAL_RANK")) {
-      // (one process per GPU under torchrun; with HIP_VISIBLE_DEVICES set per rank every rank sees ONE device and
-      //  LOCAL_RANK = k would name a device that is not there: take it modulo what is visible)
-      const int k = std::atoi(r);
-      list.push_back(visible > 0 && k >= 0 ? k % visible : k);
-    } else {
-      list.push_back(0);
-    }
-    for (int d : list) {
+    const zamd::PoolKnobs knobs = zamd::PoolSwitches(visible);
+    for (int d : knobs.devices) {
       if (d < 0 || d >= visible) {
         std::fprintf(stderr, "zopfli_amd: no HIP device %d (%d visible): ignored\n", d, visible);
         continue;
@@ -273,9 +244,8 @@ class ContextPool {
       zmx_internal_set_error("no HIP device to run on");
       Die("no usable gfx950 device (there is no CPU fallback)");
     }
-    if (const char* e = std::getenv("ZOPFLI_AMD_LANES")) lanes_ = static_cast<size_t>(std::max(1, std::atoi(e)));
-    if (const char* e = std::getenv("ZOPFLI_AMD_SMALL_LANES")) small_lanes_ = static_cast<size_t>(std::max(1, std::atoi(e)));
-    small_lanes_ = std::max(small_lanes_, lanes_);
+    lanes_ = knobs.lanes;
+    small_lanes_ = knobs.small_lanes;
     zmx_set_oom_hook(&ContextPool::OomHook);
   }
   static void OomHook(int device);
@@ -295,10 +265,7 @@ ContextPool& Pool() {
 void ContextPool::OomHook(int device) { Pool().TrimIdle(device); }
 
 // ZOPFLI_AMD_TRACE_CALL=1: where a Zopfli* call's wall time goes, per shard and for the call (stderr)
-bool TraceCall() {
-  static const bool on = [] { const char* e = std::getenv("ZOPFLI_AMD_TRACE_CALL"); return e && std::atoi(e) != 0; }();
-  return on;
-}
+bool TraceCall() { return zamd::HostSwitches().trace_call; }
 double WallMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -310,17 +277,6 @@ struct Lease {
       : ctxs(Pool().Acquire(want, per_device, &device_of, polite, small)) {}
   ~Lease() { Pool().Release(ctxs); }
 };
-
-size_t PartsPerBatch() {
-  static const size_t n = [] {
-    if (const char* e = std::getenv("ZOPFLI_AMD_PARTS_PER_BATCH")) {
-      const long v = std::atol(e);
-      if (v > 0) return static_cast<size_t>(v);
-    }
-    return static_cast<size_t>(256);  // ~40 MB of tables per 1 MB master block
-  }();
-  return n;
-}
 
 std::vector<zamd::Part> MasterBlocks(size_t insize, bool final) {
   // deflate.c:916-923: do { ... } while (i < insize), so an empty input still
@@ -337,12 +293,12 @@ std::vector<zamd::Part> MasterBlocks(size_t insize, bool final) {
 }
 
 // `group_bytes` (batches of many small inputs, zamd::ShardHooks): a DeflateParts call takes parts up to that many bytes
-// instead of PartsPerBatch() parts — 256 parts of 64 KiB would leave the device idle — and at most 2048 of them (a part
+// instead of ZOPFLI_AMD_PARTS_PER_BATCH parts — 256 parts of 64 KiB would leave the device idle — and at most 2048 of them (a part
 // may become 15 blocks or more, and the blocks of a table build are one launch dimension).
 // `part_chunks` (optional): the number of chunks of every part, in part order.
 int RunParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const std::vector<zamd::Part>& parts,
              std::vector<zamd::Chunk>* chunks, std::vector<size_t>* part_chunks = nullptr, size_t group_bytes = 0) {
-  size_t step = PartsPerBatch();
+  size_t step = zamd::HostSwitches().parts_per_batch;
   size_t step_bytes = group_bytes;
   for (size_t a = 0; a < parts.size();) {
     size_t b = a + step < parts.size() ? a + step : parts.size();
@@ -382,6 +338,259 @@ struct ChecksumRequest {
   uint32_t value;
 };
 
+struct Shard {
+  size_t first = 0, last = 0, base = 0;
+  std::vector<zamd::Chunk> chunks;
+  std::vector<size_t> part_chunks;
+  int rc = 0;
+  std::string err;
+  int err_class = ZMX_ERR_NONE;   // zmx_last_error_class() of the failure
+  zamd::Timing timing;
+  uint32_t sum = 0;
+  size_t sum_bytes = 0;
+  bool redone = false;
+  double stats[19] = {0};        // the shard thread's kernel / match / task statistics (zmx_internal_stats_take)
+};
+
+// The contexts of ONE device take their bytes over the same link: asked for at once, three uploads end together and
+// the device has nothing to do until then (12 ms of a 122 ms call on 100 MB; the kernel timeline of
+// tools/r04_timeline.sh).  One after the other, in stream order, the first context computes while the second's bytes
+// travel — and the contexts stay out of step from there on: their host phases (block split, cost models) fall
+// beside the others' kernels instead of beside each other.
+struct UploadOrder {
+  std::mutex mu;
+  std::condition_variable cv;
+  std::vector<char> done;
+  std::vector<long> after;     // the shard whose upload this one waits for, -1 = none (zamd::UploadAfter)
+};
+struct UploadTurn {     // marks a shard's upload as over, however its attempt ends
+  UploadOrder& o; size_t d; bool released = false;
+  void Wait() {
+    if (o.after[d] < 0) return;
+    std::unique_lock<std::mutex> lock(o.mu);
+    o.cv.wait(lock, [&] { return o.done[static_cast<size_t>(o.after[d])] != 0; });
+  }
+  void Release() {
+    if (released) return;
+    released = true;
+    { std::lock_guard<std::mutex> lock(o.mu); o.done[d] = 1; }
+    o.cv.notify_all();
+  }
+  ~UploadTurn() { Release(); }
+};
+
+// A call that is dealt: what its shards share.
+struct ShardedCall {
+  const ZopfliOptions& options;
+  int btype;
+  const unsigned char* in;
+  const std::vector<zamd::Part>& parts;
+  ChecksumRequest* sum;
+  bool want_part_chunks;
+  zamd::ShardHooks* hooks;
+  double t_begin;                 // WallMs() when the call asked for its contexts
+  std::vector<Shard> shards;
+  std::vector<int> priority;      // stream priority of every shard's context
+  UploadOrder order;
+};
+
+// How many contexts of each device the call takes; *runs: its data has long runs of equal bytes.
+//
+// (ZOPFLI_AMD_SPLIT_MB: from this many master blocks on, a request is dealt over ZOPFLI_AMD_SPLIT_WAYS = 3 contexts of
+//  each device — measured on 100 MB of text: 2 ways 123.2 ms, 3 ways 121.1, 4 ways 140; with block splitting 225 / 197 / 231;
+//  0 = never.  The GPU idles while the host computes a hundred cost models between two squeeze runs — 6 % of a
+//  100 MB call — and through the whole block-split search; two halves fill each other's gaps.)
+// Round 5, from how many master blocks on (profiles/r05_split_from.txt): with block splitting from 4 — the contexts'
+// split searches fall beside each other's kernels: 4 MB of text 33.7 -> 29.2 ms, 8 MB 46.5 -> 37.4, 12 MB 59.8 -> 43.6,
+// 24 MB 97.4 -> 62.8 (it was 32 until then); without block splitting it is worth 3 - 6 % from 12 MB on and nothing
+// below: from 16.
+// Data with long runs of equal bytes: there the squeeze runs wait for a few very long single-wave tasks (zmx_dp5.h)
+// and most of the device idles — but a second context's tasks on the same SIMDs slow exactly those tasks (round 3,
+// class Z: 61 -> 35 MB/s on two contexts, so such data stayed on one).  Round 5: dealt all the same, with the contexts
+// at three stream PRIORITIES (as calls with block splitting are, PlanShards): the first context's long tasks win their
+// SIMDs, the others fill what it leaves — class Z 131 -> 190 MB/s, class M 165 -> 245 (189 / 245 on four, 187 / 250 on
+// six contexts; without the priorities 112 / 170; profiles/r05_runs_ctx.txt).  Which data: zamd::LooksLikeRuns.
+// (ZOPFLI_AMD_SPLIT_RUNS=0 or ZOPFLI_AMD_STREAM_PRIO=0: such data on one context, as before — for measuring)
+size_t ContextsPerDevice(const ZopfliOptions& options, int btype, const unsigned char* in,
+                         const std::vector<zamd::Part>& parts, bool* runs) {
+  const zamd::HostKnobs& k = zamd::HostSwitches();
+  const size_t split_from = k.split_mb >= 0 ? static_cast<size_t>(k.split_mb) : (options.blocksplitting && btype == 2 ? 4 : 16);
+  *runs = false;
+  if (!split_from || parts.size() < split_from) return 1;
+  *runs = in != nullptr && zamd::LooksLikeRuns(in, parts.front().instart, parts.back().inend);
+  const bool one_context = *runs && !(k.stream_prio && k.split_runs);
+  return one_context ? 1 : k.split_ways;
+}
+
+// The shards' part ranges, stream priorities and upload order, for contexts on the devices `device_of` (one per shard).
+void PlanShards(ShardedCall* call, const std::vector<int>& device_of, bool runs) {
+  const zamd::HostKnobs& k = zamd::HostSwitches();
+  const std::vector<zamd::Part>& parts = call->parts;
+  const size_t ndev = device_of.size();
+  // Shards of equal COST, not of equal count (deal.h): on a mixed corpus the master blocks of long runs of equal bytes
+  // cost several times the others, and contiguous equal-count shards leave them to one or two contexts.  From the
+  // bytes alone — the one-process-per-GPU launchers compute the same ranges (zmx_master_block_costs).
+  // (ZOPFLI_AMD_DEAL=count: equal counts, as before — for measuring)
+  std::vector<double> cost;
+  if (k.deal_by_cost && ndev > 1 && call->in != nullptr && parts.size() > ndev) {
+    cost.resize(parts.size());
+    zamd::ParallelFor(parts.size(), [&](size_t i) { cost[i] = zamd::MasterBlockCost(call->in, parts[i].instart, parts[i].inend); });
+  }
+  const std::vector<size_t> first = zamd::ShardRanges(parts.size(), ndev, cost.empty() ? nullptr : cost.data(), k.shard_weights);
+  call->shards = std::vector<Shard>(ndev);
+  for (size_t d = 0; d < ndev; ++d) { call->shards[d].first = first[d]; call->shards[d].last = first[d + 1]; }
+  // With block splitting the contexts of one device run at three stream priorities — one after the other instead of
+  // side by side: their split searches and joins then fall beside the others' kernels (zmx_ctx_set_priority; 100 MB of
+  // text 152 -> 145 ms, without block splitting 123 -> 130: there every context stays on its default streams).
+  // Data with runs: with or without block splitting (ContextsPerDevice).
+  // (ZOPFLI_AMD_STREAM_PRIO=0: never; 2: always — for measuring)
+  const bool priorities = k.stream_prio && ((call->options.blocksplitting && call->btype == 2) || runs || k.stream_prio == 2);
+  call->priority = priorities ? zamd::ShardPriorities(device_of) : std::vector<int>(ndev, 0);
+  // (ZOPFLI_AMD_UPLOAD_ORDER=0: all at once, as before — for measuring)
+  call->order.done.assign(ndev, 0);
+  call->order.after = k.upload_order ? zamd::UploadAfter(device_of) : std::vector<long>(ndev, -1);
+}
+
+// (a call that is one shard — a small file — keeps the level its context was given when first seen: the contexts of
+//  concurrent small callers then lie on streams of all three priorities, i.e. on three sets of hardware queues instead of
+//  one — the runtime gives a priority four queues, and sixteen streams on four queues run their short kernels one after
+//  the other: 1 000 files of 64 KiB through 16 callers 26.8 -> 29.9 MB/s, 160 of 1 MB 220 -> 283, profiles/r06_small_hwq.txt;
+//  ZOPFLI_AMD_SMALL_PRIO=0: every such call on the default priority, as before)
+int SmallCallLevel(zmx_ctx* ctx) {
+  static std::mutex mu;
+  static std::unordered_map<zmx_ctx*, int> levels;
+  std::lock_guard<std::mutex> g(mu);
+  auto it = levels.find(ctx);
+  if (it == levels.end()) it = levels.emplace(ctx, static_cast<int>(levels.size() % 3) - 1).first;
+  return it->second;
+}
+
+// Shard `d` of the call on `ctx`: upload, checksum, its parts.  `retry`: again, on another shard's context.
+void RunShard(ShardedCall* call, size_t d, zmx_ctx* ctx, bool retry) {
+  const std::vector<zamd::Part>& parts = call->parts;
+  zamd::ShardHooks* hooks = call->hooks;
+  ChecksumRequest* sum = call->sum;
+  Shard& sh = call->shards[d];
+  UploadTurn turn{call->order, d};
+  int level = retry ? 0 : call->priority[d];
+  if (zamd::HostSwitches().small_prio && call->shards.size() == 1 && !retry) level = SmallCallLevel(ctx);
+  if (zmx_ctx_set_priority(ctx, level) != 0) {
+    // (not fatal: the context stays on the streams it has, the shards then run side by side instead of in turn)
+    std::fprintf(stderr, "zopfli_amd: stream priorities unavailable (%s)\n", zmx_last_error());
+  }
+  sh.rc = 0;
+  sh.err.clear();
+  sh.err_class = ZMX_ERR_NONE;
+  sh.chunks.clear();
+  sh.part_chunks.clear();
+  sh.sum = 0;
+  sh.sum_bytes = 0;
+  auto fail = [&] { sh.rc = -1; sh.err = zmx_last_error(); sh.err_class = zmx_last_error_class(); };
+  // (ZOPFLI_AMD_TEST_FAIL_SHARD=k: the k-th shard's first attempt fails before it does anything — the test of the
+  //  re-queue, RetryFailedShards)
+  if (!retry && zamd::HostSwitches().test_fail_shard == static_cast<long>(d)) {
+    sh.rc = -1;
+    sh.err = "injected failure (ZOPFLI_AMD_TEST_FAIL_SHARD): PoolAlloc(pool) too large — the text must not matter";
+    sh.err_class = ZMX_ERR_OUT_OF_MEMORY;
+    return;
+  }
+  const size_t start = parts[sh.first].instart, end = parts[sh.last - 1].inend;
+  sh.base = start > zamd::kWindow ? start - zamd::kWindow : 0;
+  if (hooks) sh.base = std::max(sh.base, hooks->floor(parts[sh.first].instart));
+  const double tr0 = WallMs();
+  if (!retry) turn.Wait();
+  const double tr1 = WallMs();
+  const int up = zmx_set_input(ctx, call->in + sh.base, end - sh.base);
+  turn.Release();
+  const double tr2 = WallMs();
+  if (up != 0 || (hooks && hooks->uploaded(d, ctx, sh.base, sh.first, sh.last) != 0)) return fail();
+  if (sum && start < sum->limit) {
+    sh.sum_bytes = std::min(end, sum->limit) - start;
+    if (zmx_checksum(ctx, sum->kind, start - sh.base, start - sh.base + sh.sum_bytes, &sh.sum) != 0) return fail();
+  }
+  std::vector<zamd::Part> mine(parts.begin() + static_cast<long>(sh.first), parts.begin() + static_cast<long>(sh.last));
+  for (auto& p : mine) { p.instart -= sh.base; p.inend -= sh.base; }
+  const double tr3 = WallMs();
+  struct SplitOnDevice {
+    bool was;
+    explicit SplitOnDevice(bool on) : was(zamd::g_split_on_device) { zamd::g_split_on_device = on || was; }
+    ~SplitOnDevice() { zamd::g_split_on_device = was; }
+  } split_on_device(hooks && hooks->split_on_device);
+  sh.rc = RunParts(ctx, call->options, call->btype, mine, &sh.chunks, call->want_part_chunks ? &sh.part_chunks : nullptr,
+                   hooks ? hooks->group_bytes : 0);
+  if (sh.rc) { sh.err = zmx_last_error(); sh.err_class = zmx_last_error_class(); }
+  if (TraceCall()) {
+    std::fprintf(stderr, "  shard %zu (%zu parts): start +%.2f ms, wait for turn %.2f, upload %.2f, checksum %.2f, parts %.2f, end +%.2f\n",
+                 d, sh.last - sh.first, tr0 - call->t_begin, tr1 - tr0, tr2 - tr1, tr3 - tr2, WallMs() - tr3, WallMs() - call->t_begin);
+  }
+  for (auto& c : sh.chunks) {
+    if (c.kind == zamd::Chunk::kStored) { c.start += sh.base; c.end += sh.base; }
+  }
+  sh.timing = zamd::ThreadTiming();
+  if (d != 0 && !retry) zmx_internal_stats_take(sh.stats);   // (a thread of its own: its sums go to the caller's below)
+}
+
+// Every shard on its context: the first on the calling thread, the others on a thread each.
+void RunShards(ShardedCall* call, const std::vector<zmx_ctx*>& ctxs) {
+  const size_t ndev = call->shards.size();
+  std::vector<std::thread> threads;
+  for (size_t d = 1; d < ndev; ++d) threads.emplace_back(RunShard, call, d, ctxs[d], false);
+  RunShard(call, 0, ctxs[0], false);
+  for (auto& t : threads) t.join();
+  for (size_t d = 1; d < ndev; ++d) zmx_internal_stats_add(call->shards[d].stats);
+  // the slowest device's breakdown stands for the request (zmx_last_timing)
+  for (size_t d = 1; d < ndev; ++d) {
+    const zamd::Timing& a = call->shards[d].timing;
+    zamd::Timing& t = zamd::ThreadTiming();
+    if (a.tables + a.greedy + a.squeeze + a.cost_model + a.split + a.encode >
+        t.tables + t.greedy + t.squeeze + t.cost_model + t.split + t.encode) t = a;
+  }
+}
+
+// A shard that failed (its device ran out of memory, its context is broken) is done again on a context that just
+// finished its own shard without error — another device's where there is one — before the request gives up: the
+// parts are independent (deflate.c:916-923), whoever computes them computes the same bits.
+void RetryFailedShards(ShardedCall* call, const std::vector<zmx_ctx*>& ctxs) {
+  std::vector<Shard>& shards = call->shards;
+  for (size_t d = 0; d < shards.size(); ++d) {
+    if (!shards[d].rc) continue;
+    // (not a failure that would repeat itself on any context — a request the device layer refuses, a table set that
+    //  overflows its pools after the retries the device layer makes itself: ZMX_ERR_REFUSED.  By the error's CLASS, not its
+    //  text: an out-of-memory inside PoolAlloc reads "PoolAlloc(...): out of memory" and is exactly what a retry is for)
+    if (shards[d].err_class == ZMX_ERR_REFUSED) continue;
+    zmx_ctx* other = nullptr;
+    for (size_t e = 0; e < shards.size() && !other; ++e) if (e != d && !shards[e].rc && !shards[e].redone) other = ctxs[e];
+    if (!other) break;
+    std::fprintf(stderr, "zopfli_amd: a shard failed (%s): done again on another context\n", shards[d].err.c_str());
+    RunShard(call, d, other, true);
+    shards[d].redone = true;
+  }
+}
+
+// The shards' chunks (and chunk counts) in stream order; the first failed shard's code, with its text on stderr.
+int CollectShards(ShardedCall* call, std::vector<zamd::Chunk>* chunks, std::vector<size_t>* part_chunks) {
+  for (auto& sh : call->shards) {
+    if (sh.rc) {
+      std::fprintf(stderr, "zopfli_amd: device error: %s\n", sh.err.c_str());
+      if (call->hooks) { call->hooks->error = sh.err; call->hooks->error_class = sh.err_class; }
+      return sh.rc;
+    }
+    for (auto& c : sh.chunks) chunks->push_back(std::move(c));
+    if (part_chunks) part_chunks->insert(part_chunks->end(), sh.part_chunks.begin(), sh.part_chunks.end());
+  }
+  return 0;
+}
+
+// A small call among other calls in flight (many small files, a caller thread each): its host phases — the split
+// searches' rounds of nine probes, the cost models of a block or two — run on the calling thread.  The worker pool takes
+// one fork-join at a time: sixteen callers queueing for it, each job a few microseconds of work per woken thread, were
+// slower than three (profiles/r06_small_files.txt); the callers are the parallelism.
+struct InlineHostWork {
+  bool on, was;
+  explicit InlineHostWork(bool o) : on(o), was(zamd::g_host_inline) { if (on) zamd::g_host_inline = true; }
+  ~InlineHostWork() { if (on) zamd::g_host_inline = was; }
+};
+
 // `hooks` (zmx_compress_batch): `in` is the concatenation of independent inputs — a shard's upload starts no lower than
 // the first byte of its first part's input, the hooks tell the context its segments after the upload, the parts are
 // grouped by bytes; `part_chunks` (optional) gets the number of chunks of every part, in part order.
@@ -389,303 +598,27 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
                         const std::vector<zamd::Part>& parts, std::vector<zamd::Chunk>* chunks,
                         ChecksumRequest* sum = nullptr, std::vector<size_t>* part_chunks = nullptr,
                         zamd::ShardHooks* hooks = nullptr) {
-  // (ZOPFLI_AMD_SPLIT_MB: from this many master blocks on, a request is dealt over ZOPFLI_AMD_SPLIT_WAYS = 3 contexts of
-  //  each device — measured on 100 MB of text: 2 ways 123.2 ms, 3 ways 121.1, 4 ways 140; with block splitting 225 / 197 / 231;
-  //  0 = never.  The GPU idles while the host computes a hundred cost models between two squeeze runs — 6 % of a
-  //  100 MB call — and through the whole block-split search; two halves fill each other's gaps.)
-  // Round 5, from how many master blocks on (profiles/r05_split_from.txt): with block splitting from 4 — the contexts'
-  // split searches fall beside each other's kernels: 4 MB of text 33.7 -> 29.2 ms, 8 MB 46.5 -> 37.4, 12 MB 59.8 -> 43.6,
-  // 24 MB 97.4 -> 62.8 (it was 32 until then); without block splitting it is worth 3 - 6 % from 12 MB on and nothing
-  // below: from 16.
-  static const long split_from_env = [] {
-    const char* e = std::getenv("ZOPFLI_AMD_SPLIT_MB");
-    return e ? static_cast<long>(std::max(0, std::atoi(e))) : -1L;
-  }();
-  const size_t split_from = split_from_env >= 0 ? static_cast<size_t>(split_from_env)
-                                                : (options.blocksplitting && btype == 2 ? 4 : 16);
-  static const size_t split_ways = [] {
-    const char* e = std::getenv("ZOPFLI_AMD_SPLIT_WAYS");
-    return e ? static_cast<size_t>(std::max(1, std::atoi(e))) : static_cast<size_t>(3);
-  }();
-  // Data with long runs of equal bytes: there the squeeze runs wait for a few very long single-wave tasks (zmx_dp5.h)
-  // and most of the device idles — but a second context's tasks on the same SIMDs slow exactly those tasks (round 3,
-  // class Z: 61 -> 35 MB/s on two contexts, so such data stayed on one).  Round 5: dealt all the same, with the contexts
-  // at three stream PRIORITIES (as calls with block splitting are, below): the first context's long tasks win their
-  // SIMDs, the others fill what it leaves — class Z 131 -> 190 MB/s, class M 165 -> 245 (189 / 245 on four, 187 / 250 on
-  // six contexts; without the priorities 112 / 170; profiles/r05_runs_ctx.txt).  Sampled: one probe every 4096 bytes,
-  // "the next 64 bytes are equal"; 1 % of the probes make a call "data with runs".
-  // (ZOPFLI_AMD_SPLIT_RUNS=0 or ZOPFLI_AMD_STREAM_PRIO=0: such data on one context, as before — for measuring)
-  bool runs = false, one_context = false;
-  if (split_from && parts.size() >= split_from && in != nullptr) {
-    const size_t lo = parts.front().instart, hi = parts.back().inend;
-    size_t probes = 0, hits = 0;
-    for (size_t i = lo; i + 64 <= hi; i += 4096, ++probes) {
-      const unsigned char c0 = in[i];
-      size_t k = 1;
-      while (k < 64 && in[i + k] == c0) ++k;
-      hits += k == 64;
-    }
-    runs = probes > 0 && hits * 100 >= probes;
-    static const int prio_on = [] { const char* e = std::getenv("ZOPFLI_AMD_STREAM_PRIO"); return e ? std::atoi(e) : 1; }();
-    static const bool split_runs = [] { const char* e = std::getenv("ZOPFLI_AMD_SPLIT_RUNS"); return !e || std::atoi(e) != 0; }();
-    one_context = runs && !(prio_on && split_runs);
-  }
+  bool runs = false;
+  const size_t per_device = ContextsPerDevice(options, btype, in, parts, &runs);
   const double tr_begin = WallMs();
-  const Lease lease(parts.size(), split_from && parts.size() >= split_from && !one_context ? split_ways : 1,
-                    /*polite=*/parts.size() < 32, /*small=*/parts.size() < 32);
+  const Lease lease(parts.size(), per_device, /*polite=*/parts.size() < 32, /*small=*/parts.size() < 32);
   const double tr_lease = WallMs();
-  // A small call among other calls in flight (many small files, a caller thread each): its host phases — the split
-  // searches' rounds of nine probes, the cost models of a block or two — run on the calling thread.  The worker pool takes
-  // one fork-join at a time: sixteen callers queueing for it, each job a few microseconds of work per woken thread, were
-  // slower than three (profiles/r06_small_files.txt); the callers are the parallelism.
-  struct InlineHostWork {
-    bool on, was;
-    explicit InlineHostWork(bool o) : on(o), was(zamd::g_host_inline) { if (on) zamd::g_host_inline = true; }
-    ~InlineHostWork() { if (on) zamd::g_host_inline = was; }
-  } inline_host(parts.size() <= 2 && Pool().InFlight() > 1);
-  const std::vector<zmx_ctx*>& ctxs = lease.ctxs;
-  const size_t ndev = std::min(ctxs.size(), parts.size());
-  struct Shard {
-    size_t first = 0, last = 0, base = 0;
-    std::vector<zamd::Chunk> chunks;
-    std::vector<size_t> part_chunks;
-    int rc = 0;
-    std::string err;
-    int err_class = ZMX_ERR_NONE;   // zmx_last_error_class() of the failure
-    zamd::Timing timing;
-    uint32_t sum = 0;
-    size_t sum_bytes = 0;
-    bool redone = false;
-    double stats[19] = {0};        // the shard thread's kernel / match / task statistics (zmx_internal_stats_take)
-  };
-  std::vector<Shard> shards(ndev);
-  for (size_t d = 0; d < ndev; ++d) {
-    shards[d].first = parts.size() * d / ndev;
-    shards[d].last = parts.size() * (d + 1) / ndev;
-  }
-  // Shards of equal COST, not of equal count (deal.h): on a mixed corpus the master blocks of long runs of equal bytes
-  // cost several times the others, and contiguous equal-count shards leave them to one or two contexts.  From the
-  // bytes alone — the one-process-per-GPU launchers compute the same ranges (zmx_master_block_costs).
-  // (ZOPFLI_AMD_DEAL=count: equal counts, as before — for measuring)
-  static const bool deal_by_cost = [] { const char* e = std::getenv("ZOPFLI_AMD_DEAL"); return !e || std::strcmp(e, "count") != 0; }();
-  if (deal_by_cost && ndev > 1 && in != nullptr && parts.size() > ndev) {
-    std::vector<double> cost(parts.size());
-    zamd::ParallelFor(parts.size(), [&](size_t i) { cost[i] = zamd::MasterBlockCost(in, parts[i].instart, parts[i].inend); });
-    std::vector<size_t> first;
-    zamd::DealByCost(cost, ndev, &first);
-    for (size_t d = 0; d < ndev; ++d) { shards[d].first = first[d]; shards[d].last = first[d + 1]; }
-  }
-  // (ZOPFLI_AMD_SHARD_WEIGHTS="28,36,36": the shares of the shards, for measuring)
-  if (const char* e = std::getenv("ZOPFLI_AMD_SHARD_WEIGHTS")) {
-    std::vector<double> w;
-    for (const char* q = e; *q;) {
-      char* end = nullptr;
-      const double v = std::strtod(q, &end);
-      if (end == q) break;
-      w.push_back(v > 0 ? v : 0);
-      q = *end == ',' ? end + 1 : end;
-    }
-    double total = 0;
-    for (size_t d = 0; d < ndev && d < w.size(); ++d) total += w[d];
-    if (w.size() >= ndev && total > 0) {
-      double acc = 0;
-      size_t at = 0;
-      for (size_t d = 0; d < ndev; ++d) {
-        acc += w[d];
-        size_t to = d + 1 == ndev ? parts.size() : static_cast<size_t>(parts.size() * acc / total + 0.5);
-        to = std::max(to, at + 1);                       // no empty shard
-        to = std::min(to, parts.size() - (ndev - 1 - d));
-        shards[d].first = at;
-        shards[d].last = to;
-        at = to;
-      }
-    }
-  }
-  // The contexts of ONE device take their bytes over the same link: asked for at once, three uploads end together and
-  // the device has nothing to do until then (12 ms of a 122 ms call on 100 MB; the kernel timeline of
-  // tools/r04_timeline.sh).  One after the other, in stream order, the first context computes while the second's bytes
-  // travel — and the contexts stay out of step from there on: their host phases (block split, cost models) fall
-  // beside the others' kernels instead of beside each other.
-  struct UploadOrder {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<char> done;
-    std::vector<long> after;     // the shard whose upload this one waits for, -1 = none
-  } order;
-  order.done.assign(ndev, 0);
-  order.after.assign(ndev, -1);
-  // With block splitting the contexts of one device run at three stream priorities — one after the other instead of
-  // side by side: their split searches and joins then fall beside the others' kernels (zmx_ctx_set_priority; 100 MB of
-  // text 152 -> 145 ms, without block splitting 123 -> 130: there every context stays on its default streams).
-  // Data with runs: with or without block splitting (above).
-  // (ZOPFLI_AMD_STREAM_PRIO=0: never; 2: always — for measuring)
-  static const int use_priorities = [] { const char* e = std::getenv("ZOPFLI_AMD_STREAM_PRIO"); return e ? std::atoi(e) : 1; }();
-  std::vector<int> shard_priority(ndev, 0);
-  if (use_priorities && ((options.blocksplitting && btype == 2) || runs || use_priorities == 2)) {
-    for (size_t d = 0; d < ndev; ++d) {
-      size_t before = 0, same = 0;
-      for (size_t e = 0; e < ndev; ++e) {
-        if (lease.device_of[e] != lease.device_of[d]) continue;
-        ++same;
-        if (e < d) ++before;
-      }
-      if (same > 1) shard_priority[d] = before == 0 ? 1 : before + 1 == same ? -1 : 0;
-    }
-  }
-  // (ZOPFLI_AMD_UPLOAD_ORDER=0: all at once, as before — for measuring)
-  static const bool ordered_uploads = [] { const char* e = std::getenv("ZOPFLI_AMD_UPLOAD_ORDER"); return !e || std::atoi(e) != 0; }();
-  for (size_t d = 1; d < ndev && ordered_uploads; ++d) {
-    for (size_t e = d; e-- > 0;) {
-      if (lease.device_of[e] == lease.device_of[d]) { order.after[d] = static_cast<long>(e); break; }
-    }
-  }
-  struct UploadTurn {     // marks a shard's upload as over, however its attempt ends
-    UploadOrder& o; size_t d; bool released = false;
-    void Wait() {
-      if (o.after[d] < 0) return;
-      std::unique_lock<std::mutex> lock(o.mu);
-      o.cv.wait(lock, [&] { return o.done[static_cast<size_t>(o.after[d])] != 0; });
-    }
-    void Release() {
-      if (released) return;
-      released = true;
-      { std::lock_guard<std::mutex> lock(o.mu); o.done[d] = 1; }
-      o.cv.notify_all();
-    }
-    ~UploadTurn() { Release(); }
-  };
-  // (ZOPFLI_AMD_TEST_FAIL_SHARD=k: the k-th shard's first attempt fails before it does anything — the test of the
-  //  re-queue below)
-  static const long fail_shard = [] { const char* e = std::getenv("ZOPFLI_AMD_TEST_FAIL_SHARD"); return e ? std::atol(e) : -1L; }();
-  auto work = [&](size_t d, zmx_ctx* ctx, bool retry) {
-    Shard& sh = shards[d];
-    UploadTurn turn{order, d};
-    int level = retry ? 0 : shard_priority[d];
-    // (a call that is one shard — a small file — keeps the level its context was given when first seen: the contexts of
-    //  concurrent small callers then lie on streams of all three priorities, i.e. on three sets of hardware queues instead of
-    //  one — the runtime gives a priority four queues, and sixteen streams on four queues run their short kernels one after
-    //  the other: 1 000 files of 64 KiB through 16 callers 26.8 -> 29.9 MB/s, 160 of 1 MB 220 -> 283, profiles/r06_small_hwq.txt;
-    //  ZOPFLI_AMD_SMALL_PRIO=0: every such call on the default priority, as before)
-    static const bool small_prio = [] { const char* e = std::getenv("ZOPFLI_AMD_SMALL_PRIO"); return !e || std::atoi(e) != 0; }();
-    if (small_prio && ndev == 1 && !retry) {
-      static std::mutex mu;
-      static std::unordered_map<zmx_ctx*, int> levels;
-      std::lock_guard<std::mutex> g(mu);
-      auto it = levels.find(ctx);
-      if (it == levels.end()) it = levels.emplace(ctx, static_cast<int>(levels.size() % 3) - 1).first;
-      level = it->second;
-    }
-    if (zmx_ctx_set_priority(ctx, level) != 0) {
-      // (not fatal: the context stays on the streams it has, the shards then run side by side instead of in turn)
-      std::fprintf(stderr, "zopfli_amd: stream priorities unavailable (%s)\n", zmx_last_error());
-    }
-    sh.rc = 0;
-    sh.err.clear();
-    sh.err_class = ZMX_ERR_NONE;
-    sh.chunks.clear();
-    sh.part_chunks.clear();
-    sh.sum = 0;
-    sh.sum_bytes = 0;
-    if (!retry && fail_shard == static_cast<long>(d)) {
-      sh.rc = -1;
-      sh.err = "injected failure (ZOPFLI_AMD_TEST_FAIL_SHARD): PoolAlloc(pool) too large — the text must not matter";
-      sh.err_class = ZMX_ERR_OUT_OF_MEMORY;
-      return;
-    }
-    const size_t start = parts[sh.first].instart, end = parts[sh.last - 1].inend;
-    sh.base = start > zamd::kWindow ? start - zamd::kWindow : 0;
-    if (hooks) sh.base = std::max(sh.base, hooks->floor(parts[sh.first].instart));
-    const double tr0 = WallMs();
-    if (!retry) turn.Wait();
-    const double tr1 = WallMs();
-    const int up = zmx_set_input(ctx, in + sh.base, end - sh.base);
-    turn.Release();
-    const double tr2 = WallMs();
-    if (up != 0 || (hooks && hooks->uploaded(d, ctx, sh.base, sh.first, sh.last) != 0)) {
-      sh.rc = -1;
-      sh.err = zmx_last_error();
-      sh.err_class = zmx_last_error_class();
-      return;
-    }
-    if (sum && start < sum->limit) {
-      sh.sum_bytes = std::min(end, sum->limit) - start;
-      if (zmx_checksum(ctx, sum->kind, start - sh.base, start - sh.base + sh.sum_bytes, &sh.sum) != 0) {
-        sh.rc = -1;
-        sh.err = zmx_last_error();
-        sh.err_class = zmx_last_error_class();
-        return;
-      }
-    }
-    std::vector<zamd::Part> mine(parts.begin() + static_cast<long>(sh.first), parts.begin() + static_cast<long>(sh.last));
-    for (auto& p : mine) { p.instart -= sh.base; p.inend -= sh.base; }
-    const double tr3 = WallMs();
-    struct SplitOnDevice {
-      bool was;
-      explicit SplitOnDevice(bool on) : was(zamd::g_split_on_device) { zamd::g_split_on_device = on || was; }
-      ~SplitOnDevice() { zamd::g_split_on_device = was; }
-    } split_on_device(hooks && hooks->split_on_device);
-    sh.rc = RunParts(ctx, options, btype, mine, &sh.chunks, part_chunks ? &sh.part_chunks : nullptr,
-                     hooks ? hooks->group_bytes : 0);
-    if (sh.rc) { sh.err = zmx_last_error(); sh.err_class = zmx_last_error_class(); }
-    if (TraceCall()) {
-      std::fprintf(stderr, "  shard %zu (%zu parts): start +%.2f ms, wait for turn %.2f, upload %.2f, checksum %.2f, parts %.2f, end +%.2f\n",
-                   d, sh.last - sh.first, tr0 - tr_begin, tr1 - tr0, tr2 - tr1, tr3 - tr2, WallMs() - tr3, WallMs() - tr_begin);
-    }
-    for (auto& c : sh.chunks) {
-      if (c.kind == zamd::Chunk::kStored) { c.start += sh.base; c.end += sh.base; }
-    }
-    sh.timing = zamd::ThreadTiming();
-    if (d != 0 && !retry) zmx_internal_stats_take(sh.stats);   // (a thread of its own: its sums go to the caller's below)
-  };
-  if (ndev == 1) {
-    work(0, ctxs[0], false);
-  } else {
-    std::vector<std::thread> threads;
-    for (size_t d = 1; d < ndev; ++d) threads.emplace_back(work, d, ctxs[d], false);
-    work(0, ctxs[0], false);
-    for (auto& t : threads) t.join();
-    for (size_t d = 1; d < ndev; ++d) zmx_internal_stats_add(shards[d].stats);
-    // the slowest device's breakdown stands for the request (zmx_last_timing)
-    for (size_t d = 1; d < ndev; ++d) {
-      const zamd::Timing& a = shards[d].timing;
-      zamd::Timing& t = zamd::ThreadTiming();
-      if (a.tables + a.greedy + a.squeeze + a.cost_model + a.split + a.encode >
-          t.tables + t.greedy + t.squeeze + t.cost_model + t.split + t.encode) t = a;
-    }
-  }
-  // A shard that failed (its device ran out of memory, its context is broken) is done again on a context that just
-  // finished its own shard without error — another device's where there is one — before the request gives up: the
-  // parts are independent (deflate.c:916-923), whoever computes them computes the same bits.
-  for (size_t d = 0; d < ndev; ++d) {
-    if (!shards[d].rc) continue;
-    // (not a failure that would repeat itself on any context — a request the device layer refuses, a table set that
-    //  overflows its pools after the retries the device layer makes itself: ZMX_ERR_REFUSED.  By the error's CLASS, not its
-    //  text: an out-of-memory inside PoolAlloc reads "PoolAlloc(...): out of memory" and is exactly what a retry is for)
-    if (shards[d].err_class == ZMX_ERR_REFUSED) continue;
-    zmx_ctx* other = nullptr;
-    for (size_t e = 0; e < ndev && !other; ++e) if (e != d && !shards[e].rc && !shards[e].redone) other = ctxs[e];
-    if (!other) break;
-    std::fprintf(stderr, "zopfli_amd: a shard failed (%s): done again on another context\n", shards[d].err.c_str());
-    work(d, other, true);
-    shards[d].redone = true;
-  }
+  const InlineHostWork inline_host(parts.size() <= 2 && Pool().InFlight() > 1);
+  const size_t ndev = std::min(lease.ctxs.size(), parts.size());
+  ShardedCall call{options, btype, in, parts, sum, part_chunks != nullptr, hooks, tr_begin, {}, {}, {}};
+  PlanShards(&call, std::vector<int>(lease.device_of.begin(), lease.device_of.begin() + static_cast<long>(ndev)), runs);
+  RunShards(&call, lease.ctxs);
+  RetryFailedShards(&call, lease.ctxs);
   const double tr_joined = WallMs();
-  for (auto& sh : shards) {
-    if (sh.rc) {
-      std::fprintf(stderr, "zopfli_amd: device error: %s\n", sh.err.c_str());
-      if (hooks) { hooks->error = sh.err; hooks->error_class = sh.err_class; }
-      return sh.rc;
-    }
-    for (auto& c : sh.chunks) chunks->push_back(std::move(c));
-    if (part_chunks) part_chunks->insert(part_chunks->end(), sh.part_chunks.begin(), sh.part_chunks.end());
-  }
+  const int rc = CollectShards(&call, chunks, part_chunks);
+  if (rc) return rc;
   if (TraceCall()) {
     std::fprintf(stderr, "RunPartsSharded: lease %.2f ms, shards done +%.2f, chunks moved +%.2f\n", tr_lease - tr_begin,
                  tr_joined - tr_begin, WallMs() - tr_begin);
   }
   if (sum) {
     sum->value = sum->kind == ZMX_ADLER32 ? 1u : 0u;   // of no bytes
-    for (auto& sh : shards) {
+    for (auto& sh : call.shards) {
       if (sh.sum_bytes) sum->value = zmx_checksum_combine(sum->kind, sum->value, sh.sum, sh.sum_bytes);
     }
   }
@@ -700,11 +633,7 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
 int RunPartsSharded(const ZopfliOptions& options, int btype, const unsigned char* in,
                     const std::vector<zamd::Part>& parts, std::vector<zamd::Chunk>* chunks,
                     ChecksumRequest* sum = nullptr) {
-  static const size_t round_parts = [] {
-    const char* e = std::getenv("ZOPFLI_AMD_ROUND_PARTS");
-    const long v = e ? std::atol(e) : 0;
-    return v > 0 ? static_cast<size_t>(v) : static_cast<size_t>(2000);
-  }();
+  const size_t round_parts = zamd::HostSwitches().round_parts;
   if (parts.size() <= round_parts) return RunPartsShardedOnce(options, btype, in, parts, chunks, sum);
   uint32_t acc = sum ? (sum->kind == ZMX_ADLER32 ? 1u : 0u) : 0u;   // of no bytes
   for (size_t a = 0; a < parts.size(); a += round_parts) {
@@ -889,7 +818,7 @@ int zmx_deflate_range(zmx_ctx* ctx, const ZopfliOptions* options, size_t instart
   const int rc = RunParts(ctx, *options, 2, parts, &chunks);
   if (rc) return rc;
   const auto ts0 = std::chrono::steady_clock::now();
-  if (std::getenv("ZOPFLI_AMD_PROF"))
+  if (zamd::HostSwitches().prof)
     std::fprintf(stderr, "zmx_deflate_range: RunParts %.1f ms\n", std::chrono::duration<double>(ts0 - tr0).count() * 1e3);
   *blob = zamd::SerializeChunks(chunks, zmx_internal_input_host(ctx), blobsize);
   if (!*blob) return -1;

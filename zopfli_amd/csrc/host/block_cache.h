@@ -21,6 +21,8 @@
 #include <new>
 #include <vector>
 
+#include "host_knobs.h"
+
 namespace zamd {
 
 class BlockCache {
@@ -30,12 +32,8 @@ class BlockCache {
 
   // smaller requests are malloc's own business (ZOPFLI_AMD_HOST_CACHE_MIN, bytes; at least 2^kMinLog2)
   static size_t MinBytes() {
-    static const size_t m = [] {
-      const char* e = std::getenv("ZOPFLI_AMD_HOST_CACHE_MIN");
-      const long v = e ? std::atol(e) : (32l << 10);
-      return v > (1l << kMinLog2) ? static_cast<size_t>(v) : static_cast<size_t>(1) << kMinLog2;
-    }();
-    return m;
+    static_assert(kMinLog2 == 10, "host_knobs.h holds ZOPFLI_AMD_HOST_CACHE_MIN at 1024 bytes or more");
+    return HostSwitches().host_cache_min;
   }
 
   // Size class of a request: capacities 2^k and 3 * 2^(k-2) (at most a third wasted), k >= kMinLog2.
@@ -118,14 +116,7 @@ class BlockCache {
     std::vector<void*> free_list[kClasses];
     size_t cached = 0;
   };
-  static size_t Budget() {
-    static const size_t b = [] {
-      const char* e = std::getenv("ZOPFLI_AMD_HOST_CACHE_MB");
-      const long mb = e ? std::atol(e) : 1024;
-      return mb > 0 ? static_cast<size_t>(mb) << 20 : static_cast<size_t>(0);
-    }();
-    return b;
-  }
+  static size_t Budget() { return HostSwitches().host_cache_mb << 20; }
   // (leaked on purpose, like the worker pools; a forked child starts with an empty cache and a fresh mutex — a thread of
   //  the parent may have held the old one at the fork)
   static State& Get() {

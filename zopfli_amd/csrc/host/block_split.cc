@@ -17,7 +17,7 @@ namespace {
 
 // ZOPFLI_AMD_PROF: evaluations of the split cost and the time they take, summed over all threads, printed per block.
 std::atomic<unsigned long long> g_split_evals{0}, g_split_ns{0};
-const bool g_split_prof = std::getenv("ZOPFLI_AMD_PROF") != nullptr;
+bool SplitProf() { return HostSwitches().prof; }
 
 constexpr double kLarge = 1e30;  // ZOPFLI_LARGE_FLOAT, util.h:65
 
@@ -25,7 +25,7 @@ struct SplitCost {
   const Lz77Store& lz77;
   size_t start, end;
   double operator()(size_t i) const {
-    if (!g_split_prof) return CalculateBlockSizeAutoType(lz77, start, i) + CalculateBlockSizeAutoType(lz77, i, end);
+    if (!SplitProf()) return CalculateBlockSizeAutoType(lz77, start, i) + CalculateBlockSizeAutoType(lz77, i, end);
     const auto t0 = std::chrono::steady_clock::now();
     const double v = CalculateBlockSizeAutoType(lz77, start, i) + CalculateBlockSizeAutoType(lz77, i, end);
     g_split_ns += static_cast<unsigned long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
@@ -119,7 +119,7 @@ void BlockSplitLz77(const Lz77Store& lz77, size_t maxblocks, std::vector<size_t>
     if (!found) break;
     if (lend - lstart < 10) break;
   }
-  if (g_split_prof)
+  if (SplitProf())
     std::fprintf(stderr, "BlockSplitLz77: %zu symbols, %zu split points; so far %llu evaluations of the split cost, %.1f us each\n", n,
                  points->size(), g_split_evals.load(), g_split_evals.load() ? g_split_ns.load() * 1e-3 / g_split_evals.load() : 0.0);
 }
@@ -289,7 +289,7 @@ bool SplitRounds(std::vector<SeqSplit>& seq, const CostBatchFn* device, size_t d
   std::vector<Eval> evals;
   std::vector<CostQuery> queries;
   std::vector<double> answers;
-  static const bool trace = [] { const char* e = std::getenv("ZOPFLI_AMD_TRACE_CALL"); return e && std::atoi(e) != 0; }();
+  const bool trace = HostSwitches().trace_call;
   size_t rounds_dev = 0, rounds_host = 0, n_dev = 0, n_host = 0;
   double t_dev = 0, t_host = 0;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };

@@ -68,6 +68,64 @@ void DealByCost(const std::vector<double>& cost, size_t shards, std::vector<size
   (*first)[shards] = n;
 }
 
+bool LooksLikeRuns(const unsigned char* in, size_t lo, size_t hi) {
+  size_t probes = 0, hits = 0;
+  for (size_t i = lo; i + 64 <= hi; i += 4096, ++probes) {
+    const unsigned char c0 = in[i];
+    size_t k = 1;
+    while (k < 64 && in[i + k] == c0) ++k;
+    hits += k == 64;
+  }
+  return probes > 0 && hits * 100 >= probes;
+}
+
+std::vector<size_t> ShardRanges(size_t nparts, size_t ndev, const double* cost, const std::vector<double>& weights) {
+  std::vector<size_t> first(ndev + 1);
+  for (size_t d = 0; d <= ndev; ++d) first[d] = nparts * d / ndev;
+  if (cost) DealByCost(std::vector<double>(cost, cost + nparts), ndev, &first);
+  double total = 0;
+  for (size_t d = 0; d < ndev && d < weights.size(); ++d) total += weights[d];
+  if (weights.size() >= ndev && total > 0) {
+    double acc = 0;
+    size_t at = 0;
+    for (size_t d = 0; d < ndev; ++d) {
+      acc += weights[d];
+      size_t to = d + 1 == ndev ? nparts : static_cast<size_t>(nparts * acc / total + 0.5);
+      to = std::max(to, at + 1);                       // no empty shard
+      to = std::min(to, nparts - (ndev - 1 - d));
+      first[d] = at;
+      first[d + 1] = to;
+      at = to;
+    }
+  }
+  return first;
+}
+
+std::vector<int> ShardPriorities(const std::vector<int>& device_of) {
+  const size_t ndev = device_of.size();
+  std::vector<int> priority(ndev, 0);
+  for (size_t d = 0; d < ndev; ++d) {
+    size_t before = 0, same = 0;
+    for (size_t e = 0; e < ndev; ++e) {
+      if (device_of[e] != device_of[d]) continue;
+      ++same;
+      if (e < d) ++before;
+    }
+    if (same > 1) priority[d] = before == 0 ? 1 : before + 1 == same ? -1 : 0;
+  }
+  return priority;
+}
+
+std::vector<long> UploadAfter(const std::vector<int>& device_of) {
+  std::vector<long> after(device_of.size(), -1);
+  for (size_t d = 1; d < device_of.size(); ++d) {
+    for (size_t e = d; e-- > 0;) {
+      if (device_of[e] == device_of[d]) { after[d] = static_cast<long>(e); break; }
+    }
+  }
+  return after;
+}
+
 }  // namespace zamd
 
 extern "C" {

@@ -19,4 +19,23 @@ double MasterBlockCost(const unsigned char* in, size_t begin, size_t end);
 // largest shard's cost as small as a prefix walk makes it.  `first` gets shards + 1 entries.
 void DealByCost(const std::vector<double>& cost, size_t shards, std::vector<size_t>* first);
 
+// The plan of a call that is dealt over several contexts (api.cc: RunPartsShardedOnce).  Functions of their arguments
+// alone: no context, no environment.
+
+// Data with long runs of equal bytes?  Sampled: one probe every 4096 bytes of in[lo, hi), "the next 64 bytes are equal";
+// 1 % of the probes make a call "data with runs".
+bool LooksLikeRuns(const unsigned char* in, size_t lo, size_t hi);
+
+// first[s] .. first[s + 1]: the parts of shard s of `ndev` (at most `nparts`), contiguous and none empty: equal counts;
+// of equal cost (DealByCost) where `cost` — nparts entries — is given; `weights` (ZOPFLI_AMD_SHARD_WEIGHTS), when there is
+// one for every shard and their sum is positive, override both with their shares.
+std::vector<size_t> ShardRanges(size_t nparts, size_t ndev, const double* cost, const std::vector<double>& weights);
+
+// The stream priorities of shards whose contexts lie on the devices `device_of`: the contexts of ONE device run at three
+// levels — its first shard 1, its last -1, those between 0; a device with a single shard stays at 0.
+std::vector<int> ShardPriorities(const std::vector<int>& device_of);
+
+// The shard whose upload each shard waits for: the one before it on the same device, -1 = none.
+std::vector<long> UploadAfter(const std::vector<int>& device_of);
+
 }  // namespace zamd

@@ -9,6 +9,7 @@
 
 #include "block_cost.h"
 #include "block_split.h"
+#include "host_knobs.h"
 #include "lz77_optimal.h"
 #include "lz77_store.h"
 #include "thread_pool.h"
@@ -16,10 +17,11 @@
 namespace zamd {
 
 namespace {
+
 // Few enough parts that one thread per part would leave the block-split search latency-bound (block_split.cc:
 // BlockSplitLz77Batch).  ZOPFLI_AMD_BATCH_SPLIT = 0 / 1 forces the choice.
 bool BatchSplit(size_t np) {
-  static const int forced = [] { const char* e = std::getenv("ZOPFLI_AMD_BATCH_SPLIT"); return e ? std::atoi(e) : -1; }();
+  const int forced = HostSwitches().batch_split;
   if (forced >= 0) return forced != 0;
   return np * 2 <= WideThreads();
 }
@@ -31,22 +33,17 @@ bool BatchSplit(size_t np) {
 // call, 38 ms on the box's 16 CPUs beside the other shards' work, against 12 ms of device rounds (18 x 0.2 ms plus the
 // queueing behind the other contexts' kernels); on text (4 000 block sizes of ~10 us, seven rounds) the host's 4 ms beat
 // the device's 5 - 24 (profiles/r06_device_split.txt).  Hence: at least `from` sequences AND at least 0.45 symbols a byte.
-bool DeviceSplit(size_t nseq, size_t from_default, size_t symbols, size_t bytes) {
-  static const int on = [] { const char* e = std::getenv("ZOPFLI_AMD_DEVICE_SPLIT"); return e ? std::atoi(e) : 1; }();
-  static const long from_env = [] { const char* e = std::getenv("ZOPFLI_AMD_DEVICE_SPLIT_FROM"); return e ? std::atol(e) : -1L; }();
-  const size_t from = from_env >= 0 ? static_cast<size_t>(from_env) : from_default;
-  if (on == 0 || nseq < from || nseq == 0) return false;
-  return on >= 2 || g_split_on_device || 20 * symbols >= 9 * bytes;
+//
+// May a search over `nseq` sequences use the device at all?  (`from_default` sequences, or ZOPFLI_AMD_DEVICE_SPLIT_FROM)
+bool DeviceSplitAllowed(size_t nseq, size_t from_default) {
+  const HostKnobs& k = HostSwitches();
+  const size_t from = k.device_split_from >= 0 ? static_cast<size_t>(k.device_split_from) : from_default;
+  return k.device_split != 0 && nseq >= from && nseq != 0;
 }
-size_t DeviceSplitMin() {
-  static const size_t v = [] { const char* e = std::getenv("ZOPFLI_AMD_DEVICE_SPLIT_MIN"); return e ? static_cast<size_t>(std::atoll(e)) : static_cast<size_t>(128); }();
-  return v;
+// ... and does it pay there: the density rule
+bool DeviceSplitPays(size_t symbols, size_t bytes) {
+  return HostSwitches().device_split >= 2 || g_split_on_device || 20 * symbols >= 9 * bytes;
 }
-struct CostStoresGuard {
-  zmx_ctx* ctx;
-  zmx_cost_stores* cs = nullptr;
-  ~CostStoresGuard() { if (cs) zmx_cost_stores_free(ctx, cs); }
-};
 // the evaluator BlockSplitLz77Batch calls (false = this round on the host: the two give the same integers)
 CostBatchFn DeviceCosts(zmx_ctx* ctx, zmx_cost_stores* cs) {
   return [ctx, cs](const CostQuery* q, size_t n, double* cost) {
@@ -54,16 +51,29 @@ CostBatchFn DeviceCosts(zmx_ctx* ctx, zmx_cost_stores* cs) {
     return zmx_block_costs(ctx, cs, n, reinterpret_cast<const uint32_t*>(q), cost) == 0;
   };
 }
-}  // namespace
-
-namespace {
 
 double Now() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// The phase clock of a DeflateParts call: End(p) books the time since the last Start() or End() to phase p.
+struct PhaseTimer {
+  enum Phase { kGreedy, kFirstSplit, kOptimal, kJoin, kSecondSplit, kCosts, kRequests, kFixed, kEncode, kCollect, kPhases };
+  double s[kPhases] = {0};
+  double last = Now();
+  void Start() { last = Now(); }
+  double End(Phase p) {
+    const double t = Now();
+    s[p] += t - last;
+    last = t;
+    return s[p];
+  }
+  double Ms(Phase p) const { return s[p] * 1e3; }
+};
+
 struct FinalBlock {
   size_t lstart = 0, lend = 0;       // symbol range in the part's store
+  size_t instart = 0, inend = 0;     // the bytes those symbols stand for (an empty block: none)
   double stored = 0, fixed = 0, dynamic = 0;
   bool expensive_fixed = false;      // re-parse with the fixed-tree cost model
   long fixed_request = -1;           // index into the batched re-parse
@@ -83,25 +93,63 @@ struct DeviceEncode {
 
 struct PartState {
   Part part{};
+  std::vector<size_t> split_bytes;   // the first split's points (byte positions)
   std::vector<zmx_block> blocks;     // first-pass deflate blocks (byte ranges)
   std::vector<size_t> block_sym_end; // symbols of the part's store up to the end of each first-pass block
   std::vector<DeviceEncode> enc;
   size_t first_block = 0;            // offset into the batched block list
   Lz77Store lz77;                    // optimal parse of the whole part
+  double totalcost = 0;              // of the first-pass blocks (deflate.c:866)
+  bool tried2 = false;               // the second split attempt is made (deflate.c:872)
+  std::vector<size_t> points2;       // ... and what it found
   std::vector<size_t> splitpoints;   // final split points (symbol indices)
   std::vector<FinalBlock> finals;
   std::vector<Chunk> chunks;
   std::string log;                   // verbose: what the reference prints for the part before its blocks are written
 };
 
-// "block split points: ..." as PrintBlockSplitPoints does (blocksplitter.c:148-180): uncompressed
-// offsets from the start of the store, decimal then hex.
-std::string SplitPointsLine(const Lz77Store& lz77, const std::vector<size_t>& points) {
+// The cost stores of a split search on the device, for as long as the search takes.
+struct CostStoresGuard {
+  zmx_ctx* ctx;
+  zmx_cost_stores* cs = nullptr;
+  ~CostStoresGuard() { if (cs) zmx_cost_stores_free(ctx, cs); }
+};
+
+// What the phases of a DeflateParts call (btype 2) share.  It owns the device table sets.
+struct DeflateCall {
+  zmx_ctx* ctx;
+  const ZopfliOptions& options;
+  std::vector<PartState> st;
+  PhaseTimer timer;
+  zmx_tables* split_tables = nullptr;   // the master blocks' match tables, reused for their deflate blocks (OptimalParse hands them on)
+  bool device_encode = true;            // (ZOPFLI_AMD_DEVICE_ENCODE=0: every block's bits on the host, as in round 1)
+  // Without block splitting a part is one block and nothing after the optimal parse needs its symbols on the host: sizes
+  // and trees come from the histogram of the best parse, the bits from the device.
+  bool no_symbols = false;
+  std::vector<SymbolRun> runs;          // the optimal parse of every block of the batched block list
+  OptimalKeep keep;                     // ... and where it lies on the device
+  std::vector<zmx_block> fixed_requests;
+  std::vector<SymbolRun> fixed_runs;    // the fixed-tree re-parses
+  OptimalKeep fkeep;
+
+  DeflateCall(zmx_ctx* c, const ZopfliOptions& o, const std::vector<Part>& parts)
+      : ctx(c), options(o), st(parts.size()), device_encode(HostSwitches().device_encode) {
+    for (size_t p = 0; p < parts.size(); ++p) st[p].part = parts[p];
+  }
+  DeflateCall(const DeflateCall&) = delete;
+  ~DeflateCall() {
+    for (zmx_tables* t : {fkeep.tables, keep.tables, split_tables}) if (t) zmx_tables_free(ctx, t);
+  }
+  size_t np() const { return st.size(); }
+};
+
+// "block split points: ..." as PrintBlockSplitPoints does (blocksplitter.c:148-180): the uncompressed offsets of
+// `positions` from `origin`, the part's start, decimal then hex.
+std::string SplitPointsLine(const std::vector<size_t>& positions, size_t origin) {
   std::string dec = "block split points: ", hex = "(hex:";
-  const size_t origin = lz77.size() ? lz77.pos(0) : 0;
   char buf[32];
-  for (size_t p : points) {
-    const int v = static_cast<int>(lz77.pos(p) - origin);
+  for (size_t pos : positions) {
+    const int v = static_cast<int>(pos - origin);
     std::snprintf(buf, sizeof(buf), "%d ", v);
     dec += buf;
     std::snprintf(buf, sizeof(buf), " %x", v);
@@ -117,10 +165,7 @@ Lz77Store StoreFromRun(const SymbolRun& run, size_t pos) {
 }
 
 // ZOPFLI_AMD_TRACE_CALL=1 (api.cc prints the call's shards): the phases of DeflateParts on stderr
-bool TraceCallEnv() {
-  static const bool on = [] { const char* e = std::getenv("ZOPFLI_AMD_TRACE_CALL"); return e && std::atoi(e) != 0; }();
-  return on;
-}
+bool TraceCallEnv() { return HostSwitches().trace_call; }
 
 Chunk BitsChunk(BitWriter* w) {
   Chunk c;
@@ -129,253 +174,239 @@ Chunk BitsChunk(BitWriter* w) {
   return c;
 }
 
-}  // namespace
+void MoveChunks(std::vector<PartState>* st, std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks) {
+  for (PartState& s : *st) {
+    for (auto& c : s.chunks) chunks->push_back(std::move(c));
+    if (part_chunks) part_chunks->push_back(s.chunks.size());
+  }
+}
 
-int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const std::vector<Part>& parts,
-                 std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks) {
+// deflate.c:827: stored blocks only
+int StoredParts(const std::vector<Part>& parts, std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks) {
+  for (const Part& part : parts) {
+    Chunk c;
+    c.kind = Chunk::kStored;
+    c.start = part.instart;
+    c.end = part.inend;
+    c.final_block = part.final_part;
+    chunks->push_back(std::move(c));
+    if (part_chunks) part_chunks->push_back(1);
+  }
+  return 0;
+}
+
+// deflate.c:830-842: one fixed-tree block per part
+int FixedParts(zmx_ctx* ctx, const std::vector<Part>& parts, std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks) {
   const size_t np = parts.size();
   std::vector<PartState> st(np);
-  for (size_t p = 0; p < np; ++p) st[p].part = parts[p];
-  int rc = 0;
+  std::vector<zmx_block> blocks(np);
+  for (size_t p = 0; p < np; ++p) blocks[p] = {parts[p].instart, parts[p].inend};
+  std::vector<SymbolRun> runs;
+  const int rc = Lz77OptimalFixedBatch(ctx, blocks, &runs);
+  if (rc) return rc;
+  ParallelFor(np, [&](size_t p) {
+    Lz77Store s = StoreFromRun(runs[p], parts[p].instart);
+    BitWriter w;
+    EncodeBlock(s, 0, s.size(), 1, parts[p].final_part, &w);
+    Chunk c = BitsChunk(&w);
+    c.log_block = true;
+    c.log_btype = 1;
+    c.log_unc = parts[p].inend - parts[p].instart;
+    st[p].chunks.push_back(std::move(c));
+  });
+  MoveChunks(&st, chunks, part_chunks);
+  return 0;
+}
 
-  if (btype == 0) {  // deflate.c:827: stored blocks only
-    for (size_t p = 0; p < np; ++p) {
-      Chunk c;
-      c.kind = Chunk::kStored;
-      c.start = parts[p].instart;
-      c.end = parts[p].inend;
-      c.final_block = parts[p].final_part;
-      chunks->push_back(std::move(c));
-      if (part_chunks) part_chunks->push_back(1);
-    }
-    return 0;
-  }
+// ---- 1. first block split on a greedy parse of each part (deflate.c:845-850, blocksplitter.c:275)
 
-  if (btype == 1) {  // deflate.c:830-842: one fixed-tree block per part
-    std::vector<zmx_block> blocks(np);
-    for (size_t p = 0; p < np; ++p) blocks[p] = {parts[p].instart, parts[p].inend};
-    std::vector<SymbolRun> runs;
-    rc = Lz77OptimalFixedBatch(ctx, blocks, &runs);
-    if (rc) return rc;
-    ParallelFor(np, [&](size_t p) {
-      Lz77Store s = StoreFromRun(runs[p], parts[p].instart);
-      BitWriter w;
-      EncodeBlock(s, 0, s.size(), 1, parts[p].final_part, &w);
-      Chunk c = BitsChunk(&w);
-      c.log_block = true;
-      c.log_btype = 1;
-      c.log_unc = parts[p].inend - parts[p].instart;
-      st[p].chunks.push_back(std::move(c));
-    });
-    for (size_t p = 0; p < np; ++p) {
-      for (auto& c : st[p].chunks) chunks->push_back(std::move(c));
-      if (part_chunks) part_chunks->push_back(st[p].chunks.size());
-    }
-    return 0;
-  }
-
-  // ---- 1. first block split on a greedy parse of each part (deflate.c:845-850,
-  //         blocksplitter.c:275)
-  std::vector<std::vector<size_t>> split_bytes(np);
-  zmx_tables* split_tables = nullptr;   // the master blocks' match tables, reused for their deflate blocks
-  if (options.blocksplitting) {
-    std::vector<zmx_block> ranges(np);
-    for (size_t p = 0; p < np; ++p) ranges[p] = {parts[p].instart, parts[p].inend};
-    std::vector<SymbolRun> greedy;
-    std::vector<uint32_t> greedy_nsym;
-    const double tg0 = Now();
-    // (the symbols stay on the device until somebody wants them on the host: with the search's block sizes computed there
-    //  nobody does — a shard of incompressible data is 130 MB of them)
-    rc = Lz77GreedyBatch(ctx, ranges, &greedy, &split_tables, &greedy_nsym, DeviceSplit(np, 6, 1, 1));
-    if (rc) return rc;
-    const double t0 = Now();
-    std::atomic<uint64_t> ns_store{0}, ns_search{0};
-    bool dev_done = false;
-    bool have_symbols = !DeviceSplit(np, 6, 1, 1);
-    size_t greedy_symbols = 0, part_bytes = 0;
-    for (size_t p = 0; p < np; ++p) { greedy_symbols += greedy_nsym[p]; part_bytes += parts[p].inend - parts[p].instart; }
-    if (DeviceSplit(np, 6, greedy_symbols, part_bytes)) {
-      // the greedy stores are on the device already (slot 0 of the master blocks' tables): every round of the search's
-      // block sizes there (zmx_block_costs), no host store at all — and the split points' byte positions from there too
-      const double a = Now();
-      CostStoresGuard dev{ctx};
-      std::vector<size_t> first(np + 1), blk(np), nsym(np);
-      std::vector<int32_t> slot(np, 0);
-      for (size_t p = 0; p < np; ++p) { first[p] = p; blk[p] = p; nsym[p] = greedy_nsym[p]; }
-      first[np] = np;
-      if (zmx_cost_stores_create(ctx, split_tables, np, first.data(), blk.data(), slot.data(), nsym.data(), &dev.cs) == 0) {
-        const double b = Now();
-        std::vector<std::vector<size_t>> pts;
-        dev_done = BlockSplitSizesBatch(nsym, static_cast<size_t>(options.blocksplittingmax), &pts, DeviceCosts(ctx, dev.cs));
-        const double c = Now();
-        if (dev_done) {
-          // SplitPointsToBytes without a store: the bytes the symbols before each point stand for (zmx_cost_positions)
-          std::vector<uint32_t> pairs;
-          for (size_t p = 0; p < np; ++p) for (size_t pt : pts[p]) { pairs.push_back(static_cast<uint32_t>(p)); pairs.push_back(static_cast<uint32_t>(pt)); }
-          std::vector<uint64_t> bytes(pairs.size() / 2);
-          dev_done = zmx_cost_positions(ctx, dev.cs, bytes.size(), pairs.data(), bytes.data()) == 0;
-          size_t k = 0;
-          for (size_t p = 0; p < np && dev_done; ++p) {
-            split_bytes[p].clear();
-            for (size_t i = 0; i < pts[p].size(); ++i) split_bytes[p].push_back(parts[p].instart + bytes[k++]);
-            if (options.verbose) {    // blocksplitter.c:266-268, PrintBlockSplitPoints :148-180
-              std::string dec = "block split points: ", hex = "(hex:";
-              char buf[32];
-              for (size_t bp : split_bytes[p]) {
-                const int v = static_cast<int>(bp - parts[p].instart);
-                std::snprintf(buf, sizeof(buf), "%d ", v);
-                dec += buf;
-                std::snprintf(buf, sizeof(buf), " %x", v);
-                hex += buf;
-              }
-              st[p].log += dec + hex + ")\n";
-            }
-          }
-        }
-        if (TraceCallEnv()) std::fprintf(stderr, "    DeflateParts(%zu parts): first split on the device: sequences %.2f ms, rounds %.2f ms, points %.2f ms\n", np, (b - a) * 1e3, (c - b) * 1e3, (Now() - c) * 1e3);
+// The greedy stores are on the device already (slot 0 of the master blocks' tables): every round of the search's
+// block sizes there (zmx_block_costs), no host store at all — and the split points' byte positions from there too.
+// false: the device did not serve; the host searches.
+bool FirstSplitOnDevice(DeflateCall* call, const std::vector<uint32_t>& greedy_nsym) {
+  zmx_ctx* ctx = call->ctx;
+  const size_t np = call->np();
+  const double a = Now();
+  CostStoresGuard dev{ctx};
+  std::vector<size_t> first(np + 1), blk(np), nsym(np);
+  std::vector<int32_t> slot(np, 0);
+  for (size_t p = 0; p < np; ++p) { first[p] = p; blk[p] = p; nsym[p] = greedy_nsym[p]; }
+  first[np] = np;
+  bool done = false;
+  if (zmx_cost_stores_create(ctx, call->split_tables, np, first.data(), blk.data(), slot.data(), nsym.data(), &dev.cs) == 0) {
+    const double b = Now();
+    std::vector<std::vector<size_t>> pts;
+    done = BlockSplitSizesBatch(nsym, static_cast<size_t>(call->options.blocksplittingmax), &pts, DeviceCosts(ctx, dev.cs));
+    const double c = Now();
+    if (done) {
+      // SplitPointsToBytes without a store: the bytes the symbols before each point stand for (zmx_cost_positions)
+      std::vector<uint32_t> pairs;
+      for (size_t p = 0; p < np; ++p) for (size_t pt : pts[p]) { pairs.push_back(static_cast<uint32_t>(p)); pairs.push_back(static_cast<uint32_t>(pt)); }
+      std::vector<uint64_t> bytes(pairs.size() / 2);
+      done = zmx_cost_positions(ctx, dev.cs, bytes.size(), pairs.data(), bytes.data()) == 0;
+      size_t k = 0;
+      for (size_t p = 0; p < np && done; ++p) {
+        PartState& s = call->st[p];
+        s.split_bytes.clear();
+        for (size_t i = 0; i < pts[p].size(); ++i) s.split_bytes.push_back(s.part.instart + bytes[k++]);
+        if (call->options.verbose) s.log += SplitPointsLine(s.split_bytes, s.part.instart);   // blocksplitter.c:266-268
       }
-      if (!dev_done && TraceCallEnv()) std::fprintf(stderr, "    DeflateParts: no device block sizes (%s): the host evaluates\n", zmx_last_error());
     }
-    if (!dev_done && !have_symbols) {
-      rc = Lz77GreedyDownload(ctx, split_tables, greedy_nsym, &greedy);
+    if (TraceCallEnv()) std::fprintf(stderr, "    DeflateParts(%zu parts): first split on the device: sequences %.2f ms, rounds %.2f ms, points %.2f ms\n", np, (b - a) * 1e3, (c - b) * 1e3, (Now() - c) * 1e3);
+  }
+  if (!done && TraceCallEnv()) std::fprintf(stderr, "    DeflateParts: no device block sizes (%s): the host evaluates\n", zmx_last_error());
+  return done;
+}
+
+// a few parts: all their searches advance together, round by round, on the whole pool (block_split.cc)
+void FirstSplitTogether(DeflateCall* call, const std::vector<SymbolRun>& greedy) {
+  const size_t np = call->np();
+  std::vector<Lz77Store> stores(np);
+  ParallelForWide(np, [&](size_t p) { stores[p] = StoreFromRun(greedy[p], call->st[p].part.instart); });
+  std::vector<const Lz77Store*> ptrs(np);
+  for (size_t p = 0; p < np; ++p) ptrs[p] = &stores[p];
+  std::vector<std::vector<size_t>> pts;
+  BlockSplitLz77Batch(ptrs, static_cast<size_t>(call->options.blocksplittingmax), &pts);
+  for (size_t p = 0; p < np; ++p) {
+    PartState& s = call->st[p];
+    s.split_bytes = SplitPointsToBytes(stores[p], pts[p], s.part.instart);
+    if (call->options.verbose) s.log += SplitPointsLine(s.split_bytes, s.part.instart);   // blocksplitter.c:266-268
+  }
+}
+
+// many parts: a search per thread; *ns_store, *ns_search: what building the stores and searching them took, over all parts
+void FirstSplitOneByOne(DeflateCall* call, const std::vector<SymbolRun>& greedy, std::atomic<uint64_t>* ns_store,
+                        std::atomic<uint64_t>* ns_search) {
+  ParallelForWide(call->np(), [&](size_t p) {
+    PartState& s = call->st[p];
+    const double a = Now();
+    Lz77Store store = StoreFromRun(greedy[p], s.part.instart);
+    const double b = Now();
+    std::vector<size_t> pts;
+    BlockSplitLz77(store, static_cast<size_t>(call->options.blocksplittingmax), &pts);
+    s.split_bytes = SplitPointsToBytes(store, pts, s.part.instart);
+    if (call->options.verbose) s.log += SplitPointsLine(s.split_bytes, s.part.instart);   // blocksplitter.c:266-268
+    ns_store->fetch_add(static_cast<uint64_t>((b - a) * 1e9), std::memory_order_relaxed);
+    ns_search->fetch_add(static_cast<uint64_t>((Now() - b) * 1e9), std::memory_order_relaxed);
+  });
+}
+
+int FirstSplit(DeflateCall* call) {
+  zmx_ctx* ctx = call->ctx;
+  const size_t np = call->np();
+  std::vector<zmx_block> ranges(np);
+  for (size_t p = 0; p < np; ++p) ranges[p] = {call->st[p].part.instart, call->st[p].part.inend};
+  std::vector<SymbolRun> greedy;
+  std::vector<uint32_t> greedy_nsym;
+  call->timer.Start();
+  // (the symbols stay on the device until somebody wants them on the host: with the search's block sizes computed there
+  //  nobody does — a shard of incompressible data is 130 MB of them)
+  const bool may_device = DeviceSplitAllowed(np, 6);
+  int rc = Lz77GreedyBatch(ctx, ranges, &greedy, &call->split_tables, &greedy_nsym, may_device);
+  if (rc) return rc;
+  call->timer.End(PhaseTimer::kGreedy);
+  std::atomic<uint64_t> ns_store{0}, ns_search{0};
+  size_t greedy_symbols = 0, part_bytes = 0;
+  for (size_t p = 0; p < np; ++p) { greedy_symbols += greedy_nsym[p]; part_bytes += ranges[p].inend - ranges[p].instart; }
+  const bool dev_done = may_device && DeviceSplitPays(greedy_symbols, part_bytes) && FirstSplitOnDevice(call, greedy_nsym);
+  if (!dev_done) {
+    if (may_device) {   // the symbols after all
+      rc = Lz77GreedyDownload(ctx, call->split_tables, greedy_nsym, &greedy);
       if (rc) return rc;
     }
-    if (dev_done) {
-    } else if (BatchSplit(np)) {
-      // a few parts: all their searches advance together, round by round, on the whole pool (block_split.cc)
-      std::vector<Lz77Store> stores(np);
-      ParallelForWide(np, [&](size_t p) { stores[p] = StoreFromRun(greedy[p], parts[p].instart); });
-      std::vector<const Lz77Store*> ptrs(np);
-      for (size_t p = 0; p < np; ++p) ptrs[p] = &stores[p];
-      std::vector<std::vector<size_t>> pts;
-      BlockSplitLz77Batch(ptrs, static_cast<size_t>(options.blocksplittingmax), &pts);
-      for (size_t p = 0; p < np; ++p) {
-        if (options.verbose) st[p].log += SplitPointsLine(stores[p], pts[p]);   // blocksplitter.c:266-268
-        split_bytes[p] = SplitPointsToBytes(stores[p], pts[p], parts[p].instart);
-      }
-    } else {
-      ParallelForWide(np, [&](size_t p) {
-        const double a = Now();
-        Lz77Store s = StoreFromRun(greedy[p], parts[p].instart);
-        const double b = Now();
-        std::vector<size_t> pts;
-        BlockSplitLz77(s, static_cast<size_t>(options.blocksplittingmax), &pts);
-        if (options.verbose) st[p].log += SplitPointsLine(s, pts);   // blocksplitter.c:266-268
-        split_bytes[p] = SplitPointsToBytes(s, pts, parts[p].instart);
-        ns_store.fetch_add(static_cast<uint64_t>((b - a) * 1e9), std::memory_order_relaxed);
-        ns_search.fetch_add(static_cast<uint64_t>((Now() - b) * 1e9), std::memory_order_relaxed);
-      });
-    }
-    ThreadTiming().split += Now() - t0;
-    if (TraceCallEnv()) {
-      std::fprintf(stderr, "    DeflateParts(%zu parts): greedy batch %.2f ms, first split %.2f ms (per part: store %.2f, search %.2f)\n", np,
-                   (t0 - tg0) * 1e3, (Now() - t0) * 1e3, ns_store.load() / 1e6 / np, ns_search.load() / 1e6 / np);
-    }
+    if (BatchSplit(np)) FirstSplitTogether(call, greedy);
+    else FirstSplitOneByOne(call, greedy, &ns_store, &ns_search);
   }
+  ThreadTiming().split += call->timer.End(PhaseTimer::kFirstSplit);
+  if (TraceCallEnv()) {
+    std::fprintf(stderr, "    DeflateParts(%zu parts): greedy batch %.2f ms, first split %.2f ms (per part: store %.2f, search %.2f)\n", np,
+                 call->timer.Ms(PhaseTimer::kGreedy), call->timer.Ms(PhaseTimer::kFirstSplit), ns_store.load() / 1e6 / np, ns_search.load() / 1e6 / np);
+  }
+  return 0;
+}
 
-  // ---- 2. optimal parse of every block of every part, one batch (deflate.c:854-869)
+// ---- 2. optimal parse of every block of every part, one batch (deflate.c:854-869)
+int OptimalParse(DeflateCall* call) {
   std::vector<zmx_block> all_blocks;
-  for (size_t p = 0; p < np; ++p) {
-    st[p].first_block = all_blocks.size();
-    const auto& sp = split_bytes[p];
+  for (PartState& s : call->st) {
+    s.first_block = all_blocks.size();
+    const auto& sp = s.split_bytes;
     for (size_t i = 0; i <= sp.size(); ++i) {
-      const size_t s = i == 0 ? parts[p].instart : sp[i - 1];
-      const size_t e = i == sp.size() ? parts[p].inend : sp[i];
-      st[p].blocks.push_back({s, e});
-      all_blocks.push_back({s, e});
+      const size_t b = i == 0 ? s.part.instart : sp[i - 1];
+      const size_t e = i == sp.size() ? s.part.inend : sp[i];
+      s.blocks.push_back({b, e});
+      all_blocks.push_back({b, e});
     }
   }
-  static const bool trace_phases = std::getenv("ZOPFLI_AMD_PROF") != nullptr || TraceCallEnv();
-  const double tp0 = Now();
-  std::vector<SymbolRun> runs;
-  // (ZOPFLI_AMD_DEVICE_ENCODE=0: every block's bits on the host, as in round 1)
-  static const bool device_encode = [] { const char* e = std::getenv("ZOPFLI_AMD_DEVICE_ENCODE"); return !e || std::atoi(e) != 0; }();
-  // Without block splitting a part is one block and nothing below needs its symbols on the host: sizes and trees
-  // come from the histogram of the best parse, the bits from the device.
-  const bool no_symbols = device_encode && !options.blocksplitting && all_blocks.size() == np;
-  OptimalKeep keep;
-  keep.skip_download = no_symbols;
-  rc = Lz77OptimalBatch(ctx, options, all_blocks, &runs, split_tables, device_encode ? &keep : nullptr);
-  if (rc) return rc;
-  struct TablesGuard {
-    zmx_ctx* ctx; zmx_tables* t;
-    ~TablesGuard() { if (t) zmx_tables_free(ctx, t); }
-  } tables_guard{ctx, keep.tables};
-  const double tp1 = Now();
+  call->timer.Start();
+  call->no_symbols = call->device_encode && !call->options.blocksplitting && all_blocks.size() == call->np();
+  call->keep.skip_download = call->no_symbols;
+  zmx_tables* parent = call->split_tables;
+  call->split_tables = nullptr;         // (Lz77OptimalBatch consumes them)
+  const int rc = Lz77OptimalBatch(call->ctx, call->options, all_blocks, &call->runs, parent, call->device_encode ? &call->keep : nullptr);
+  call->timer.End(PhaseTimer::kOptimal);
+  return rc;
+}
 
-  // ---- 3. join the blocks, second split attempt, per-block type costs
-  std::vector<zmx_block> fixed_requests;
-  std::vector<std::pair<size_t, size_t>> fixed_owner;  // (part, final index)
-  const double t3 = Now();
-  auto block_hist = [&](size_t block) {
-    Histogram h;
-    const uint32_t* c = &keep.hist[block * ZMX_HIST];
-    for (int k = 0; k < kNumLL; ++k) h.ll[k] = c[k];
-    for (int k = 0; k < kNumD; ++k) h.d[k] = c[kNumLL + k];
-    return h;
-  };
-  if (no_symbols) {
-    ParallelForWide(np, [&](size_t p) {   // one block per part; AddLZ77BlockAutoType (deflate.c:747-762) on its histogram
-      PartState& s = st[p];
-      s.log += runs[s.first_block].log;
-      const size_t nsym = keep.nsym[s.first_block];
-      const size_t length = s.blocks[0].inend - s.blocks[0].instart;
-      const Histogram h = block_hist(s.first_block);
-      FinalBlock f;
-      f.lstart = 0;
-      f.lend = nsym;
-      f.stored = static_cast<double>((length / 65535 + (length % 65535 ? 1 : 0)) * 5 * 8 + length * 8);   // deflate.c:591-597
-      f.fixed = BlockSizeFromHistogram(h, 1);
-      f.dynamic = BlockSizeFromHistogram(h, 2);
-      f.expensive_fixed = nsym < 1000 || f.fixed <= f.dynamic * 1.1;
-      s.block_sym_end.push_back(nsym);
-      s.finals.push_back(f);
-    });
-  } else {
-  std::vector<double> totalcost(np, 0.0);
-  ParallelForWide(np, [&](size_t p) {
-    PartState& s = st[p];
+// ---- 3. join the blocks, second split attempt, per-block type costs
+
+// A part's optimal parse = its blocks' parses, one after the other; what the blocks cost as they are.
+void JoinBlocks(DeflateCall* call) {
+  ParallelForWide(call->np(), [&](size_t p) {
+    PartState& s = call->st[p];
+    if (call->no_symbols) {     // one block, its symbols on the device only
+      s.log += call->runs[s.first_block].log;
+      s.block_sym_end.push_back(call->keep.nsym[s.first_block]);
+      return;
+    }
     const size_t npoints = s.blocks.size() - 1;
     {
       size_t total = 0;      // (one allocation for the part's store: appending block by block re-allocated it every time)
-      for (size_t i = 0; i <= npoints; ++i) total += runs[s.first_block + i].litlens.size();
+      for (size_t i = 0; i <= npoints; ++i) total += call->runs[s.first_block + i].litlens.size();
       s.lz77.Reserve(total);
     }
     for (size_t i = 0; i <= npoints; ++i) {
-      const SymbolRun& run = runs[s.first_block + i];
+      const SymbolRun& run = call->runs[s.first_block + i];
       s.log += run.log;       // "Iteration i: n bit" (squeeze.c:493), block after block
       // (the block's symbols straight into the part's store; the reference prices the block's own store,
       //  deflate.c:866: its size is what the fixed-tree rule of :615 looks at)
       const size_t lstart = s.lz77.size();
       s.lz77.Append(run.litlens.data(), run.dists.data(), run.litlens.size(), s.blocks[i].instart);
-      totalcost[p] += CalculateBlockSizeAutoTypeOf(s.lz77, lstart, s.lz77.size(), run.litlens.size());
+      s.totalcost += CalculateBlockSizeAutoTypeOf(s.lz77, lstart, s.lz77.size(), run.litlens.size());
       s.block_sym_end.push_back(s.lz77.size());
       if (i < npoints) s.splitpoints.push_back(s.lz77.size());
     }
   });
-  const double tj1 = Now();
-  // deflate.c:872-893: the second split attempt, on the optimal parse
-  std::vector<std::vector<size_t>> pts2(np);
-  std::vector<char> tried(np, 0);
-  for (size_t p = 0; p < np; ++p) tried[p] = options.blocksplitting && st[p].blocks.size() - 1 > 1;
+  call->timer.End(PhaseTimer::kJoin);
+}
+
+// deflate.c:872-893: the second split attempt, on the optimal parse
+void SecondSplit(DeflateCall* call) {
+  zmx_ctx* ctx = call->ctx;
+  std::vector<PartState>& st = call->st;
+  const size_t np = call->np();
+  const size_t maxblocks = static_cast<size_t>(call->options.blocksplittingmax);
   size_t ntried = 0, tried_symbols = 0, tried_bytes = 0;
-  for (size_t p = 0; p < np; ++p) {
-    if (!tried[p]) continue;
+  for (PartState& s : st) {
+    s.tried2 = call->options.blocksplitting && s.blocks.size() - 1 > 1;
+    if (!s.tried2) continue;
     ++ntried;
-    tried_symbols += st[p].lz77.size();
-    tried_bytes += parts[p].inend - parts[p].instart;
+    tried_symbols += s.lz77.size();
+    tried_bytes += s.part.inend - s.part.instart;
   }
   // (the second try has fewer sequences — only the parts that were split — and as many rounds: from 24 sequences on)
-  const bool dev_split2 = device_encode && keep.tables != nullptr && DeviceSplit(ntried, 24, tried_symbols, tried_bytes);
-  if (BatchSplit(np) || dev_split2) {
+  const bool on_device = call->device_encode && call->keep.tables != nullptr && DeviceSplitAllowed(ntried, 24) &&
+                         DeviceSplitPays(tried_symbols, tried_bytes);
+  if (BatchSplit(np) || on_device) {
     std::vector<const Lz77Store*> ptrs;
     std::vector<size_t> owner;
-    for (size_t p = 0; p < np; ++p) if (tried[p]) { ptrs.push_back(&st[p].lz77); owner.push_back(p); }
+    for (size_t p = 0; p < np; ++p) if (st[p].tried2) { ptrs.push_back(&st[p].lz77); owner.push_back(p); }
     std::vector<std::vector<size_t>> got;
     CostStoresGuard dev{ctx};
     CostBatchFn fn;
-    if (dev_split2 && !ptrs.empty()) {
+    if (on_device && !ptrs.empty()) {
       // a part's optimal parse = the best stores of its blocks, one after the other, where they lie on the device
+      const OptimalKeep& keep = call->keep;
       std::vector<size_t> first(owner.size() + 1, 0), blk, nsym;
       std::vector<int32_t> slot;
       for (size_t i = 0; i < owner.size(); ++i) {
@@ -390,30 +421,59 @@ int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const st
       if (zmx_cost_stores_create(ctx, keep.tables, owner.size(), first.data(), blk.data(), slot.data(), nsym.data(), &dev.cs) == 0) fn = DeviceCosts(ctx, dev.cs);
       else if (TraceCallEnv()) std::fprintf(stderr, "    DeflateParts: no device block sizes (%s): the host evaluates\n", zmx_last_error());
     }
-    BlockSplitLz77Batch(ptrs, static_cast<size_t>(options.blocksplittingmax), &got, fn ? &fn : nullptr, DeviceSplitMin());
-    for (size_t i = 0; i < owner.size(); ++i) pts2[owner[i]].swap(got[i]);
+    BlockSplitLz77Batch(ptrs, maxblocks, &got, fn ? &fn : nullptr, HostSwitches().device_split_min);
+    for (size_t i = 0; i < owner.size(); ++i) st[owner[i]].points2.swap(got[i]);
   } else {
     ParallelForWide(np, [&](size_t p) {
-      if (tried[p]) BlockSplitLz77(st[p].lz77, static_cast<size_t>(options.blocksplittingmax), &pts2[p]);
+      if (st[p].tried2) BlockSplitLz77(st[p].lz77, maxblocks, &st[p].points2);
     });
   }
-  const double tj2 = Now();
-  ParallelForWide(np, [&](size_t p) {
-    PartState& s = st[p];
-    if (tried[p]) {
-      if (options.verbose) s.log += SplitPointsLine(s.lz77, pts2[p]);
+  call->timer.End(PhaseTimer::kSecondSplit);
+}
+
+// The part's final blocks — those of the second split where it is cheaper (deflate.c:887-893) — and what each costs
+// stored, fixed and dynamic: AddLZ77BlockAutoType, deflate.c:747-762.
+void PriceFinalBlocks(DeflateCall* call) {
+  const bool verbose = call->options.verbose;
+  ParallelForWide(call->np(), [&](size_t p) {
+    PartState& s = call->st[p];
+    if (call->no_symbols) {   // the one block, on its histogram
+      const size_t nsym = call->keep.nsym[s.first_block];
+      const Histogram h = HistogramFrom(&call->keep.hist[s.first_block * ZMX_HIST]);
+      FinalBlock f;
+      f.lend = nsym;
+      f.instart = s.blocks[0].instart;
+      f.inend = s.blocks[0].inend;
+      const size_t length = f.inend - f.instart;
+      f.stored = static_cast<double>((length / 65535 + (length % 65535 ? 1 : 0)) * 5 * 8 + length * 8);   // deflate.c:591-597
+      f.fixed = BlockSizeFromHistogram(h, 1);
+      f.dynamic = BlockSizeFromHistogram(h, 2);
+      f.expensive_fixed = nsym < 1000 || f.fixed <= f.dynamic * 1.1;
+      s.finals.push_back(f);
+      return;
+    }
+    if (s.tried2) {
+      if (verbose) {
+        std::vector<size_t> positions;
+        for (size_t pt : s.points2) positions.push_back(s.lz77.pos(pt));
+        s.log += SplitPointsLine(positions, s.part.instart);
+      }
       double totalcost2 = 0;
-      for (size_t i = 0; i <= pts2[p].size(); ++i) {
-        const size_t a = i == 0 ? 0 : pts2[p][i - 1];
-        const size_t b = i == pts2[p].size() ? s.lz77.size() : pts2[p][i];
+      for (size_t i = 0; i <= s.points2.size(); ++i) {
+        const size_t a = i == 0 ? 0 : s.points2[i - 1];
+        const size_t b = i == s.points2.size() ? s.lz77.size() : s.points2[i];
         totalcost2 += CalculateBlockSizeAutoType(s.lz77, a, b);
       }
-      if (totalcost2 < totalcost[p]) s.splitpoints.swap(pts2[p]);
+      if (totalcost2 < s.totalcost) s.splitpoints.swap(s.points2);
     }
-    for (size_t i = 0; i <= s.splitpoints.size(); ++i) {  // AddLZ77BlockAutoType, deflate.c:747-762
+    for (size_t i = 0; i <= s.splitpoints.size(); ++i) {
       FinalBlock f;
       f.lstart = i == 0 ? 0 : s.splitpoints[i - 1];
       f.lend = i == s.splitpoints.size() ? s.lz77.size() : s.splitpoints[i];
+      if (f.lstart != f.lend) {
+        f.instart = s.lz77.pos(f.lstart);
+        f.inend = f.instart + s.lz77.ByteRange(f.lstart, f.lend);
+      }
       f.stored = CalculateBlockSize(s.lz77, f.lstart, f.lend, 0);
       f.fixed = CalculateBlockSize(s.lz77, f.lstart, f.lend, 1);
       f.dynamic = CalculateBlockSize(s.lz77, f.lstart, f.lend, 2);
@@ -421,194 +481,219 @@ int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const st
       s.finals.push_back(f);
     }
   });
-  if (TraceCallEnv()) {
-    std::fprintf(stderr, "    DeflateParts(%zu parts): optimal batch %.2f ms; stores joined %.2f ms, second split %.2f ms, block costs %.2f ms\n", np,
-                 (tp1 - tp0) * 1e3, (tj1 - t3) * 1e3, (tj2 - tj1) * 1e3, (Now() - tj2) * 1e3);
+  const PhaseTimer& t = call->timer;
+  call->timer.End(PhaseTimer::kCosts);
+  if (TraceCallEnv() && !call->no_symbols) {
+    std::fprintf(stderr, "    DeflateParts(%zu parts): optimal batch %.2f ms; stores joined %.2f ms, second split %.2f ms, block costs %.2f ms\n", call->np(),
+                 t.Ms(PhaseTimer::kOptimal), t.Ms(PhaseTimer::kJoin), t.Ms(PhaseTimer::kSecondSplit), t.Ms(PhaseTimer::kCosts));
   }
-  }
-  ThreadTiming().split += Now() - t3;
+  ThreadTiming().split += t.s[PhaseTimer::kJoin] + t.s[PhaseTimer::kSecondSplit] + t.s[PhaseTimer::kCosts];
+}
 
-  for (size_t p = 0; p < np; ++p) {
-    for (size_t i = 0; i < st[p].finals.size(); ++i) {
-      FinalBlock& f = st[p].finals[i];
+// ---- 4. fixed-tree re-parse where it may win (deflate.c:770-781)
+int RequestFixedReparses(DeflateCall* call) {
+  for (PartState& s : call->st) {
+    for (FinalBlock& f : s.finals) {
       if (f.lstart == f.lend || !f.expensive_fixed) continue;
-      const size_t instart = no_symbols ? st[p].blocks[0].instart : st[p].lz77.pos(f.lstart);
-      const size_t inend = no_symbols ? st[p].blocks[0].inend : instart + st[p].lz77.ByteRange(f.lstart, f.lend);
-      f.fixed_request = static_cast<long>(fixed_requests.size());
-      fixed_requests.push_back({instart, inend});
+      f.fixed_request = static_cast<long>(call->fixed_requests.size());
+      call->fixed_requests.push_back({f.instart, f.inend});
     }
   }
-
-  // ---- 4. fixed-tree re-parse where it may win (deflate.c:770-781)
-  const double tp2 = Now();
+  call->timer.End(PhaseTimer::kRequests);
   // (with the device bit writer the re-parses stay on the device as well: their cost comes from their histograms,
   //  their bits — where the fixed tree wins — from zmx_encode_blocks.  Incompressible input asks for a re-parse of
   //  every block: downloading those stores and indexing them on the host was most of what such input cost.)
-  std::vector<SymbolRun> fixed_runs;
   // (the tables of the optimal batch are only wanted for their stores from here on: the bit writer reads them.  Records,
   //  codes, window records and snapshots go back to the pool before the fixed-tree batch builds its own)
-  if (keep.tables) {
-    rc = zmx_tables_trim(ctx, keep.tables);
+  if (call->keep.tables) {
+    const int rc = zmx_tables_trim(call->ctx, call->keep.tables);
     if (rc) return rc;
   }
-  OptimalKeep fkeep;
-  fkeep.skip_download = device_encode;
-  rc = Lz77OptimalFixedBatch(ctx, fixed_requests, &fixed_runs, device_encode ? &fkeep : nullptr);
-  if (rc) return rc;
-  TablesGuard fixed_guard{ctx, fkeep.tables};
-  const double tp3 = Now();
+  call->fkeep.skip_download = call->device_encode;
+  const int rc = Lz77OptimalFixedBatch(call->ctx, call->fixed_requests, &call->fixed_runs, call->device_encode ? &call->fkeep : nullptr);
+  call->timer.End(PhaseTimer::kFixed);
+  return rc;
+}
 
-  // ---- 5. pick the block type and encode
-  const double t5 = Now();
+// ---- 5. pick the block type and encode: final block `i` of part `p`
+void ChooseAndEncodeBlock(DeflateCall* call, size_t p, size_t i) {
+  PartState& s = call->st[p];
+  const OptimalKeep& keep = call->keep;
+  const OptimalKeep& fkeep = call->fkeep;
+  const FinalBlock& f = s.finals[i];
+  const bool final_block = (i + 1 == s.finals.size()) && s.part.final_part;
+  BitWriter w;
+  if (f.lstart == f.lend) {  // smallest empty block: fixed, end symbol only
+    w.AddBits(final_block ? 1 : 0, 1);
+    w.AddBits(1, 2);
+    w.AddBits(0, 7);
+    s.chunks[i] = BitsChunk(&w);
+    return;
+  }
+  double fixedcost = f.fixed;
+  Lz77Store fixedstore;
+  Histogram fixedhist;
+  if (f.expensive_fixed) {
+    if (fkeep.tables) {
+      fixedhist = HistogramFrom(&fkeep.hist[static_cast<size_t>(f.fixed_request) * ZMX_HIST]);
+      fixedcost = BlockSizeFromHistogram(fixedhist, 1);
+    } else {
+      fixedstore = StoreFromRun(call->fixed_runs[f.fixed_request], call->fixed_requests[f.fixed_request].instart);
+      fixedcost = CalculateBlockSize(fixedstore, 0, fixedstore.size(), 1);
+    }
+  }
+  if (f.stored < fixedcost && f.stored < f.dynamic) {
+    Chunk c;
+    c.kind = Chunk::kStored;
+    c.start = f.instart;
+    c.end = f.inend;
+    c.final_block = final_block;
+    s.chunks[i] = std::move(c);
+    return;
+  }
+  size_t tree_bits = 0;
+  const int used_btype = fixedcost < f.dynamic ? 1 : 2;
+  // the symbols of a block that is a whole block of the optimal batch are still on the device: it writes them
+  long dev_block = -1;
+  const bool fixed_on_device = used_btype == 1 && f.expensive_fixed && fkeep.tables != nullptr;
+  if (fixed_on_device) dev_block = f.fixed_request;
+  if (keep.tables && !(used_btype == 1 && f.expensive_fixed)) {
+    for (size_t k = 0; k < s.block_sym_end.size(); ++k) {
+      if (s.block_sym_end[k] == f.lend && (k == 0 ? 0 : s.block_sym_end[k - 1]) == f.lstart) dev_block = static_cast<long>(s.first_block + k);
+    }
+  }
+  Chunk c;
+  if (dev_block >= 0) {
+    DeviceEncode e;
+    e.from_fixed = fixed_on_device;
+    Histogram h;
+    if (fixed_on_device) h = fixedhist;          // (not read for btype 1)
+    else if (call->no_symbols) h = HistogramFrom(&keep.hist[s.first_block * ZMX_HIST]);
+    else s.lz77.GetHistogram(f.lstart, f.lend, &h);
+    e.data_bits = EncodeBlockHeader(h, used_btype, final_block, &w, &tree_bits, e.codes);
+    e.header = w.Finish(&e.header_bits);
+    e.block = static_cast<size_t>(dev_block);
+    e.chunk = i;
+    e.used = true;
+    c.kind = Chunk::kBits;
+    c.nbits = e.header_bits + e.data_bits;
+    s.enc[i] = std::move(e);
+  } else {
+    if (used_btype == 1) {
+      if (f.expensive_fixed) {
+        EncodeBlock(fixedstore, 0, fixedstore.size(), 1, final_block, &w);
+      } else {
+        EncodeBlock(s.lz77, f.lstart, f.lend, 1, final_block, &w);
+      }
+    } else {
+      EncodeBlock(s.lz77, f.lstart, f.lend, 2, final_block, &w, &tree_bits);
+    }
+    c = BitsChunk(&w);
+  }
+  c.log_block = true;
+  c.log_btype = used_btype;
+  c.log_tree_bits = tree_bits;
+  c.log_unc = f.inend - f.instart;
+  s.chunks[i] = std::move(c);
+}
+
+// ---- 5b. the device writes the symbols of its blocks behind the headers: the blocks of the optimal batch (`fixed` false)
+//          or those of the fixed-tree re-parses
+int WriteBitsOnDevice(DeflateCall* call, bool fixed) {
+  std::vector<PartState>& st = call->st;
+  const OptimalKeep& kp = fixed ? call->fkeep : call->keep;
+  if (!kp.tables) return 0;
+  std::vector<zmx_enc_job> jobs;
+  std::vector<uint32_t> codes;
+  std::vector<unsigned char*> outs;
+  std::vector<std::pair<size_t, size_t>> owner;    // (part, index in its enc)
+  for (size_t p = 0; p < st.size(); ++p) {
+    for (size_t k = 0; k < st[p].enc.size(); ++k) {
+      DeviceEncode& e = st[p].enc[k];
+      if (e.from_fixed != fixed) continue;
+      zmx_enc_job j;
+      j.block = static_cast<uint32_t>(e.block);
+      j.slot = kp.slot[e.block];
+      j.nsym = kp.nsym[e.block];
+      j.bit_start = static_cast<uint32_t>(e.header_bits);
+      j.nbits = e.data_bits;
+      jobs.push_back(j);
+      codes.insert(codes.end(), e.codes, e.codes + 320);
+      owner.push_back({p, k});
+    }
+  }
+  if (jobs.empty()) return 0;
+  // (the chunks' memory — a third of the input's size in all — is allocated and touched by the workers, not by
+  //  this thread: first-touch page faults of 30 MB were most of what this phase took)
+  outs.resize(jobs.size());
+  ParallelFor(jobs.size(), [&](size_t i) {
+    Chunk& c = st[owner[i].first].chunks[st[owner[i].first].enc[owner[i].second].chunk];
+    c.bits.assign((c.nbits + 7) / 8, 0);
+    outs[i] = c.bits.data();
+  });
+  const int rc = zmx_encode_blocks(call->ctx, kp.tables, jobs.size(), jobs.data(), codes.data(), outs.data());
+  if (rc) return rc;
+  ParallelFor(jobs.size(), [&](size_t i) {
+    const DeviceEncode& e = st[owner[i].first].enc[owner[i].second];
+    uint8_t* b = st[owner[i].first].chunks[e.chunk].bits.data();
+    for (size_t k = 0; k < e.header.size(); ++k) b[k] |= e.header[k];
+  });
+  return 0;
+}
+
+int EncodeBlocks(DeflateCall* call) {
+  std::vector<PartState>& st = call->st;
   // One task per final BLOCK, not per part: a block the device cannot write (the second split attempt moved its
   // ends: its symbols are a stretch of several device blocks) has its bits made here, symbol by symbol — 4 ms for the
   // 250 000 symbols of one master block, a tenth of a 1 MB call when its blocks took turns on one thread.
   struct BlockTask { size_t p, i; };
   std::vector<BlockTask> block_tasks;
-  for (size_t p = 0; p < np; ++p) {
+  for (size_t p = 0; p < st.size(); ++p) {
     st[p].chunks.assign(st[p].finals.size(), Chunk());
     st[p].enc.assign(st[p].finals.size(), DeviceEncode());
     for (size_t i = 0; i < st[p].finals.size(); ++i) block_tasks.push_back({p, i});
   }
-  ParallelForWide(block_tasks.size(), [&](size_t task) {
-    const size_t p = block_tasks[task].p, i = block_tasks[task].i;
-    PartState& s = st[p];
-    const FinalBlock& f = s.finals[i];
-    const bool final_block = (i + 1 == s.finals.size()) && s.part.final_part;
-    BitWriter w;
-    if (f.lstart == f.lend) {  // smallest empty block: fixed, end symbol only
-      w.AddBits(final_block ? 1 : 0, 1);
-      w.AddBits(1, 2);
-      w.AddBits(0, 7);
-      s.chunks[i] = BitsChunk(&w);
-      return;
-    }
-    double fixedcost = f.fixed;
-    Lz77Store fixedstore;
-    Histogram fixedhist;
-    if (f.expensive_fixed) {
-      if (fkeep.tables) {
-        const uint32_t* c = &fkeep.hist[static_cast<size_t>(f.fixed_request) * ZMX_HIST];
-        for (int k = 0; k < kNumLL; ++k) fixedhist.ll[k] = c[k];
-        for (int k = 0; k < kNumD; ++k) fixedhist.d[k] = c[kNumLL + k];
-        fixedcost = BlockSizeFromHistogram(fixedhist, 1);
-      } else {
-        fixedstore = StoreFromRun(fixed_runs[f.fixed_request], fixed_requests[f.fixed_request].instart);
-        fixedcost = CalculateBlockSize(fixedstore, 0, fixedstore.size(), 1);
-      }
-    }
-    if (f.stored < fixedcost && f.stored < f.dynamic) {
-      Chunk c;
-      c.kind = Chunk::kStored;
-      c.start = no_symbols ? s.blocks[0].instart : s.lz77.pos(f.lstart);
-      c.end = no_symbols ? s.blocks[0].inend : c.start + s.lz77.ByteRange(f.lstart, f.lend);
-      c.final_block = final_block;
-      s.chunks[i] = std::move(c);
-      return;
-    }
-    size_t tree_bits = 0;
-    const int used_btype = fixedcost < f.dynamic ? 1 : 2;
-    // the symbols of a block that is a whole block of the optimal batch are still on the device: it writes them
-    long dev_block = -1;
-    const bool fixed_on_device = used_btype == 1 && f.expensive_fixed && fkeep.tables != nullptr;
-    if (fixed_on_device) dev_block = f.fixed_request;
-    if (keep.tables && !(used_btype == 1 && f.expensive_fixed)) {
-      for (size_t k = 0; k < s.block_sym_end.size(); ++k) {
-        if (s.block_sym_end[k] == f.lend && (k == 0 ? 0 : s.block_sym_end[k - 1]) == f.lstart) dev_block = static_cast<long>(s.first_block + k);
-      }
-    }
-    Chunk c;
-    if (dev_block >= 0) {
-      DeviceEncode e;
-      e.from_fixed = fixed_on_device;
-      Histogram h;
-      if (fixed_on_device) h = fixedhist;          // (not read for btype 1)
-      else if (no_symbols) h = block_hist(s.first_block);
-      else s.lz77.GetHistogram(f.lstart, f.lend, &h);
-      e.data_bits = EncodeBlockHeader(h, used_btype, final_block, &w, &tree_bits, e.codes);
-      e.header = w.Finish(&e.header_bits);
-      e.block = static_cast<size_t>(dev_block);
-      e.chunk = i;
-      e.used = true;
-      c.kind = Chunk::kBits;
-      c.nbits = e.header_bits + e.data_bits;
-      s.enc[i] = std::move(e);
-    } else {
-      if (used_btype == 1) {
-        if (f.expensive_fixed) {
-          EncodeBlock(fixedstore, 0, fixedstore.size(), 1, final_block, &w);
-        } else {
-          EncodeBlock(s.lz77, f.lstart, f.lend, 1, final_block, &w);
-        }
-      } else {
-        EncodeBlock(s.lz77, f.lstart, f.lend, 2, final_block, &w, &tree_bits);
-      }
-      c = BitsChunk(&w);
-    }
-    c.log_block = true;
-    c.log_btype = used_btype;
-    c.log_tree_bits = tree_bits;
-    c.log_unc = no_symbols ? s.blocks[0].inend - s.blocks[0].instart : s.lz77.ByteRange(f.lstart, f.lend);
-    s.chunks[i] = std::move(c);
-  });
-  for (size_t p = 0; p < np; ++p) {
-    PartState& s = st[p];
+  ParallelForWide(block_tasks.size(), [&](size_t task) { ChooseAndEncodeBlock(call, block_tasks[task].p, block_tasks[task].i); });
+  for (PartState& s : st) {
     s.enc.erase(std::remove_if(s.enc.begin(), s.enc.end(), [](const DeviceEncode& e) { return !e.used; }), s.enc.end());
-    if (options.verbose && !s.chunks.empty()) s.chunks.front().log_pre = std::move(s.log);
+    if (call->options.verbose && !s.chunks.empty()) s.chunks.front().log_pre = std::move(s.log);
   }
-  // ---- 5b. the device writes the symbols of its blocks behind the headers (the blocks of the optimal batch, then
-  //          those of the fixed-tree re-parses)
-  for (int pass = 0; pass < 2; ++pass) {
-    const OptimalKeep& kp = pass == 0 ? keep : fkeep;
-    if (!kp.tables) continue;
-    std::vector<zmx_enc_job> jobs;
-    std::vector<uint32_t> codes;
-    std::vector<unsigned char*> outs;
-    std::vector<std::pair<size_t, size_t>> owner;    // (part, index in its enc)
-    for (size_t p = 0; p < np; ++p) {
-      for (size_t k = 0; k < st[p].enc.size(); ++k) {
-        DeviceEncode& e = st[p].enc[k];
-        if (e.from_fixed != (pass == 1)) continue;
-        zmx_enc_job j;
-        j.block = static_cast<uint32_t>(e.block);
-        j.slot = kp.slot[e.block];
-        j.nsym = kp.nsym[e.block];
-        j.bit_start = static_cast<uint32_t>(e.header_bits);
-        j.nbits = e.data_bits;
-        jobs.push_back(j);
-        codes.insert(codes.end(), e.codes, e.codes + 320);
-        owner.push_back({p, k});
-      }
-    }
-    if (jobs.empty()) continue;
-    // (the chunks' memory — a third of the input's size in all — is allocated and touched by the workers, not by
-    //  this thread: first-touch page faults of 30 MB were most of what this phase took)
-    outs.resize(jobs.size());
-    ParallelFor(jobs.size(), [&](size_t i) {
-      Chunk& c = st[owner[i].first].chunks[st[owner[i].first].enc[owner[i].second].chunk];
-      c.bits.assign((c.nbits + 7) / 8, 0);
-      outs[i] = c.bits.data();
-    });
-    rc = zmx_encode_blocks(ctx, kp.tables, jobs.size(), jobs.data(), codes.data(), outs.data());
-    if (rc) return rc;
-    ParallelFor(jobs.size(), [&](size_t i) {
-      const DeviceEncode& e = st[owner[i].first].enc[owner[i].second];
-      uint8_t* b = st[owner[i].first].chunks[e.chunk].bits.data();
-      for (size_t k = 0; k < e.header.size(); ++k) b[k] |= e.header[k];
-    });
-  }
-  ThreadTiming().encode += Now() - t5;
+  int rc = WriteBitsOnDevice(call, /*fixed=*/false);
+  if (!rc) rc = WriteBitsOnDevice(call, /*fixed=*/true);
+  if (rc) return rc;
+  ThreadTiming().encode += call->timer.End(PhaseTimer::kEncode);
+  return 0;
+}
 
-  const double tp4 = Now();
-  for (size_t p = 0; p < np; ++p) {
-    for (auto& c : st[p].chunks) chunks->push_back(std::move(c));
-    if (part_chunks) part_chunks->push_back(st[p].chunks.size());
-  }
-  if (trace_phases) {
+void Collect(DeflateCall* call, std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks) {
+  MoveChunks(&call->st, chunks, part_chunks);
+  const PhaseTimer& t = call->timer;
+  call->timer.End(PhaseTimer::kCollect);
+  if (HostSwitches().prof || TraceCallEnv()) {
     std::fprintf(stderr, "DeflateParts: optimal batch %.1f ms, join/split %.1f ms, fixed batch %.1f ms (%zu requests), "
-                 "encode %.1f ms, chunk move %.1f ms\n", (tp1 - tp0) * 1e3, (tp2 - tp1) * 1e3, (tp3 - tp2) * 1e3,
-                 fixed_requests.size(), (tp4 - tp3) * 1e3, (Now() - tp4) * 1e3);
+                 "encode %.1f ms, chunk move %.1f ms\n", t.Ms(PhaseTimer::kOptimal),
+                 t.Ms(PhaseTimer::kJoin) + t.Ms(PhaseTimer::kSecondSplit) + t.Ms(PhaseTimer::kCosts) + t.Ms(PhaseTimer::kRequests),
+                 t.Ms(PhaseTimer::kFixed), call->fixed_requests.size(), t.Ms(PhaseTimer::kEncode), t.Ms(PhaseTimer::kCollect));
   }
+}
+
+}  // namespace
+
+int DeflateParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const std::vector<Part>& parts,
+                 std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks) {
+  if (btype == 0) return StoredParts(parts, chunks, part_chunks);
+  if (btype == 1) return FixedParts(ctx, parts, chunks, part_chunks);
+  DeflateCall call(ctx, options, parts);
+  int rc = options.blocksplitting ? FirstSplit(&call) : 0;
+  if (!rc) rc = OptimalParse(&call);
+  if (rc) return rc;
+  JoinBlocks(&call);
+  if (!call.no_symbols) SecondSplit(&call);
+  PriceFinalBlocks(&call);
+  rc = RequestFixedReparses(&call);
+  if (!rc) rc = EncodeBlocks(&call);
+  if (rc) return rc;
+  Collect(&call, chunks, part_chunks);
   return 0;
 }
 
@@ -645,6 +730,22 @@ unsigned PeekBits(const uint8_t* src, size_t src_bytes, size_t s0, unsigned n) {
   return (v >> r) & ((1u << n) - 1u);
 }
 
+struct Place { size_t bit0; };    // where a chunk starts in the output, in bits
+
+// What the reference prints while it writes the blocks (deflate.c:719-744): byte counts of the
+// growing output array, i.e. differences of ceil(bit position / 8)
+void PrintBlockLog(const std::vector<Chunk>& chunks, const std::vector<Place>& place) {
+  for (size_t i = 0; i < chunks.size(); ++i) {
+    const Chunk& c = chunks[i];
+    if (!c.log_pre.empty()) std::fputs(c.log_pre.c_str(), stderr);
+    if (c.kind != Chunk::kBits || !c.log_block) continue;
+    const size_t p1 = place[i].bit0 + 3, p2 = p1 + c.log_tree_bits, p3 = place[i].bit0 + c.nbits;
+    if (c.log_btype == 2) std::fprintf(stderr, "treesize: %d\n", static_cast<int>((p2 + 7) / 8 - (p1 + 7) / 8));
+    const size_t compressed = (p3 + 7) / 8 - (p2 + 7) / 8;
+    std::fprintf(stderr, "compressed block size: %d (%dk) (unc: %d)\n", static_cast<int>(compressed),
+                 static_cast<int>(compressed / 1024), static_cast<int>(c.log_unc));
+  }
+}
 }  // namespace
 
 // Joins the chunks at the running bit position of `stream`.  Every chunk's place in the output is
@@ -654,7 +755,6 @@ unsigned PeekBits(const uint8_t* src, size_t src_bytes, size_t s0, unsigned n) {
 // at most 65535 bytes, each byte-aligned after its 3 header bits.
 void MergeChunks(const std::vector<Chunk>& chunks, const unsigned char* in, unsigned char* bp,
                  unsigned char** outp, size_t* outsize, bool verbose) {
-  struct Place { size_t bit0; };
   std::vector<Place> place(chunks.size());
   // bit position 0 = the first bit of (*outp)[0]; *bp bits of the last byte are used
   unsigned bp0 = *bp & 7u;
@@ -677,20 +777,7 @@ void MergeChunks(const std::vector<Chunk>& chunks, const unsigned char* in, unsi
       }
     }
   }
-  if (verbose) {
-    // what the reference prints while it writes the blocks (deflate.c:719-744): byte counts of the
-    // growing output array, i.e. differences of ceil(bit position / 8)
-    for (size_t i = 0; i < chunks.size(); ++i) {
-      const Chunk& c = chunks[i];
-      if (!c.log_pre.empty()) std::fputs(c.log_pre.c_str(), stderr);
-      if (c.kind != Chunk::kBits || !c.log_block) continue;
-      const size_t p1 = place[i].bit0 + 3, p2 = p1 + c.log_tree_bits, p3 = place[i].bit0 + c.nbits;
-      if (c.log_btype == 2) std::fprintf(stderr, "treesize: %d\n", static_cast<int>((p2 + 7) / 8 - (p1 + 7) / 8));
-      const size_t compressed = (p3 + 7) / 8 - (p2 + 7) / 8;
-      std::fprintf(stderr, "compressed block size: %d (%dk) (unc: %d)\n", static_cast<int>(compressed),
-                   static_cast<int>(compressed / 1024), static_cast<int>(c.log_unc));
-    }
-  }
+  if (verbose) PrintBlockLog(chunks, place);
   const size_t newsize = (cur + 7) / 8;
   const size_t keep = *outsize;   // bytes [0, keep) hold earlier output
   ReserveOutput(newsize - *outsize, outp, outsize, /*zero=*/false);

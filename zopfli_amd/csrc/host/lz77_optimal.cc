@@ -88,11 +88,6 @@ double ModelMinCost(const double* ll, const double* d) {
   return MatchCost(ll, d, bestlength, bestdist);
 }
 
-void ToHistogram(const uint32_t* hist, Histogram* h) {
-  for (int i = 0; i < kNumLL; ++i) h->ll[i] = hist[i];
-  for (int i = 0; i < kNumD; ++i) h->d[i] = hist[kNumLL + i];
-}
-
 struct BlockIter {
   SymbolStats stats, beststats, laststats;
   Mwc rng;
@@ -128,10 +123,7 @@ int DownloadAll(zmx_ctx* ctx, zmx_tables* t, const std::vector<int32_t>& slot, c
 }  // namespace
 
 // ZOPFLI_AMD_VERIFY: ZopfliVerifyLenDist (lz77.c:270-295) on the device for every parse that is kept
-static bool VerifyWanted() {
-  static const bool v = [] { const char* e = std::getenv("ZOPFLI_AMD_VERIFY"); return e && std::atoi(e) != 0; }();
-  return v;
-}
+static bool VerifyWanted() { return HostSwitches().verify; }
 static int VerifyAll(zmx_ctx* ctx, zmx_tables* t, const std::vector<int32_t>& slot, const std::vector<uint32_t>& nsym) {
   std::vector<size_t> block(slot.size()), n(nsym.begin(), nsym.end());
   for (size_t b = 0; b < block.size(); ++b) block[b] = b;
@@ -229,8 +221,7 @@ int Lz77OptimalBatch(zmx_ctx* ctx, const ZopfliOptions& options, const std::vect
     ParallelFor(nb, [&](size_t b) {
       BlockIter& s = it[b];
       const uint32_t* h = &hist[b * ZMX_HIST];
-      Histogram hh;
-      ToHistogram(h, &hh);
+      const Histogram hh = HistogramFrom(h);
       // ZopfliCalculateBlockSize(&currentstore, 0, size, 2): depends on the
       // histogram only (deflate.c:584 -> :569 -> :383)
       const double c = BlockSizeFromHistogram(hh, 2);

@@ -22,6 +22,14 @@ struct Histogram {
   void Clear() { std::memset(this, 0, sizeof(*this)); }
 };
 
+// The device layer's histogram of a block (ZMX_HIST counters: the litlen symbols, then the distance symbols).
+inline Histogram HistogramFrom(const uint32_t* counts) {
+  Histogram h;
+  for (int i = 0; i < kNumLL; ++i) h.ll[i] = counts[i];
+  for (int i = 0; i < kNumD; ++i) h.d[i] = counts[kNumLL + i];
+  return h;
+}
+
 class Lz77Store {
  public:
   // (a sample is 2.5 KB: every 256 symbols that was 10 bytes written per symbol, more than the symbols themselves — a store of

@@ -24,6 +24,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "host_knobs.h"
+
 namespace zamd {
 
 // The processors this process may run on: the online count cut down by the scheduling affinity.  A
@@ -71,10 +73,7 @@ inline unsigned QuotaCap(unsigned n) {
 
 inline unsigned HostThreads() {
   static const unsigned n = [] {
-    if (const char* e = std::getenv("ZOPFLI_AMD_THREADS")) {
-      const int v = std::atoi(e);
-      if (v > 0) return static_cast<unsigned>(v);
-    }
+    if (HostSwitches().threads) return HostSwitches().threads;
     const unsigned hc = UsableCpus();
     // beyond this the wake-up cost outweighs the per-block work (the cost model of a block's next run takes a few
     // microseconds since the package-merge rewrite; measured per 100 MB request, 15 runs: 2.8 ms of cost-model phase
@@ -90,11 +89,8 @@ inline unsigned HostThreads() {
 // and the wake-up cost is paid three times per call, not twice per squeeze run.
 inline unsigned WideThreads() {
   static const unsigned n = [] {
-    if (const char* e = std::getenv("ZOPFLI_AMD_WIDE_THREADS")) {    // (for measuring)
-      const int v = std::atoi(e);
-      if (v > 0) return static_cast<unsigned>(v);
-    }
-    if (std::getenv("ZOPFLI_AMD_THREADS")) return HostThreads();   // an explicit budget covers both pools
+    if (HostSwitches().wide_threads) return HostSwitches().wide_threads;    // (for measuring)
+    if (HostSwitches().threads_set) return HostThreads();   // an explicit budget covers both pools
     const unsigned hc = UsableCpus();
     const unsigned cap = 128;
     const unsigned w = QuotaCap(hc < cap ? hc : cap);
