@@ -458,7 +458,8 @@ int zmx_last_match_walk(double* out3);
  * busy) returns -2, "come back with fewer blocks", like one beyond that budget.  zmx_ctx_trim_cache gives an IDLE
  * context's cached arrays back to the device; the hook (one per process, may be null) is called with the device index when
  * an allocation still fails after the failing context dropped its own cache — the owner of the contexts trims the idle
- * ones there — and the allocation is tried once more.  zmx_ctx_set_share tells a context how many share its device. */
+ * ones there — and the allocation is tried once more.  zmx_ctx_set_share keeps nothing (the budgets are the device's, however many share it): it refuses a null context and
+ * returns 0. */
 typedef void (*zmx_oom_hook_t)(int device);
 void zmx_set_oom_hook(zmx_oom_hook_t hook);
 int zmx_ctx_set_share(zmx_ctx* ctx, unsigned contexts_on_device);

@@ -268,7 +268,7 @@ def test_rounds_of_master_blocks():
 
 
 def test_calls_of_few_master_blocks_are_dealt_from_the_nth_on():
-    """api.cc ContextPool::Acquire, `polite`: a call below 32 master blocks is dealt over three contexts of its device
+    """context_pool.h ContextPool::Acquire, `polite`: a call below 32 master blocks is dealt over three contexts of its device
     (from 4 master blocks on with block splitting), but the contexts beyond the first are only created from the process's
     ZOPFLI_AMD_DEAL_AFTER-th such call on (8 by default: setting a context up costs more than a short-lived program gets
     back).  With 3: the call trace shows one shard for the first two calls and three for the third and fourth; all four
@@ -434,7 +434,7 @@ def test_checksum_pieces_and_combine(host):
 
 def test_concurrent_callers():
     """The reference has no globals: concurrent calls on distinct buffers are allowed.  Here a request
-    takes one of a device's contexts (api.cc ContextPool: ZOPFLI_AMD_LANES of them per device, three by default) and
+    takes one of a device's contexts (context_pool.h ContextPool: ZOPFLI_AMD_LANES of them per device, three by default) and
     other callers overlap with it or wait: four threads, each with its own input, get what they get alone."""
     import threading
 

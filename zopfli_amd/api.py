@@ -246,6 +246,25 @@ class Context:
             self.lib.zmx_ctx_destroy(self.handle)
             self.handle = ctypes.c_void_p()
 
+    def pool_stats(self):
+        """zmx_internal_pool_stats: the context's memory pool in numbers (reads only).  live / live_bytes: device arrays
+        in use; cached / cached_bytes: blocks kept for the next request; device_cached: what all contexts of the device
+        keep cached; pinned: cached pinned host buffers; fresh / from_cache: allocations served by hipMalloc / from the
+        cache since the context was created."""
+        out = (ctypes.c_uint64 * 8)()
+        fn = self.lib.zmx_internal_pool_stats
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        fn.restype = None
+        fn(self.handle, out)
+        keys = ["live", "live_bytes", "cached", "cached_bytes", "device_cached", "pinned", "fresh", "from_cache"]
+        return dict(zip(keys, [int(v) for v in out]))
+
+    def trim_cache(self):
+        """zmx_ctx_trim_cache: the cached blocks go back to the device."""
+        fn = self.lib.zmx_ctx_trim_cache
+        fn.argtypes = [ctypes.c_void_p]
+        self._check(fn(self.handle), "zmx_ctx_trim_cache")
+
     def set_input(self, data):
         self._input = data
         self._segments = None

@@ -109,31 +109,9 @@ constexpr u32 kMatchGrid = 1024;  // persistent workgroups: 256 CUs x 4 (LDS-lim
 constexpr u32 kMatchGrid5 = 1536; // k_match5: 256 CUs x 6 workgroups of 4 waves (its scratch is k_match2's: 1536 x 256 <= 1024 x 512 lanes)
 constexpr size_t kInputPad = 4096;
 
-// ---------------------------------------------------------------------------------------------
-// ZOPFLI_AMD_GUARD=1 — a debugging mode for the device allocations (round-2 verdict: an unexplained
-// "Memory access fault by GPU" must be localisable).  Every pooled or direct allocation gets a red zone of
-// kGuardBytes before and after it, filled with 0xA5; its body is filled with 0xCD whenever it is handed out
-// (fresh or recycled: stale contents of an earlier batch cannot stand in for data a kernel forgot to write);
-// after EVERY kernel launch the stream is drained and k_guard_check reads all red zones of the context: the
-// first byte that changed is reported with the kernel that just ran, the allocation's tag and size, and the
-// offset.  Slow (a synchronisation per launch); off by default.
-// ---------------------------------------------------------------------------------------------
-constexpr size_t kGuardBytes = 4096;
-constexpr u32 kGuardMaxAllocs = 256;
-bool GuardOn() { return Knobs().guard; }
-
 }  // namespace
 
-// zones[2 i], zones[2 i + 1] = device addresses of the two red zones of allocation i; res = {flag, alloc, offset, value}
-__global__ __launch_bounds__(256) void k_guard_check(const u64* zones, u32 nzones, u32* res) {
-  const u32 z = blockIdx.x;
-  if (z >= nzones) return;
-  const u32* q = reinterpret_cast<const u32*>(zones[z]);
-  for (u32 i = threadIdx.x; i < kGuardBytes / 4; i += 256) {
-    const u32 v = q[i];
-    if (v != 0xa5a5a5a5u && atomicCAS(&res[0], 0u, 1u) == 0u) { res[1] = z; res[2] = i * 4; res[3] = v; }
-  }
-}
+#include "zmx_pool.h"
 
 struct zmx_ctx {
   int device = 0;
@@ -144,30 +122,15 @@ struct zmx_ctx {
   std::vector<u64> seg_starts;          // zmx_set_input_segments: first byte of each independent input (empty: one input)
   u32* d_scratch = nullptr;  // k_match2 per-lane overflow change points
   u32* d_scratch5 = nullptr; // k_match5's (it may run beside k_match2)
-  // table arrays are recycled between batches and calls: hipMalloc/hipFree of multi-GB arrays
-  // cost more than the kernels that fill them
-  std::unordered_map<void*, size_t> pool_live;
-  std::vector<std::pair<void*, size_t>> pool_free;
-  size_t pool_free_bytes = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipStream_t stream2 = nullptr;   // the run tasks' k_dp5_spec beside the others' (zmx_squeeze_run)
   bool stream2_outstanding = false;   // a kernel on stream2 reads pooled scratch arrays and `stream` has not been made to wait for it yet
   hipStream_t alt_stream[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};   // zmx_ctx_set_priority: [0] the created pair, [1] high, [2] low
   hipEvent_t ev2[2] = {nullptr, nullptr};
   u32* h_stage = nullptr;    // pinned staging for store downloads (grow-only)
-  // pinned buffers of table sets that were freed (h_runin / h_runout: a few KB per block), kept for the next set:
-  // hipHostMalloc + hipHostFree were ~ 0.4 ms of every table set, a tenth of a small call's fixed cost
-  std::vector<std::pair<unsigned char*, size_t>> pinned_free;
   size_t stage_cap = 0;      // in u32
-  // ZOPFLI_AMD_GUARD (below): the bytes the caller asked for and who asked, per live allocation (keyed like pool_live)
-  struct GuardInfo { size_t bytes; const char* tag; };
-  std::unordered_map<void*, GuardInfo> guard_live;
-  size_t pool_keep = 0;      // what the pool may keep cached between batches, and what one batch's DP edges may take:
-  size_t code_budget = 0;    // a third of the device's memory each (hipMemGetInfo at creation), at most 96 GiB,
-  size_t keep_base = 0;
-  unsigned shares = 1;       // contexts on this device (zmx_ctx_set_share)
-  u64* d_guard_tab = nullptr;   // [kGuardMaxAllocs][2] zone pairs for k_guard_check, then 4 result words
-  u64 guard_checks = 0;
+  size_t code_budget = 0;    // what one batch's DP edges may take (BuildDpRows): a third of the device's memory (hipMemGetInfo at creation), at most 96 GiB
+  DevicePool pool;           // every device array and pinned buffer of the context (zmx_pool.h)
 };
 
 // What a squeeze run takes and gives, each side ONE array on the device and one pinned mirror on the host, so that a run
@@ -297,80 +260,9 @@ namespace {
 
 constexpr size_t kPoolKeepMax = 96ull << 30;
 
-// The red zones and the poison of an allocation that is being handed out (guard mode): base = what hipMalloc
-// returned, the caller gets base + kGuardBytes.
-hipError_t GuardDress(zmx_ctx* c, void* base, size_t bytes, size_t cap, const char* tag, void** user) {
-  unsigned char* b = static_cast<unsigned char*>(base);
-  const size_t body = (bytes + 15) & ~static_cast<size_t>(15);
-  hipError_t e = hipMemsetAsync(b, 0xa5, kGuardBytes, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(b + kGuardBytes, 0xcd, cap - 2 * kGuardBytes, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(b + kGuardBytes + body, 0xa5, kGuardBytes, c->stream);
-  *user = b + kGuardBytes;
-  c->guard_live[*user] = zmx_ctx::GuardInfo{body, tag};
-  return e;
-}
-
-std::atomic<zmx_oom_hook_t> g_oom_hook{nullptr};
-// What the pools of ALL contexts of a device keep cached between batches, against ONE budget per device (a third of its
-// memory): a lone busy context may cache all of it (100 MB of long runs are 52 GB of DP codes per batch; with a
-// per-context third of a third they were hipFree'd and hipMalloc'ed every step: class Z 132 -> 49 MB/s), three busy
-// ones share it, and idle ones are trimmed when another runs out (zmx_set_oom_hook).
-constexpr int kMaxDevices = 64;
-std::atomic<size_t> g_dev_cached[kMaxDevices];
-inline std::atomic<size_t>& DevCached(const zmx_ctx* c) { return g_dev_cached[c->device >= 0 && c->device < kMaxDevices ? c->device : 0]; }
-
-hipError_t PoolAllocBytes(zmx_ctx* c, void** p, size_t bytes, const char* tag) {
-  if (bytes == 0) bytes = 1;
-  const bool guard = GuardOn();
-  const size_t want = guard ? ((bytes + 15) & ~static_cast<size_t>(15)) + 2 * kGuardBytes : bytes;
-  size_t best = c->pool_free.size();
-  for (size_t i = 0; i < c->pool_free.size(); ++i) {
-    const size_t cap = c->pool_free[i].second;
-    if (cap >= want && cap <= 2 * want + (1u << 20) && (best == c->pool_free.size() || cap < c->pool_free[best].second)) {
-      best = i;
-    }
-  }
-  void* base = nullptr;
-  size_t cap = want;
-  if (best != c->pool_free.size()) {
-    base = c->pool_free[best].first;
-    cap = c->pool_free[best].second;
-    c->pool_free_bytes -= cap;
-    DevCached(c).fetch_sub(cap, std::memory_order_relaxed);
-    c->pool_free.erase(c->pool_free.begin() + static_cast<long>(best));
-  } else {
-    hipError_t e = hipMalloc(&base, want);
-    if (e != hipSuccess && !c->pool_free.empty()) {  // out of memory: drop the cache and retry
-      (void)hipGetLastError();
-      for (auto& f : c->pool_free) (void)hipFree(f.first);
-      c->pool_free.clear();
-      DevCached(c).fetch_sub(c->pool_free_bytes, std::memory_order_relaxed);
-      c->pool_free_bytes = 0;
-      e = hipMalloc(&base, want);
-    }
-    if (e != hipSuccess) {
-      // still out of memory: the idle contexts of the same device may sit on gigabytes of cached arrays (the owner
-      // of the contexts — api.cc's ContextPool — trims them through this hook)
-      if (const zmx_oom_hook_t hook = g_oom_hook.load(std::memory_order_acquire)) {
-        (void)hipGetLastError();
-        hook(c->device);
-        e = hipMalloc(&base, want);
-      }
-    }
-    if (e != hipSuccess) return e;
-  }
-  *p = base;
-  if (guard) {
-    const hipError_t e = GuardDress(c, base, bytes, cap, tag, p);
-    if (e != hipSuccess) return e;
-  }
-  c->pool_live[*p] = cap;
-  return hipSuccess;
-}
-
 template <typename T>
 hipError_t PoolAllocT(zmx_ctx* c, T** p, size_t n, const char* tag) {
-  return PoolAllocBytes(c, reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T), tag);
+  return c->pool.Alloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T), tag, c->stream);
 }
 #define PoolAlloc(c, p, n) PoolAllocT(c, p, n, #p)
 
@@ -410,75 +302,17 @@ struct PoolScope {
   }
 };
 
+// (zmx_tables_free without a context: straight back to the device)
 void PoolFree(zmx_ctx* c, void* p) {
-  if (!p) return;
-  void* base = p;
-  if (c) {
-    auto it = c->pool_live.find(p);
-    if (it != c->pool_live.end()) {
-      const size_t cap = it->second;
-      c->pool_live.erase(it);
-      if (c->guard_live.erase(p)) base = static_cast<unsigned char*>(p) - kGuardBytes;
-      if (DevCached(c).load(std::memory_order_relaxed) + cap > c->pool_keep &&
-          DevCached(c).load(std::memory_order_relaxed) > c->pool_free_bytes) {
-        // the device's cache budget is used up and some of it is ANOTHER context's: the idle contexts' caches go
-        // first — the context that is working is the one whose arrays will be asked for again.  (Not when the cache is
-        // all this context's own: the hook would take the pool's lock and find nothing, on every free of the hot path.)
-        if (const zmx_oom_hook_t hook = g_oom_hook.load(std::memory_order_acquire)) hook(c->device);
-      }
-      if (DevCached(c).load(std::memory_order_relaxed) + cap <= c->pool_keep) {
-        c->pool_free.emplace_back(base, cap);
-        c->pool_free_bytes += cap;
-        DevCached(c).fetch_add(cap, std::memory_order_relaxed);
-        return;
-      }
-    }
-  }
-  (void)hipFree(base);
+  if (c) c->pool.Free(p);
+  else if (p) (void)hipFree(p);
 }
 
-// Guard mode: drain the stream and check every red zone of the context.  `where` = the kernel that just ran.
-int GuardVerify(zmx_ctx* c, const char* where) {
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return FailFault(std::string("ZOPFLI_AMD_GUARD: the stream failed after ") + where);
-  if (c->guard_live.empty()) return 0;
-  // (ZOPFLI_AMD_GUARD_SELFTEST=N: the N-th check finds a byte that this function itself just broke — the test that the
-  //  mode reports what it is there to report)
-  const u64 selftest = Knobs().guard_selftest;
-  std::vector<std::pair<void*, zmx_ctx::GuardInfo>> live(c->guard_live.begin(), c->guard_live.end());
-  if (!c->d_guard_tab) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_guard_tab), (2 * static_cast<size_t>(kGuardMaxAllocs) + 2) * sizeof(u64)));
-  ++c->guard_checks;
-  // every live allocation, kGuardMaxAllocs at a time (a context that holds parent, optimal and fixed-tree tables plus
-  // temporaries has more than one table's worth)
-  for (size_t first = 0; first < live.size(); first += kGuardMaxAllocs) {
-    const u32 n = static_cast<u32>(std::min<size_t>(live.size() - first, kGuardMaxAllocs));
-    std::vector<u64> tab(2 * static_cast<size_t>(kGuardMaxAllocs) + 2, 0);
-    for (u32 i = 0; i < n; ++i) {
-      const unsigned char* user = static_cast<const unsigned char*>(live[first + i].first);
-      tab[2 * i] = reinterpret_cast<u64>(user - kGuardBytes);
-      tab[2 * i + 1] = reinterpret_cast<u64>(user + live[first + i].second.bytes);
-    }
-    if (first == 0 && selftest && c->guard_checks == selftest) HIPCHK(hipMemset(reinterpret_cast<void*>(tab[1] + 100), 0x5a, 1));
-    HIPCHK(hipMemcpy(c->d_guard_tab, tab.data(), tab.size() * sizeof(u64), hipMemcpyHostToDevice));   // (the result words zeroed with it)
-    u32* res = reinterpret_cast<u32*>(c->d_guard_tab + 2 * static_cast<size_t>(kGuardMaxAllocs));
-    hipLaunchKernelGGL(k_guard_check, dim3(2 * n), dim3(256), 0, c->stream, c->d_guard_tab, 2 * n, res);
-    HIPCHK(hipGetLastError());
-    u32 h[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpy(h, res, sizeof(h), hipMemcpyDeviceToHost));
-    if (h[0] == 0) continue;
-    const auto& g = live[first + (h[1] >> 1)].second;
-    char buf[400];
-    std::snprintf(buf, sizeof(buf), "ZOPFLI_AMD_GUARD: after %s the red zone %s allocation '%s' (%zu bytes) changed: byte offset %u of the zone holds 0x%08x",
-                  where, (h[1] & 1u) ? "behind" : "in front of", g.tag ? g.tag : "?", g.bytes, h[2], h[3]);
-    std::fprintf(stderr, "%s\n", buf);
-    return FailFault(buf);
-  }
-  return 0;
-}
 // after every kernel launch: the launch error, and in guard mode the red zones
 #define KCHK(c, name)                                            \
   do {                                                           \
     HIPCHK(hipGetLastError());                                   \
-    if (GuardOn()) { const int rc_ = GuardVerify(c, name); if (rc_) return rc_; } \
+    if (GuardOn()) { const int rc_ = (c)->pool.GuardVerify((c)->stream, name); if (rc_) return rc_; } \
   } while (0)
 
 PoolScope::~PoolScope() {
@@ -515,15 +349,12 @@ void zmx_set_kernel_timing(int on) { g_kernel_timing.store(on ? 1 : 0, std::memo
 
 int zmx_has_experiments(void) { return 0; }   // (always 0; kept for ABI)
 
-void zmx_set_oom_hook(zmx_oom_hook_t hook) { g_oom_hook.store(hook, std::memory_order_release); }
+void zmx_set_oom_hook(zmx_oom_hook_t hook) { DevicePool::SetOomHook(hook); }
 
-int zmx_ctx_set_share(zmx_ctx* c, unsigned contexts_on_device) {
+// Keeps nothing: the budgets are per DEVICE, whoever uses them (zmx_pool.h), and no context needs to know how many share
+// its device.  Kept for the ABI.
+int zmx_ctx_set_share(zmx_ctx* c, unsigned /*contexts_on_device*/) {
   if (!c) return FailMsg("zmx_ctx_set_share: no context");
-  // (The budgets are per DEVICE now, whoever uses them: the cache of all its contexts together against one third of its
-  //  memory — g_dev_cached —, one batch's DP edges against one third.  The number of contexts that share the device is
-  //  kept for the record; a build that cannot allocate because the others are busy comes back as "too large" and the
-  //  caller halves the batch.)
-  c->shares = contexts_on_device ? contexts_on_device : 1;
   return 0;
 }
 
@@ -531,10 +362,7 @@ int zmx_ctx_trim_cache(zmx_ctx* c) {
   if (!c) return 0;
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
-  for (auto& f : c->pool_free) (void)hipFree(f.first);
-  c->pool_free.clear();
-  DevCached(c).fetch_sub(c->pool_free_bytes, std::memory_order_relaxed);
-  c->pool_free_bytes = 0;
+  c->pool.DropCache();
   return 0;
 }
 
@@ -555,6 +383,8 @@ int zmx_internal_device(zmx_ctx* ctx) { return ctx->device; }
 void zmx_internal_set_error(const char* msg) { g_err = msg; g_err_class = ZMX_ERR_DEVICE; }
 void zmx_internal_set_error_class(const char* msg, int cls) { g_err = msg; g_err_class = cls; }
 const unsigned char* zmx_internal_input_host(zmx_ctx* ctx) { return ctx->h_in; }
+// the context's memory pool in numbers (DevicePool::Stats says which); reads only
+__attribute__((visibility("default"))) void zmx_internal_pool_stats(zmx_ctx* ctx, uint64_t out[8]) { ctx->pool.Stats(out); }
 
 void zmx_internal_seg_stats(double* out8, int reset) {
   // (thread-local: no lock)
@@ -594,27 +424,32 @@ void zmx_internal_stats_add(const double* in19) {
   for (int i = 0; i < 19; ++i) d[i] += in19[i];
 }
 
-// Pinned host buffers of a context, recycled between table sets (see zmx_ctx::pinned_free).
-static hipError_t PinnedTake(zmx_ctx* c, unsigned char** p, size_t bytes, size_t* cap) {
-  size_t best = c->pinned_free.size();
-  for (size_t i = 0; i < c->pinned_free.size(); ++i) {
-    const size_t k = c->pinned_free[i].second;
-    if (k >= bytes && k <= 4 * bytes + 4096 && (best == c->pinned_free.size() || k < c->pinned_free[best].second)) best = i;
-  }
-  if (best != c->pinned_free.size()) {
-    *p = c->pinned_free[best].first;
-    *cap = c->pinned_free[best].second;
-    c->pinned_free.erase(c->pinned_free.begin() + static_cast<long>(best));
-    return hipSuccess;
-  }
-  *cap = bytes < 4096 ? 4096 : bytes;
-  return hipHostMalloc(reinterpret_cast<void**>(p), *cap, hipHostMallocDefault);
-}
+// (no context: as PoolFree)
 static void PinnedGive(zmx_ctx* c, unsigned char** p, size_t cap) {
   if (!*p) return;
-  if (c && c->pinned_free.size() < 8 && cap <= (64u << 20)) c->pinned_free.emplace_back(*p, cap);
+  if (c) c->pool.PinnedGive(*p, cap);
   else (void)hipHostFree(*p);
   *p = nullptr;
+}
+
+// The streams, events and budgets of a new context, on its device.
+static int InitContext(zmx_ctx* c) {
+  HIPCHK(hipStreamCreate(&c->stream));
+  for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&c->ev[i]));
+  HIPCHK(hipStreamCreate(&c->stream2));
+  for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&c->ev2[i], hipEventDisableTiming));
+  {
+    // Budgets from what the device has, not from what an MI355X has on paper: several contexts may share one
+    // device (ZOPFLI_AMD_DEVICES=0,0), other processes may hold memory already.
+    size_t mem_free = 0, mem_total = 0;
+    HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+    c->code_budget = std::min<size_t>(kPoolKeepMax, mem_free / 3);
+    c->pool.Init(c->device, c->code_budget);
+  }
+
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             CH_LDS_BYTES));
+  return 0;
 }
 
 int zmx_ctx_create(int device, zmx_ctx** out) {
@@ -630,22 +465,11 @@ int zmx_ctx_create(int device, zmx_ctx** out) {
   }
   zmx_ctx* c = new zmx_ctx();
   c->device = device;
-  HIPCHK(hipStreamCreate(&c->stream));
-  for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&c->ev[i]));
-  HIPCHK(hipStreamCreate(&c->stream2));
-  for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&c->ev2[i], hipEventDisableTiming));
-  {
-    // Budgets from what the device has, not from what an MI355X has on paper: several contexts may share one
-    // device (ZOPFLI_AMD_DEVICES=0,0), other processes may hold memory already.
-    size_t mem_free = 0, mem_total = 0;
-    HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-    c->keep_base = std::min<size_t>(kPoolKeepMax, mem_free / 3);
-    c->pool_keep = c->keep_base;
-    c->code_budget = c->keep_base;
+  const int rc = InitContext(c);
+  if (rc != 0) {
+    zmx_ctx_destroy(c);   // (what InitContext made so far; the error it reported stays)
+    return rc;
   }
-
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             CH_LDS_BYTES));
   *out = c;
   return 0;
 }
@@ -682,12 +506,7 @@ void zmx_ctx_destroy(zmx_ctx* c) {
   if (!c) return;
   DeviceGuard dev_guard(c->device);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (auto& f : c->pinned_free) (void)hipHostFree(f.first);
-  for (auto& f : c->pool_free) (void)hipFree(f.first);
-  DevCached(c).fetch_sub(c->pool_free_bytes, std::memory_order_relaxed);
-  // (the input and k_match2's scratch are pooled allocations too; in guard mode the caller's pointer lies behind a red zone)
-  for (auto& f : c->pool_live) (void)hipFree(c->guard_live.count(f.first) ? static_cast<unsigned char*>(f.first) - kGuardBytes : f.first);
-  (void)hipFree(c->d_guard_tab);
+  c->pool.ReleaseAll();   // (the input and k_match2's scratch are pooled allocations too)
   for (int i = 0; i < 4; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   for (int i = 0; i < 2; ++i) if (c->ev2[i]) (void)hipEventDestroy(c->ev2[i]);
   if (c->alt_stream[0][0]) {       // (stream / stream2 are one of these pairs)
@@ -917,8 +736,8 @@ static int AllocTableArrays(zmx_ctx* c, zmx_tables* t, u64 la_off) {
   t->run = RunLayout(nb);
   HIPCHK(PoolAlloc(c, &t->d_runin, t->run.in_bytes));
   HIPCHK(PoolAlloc(c, &t->d_runout, t->run.out_bytes));
-  HIPCHK(PinnedTake(c, &t->h_runin, t->run.in_bytes, &t->h_runin_cap));
-  HIPCHK(PinnedTake(c, &t->h_runout, t->run.out_bytes, &t->h_runout_cap));
+  HIPCHK(c->pool.PinnedTake(&t->h_runin, t->run.in_bytes, &t->h_runin_cap));
+  HIPCHK(c->pool.PinnedTake(&t->h_runout, t->run.out_bytes, &t->h_runout_cap));
   t->d_slot = t->run.slot(t->d_runin);
   t->d_hist = t->run.hist(t->d_runout);
   t->d_nsym = t->run.nsym(t->d_runout);

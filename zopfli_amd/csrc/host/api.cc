@@ -18,6 +18,7 @@
 
 #include "block_cache.h"
 #include "block_cost.h"
+#include "context_pool.h"
 #include "deflate.h"
 #include "lz77_optimal.h"
 #include "symbols.h"
@@ -39,9 +40,7 @@ extern "C" size_t zmx_internal_input_size(zmx_ctx* ctx);
 extern "C" const unsigned char* zmx_internal_input_host(zmx_ctx* ctx);
 extern "C" void zmx_internal_set_error(const char* msg);
 
-namespace {
-
-using zamd::kMasterBlock;
+namespace zamd {
 
 [[noreturn]] void Die(const char* what) {
   std::fprintf(stderr, "zopfli_amd: %s: %s\n", what, zmx_last_error());
@@ -72,211 +71,21 @@ void MaybeKeepHeap() {
   (void)once;
 }
 
-// The device contexts of the Zopfli* entry points.
-//
-// Which devices: ONE by default — ZOPFLI_AMD_DEVICE, else LOCAL_RANK (one process per GPU under torchrun), else
-// device 0: a program that links libzopfli.so.1 must not find itself holding every GPU of the node.  Several only
-// when asked: ZOPFLI_AMD_DEVICES = "all", a count, or a comma separated list of HIP device indices (an index may
-// repeat: two contexts on one device, which is how the multi-device path is exercised on a one-GPU box); master
-// blocks are independent (deflate.c:916-923), so a request with several of them is dealt across those devices.
-//
-// Re-entrancy (the reference has no globals: callers may run concurrent calls on distinct buffers): a
-// device has up to ZOPFLI_AMD_LANES contexts (default 3), created when first needed; a request takes one free
-// context on each device it uses and gives them back when it is done, so callers overlap — one's host phases
-// (cost models, block splitting, merging) with the others' kernels — and a fourth waits.  A device whose context
-// cannot be created (not gfx950, out of memory) is dropped from the list; only when none is left does the call die.
-class ContextPool {
- public:
-  // one free context on each of up to `want` devices (at least one), in device order; with `per_device` > 1 up to
-  // that many free contexts of every device it uses (a large request on one device is dealt over two of its
-  // contexts: one half's host phases run beside the other half's kernels)
-  // `polite`: a call that is not large takes several contexts of a device only while it is the only caller — with other
-  // calls in flight (holding contexts or waiting for one) it takes one, as every call below the dealing threshold does.
-  // `small`: a call below the 32 master blocks from which calls are dealt whatever else runs (small files — what zopfli is
-  // mostly used on — and the medium calls that, alone, politely take all three dealing contexts: a second such caller
-  // no longer waits for the first to finish).  When every context of its
-  // device is busy such a call gets a context of its own beyond the ZOPFLI_AMD_LANES of the dealing — up to
-  // ZOPFLI_AMD_SMALL_LANES (16) per device — instead of waiting: sixteen callers with 64 KiB files keep eight streams of
-  // small kernels and eight host threads' split searches going, where three contexts left thirteen of them waiting.
-  std::vector<zmx_ctx*> Acquire(size_t want, size_t per_device = 1, std::vector<int>* device_of = nullptr,
-                                bool polite = false, bool small = false) {
-    std::unique_lock<std::mutex> lock(mu_);
-    Init();
-    ++in_flight_;
-    // ... and it does not CREATE the further contexts before the eighth such call of the process (ZOPFLI_AMD_DEAL_AFTER):
-    // a context costs ~ 50 ms to set up and saves such a call 5 - 15 ms, which a program that compresses a few files
-    // and exits never earns back (zopflipng on one 1024 x 1024 image: 0.62 -> 0.70 s when its calls set up two more
-    // contexts); a long-lived caller pays once.  (The first context a call takes is created whenever none is free.)
-    const bool may_create_more = !polite || per_device <= 1 || ++polite_wishes_ >= zamd::HostSwitches().deal_after;
-    for (;;) {
-      if (polite && in_flight_ > 1) per_device = 1;
-      std::vector<Slot*> slots;
-      size_t used_devices = 0;
-      for (auto& dev : devices_) {
-        if (used_devices == want) break;
-        if (dev.dead) continue;
-        size_t here = 0;
-        for (size_t lane = 0; lane < per_device; ++lane) {
-          Slot* s = nullptr;
-          for (auto& sl : dev.slots) {
-            if (!sl->busy && std::find(slots.begin(), slots.end(), sl.get()) == slots.end()) { s = sl.get(); break; }
-          }
-          if (!s && (dev.slots.size() < lanes_ || (small && per_device == 1 && dev.slots.size() < small_lanes_)) &&
-              (may_create_more || lane == 0)) {
-            // a new context: the slot is taken now, the context is created below without the pool's lock (HIP
-            // start-up, streams, events: up to seconds on first use, and every Release would wait behind it)
-            dev.slots.emplace_back(new Slot{nullptr, false, &dev});
-            s = dev.slots.back().get();
-          }
-          if (!s) break;
-          slots.push_back(s);
-          ++here;
-        }
-        if (here) ++used_devices;
-      }
-      if (!slots.empty()) {
-        for (Slot* s : slots) s->busy = true;
-        bool need_create = false;
-        for (Slot* s : slots) need_create |= s->ctx == nullptr;
-        if (need_create) {
-          lock.unlock();
-          std::vector<std::pair<Slot*, zmx_ctx*>> made;
-          std::vector<std::pair<Slot*, std::string>> failed;
-          for (Slot* s : slots) {
-            if (s->ctx) continue;
-            zmx_ctx* c = nullptr;
-            if (zmx_ctx_create(s->dev->index, &c) != 0) failed.emplace_back(s, zmx_last_error());
-            else made.emplace_back(s, c);
-          }
-          lock.lock();
-          for (auto& m : made) {
-            m.first->ctx = m.second;
-            // budgets per DEVICE, not per context: every context of the device gets its share of what a lone
-            // context would keep cached / spend on one batch's DP edges
-            size_t same = 0;
-            for (auto& d : devices_) same += d.index == m.first->dev->index ? 1 : 0;
-            zmx_ctx_set_share(m.second, static_cast<unsigned>(lanes_ * same));
-          }
-          for (auto& f : failed) {
-            Device* dev = f.first->dev;
-            for (size_t i = 0; i < dev->slots.size(); ++i) {
-              if (dev->slots[i].get() == f.first) { dev->slots.erase(dev->slots.begin() + static_cast<long>(i)); break; }
-            }
-            slots.erase(std::find(slots.begin(), slots.end(), f.first));
-            if (dev->slots.empty()) {
-              std::fprintf(stderr, "zopfli_amd: device %d is not usable: %s\n", dev->index, f.second.c_str());
-              dev->dead = true;
-            }
-          }
-          if (!failed.empty()) cv_.notify_all();
-        }
-      }
-      bool any_alive = false;
-      for (auto& dev : devices_) any_alive |= !dev.dead;
-      if (!any_alive) Die("no usable gfx950 device (there is no CPU fallback)");
-      if (!slots.empty()) {
-        std::vector<zmx_ctx*> got;
-        for (Slot* s : slots) got.push_back(s->ctx);
-        if (device_of) {
-          device_of->clear();
-          for (Slot* s : slots) device_of->push_back(s->dev->index);
-        }
-        return got;
-      }
-      cv_.wait(lock);   // every context of every device is busy
-    }
-  }
-  // zmx_set_oom_hook: a context of `device` is out of memory even after dropping its own cache — the idle contexts of
-  // that device give their cached arrays back
-  void TrimIdle(int device) {
-    // hipFree synchronises the device: not under the pool's lock (every Acquire / Release would wait behind it).  The
-    // idle contexts are taken out of circulation, trimmed, and put back.
-    std::vector<Slot*> mine;
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      for (auto& dev : devices_) {
-        if (dev.index != device) continue;
-        for (auto& sl : dev.slots) if (!sl->busy && sl->ctx) { sl->busy = true; mine.push_back(sl.get()); }
-      }
-    }
-    if (mine.empty()) return;
-    for (Slot* sl : mine) zmx_ctx_trim_cache(sl->ctx);
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      for (Slot* sl : mine) sl->busy = false;
-    }
-    cv_.notify_all();
-  }
-  size_t InFlight() {
-    std::lock_guard<std::mutex> lock(mu_);
-    return in_flight_;
-  }
-  void Release(const std::vector<zmx_ctx*>& ctxs) {
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      if (in_flight_) --in_flight_;
-      for (auto& dev : devices_)
-        for (auto& sl : dev.slots)
-          if (std::find(ctxs.begin(), ctxs.end(), sl->ctx) != ctxs.end()) sl->busy = false;
-    }
-    cv_.notify_all();
-  }
+}  // namespace zamd
 
- private:
-  struct Device;
-  struct Slot { zmx_ctx* ctx; bool busy; Device* dev; };
-  struct Device { int index; bool dead = false; std::vector<std::unique_ptr<Slot>> slots; };
-  void Init() {
-    if (!devices_.empty()) return;
-    MaybeKeepHeap();
-    const int visible = zmx_device_count();
-    const zamd::PoolKnobs knobs = zamd::PoolSwitches(visible);
-    for (int d : knobs.devices) {
-      if (d < 0 || d >= visible) {
-        std::fprintf(stderr, "zopfli_amd: no HIP device %d (%d visible): ignored\n", d, visible);
-        continue;
-      }
-      Device dev;
-      dev.index = d;
-      devices_.push_back(std::move(dev));
-    }
-    if (devices_.empty()) {
-      zmx_internal_set_error("no HIP device to run on");
-      Die("no usable gfx950 device (there is no CPU fallback)");
-    }
-    lanes_ = knobs.lanes;
-    small_lanes_ = knobs.small_lanes;
-    zmx_set_oom_hook(&ContextPool::OomHook);
-  }
-  static void OomHook(int device);
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::vector<Device> devices_;
-  size_t lanes_ = 3;
-  size_t small_lanes_ = 16;  // contexts per device that calls of one or two master blocks may bring into being (1000 x 64 KiB through 16 callers: 8.9 MB/s with 3, 20.4 with 8, 27.7 with 16; profiles/r06_small_files.txt)
-  size_t in_flight_ = 0;     // calls between Acquire and Release
-  size_t polite_wishes_ = 0; // polite calls so far that asked for more than one context of a device
-};
+namespace {
 
-ContextPool& Pool() {
-  static ContextPool* pool = new ContextPool();   // (never destroyed: HIP may be gone by the time statics are)
-  return *pool;
-}
-void ContextPool::OomHook(int device) { Pool().TrimIdle(device); }
+using zamd::Die;
+using zamd::kMasterBlock;
+using zamd::Lease;
+using zamd::MaybeKeepHeap;
+using zamd::Pool;
 
 // ZOPFLI_AMD_TRACE_CALL=1: where a Zopfli* call's wall time goes, per shard and for the call (stderr)
 bool TraceCall() { return zamd::HostSwitches().trace_call; }
 double WallMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-
-struct Lease {
-  std::vector<int> device_of;      // HIP device index of ctxs[i]
-  std::vector<zmx_ctx*> ctxs;
-  explicit Lease(size_t want, size_t per_device = 1, bool polite = false, bool small = false)
-      : ctxs(Pool().Acquire(want, per_device, &device_of, polite, small)) {}
-  ~Lease() { Pool().Release(ctxs); }
-};
 
 std::vector<zamd::Part> MasterBlocks(size_t insize, bool final) {
   // deflate.c:916-923: do { ... } while (i < insize), so an empty input still

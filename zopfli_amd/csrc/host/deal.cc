@@ -126,6 +126,31 @@ std::vector<long> UploadAfter(const std::vector<int>& device_of) {
   return after;
 }
 
+std::vector<SlotPick> ChooseSlots(const std::vector<DeviceSlots>& devices, const SlotWish& wish) {
+  std::vector<SlotPick> picks;
+  size_t used_devices = 0;
+  for (size_t d = 0; d < devices.size() && used_devices != wish.want; ++d) {
+    const DeviceSlots& dev = devices[d];
+    if (dev.dead) continue;
+    size_t next = 0;                    // the existing slots before it are busy or picked
+    size_t total = dev.slots.size();    // ... with the new ones of this answer
+    size_t here = 0;
+    for (size_t lane = 0; lane < wish.per_device; ++lane, ++here) {
+      while (next < dev.slots.size() && dev.slots[next].busy) ++next;
+      if (next < dev.slots.size()) {
+        picks.push_back({d, next, !dev.slots[next].created});
+        ++next;
+        continue;
+      }
+      const bool room = total < wish.lanes || (wish.small && wish.per_device == 1 && total < wish.small_lanes);
+      if (!room || !(wish.may_create_more || lane == 0)) break;
+      picks.push_back({d, total++, true});
+    }
+    if (here) ++used_devices;
+  }
+  return picks;
+}
+
 }  // namespace zamd
 
 extern "C" {

@@ -38,4 +38,24 @@ std::vector<int> ShardPriorities(const std::vector<int>& device_of);
 // The shard whose upload each shard waits for: the one before it on the same device, -1 = none.
 std::vector<long> UploadAfter(const std::vector<int>& device_of);
 
+// Which contexts a call takes (context_pool.h: ContextPool::Acquire), as a function of a snapshot of the pool.  A device
+// has slots, each with one context or waiting for its own to be made.
+struct SlotState { bool busy, created; };
+struct DeviceSlots { int index; bool dead; std::vector<SlotState> slots; };
+struct SlotWish {
+  size_t want;            // devices (each with at least one slot)
+  size_t per_device;      // free slots of every device the call uses, at most
+  bool small;             // the call may bring a slot beyond `lanes` into being rather than wait
+  bool may_create_more;   // false: only a device's first slot of this call may be a new one
+  size_t lanes;           // slots per device
+  size_t small_lanes;     // ... with those that `small` calls add
+};
+// `slot` of the device at position `device` of the snapshot; slot >= its slots.size(): a new slot, to be appended.
+// `create`: the slot has no context yet.
+struct SlotPick { size_t device, slot; bool create; };
+// In device order, a device's existing free slots before its new ones; empty when everything is busy and nothing may be
+// made.  Dead devices are skipped.  A `small` call with per_device 1 fills the FIRST live device up to small_lanes before
+// it looks at the next one (ADVICE.md item 1 argues against that; the policy is kept as it is here).
+std::vector<SlotPick> ChooseSlots(const std::vector<DeviceSlots>& devices, const SlotWish& wish);
+
 }  // namespace zamd
