@@ -163,6 +163,16 @@ void zmx_ctx_destroy(zmx_ctx* ctx);
  * this context.  The calling thread's current HIP device is left as it was. */
 int zmx_set_input(zmx_ctx* ctx, const unsigned char* in, size_t insize);
 
+/* The same for bytes that already lie in device memory (a tensor, a checkpoint shard, a rendered frame): `d_in` is a
+ * device pointer, of this context's device or of another one (the bytes are copied into the context's own buffer with
+ * hipMemcpyDefault semantics, padded as for zmx_set_input).  The caller's buffer is only read, and only during the
+ * call: it need not outlive it, and the host keeps no pointer to the input — what it used to read of `in` (block ends,
+ * stored blocks' bytes) it takes from the context's copy.  The data must be complete when the call is made: the caller
+ * synchronises the stream that produced it.  Refused on the host, before any copy or launch (ZMX_ERR_REFUSED): a null
+ * pointer with a non-zero size, a pointer that is not device memory (host memory, pinned or not), managed memory, a
+ * range that leaves its allocation.  insize = 0 is valid with any pointer. */
+int zmx_set_input_device(zmx_ctx* ctx, const void* d_in, size_t insize);
+
 /* Declares the resident input (the last zmx_set_input, which resets it to one segment) to be the concatenation of nseg
  * independent inputs: segment i is bytes [starts[i], starts[i + 1]), the last one ends at the input's end; starts[0] = 0,
  * the starts never decrease and none lies past the end (empty segments are allowed).  From this call on the window of a
@@ -367,6 +377,18 @@ int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat output_type, s
                        const unsigned char* const* in, const size_t* insize,
                        unsigned char** out, size_t* outsize);
 
+/* ZopfliCompress of `insize` bytes of DEVICE memory at `d_in` (see zmx_set_input_device for what is taken and what is
+ * refused): *out, *outsize end as ZopfliCompress(options, output_type, the same bytes on the host, ...) leaves them —
+ * byte for byte, appended to a malloc'ed host array under the reference's convention; the caller frees.  The input never
+ * visits the host: the contexts copy their shards device to device (any device of ZOPFLI_AMD_DEVICES, whichever the
+ * pointer lies on), the dealing takes its estimates from counts made on the device, and only the bytes of stored
+ * blocks — incompressible data — come down, to be written into the stream.  Same context pool, dealing, priorities,
+ * shard retry and rounds as ZopfliCompress.  The data must be complete when the call is made (the caller synchronises
+ * its own stream); the buffer is only read and may be reused as soon as the call returns.  0 on success; -1 with
+ * zmx_last_error / zmx_last_error_class, and *out, *outsize unchanged, on failure. */
+int zmx_compress_device(const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in, size_t insize,
+                        unsigned char** out, size_t* outsize);
+
 /* -------- whole-stream entry points on a resident input (bench, multi-GPU) */
 
 /* ZopfliDeflate (deflate.c:908) of bytes [instart, inend) of the resident input,
@@ -418,6 +440,9 @@ int zmx_dist_gather(zmx_dist* dist, const unsigned char* blob, size_t size, unsi
  * their contexts this way; one-process-per-GPU launchers (zopfli_amd/sharding.py, bench.py) call these two. */
 int zmx_master_block_costs(const unsigned char* in, size_t insize, double* cost, size_t ncost);
 int zmx_deal_master_blocks(const double* cost, size_t nblocks, size_t shards, size_t* first);
+/* zmx_master_block_costs of the context's resident input (zmx_set_input or zmx_set_input_device), the probes counted on
+ * the device (k_probe_counts): the same doubles, bit for bit. */
+int zmx_master_block_costs_device(zmx_ctx* ctx, double* cost, size_t ncost);
 
 /* (The kernel, match and task statistics below are sums over the last Zopfli* / zmx_deflate_range call of the CALLING
  * THREAD — its shard threads' numbers included — reset when the call starts: concurrent callers read their own.)
@@ -441,6 +466,10 @@ void zmx_set_kernel_timing(int on);
 /* Host tail of the last call on this thread, seconds: [0] best LZ77 stores device -> host
  * [1] chunk serialisation (zmx_deflate_range). */
 int zmx_last_host_timing(double* out2);
+
+/* Input bytes the last Zopfli* / zmx_compress_* / zmx_deflate_range call on this thread moved: [0] host to device
+ * [1] device to device [2] device to host.  (A shard's upload includes the 32 KiB window before its first block.) */
+int zmx_last_input_traffic(double* out3);
 
 /* Match-table builds since the last Zopfli* / zmx_deflate_range call started (HIP events):
  * [0] seconds in the match kernel (k_match2 / k_match5) [1] seconds in k_same +

@@ -173,6 +173,55 @@ def compress_batch(datas, fmt=FORMAT_GZIP, options=None, lib=None):
     return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
 
 
+def _device_range(src, nbytes):
+    """(pointer, bytes) of an integer device pointer with `nbytes`, or of a contiguous tensor-like object."""
+    if isinstance(src, int):
+        if nbytes is None:
+            raise ValueError("a device pointer needs nbytes")
+        return src, int(nbytes)
+    if not src.is_contiguous():
+        raise ValueError("the tensor is not contiguous: its bytes are not one range of device memory")
+    size = src.numel() * src.element_size()
+    if nbytes is not None and int(nbytes) != size:
+        raise ValueError(f"nbytes = {nbytes}, but the tensor holds {size} bytes")
+    # the data must be complete before the library's own streams read it
+    if type(src).__module__.split(".")[0] == "torch":
+        import torch
+        torch.cuda.current_stream(src.device).synchronize()
+    return src.data_ptr(), size
+
+
+def compress_device(src, nbytes=None, fmt=FORMAT_GZIP, options=None, lib=None):
+    """zmx_compress_device: ZopfliCompress of bytes in device memory — `src` is an integer device pointer with `nbytes`,
+    or an object with data_ptr(), numel(), element_size() and is_contiguous() (a torch tensor, whose current stream is
+    synchronised first).  Raises ValueError for a non-contiguous tensor, RuntimeError with the library's message when the
+    library refuses the pointer or fails."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    ptr, size = _device_range(src, nbytes)
+    out, outsize = _u8p(), ctypes.c_size_t(0)
+    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
+    fn = lib.zmx_compress_device
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_u8p),
+                   ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), fmt, ptr, size, ctypes.byref(out), ctypes.byref(outsize)) != 0:
+        raise RuntimeError("zmx_compress_device: " + (lib.zmx_last_error() or b"").decode())
+    return _take(out, outsize)
+
+
+def last_input_traffic(lib=None):
+    """zmx_last_input_traffic: input bytes of this thread's last call that went host to device, device to device,
+    device to host."""
+    lib = lib or library()
+    t = (ctypes.c_double * 3)()
+    fn = lib.zmx_last_input_traffic
+    fn.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    fn.restype = ctypes.c_int
+    fn(t)
+    return [float(v) for v in t]
+
+
 def deflate(data, btype=2, final=1, options=None, lib=None):
     """ZopfliDeflate (deflate.c:908) from bp = 0; returns (bytes, bp)."""
     lib = lib or library()
@@ -230,6 +279,7 @@ class Context:
         self.lib = lib or library()
         self.handle = ctypes.c_void_p()
         self._input = None
+        self._nbytes = 0
         self._segments = None
         if self.lib.zmx_ctx_create(device, ctypes.byref(self.handle)) != 0:
             raise RuntimeError("zmx_ctx_create: " + self.error())
@@ -267,8 +317,32 @@ class Context:
 
     def set_input(self, data):
         self._input = data
+        self._nbytes = len(data)
         self._segments = None
         self._check(self.lib.zmx_set_input(self.handle, data, len(data)), "zmx_set_input")
+
+    def set_input_device(self, ptr, nbytes):
+        """zmx_set_input_device: `nbytes` bytes of device memory at the integer pointer `ptr` become the resident
+        input (copied; the buffer may be reused when the call returns)."""
+        self._input = None
+        self._nbytes = int(nbytes)
+        self._segments = None
+        fn = self.lib.zmx_set_input_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, ptr, nbytes), "zmx_set_input_device")
+
+    def master_block_costs_device(self):
+        """zmx_master_block_costs_device: the dealing costs of the resident input's master blocks, counted on the device."""
+        import numpy as np
+        cost = np.zeros(max(1, (self._nbytes + 999999) // 1000000), dtype=np.float64)
+        fn = self.lib.zmx_master_block_costs_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_size_t]
+        fn.restype = ctypes.c_int
+        n = fn(self.handle, cost.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cost.size)
+        if n < 0:
+            raise RuntimeError("zmx_master_block_costs_device: " + self.error())
+        return cost[:n]
 
     def set_input_segments(self, starts):
         """zmx_set_input_segments: the resident input is the concatenation of independent inputs starting at

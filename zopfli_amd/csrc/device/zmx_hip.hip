@@ -27,8 +27,11 @@
 #include "zmx_png.h"
 #include "zmx_png_brute.h"
 #include "zmx_blockcost.h"
+#define ZMX_PROBE_KERNELS
+#include "zmx_probe.h"
 #include "zmx_knobs.h"
 #include "zopfli_amd.h"
+#include "../host/deal.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
 
@@ -118,7 +121,7 @@ struct zmx_ctx {
   hipStream_t stream = nullptr;
   u8* d_in = nullptr;
   size_t insize = 0, in_cap = 0;
-  const unsigned char* h_in = nullptr;  // caller's buffer (borrowed until the next zmx_set_input)
+  const unsigned char* h_in = nullptr;  // caller's buffer (borrowed until the next zmx_set_input); null: the input came from device memory (zmx_set_input_device)
   std::vector<u64> seg_starts;          // zmx_set_input_segments: first byte of each independent input (empty: one input)
   u32* d_scratch = nullptr;  // k_match2 per-lane overflow change points
   u32* d_scratch5 = nullptr; // k_match5's (it may run beside k_match2)
@@ -518,7 +521,8 @@ void zmx_ctx_destroy(zmx_ctx* c) {
   delete c;
 }
 
-int zmx_set_input(zmx_ctx* c, const unsigned char* in, size_t insize) {
+// `insize` bytes at `src` become the context's resident input: its own copy, kInputPad zero bytes behind it.
+static int CopyInput(zmx_ctx* c, const void* src, size_t insize, hipMemcpyKind kind) {
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   if (insize + kInputPad > c->in_cap) {
@@ -527,13 +531,125 @@ int zmx_set_input(zmx_ctx* c, const unsigned char* in, size_t insize) {
     c->in_cap = insize + kInputPad;
     HIPCHK(PoolAllocT(c, &c->d_in, c->in_cap, "d_in"));
   }
-  if (insize) HIPCHK(hipMemcpyAsync(c->d_in, in, insize, hipMemcpyHostToDevice, c->stream));
+  if (insize) HIPCHK(hipMemcpyAsync(c->d_in, src, insize, kind, c->stream));
   HIPCHK(hipMemsetAsync(c->d_in + insize, 0, kInputPad, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   c->insize = insize;
-  c->h_in = in;
+  c->h_in = nullptr;
   c->seg_starts.clear();
   return 0;
+}
+
+int zmx_set_input(zmx_ctx* c, const unsigned char* in, size_t insize) {
+  if (const int rc = CopyInput(c, in, insize, hipMemcpyHostToDevice)) return rc;
+  c->h_in = in;
+  return 0;
+}
+
+// [p, p + n) must be plain device memory: what the copy engines and a kernel of the pointer's device read without the
+// host's help.  Refused before any copy or launch: a null pointer, host memory (registered or not), managed memory
+// (its pages may live on the host: reading them depends on XNACK), a range that leaves its allocation.
+// *device: the HIP device the memory lies on (-1 for n = 0, where any pointer goes).
+static int CheckDevicePointer(const char* who, const void* p, size_t n, int* device) {
+  *device = -1;
+  if (n == 0) return 0;
+  const std::string w(who);
+  if (p == nullptr) return FailMsg(w + ": null pointer with a non-zero size");
+  hipPointerAttribute_t a;
+  std::memset(&a, 0, sizeof(a));
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();   // (a pointer the runtime has never seen: not an error of the device)
+    return FailMsg(w + ": the pointer is not device memory");
+  }
+  if (a.isManaged || a.type == hipMemoryTypeManaged) return FailMsg(w + ": managed memory is not taken (copy it to device memory)");
+  if (a.type != hipMemoryTypeDevice) return FailMsg(w + ": the pointer is not device memory");
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return FailMsg(w + ": the pointer's allocation is unknown");
+  }
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at = reinterpret_cast<uintptr_t>(p);
+  if (at < lo || at - lo > size || n > size - (at - lo)) return FailMsg(w + ": the range leaves its allocation");
+  *device = a.device;
+  return 0;
+}
+
+int zmx_internal_device_pointer(const char* who, const void* p, size_t n, int* device) {
+  return CheckDevicePointer(who, p, n, device);
+}
+
+int zmx_set_input_device(zmx_ctx* c, const void* d_in, size_t insize) {
+  int device = -1;
+  if (const int rc = CheckDevicePointer("zmx_set_input_device", d_in, insize, &device)) return rc;
+  // (hipMemcpyDefault: the runtime finds the source's device itself — a peer copy where it is another one)
+  return CopyInput(c, d_in, insize, hipMemcpyDefault);
+}
+
+// Bytes [begin, end) of the resident input, device to host (the bytes of a stored block when the input came from device
+// memory: the host has no copy of its own).
+int zmx_internal_input_fetch(zmx_ctx* c, size_t begin, size_t end, unsigned char* dst) {
+  if (begin > end || end > c->insize) return FailMsg("zmx_internal_input_fetch: range outside the resident input");
+  if (begin == end) return 0;
+  DeviceGuard dev_guard(c->device);
+  HIPCHK(dev_guard.err);
+  HIPCHK(hipMemcpyAsync(dst, c->d_in + begin, end - begin, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// k_probe_counts over n ranges of `bytes` — device memory of the context's device; null: the resident input —, the
+// caller having checked the ranges against it: counts[r][zamd::kProbeCounts].
+int zmx_internal_probe_counts(zmx_ctx* c, const void* bytes, size_t n, const uint64_t* ranges, uint32_t* counts) {
+  if (n == 0) return 0;
+  if (n > 65535) return FailMsg("zmx_internal_probe_counts: too many ranges for one launch");
+  u64 longest = 0;
+  for (size_t r = 0; r < n; ++r) {
+    if (bytes == nullptr && (ranges[2 * r] > ranges[2 * r + 1] || ranges[2 * r + 1] > c->insize)) {
+      return FailMsg("zmx_internal_probe_counts: range outside the resident input");
+    }
+    longest = std::max<u64>(longest, zamd::ProbeCount(ranges[2 * r], ranges[2 * r + 1]));
+  }
+  std::memset(counts, 0, n * zamd::kProbeCounts * sizeof(uint32_t));
+  if (longest == 0) return 0;
+  DeviceGuard dev_guard(c->device);
+  HIPCHK(dev_guard.err);
+  PoolScope tmp(c);
+  uint64_t* d_ranges = nullptr;
+  uint32_t* d_counts = nullptr;
+  HIPCHK(tmp.AllocT(&d_ranges, 2 * n, "d_ranges"));
+  HIPCHK(tmp.AllocT(&d_counts, n * zamd::kProbeCounts, "d_counts"));
+  HIPCHK(hipMemcpyAsync(d_ranges, ranges, 2 * n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(d_counts, 0, n * zamd::kProbeCounts * sizeof(uint32_t), c->stream));
+  ProbeParams P;
+  P.in = bytes ? static_cast<const unsigned char*>(bytes) : c->d_in;
+  P.ranges = d_ranges;
+  P.counts = d_counts;
+  const unsigned gx = static_cast<unsigned>(std::min<u64>((longest + 255) / 256, 64));
+  hipLaunchKernelGGL(k_probe_counts, dim3(gx, static_cast<unsigned>(n)), dim3(256), 0, c->stream, P);
+  KCHK(c, "k_probe_counts");
+  HIPCHK(hipMemcpyAsync(counts, d_counts, n * zamd::kProbeCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int zmx_master_block_costs_device(zmx_ctx* c, double* cost, size_t ncost) {
+  const size_t kMb = 1000000;   // ZOPFLI_MASTER_BLOCK_SIZE, util.h:60
+  const size_t n = c->insize == 0 ? 1 : (c->insize + kMb - 1) / kMb;
+  if (ncost < n) return -1;
+  if (n > 65535) return FailMsg("zmx_master_block_costs_device: more than 65535 master blocks");
+  std::vector<uint64_t> ranges(2 * n);
+  for (size_t b = 0; b < n; ++b) {
+    ranges[2 * b] = b * kMb;
+    ranges[2 * b + 1] = std::min(c->insize, (b + 1) * kMb);
+  }
+  std::vector<uint32_t> counts(n * zamd::kProbeCounts);
+  if (const int rc = zmx_internal_probe_counts(c, nullptr, n, ranges.data(), counts.data())) return rc;
+  for (size_t b = 0; b < n; ++b) {
+    const uint32_t* k = &counts[b * zamd::kProbeCounts];
+    cost[b] = zamd::CostFromCounts(ranges[2 * b + 1] - ranges[2 * b], k[zamd::kProbes], k[zamd::kRuns], k[zamd::kFew]);
+  }
+  return static_cast<int>(n);
 }
 
 // The resident input is the concatenation of independent inputs: a block's window stops at the first byte of its own
@@ -677,12 +793,13 @@ struct ReusePlan {
   std::vector<u64> link_lo;       // per block: first links[] index the recomputed tiles read (its L: none)
   std::vector<u32> tile_list;     // the tiles whose records are computed again
 };
-static ReusePlan PlanReuse(const zmx_ctx* c, const zmx_tables* t, const zmx_tables* parent) {
+// `tail_r` (an input that came from device memory): every block's zamd::TailRunStart, from k_tail_runs.
+static ReusePlan PlanReuse(const zmx_ctx* c, const zmx_tables* t, const zmx_tables* parent, const std::vector<uint64_t>& tail_r) {
   const size_t nb = t->nb;
   const u64 pos_off = t->total_b;
   const std::vector<u32>& tile_off = t->tile_off;
   ReusePlan plan;
-  bool reuse = parent != nullptr && parent->nb > 0 && c->h_in != nullptr && parent->d_recs != nullptr &&
+  bool reuse = parent != nullptr && parent->nb > 0 && (c->h_in != nullptr || tail_r.size() == nb) && parent->d_recs != nullptr &&
                parent->total_b + pos_off < (3ull << 30);
   if (reuse) {
     plan.src_pos.resize(nb);
@@ -702,9 +819,7 @@ static ReusePlan PlanReuse(const zmx_ctx* c, const zmx_tables* t, const zmx_tabl
       if (B == 0 || d.inend == pd.inend) continue;   // same end: every record is the same
       // first position whose record may differ
       u64 t0 = B > ZMX_MAX_MATCH ? d.inend - ZMX_MAX_MATCH : d.instart;
-      const unsigned char lastb = c->h_in[d.inend - 1];
-      u64 r = d.inend - 1;
-      while (r > d.instart && d.inend - r < 65600 && c->h_in[r - 1] == lastb) --r;
+      const u64 r = c->h_in ? zamd::TailRunStart(c->h_in, d.instart, d.inend) : tail_r[b];
       if (r < t0) t0 = r;
       const u32 tile_first = static_cast<u32>((t0 - d.instart) / MT);
       for (u32 tile = tile_first; tile < tile_off[b + 1] - tile_off[b]; ++tile) {
@@ -717,6 +832,32 @@ static ReusePlan PlanReuse(const zmx_ctx* c, const zmx_tables* t, const zmx_tabl
   }
   plan.reuse = reuse;
   return plan;
+}
+
+// Phase 2, for an input the host holds no copy of: where every block's tail run begins (k_tail_runs), a u64 a block.
+static int TailRuns(zmx_ctx* c, const zmx_tables* t, std::vector<uint64_t>* r) {
+  const size_t nb = t->nb;
+  std::vector<uint64_t> blocks(2 * nb);
+  for (size_t b = 0; b < nb; ++b) {
+    blocks[2 * b] = t->blocks[b].instart;      // (LayoutBlocks has checked them against the resident input)
+    blocks[2 * b + 1] = t->blocks[b].inend;
+  }
+  PoolScope tmp(c);
+  uint64_t* d_blocks = nullptr;
+  uint64_t* d_r = nullptr;
+  HIPCHK(tmp.AllocT(&d_blocks, 2 * nb, "d_blocks"));
+  HIPCHK(tmp.AllocT(&d_r, nb, "d_r"));
+  HIPCHK(hipMemcpyAsync(d_blocks, blocks.data(), 2 * nb * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  TailRunParams P;
+  P.in = c->d_in;
+  P.blocks = d_blocks;
+  P.r = d_r;
+  hipLaunchKernelGGL(k_tail_runs, dim3(static_cast<unsigned>(nb)), dim3(64), 0, c->stream, P);
+  KCHK(c, "k_tail_runs");
+  r->resize(nb);
+  HIPCHK(hipMemcpyAsync(r->data(), d_r, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // Phase 3: the table set's arrays and the mirrors of a squeeze run's input and output.
@@ -1400,7 +1541,11 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
   u64 la_off = 0, max_l = 0;
   if (const int rc = LayoutBlocks(c, blocks, nb, t, &la_off, &max_l)) return rc;
   if (nb == 0) return 0;
-  const ReusePlan plan = PlanReuse(c, t, parent);
+  std::vector<uint64_t> tail_r;
+  if (parent != nullptr && c->h_in == nullptr) {
+    if (const int rc = TailRuns(c, t, &tail_r)) return rc;
+  }
+  const ReusePlan plan = PlanReuse(c, t, parent, tail_r);
   if (const int rc = AllocTableArrays(c, t, la_off)) return rc;
   MatchBuild m(c);
   if (const int rc = BuildHashLinks(c, t, mk, max_l, plan, m)) return rc;

@@ -39,6 +39,9 @@ extern "C" size_t zmx_internal_input_size(zmx_ctx* ctx);
 // implemented by the device layer: the caller's host copy of the resident input (borrowed)
 extern "C" const unsigned char* zmx_internal_input_host(zmx_ctx* ctx);
 extern "C" void zmx_internal_set_error(const char* msg);
+// implemented by the device layer alone: bytes [begin, end) of the resident input, device to host.  (Weak: the host test
+// library's stand-in for the device layer keeps every input on the host and has no such function.)
+extern "C" __attribute__((weak)) int zmx_internal_input_fetch(zmx_ctx* ctx, size_t begin, size_t end, unsigned char* dst);
 
 namespace zamd {
 
@@ -85,6 +88,26 @@ using zamd::Pool;
 bool TraceCall() { return zamd::HostSwitches().trace_call; }
 double WallMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// zmx_last_input_traffic: the input bytes of the calling thread's last call that went host to device, device to device,
+// device to host (a call's shard threads hand theirs to the caller's at the join)
+thread_local double g_traffic[3] = {0, 0, 0};
+
+// The stored chunks of an input the host holds no copy of (zmx_set_input_device) take their bytes from the context
+// they were computed on, each its own range only; positions relative to the context's input.
+int FetchStoredBytes(zmx_ctx* ctx, std::vector<zamd::Chunk>* chunks, double* fetched) {
+  for (zamd::Chunk& c : *chunks) {
+    if (c.kind != zamd::Chunk::kStored || c.end == c.start) continue;
+    if (!zmx_internal_input_fetch) {
+      zmx_internal_set_error("stored block of a device input: this build cannot fetch its bytes");
+      return -1;
+    }
+    c.raw.resize(c.end - c.start);
+    if (zmx_internal_input_fetch(ctx, c.start, c.end, c.raw.data()) != 0) return -1;
+    *fetched += static_cast<double>(c.end - c.start);
+  }
+  return 0;
 }
 
 std::vector<zamd::Part> MasterBlocks(size_t insize, bool final) {
@@ -141,11 +164,7 @@ int RunParts(zmx_ctx* ctx, const ZopfliOptions& options, int btype, const std::v
 //
 // `sum` (optional): the container's checksum over in[0, sum->limit), taken on the devices from the bytes
 // they hold anyway — each device its own parts' bytes, put together in stream order.
-struct ChecksumRequest {
-  int kind;         // ZMX_CRC32 / ZMX_ADLER32
-  size_t limit;     // bytes covered (the parts must start at 0 and cover them)
-  uint32_t value;
-};
+using zamd::ChecksumRequest;   // (dealing.h)
 
 struct Shard {
   size_t first = 0, last = 0, base = 0;
@@ -159,6 +178,7 @@ struct Shard {
   size_t sum_bytes = 0;
   bool redone = false;
   double stats[19] = {0};        // the shard thread's kernel / match / task statistics (zmx_internal_stats_take)
+  double traffic[3] = {0, 0, 0}; // its input bytes, as g_traffic (all attempts)
 };
 
 // The contexts of ONE device take their bytes over the same link: asked for at once, three uploads end together and
@@ -193,6 +213,7 @@ struct ShardedCall {
   const ZopfliOptions& options;
   int btype;
   const unsigned char* in;
+  zamd::DeviceInput* dev;         // the input lies in device memory (`in` is null then)
   const std::vector<zamd::Part>& parts;
   ChecksumRequest* sum;
   bool want_part_chunks;
@@ -220,13 +241,14 @@ struct ShardedCall {
 // SIMDs, the others fill what it leaves — class Z 131 -> 190 MB/s, class M 165 -> 245 (189 / 245 on four, 187 / 250 on
 // six contexts; without the priorities 112 / 170; profiles/r05_runs_ctx.txt).  Which data: zamd::LooksLikeRuns.
 // (ZOPFLI_AMD_SPLIT_RUNS=0 or ZOPFLI_AMD_STREAM_PRIO=0: such data on one context, as before — for measuring)
-size_t ContextsPerDevice(const ZopfliOptions& options, int btype, const unsigned char* in,
+size_t ContextsPerDevice(const ZopfliOptions& options, int btype, const unsigned char* in, const zamd::DeviceInput* dev,
                          const std::vector<zamd::Part>& parts, bool* runs) {
   const zamd::HostKnobs& k = zamd::HostSwitches();
   const size_t split_from = k.split_mb >= 0 ? static_cast<size_t>(k.split_mb) : (options.blocksplitting && btype == 2 ? 4 : 16);
   *runs = false;
   if (!split_from || parts.size() < split_from) return 1;
-  *runs = in != nullptr && zamd::LooksLikeRuns(in, parts.front().instart, parts.back().inend);
+  *runs = dev ? dev->Runs(parts.front().instart)
+              : in != nullptr && zamd::LooksLikeRuns(in, parts.front().instart, parts.back().inend);
   const bool one_context = *runs && !(k.stream_prio && k.split_runs);
   return one_context ? 1 : k.split_ways;
 }
@@ -241,9 +263,14 @@ void PlanShards(ShardedCall* call, const std::vector<int>& device_of, bool runs)
   // bytes alone — the one-process-per-GPU launchers compute the same ranges (zmx_master_block_costs).
   // (ZOPFLI_AMD_DEAL=count: equal counts, as before — for measuring)
   std::vector<double> cost;
-  if (k.deal_by_cost && ndev > 1 && call->in != nullptr && parts.size() > ndev) {
+  const bool have_costs = call->dev ? !call->dev->cost.empty() : call->in != nullptr;
+  if (k.deal_by_cost && ndev > 1 && have_costs && parts.size() > ndev) {
     cost.resize(parts.size());
-    zamd::ParallelFor(parts.size(), [&](size_t i) { cost[i] = zamd::MasterBlockCost(call->in, parts[i].instart, parts[i].inend); });
+    if (call->dev) {
+      for (size_t i = 0; i < parts.size(); ++i) cost[i] = call->dev->cost[parts[i].instart / kMasterBlock];
+    } else {
+      zamd::ParallelFor(parts.size(), [&](size_t i) { cost[i] = zamd::MasterBlockCost(call->in, parts[i].instart, parts[i].inend); });
+    }
   }
   const std::vector<size_t> first = zamd::ShardRanges(parts.size(), ndev, cost.empty() ? nullptr : cost.data(), k.shard_weights);
   call->shards = std::vector<Shard>(ndev);
@@ -309,7 +336,8 @@ void RunShard(ShardedCall* call, size_t d, zmx_ctx* ctx, bool retry) {
   const double tr0 = WallMs();
   if (!retry) turn.Wait();
   const double tr1 = WallMs();
-  const int up = zmx_set_input(ctx, call->in + sh.base, end - sh.base);
+  const int up = call->dev ? call->dev->upload(ctx, sh.base, end - sh.base) : zmx_set_input(ctx, call->in + sh.base, end - sh.base);
+  sh.traffic[call->dev ? 1 : 0] += static_cast<double>(end - sh.base);
   turn.Release();
   const double tr2 = WallMs();
   if (up != 0 || (hooks && hooks->uploaded(d, ctx, sh.base, sh.first, sh.last) != 0)) return fail();
@@ -327,6 +355,7 @@ void RunShard(ShardedCall* call, size_t d, zmx_ctx* ctx, bool retry) {
   } split_on_device(hooks && hooks->split_on_device);
   sh.rc = RunParts(ctx, call->options, call->btype, mine, &sh.chunks, call->want_part_chunks ? &sh.part_chunks : nullptr,
                    hooks ? hooks->group_bytes : 0);
+  if (!sh.rc && call->dev && FetchStoredBytes(ctx, &sh.chunks, &sh.traffic[2]) != 0) sh.rc = -1;
   if (sh.rc) { sh.err = zmx_last_error(); sh.err_class = zmx_last_error_class(); }
   if (TraceCall()) {
     std::fprintf(stderr, "  shard %zu (%zu parts): start +%.2f ms, wait for turn %.2f, upload %.2f, checksum %.2f, parts %.2f, end +%.2f\n",
@@ -382,6 +411,7 @@ int CollectShards(ShardedCall* call, std::vector<zamd::Chunk>* chunks, std::vect
     if (sh.rc) {
       std::fprintf(stderr, "zopfli_amd: device error: %s\n", sh.err.c_str());
       if (call->hooks) { call->hooks->error = sh.err; call->hooks->error_class = sh.err_class; }
+      if (call->dev) { call->dev->error = sh.err; call->dev->error_class = sh.err_class; }
       return sh.rc;
     }
     for (auto& c : sh.chunks) chunks->push_back(std::move(c));
@@ -406,18 +436,19 @@ struct InlineHostWork {
 int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned char* in,
                         const std::vector<zamd::Part>& parts, std::vector<zamd::Chunk>* chunks,
                         ChecksumRequest* sum = nullptr, std::vector<size_t>* part_chunks = nullptr,
-                        zamd::ShardHooks* hooks = nullptr) {
+                        zamd::ShardHooks* hooks = nullptr, zamd::DeviceInput* dev = nullptr) {
   bool runs = false;
-  const size_t per_device = ContextsPerDevice(options, btype, in, parts, &runs);
+  const size_t per_device = ContextsPerDevice(options, btype, in, dev, parts, &runs);
   const double tr_begin = WallMs();
   const Lease lease(parts.size(), per_device, /*polite=*/parts.size() < 32, /*small=*/parts.size() < 32);
   const double tr_lease = WallMs();
   const InlineHostWork inline_host(parts.size() <= 2 && Pool().InFlight() > 1);
   const size_t ndev = std::min(lease.ctxs.size(), parts.size());
-  ShardedCall call{options, btype, in, parts, sum, part_chunks != nullptr, hooks, tr_begin, {}, {}, {}};
+  ShardedCall call{options, btype, in, dev, parts, sum, part_chunks != nullptr, hooks, tr_begin, {}, {}, {}};
   PlanShards(&call, std::vector<int>(lease.device_of.begin(), lease.device_of.begin() + static_cast<long>(ndev)), runs);
   RunShards(&call, lease.ctxs);
   RetryFailedShards(&call, lease.ctxs);
+  for (const Shard& sh : call.shards) for (int i = 0; i < 3; ++i) g_traffic[i] += sh.traffic[i];
   const double tr_joined = WallMs();
   const int rc = CollectShards(&call, chunks, part_chunks);
   if (rc) return rc;
@@ -441,15 +472,15 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
 // and the container checksum of the rounds is put together like that of the shards (zmx_checksum_combine).
 int RunPartsSharded(const ZopfliOptions& options, int btype, const unsigned char* in,
                     const std::vector<zamd::Part>& parts, std::vector<zamd::Chunk>* chunks,
-                    ChecksumRequest* sum = nullptr) {
+                    ChecksumRequest* sum = nullptr, zamd::DeviceInput* dev = nullptr) {
   const size_t round_parts = zamd::HostSwitches().round_parts;
-  if (parts.size() <= round_parts) return RunPartsShardedOnce(options, btype, in, parts, chunks, sum);
+  if (parts.size() <= round_parts) return RunPartsShardedOnce(options, btype, in, parts, chunks, sum, nullptr, nullptr, dev);
   uint32_t acc = sum ? (sum->kind == ZMX_ADLER32 ? 1u : 0u) : 0u;   // of no bytes
   for (size_t a = 0; a < parts.size(); a += round_parts) {
     const size_t b = std::min(parts.size(), a + round_parts);
     const std::vector<zamd::Part> round(parts.begin() + static_cast<long>(a), parts.begin() + static_cast<long>(b));
     ChecksumRequest rs{sum ? sum->kind : 0, sum ? sum->limit : 0, 0};
-    const int rc = RunPartsShardedOnce(options, btype, in, round, chunks, sum ? &rs : nullptr);
+    const int rc = RunPartsShardedOnce(options, btype, in, round, chunks, sum ? &rs : nullptr, nullptr, nullptr, dev);
     if (rc) return rc;
     if (sum && round.front().instart < sum->limit) {
       const size_t covered = std::min(round.back().inend, sum->limit) - round.front().instart;
@@ -473,6 +504,7 @@ void ResetTiming() {
   zmx_internal_seg_stats(a, 1);
   zmx_internal_match_stats(a, 1);
   zmx_internal_match5_stats(a, 1);
+  g_traffic[0] = g_traffic[1] = g_traffic[2] = 0;
 }
 
 void PushByte(unsigned v, unsigned char** out, size_t* outsize) {
@@ -522,19 +554,31 @@ void ZopfliDeflatePart(const ZopfliOptions* options, int btype, int final, const
   EmitChunks(chunks, in, bp, out, outsize, options->verbose != 0);
 }
 
+}  // extern "C"
+
 namespace {
-// ZopfliDeflate (deflate.c:908-931); `sum`: see RunPartsSharded
-void DeflateWhole(const ZopfliOptions* options, int btype, int final, const unsigned char* in, size_t insize,
-                  unsigned char* bp, unsigned char** out, size_t* outsize, ChecksumRequest* sum) {
-  const size_t offset = *outsize;
+// The input of a whole-stream call: host bytes, or device memory (`in` is null then).
+struct Input {
+  const unsigned char* in;
+  zamd::DeviceInput* dev;
+};
+
+// ZopfliDeflate (deflate.c:908-931); `sum`: see RunPartsSharded; `prefix`: the container's header, appended once the
+// parts are done — a call that fails (non-zero, zmx_last_error) leaves *out and *outsize as they were
+int DeflateWhole(const ZopfliOptions* options, int btype, int final, const Input& input, size_t insize,
+                 const unsigned char* prefix, size_t nprefix, unsigned char* bp, unsigned char** out, size_t* outsize,
+                 ChecksumRequest* sum) {
+  const unsigned char* in = input.in;
+  const size_t offset = *outsize + nprefix;
   {
     const double tr0 = WallMs();
     ResetTiming();
     const std::vector<zamd::Part> parts = MasterBlocks(insize, final != 0);
     std::vector<zamd::Chunk> chunks;
     const double tr1 = WallMs();
-    if (RunPartsSharded(*options, btype, in, parts, &chunks, sum) != 0) Die("device error");
+    if (const int rc = RunPartsSharded(*options, btype, in, parts, &chunks, sum, input.dev)) return rc;
     const double tr2 = WallMs();
+    if (nprefix) zamd::AppendToOutput(prefix, nprefix, out, outsize);
     EmitChunks(chunks, in, bp, out, outsize, options->verbose != 0);
     const double tr3 = WallMs();
     chunks.clear();
@@ -549,22 +593,15 @@ void DeflateWhole(const ZopfliOptions* options, int btype, int final, const unsi
                  static_cast<unsigned long>(insize), static_cast<unsigned long>(*outsize - offset),
                  100.0 * static_cast<double>(insize - (*outsize - offset)) / static_cast<double>(insize));
   }
-}
-}  // namespace
-
-void ZopfliDeflate(const ZopfliOptions* options, int btype, int final, const unsigned char* in,
-                   size_t insize, unsigned char* bp, unsigned char** out, size_t* outsize) {
-  DeflateWhole(options, btype, final, in, insize, bp, out, outsize, nullptr);
+  return 0;
 }
 
-void ZopfliGzipCompress(const ZopfliOptions* options, const unsigned char* in, size_t insize,
-                        unsigned char** out, size_t* outsize) {
+int GzipFrom(const ZopfliOptions* options, const Input& input, size_t insize, unsigned char** out, size_t* outsize) {
   // the CRC is taken on the device(s) from the resident input (zmx_checksum)
   ChecksumRequest sum{ZMX_CRC32, insize, 0};
   unsigned char bp = 0;
   static const unsigned char header[10] = {31, 139, 8, 0, 0, 0, 0, 0, 2, 3};  // gzip_container.c:90-101
-  zamd::AppendToOutput(header, 10, out, outsize);
-  DeflateWhole(options, 2, 1, in, insize, &bp, out, outsize, &sum);
+  if (const int rc = DeflateWhole(options, 2, 1, input, insize, header, 10, &bp, out, outsize, &sum)) return rc;
   const uint32_t crc = sum.value;
   for (int i = 0; i < 4; ++i) PushByte((crc >> (8 * i)) & 255, out, outsize);
   for (int i = 0; i < 4; ++i) PushByte((insize >> (8 * i)) & 255, out, outsize);
@@ -572,25 +609,54 @@ void ZopfliGzipCompress(const ZopfliOptions* options, const unsigned char* in, s
     std::fprintf(stderr, "Original Size: %d, Gzip: %d, Compression: %f%% Removed\n", static_cast<int>(insize),
                  static_cast<int>(*outsize), 100.0 * static_cast<double>(insize - *outsize) / static_cast<double>(insize));
   }
+  return 0;
 }
 
-void ZopfliZlibCompress(const ZopfliOptions* options, const unsigned char* in, size_t insize,
-                        unsigned char** out, size_t* outsize) {
+int ZlibFrom(const ZopfliOptions* options, const Input& input, size_t insize, unsigned char** out, size_t* outsize) {
   // the reference truncates the size to unsigned here (zlib_container.c:54)
   ChecksumRequest sum{ZMX_ADLER32, static_cast<unsigned>(insize), 0};
   unsigned char bp = 0;
   const unsigned cmf = 120, flevel = 3, fdict = 0;  // CM 8, CINFO 7
   unsigned cmfflg = 256 * cmf + fdict * 32 + flevel * 64;
   cmfflg += 31 - cmfflg % 31;
-  PushByte(cmfflg / 256, out, outsize);
-  PushByte(cmfflg % 256, out, outsize);
-  DeflateWhole(options, 2, 1, in, insize, &bp, out, outsize, &sum);
+  const unsigned char header[2] = {static_cast<unsigned char>(cmfflg / 256), static_cast<unsigned char>(cmfflg % 256)};
+  if (const int rc = DeflateWhole(options, 2, 1, input, insize, header, 2, &bp, out, outsize, &sum)) return rc;
   const uint32_t checksum = sum.value;
   for (int i = 3; i >= 0; --i) PushByte((checksum >> (8 * i)) & 255, out, outsize);
   if (options->verbose) {
     std::fprintf(stderr, "Original Size: %d, Zlib: %d, Compression: %f%% Removed\n", static_cast<int>(insize),
                  static_cast<int>(*outsize), 100.0 * static_cast<double>(insize - *outsize) / static_cast<double>(insize));
   }
+  return 0;
+}
+}  // namespace
+
+namespace zamd {
+int CompressFromDevice(const ZopfliOptions* options, ZopfliFormat output_type, DeviceInput* dev, size_t insize,
+                       unsigned char** out, size_t* outsize) {
+  const Input input{nullptr, dev};
+  if (output_type == ZOPFLI_FORMAT_GZIP) return GzipFrom(options, input, insize, out, outsize);
+  if (output_type == ZOPFLI_FORMAT_ZLIB) return ZlibFrom(options, input, insize, out, outsize);
+  unsigned char bp = 0;
+  return DeflateWhole(options, 2, 1, input, insize, nullptr, 0, &bp, out, outsize, nullptr);
+}
+}  // namespace zamd
+
+extern "C" {
+
+void ZopfliDeflate(const ZopfliOptions* options, int btype, int final, const unsigned char* in,
+                   size_t insize, unsigned char* bp, unsigned char** out, size_t* outsize) {
+  if (DeflateWhole(options, btype, final, Input{in, nullptr}, insize, nullptr, 0, bp, out, outsize, nullptr) != 0) Die("device error");
+}
+
+void ZopfliGzipCompress(const ZopfliOptions* options, const unsigned char* in, size_t insize,
+                        unsigned char** out, size_t* outsize) {
+  if (GzipFrom(options, Input{in, nullptr}, insize, out, outsize) != 0) Die("device error");
+}
+
+void ZopfliZlibCompress(const ZopfliOptions* options, const unsigned char* in, size_t insize,
+                        unsigned char** out, size_t* outsize) {
+  if (ZlibFrom(options, Input{in, nullptr}, insize, out, outsize) != 0) Die("device error");
 }
 
 void ZopfliCompress(const ZopfliOptions* options, ZopfliFormat output_type, const unsigned char* in,
@@ -629,7 +695,10 @@ int zmx_deflate_range(zmx_ctx* ctx, const ZopfliOptions* options, size_t instart
   const auto ts0 = std::chrono::steady_clock::now();
   if (zamd::HostSwitches().prof)
     std::fprintf(stderr, "zmx_deflate_range: RunParts %.1f ms\n", std::chrono::duration<double>(ts0 - tr0).count() * 1e3);
-  *blob = zamd::SerializeChunks(chunks, zmx_internal_input_host(ctx), blobsize);
+  const unsigned char* host = zmx_internal_input_host(ctx);
+  // (an input set from device memory: the host has no copy, the stored blocks bring their bytes)
+  if (!host && FetchStoredBytes(ctx, &chunks, &g_traffic[2]) != 0) return -1;
+  *blob = zamd::SerializeChunks(chunks, host, blobsize);
   if (!*blob) return -1;
   zamd::ThreadTiming().serialize += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count();
   return 0;
@@ -676,6 +745,11 @@ int zmx_last_match_walk(double* out3) {
 
 int zmx_last_seg_stats(double* out8) {
   zmx_internal_seg_stats(out8, 0);
+  return 0;
+}
+
+int zmx_last_input_traffic(double* out3) {
+  for (int i = 0; i < 3; ++i) out3[i] = g_traffic[i];
   return 0;
 }
 

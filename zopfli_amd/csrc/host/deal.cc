@@ -14,6 +14,16 @@ namespace zamd {
 static constexpr double kRunWeight = 3.6;      // added per byte that lies in a run of 64+ equal bytes
 static constexpr double kFewWeight = 1.3;      // added per byte in a stretch of at most 4 distinct byte values (not a run)
 
+double CostFromCounts(size_t bytes, size_t probes, size_t runs, size_t few) {
+  if (bytes == 0) return 0.0;
+  const double n = static_cast<double>(bytes) / 1e6;
+  if (probes == 0) return n;
+  return n * (1.0 + kRunWeight * static_cast<double>(runs) / static_cast<double>(probes) +
+              kFewWeight * static_cast<double>(few) / static_cast<double>(probes));
+}
+
+bool RunsFromCounts(size_t probes, size_t hits) { return probes > 0 && hits * 100 >= probes; }
+
 double MasterBlockCost(const unsigned char* in, size_t begin, size_t end) {
   if (end <= begin) return 0.0;
   size_t probes = 0, runs = 0, few = 0;
@@ -31,10 +41,7 @@ double MasterBlockCost(const unsigned char* in, size_t begin, size_t end) {
     }
     if (distinct <= 4) ++few;
   }
-  const double n = static_cast<double>(end - begin) / 1e6;
-  if (probes == 0) return n;
-  return n * (1.0 + kRunWeight * static_cast<double>(runs) / static_cast<double>(probes) +
-              kFewWeight * static_cast<double>(few) / static_cast<double>(probes));
+  return CostFromCounts(end - begin, probes, runs, few);
 }
 
 void DealByCost(const std::vector<double>& cost, size_t shards, std::vector<size_t>* first) {
@@ -76,7 +83,7 @@ bool LooksLikeRuns(const unsigned char* in, size_t lo, size_t hi) {
     while (k < 64 && in[i + k] == c0) ++k;
     hits += k == 64;
   }
-  return probes > 0 && hits * 100 >= probes;
+  return RunsFromCounts(probes, hits);
 }
 
 std::vector<size_t> ShardRanges(size_t nparts, size_t ndev, const double* cost, const std::vector<double>& weights) {

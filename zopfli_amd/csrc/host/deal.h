@@ -14,6 +14,9 @@ namespace zamd {
 // Cost of compressing in[begin, end) relative to the same number of bytes of text (1.0 per 1 000 000 bytes), from
 // probes of 64 bytes every 1024.
 double MasterBlockCost(const unsigned char* in, size_t begin, size_t end);
+// ... from its counts: `probes` probes over `bytes` bytes, of which `runs` found 64 equal bytes and `few` at most 4
+// distinct values.  MasterBlockCost ends here, and so do counts taken on the device (device/zmx_probe.h).
+double CostFromCounts(size_t bytes, size_t probes, size_t runs, size_t few);
 
 // first[s] .. first[s + 1]: the blocks of shard s — contiguous, in order, none empty while blocks >= shards, the
 // largest shard's cost as small as a prefix walk makes it.  `first` gets shards + 1 entries.
@@ -25,6 +28,8 @@ void DealByCost(const std::vector<double>& cost, size_t shards, std::vector<size
 // Data with long runs of equal bytes?  Sampled: one probe every 4096 bytes of in[lo, hi), "the next 64 bytes are equal";
 // 1 % of the probes make a call "data with runs".
 bool LooksLikeRuns(const unsigned char* in, size_t lo, size_t hi);
+// ... from its counts: `hits` of `probes` probes found 64 equal bytes
+bool RunsFromCounts(size_t probes, size_t hits);
 
 // first[s] .. first[s + 1]: the parts of shard s of `ndev` (at most `nparts`), contiguous and none empty: equal counts;
 // of equal cost (DealByCost) where `cost` — nparts entries — is given; `weights` (ZOPFLI_AMD_SHARD_WEIGHTS), when there is

@@ -4,11 +4,13 @@
 // added: the hooks below are where batch.cc tells a context about its segments and takes its checksums.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 #include <functional>
 #include <string>
 #include <vector>
 
 #include "deflate.h"
+#include "symbols.h"
 #include "zopfli_amd.h"
 
 namespace zamd {
@@ -29,6 +31,37 @@ struct ShardHooks {
   std::string error;
   int error_class = ZMX_ERR_NONE;
 };
+
+// The container's checksum over in[0, limit) of a dealt call, taken on the devices from the bytes they hold anyway —
+// each device its own parts' bytes, put together in stream order.
+struct ChecksumRequest {
+  int kind;         // ZMX_CRC32 / ZMX_ADLER32
+  size_t limit;     // bytes covered (the parts must start at 0 and cover them)
+  uint32_t value;
+};
+
+// A request whose input lies in device memory (zmx_compress_device, device_input.cc): the host holds no byte of it.
+// What the dealing reads of the bytes comes from counts taken on the device before it (k_probe_counts), so the
+// dealing is that of the same bytes on the host.
+struct DeviceInput {
+  // bytes [base, base + n) of the input become the resident input of `ctx` (zmx_set_input_device)
+  std::function<int(zmx_ctx* ctx, size_t base, size_t n)> upload;
+  std::vector<double> cost;   // MasterBlockCost of every master block (empty: one master block, nothing to deal)
+  std::vector<char> runs;     // LooksLikeRuns of every round of `round_parts` master blocks (ZOPFLI_AMD_ROUND_PARTS)
+  size_t round_parts = 1;
+  // the failure of the request, when it fails
+  std::string error;
+  int error_class = ZMX_ERR_NONE;
+  // of the round whose first part starts at `instart`
+  bool Runs(size_t instart) const {
+    const size_t round = instart / kMasterBlock / round_parts;
+    return round < runs.size() && runs[round] != 0;
+  }
+};
+// ZopfliCompress of `insize` bytes of device memory: dealt, retried and done in rounds as a host call's; non-zero on
+// failure, with dev->error / error_class set and *out, *outsize as they were
+int CompressFromDevice(const ZopfliOptions* options, ZopfliFormat output_type, DeviceInput* dev, size_t insize,
+                       unsigned char** out, size_t* outsize);
 
 // ZopfliDeflate's master blocks of an input of `insize` bytes (deflate.c:916-923): at least one, even when empty
 std::vector<Part> InputMasterBlocks(size_t insize, bool final);
