@@ -173,6 +173,16 @@ int zmx_set_input(zmx_ctx* ctx, const unsigned char* in, size_t insize);
  * range that leaves its allocation.  insize = 0 is valid with any pointer. */
 int zmx_set_input_device(zmx_ctx* ctx, const void* d_in, size_t insize);
 
+/* d_dst[0, sum nbytes) = the bytes of d_src[0], d_src[1], ... end to end.  Every source and the destination are checked as
+ * zmx_set_input_device checks its pointer (ZMX_ERR_REFUSED before any launch: null with a size, host or managed memory,
+ * a range that leaves its allocation), and so is a destination that overlaps a source or that does not lie on the
+ * context's device.  Sources on the context's device go through one kernel launch (k_gather, device/zmx_gather.h: at
+ * most 2048 workgroups whatever n and the total); sources on another device take one hipMemcpyDefault copy each.
+ * Empty pieces are allowed, with any pointer.  The resident input is not touched.  Synchronous.  (While kernel timing
+ * is on — zmx_set_kernel_timing — the call records two events around its copies, like the squeeze runs' phase times;
+ * the measuring tool reads the milliseconds through zmx_internal_gather_ms.  Off, it records none.) */
+int zmx_gather_device(zmx_ctx* ctx, size_t n, const void* const* d_src, const size_t* nbytes, void* d_dst);
+
 /* Declares the resident input (the last zmx_set_input, which resets it to one segment) to be the concatenation of nseg
  * independent inputs: segment i is bytes [starts[i], starts[i + 1]), the last one ends at the input's end; starts[0] = 0,
  * the starts never decrease and none lies past the end (empty segments are allowed).  From this call on the window of a
@@ -389,6 +399,17 @@ int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat output_type, s
 int zmx_compress_device(const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in, size_t insize,
                         unsigned char** out, size_t* outsize);
 
+/* zmx_compress_batch for inputs that lie in device memory: out[i], outsize[i] end as ZopfliCompress(options, output_type,
+ * the bytes of d_in[i] on the host, insize[i], ...) leaves them, byte for byte, whatever the other inputs, their order,
+ * their addresses (adjacent slices of one allocation are still independent inputs) and their devices.  Nothing of a
+ * compressible input visits the host; only stored blocks' bytes come down.  The inputs are put end to end on the device
+ * (zmx_gather_device into a staging buffer of the call's own, a round of at most 2 GB at a time), the dealing takes its
+ * estimates from counts made there, and the shards copy their bytes from the staging buffer.  The buffers are only read,
+ * only during the call; the caller synchronises the streams that produced them.  0 on success (n = 0 included); -1 with
+ * zmx_last_error / zmx_last_error_class and NO out[i] changed on failure, a refused pointer anywhere in the list included. */
+int zmx_compress_device_batch(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
+                              const void* const* d_in, const size_t* insize, unsigned char** out, size_t* outsize);
+
 /* -------- whole-stream entry points on a resident input (bench, multi-GPU) */
 
 /* ZopfliDeflate (deflate.c:908) of bytes [instart, inend) of the resident input,
@@ -468,7 +489,8 @@ void zmx_set_kernel_timing(int on);
 int zmx_last_host_timing(double* out2);
 
 /* Input bytes the last Zopfli* / zmx_compress_* / zmx_deflate_range call on this thread moved: [0] host to device
- * [1] device to device [2] device to host.  (A shard's upload includes the 32 KiB window before its first block.) */
+ * [1] device to device [2] device to host.  (A shard's upload includes the 32 KiB window before its first block;
+ * zmx_compress_device_batch: [1] counts the gather into the staging buffer and the shards' copies from it.) */
 int zmx_last_input_traffic(double* out3);
 
 /* Match-table builds since the last Zopfli* / zmx_deflate_range call started (HIP events):

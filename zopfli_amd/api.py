@@ -173,8 +173,9 @@ def compress_batch(datas, fmt=FORMAT_GZIP, options=None, lib=None):
     return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
 
 
-def _device_range(src, nbytes):
-    """(pointer, bytes) of an integer device pointer with `nbytes`, or of a contiguous tensor-like object."""
+def _device_range(src, nbytes, sync=True):
+    """(pointer, bytes) of an integer device pointer with `nbytes`, or of a contiguous tensor-like object (`sync`: a
+    torch tensor's current stream is synchronised)."""
     if isinstance(src, int):
         if nbytes is None:
             raise ValueError("a device pointer needs nbytes")
@@ -185,7 +186,7 @@ def _device_range(src, nbytes):
     if nbytes is not None and int(nbytes) != size:
         raise ValueError(f"nbytes = {nbytes}, but the tensor holds {size} bytes")
     # the data must be complete before the library's own streams read it
-    if type(src).__module__.split(".")[0] == "torch":
+    if sync and type(src).__module__.split(".")[0] == "torch":
         import torch
         torch.cuda.current_stream(src.device).synchronize()
     return src.data_ptr(), size
@@ -208,6 +209,49 @@ def compress_device(src, nbytes=None, fmt=FORMAT_GZIP, options=None, lib=None):
     if fn(ctypes.byref(options), fmt, ptr, size, ctypes.byref(out), ctypes.byref(outsize)) != 0:
         raise RuntimeError("zmx_compress_device: " + (lib.zmx_last_error() or b"").decode())
     return _take(out, outsize)
+
+
+def _device_ranges(srcs):
+    """(pointers, sizes) of a list of tensors or (pointer, nbytes) pairs; the current stream of every distinct torch
+    device among them is synchronised once."""
+    ptrs, sizes, devices = [], [], {}
+    for src in srcs:
+        if isinstance(src, (tuple, list)):
+            ptr, size = _device_range(int(src[0]), src[1])
+        else:
+            ptr, size = _device_range(src, None, sync=False)
+            if type(src).__module__.split(".")[0] == "torch":
+                devices[str(src.device)] = src.device
+        ptrs.append(ptr)
+        sizes.append(size)
+    if devices:
+        import torch
+        for device in devices.values():
+            torch.cuda.current_stream(device).synchronize()
+    return ptrs, sizes
+
+
+def compress_device_batch(srcs, fmt=FORMAT_GZIP, options=None, lib=None):
+    """zmx_compress_device_batch: one ZopfliCompress output per input in device memory — `srcs` is a list of tensors
+    (objects with data_ptr(), numel(), element_size() and is_contiguous(); the current stream of every torch device
+    among them is synchronised first) or of (integer device pointer, nbytes) pairs.  Raises ValueError for a
+    non-contiguous tensor, RuntimeError with the library's message when the library refuses a pointer or fails."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    ptrs, sizes = _device_ranges(srcs)
+    n = len(ptrs)
+    ins = (ctypes.c_void_p * max(n, 1))(*ptrs)
+    insizes = (ctypes.c_size_t * max(n, 1))(*sizes)
+    outs = (_u8p * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
+    fn = lib.zmx_compress_device_batch
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p),
+                   ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), fmt, n, ins, insizes, outs, outsizes) != 0:
+        raise RuntimeError("zmx_compress_device_batch: " + (lib.zmx_last_error() or b"").decode())
+    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
 
 
 def last_input_traffic(lib=None):
@@ -331,6 +375,20 @@ class Context:
         fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, ptr, nbytes), "zmx_set_input_device")
+
+    def gather_device(self, srcs, dst):
+        """zmx_gather_device: the bytes of `srcs` (tensors or (pointer, nbytes) pairs, as compress_device_batch takes
+        them) end to end at `dst`, a tensor or an integer pointer into memory of this context's device."""
+        ptrs, sizes = _device_ranges(srcs)
+        n = len(ptrs)
+        if not isinstance(dst, int):
+            dst = _device_range(dst, None)[0]
+        fn = self.lib.zmx_gather_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                       ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes), dst),
+                    "zmx_gather_device")
 
     def master_block_costs_device(self):
         """zmx_master_block_costs_device: the dealing costs of the resident input's master blocks, counted on the device."""

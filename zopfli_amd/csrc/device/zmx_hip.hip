@@ -29,6 +29,8 @@
 #include "zmx_blockcost.h"
 #define ZMX_PROBE_KERNELS
 #include "zmx_probe.h"
+#define ZMX_GATHER_KERNELS
+#include "zmx_gather.h"
 #include "zmx_knobs.h"
 #include "zopfli_amd.h"
 #include "../host/deal.h"
@@ -550,7 +552,9 @@ int zmx_set_input(zmx_ctx* c, const unsigned char* in, size_t insize) {
 // host's help.  Refused before any copy or launch: a null pointer, host memory (registered or not), managed memory
 // (its pages may live on the host: reading them depends on XNACK), a range that leaves its allocation.
 // *device: the HIP device the memory lies on (-1 for n = 0, where any pointer goes).
-static int CheckDevicePointer(const char* who, const void* p, size_t n, int* device) {
+// (alloc_lo, alloc_size: optional, the allocation the range lies in)
+static int CheckDevicePointer(const char* who, const void* p, size_t n, int* device, uintptr_t* alloc_lo = nullptr,
+                              size_t* alloc_size = nullptr) {
   *device = -1;
   if (n == 0) return 0;
   const std::string w(who);
@@ -572,11 +576,59 @@ static int CheckDevicePointer(const char* who, const void* p, size_t n, int* dev
   const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at = reinterpret_cast<uintptr_t>(p);
   if (at < lo || at - lo > size || n > size - (at - lo)) return FailMsg(w + ": the range leaves its allocation");
   *device = a.device;
+  if (alloc_lo) *alloc_lo = lo;
+  if (alloc_size) *alloc_size = size;
   return 0;
 }
 
+// CheckDevicePointer for the ranges of a list: the runtime is asked once for consecutive ranges of one allocation
+// (slices of a tensor, the tensors of one arena).
+struct DeviceRangeChecker {
+  uintptr_t lo = 0;
+  size_t size = 0;
+  int device = -1;
+  int Check(const char* who, const void* p, size_t n, int* device_out) {
+    const uintptr_t at = reinterpret_cast<uintptr_t>(p);
+    if (n != 0 && size != 0 && at >= lo && at - lo <= size && n <= size - (at - lo)) {
+      *device_out = device;
+      return 0;
+    }
+    uintptr_t l = 0;
+    size_t s = 0;
+    if (const int rc = CheckDevicePointer(who, p, n, device_out, &l, &s)) return rc;
+    if (n != 0) { lo = l; size = s; device = *device_out; }
+    return 0;
+  }
+};
+
 int zmx_internal_device_pointer(const char* who, const void* p, size_t n, int* device) {
   return CheckDevicePointer(who, p, n, device);
+}
+
+// the same for n ranges, before anything is done with any of them (zmx_compress_device_batch)
+int zmx_internal_device_pointers(const char* who, size_t n, const void* const* p, const size_t* nbytes) {
+  DeviceRangeChecker checker;
+  int device = -1;
+  for (size_t i = 0; i < n; ++i) {
+    if (const int rc = checker.Check(who, p[i], nbytes[i], &device)) return rc;
+  }
+  return 0;
+}
+
+// A plain allocation of `device` that its caller owns (the staging buffer of zmx_compress_device_batch: it outlives the
+// context it was filled on, which goes back to the pool while the shards copy from it).
+int zmx_internal_device_alloc(int device, size_t n, void** p) {
+  *p = nullptr;
+  DeviceGuard dev_guard(device);
+  HIPCHK(dev_guard.err);
+  HIPCHK(hipMalloc(p, n ? n : 1));
+  return 0;
+}
+
+void zmx_internal_device_free(int device, void* p) {
+  if (!p) return;
+  DeviceGuard dev_guard(device);
+  (void)hipFree(p);
 }
 
 int zmx_set_input_device(zmx_ctx* c, const void* d_in, size_t insize) {
@@ -630,6 +682,87 @@ int zmx_internal_probe_counts(zmx_ctx* c, const void* bytes, size_t n, const uin
   KCHK(c, "k_probe_counts");
   HIPCHK(hipMemcpyAsync(counts, d_counts, n * zamd::kProbeCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
+// (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing, as the other phase
+// times; include/zopfli_amd.h says so at zmx_gather_device); else 0.  For tools/batch_files.py --device.
+static thread_local double g_gather_ms = 0;
+__attribute__((visibility("default"))) double zmx_internal_gather_ms(void) { return g_gather_ms; }
+
+int zmx_gather_device(zmx_ctx* c, size_t n, const void* const* d_src, const size_t* nbytes, void* d_dst) {
+  g_gather_ms = 0;
+  if (n == 0) return 0;
+  if (!d_src || !nbytes) return FailMsg("zmx_gather_device: null array");
+  std::vector<uint64_t> start(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    if (nbytes[i] > SIZE_MAX - start[i]) return FailMsg("zmx_gather_device: the sizes overflow");
+    start[i + 1] = start[i] + nbytes[i];
+  }
+  const uint64_t total = start[n];
+  // ---- every range checked before anything is copied
+  int dst_device = -1;
+  if (const int rc = CheckDevicePointer("zmx_gather_device", d_dst, total, &dst_device)) return rc;
+  DeviceRangeChecker checker;
+  std::vector<const unsigned char*> src(n, nullptr);   // the kernel's pieces: those on the context's device
+  std::vector<size_t> foreign;                         // the others: a copy each
+  size_t local = 0;
+  const uintptr_t dlo = reinterpret_cast<uintptr_t>(d_dst);
+  for (size_t i = 0; i < n; ++i) {
+    int device = -1;
+    if (const int rc = checker.Check("zmx_gather_device", d_src[i], nbytes[i], &device)) return rc;
+    if (nbytes[i] == 0) continue;
+    const uintptr_t slo = reinterpret_cast<uintptr_t>(d_src[i]);
+    if (slo < dlo + total && dlo < slo + nbytes[i]) return FailMsg("zmx_gather_device: the destination overlaps a source");
+    if (device == c->device) { src[i] = static_cast<const unsigned char*>(d_src[i]); ++local; }
+    else foreign.push_back(i);
+  }
+  if (total == 0) return 0;
+  if (dst_device != c->device) return FailMsg("zmx_gather_device: the destination is not memory of the context's device");
+  DeviceGuard dev_guard(c->device);
+  HIPCHK(dev_guard.err);
+  PoolScope tmp(c);   // (the table: held until the stream is drained, on the failing paths too — below)
+  const bool timed = KernelTiming();
+  const auto enqueue = [&]() -> int {
+    if (timed && local == 0) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    if (local != 0) {
+      const unsigned char** d_ptrs = nullptr;
+      uint64_t* d_start = nullptr;
+      HIPCHK(tmp.AllocT(&d_ptrs, n, "gather_src"));
+      HIPCHK(tmp.AllocT(&d_start, n + 1, "gather_start"));
+      HIPCHK(hipMemcpyAsync(d_ptrs, src.data(), n * sizeof(src[0]), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(d_start, start.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+      zamd::GatherTable T;
+      T.src = d_ptrs;
+      T.start = d_start;
+      T.dst = static_cast<unsigned char*>(d_dst);
+      T.n = n;
+      // (the grid: tiles of the destination up to the cap, whatever n and the total)
+      const uint64_t ntiles = (total + zamd::kGatherTile - 1) / zamd::kGatherTile;
+      const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(ntiles, zamd::kGatherMaxBlocks));
+      if (timed) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+      hipLaunchKernelGGL(k_gather, dim3(grid), dim3(zamd::kGatherThreads), 0, c->stream, T, ntiles);
+      KCHK(c, "k_gather");
+    }
+    for (const size_t i : foreign) {
+      HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(d_dst) + start[i], d_src[i], nbytes[i], hipMemcpyDefault, c->stream));
+    }
+    if (timed) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    return 0;
+  };
+  if (const int rc = enqueue()) {
+    // what was queued before the failure may still read the table: drained before `tmp` gives it back (the failure's
+    // message and class stay as they are)
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    g_gather_ms = ms;
+  }
   return 0;
 }
 

@@ -247,7 +247,7 @@ size_t ContextsPerDevice(const ZopfliOptions& options, int btype, const unsigned
   const size_t split_from = k.split_mb >= 0 ? static_cast<size_t>(k.split_mb) : (options.blocksplitting && btype == 2 ? 4 : 16);
   *runs = false;
   if (!split_from || parts.size() < split_from) return 1;
-  *runs = dev ? dev->Runs(parts.front().instart)
+  *runs = dev ? dev->Runs()
               : in != nullptr && zamd::LooksLikeRuns(in, parts.front().instart, parts.back().inend);
   const bool one_context = *runs && !(k.stream_prio && k.split_runs);
   return one_context ? 1 : k.split_ways;
@@ -267,7 +267,7 @@ void PlanShards(ShardedCall* call, const std::vector<int>& device_of, bool runs)
   if (k.deal_by_cost && ndev > 1 && have_costs && parts.size() > ndev) {
     cost.resize(parts.size());
     if (call->dev) {
-      for (size_t i = 0; i < parts.size(); ++i) cost[i] = call->dev->cost[parts[i].instart / kMasterBlock];
+      for (size_t i = 0; i < parts.size(); ++i) cost[i] = call->dev->Cost(i);
     } else {
       zamd::ParallelFor(parts.size(), [&](size_t i) { cost[i] = zamd::MasterBlockCost(call->in, parts[i].instart, parts[i].inend); });
     }
@@ -474,10 +474,12 @@ int RunPartsSharded(const ZopfliOptions& options, int btype, const unsigned char
                     const std::vector<zamd::Part>& parts, std::vector<zamd::Chunk>* chunks,
                     ChecksumRequest* sum = nullptr, zamd::DeviceInput* dev = nullptr) {
   const size_t round_parts = zamd::HostSwitches().round_parts;
+  if (dev) dev->first_part = 0;
   if (parts.size() <= round_parts) return RunPartsShardedOnce(options, btype, in, parts, chunks, sum, nullptr, nullptr, dev);
   uint32_t acc = sum ? (sum->kind == ZMX_ADLER32 ? 1u : 0u) : 0u;   // of no bytes
   for (size_t a = 0; a < parts.size(); a += round_parts) {
     const size_t b = std::min(parts.size(), a + round_parts);
+    if (dev) dev->first_part = a;
     const std::vector<zamd::Part> round(parts.begin() + static_cast<long>(a), parts.begin() + static_cast<long>(b));
     ChecksumRequest rs{sum ? sum->kind : 0, sum ? sum->limit : 0, 0};
     const int rc = RunPartsShardedOnce(options, btype, in, round, chunks, sum ? &rs : nullptr, nullptr, nullptr, dev);
@@ -518,10 +520,11 @@ void PushByte(unsigned v, unsigned char** out, size_t* outsize) {
 namespace zamd {
 std::vector<Part> InputMasterBlocks(size_t insize, bool final) { return MasterBlocks(insize, final); }
 int RunPartsDealt(const ZopfliOptions& options, int btype, const unsigned char* in, const std::vector<Part>& parts,
-                  std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks, ShardHooks* hooks) {
-  return RunPartsShardedOnce(options, btype, in, parts, chunks, nullptr, part_chunks, hooks);
+                  std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks, ShardHooks* hooks, DeviceInput* dev) {
+  return RunPartsShardedOnce(options, btype, in, parts, chunks, nullptr, part_chunks, hooks, dev);
 }
 void ResetCallStats() { ResetTiming(); }
+void AddDeviceTraffic(double bytes) { g_traffic[1] += bytes; }
 bool TraceCallOn() { return TraceCall(); }
 double CallWallMs() { return WallMs(); }
 int OnPooledContext(const std::function<int(zmx_ctx*)>& fn) {

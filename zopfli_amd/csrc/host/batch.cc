@@ -16,18 +16,28 @@
 #include <string>
 #include <vector>
 
+#include "deal.h"
 #include "deflate.h"
 #include "dealing.h"
 #include "symbols.h"
 #include "thread_pool.h"
 #include "zopfli_amd.h"
+#include "../device/zmx_probe.h"
 
 extern "C" void zmx_internal_set_error_class(const char* msg, int cls);
+extern "C" int zmx_internal_device(zmx_ctx* ctx);
+// implemented by the device layer: every [p[i], p[i] + nbytes[i]) is plain device memory (else ZMX_ERR_REFUSED)
+extern "C" int zmx_internal_device_pointers(const char* who, size_t n, const void* const* p, const size_t* nbytes);
+// implemented by the device layer: k_probe_counts over n <= 65535 ranges (begin, end) of `bytes`
+extern "C" int zmx_internal_probe_counts(zmx_ctx* ctx, const void* bytes, size_t n, const uint64_t* ranges, uint32_t* counts);
+// implemented by the device layer: a plain allocation of `device` that the caller owns
+extern "C" int zmx_internal_device_alloc(int device, size_t n, void** p);
+extern "C" void zmx_internal_device_free(int device, void* p);
 
 namespace {
 
-int Refuse(const char* msg) {
-  zmx_internal_set_error_class(msg, ZMX_ERR_REFUSED);
+int Refuse(const std::string& msg) {
+  zmx_internal_set_error_class(msg.c_str(), ZMX_ERR_REFUSED);
   return -1;
 }
 
@@ -42,21 +52,90 @@ void PushByte(unsigned v, unsigned char** out, size_t* outsize) {
   zamd::AppendToOutput(&b, 1, out, outsize);
 }
 
-}  // namespace
+// Where the inputs of a batch lie: n host arrays, or n ranges of device memory.
+struct BatchBytes {
+  const unsigned char* const* host = nullptr;
+  const void* const* device = nullptr;
+};
 
-extern "C" int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
-                                  const unsigned char* const* in, const size_t* insize, unsigned char** out,
-                                  size_t* outsize) {
-  if (!options) return Refuse("zmx_compress_batch: no options");
+// The bytes [lo, lo + size) of the inputs' concatenation in device memory: a plain allocation the call owns, not the
+// context that filled it — that one is back in the pool while the shards copy from here (a call that held it would
+// starve a pool of one context).
+struct Staging {
+  int device = -1;
+  void* p = nullptr;
+  size_t lo = 0, size = 0;
+  Staging() = default;
+  Staging(const Staging&) = delete;
+  Staging& operator=(const Staging&) = delete;
+  ~Staging() { zmx_internal_device_free(device, p); }
+};
+
+// A round of a device batch, on one pooled context: the inputs' bytes [stage->lo, round's end) gathered into `stage`,
+// and the counts behind the dealing taken from them — one range per part, over that part's own bytes (PlanShards'
+// MasterBlockCost), and one over the round (ContextsPerDevice's LooksLikeRuns).
+int StageRound(const void* const* d_in, const std::vector<size_t>& start, size_t file_lo, size_t file_hi,
+               const std::vector<zamd::Part>& round, size_t lo, Staging* stage, zamd::DeviceInput* dev) {
+  const size_t hi = round.back().inend;
+  std::vector<const void*> src;
+  std::vector<size_t> len;
+  for (size_t f = file_lo; f <= file_hi; ++f) {
+    const size_t s = std::max(start[f], lo), e = std::min(start[f + 1], hi);
+    if (e <= s) continue;
+    src.push_back(static_cast<const unsigned char*>(d_in[f]) + (s - start[f]));
+    len.push_back(e - s);
+  }
+  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    stage->device = zmx_internal_device(ctx);
+    stage->lo = lo;
+    stage->size = hi - lo;
+    if (zmx_internal_device_alloc(stage->device, stage->size, &stage->p) != 0) return -1;
+    if (zmx_gather_device(ctx, src.size(), src.data(), len.data(), stage->p) != 0) return -1;
+    zamd::AddDeviceTraffic(static_cast<double>(stage->size));
+    if (round.size() < 2) return 0;   // (one part: one shard on one context, whatever its bytes)
+    const size_t nranges = round.size() + 1;
+    std::vector<uint64_t> ranges;
+    for (const zamd::Part& p : round) {
+      ranges.push_back(p.instart - lo);
+      ranges.push_back(p.inend - lo);
+    }
+    ranges.push_back(round.front().instart - lo);
+    ranges.push_back(hi - lo);
+    std::vector<uint32_t> counts(nranges * zamd::kProbeCounts);
+    constexpr size_t kSlice = 65535;   // ranges of one launch (zmx_internal_probe_counts)
+    for (size_t r = 0; r < nranges; r += kSlice) {
+      if (zmx_internal_probe_counts(ctx, stage->p, std::min(kSlice, nranges - r), &ranges[2 * r],
+                                    &counts[r * zamd::kProbeCounts]) != 0) return -1;
+    }
+    dev->cost.resize(round.size());
+    for (size_t i = 0; i < round.size(); ++i) {
+      const uint32_t* k = &counts[i * zamd::kProbeCounts];
+      dev->cost[i] = zamd::CostFromCounts(round[i].inend - round[i].instart, k[zamd::kProbes], k[zamd::kRuns], k[zamd::kFew]);
+    }
+    const uint32_t* k = &counts[round.size() * zamd::kProbeCounts];
+    dev->runs.assign(1, zamd::RunsFromCounts(k[zamd::kProbes4k], k[zamd::kHits]) ? 1 : 0);
+    dev->round_parts = round.size();
+    dev->first_part = 0;
+    return 0;
+  });
+}
+
+// The n ZopfliCompress calls of `who` (an entry point's name), the inputs lying where `bytes` says.
+int CompressBatch(const char* who, const ZopfliOptions* options, ZopfliFormat output_type, size_t n, const BatchBytes& bytes,
+                  const size_t* insize, unsigned char** out, size_t* outsize) {
+  const std::string w(who);
+  if (!options) return Refuse(w + ": no options");
   if (output_type != ZOPFLI_FORMAT_GZIP && output_type != ZOPFLI_FORMAT_ZLIB && output_type != ZOPFLI_FORMAT_DEFLATE) {
-    char msg[96];
-    std::snprintf(msg, sizeof(msg), "zmx_compress_batch: invalid ZopfliFormat %d", static_cast<int>(output_type));
-    return Refuse(msg);
+    return Refuse(w + ": invalid ZopfliFormat " + std::to_string(static_cast<int>(output_type)));
   }
   if (n == 0) return 0;
-  if (!in || !insize || !out || !outsize) return Refuse("zmx_compress_batch: null array");
-  for (size_t i = 0; i < n; ++i) {
-    if (insize[i] && !in[i]) return Refuse("zmx_compress_batch: null input with a non-zero size");
+  if ((!bytes.host && !bytes.device) || !insize || !out || !outsize) return Refuse(w + ": null array");
+  if (bytes.host) {
+    for (size_t i = 0; i < n; ++i) {
+      if (insize[i] && !bytes.host[i]) return Refuse(w + ": null input with a non-zero size");
+    }
+  } else if (zmx_internal_device_pointers(who, n, bytes.device, insize) != 0) {
+    return -1;   // (every pointer before anything is done with any: the device layer's refusal stands)
   }
   zamd::ResetCallStats();
   const double tr0 = zamd::CallWallMs();
@@ -65,8 +144,11 @@ extern "C" int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat out
   std::vector<size_t> start(n + 1, 0);
   for (size_t i = 0; i < n; ++i) start[i + 1] = start[i] + insize[i];
   const size_t total = start[n];
-  std::unique_ptr<unsigned char[]> cat(new unsigned char[total ? total : 1]);
-  zamd::ParallelFor(n, [&](size_t i) { if (insize[i]) std::memcpy(cat.get() + start[i], in[i], insize[i]); });
+  std::unique_ptr<unsigned char[]> cat;   // (device inputs: none — stored chunks carry their bytes)
+  if (bytes.host) {
+    cat.reset(new unsigned char[total ? total : 1]);
+    zamd::ParallelFor(n, [&](size_t i) { if (insize[i]) std::memcpy(cat.get() + start[i], bytes.host[i], insize[i]); });
+  }
   std::vector<zamd::Part> parts;
   std::vector<size_t> part_file, first_part(n + 1, 0);
   for (size_t i = 0; i < n; ++i) {
@@ -142,7 +224,23 @@ extern "C" int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat out
     round_parts = &round;
     round_first = a;
     shard_sums.clear();
-    const int rc = zamd::RunPartsDealt(*options, 2, cat.get(), round, &chunks, &part_chunks, &hooks);
+    Staging stage;
+    zamd::DeviceInput dev;
+    if (bytes.device) {
+      // from the floor of the window of the round's first part (RunShard's base): its input's first byte, unless the
+      // input began in a round before this one
+      const size_t first = round.front().instart;
+      const size_t lo = std::max(hooks.floor(first), first > zamd::kWindow ? first - zamd::kWindow : 0);
+      if (StageRound(bytes.device, start, part_file[a], part_file[b - 1], round, lo, &stage, &dev) != 0) return -1;
+      dev.upload = [&stage](zmx_ctx* ctx, size_t base, size_t nbytes) {
+        if (base < stage.lo || nbytes > stage.size - (base - stage.lo)) {
+          zmx_internal_set_error_class("device batch: a shard reaches outside the round's staging buffer", ZMX_ERR_REFUSED);
+          return -1;
+        }
+        return zmx_set_input_device(ctx, static_cast<const unsigned char*>(stage.p) + (base - stage.lo), nbytes);
+      };
+    }
+    const int rc = zamd::RunPartsDealt(*options, 2, cat.get(), round, &chunks, &part_chunks, &hooks, bytes.device ? &dev : nullptr);
     if (rc) {
       zmx_internal_set_error_class(hooks.error.c_str(), hooks.error_class);
       return -1;
@@ -152,7 +250,7 @@ extern "C" int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat out
     }
     a = b;
   }
-  if (part_chunks.size() != parts.size()) return Refuse("zmx_compress_batch: chunks do not match the parts");
+  if (part_chunks.size() != parts.size()) return Refuse(w + ": chunks do not match the parts");
   const double tr1 = zamd::CallWallMs();
 
   // ---- each input merged on its own at bit 0 (ZopfliGzipCompress / ZopfliZlibCompress / ZopfliDeflate)
@@ -203,8 +301,26 @@ extern "C" int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat out
     zamd::ParallelFor(n, assemble);
   }
   if (zamd::TraceCallOn()) {
-    std::fprintf(stderr, "zmx_compress_batch(%zu inputs, %zu parts, %zu bytes): parts %.2f ms, merge %.2f ms\n", n,
-                 parts.size(), total, tr1 - tr0, zamd::CallWallMs() - tr1);
+    std::fprintf(stderr, "%s(%zu inputs, %zu parts, %zu bytes): parts %.2f ms, merge %.2f ms\n", who, n, parts.size(), total,
+                 tr1 - tr0, zamd::CallWallMs() - tr1);
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int zmx_compress_batch(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
+                                  const unsigned char* const* in, const size_t* insize, unsigned char** out,
+                                  size_t* outsize) {
+  BatchBytes bytes;
+  bytes.host = in;
+  return CompressBatch("zmx_compress_batch", options, output_type, n, bytes, insize, out, outsize);
+}
+
+extern "C" int zmx_compress_device_batch(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
+                                         const void* const* d_in, const size_t* insize, unsigned char** out,
+                                         size_t* outsize) {
+  BatchBytes bytes;
+  bytes.device = d_in;
+  return CompressBatch("zmx_compress_device_batch", options, output_type, n, bytes, insize, out, outsize);
 }

@@ -40,21 +40,25 @@ struct ChecksumRequest {
   uint32_t value;
 };
 
-// A request whose input lies in device memory (zmx_compress_device, device_input.cc): the host holds no byte of it.
-// What the dealing reads of the bytes comes from counts taken on the device before it (k_probe_counts), so the
-// dealing is that of the same bytes on the host.
+// A request whose input lies in device memory (zmx_compress_device, device_input.cc; zmx_compress_device_batch,
+// batch.cc): the host holds no byte of it.  What the dealing reads of the bytes comes from counts taken on the device
+// before it (k_probe_counts), so the dealing is that of the same bytes on the host.
 struct DeviceInput {
   // bytes [base, base + n) of the input become the resident input of `ctx` (zmx_set_input_device)
   std::function<int(zmx_ctx* ctx, size_t base, size_t n)> upload;
-  std::vector<double> cost;   // MasterBlockCost of every master block (empty: one master block, nothing to deal)
-  std::vector<char> runs;     // LooksLikeRuns of every round of `round_parts` master blocks (ZOPFLI_AMD_ROUND_PARTS)
+  // By PART of the request, wherever its bytes start (the parts of a batch start where their inputs do):
+  std::vector<double> cost;   // MasterBlockCost of every part (empty: nothing to deal)
+  std::vector<char> runs;     // LooksLikeRuns of every round of `round_parts` parts (ZOPFLI_AMD_ROUND_PARTS)
   size_t round_parts = 1;
+  size_t first_part = 0;      // the part of the request that the round being dealt begins with (set by who runs the rounds)
   // the failure of the request, when it fails
   std::string error;
   int error_class = ZMX_ERR_NONE;
-  // of the round whose first part starts at `instart`
-  bool Runs(size_t instart) const {
-    const size_t round = instart / kMasterBlock / round_parts;
+  // of part i of the round being dealt
+  double Cost(size_t i) const { return cost[first_part + i]; }
+  // of the round being dealt
+  bool Runs() const {
+    const size_t round = first_part / round_parts;
     return round < runs.size() && runs[round] != 0;
   }
 };
@@ -66,11 +70,14 @@ int CompressFromDevice(const ZopfliOptions* options, ZopfliFormat output_type, D
 // ZopfliDeflate's master blocks of an input of `insize` bytes (deflate.c:916-923): at least one, even when empty
 std::vector<Part> InputMasterBlocks(size_t insize, bool final);
 // the parts of a request dealt over the pool's contexts (one round: the request's bytes plus a window stay below 2^32);
-// `part_chunks` gets the number of chunks of every part, in part order
+// `part_chunks` gets the number of chunks of every part, in part order.  `dev` (with `in` null): the bytes lie in device
+// memory, positions as for `in`; stored chunks then carry their bytes.
 int RunPartsDealt(const ZopfliOptions& options, int btype, const unsigned char* in, const std::vector<Part>& parts,
-                  std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks, ShardHooks* hooks);
+                  std::vector<Chunk>* chunks, std::vector<size_t>* part_chunks, ShardHooks* hooks, DeviceInput* dev = nullptr);
 // the per-call timing and statistics of the calling thread start again (zmx_last_timing ...)
 void ResetCallStats();
+// input bytes the calling thread's call moved device to device outside its shards (zmx_last_input_traffic [1])
+void AddDeviceTraffic(double bytes);
 // ZOPFLI_AMD_TRACE_CALL=1, and the clock of its lines
 bool TraceCallOn();
 double CallWallMs();
