@@ -17,9 +17,11 @@
 #include "block_cost.h"
 #include "block_split.h"
 #include "checksum.h"
+#include "entry_checks.h"
 #include "huffman.h"
 #include "lz77_store.h"
 #include "symbol_check.h"
+#include "zmx_internal.h"
 extern "C" {
 #include "zopfli_oracle.h"
 }
@@ -42,23 +44,26 @@ struct zmx_tables {
 };
 
 static thread_local std::string g_err;
-static thread_local std::string g_refused;   // the message of the last refusal: the error is one while g_err still holds it
+static thread_local int g_err_class = ZMX_ERR_NONE;   // what kind of failure g_err is (zmx_last_error_class)
 
-// The device layer's entry checks (CheckTables, CheckStoreRef in zmx_hip.hip), with its texts.
-static int Refuse(const char* who, const std::string& m) {
-  g_err = g_refused = std::string(who) + ": " + m;
+static int Fail(const std::string& m) {
+  zmx_internal_set_error(m.c_str(), ZMX_ERR_DEVICE);
   return -1;
 }
-static int CheckTables(const char* who, const zmx_tables* t, bool untrimmed, bool with_dp) {
-  if (!t) return Refuse(who, "no tables");
-  if ((untrimmed || with_dp) && t->trimmed) return Refuse(who, "these tables were trimmed to their stores (zmx_tables_trim)");
-  if (with_dp && t->matches_only) return Refuse(who, "these tables hold matches only (zmx_tables_build_matches)");
-  return 0;
+// The entry checks are the device layer's own (host/entry_checks.h): a message they return is a refusal.
+static int Refuse(const std::string& refusal) {
+  if (refusal.empty()) return 0;
+  zmx_internal_set_error(refusal.c_str(), ZMX_ERR_REFUSED);
+  return -1;
+}
+static int CheckTables(const char* who, const zmx_tables* t, zamd::TableNeeds needs) {
+  return Refuse(zamd::CheckTables(who, t != nullptr, t && t->trimmed, t && t->matches_only, needs));
+}
+static int CheckBlock(const char* who, const zmx_tables* t, size_t block) {
+  return Refuse(zamd::CheckBlock(who, t->blocks.size(), block));
 }
 static int CheckStoreRef(const char* who, const zmx_tables* t, size_t block, int slot, size_t nsym) {
-  if (block >= t->blocks.size() || (slot != 0 && slot != 1)) return Refuse(who, "bad block or slot");
-  if (nsym > t->blocks[block].nsym[slot]) return Refuse(who, "nsym exceeds the store");
-  return 0;
+  return Refuse(zamd::CheckStoreRef(who, t->blocks.size(), block, slot, nsym, [&] { return t->blocks[block].nsym[slot]; }));
 }
 
 extern "C" {
@@ -71,8 +76,8 @@ int zmx_device_count(void) {
 const char* zmx_last_error(void) { return g_err.c_str(); }
 int zmx_has_experiments(void) { return 0; }
 void zmx_set_kernel_timing(int) {}
-int zmx_last_error_class(void) { return g_err.empty() ? ZMX_ERR_NONE : g_err == g_refused ? ZMX_ERR_REFUSED : ZMX_ERR_DEVICE; }
-void zmx_internal_set_error(const char* msg) { g_err = msg; }
+int zmx_last_error_class(void) { return g_err_class; }
+void zmx_internal_set_error(const char* msg, int cls) { g_err = msg; g_err_class = cls; }
 
 int zmx_ctx_create(int, zmx_ctx** ctx) {
   *ctx = new zmx_ctx();
@@ -86,26 +91,24 @@ int zmx_set_input(zmx_ctx* ctx, const unsigned char* in, size_t insize) {
 }
 size_t zmx_internal_input_size(zmx_ctx* ctx) { return ctx->input.size(); }
 const unsigned char* zmx_internal_input_host(zmx_ctx* ctx) { return ctx->input.data(); }
-void zmx_internal_kernel_stats(double* a, double* b, int) { a[0] = a[1] = a[2] = 0; *b = 0; }
-void zmx_internal_seg_stats(double* a, int) { for (int i = 0; i < 8; ++i) a[i] = 0; }
-void zmx_internal_match_stats(double* a, int) { for (int i = 0; i < 4; ++i) a[i] = 0; }
-void zmx_internal_match5_stats(double* a, int) { for (int i = 0; i < 3; ++i) a[i] = 0; }
-void zmx_internal_stats_take(double* a) { for (int i = 0; i < 19; ++i) a[i] = 0; }
-void zmx_internal_stats_add(const double*) {}
-int zmx_hash_links_download(zmx_ctx*, zmx_tables*, size_t, uint16_t*, uint16_t*, uint16_t*) { g_err = "not in the host test library"; return -1; }
-int zmx_match_digest(zmx_ctx*, zmx_tables*, uint64_t*) { g_err = "not in the host test library"; return -1; }
+// (every input stays on the host: nothing to fetch.  No kernels either: nothing adds to the statistics, they read zeros.)
+int zmx_internal_input_fetch(zmx_ctx*, size_t, size_t, unsigned char*) {
+  return Fail("stored block of a device input: this build cannot fetch its bytes");
+}
+int zmx_hash_links_download(zmx_ctx*, zmx_tables*, size_t, uint16_t*, uint16_t*, uint16_t*) { return Fail("not in the host test library"); }
+int zmx_match_digest(zmx_ctx*, zmx_tables*, uint64_t*) { return Fail("not in the host test library"); }
 int zmx_set_match_kernel(int) { return 0; }   // (no kernels here)
 void zmx_set_oom_hook(zmx_oom_hook_t) {}
 int zmx_ctx_set_share(zmx_ctx*, unsigned) { return 0; }
 int zmx_ctx_trim_cache(zmx_ctx*) { return 0; }
 int zmx_ctx_set_priority(zmx_ctx*, int) { return 0; }
-int zmx_png_filter_types(zmx_ctx*, const unsigned char*, size_t, size_t, size_t, unsigned char*, unsigned char*) { g_err = "not in the host test library"; return -1; }
+int zmx_png_filter_types(zmx_ctx*, const unsigned char*, size_t, size_t, size_t, unsigned char*, unsigned char*) { return Fail("not in the host test library"); }
 // (the RCCL gather of dist.cc is not part of the host-logic test library)
-int zmx_dist_unique_id(unsigned char*) { g_err = "no RCCL in the host test library"; return -1; }
-int zmx_dist_init(zmx_ctx*, int, int, const unsigned char*, zmx_dist**) { g_err = "no RCCL in the host test library"; return -1; }
+int zmx_dist_unique_id(unsigned char*) { return Fail("no RCCL in the host test library"); }
+int zmx_dist_init(zmx_ctx*, int, int, const unsigned char*, zmx_dist**) { return Fail("no RCCL in the host test library"); }
 void zmx_dist_destroy(zmx_dist*) {}
 int zmx_dist_comm_count(zmx_dist*) { return -1; }
-int zmx_dist_gather(zmx_dist*, const unsigned char*, size_t, unsigned char**, size_t*) { g_err = "no RCCL in the host test library"; return -1; }
+int zmx_dist_gather(zmx_dist*, const unsigned char*, size_t, unsigned char**, size_t*) { return Fail("no RCCL in the host test library"); }
 
 int zmx_tables_build(zmx_ctx* ctx, const zmx_block* blocks, size_t nblocks, zmx_tables** tables) {
   zmx_tables* t = new zmx_tables();
@@ -144,7 +147,7 @@ void zmx_tables_free(zmx_ctx*, zmx_tables* t) {
 }
 
 int zmx_lz77_greedy(zmx_ctx*, zmx_tables* t, int slot, uint32_t* nsym, uint32_t* hist) {
-  if (const int rc = CheckTables("zmx_lz77_greedy", t, true, false)) return rc;
+  if (const int rc = CheckTables("zmx_lz77_greedy", t, zamd::kUntrimmed)) return rc;
   for (size_t b = 0; b < t->blocks.size(); ++b) {
     BlockData& d = t->blocks[b];
     d.nsym[slot] = zo_greedy(d.table, d.litlens[slot].data(), d.dists[slot].data());
@@ -156,7 +159,7 @@ int zmx_lz77_greedy(zmx_ctx*, zmx_tables* t, int slot, uint32_t* nsym, uint32_t*
 
 int zmx_squeeze_run(zmx_ctx*, zmx_tables* t, const double* cost, const double* mincost, const int32_t* slot,
                     uint32_t* nsym, uint32_t* hist) {
-  if (const int rc = CheckTables("zmx_squeeze_run", t, true, !(t && t->blocks.empty()))) return rc;
+  if (const int rc = CheckTables("zmx_squeeze_run", t, zamd::SqueezeRunNeeds(t ? t->blocks.size() : 0))) return rc;
   for (size_t b = 0; b < t->blocks.size(); ++b) {
     BlockData& d = t->blocks[b];
     const int s = slot[b];
@@ -174,20 +177,10 @@ int zmx_squeeze_run(zmx_ctx*, zmx_tables* t, const double* cost, const double* m
 // reports a length the record at the symbol's start does not hold (flag 4).)
 int zmx_trace_length_arrays(zmx_ctx*, zmx_tables* t, size_t nblocks, const uint16_t* const* length_arrays,
                             const size_t* entries, const int32_t* slot, uint32_t* nsym, uint32_t* hist) {
-  auto refuse = [](const std::string& m) { return Refuse("zmx_trace_length_arrays", m); };
-  if (const int rc = CheckTables("zmx_trace_length_arrays", t, true, true)) return rc;
-  if (nblocks != t->blocks.size()) return refuse("one length array per block of the tables");
-  for (size_t b = 0; b < nblocks; ++b) {
-    const size_t B = t->blocks[b].blk.inend - t->blocks[b].blk.instart;
-    if (slot[b] != 0 && slot[b] != 1) return refuse("slot must be 0 or 1");
-    if (entries[b] != B + 1) return refuse("block " + std::to_string(b) + " has " + std::to_string(B) + " + 1 cells, not " + std::to_string(entries[b]));
-    for (size_t h = 0; h <= B; ++h) {
-      const unsigned v = length_arrays[b][h];
-      if (v == 2 || v > (h < 258 ? h : 258)) {
-        return refuse("block " + std::to_string(b) + ", cell " + std::to_string(h) + " holds " + std::to_string(v) + ": no step of a path");
-      }
-    }
-  }
+  if (const int rc = CheckTables("zmx_trace_length_arrays", t, zamd::kWithDp)) return rc;
+  auto bsize = [&](size_t b) { return t->blocks[b].blk.inend - t->blocks[b].blk.instart; };
+  if (const int rc = Refuse(zamd::CheckLengthArrays("zmx_trace_length_arrays", t->blocks.size(), bsize, nblocks, length_arrays,
+                                                    entries, slot))) return rc;
   unsigned flags = 0;
   std::vector<std::vector<uint16_t>> path(nblocks);
   for (size_t b = 0; b < nblocks; ++b) {
@@ -209,8 +202,7 @@ int zmx_trace_length_arrays(zmx_ctx*, zmx_tables* t, size_t nblocks, const uint1
   if (flags) {
     char buf[96];
     std::snprintf(buf, sizeof(buf), "zmx_trace_length_arrays: device consistency flags 0x%x", flags);
-    g_err = buf;
-    return -1;
+    return Fail(buf);
   }
   for (size_t b = 0; b < nblocks; ++b) {
     BlockData& d = t->blocks[b];
@@ -224,7 +216,7 @@ int zmx_trace_length_arrays(zmx_ctx*, zmx_tables* t, size_t nblocks, const uint1
 
 int zmx_store_download(zmx_ctx*, zmx_tables* t, size_t block, int slot, uint16_t* litlens, uint16_t* dists,
                        size_t nsym) {
-  if (const int rc = CheckTables("zmx_store_download", t, false, false)) return rc;
+  if (const int rc = CheckTables("zmx_store_download", t, zamd::kAnyTables)) return rc;
   if (const int rc = CheckStoreRef("zmx_store_download", t, block, slot, nsym)) return rc;
   BlockData& d = t->blocks[block];
   std::memcpy(litlens, d.litlens[slot].data(), nsym * 2);
@@ -234,7 +226,7 @@ int zmx_store_download(zmx_ctx*, zmx_tables* t, size_t block, int slot, uint16_t
 
 int zmx_store_download_batch(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, const int32_t* slot,
                              const size_t* nsym, uint16_t* const* litlens, uint16_t* const* dists) {
-  if (const int rc = CheckTables("zmx_store_download_batch", t, false, false)) return rc;
+  if (const int rc = CheckTables("zmx_store_download_batch", t, zamd::kAnyTables)) return rc;
   for (size_t i = 0; i < n; ++i) {
     if (const int rc = CheckStoreRef("zmx_store_download_batch", t, block[i], slot[i], nsym[i])) return rc;
   }
@@ -247,7 +239,7 @@ int zmx_store_download_batch(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* 
 
 // (CPU stand-in for the device's verify pass)
 int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, const int32_t* slot, const size_t* nsym) {
-  if (const int rc = CheckTables("zmx_verify_stores", t, true, false)) return rc;
+  if (const int rc = CheckTables("zmx_verify_stores", t, zamd::kUntrimmed)) return rc;
   for (size_t i = 0; i < n; ++i) {
     if (const int rc = CheckStoreRef("zmx_verify_stores", t, block[i], slot[i], nsym[i])) return rc;
   }
@@ -257,17 +249,17 @@ int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, 
     for (size_t k = 0; k < nsym[i]; ++k) {
       const unsigned litlen = d.litlens[slot[i]][k], dist = d.dists[slot[i]][k];
       if (dist == 0) {
-        if (pos >= d.blk.inend || c->input[pos] != litlen) { g_err = "zmx_verify_stores: literal"; return -1; }
+        if (pos >= d.blk.inend || c->input[pos] != litlen) { return Fail("zmx_verify_stores: literal"); }
         pos += 1;
       } else {
-        if (litlen < 3 || litlen > 258 || dist > pos || pos + litlen > d.blk.inend) { g_err = "zmx_verify_stores: range"; return -1; }
+        if (litlen < 3 || litlen > 258 || dist > pos || pos + litlen > d.blk.inend) { return Fail("zmx_verify_stores: range"); }
         for (unsigned q = 0; q < litlen; ++q) {
-          if (c->input[pos + q] != c->input[pos + q - dist]) { g_err = "zmx_verify_stores: bytes"; return -1; }
+          if (c->input[pos + q] != c->input[pos + q - dist]) { return Fail("zmx_verify_stores: bytes"); }
         }
         pos += litlen;
       }
     }
-    if (pos != d.blk.inend) { g_err = "zmx_verify_stores: coverage"; return -1; }
+    if (pos != d.blk.inend) { return Fail("zmx_verify_stores: coverage"); }
   }
   return 0;
 }
@@ -276,8 +268,8 @@ int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, 
 // CPU suite exercises the arithmetic of host/checksum.cc the way the device feeds it)
 int zmx_checksum(zmx_ctx* c, int kind, size_t begin, size_t end, uint32_t* value) {
   using namespace zamd;
-  if (kind != ZMX_CRC32 && kind != ZMX_ADLER32) { g_err = "zmx_checksum: unknown kind"; return -1; }
-  if (begin > end || end > c->input.size()) { g_err = "zmx_checksum: range outside the resident input"; return -1; }
+  if (kind != ZMX_CRC32 && kind != ZMX_ADLER32) { return Fail("zmx_checksum: unknown kind"); }
+  if (begin > end || end > c->input.size()) { return Fail("zmx_checksum: range outside the resident input"); }
   const size_t n = end - begin, npieces = (n + kChecksumPieceBytes - 1) / kChecksumPieceBytes;
   uint32_t xpow[8];
   ChecksumTreePowers(xpow);
@@ -316,7 +308,7 @@ int zmx_checksum(zmx_ctx* c, int kind, size_t begin, size_t end, uint32_t* value
 int zmx_encode_blocks(zmx_ctx*, zmx_tables* t, size_t njobs, const zmx_enc_job* jobs, const uint32_t* codes,
                       unsigned char* const* out) {
   if (njobs == 0) return 0;
-  if (const int rc = CheckTables("zmx_encode_blocks", t, false, false)) return rc;
+  if (const int rc = CheckTables("zmx_encode_blocks", t, zamd::kAnyTables)) return rc;
   for (size_t j = 0; j < njobs; ++j) {
     if (const int rc = CheckStoreRef("zmx_encode_blocks", t, jobs[j].block, jobs[j].slot, jobs[j].nsym)) return rc;
   }
@@ -356,15 +348,15 @@ int zmx_encode_blocks(zmx_ctx*, zmx_tables* t, size_t njobs, const zmx_enc_job* 
 
 int zmx_find_longest_match(zmx_ctx*, zmx_tables* t, size_t block, size_t pos, uint16_t* sublen,
                            uint16_t* distance, uint16_t* length) {
-  if (const int rc = CheckTables("zmx_find_longest_match", t, true, false)) return rc;
-  if (block >= t->blocks.size()) return Refuse("zmx_find_longest_match", "bad block");
+  if (const int rc = CheckTables("zmx_find_longest_match", t, zamd::kUntrimmed)) return rc;
+  if (const int rc = CheckBlock("zmx_find_longest_match", t, block)) return rc;
   zo_find_longest_match(t->blocks[block].table, pos, sublen, distance, length);
   return 0;
 }
 
 int zmx_length_array_download(zmx_ctx*, zmx_tables* t, size_t block, uint16_t* out) {
-  if (const int rc = CheckTables("zmx_length_array_download", t, true, false)) return rc;
-  if (block >= t->blocks.size()) return Refuse("zmx_length_array_download", "bad block");
+  if (const int rc = CheckTables("zmx_length_array_download", t, zamd::kUntrimmed)) return rc;
+  if (const int rc = CheckBlock("zmx_length_array_download", t, block)) return rc;
   const auto& la = t->blocks[block].length_array;
   std::memcpy(out, la.data(), la.size() * 2);
   return 0;
@@ -378,8 +370,8 @@ struct zmx_cost_stores {
 int zmx_cost_stores_create(zmx_ctx*, zmx_tables* t, size_t nstores, const size_t* piece_first, const size_t* block,
                            const int32_t* slot, const size_t* nsym, zmx_cost_stores** out) {
   *out = nullptr;
-  if (nstores == 0) return Refuse("zmx_cost_stores_create", "no sequence");
-  if (const int rc = CheckTables("zmx_cost_stores_create", t, false, false)) return rc;
+  if (nstores == 0) return Refuse("zmx_cost_stores_create: no sequence");
+  if (const int rc = CheckTables("zmx_cost_stores_create", t, zamd::kAnyTables)) return rc;
   for (size_t p = 0; p < piece_first[nstores]; ++p) {
     if (const int rc = CheckStoreRef("zmx_cost_stores_create", t, block[p], slot[p], nsym[p])) return rc;
   }
@@ -404,8 +396,7 @@ int zmx_cost_stores_create_host(zmx_ctx*, size_t nstores, const uint16_t* const*
   for (size_t q = 0; q < nstores; ++q) {
     const size_t bad = zamd::FirstInvalidSymbol(litlens[q], dists[q], nsym[q]);
     if (bad < nsym[q]) {
-      g_err = g_refused = "zmx_cost_stores_create_host: sequence " + std::to_string(q) + ", symbol " + std::to_string(bad) + " is no LZ77 symbol";
-      return -1;
+      return Refuse("zmx_cost_stores_create_host: sequence " + std::to_string(q) + ", symbol " + std::to_string(bad) + " is no LZ77 symbol");
     }
   }
   zmx_cost_stores* s = new zmx_cost_stores();
@@ -417,7 +408,7 @@ int zmx_cost_stores_create_host(zmx_ctx*, size_t nstores, const uint16_t* const*
 void zmx_cost_stores_free(zmx_ctx*, zmx_cost_stores* s) { delete s; }
 int zmx_cost_positions(zmx_ctx*, zmx_cost_stores* s, size_t n, const uint32_t* pairs, uint64_t* bytes) {
   for (size_t i = 0; i < n; ++i) {
-    if (pairs[2 * i] >= s->stores.size() || pairs[2 * i + 1] > s->stores[pairs[2 * i]].size()) { g_err = "zmx_cost_positions: an index outside its sequence"; return -1; }
+    if (pairs[2 * i] >= s->stores.size() || pairs[2 * i + 1] > s->stores[pairs[2 * i]].size()) { return Fail("zmx_cost_positions: an index outside its sequence"); }
     bytes[i] = s->stores[pairs[2 * i]].ByteRange(0, pairs[2 * i + 1]);
   }
   return 0;
@@ -426,9 +417,9 @@ int zmx_block_costs(zmx_ctx*, zmx_cost_stores* s, size_t n, const uint32_t* r, d
   // (ZOPFLI_HOSTTEST_COSTS_FAIL_AFTER=k: the k-th call and every later one fails — the host's fall-back in mid-search)
   static const long fail_after = [] { const char* e = std::getenv("ZOPFLI_HOSTTEST_COSTS_FAIL_AFTER"); return e ? std::atol(e) : -1L; }();
   static std::atomic<long> calls{0};
-  if (fail_after >= 0 && calls.fetch_add(1) >= fail_after) { g_err = "zmx_block_costs: injected failure"; return -1; }
+  if (fail_after >= 0 && calls.fetch_add(1) >= fail_after) { return Fail("zmx_block_costs: injected failure"); }
   for (size_t i = 0; i < n; ++i) {
-    if (r[3 * i] >= s->stores.size() || r[3 * i + 1] > r[3 * i + 2] || r[3 * i + 2] > s->stores[r[3 * i]].size()) { g_err = "zmx_block_costs: a range outside its sequence"; return -1; }
+    if (r[3 * i] >= s->stores.size() || r[3 * i + 1] > r[3 * i + 2] || r[3 * i + 2] > s->stores[r[3 * i]].size()) { return Fail("zmx_block_costs: a range outside its sequence"); }
     cost[i] = zamd::CalculateBlockSizeAutoType(s->stores[r[3 * i]], r[3 * i + 1], r[3 * i + 2]);
   }
   return 0;

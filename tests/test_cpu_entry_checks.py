@@ -1,6 +1,6 @@
 """The entry checks of test_gpu_entry_checks.py against the host test library: its stand-in for the device layer
-(tests/hostlib/zmx_oracle_backend.cc) refuses the same requests with the same texts and class, for every entry it has
-(it has no hash links).  CPU only."""
+(tests/hostlib/zmx_oracle_backend.cc) runs the device layer's own rules (csrc/host/entry_checks.h) on its own tables,
+for every entry it has (it has no hash links): the same requests are refused, with the same texts and class.  CPU only."""
 import pytest
 
 import oracle_lib as ol

@@ -338,6 +338,33 @@ def test_retry_goes_by_error_class_not_by_text():
     assert 'err.find("pool")' not in src and "err_class == ZMX_ERR_REFUSED" in src
 
 
+def test_host_device_seam_is_declared_once():
+    """The zmx_internal_* functions between the host layer and the device layer have ONE declaration site,
+    csrc/host/zmx_internal.h: no other source under zopfli_amd/csrc or tests/hostlib holds a prototype of one (a return
+    type, the name, a parameter list and a semicolon), and the two files that define them — the device layer and the host
+    test library's stand-in for it — include the header, so every definition is compiled against its declaration."""
+    import re
+    root = os.path.dirname(os.path.dirname(__file__))
+    proto = re.compile(r'^[ \t]*(?:extern\s+"C"\s+)?(?:__attribute__\(\(.*?\)\)\s*)?(?!return\b|else\b)'
+                       r'[A-Za-z_][\w \t\*]*[ \t\*]zmx_internal_\w+\s*\([^;{}]*\)\s*;', re.MULTILINE)
+    found = {}
+    for top in (os.path.join(root, "zopfli_amd", "csrc"), os.path.join(root, "tests", "hostlib")):
+        for folder, _, names in os.walk(top):
+            for name in names:
+                if name.endswith((".h", ".cc", ".c", ".hip", ".cpp")):
+                    path = os.path.join(folder, name)
+                    hits = proto.findall(open(path, encoding="utf-8").read())
+                    if hits:
+                        found[os.path.relpath(path, root)] = hits
+    header = os.path.join("zopfli_amd", "csrc", "host", "zmx_internal.h")
+    assert list(found) == [header], found
+    assert len(found[header]) >= 13                     # (the pattern does find prototypes: all of the seam's)
+    for user in (os.path.join("zopfli_amd", "csrc", "device", "zmx_hip.hip"),
+                 os.path.join("tests", "hostlib", "zmx_oracle_backend.cc")):
+        text = open(os.path.join(root, user), encoding="utf-8").read()
+        assert re.search(r'^#include ".*\bzmx_internal\.h"', text, re.MULTILINE), user
+
+
 def test_host_block_cache_and_no_mallopt():
     """The library keeps its large host arrays in a cache of its own (block_cache.h) instead of reconfiguring the host
     process's malloc: after a call with block splitting zmx_host_cache_trim() gives bytes back, a second trim nothing;

@@ -8,6 +8,8 @@ import pytest
 import oracle_lib as ol
 import walk_cases as wc
 
+ZMX_ERR_REFUSED = 3
+
 
 # ------------------------------------------------------------------------------------------------ the references
 def test_zeros_have_one_distance():
@@ -208,6 +210,43 @@ def host_ctx():
 def test_refusal_rules_host_backend(host_ctx):
     from test_gpu_walk_edges import refusals
     refusals(host_ctx)
+
+
+def test_cell_rule_at_its_edges(host_ctx):
+    """The cell rule of zmx_trace_length_arrays (PathCell, csrc/host/entry_checks.h: the device layer and the host test
+    library run the same function) at cells 0, 1, 2, 3, 257, 258, 259 and 300 of one block of 300 bytes, each holding 0,
+    1, 2, 3, h - 1, h, h + 1, 258 and 259 in turn.  A cell is accepted exactly when its value is 0 or 1 or a length
+    3 .. min(h, 258) — and no step back past the block's start: a 1 in cell 0 is refused, as it was before the rule had
+    a home of its own (refusals() of test_gpu_walk_edges.py asserts that one case on the device as well).  A refusal
+    carries the full text and class REFUSED; an accepted array is traced, or fails for what its path holds (class
+    DEVICE) — never as a refusal."""
+    from zopfli_amd import generate
+    size = 300
+    host_ctx.set_input(generate("M", size))
+    t = host_ctx.build_tables([(0, size)])
+    try:
+        base = np.ones(size + 1, dtype=np.uint16)       # a path of literals: valid, and every cell is on it
+        base[0] = 0
+        tried = 0
+        for h in (0, 1, 2, 3, 257, 258, 259, 300):
+            for v in sorted({0, 1, 2, 3, h - 1, h, h + 1, 258, 259}):
+                if v < 0:
+                    continue
+                la = base.copy()
+                la[h] = v
+                accept = (v in (0, 1) or 3 <= v <= min(h, 258)) and v <= h
+                try:
+                    t.trace([la], [0])
+                    refused = False
+                except RuntimeError:
+                    refused = host_ctx.lib.zmx_last_error_class() == ZMX_ERR_REFUSED
+                assert refused == (not accept), (h, v)
+                if refused:
+                    assert host_ctx.error() == f"zmx_trace_length_arrays: block 0, cell {h} holds {v}: no step of a path"
+                tried += 1
+        assert tried == 56                              # (72 pairs less h - 1 = -1 and the values that coincide)
+    finally:
+        t.free()
 
 
 def test_error_reports_host_backend(host_ctx):

@@ -1,4 +1,4 @@
-"""What the zmx_* entries refuse before they touch anything (CheckTables, CheckStoreRef in zmx_hip.hip): a block, a slot
+"""What the zmx_* entries refuse before they touch anything (the rules of csrc/host/entry_checks.h): a block, a slot
 or a symbol count that the tables do not have, trimmed tables, tables that hold matches only.  Every refusal is class
 ZMX_ERR_REFUSED and its message is the entry's own name, then the one text all entries share.  String and integer
 equality, no tolerance.
@@ -9,7 +9,7 @@ count.  A greedy store starts at the front of its slot and the layer does not ke
 block's size, and one more than that is refused.
 
 The bodies take the context as an argument: test_cpu_entry_checks.py runs them against the host test library, whose
-stand-in mirrors the texts."""
+stand-in for the device layer calls the same rules."""
 import ctypes
 
 import numpy as np

@@ -877,6 +877,43 @@ def test_mid_size_calls_dealt_at_stream_priorities():
         assert res["dealt"][0] == hashlib.sha256(ol.ref_compress(data, 0, 3)).hexdigest()
 
 
+def test_statistics_survive_the_join_of_a_dealt_call():
+    """A dealt call's shard threads hand their kernel / match / task sums to the caller's thread at the join (api.cc
+    RunShards: TakeStats on each shard thread, AddStats on the caller's), and zmx_last_* read the caller's.  2 500 000 bytes of class T (three master blocks), two iterations, no block splitting, deflate,
+    in two fresh processes (the switches are read once): never dealt (ZOPFLI_AMD_SPLIT_MB=0) and dealt from one master
+    block on (ZOPFLI_AMD_SPLIT_MB=1, with ZOPFLI_AMD_DEAL_AFTER=0: a call this small is otherwise dealt only from the
+    process's eighth on).  The streams are byte-identical, the call trace shows that the second was dealt, and the
+    tasks and the positions over all squeeze runs — both per block and per run, whichever context runs the block — are
+    positive and the same in both: nothing a shard thread counted is lost at the join.  Integer equality."""
+    import subprocess
+    import sys
+    code = (
+        "import hashlib, sys\n"
+        "sys.path.insert(0, %r)\n"
+        "from zopfli_amd import ZopfliOptions, api, generate\n"
+        "o = ZopfliOptions(2)\n"
+        "o.blocksplitting = 0\n"
+        "out = api.compress(generate('T', 2500000), api.FORMAT_DEFLATE, o)\n"
+        "s = api.last_seg_stats()\n"
+        "print(hashlib.sha256(out).hexdigest(), len(out), repr(s['tasks']), repr(s['positions']))\n"
+        % os.path.dirname(os.path.dirname(__file__)))
+    res = {}
+    for name, split_mb in (("never", "0"), ("dealt", "1")):
+        env = dict(os.environ, ZOPFLI_AMD_SPLIT_MB=split_mb, ZOPFLI_AMD_DEAL_AFTER="0", ZOPFLI_AMD_TRACE_CALL="1")
+        for k in ("LOCAL_RANK", "ZOPFLI_AMD_DEVICES", "ZOPFLI_AMD_SPLIT_WAYS"):
+            env.pop(k, None)
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        digest, size, tasks, positions = r.stdout.split()
+        res[name] = (digest, int(size), float(tasks), float(positions))
+        print(name, res[name])
+        assert r.stderr.count("shard 2 (") == (1 if name == "dealt" else 0), r.stderr[-3000:]
+    assert res["never"][:2] == res["dealt"][:2]
+    for name in res:
+        assert res[name][2] > 0 and res[name][3] > 0, res
+    assert res["never"][2:] == res["dealt"][2:], res
+
+
 def test_rccl_gather_world_of_one(gpu_ctx):
     """zmx_dist_* (dist.cc): librccl loads, a communicator of one rank forms on the device and the
     gather returns rank 0's own blob — all of the RCCL path a one-GPU box can run; with more ranks the

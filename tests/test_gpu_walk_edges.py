@@ -58,9 +58,11 @@ def _expect_flags(ctx, t, las, slots, flags):
     assert ctx.lib.zmx_last_error_class() == ZMX_ERR_DEVICE
 
 
-def _expect_refused(ctx, t, las, slots):
+def _expect_refused(ctx, t, las, slots, text):
+    """The refusal's whole message: the entry's name, then `text` (host/entry_checks.h holds the texts, once)."""
     with pytest.raises(RuntimeError, match="zmx_trace_length_arrays"):
         t.trace(las, slots)
+    assert ctx.error() == "zmx_trace_length_arrays: " + text
     assert ctx.lib.zmx_last_error_class() == ZMX_ERR_REFUSED
 
 
@@ -133,20 +135,23 @@ def refusals(ctx):
         def bad(b, h, v):
             las = [a.copy() for a in good]
             las[b][h] = v
-            return las
+            return las, f"block {b}, cell {h} holds {v}: no step of a path"
 
         off_path = next(h for h in range(3000, 4000) if case.las[1][h] == 0)
         on_path = refs[1]["heads"][7]
-        for las in (bad(1, off_path, 259), bad(1, on_path, 259), bad(1, off_path, 2), bad(1, on_path, 2), bad(0, 0, 1),
-                    bad(0, 1, 3), bad(2, 5, 6), bad(6, 100, 101), bad(nb - 1, len(good[nb - 1]) - 1, 65535)):
-            _expect_refused(ctx, t, las, slots)
+        for las, text in (bad(1, off_path, 259), bad(1, on_path, 259), bad(1, off_path, 2), bad(1, on_path, 2), bad(0, 0, 1),
+                          bad(0, 1, 3), bad(2, 5, 6), bad(6, 100, 101), bad(nb - 1, len(good[nb - 1]) - 1, 65535)):
+            _expect_refused(ctx, t, las, slots, text)
             nsym, hist = t.trace(good, slots)
             assert_stores(t, slots, nsym, hist, refs, "after a refusal")
-        _expect_refused(ctx, t, good[:-1], slots[:-1])                     # a block short
-        _expect_refused(ctx, t, good + [good[0]], slots + [0])             # a block too many
-        _expect_refused(ctx, t, [good[0][:-1]] + good[1:], slots)          # a cell short
-        _expect_refused(ctx, t, [np.append(good[0], 1)] + good[1:], slots)
-        _expect_refused(ctx, t, good, [2] + slots[1:])
+        per_block = "one length array per block of the tables"
+        size0 = len(good[0]) - 1
+        _expect_refused(ctx, t, good[:-1], slots[:-1], per_block)                     # a block short
+        _expect_refused(ctx, t, good + [good[0]], slots + [0], per_block)             # a block too many
+        _expect_refused(ctx, t, [good[0][:-1]] + good[1:], slots,                     # a cell short
+                        f"block 0 has {size0} + 1 cells, not {size0}")
+        _expect_refused(ctx, t, [np.append(good[0], 1)] + good[1:], slots, f"block 0 has {size0} + 1 cells, not {size0 + 2}")
+        _expect_refused(ctx, t, good, [2] + slots[1:], "slot must be 0 or 1")
         # the valid side of the rule: 0 anywhere off the path, 1 at cell 1, 258 at cell 258, h at cell h < 258
         las = [a.copy() for a in case.las]
         for b in range(nb):
@@ -156,12 +161,12 @@ def refusals(ctx):
         nsym, hist = t.trace(las, slots)
         assert_stores(t, slots, nsym, hist, refs, "valid edges")
         t.trim()
-        _expect_refused(ctx, t, good, slots)
+        _expect_refused(ctx, t, good, slots, "these tables were trimmed to their stores (zmx_tables_trim)")
     finally:
         t.free()
     t = ctx.build_tables(o["blocks"], matches_only=True)
     try:
-        _expect_refused(ctx, t, good, slots)
+        _expect_refused(ctx, t, good, slots, "these tables hold matches only (zmx_tables_build_matches)")
     finally:
         t.free()
 

@@ -34,31 +34,16 @@
 #include "zmx_knobs.h"
 #include "zopfli_amd.h"
 #include "../host/deal.h"
+#include "../host/entry_checks.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
+#include "../host/zmx_internal.h"
 
 namespace {
 
 using zamd::Knobs;   // the ZOPFLI_AMD_* switches of this file (zmx_knobs.h)
 
 thread_local std::string g_err;   // per calling thread (zmx_last_error)
-// Kernel, match and task statistics: per calling THREAD (a Zopfli* call's shard threads hand theirs to the caller's
-// at the join, api.cc), so that concurrent callers read their own numbers (zmx_last_*).
-struct ThreadStats {
-  double kernel_seconds[3];  // k_wtab + k_badscan, chain kernels (k_dp5_spec + k_dpcheck + k_dp4_fix), k_trace (HIP events)
-  double squeeze_launches;
-  double match5[3];          // k_match5: entries in flight summed over lanes and iterations, wave iterations, positions it walked
-  double match[4];           // match kernel seconds, k_same + k_chain (+ k_levels ...) seconds, table builds, positions matched
-  double seg[8];             // tasks, accepted, re-run: state / level / tie, positions re-run, re-run: values, positions
-};
-static_assert(sizeof(ThreadStats) == 19 * sizeof(double), "zmx_internal_stats_take / _add move 19 doubles");
-thread_local ThreadStats g_ts = {};
-#define g_kernel_seconds g_ts.kernel_seconds
-#define g_squeeze_launches g_ts.squeeze_launches
-#define g_match5_stats g_ts.match5
-#define g_match_stats g_ts.match
-#define g_seg_stats g_ts.seg
-
 thread_local bool g_last_oom = false;   // the last failure of this thread was an allocation the device could not serve
 // What KIND of failure the last one of this thread was (zmx_last_error_class): callers decide by this code, never by the
 // message's text (the text holds the failing expression and __FILE__: "PoolAlloc(...)", a build path).
@@ -383,51 +368,12 @@ int zmx_set_match_order(int on) {
   return 0;
 }
 
+// ---- the seam to the host layer (host/zmx_internal.h says what each does)
 size_t zmx_internal_input_size(zmx_ctx* ctx) { return ctx->insize; }
 int zmx_internal_device(zmx_ctx* ctx) { return ctx->device; }
-void zmx_internal_set_error(const char* msg) { g_err = msg; g_err_class = ZMX_ERR_DEVICE; }
-void zmx_internal_set_error_class(const char* msg, int cls) { g_err = msg; g_err_class = cls; }
+void zmx_internal_set_error(const char* msg, int cls) { g_err = msg; g_err_class = cls; }
 const unsigned char* zmx_internal_input_host(zmx_ctx* ctx) { return ctx->h_in; }
-// the context's memory pool in numbers (DevicePool::Stats says which); reads only
-__attribute__((visibility("default"))) void zmx_internal_pool_stats(zmx_ctx* ctx, uint64_t out[8]) { ctx->pool.Stats(out); }
-
-void zmx_internal_seg_stats(double* out8, int reset) {
-  // (thread-local: no lock)
-  for (int i = 0; i < 8; ++i) out8[i] = g_seg_stats[i];
-  if (reset) for (int i = 0; i < 8; ++i) g_seg_stats[i] = 0;
-}
-
-void zmx_internal_match5_stats(double* out3, int reset) {
-  // (thread-local: no lock)
-  for (int i = 0; i < 3; ++i) out3[i] = g_match5_stats[i];
-  if (reset) for (int i = 0; i < 3; ++i) g_match5_stats[i] = 0;
-}
-
-void zmx_internal_match_stats(double* out4, int reset) {
-  // (thread-local: no lock)
-  for (int i = 0; i < 4; ++i) out4[i] = g_match_stats[i];
-  if (reset) for (int i = 0; i < 4; ++i) g_match_stats[i] = 0;
-}
-
-void zmx_internal_kernel_stats(double* seconds3, double* squeeze_launches, int reset) {
-  // (thread-local: no lock)
-  for (int i = 0; i < 3; ++i) seconds3[i] = g_kernel_seconds[i];
-  *squeeze_launches = g_squeeze_launches;
-  if (reset) {
-    g_kernel_seconds[0] = g_kernel_seconds[1] = g_kernel_seconds[2] = 0;
-    g_squeeze_launches = 0;
-  }
-}
-
-// a shard thread's sums since it started, zeroed — and added to the calling thread's (api.cc, at the join of a call's shards)
-void zmx_internal_stats_take(double* out19) {
-  std::memcpy(out19, &g_ts, sizeof(g_ts));
-  g_ts = ThreadStats{};
-}
-void zmx_internal_stats_add(const double* in19) {
-  double* d = reinterpret_cast<double*>(&g_ts);
-  for (int i = 0; i < 19; ++i) d[i] += in19[i];
-}
+void zmx_internal_pool_stats(zmx_ctx* ctx, uint64_t out[8]) { ctx->pool.Stats(out); }
 
 // (no context: as PoolFree)
 static void PinnedGive(zmx_ctx* c, unsigned char** p, size_t cap) {
@@ -605,7 +551,6 @@ int zmx_internal_device_pointer(const char* who, const void* p, size_t n, int* d
   return CheckDevicePointer(who, p, n, device);
 }
 
-// the same for n ranges, before anything is done with any of them (zmx_compress_device_batch)
 int zmx_internal_device_pointers(const char* who, size_t n, const void* const* p, const size_t* nbytes) {
   DeviceRangeChecker checker;
   int device = -1;
@@ -615,8 +560,6 @@ int zmx_internal_device_pointers(const char* who, size_t n, const void* const* p
   return 0;
 }
 
-// A plain allocation of `device` that its caller owns (the staging buffer of zmx_compress_device_batch: it outlives the
-// context it was filled on, which goes back to the pool while the shards copy from it).
 int zmx_internal_device_alloc(int device, size_t n, void** p) {
   *p = nullptr;
   DeviceGuard dev_guard(device);
@@ -638,8 +581,6 @@ int zmx_set_input_device(zmx_ctx* c, const void* d_in, size_t insize) {
   return CopyInput(c, d_in, insize, hipMemcpyDefault);
 }
 
-// Bytes [begin, end) of the resident input, device to host (the bytes of a stored block when the input came from device
-// memory: the host has no copy of its own).
 int zmx_internal_input_fetch(zmx_ctx* c, size_t begin, size_t end, unsigned char* dst) {
   if (begin > end || end > c->insize) return FailMsg("zmx_internal_input_fetch: range outside the resident input");
   if (begin == end) return 0;
@@ -650,8 +591,6 @@ int zmx_internal_input_fetch(zmx_ctx* c, size_t begin, size_t end, unsigned char
   return 0;
 }
 
-// k_probe_counts over n ranges of `bytes` — device memory of the context's device; null: the resident input —, the
-// caller having checked the ranges against it: counts[r][zamd::kProbeCounts].
 int zmx_internal_probe_counts(zmx_ctx* c, const void* bytes, size_t n, const uint64_t* ranges, uint32_t* counts) {
   if (n == 0) return 0;
   if (n > 65535) return FailMsg("zmx_internal_probe_counts: too many ranges for one launch");
@@ -685,11 +624,8 @@ int zmx_internal_probe_counts(zmx_ctx* c, const void* bytes, size_t n, const uin
   return 0;
 }
 
-// The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
-// (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing, as the other phase
-// times; include/zopfli_amd.h says so at zmx_gather_device); else 0.  For tools/batch_files.py --device.
-static thread_local double g_gather_ms = 0;
-__attribute__((visibility("default"))) double zmx_internal_gather_ms(void) { return g_gather_ms; }
+static thread_local double g_gather_ms = 0;   // (zmx_internal_gather_ms)
+double zmx_internal_gather_ms(void) { return g_gather_ms; }
 
 int zmx_gather_device(zmx_ctx* c, size_t n, const void* const* d_src, const size_t* nbytes, void* d_dst) {
   g_gather_ms = 0;
@@ -1327,15 +1263,15 @@ static int BuildMatchRecords(zmx_ctx* c, zmx_tables* t, zmx_tables* parent, int 
     float ms_hash = 0, ms_match = 0;
     HIPCHK(hipEventElapsedTime(&ms_hash, c->ev[0], c->ev[1]));
     HIPCHK(hipEventElapsedTime(&ms_match, c->ev[1], c->ev[2]));
-    // (thread-local: no lock)
-    g_match_stats[0] += ms_match * 1e-3;
-    g_match_stats[1] += ms_hash * 1e-3;
-    g_match_stats[2] += 1;
-    g_match_stats[3] += reuse ? static_cast<double>(plan.tile_list.size()) * MT : match_positions;
+    zmx_stats& ts = zamd::ThreadStats();   // (thread-local: no lock)
+    ts.match[0] += ms_match * 1e-3;
+    ts.match[1] += ms_hash * 1e-3;
+    ts.match[2] += 1;
+    ts.match[3] += reuse ? static_cast<double>(plan.tile_list.size()) * MT : match_positions;
     if (m.skip_any && !reuse) {
-      g_match5_stats[0] += m5_lane_iters;
-      g_match5_stats[1] += m5_iters;
-      g_match5_stats[2] += m.skip_positions;
+      ts.match5[0] += m5_lane_iters;
+      ts.match5[1] += m5_iters;
+      ts.match5[2] += m.skip_positions;
     }
     if (Knobs().prof && !reuse) {
       unsigned long long hc[2] = {0, 0};
@@ -1698,25 +1634,19 @@ static int BuildTables(zmx_ctx* c, const zmx_block* blocks, size_t nb, zmx_table
 
 // ---------------------------------------------------------------------------------------------
 // What the entries check of their arguments before they touch anything.  `who` is the entry's name: the messages
-// start with it.
+// start with it.  The rules and their texts are host/entry_checks.h's; here they meet the tables.
 // ---------------------------------------------------------------------------------------------
-enum TableNeeds {
-  kAnyTables,     // the stores are enough (they survive zmx_tables_trim)
-  kUntrimmed,     // ... the match records and what goes with them
-  kWithDp,        // ... and DP rows, codes, windows and tasks (not zmx_tables_build_matches)
-};
-static int CheckTables(const char* who, const zmx_tables* t, TableNeeds needs) {
-  const std::string w(who);
-  if (!t) return FailMsg(w + ": no tables");
-  if (needs >= kUntrimmed && t->trimmed) return FailMsg(w + ": these tables were trimmed to their stores (zmx_tables_trim)");
-  if (needs >= kWithDp && t->matches_only) return FailMsg(w + ": these tables hold matches only (zmx_tables_build_matches)");
-  return 0;
+static int Refused(const std::string& refusal) { return refusal.empty() ? 0 : FailMsg(refusal); }
+static int CheckTables(const char* who, const zmx_tables* t, zamd::TableNeeds needs) {
+  return Refused(zamd::CheckTables(who, t != nullptr, t && t->trimmed, t && t->matches_only, needs));
+}
+static int CheckBlock(const char* who, const zmx_tables* t, size_t block) {
+  return Refused(zamd::CheckBlock(who, t->nb, block));
 }
 // symbols [0, nsym) of the store in `slot` of `block`
 static int CheckStoreRef(const char* who, const zmx_tables* t, size_t block, int slot, size_t nsym) {
-  if (block >= t->nb || (slot != 0 && slot != 1)) return FailMsg(std::string(who) + ": bad block or slot");
-  if (t->store_begin[slot][block] + nsym > t->bsize[block]) return FailMsg(std::string(who) + ": nsym exceeds the store");
-  return 0;
+  return Refused(zamd::CheckStoreRef(who, t->nb, block, slot, nsym,
+                                     [&] { return static_cast<size_t>(t->bsize[block] - t->store_begin[slot][block]); }));
 }
 // The pinned staging buffer of a context holds at least `words` u32 (grow-only, with a quarter to spare).
 static int StageReserve(zmx_ctx* c, size_t words) {
@@ -1762,12 +1692,12 @@ int zmx_tables_build_matches(zmx_ctx* c, const zmx_block* blocks, size_t nblocks
 // of equal bytes that reaches the end — only the tiles holding such positions are recomputed,
 // everything else is copied.  Hash links (k_same, k_chain) are rebuilt: they are cheap.
 int zmx_tables_build_from(zmx_ctx* c, zmx_tables* parent, const zmx_block* blocks, size_t nblocks, zmx_tables** out) {
-  if (parent != nullptr && CheckTables("zmx_tables_build_from", parent, kUntrimmed) != 0) return -1;
+  if (parent != nullptr && CheckTables("zmx_tables_build_from", parent, zamd::kUntrimmed) != 0) return -1;
   return BuildTablesEntry(c, parent, blocks, nblocks, true, out);
 }
 
 int zmx_lz77_greedy(zmx_ctx* c, zmx_tables* t, int slot, uint32_t* nsym, uint32_t* hist) {
-  if (const int rc = CheckTables("zmx_lz77_greedy", t, kUntrimmed)) return rc;
+  if (const int rc = CheckTables("zmx_lz77_greedy", t, zamd::kUntrimmed)) return rc;
   if (t->nb == 0) return 0;
   if (slot != 0 && slot != 1) return FailMsg("zmx_lz77_greedy: slot must be 0 or 1");
   DeviceGuard dev_guard(c->device);
@@ -1867,7 +1797,7 @@ static void RunInfo(const double* cost, const u32* hist, u32 B, float* wmax_out,
 }
 
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model, no device involved.
-__attribute__((visibility("default"))) void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask) {
+void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask) {
   float est;
   RunInfo(cost320, nullptr, 0, wmax, tiemask, &est);
 }
@@ -1971,9 +1901,8 @@ static void LaunchFix(hipStream_t stream, unsigned nblk, const Dp4Params& p) {
 
 int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double* mincost, const int32_t* slot,
                     uint32_t* nsym, uint32_t* hist) {
-  if (const int rc = CheckTables("zmx_squeeze_run", t, kUntrimmed)) return rc;
+  if (const int rc = CheckTables("zmx_squeeze_run", t, zamd::SqueezeRunNeeds(t ? t->nb : 0))) return rc;
   if (t->nb == 0) return 0;
-  if (const int rc = CheckTables("zmx_squeeze_run", t, kWithDp)) return rc;
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   for (size_t b = 0; b < t->nb; ++b) {
@@ -2092,11 +2021,11 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
   }
   ++t->squeeze_runs;
   {
-    // (thread-local: no lock)
-    for (int i = 0; i < 3; ++i) g_kernel_seconds[i] += ksec[i];
-    g_squeeze_launches += 1;
-    for (int i = 0; i < 7; ++i) g_seg_stats[i] += segstats[i];
-    g_seg_stats[7] += static_cast<double>(t->total_b);
+    zmx_stats& ts = zamd::ThreadStats();   // (thread-local: no lock)
+    for (int i = 0; i < 3; ++i) ts.kernel_seconds[i] += ksec[i];
+    ts.squeeze_launches += 1;
+    for (int i = 0; i < 7; ++i) ts.seg[i] += segstats[i];
+    ts.seg[7] += static_cast<double>(t->total_b);
   }
   if (t->d_prof) return ReportSqueezeProf(t, ksec, segstats);
   return 0;
@@ -2108,25 +2037,11 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
 // device's own business (flags 2 and 4 of k_trace_emit).
 int zmx_trace_length_arrays(zmx_ctx* c, zmx_tables* t, size_t nblocks, const uint16_t* const* length_arrays,
                             const size_t* entries, const int32_t* slot, uint32_t* nsym, uint32_t* hist) {
-  if (const int rc = CheckTables("zmx_trace_length_arrays", t, kWithDp)) return rc;
-  if (nblocks != t->nb) return FailMsg("zmx_trace_length_arrays: one length array per block of the tables");
+  if (const int rc = CheckTables("zmx_trace_length_arrays", t, zamd::kWithDp)) return rc;
+  if (const int rc = Refused(zamd::CheckLengthArrays("zmx_trace_length_arrays", t->nb, [&](size_t b) { return size_t{t->bsize[b]}; },
+                                                     nblocks, length_arrays, entries, slot))) return rc;
   const size_t nb = t->nb;
   if (nb == 0) return 0;
-  char buf[160];
-  for (size_t b = 0; b < nb; ++b) {
-    if (slot[b] != 0 && slot[b] != 1) return FailMsg("zmx_trace_length_arrays: slot must be 0 or 1");
-    if (entries[b] != static_cast<size_t>(t->bsize[b]) + 1) {
-      std::snprintf(buf, sizeof(buf), "zmx_trace_length_arrays: block %zu has %u + 1 cells, not %zu", b, t->bsize[b], entries[b]);
-      return FailMsg(buf);
-    }
-    for (size_t h = 0; h < entries[b]; ++h) {
-      const unsigned v = length_arrays[b][h];
-      if (v == 2 || v > (h < ZMX_MAX_MATCH ? h : ZMX_MAX_MATCH)) {
-        std::snprintf(buf, sizeof(buf), "zmx_trace_length_arrays: block %zu, cell %zu holds %u: no step of a path", b, h, v);
-        return FailMsg(buf);
-      }
-    }
-  }
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   // la[] rows as LayoutBlocks laid them out (padded to 8 entries), in one blocking copy
@@ -2148,7 +2063,7 @@ int zmx_trace_length_arrays(zmx_ctx* c, zmx_tables* t, size_t nblocks, const uin
 
 int zmx_store_download(zmx_ctx* c, zmx_tables* t, size_t block, int slot, uint16_t* litlens, uint16_t* dists,
                        size_t nsym) {
-  if (const int rc = CheckTables("zmx_store_download", t, kAnyTables)) return rc;
+  if (const int rc = CheckTables("zmx_store_download", t, zamd::kAnyTables)) return rc;
   if (const int rc = CheckStoreRef("zmx_store_download", t, block, slot, nsym)) return rc;
   if (nsym == 0) return 0;
   const u32 begin = t->store_begin[slot][block];
@@ -2167,7 +2082,7 @@ int zmx_store_download(zmx_ctx* c, zmx_tables* t, size_t block, int slot, uint16
 
 int zmx_store_download_batch(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, const int32_t* slot,
                              const size_t* nsym, uint16_t* const* litlens, uint16_t* const* dists) {
-  if (const int rc = CheckTables("zmx_store_download_batch", t, kAnyTables)) return rc;
+  if (const int rc = CheckTables("zmx_store_download_batch", t, zamd::kAnyTables)) return rc;
   std::vector<size_t> off(n + 1, 0);
   for (size_t i = 0; i < n; ++i) {
     if (const int rc = CheckStoreRef("zmx_store_download_batch", t, block[i], slot[i], nsym[i])) return rc;
@@ -2199,7 +2114,7 @@ int zmx_store_download_batch(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* 
 }
 
 int zmx_verify_stores(zmx_ctx* c, zmx_tables* t, size_t n, const size_t* block, const int32_t* slot, const size_t* nsym) {
-  if (const int rc = CheckTables("zmx_verify_stores", t, kUntrimmed)) return rc;
+  if (const int rc = CheckTables("zmx_verify_stores", t, zamd::kUntrimmed)) return rc;
   if (n == 0) return 0;
   std::vector<VerifyJob> vj(n);
   for (size_t i = 0; i < n; ++i) {
@@ -2323,7 +2238,7 @@ int zmx_checksums(zmx_ctx* c, int kind, size_t n, const uint64_t* begin, const u
 int zmx_encode_blocks(zmx_ctx* c, zmx_tables* t, size_t njobs, const zmx_enc_job* jobs, const uint32_t* codes,
                       unsigned char* const* out) {
   if (njobs == 0) return 0;
-  if (const int rc = CheckTables("zmx_encode_blocks", t, kAnyTables)) return rc;
+  if (const int rc = CheckTables("zmx_encode_blocks", t, zamd::kAnyTables)) return rc;
   std::vector<EncJob> ej(njobs);
   std::vector<u32> tile_job;
   std::vector<size_t> out_off(njobs + 1, 0);     // in the device / staging buffer, 8-byte aligned
@@ -2552,8 +2467,8 @@ int zmx_match_digest(zmx_ctx* c, zmx_tables* t, uint64_t* out2) {
 
 int zmx_find_longest_match(zmx_ctx* c, zmx_tables* t, size_t block, size_t pos, uint16_t* sublen,
                            uint16_t* distance, uint16_t* length) {
-  if (const int rc = CheckTables("zmx_find_longest_match", t, kUntrimmed)) return rc;
-  if (block >= t->nb) return FailMsg("zmx_find_longest_match: bad block");
+  if (const int rc = CheckTables("zmx_find_longest_match", t, zamd::kUntrimmed)) return rc;
+  if (const int rc = CheckBlock("zmx_find_longest_match", t, block)) return rc;
   const BlockDesc& d = t->blocks[block];
   if (pos < d.instart || pos >= d.inend) return FailMsg("zmx_find_longest_match: pos outside the block");
   DeviceGuard dev_guard(c->device);
@@ -2597,8 +2512,8 @@ int zmx_find_longest_match(zmx_ctx* c, zmx_tables* t, size_t block, size_t pos, 
 }
 
 int zmx_hash_links_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* same, uint16_t* prev1, uint16_t* prev2) {
-  if (const int rc = CheckTables("zmx_hash_links_download", t, kUntrimmed)) return rc;
-  if (block >= t->nb) return FailMsg("zmx_hash_links_download: bad block");
+  if (const int rc = CheckTables("zmx_hash_links_download", t, zamd::kUntrimmed)) return rc;
+  if (const int rc = CheckBlock("zmx_hash_links_download", t, block)) return rc;
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   if (t->links_partial) return FailMsg("zmx_hash_links_download: tables built from a parent hold the hash arrays only near the block ends");
@@ -2615,8 +2530,8 @@ int zmx_hash_links_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* s
 }
 
 int zmx_length_array_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* out) {
-  if (const int rc = CheckTables("zmx_length_array_download", t, kUntrimmed)) return rc;
-  if (block >= t->nb) return FailMsg("zmx_length_array_download: bad block");
+  if (const int rc = CheckTables("zmx_length_array_download", t, zamd::kUntrimmed)) return rc;
+  if (const int rc = CheckBlock("zmx_length_array_download", t, block)) return rc;
   DeviceGuard dev_guard(c->device);
   HIPCHK(dev_guard.err);
   HIPCHK(hipMemcpy(out, t->d_la + t->blocks[block].la_off, (static_cast<size_t>(t->bsize[block]) + 1) * sizeof(u16),
@@ -2710,7 +2625,7 @@ int zmx_cost_stores_create(zmx_ctx* c, zmx_tables* t, size_t nstores, const size
                            const int32_t* slot, const size_t* nsym, zmx_cost_stores** out) {
   *out = nullptr;
   if (nstores == 0) return FailMsg("zmx_cost_stores_create: no sequence");
-  if (const int rc = CheckTables("zmx_cost_stores_create", t, kAnyTables)) return rc;
+  if (const int rc = CheckTables("zmx_cost_stores_create", t, zamd::kAnyTables)) return rc;
   const size_t np = piece_first[nstores];
   std::vector<size_t> total(nstores, 0);
   for (size_t s = 0; s < nstores; ++s) {

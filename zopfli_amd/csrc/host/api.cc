@@ -25,23 +25,8 @@
 #include "deal.h"
 #include "dealing.h"
 #include "thread_pool.h"
+#include "zmx_internal.h"
 #include "zopfli_amd.h"
-
-// implemented by the device layer: kernel-only seconds / launches of the squeeze kernel
-extern "C" void zmx_internal_kernel_stats(double* seconds3, double* squeeze_launches, int reset);
-extern "C" void zmx_internal_seg_stats(double* out8, int reset);
-extern "C" void zmx_internal_match_stats(double* out4, int reset);
-extern "C" void zmx_internal_match5_stats(double* out3, int reset);
-extern "C" void zmx_internal_stats_take(double* out19);
-extern "C" void zmx_internal_stats_add(const double* in19);
-// implemented by the device layer: size of the resident input
-extern "C" size_t zmx_internal_input_size(zmx_ctx* ctx);
-// implemented by the device layer: the caller's host copy of the resident input (borrowed)
-extern "C" const unsigned char* zmx_internal_input_host(zmx_ctx* ctx);
-extern "C" void zmx_internal_set_error(const char* msg);
-// implemented by the device layer alone: bytes [begin, end) of the resident input, device to host.  (Weak: the host test
-// library's stand-in for the device layer keeps every input on the host and has no such function.)
-extern "C" __attribute__((weak)) int zmx_internal_input_fetch(zmx_ctx* ctx, size_t begin, size_t end, unsigned char* dst);
 
 namespace zamd {
 
@@ -74,9 +59,29 @@ void MaybeKeepHeap() {
   (void)once;
 }
 
+zmx_stats& ThreadStats() {
+  static thread_local zmx_stats stats = {};
+  return stats;
+}
+
 }  // namespace zamd
 
 namespace {
+
+// a shard thread's sums since it started, zeroed — and added to the calling thread's (at the join of a call's shards)
+zmx_stats TakeStats() {
+  const zmx_stats s = zamd::ThreadStats();
+  zamd::ThreadStats() = zmx_stats{};
+  return s;
+}
+void AddStats(const zmx_stats& s) {
+  zmx_stats& t = zamd::ThreadStats();
+  for (int i = 0; i < 3; ++i) t.kernel_seconds[i] += s.kernel_seconds[i];
+  t.squeeze_launches += s.squeeze_launches;
+  for (int i = 0; i < 3; ++i) t.match5[i] += s.match5[i];
+  for (int i = 0; i < 4; ++i) t.match[i] += s.match[i];
+  for (int i = 0; i < 8; ++i) t.seg[i] += s.seg[i];
+}
 
 using zamd::Die;
 using zamd::kMasterBlock;
@@ -96,11 +101,15 @@ thread_local double g_traffic[3] = {0, 0, 0};
 
 // The stored chunks of an input the host holds no copy of (zmx_set_input_device) take their bytes from the context
 // they were computed on, each its own range only; positions relative to the context's input.
+// (The reference from THIS file is weak, the declaration and the device layer's definition are not: these host sources
+//  also load with the device-layer stand-in of the commit before this function's stub, so that that commit's host tests
+//  run against them unchanged.  Only a stand-in can lack it, and no stand-in holds an input in device memory.)
+#pragma weak zmx_internal_input_fetch
 int FetchStoredBytes(zmx_ctx* ctx, std::vector<zamd::Chunk>* chunks, double* fetched) {
   for (zamd::Chunk& c : *chunks) {
     if (c.kind != zamd::Chunk::kStored || c.end == c.start) continue;
     if (!zmx_internal_input_fetch) {
-      zmx_internal_set_error("stored block of a device input: this build cannot fetch its bytes");
+      zmx_internal_set_error("stored block of a device input: this build cannot fetch its bytes", ZMX_ERR_DEVICE);
       return -1;
     }
     c.raw.resize(c.end - c.start);
@@ -177,7 +186,7 @@ struct Shard {
   uint32_t sum = 0;
   size_t sum_bytes = 0;
   bool redone = false;
-  double stats[19] = {0};        // the shard thread's kernel / match / task statistics (zmx_internal_stats_take)
+  zmx_stats stats = {};          // the shard thread's kernel / match / task statistics (TakeStats)
   double traffic[3] = {0, 0, 0}; // its input bytes, as g_traffic (all attempts)
 };
 
@@ -355,7 +364,7 @@ void RunShard(ShardedCall* call, size_t d, zmx_ctx* ctx, bool retry) {
   } split_on_device(hooks && hooks->split_on_device);
   sh.rc = RunParts(ctx, call->options, call->btype, mine, &sh.chunks, call->want_part_chunks ? &sh.part_chunks : nullptr,
                    hooks ? hooks->group_bytes : 0);
-  if (!sh.rc && call->dev && FetchStoredBytes(ctx, &sh.chunks, &sh.traffic[2]) != 0) sh.rc = -1;
+  if (!sh.rc && call->dev && FetchStoredBytes(ctx,&sh.chunks, &sh.traffic[2]) != 0) sh.rc = -1;
   if (sh.rc) { sh.err = zmx_last_error(); sh.err_class = zmx_last_error_class(); }
   if (TraceCall()) {
     std::fprintf(stderr, "  shard %zu (%zu parts): start +%.2f ms, wait for turn %.2f, upload %.2f, checksum %.2f, parts %.2f, end +%.2f\n",
@@ -365,7 +374,7 @@ void RunShard(ShardedCall* call, size_t d, zmx_ctx* ctx, bool retry) {
     if (c.kind == zamd::Chunk::kStored) { c.start += sh.base; c.end += sh.base; }
   }
   sh.timing = zamd::ThreadTiming();
-  if (d != 0 && !retry) zmx_internal_stats_take(sh.stats);   // (a thread of its own: its sums go to the caller's below)
+  if (d != 0 && !retry) sh.stats = TakeStats();   // (a thread of its own: its sums go to the caller's below)
 }
 
 // Every shard on its context: the first on the calling thread, the others on a thread each.
@@ -375,7 +384,7 @@ void RunShards(ShardedCall* call, const std::vector<zmx_ctx*>& ctxs) {
   for (size_t d = 1; d < ndev; ++d) threads.emplace_back(RunShard, call, d, ctxs[d], false);
   RunShard(call, 0, ctxs[0], false);
   for (auto& t : threads) t.join();
-  for (size_t d = 1; d < ndev; ++d) zmx_internal_stats_add(call->shards[d].stats);
+  for (size_t d = 1; d < ndev; ++d) AddStats(call->shards[d].stats);
   // the slowest device's breakdown stands for the request (zmx_last_timing)
   for (size_t d = 1; d < ndev; ++d) {
     const zamd::Timing& a = call->shards[d].timing;
@@ -501,11 +510,7 @@ void EmitChunks(const std::vector<zamd::Chunk>& chunks, const unsigned char* in,
 
 void ResetTiming() {
   zamd::ThreadTiming() = zamd::Timing();
-  double a[8], b;
-  zmx_internal_kernel_stats(a, &b, 1);
-  zmx_internal_seg_stats(a, 1);
-  zmx_internal_match_stats(a, 1);
-  zmx_internal_match5_stats(a, 1);
+  (void)TakeStats();
   g_traffic[0] = g_traffic[1] = g_traffic[2] = 0;
 }
 
@@ -725,29 +730,34 @@ int zmx_last_timing(double* out8) {
   out8[3] = t.cost_model;
   out8[4] = t.split;
   out8[5] = t.encode;
-  double k[3];
-  zmx_internal_kernel_stats(k, &out8[7], 0);
-  out8[6] = k[1];
+  const zmx_stats& s = zamd::ThreadStats();
+  out8[6] = s.kernel_seconds[1];
+  out8[7] = s.squeeze_launches;
   return 0;
 }
 
 int zmx_last_kernel_timing(double* out4) {
-  zmx_internal_kernel_stats(out4, &out4[3], 0);
+  const zmx_stats& s = zamd::ThreadStats();
+  for (int i = 0; i < 3; ++i) out4[i] = s.kernel_seconds[i];
+  out4[3] = s.squeeze_launches;
   return 0;
 }
 
 int zmx_last_match_timing(double* out4) {
-  zmx_internal_match_stats(out4, 0);
+  const zmx_stats& s = zamd::ThreadStats();
+  for (int i = 0; i < 4; ++i) out4[i] = s.match[i];
   return 0;
 }
 
 int zmx_last_match_walk(double* out3) {
-  zmx_internal_match5_stats(out3, 0);
+  const zmx_stats& s = zamd::ThreadStats();
+  for (int i = 0; i < 3; ++i) out3[i] = s.match5[i];
   return 0;
 }
 
 int zmx_last_seg_stats(double* out8) {
-  zmx_internal_seg_stats(out8, 0);
+  const zmx_stats& s = zamd::ThreadStats();
+  for (int i = 0; i < 8; ++i) out8[i] = s.seg[i];
   return 0;
 }
 

@@ -21,23 +21,14 @@
 #include "dealing.h"
 #include "symbols.h"
 #include "thread_pool.h"
+#include "zmx_internal.h"
 #include "zopfli_amd.h"
 #include "../device/zmx_probe.h"
-
-extern "C" void zmx_internal_set_error_class(const char* msg, int cls);
-extern "C" int zmx_internal_device(zmx_ctx* ctx);
-// implemented by the device layer: every [p[i], p[i] + nbytes[i]) is plain device memory (else ZMX_ERR_REFUSED)
-extern "C" int zmx_internal_device_pointers(const char* who, size_t n, const void* const* p, const size_t* nbytes);
-// implemented by the device layer: k_probe_counts over n <= 65535 ranges (begin, end) of `bytes`
-extern "C" int zmx_internal_probe_counts(zmx_ctx* ctx, const void* bytes, size_t n, const uint64_t* ranges, uint32_t* counts);
-// implemented by the device layer: a plain allocation of `device` that the caller owns
-extern "C" int zmx_internal_device_alloc(int device, size_t n, void** p);
-extern "C" void zmx_internal_device_free(int device, void* p);
 
 namespace {
 
 int Refuse(const std::string& msg) {
-  zmx_internal_set_error_class(msg.c_str(), ZMX_ERR_REFUSED);
+  zmx_internal_set_error(msg.c_str(), ZMX_ERR_REFUSED);
   return -1;
 }
 
@@ -234,7 +225,7 @@ int CompressBatch(const char* who, const ZopfliOptions* options, ZopfliFormat ou
       if (StageRound(bytes.device, start, part_file[a], part_file[b - 1], round, lo, &stage, &dev) != 0) return -1;
       dev.upload = [&stage](zmx_ctx* ctx, size_t base, size_t nbytes) {
         if (base < stage.lo || nbytes > stage.size - (base - stage.lo)) {
-          zmx_internal_set_error_class("device batch: a shard reaches outside the round's staging buffer", ZMX_ERR_REFUSED);
+          zmx_internal_set_error("device batch: a shard reaches outside the round's staging buffer", ZMX_ERR_REFUSED);
           return -1;
         }
         return zmx_set_input_device(ctx, static_cast<const unsigned char*>(stage.p) + (base - stage.lo), nbytes);
@@ -242,7 +233,7 @@ int CompressBatch(const char* who, const ZopfliOptions* options, ZopfliFormat ou
     }
     const int rc = zamd::RunPartsDealt(*options, 2, cat.get(), round, &chunks, &part_chunks, &hooks, bytes.device ? &dev : nullptr);
     if (rc) {
-      zmx_internal_set_error_class(hooks.error.c_str(), hooks.error_class);
+      zmx_internal_set_error(hooks.error.c_str(), hooks.error_class);
       return -1;
     }
     for (const ShardSums& ss : shard_sums) {

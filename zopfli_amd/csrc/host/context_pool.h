@@ -24,9 +24,8 @@
 
 #include "deal.h"
 #include "host_knobs.h"
+#include "zmx_internal.h"
 #include "zopfli_amd.h"
-
-extern "C" void zmx_internal_set_error(const char* msg);
 
 namespace zamd {
 
@@ -132,7 +131,7 @@ class ContextPool {
       devices_.push_back(std::move(dev));
     }
     if (devices_.empty()) {
-      zmx_internal_set_error("no HIP device to run on");
+      zmx_internal_set_error("no HIP device to run on", ZMX_ERR_DEVICE);
       Die("no usable gfx950 device (there is no CPU fallback)");
     }
     lanes_ = knobs.lanes;

@@ -13,20 +13,14 @@
 #include "dealing.h"
 #include "host_knobs.h"
 #include "symbols.h"
+#include "zmx_internal.h"
 #include "zopfli_amd.h"
 #include "../device/zmx_probe.h"
-
-extern "C" void zmx_internal_set_error_class(const char* msg, int cls);
-extern "C" int zmx_internal_device(zmx_ctx* ctx);
-// implemented by the device layer: [p, p + n) is plain device memory (else ZMX_ERR_REFUSED) of HIP device *device
-extern "C" int zmx_internal_device_pointer(const char* who, const void* p, size_t n, int* device);
-// implemented by the device layer: k_probe_counts over n ranges (begin, end) of `bytes` (null: the resident input)
-extern "C" int zmx_internal_probe_counts(zmx_ctx* ctx, const void* bytes, size_t n, const uint64_t* ranges, uint32_t* counts);
 
 namespace {
 
 int Refuse(const char* msg) {
-  zmx_internal_set_error_class(msg, ZMX_ERR_REFUSED);
+  zmx_internal_set_error(msg, ZMX_ERR_REFUSED);
   return -1;
 }
 
@@ -88,7 +82,7 @@ extern "C" int zmx_compress_device(const ZopfliOptions* options, ZopfliFormat ou
   // (one master block: one shard on one context, whatever its bytes — nothing reads the counts)
   if (insize > zamd::kMasterBlock && ProbeInput(d_in, insize, device, &dev) != 0) return -1;
   if (zamd::CompressFromDevice(options, output_type, &dev, insize, out, outsize) != 0) {
-    zmx_internal_set_error_class(dev.error.c_str(), dev.error_class);
+    zmx_internal_set_error(dev.error.c_str(), dev.error_class);
     return -1;
   }
   return 0;

@@ -19,10 +19,8 @@
 #include <vector>
 
 #include "dist_core.h"
+#include "zmx_internal.h"
 #include "zopfli_amd.h"
-
-extern "C" int zmx_internal_device(zmx_ctx* ctx);
-extern "C" void zmx_internal_set_error(const char* msg);
 
 namespace {
 
@@ -72,7 +70,7 @@ Rccl* LoadRccl() {
 }
 
 int Fail(const std::string& m) {
-  zmx_internal_set_error(m.c_str());
+  zmx_internal_set_error(m.c_str(), ZMX_ERR_DEVICE);
   return -1;
 }
 
@@ -238,7 +236,7 @@ int zmx_dist_gather(zmx_dist* d, const unsigned char* blob, size_t size, unsigne
   t.exchange = RcclExchange;
   t.error = &err;
   const int rc = zamd::GatherBlobs(t, blob, size, gathered, sizes);
-  if (rc != 0 && !err.empty()) zmx_internal_set_error(err.c_str());
+  if (rc != 0 && !err.empty()) zmx_internal_set_error(err.c_str(), ZMX_ERR_DEVICE);
   return rc;
 }
 

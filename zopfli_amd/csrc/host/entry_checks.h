@@ -1,0 +1,72 @@
+// What the zmx_* entries refuse of their arguments before they touch anything: the rules and their texts, as plain
+// functions that the device layer (device/zmx_hip.hip) and the host test library's stand-in for it
+// (tests/hostlib/zmx_oracle_backend.cc) both run.  No HIP, no globals: each function returns the refusal's message —
+// `who`, the entry's name, then ": ", then the text — or an empty string when there is nothing to refuse.  Either side
+// turns a message into its own ZMX_ERR_REFUSED.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "symbols.h"
+
+namespace zamd {
+
+inline std::string Refusal(const char* who, const std::string& text) { return std::string(who) + ": " + text; }
+
+// ---- the tables an entry is handed
+enum TableNeeds {
+  kAnyTables,     // the stores are enough (they survive zmx_tables_trim)
+  kUntrimmed,     // ... the match records and what goes with them
+  kWithDp,        // ... and DP rows, codes, windows and tasks (not zmx_tables_build_matches)
+};
+inline std::string CheckTables(const char* who, bool exist, bool trimmed, bool matches_only, TableNeeds needs) {
+  if (!exist) return Refusal(who, "no tables");
+  if (needs >= kUntrimmed && trimmed) return Refusal(who, "these tables were trimmed to their stores (zmx_tables_trim)");
+  if (needs >= kWithDp && matches_only) return Refusal(who, "these tables hold matches only (zmx_tables_build_matches)");
+  return std::string();
+}
+// zmx_squeeze_run: tables of no block have nothing to run, whatever they were built with
+inline TableNeeds SqueezeRunNeeds(size_t nblocks) { return nblocks == 0 ? kUntrimmed : kWithDp; }
+
+// ---- a block, and symbols [0, nsym) of the store in `slot` of `block`
+inline std::string CheckBlock(const char* who, size_t nblocks, size_t block) {
+  return block < nblocks ? std::string() : Refusal(who, "bad block");
+}
+// capacity(): how many symbols the store can hold from where it begins (asked only of a block and slot that exist)
+template <class Capacity>
+inline std::string CheckStoreRef(const char* who, size_t nblocks, size_t block, int slot, size_t nsym, Capacity capacity) {
+  if (block >= nblocks || (slot != 0 && slot != 1)) return Refusal(who, "bad block or slot");
+  if (nsym > capacity()) return Refusal(who, "nsym exceeds the store");
+  return std::string();
+}
+
+// ---- the length arrays of zmx_trace_length_arrays
+// What the trace kernels cannot bound themselves: a cell h may hold 0 (GetBestLengths never reached it), 1 or a length
+// 3 .. min(h, 258) — a step back from h that stays inside the block, so cell 0 holds 0 alone.
+inline bool PathCell(size_t h, unsigned v) {
+  const size_t longest = h < static_cast<size_t>(kMaxMatch) ? h : static_cast<size_t>(kMaxMatch);
+  return v <= longest && (v <= 1 || v >= static_cast<unsigned>(kMinMatch));
+}
+// bsize(b): the bytes of block b of the tables, which have table_blocks of them
+template <class BlockSize>
+inline std::string CheckLengthArrays(const char* who, size_t table_blocks, BlockSize bsize, size_t nblocks,
+                                     const uint16_t* const* length_arrays, const size_t* entries, const int32_t* slot) {
+  if (nblocks != table_blocks) return Refusal(who, "one length array per block of the tables");
+  for (size_t b = 0; b < nblocks; ++b) {
+    const size_t B = bsize(b);
+    if (slot[b] != 0 && slot[b] != 1) return Refusal(who, "slot must be 0 or 1");
+    if (entries[b] != B + 1) {
+      return Refusal(who, "block " + std::to_string(b) + " has " + std::to_string(B) + " + 1 cells, not " + std::to_string(entries[b]));
+    }
+    for (size_t h = 0; h <= B; ++h) {
+      const unsigned v = length_arrays[b][h];
+      if (!PathCell(h, v)) {
+        return Refusal(who, "block " + std::to_string(b) + ", cell " + std::to_string(h) + " holds " + std::to_string(v) + ": no step of a path");
+      }
+    }
+  }
+  return std::string();
+}
+
+}  // namespace zamd

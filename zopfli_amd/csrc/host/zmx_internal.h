@@ -1,0 +1,75 @@
+// The seam between the host layer (csrc/host/*.cc) and the device layer (csrc/device/zmx_hip.hip) that is no part of
+// the public ABI (include/zopfli_amd.h), declared ONCE.  Host to device: every zmx_internal_* function.  The device
+// layer defines them and includes this header, as every caller does and as the host test library's stand-in for the
+// device layer does (tests/hostlib/zmx_oracle_backend.cc), so a parameter list that changes on one side only does not
+// compile.  Device to host: the statistics, which the host layer owns.
+// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the three
+// functions that tests and tools reach from outside (here and nowhere else).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "zopfli_amd.h"
+
+#define ZMX_INTERNAL_EXPORT __attribute__((visibility("default")))
+
+// Kernel, match and task statistics, summed per calling THREAD since the start of its call.  Only the host layer
+// reads, takes and adds them (api.cc: zmx_last_*, and a call's shard threads hand theirs to the caller's at the join),
+// so it owns them, as it owns zamd::ThreadTiming; the device layer adds to them where it times its kernels.
+struct zmx_stats {
+  double kernel_seconds[3];  // k_wtab + k_badscan, chain kernels (k_dp5_spec + k_dpcheck + k_dp4_fix), k_trace (HIP events)
+  double squeeze_launches;
+  double match5[3];          // k_match5: entries in flight summed over lanes and iterations, wave iterations, positions it walked
+  double match[4];           // match kernel seconds, k_same + k_chain (+ k_levels ...) seconds, table builds, positions matched
+  double seg[8];             // tasks, accepted, re-run: state / level / tie, positions re-run, re-run: values, positions
+};
+namespace zamd {
+zmx_stats& ThreadStats();   // the calling thread's (thread-local: no lock)
+}
+
+extern "C" {
+
+// ---- errors
+// Makes `msg` the calling thread's last error (zmx_last_error) and `cls` its class (zmx_last_error_class, a ZMX_ERR_*).
+void zmx_internal_set_error(const char* msg, int cls);
+
+// ---- a context and its resident input
+// The HIP device the context runs on.
+int zmx_internal_device(zmx_ctx* ctx);
+// The size of the resident input in bytes.
+size_t zmx_internal_input_size(zmx_ctx* ctx);
+// The caller's host copy of the resident input (borrowed until the next zmx_set_input); null when the input came from
+// device memory (zmx_set_input_device).
+const unsigned char* zmx_internal_input_host(zmx_ctx* ctx);
+// Bytes [begin, end) of the resident input, device to host (the bytes of a stored block when the input came from device
+// memory: the host has no copy of its own).  0, or -1 with the error set (ZMX_ERR_REFUSED: a range outside the input).
+int zmx_internal_input_fetch(zmx_ctx* ctx, size_t begin, size_t end, unsigned char* dst);
+// k_probe_counts over n <= 65535 ranges (begin, end) of `bytes` — device memory of the context's device; null: the
+// resident input —, the caller having checked the ranges against it: counts[r][zamd::kProbeCounts].  0, or -1 with the
+// error set.
+int zmx_internal_probe_counts(zmx_ctx* ctx, const void* bytes, size_t n, const uint64_t* ranges, uint32_t* counts);
+// The context's memory pool in numbers (DevicePool::Stats says which); reads only.
+ZMX_INTERNAL_EXPORT void zmx_internal_pool_stats(zmx_ctx* ctx, uint64_t out[8]);
+
+// ---- device memory that is no context's
+// 0 when [p, p + n) is plain device memory, with its HIP device in *device; else -1 with the error set
+// (ZMX_ERR_REFUSED, the message starts with `who`).
+int zmx_internal_device_pointer(const char* who, const void* p, size_t n, int* device);
+// The same for n ranges [p[i], p[i] + nbytes[i]), before anything is done with any of them (zmx_compress_device_batch).
+int zmx_internal_device_pointers(const char* who, size_t n, const void* const* p, const size_t* nbytes);
+// A plain allocation of `device` that its caller owns (the staging buffer of zmx_compress_device_batch: it outlives the
+// context it was filled on, which goes back to the pool while the shards copy from it).  0, or -1 with the error set.
+int zmx_internal_device_alloc(int device, size_t n, void** p);
+// Frees what zmx_internal_device_alloc gave (null: nothing).
+void zmx_internal_device_free(int device, void* p);
+
+// ---- for tests and tools
+// The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
+// (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing); else 0.  For
+// tools/batch_files.py --device.
+ZMX_INTERNAL_EXPORT double zmx_internal_gather_ms(void);
+// Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
+// squeeze run computes them — *wmax, *tiemask —, no device involved.
+ZMX_INTERNAL_EXPORT void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask);
+
+}  // extern "C"
