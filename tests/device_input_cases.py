@@ -63,7 +63,7 @@ def runs_threshold(hits, probes=200):
 
 def tail_run_start(data, instart, inend):
     """Where the run of bytes equal to data[inend - 1] begins — no lower than instart, and no further than 65600 bytes
-    from inend (the walk of PlanReuse, zmx_hip.hip)."""
+    from inend (the walk of PlanReuse, drv_build.h)."""
     r = inend - 1
     while r > instart and inend - r < 65600 and data[r - 1] == data[inend - 1]:
         r -= 1

@@ -88,7 +88,7 @@ def _ref_run_info(cost):
 
 
 def test_chain_acceptance_facts():
-    """zmx_hip.hip RunInfo (what k_dp4_fix's acceptance test knows about a cost model) against exact
+    """drv_squeeze.h RunInfo (what k_dp4_fix's acceptance test knows about a cost model) against exact
     arithmetic: random entropy-like tables never tie; weights built to tie in a chosen binade do."""
     import numpy as np
     from zopfli_amd import api

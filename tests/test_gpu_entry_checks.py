@@ -40,6 +40,7 @@ def _download_batch(t, block, slot, nsym):
     t.ctx._check(fn(t.ctx.handle, t.handle, 1, ctypes.cast(b, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
                     ctypes.cast(k, ctypes.c_void_p), ctypes.cast(pl, ctypes.c_void_p), ctypes.cast(pd, ctypes.c_void_p)),
                  "zmx_store_download_batch")
+    return ll[:int(nsym)], dd[:int(nsym)]
 
 
 def _cost_stores(t, block, slot, nsym):
@@ -153,3 +154,24 @@ def test_trimmed_tables_refuse(gpu_ctx):
 @pytest.mark.gpu
 def test_matches_only_tables_refuse(gpu_ctx):
     matches_only_tables_refuse(gpu_ctx)
+
+
+@pytest.mark.gpu
+def test_store_download_paths_agree(gpu_ctx):
+    """zmx_store_download and zmx_store_download_batch split a store's u32 symbols with one function (UnpackSymbols,
+    drv_stores.h) behind their own copy paths.  8 KiB of class T, one block, the greedy parse in slot 0: both entries
+    return the same litlens and dists, and those are the CPU oracle's greedy store.  Integer equality."""
+    data = generate("T", 8192)
+    gpu_ctx.set_input(data)
+    t = gpu_ctx.build_tables([(0, len(data))])
+    try:
+        nsym = int(t.greedy(0)[0][0])
+        want = ol.OracleTable(data, 0, len(data)).greedy()
+        assert nsym == len(want[0]) > 0
+        one = t.store(0, 0, nsym)
+        many = _download_batch(t, 0, 0, nsym)
+        for got in (one, many):
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+        assert np.array_equal(one[0], many[0]) and np.array_equal(one[1], many[1])
+    finally:
+        t.free()

@@ -1,0 +1,95 @@
+// Driver part: the parity probes — zmx_match_digest (its kernel k_rec_digest: zmx_probe.h), zmx_find_longest_match,
+// zmx_hash_links_download, zmx_length_array_download.  Needs drv_context.h (PoolScope) and drv_tables.h (zmx_tables, the checks).
+#pragma once
+
+extern "C" {
+int zmx_match_digest(zmx_ctx* c, zmx_tables* t, uint64_t* out2) {
+  if (!t || t->trimmed || !t->d_recs) return FailMsg("zmx_match_digest: no match records in these tables");
+  DEVICE_ENTRY(c->device);
+  out2[0] = out2[1] = 0;
+  if (t->nb == 0) return 0;
+  PoolScope tmp(c);
+  unsigned long long* d_out = nullptr;
+  HIPCHK(tmp.AllocT(&d_out, 2, "d_digest"));
+  HIPCHK(hipMemsetAsync(d_out, 0, 2 * sizeof(unsigned long long), c->stream));
+  u64 max_b = 0;
+  for (size_t b = 0; b < t->nb; ++b) max_b = std::max<u64>(max_b, t->bsize[b]);
+  const unsigned gx = static_cast<unsigned>(std::min<u64>(std::max<u64>((max_b + 256 * 8 - 1) / (256 * 8), 1), 2048));
+  hipLaunchKernelGGL(k_rec_digest, dim3(gx, static_cast<unsigned>(t->nb)), dim3(256), 0, c->stream, t->d_blocks, t->d_recs, t->d_pool, d_out);
+  KCHK(c, "k_rec_digest");
+  HIPCHK(hipMemcpyAsync(out2, d_out, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int zmx_find_longest_match(zmx_ctx* c, zmx_tables* t, size_t block, size_t pos, uint16_t* sublen,
+                           uint16_t* distance, uint16_t* length) {
+  if (const int rc = CheckTables("zmx_find_longest_match", t, zamd::kUntrimmed)) return rc;
+  if (const int rc = CheckBlock("zmx_find_longest_match", t, block)) return rc;
+  const BlockDesc& d = t->blocks[block];
+  if (pos < d.instart || pos >= d.inend) return FailMsg("zmx_find_longest_match: pos outside the block");
+  DEVICE_ENTRY(c->device);
+  if (t->probe_recs.empty()) t->probe_recs.resize(t->nb);
+  std::vector<u32>& recs = t->probe_recs[block];
+  if (recs.empty()) {
+    recs.resize(static_cast<size_t>(t->bsize[block]) * 8);
+    HIPCHK(hipMemcpy(recs.data(), t->d_recs + d.pos_off * 8, recs.size() * sizeof(u32), hipMemcpyDeviceToHost));
+  }
+  const u32* r = &recs[(pos - d.instart) * 8];
+  *length = static_cast<uint16_t>(r[0] & 0xffffu);
+  *distance = static_cast<uint16_t>(r[0] >> 16);
+  if (!sublen) return 0;
+  const u32 ncpf = r[1] >> 24;
+  unsigned prev = 2;  // sublen[3..] only; the reference also fills sublen[2] for 2-byte hits, which nobody reads
+  if (ncpf != 0xffu) {
+    const u8* bytes = reinterpret_cast<const u8*>(r) + 8;
+    for (u32 e = 0; e < ncpf; ++e) {
+      const unsigned len = bytes[3 * e] + 3u, dist = bytes[3 * e + 1] | (bytes[3 * e + 2] << 8);
+      for (unsigned l = prev + 1; l <= len; ++l) sublen[l] = static_cast<uint16_t>(dist);
+      prev = len;
+    }
+  } else {
+    if (!t->probe_pool_ready) {
+      u32 used = 0;
+      HIPCHK(hipMemcpy(&used, t->d_counters, sizeof(u32), hipMemcpyDeviceToHost));
+      t->probe_pool.resize(used);
+      if (used) HIPCHK(hipMemcpy(t->probe_pool.data(), t->d_pool, used * sizeof(u32), hipMemcpyDeviceToHost));
+      t->probe_pool_ready = true;
+    }
+    const u32 off = r[2], n = r[3] & 0xffffu;
+    for (u32 e = 0; e < n; ++e) {
+      const u32 x = t->probe_pool[off + e];
+      const unsigned len = x & 0xffffu, dist = x >> 16;
+      for (unsigned l = prev + 1; l <= len; ++l) sublen[l] = static_cast<uint16_t>(dist);
+      prev = len;
+    }
+  }
+  return 0;
+}
+
+int zmx_hash_links_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* same, uint16_t* prev1, uint16_t* prev2) {
+  if (const int rc = CheckTables("zmx_hash_links_download", t, zamd::kUntrimmed)) return rc;
+  if (const int rc = CheckBlock("zmx_hash_links_download", t, block)) return rc;
+  DEVICE_ENTRY(c->device);
+  if (t->links_partial) return FailMsg("zmx_hash_links_download: tables built from a parent hold the hash arrays only near the block ends");
+  const BlockDesc& d = t->blocks[block];
+  const size_t n = static_cast<size_t>(d.inend - d.ws);
+  std::vector<ushort4> lk(n);
+  if (n) HIPCHK(hipMemcpy(lk.data(), t->d_links + d.reg_off, n * sizeof(ushort4), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i) {
+    prev1[i] = lk[i].x;
+    prev2[i] = lk[i].y;
+    same[i] = lk[i].z;
+  }
+  return 0;
+}
+
+int zmx_length_array_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t* out) {
+  if (const int rc = CheckTables("zmx_length_array_download", t, zamd::kUntrimmed)) return rc;
+  if (const int rc = CheckBlock("zmx_length_array_download", t, block)) return rc;
+  DEVICE_ENTRY(c->device);
+  HIPCHK(hipMemcpy(out, t->d_la + t->blocks[block].la_off, (static_cast<size_t>(t->bsize[block]) + 1) * sizeof(u16),
+                   hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // extern "C"

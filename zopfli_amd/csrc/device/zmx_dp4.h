@@ -11,7 +11,7 @@
 //    to every value and changes no comparison: dbl(w + c + D) = dbl(w + c) + D because c and D are
 //    multiples of 2^(e-23), an even multiple of the double ulp 2^(e-52), and fl(x + D) = fl(x) + D
 //    unless x lies exactly half-way between two floats — which depends only on the edge weight w
-//    and e and is excluded per block and binade up front (zmx_hip.hip, tie mask).
+//    and e and is excluded per block and binade up front (RunInfo in drv_squeeze.h, tie mask).
 //  * Coalescence.  The state of the chain at position p (the <= 259 live cells, their values up
 //    to a common shift and the edges that reached them) is the same whether the chain started at 0
 //    or a few hundred positions before p from a single cell: all surviving paths pass through a

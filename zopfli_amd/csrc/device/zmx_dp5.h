@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void k_mkdesc(MkDescParams P) {
 // PATTERNS of the floats:   update <=> bits(cj) + RH < bits(c),   bits(c) <- min(bits(c), bits(cj) + RR)
 // (if bits(cj) + RH < bits(c) then bits(cj) + RR <= bits(c), so the min is the update; otherwise it leaves
 // c alone) — five full-rate 32-bit VALU instructions instead of six double-precision ones.  r is the very
-// integer the tie mask is computed from (RunInfo, zmx_hip.hip); a binade in which a weight can tie is never
+// integer the tie mask is computed from (RunInfo, drv_squeeze.h); a binade in which a weight can tie is never
 // taken.  D5IntTab is the table {RR, RH} of one binade, built by the workgroup from the run's weights;
 // a window takes the integer path only if its 32 source cells lie in that binade and, with 33 times the
 // largest weight on top (a cell can become a source 32 times over), stay below its end.

@@ -1,5 +1,5 @@
-// The ZOPFLI_AMD_* switches of the device layer (zmx_hip.hip), in one place: what each is, how its text is read, and the
-// process-wide instance.  Host only — no HIP here, so that tests/hostlib/knob_print.cc compiles it with plain g++.  The
+// The ZOPFLI_AMD_* switches of the device layer (the driver parts drv_*.h that zmx_hip.hip lists), in one place: what
+// each is, how its text is read, and the process-wide instance.  Host only — no HIP here, so that tests/hostlib/knob_print.cc compiles it with plain g++.  The
 // switches of the host layer (api.cc, deflate.cc, block_split.cc, block_cache.h, thread_pool.h) are host/host_knobs.h.
 #pragma once
 

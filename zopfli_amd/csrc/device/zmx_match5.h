@@ -30,7 +30,7 @@
 //     same candidate as in the reference, and a candidate beyond it is never looked at.
 // Which blocks: k_hits estimates the hits per position the reference's walk would make (sum over 32768-position
 // chunks of the squared val2 class sizes / positions); a block above ZOPFLI_AMD_MATCH_HITS (300) takes this kernel,
-// the others k_match2, side by side on two streams (zmx_hip.hip: BuildTables).
+// the others k_match2, side by side on two streams (drv_build.h: BuildTables).
 // tools/match_skip_model.c is the CPU model of this walk (checked against the oracle's hit-by-hit walk on every
 // position of every class, with the cap and the switch rule binding on classes B, Z and P); the kernels are checked
 // against k_match2 and the oracle in tests/test_gpu_parity.py and tests/test_gpu_match_adversarial.py.

@@ -1,6 +1,6 @@
-// The device memory of one context (zmx_hip.hip): every array it holds on the device, the ones it keeps cached for the
-// next batch, its pinned host buffers, and the red zones of ZOPFLI_AMD_GUARD.  A part of zmx_hip.hip, included after its
-// error helpers (HIPCHK, FailFault) and the device switches (Knobs).  The rules — which cached block serves a request,
+// The device memory of one context (zmx_ctx, drv_context.h): every array it holds on the device, the ones it keeps cached
+// for the next batch, its pinned host buffers, and the red zones of ZOPFLI_AMD_GUARD.  A part of the driver that zmx_hip.hip
+// lists, included after the error helpers (drv_errors.h: HIPCHK, FailFault) and the device switches (Knobs).  The rules — which cached block serves a request,
 // what becomes of a block that is given back — are zmx_pool_rules.h.
 #pragma once
 

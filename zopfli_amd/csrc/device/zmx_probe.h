@@ -2,7 +2,9 @@
 // (zmx_set_input_device, zmx_compress_device):
 //   k_probe_counts  the integer counts behind zamd::MasterBlockCost and zamd::LooksLikeRuns (host/deal.cc) of a list of
 //                   ranges; the doubles come from the counts on the host (zamd::CostFromCounts, zamd::RunsFromCounts)
-//   k_tail_runs     per block, where the run of bytes equal to its last byte begins (PlanReuse, zmx_hip.hip)
+//   k_tail_runs     per block, where the run of bytes equal to its last byte begins (PlanReuse, drv_build.h)
+// and, beside them, the parity probe of whole match tables:
+//   k_rec_digest    two 64-bit sums over the logical content of every match record (zmx_match_digest, drv_probes.h)
 // The rules are __host__ __device__ functions, so a CPU program (tests/hostlib/probe_print.cc) runs the very code of
 // the kernels against the host's own loops in deal.cc; PlanReuse walks a host input with TailRunStart.  This header compiles without HIP; the kernels are there for the device layer only (ZMX_PROBE_KERNELS).
 #ifndef ZMX_PROBE_H_
@@ -86,6 +88,8 @@ inline uint64_t TailRunStart(const unsigned char* in, uint64_t instart, uint64_t
 
 #if defined(ZMX_PROBE_KERNELS)
 
+#include "zmx_kernels.h"   // BlockDesc and the record layout (k_rec_digest)
+
 // Workgroups (x, range): a lane per probe, striding over the range's probes; a wave sums its lanes' counts and adds them
 // to the range's five words (zeroed by the host).  Byte loads: the input may start at any address.
 struct ProbeParams {
@@ -135,6 +139,46 @@ __global__ __launch_bounds__(64) void k_tail_runs(TailRunParams P) {
     }
   }
   if (threadIdx.x == 0) P.r[blockIdx.x] = r;
+}
+
+// Parity probe over WHOLE tables: two 64-bit sums over all positions of a hash of (block, position in the block,
+// length, distance, same, literal, every change point of sublen) — the logical content of the records, whatever
+// the order the pool handed out its entries in.  Two table sets over the same blocks with equal digests hold the
+// same ZopfliFindLongestMatch results (test_match_kernels_agree compares the kernels at sizes no per-position
+// loop reaches).
+__device__ __forceinline__ u64 dg_mix(u64 h, u64 v) {
+  h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 31;
+  return h;
+}
+// (C linkage: the kernel keeps the plain name it has in the resource tables and the profiles)
+extern "C" __global__ __launch_bounds__(256) void k_rec_digest(const BlockDesc* __restrict__ blocks, const u32* __restrict__ recs,
+                                                               const u32* __restrict__ pool, unsigned long long* out) {
+  const BlockDesc bd = blocks[blockIdx.y];
+  const u64 B = bd.inend - bd.instart;
+  u64 s0 = 0, s1 = 0;
+  for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < B; i += (u64)gridDim.x * 256) {
+    const u32* r = recs + (bd.pos_off + i) * 8;
+    u64 h = dg_mix((u64)blockIdx.y * 0x100000001B3ull, i);
+    h = dg_mix(h, r[0]);
+    const u32 d1 = r[1];
+    const u32 ncpf = d1 >> 24;
+    h = dg_mix(h, d1 & 0xffffffu);
+    if (ncpf != 0xffu) {
+      const u8* b = reinterpret_cast<const u8*>(r) + 8;
+      h = dg_mix(h, ncpf);
+      for (u32 e = 0; e < ncpf; ++e) h = dg_mix(h, ((u32)b[3 * e] + 3u) | (((u32)b[3 * e + 1] | ((u32)b[3 * e + 2] << 8)) << 16));
+    } else {
+      const u32 off = r[2], n = r[3] & 0xffffu;
+      h = dg_mix(h, n);
+      for (u32 e = 0; e < n; ++e) h = dg_mix(h, pool[off + e]);
+    }
+    s0 += h;
+    s1 += (h >> 17 | h << 47) * 0x94D049BB133111EBull;
+  }
+  atomicAdd(out, s0);
+  atomicAdd(out + 1, s1);
 }
 
 #endif  // ZMX_PROBE_KERNELS

@@ -1,5 +1,5 @@
 // What the zmx_* entries refuse of their arguments before they touch anything: the rules and their texts, as plain
-// functions that the device layer (device/zmx_hip.hip) and the host test library's stand-in for it
+// functions that the device layer (device/drv_tables.h, a part of zmx_hip.hip) and the host test library's stand-in for it
 // (tests/hostlib/zmx_oracle_backend.cc) both run.  No HIP, no globals: each function returns the refusal's message —
 // `who`, the entry's name, then ": ", then the text — or an empty string when there is nothing to refuse.  Either side
 // turns a message into its own ZMX_ERR_REFUSED.

@@ -1,4 +1,5 @@
-// The seam between the host layer (csrc/host/*.cc) and the device layer (csrc/device/zmx_hip.hip) that is no part of
+// The seam between the host layer (csrc/host/*.cc) and the device layer (csrc/device/zmx_hip.hip, which
+// lists its parts: the definitions are in drv_input.h and drv_squeeze.h) that is no part of
 // the public ABI (include/zopfli_amd.h), declared ONCE.  Host to device: every zmx_internal_* function.  The device
 // layer defines them and includes this header, as every caller does and as the host test library's stand-in for the
 // device layer does (tests/hostlib/zmx_oracle_backend.cc), so a parameter list that changes on one side only does not
