@@ -36,34 +36,21 @@ int zmx_find_longest_match(zmx_ctx* c, zmx_tables* t, size_t block, size_t pos, 
     HIPCHK(hipMemcpy(recs.data(), t->d_recs + d.pos_off * 8, recs.size() * sizeof(u32), hipMemcpyDeviceToHost));
   }
   const u32* r = &recs[(pos - d.instart) * 8];
-  *length = static_cast<uint16_t>(r[0] & 0xffffu);
-  *distance = static_cast<uint16_t>(r[0] >> 16);
+  *length = static_cast<uint16_t>(zamd::RecLength(r[0]));
+  *distance = static_cast<uint16_t>(zamd::RecDist(r[0]));
   if (!sublen) return 0;
-  const u32 ncpf = r[1] >> 24;
-  unsigned prev = 2;  // sublen[3..] only; the reference also fills sublen[2] for 2-byte hits, which nobody reads
-  if (ncpf != 0xffu) {
-    const u8* bytes = reinterpret_cast<const u8*>(r) + 8;
-    for (u32 e = 0; e < ncpf; ++e) {
-      const unsigned len = bytes[3 * e] + 3u, dist = bytes[3 * e + 1] | (bytes[3 * e + 2] << 8);
-      for (unsigned l = prev + 1; l <= len; ++l) sublen[l] = static_cast<uint16_t>(dist);
-      prev = len;
-    }
-  } else {
-    if (!t->probe_pool_ready) {
-      u32 used = 0;
-      HIPCHK(hipMemcpy(&used, t->d_counters, sizeof(u32), hipMemcpyDeviceToHost));
-      t->probe_pool.resize(used);
-      if (used) HIPCHK(hipMemcpy(t->probe_pool.data(), t->d_pool, used * sizeof(u32), hipMemcpyDeviceToHost));
-      t->probe_pool_ready = true;
-    }
-    const u32 off = r[2], n = r[3] & 0xffffu;
-    for (u32 e = 0; e < n; ++e) {
-      const u32 x = t->probe_pool[off + e];
-      const unsigned len = x & 0xffffu, dist = x >> 16;
-      for (unsigned l = prev + 1; l <= len; ++l) sublen[l] = static_cast<uint16_t>(dist);
-      prev = len;
-    }
+  if (zamd::RecIsOverflow(r[1]) && !t->probe_pool_ready) {
+    u32 used = 0;
+    HIPCHK(hipMemcpy(&used, t->d_counters, sizeof(u32), hipMemcpyDeviceToHost));
+    t->probe_pool.resize(used);
+    if (used) HIPCHK(hipMemcpy(t->probe_pool.data(), t->d_pool, used * sizeof(u32), hipMemcpyDeviceToHost));
+    t->probe_pool_ready = true;
   }
+  unsigned prev = 2;  // sublen[3..] only; the reference also fills sublen[2] for 2-byte hits, which nobody reads
+  zamd::RecWalkCps(r, t->probe_pool.data(), [&](u32 len, u32 dist) {
+    for (unsigned l = prev + 1; l <= len; ++l) sublen[l] = static_cast<uint16_t>(dist);
+    prev = len;
+  });
   return 0;
 }
 

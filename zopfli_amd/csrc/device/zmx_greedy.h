@@ -31,7 +31,7 @@ struct GreedySegParams {
 // One visit of the automaton.  Returns the symbols emitted (0..2); i and held are updated.
 // h = record header of position i, hp = header of position i - 1 (the held match).
 __device__ __forceinline__ int gs_score(u32 h) {
-  const u32 leng = h & 0xffffu, dist = h >> 16;
+  const u32 leng = zamd::RecLength(h), dist = zamd::RecDist(h);
   return dist > 1024 ? (int)leng - 1 : (int)leng;      // lz77.c:265-271
 }
 
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_greedy_exits(GreedySegParams P) 
   __shared__ u32 s_h[TS_SEG + 1];   // s_h[x] = header of position lo - 1 + x
   __shared__ u32 s_j[2 * TS_SEG];
   const u32 seg = blockIdx.x;
-  const u32 b = ts_find_block(P.seg_off, P.nb, seg);
+  const u32 b = find_block(P.seg_off, P.nb, seg);
   const BlockDesc bd = P.blocks[b];
   const u32 B = (u32)(bd.inend - bd.instart);
   const u32 lo = (seg - P.seg_off[b]) * TS_SEG;
@@ -63,13 +63,13 @@ __global__ __launch_bounds__(GS_THREADS) void k_greedy_exits(GreedySegParams P) 
     bool held = st & 1;
     u32 cnt = 0;
     const u32 h = s_h[i - lo + 1];
-    const u32 leng = h & 0xffffu;
+    const u32 leng = zamd::RecLength(h);
     const int score = gs_score(h);
     bool done = false;
     if (held) {                                                               // lz77.c:581-607
       held = false;
       const u32 hp = s_h[i - lo];
-      if ((hp & 0xffffu) < 3u) {                 // no match can be held at i - 1: the state is never reached;
+      if (zamd::RecLength(hp) < 3u) {                 // no match can be held at i - 1: the state is never reached;
         s_j[st] = 0x8000u;                       // park it (every live transition moves forward, runs terminate)
         continue;
       }
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_greedy_exits(GreedySegParams P) 
       if (score > gs_score(hp) + 1) {
         if (score >= 3 && leng < ZMX_MAX_MATCH) { held = true; ++i; done = true; }
       } else {
-        i += (hp & 0xffffu) - 1;
+        i += zamd::RecLength(hp) - 1;
         done = true;
       }
     } else if (score >= 3 && leng < ZMX_MAX_MATCH) {                          // lz77.c:608-613
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64) void k_greedy_link(GreedySegParams P) {
 __global__ __launch_bounds__(64) void k_greedy_emit(GreedySegParams P) {
   __shared__ u32 s_hist[320];
   const u32 seg = blockIdx.x;
-  const u32 b = ts_find_block(P.seg_off, P.nb, seg);
+  const u32 b = find_block(P.seg_off, P.nb, seg);
   const BlockDesc bd = P.blocks[b];
   const u32 B = (u32)(bd.inend - bd.instart);
   const u32 lane = threadIdx.x;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(64) void k_greedy_emit(GreedySegParams P) {
     if (avail) {
       const uint2 hp = *reinterpret_cast<const uint2*>(rbase + (u64)(i - 1) * 8);
       prev_h = hp.x;
-      prev_lit = (hp.y >> 16) & 255u;
+      prev_lit = zamd::RecLiteral(hp.y);
       prevscore = gs_score(prev_h);
     }
     // 64 record headers sit in VGPRs (lane l = position wb + l, the next window is prefetched); a
@@ -175,14 +175,14 @@ __global__ __launch_bounds__(64) void k_greedy_emit(GreedySegParams P) {
     while (i < E) {
       const u32 nwin = E - wb < 64u ? E - wb : 64u;
       const u32 d0_v = cur.x;                    // length | dist << 16 of the position of this lane
-      const u32 lit_v = (cur.y >> 16) & 255u;
+      const u32 lit_v = zamd::RecLiteral(cur.y);
       u64 m_lit = 0, m_match = 0;
       u32 carry = 0, carry_sym = 0;              // a symbol for position wb - 1 (held across the window edge)
       int idx = (int)(i - wb);
       int last = idx;
       while (idx < (int)nwin) {
         const u32 h = rdlane_u32(d0_v, (u32)idx);
-        const u32 leng = h & 0xffffu;
+        const u32 leng = zamd::RecLength(h);
         const int score = gs_score(h);
         last = idx;
         if (avail) {                                                          // lz77.c:581-607
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64) void k_greedy_emit(GreedySegParams P) {
             }
           } else {
             if (idx > 0) m_match |= 1ull << (idx - 1); else { carry = 1; carry_sym = prev_h; }
-            idx += (int)(prev_h & 0xffffu) - 1;                               // (i - 1) + prev_length
+            idx += (int)zamd::RecLength(prev_h) - 1;                              // (i - 1) + prev_length
             continue;
           }
         } else if (score >= 3 && leng < ZMX_MAX_MATCH) {                      // lz77.c:608-613

@@ -6,17 +6,15 @@
 //               .x prev1  distance to the previous position with the same 3-byte hash (0 = none)
 //               .y prev2  same for the run-length hash (hash.c:129-135)
 //               .z same   number of following equal bytes inside the block (hash.c:116-126)
-//   recs[]    per block position, 32 bytes = the ZopfliFindLongestMatch result:
-//               d0 = length | dist << 16
-//               d1 = same | literal << 16 | ncp << 24        (ncp 0..8, 0xff = overflow)
-//               24 bytes: 8 change points of sublen, 3 bytes each (len-3, dist lo, dist hi)
-//               overflow: bytes 8..11 = offset into pool[], bytes 12..13 = ncp; pool entries
-//               are len | dist << 16
+//   recs[]    per block position, 32 bytes = the ZopfliFindLongestMatch result, with pool[] for the change points that
+//             do not fit: zmx_record.h defines the layout and every access to it
 //   la[]      length_array of the last squeeze run, u16, blocksize+1 per block
 //   store[]   two slots of LZ77 symbols per block, u32 = litlen | dist << 16
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "zmx_record.h"
 
 typedef unsigned char u8;
 typedef unsigned short u16;
@@ -61,6 +59,16 @@ __device__ __forceinline__ int dev_length_extra_bits(u32 l) {
 // ----------------------------------------------------------------------------
 // wave-level helpers
 // ----------------------------------------------------------------------------
+// The block that owns tile / segment x: the last index i < n with off[i] <= x (off[0] = 0, the offsets never decrease).
+__device__ __forceinline__ u32 find_block(const u32* off, u32 n, u32 x) {
+  u32 lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const u32 mid = (lo + hi) >> 1;
+    if (off[mid] <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // wave64 inclusive scans on the DPP network (row_shr 1/2/4/8, row_bcast 15/31)
 #define ZMX_WAVE_SCAN(NAME, OP, IDENT)                                                   \
   __device__ __forceinline__ u32 NAME(u32 v) {                                           \
@@ -312,6 +320,22 @@ __device__ __forceinline__ u32 lds_u32_unaligned(const u32* w, u32 a) {
   return __builtin_amdgcn_alignbyte(hi, lo, a & 3);
 }
 
+// The pool claim of a record with ncp > 8 change points (k_match2, k_match5): ncp entries of pool[], the first eight
+// from first8(e), the others from the lane's scratch; `off` is where they begin (the record's word 2).  False: the pool
+// is full — counters[1] is raised, the host repeats the build with a larger pool, and the record's words 2 and 3 are zero.
+template <class First8>
+__device__ __forceinline__ bool rec_pool_claim(const MatchParams& P, u32 ncp, const u32* scratch, First8 first8, u32& off) {
+  off = atomicAdd(&P.counters[0], ncp);
+  if (off + ncp <= P.pool_cap) {
+#pragma unroll
+    for (u32 e = 0; e < zamd::kRecInlineCps; ++e) P.pool[off + e] = first8(e);
+    for (u32 e = zamd::kRecInlineCps; e < ncp; ++e) P.pool[off + e] = scratch[e];
+    return true;
+  }
+  atomicOr(&P.counters[1], 1u);
+  return false;
+}
+
 // Match records of a block that lies inside a block of an earlier table: the records of all
 // positions but the last few (see BuildTablesFrom) are the same — copy them.
 struct CopyRecsParams {
@@ -327,28 +351,6 @@ __global__ __launch_bounds__(256) void k_copy_recs(CopyRecsParams P) {
   const uint4* src = P.src + P.src_pos[blockIdx.y] * 2;
   uint4* dst = P.dst + bd.pos_off * 2;
   for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) dst[i] = src[i];
-}
-
-// ----------------------------------------------------------------------------
-// record access helpers shared by greedy / squeeze
-// ----------------------------------------------------------------------------
-// distance for `len` at a record: first change point with cp.len >= len  (= sublen[len])
-__device__ __forceinline__ u32 rec_dist_for(const u32* __restrict__ rec, const u32* __restrict__ pool, u32 len) {
-  const u32 d1 = rec[1];
-  const u32 ncpf = d1 >> 24;
-  if (ncpf != 0xffu) {
-    const u8* b = reinterpret_cast<const u8*>(rec) + 8;
-    for (u32 e = 0; e < ncpf; ++e) {
-      if ((u32)b[3 * e] + 3u >= len) return (u32)b[3 * e + 1] | ((u32)b[3 * e + 2] << 8);
-    }
-    return 0;
-  }
-  const u32 off = rec[2], n = rec[3] & 0xffffu;
-  for (u32 e = 0; e < n; ++e) {
-    const u32 x = pool[off + e];
-    if ((x & 0xffffu) >= len) return x >> 16;
-  }
-  return 0;
 }
 
 __device__ __forceinline__ void hist_add_symbol(u32* hist, u32 litlen, u32 dist) {
@@ -420,17 +422,17 @@ __global__ __launch_bounds__(1024) void k_rowscan(RowScanParams P) {
     u32 kend = 0, sflag = 0;
     if (act) {
       const uint2 h = *reinterpret_cast<const uint2*>(rbase + (u64)jj * 8);
-      const u32 leng = h.x & 0xffffu, same_i = h.y & 0xffffu;
+      const u32 leng = zamd::RecLength(h.x), dist = zamd::RecDist(h.x), same_i = zamd::RecSame(h.y), ncp = zamd::RecCount(h.y);
       // a "run row": one change point, at distance 1 — every match edge of the position is (k, distance 1), k = 3 .. kend
       // (the inside of a run of equal bytes): the chain kernels take its weights from a 258-entry table instead of
       // the row's codes (zmx_dp5.h).  And the literal, so that they need not look at the codes at all.
-      if (leng >= 3 && (h.x >> 16) == 1u && (h.y >> 24) == 1u) sflag |= 2u;
-      sflag |= ((h.y >> 16) & 255u) << 2;
+      if (leng >= 3 && dist == 1u && ncp == 1u) sflag |= 2u;
+      sflag |= zamd::RecLiteral(h.y) << 2;
       kend = leng < B - jj ? leng : B - jj;        // squeeze.c:286
       if (kend < 3) kend = 1;
       // long-run shortcut test (squeeze.c:251-258): i > instart + 259, i + 517 < inend
       if (same_i > 2 * ZMX_MAX_MATCH && jj > ZMX_MAX_MATCH + 1 && jj + 2 * ZMX_MAX_MATCH + 1 < B) {
-        const u32 same_back = rbase[(u64)(jj - ZMX_MAX_MATCH) * 8 + 1] & 0xffffu;
+        const u32 same_back = zamd::RecSame(rbase[(u64)(jj - ZMX_MAX_MATCH) * 8 + 1]);
         sflag |= same_back > ZMX_MAX_MATCH ? 1u : 0u;
       }
     }
@@ -492,12 +494,7 @@ __global__ __launch_bounds__(256) void k_codes(CodeParams P) {
 
   const u32 tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const u32 tile = blockIdx.x;
-  u32 lo = 0, hi = P.nb_total;
-  while (hi - lo > 1) {
-    const u32 mid = (lo + hi) >> 1;
-    if (P.tile_off[mid] <= tile) lo = mid; else hi = mid;
-  }
-  const u32 b = lo;
+  const u32 b = find_block(P.tile_off, P.nb_total, tile);
   const BlockDesc bd = P.blocks[b];
   const u32 B = (u32)(bd.inend - bd.instart);
   const u32 tp0 = (tile - P.tile_off[b]) * MT;
@@ -519,8 +516,8 @@ __global__ __launch_bounds__(256) void k_codes(CodeParams P) {
       rb = *reinterpret_cast<const uint4*>(rbase + (u64)jj * 8 + 4);
       dh = dbase[jj];
     }
-    const u32 lit = (ra.y >> 16) & 255u;
-    const u32 ncpf = ra.y >> 24;
+    const u32 lit = zamd::RecLiteral(ra.y);
+    const u32 ncpf = zamd::RecCount(ra.y);
     const u32 kend = dh.y & 0xffffu;
     const u32 klay = dph_layout_len(dh.y);      // (0: a wide run row, no codes)
     const u32 off = dh.x;                       // block-relative row offset
@@ -529,11 +526,11 @@ __global__ __launch_bounds__(256) void k_codes(CodeParams P) {
 
     wave_lds_sync();  // the previous group's headers are dead
     {
-      const bool ovf = ncpf == 0xffu;
+      const bool ovf = ncpf == zamd::kRecOverflow;
       s_hoff[wid][lane] = (off - off0) | (lit << 16) | ((ovf ? 1u : 0u) << 24);
       if (ovf) {
-        s_hpool[wid][lane][0] = ra.z;
-        s_hpool[wid][lane][1] = ra.w & 0xffffu;
+        s_hpool[wid][lane][0] = zamd::RecPoolOffset(ra.z);
+        s_hpool[wid][lane][1] = zamd::RecPoolCount(ra.w);
         s_hthr[wid][lane][0] = 0xffffffffu;
         s_hthr[wid][lane][1] = 0xffffffffu;
       } else {
@@ -541,12 +538,9 @@ __global__ __launch_bounds__(256) void k_codes(CodeParams P) {
         u32 t0 = 0, t1 = 0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const u32 bit = 24u * e;
-          const u32 lo32 = w[bit >> 5] >> (bit & 31);
-          const u32 v = (bit & 31) > 8 ? (lo32 | (w[(bit >> 5) + 1 > 5 ? 5 : (bit >> 5) + 1] << (32 - (bit & 31)))) : lo32;
-          const u32 thr = (u32)e < ncpf ? (v & 255u) : 255u;
-          if (e < 4) t0 |= thr << (8 * e); else t1 |= thr << (8 * (e - 4));
-          s_hdist[wid][lane][e] = (u16)((v >> 8) & 0xffffu);
+          const u32 v = zamd::RecCpFieldOfWords(w, (u32)e);
+          zamd::RecCpThresholdPut(t0, t1, (u32)e, ncpf, v);
+          s_hdist[wid][lane][e] = (u16)zamd::RecCpDist(v);
         }
         s_hthr[wid][lane][0] = t0;
         s_hthr[wid][lane][1] = t1;
@@ -566,7 +560,7 @@ __global__ __launch_bounds__(256) void k_codes(CodeParams P) {
       wave_lds_sync();
       const u32 rel_q = off_q - off0;
       u32 carry = q + 1;
-      u64 ovf_mask = __ballot(lane >= q && lane < q + n && ncpf == 0xffu);
+      u64 ovf_mask = __ballot(lane >= q && lane < q + n && ncpf == zamd::kRecOverflow);
       for (u32 t0 = 0; t0 < E; t0 += 64) {
         const u32 e = t0 + lane;
         const u32 mk = e < E ? (u32)mark[e] : 0u;
@@ -583,13 +577,8 @@ __global__ __launch_bounds__(256) void k_codes(CodeParams P) {
           } else if (k == 2 || (h >> 24)) {
             code = 0;                                // dead slot (overflow rows are filled below)
           } else {
-            const u32 x = k - 3;
             // first change point with len >= k: thresholds ascending, binary search over 8 bytes
-            const u32 tlo = s_hthr[wid][p][0], thi = s_hthr[wid][p][1];
-            u32 idx = ((tlo >> 24) < x) ? 4u : 0u;
-            u32 half = idx ? thi : tlo;
-            if (((half >> 8) & 255u) < x) { idx += 2; half >>= 16; }
-            if ((half & 255u) < x) idx += 1;
+            const u32 idx = zamd::RecCpThresholdIndex(s_hthr[wid][p][0], s_hthr[wid][p][1], k - 3);
             code = weight_code(k, s_hdist[wid][p][idx]);
           }
           codes[(u64)off_q + e] = (u16)code;
@@ -603,12 +592,8 @@ __global__ __launch_bounds__(256) void k_codes(CodeParams P) {
         const u32 ke = rdlane_u32(kend, p);
         const u32 poff = s_hpool[wid][p][0], pn = s_hpool[wid][p][1];
         for (u32 k = 3 + lane; k <= ke; k += 64) {
-          u32 plo = 0, phi = pn;   // first entry with len >= k (entries ascending in len)
-          while (plo < phi) {
-            const u32 mid = (plo + phi) >> 1;
-            if ((P.pool[poff + mid] & 0xffffu) < k) plo = mid + 1; else phi = mid;
-          }
-          const u32 dist = plo < pn ? P.pool[poff + plo] >> 16 : 1u;
+          const u32 plo = zamd::RecPoolFind(P.pool, poff, pn, k);   // first entry with len >= k
+          const u32 dist = plo < pn ? zamd::RecPoolDist(P.pool[poff + plo]) : 1u;
           codes[(u64)roff_p + k - 1] = (u16)weight_code(k, dist);
         }
       }
@@ -674,12 +659,7 @@ struct BadScanParams {
 
 __global__ __launch_bounds__(256) void k_badscan(BadScanParams P) {
   const u32 tile = blockIdx.x;
-  u32 lo = 0, hi = P.nb_total;
-  while (hi - lo > 1) {
-    const u32 mid = (lo + hi) >> 1;
-    if (P.tile_off[mid] <= tile) lo = mid; else hi = mid;
-  }
-  const u32 b = lo;
+  const u32 b = find_block(P.tile_off, P.nb_total, tile);
   const u32* bad = P.badcodes + (u64)b * 40;
   if (bad[0] == 0) return;
   const BlockDesc bd = P.blocks[b];

@@ -96,12 +96,7 @@ __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match
     if (s_tile >= P.total_tiles) break;
     const u32 tile = P.tile_list ? P.tile_list[s_tile] : s_tile;
 
-    // block of this tile: largest b with tile_off[b] <= tile
-    u32 lo = 0, hi = P.nb;
-    while (hi - lo > 1) {
-      const u32 mid = (lo + hi) >> 1;
-      if (P.tile_off[mid] <= tile) lo = mid; else hi = mid;
-    }
+    const u32 lo = find_block(P.tile_off, P.nb, tile);
     const BlockDesc bd = P.blocks[lo];
     if (P.skip_energy && P.skip_energy[lo] > P.skip_thr * (bd.inend - bd.ws)) continue;   // the skip-walk's block (zmx_match5.h)
     const u64 p0 = bd.instart + (u64)(tile - P.tile_off[lo]) * MT;
@@ -170,10 +165,10 @@ __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match
     u32 hits_left = 0, chain = 1;
     uint2 L = make_uint2(0, 0);    // link record of the candidate
     u32 n_hits = 0, n_iter = 0;
-    // the first 8 change points of sublen (3 bytes each: length - 3, distance) as they will lie in the record:
+    // the first 8 change points of sublen as they will lie in the record (zmx_record.h's three accumulators):
     // built in registers, written with the record in two 16-byte stores (byte stores into HBM as they were
     // found cost 9.2 GB of write traffic for 3.2 GB of records)
-    u64 cw0 = 0, cw1 = 0, cw2 = 0;
+    uint64_t cw0 = 0, cw1 = 0, cw2 = 0;
 
     for (;;) {
       // ---- service: record writes and refills, queued (MATCH_BATCH lanes, or nobody left walking)
@@ -182,32 +177,22 @@ __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match
       if (m_need != 0 && ((u32)__popcll(m_need) >= MATCH_BATCH || m_run == 0)) {
         if (st == M2_PEND) {
           st = M2_IDLE;
+          u32 w[6];
+          zamd::RecCpAccWords(cw0, cw1, cw2, w);
           uint4 r0, r1;
-          r0.x = bestlen | (bestdist << 16);
-          r0.z = (u32)cw0; r0.w = (u32)(cw0 >> 32);
-          r1.x = (u32)cw1; r1.y = (u32)(cw1 >> 32); r1.z = (u32)cw2; r1.w = (u32)(cw2 >> 32);
-          if (ncp <= 8) {
-            r0.y = same_pos | (byte0 << 16) | (ncp << 24);
+          r0.x = zamd::RecWord0(bestlen, bestdist);
+          r0.z = w[0]; r0.w = w[1];
+          r1.x = w[2]; r1.y = w[3]; r1.z = w[4]; r1.w = w[5];
+          if (ncp <= zamd::kRecInlineCps) {
+            r0.y = zamd::RecWord1(same_pos, byte0, ncp);
           } else {
-            r0.y = same_pos | (byte0 << 16) | (0xffu << 24);
-            const u32 off = atomicAdd(&P.counters[0], ncp);
-            if (off + ncp <= P.pool_cap) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                // entry e = bits 24 e .. 24 e + 23 of cw2 : cw1 : cw0
-                const u32 bit = 24u * (u32)e, wi = bit >> 6, sh = bit & 63u;
-                const u64 a = wi == 0 ? cw0 : wi == 1 ? cw1 : cw2, b2 = wi == 0 ? cw1 : cw2;
-                const u32 v = (u32)((sh > 40 ? (a >> sh) | (b2 << (64u - sh)) : a >> sh) & 0xffffffu);
-                P.pool[off + e] = ((v & 255u) + 3u) | ((v >> 8) << 16);
-              }
-              for (u32 e = 8; e < ncp; ++e) P.pool[off + e] = my_scratch[e];
-              r0.z = off;
-              r0.w = ncp;
-            } else {
-              atomicOr(&P.counters[1], 1u);  // host retries with a larger pool
-              r0.z = 0;
-              r0.w = 0;
-            }
+            r0.y = zamd::RecWord1(same_pos, byte0, zamd::kRecOverflow);
+            u32 off;
+            const bool claimed = rec_pool_claim(P, ncp, my_scratch, [&](u32 e) __attribute__((always_inline)) {
+              return zamd::RecCpPoolEntry(zamd::RecCpFieldOfAcc(cw0, cw1, cw2, e));
+            }, off);
+            r0.z = claimed ? off : 0u;
+            r0.w = claimed ? ncp : 0u;
           }
           u32* const rec = rec0 + (u64)(lp - lp0) * 8;
           reinterpret_cast<uint4*>(rec)[0] = r0;
@@ -230,14 +215,14 @@ __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match
             cw0 = 0; cw1 = 0; cw2 = 0;
             bestlen = 1; bestdist = 0; chain = 1; hits_left = ZMX_MAX_CHAIN_HITS;
             if (size_rem < 3) {                      // lz77.c:440-446
-              rec[0] = 0;
-              rec[1] = same_pos | (byte0 << 16);
+              rec[0] = zamd::RecWord0(0, 0);
+              rec[1] = zamd::RecWord1(same_pos, byte0, 0);
             } else {
               limit = size_rem < ZMX_MAX_MATCH ? size_rem : ZMX_MAX_MATCH;  // lz77.c:448-450
               dist = Lp.x & 0xffffu;
               if (dist == 0) {                       // empty chain
-                rec[0] = 1;
-                rec[1] = same_pos | (byte0 << 16);
+                rec[0] = zamd::RecWord0(1, 0);
+                rec[1] = zamd::RecWord1(same_pos, byte0, 0);
               } else {
                 lc = lp - dist;
                 L = lk[li - dist];
@@ -305,16 +290,8 @@ __global__ __launch_bounds__(M2_THREADS, M2_THREADS == 512 ? 8 : 4) void k_match
           if (cur > bestlen) {  // lz77.c:495-505: new change point of sublen
             // (a 2-byte "match" only moves bestlength; sublen[2] is never read)
             if (cur >= 3) {
-              if (ncp < 8) {
-                const u64 v = (u64)((cur - 3u) | (dist << 8));          // 24 bits at bit 24 ncp of cw2 : cw1 : cw0
-                const u32 bit = 24u * ncp, wi = bit >> 6, sh = bit & 63u;
-                const u64 lo = v << sh, hi = sh > 40 ? v >> (64u - sh) : 0ull;
-                cw0 |= wi == 0 ? lo : 0ull;
-                cw1 |= wi == 1 ? lo : wi == 0 ? hi : 0ull;
-                cw2 |= wi == 2 ? lo : wi == 1 ? hi : 0ull;
-              } else if (ncp < SCRATCH_CPS) {
-                my_scratch[ncp] = cur | (dist << 16);
-              }
+              if (ncp < zamd::kRecInlineCps) zamd::RecCpAppend(cw0, cw1, cw2, ncp, zamd::RecCpField(cur, dist));
+              else if (ncp < SCRATCH_CPS) my_scratch[ncp] = zamd::RecPoolEntry(cur, dist);
               ++ncp;
             }
             bestlen = cur;

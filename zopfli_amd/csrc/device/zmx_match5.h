@@ -619,11 +619,7 @@ __global__ __launch_bounds__(M5_THREADS, 4) void k_match5(Match5Params Q) {
     const u32 tile = P.tile_list ? P.tile_list[t_idx] : t_idx;
     const u32 unit = MT >> Q.sub_shift;
 
-    u32 lo = 0, hi = P.nb;
-    while (hi - lo > 1) {
-      const u32 mid = (lo + hi) >> 1;
-      if (P.tile_off[mid] <= tile) lo = mid; else hi = mid;
-    }
+    const u32 lo = find_block(P.tile_off, P.nb, tile);
     const BlockDesc bd = P.blocks[lo];
     if (!m5_block_on(Q.energy, Q.thr, lo, bd.inend - bd.ws)) continue;     // k_match2's block
     const u64 p0 = bd.instart + (u64)(tile - P.tile_off[lo]) * MT + (u64)(q_idx & (sub - 1u)) * unit;
@@ -774,37 +770,26 @@ __global__ __launch_bounds__(M5_THREADS, 4) void k_match5(Match5Params Q) {
       if (m_need != 0 && ((u32)__popcll(m_need) >= M5_BATCH || m_run == 0)) {
         if (st == M5_PEND) {
           st = M5_IDLE;
-          // the record: the first 8 change points, 3 bytes each (length - 3, distance), from the lane's slots
-          u32 v[8];
+          // the record: the first 8 change points as 24-bit fields, from the lane's slots
+          u32 v[8], w[6];
 #pragma unroll
           for (u32 e = 0; e < 8; ++e) {
             const u32 x = s_cp[e * M5_THREADS + tid];
-            v[e] = e < ncp ? (((x & 0xffffu) - 3u) | ((x >> 16) << 8)) : 0u;
+            v[e] = e < ncp ? zamd::RecCpField(zamd::RecPoolLength(x), zamd::RecPoolDist(x)) : 0u;
           }
+          zamd::RecCpPackFields(v, w);
           uint4 r0, r1;
-          r0.x = bestlen | (bestdist << 16);
-          r0.z = v[0] | (v[1] << 24);
-          r0.w = (v[1] >> 8) | (v[2] << 16);
-          r1.x = (v[2] >> 16) | (v[3] << 8);
-          r1.y = v[4] | (v[5] << 24);
-          r1.z = (v[5] >> 8) | (v[6] << 16);
-          r1.w = (v[6] >> 16) | (v[7] << 8);
-          if (ncp <= 8) {
-            r0.y = same_pos | (byte0 << 16) | (ncp << 24);
+          r0.x = zamd::RecWord0(bestlen, bestdist);
+          r0.z = w[0]; r0.w = w[1];
+          r1.x = w[2]; r1.y = w[3]; r1.z = w[4]; r1.w = w[5];
+          if (ncp <= zamd::kRecInlineCps) {
+            r0.y = zamd::RecWord1(same_pos, byte0, ncp);
           } else {
-            r0.y = same_pos | (byte0 << 16) | (0xffu << 24);
-            const u32 off = atomicAdd(&P.counters[0], ncp);
-            if (off + ncp <= P.pool_cap) {
-#pragma unroll
-              for (u32 e = 0; e < 8; ++e) P.pool[off + e] = s_cp[e * M5_THREADS + tid];
-              for (u32 e = 8; e < ncp; ++e) P.pool[off + e] = my_scratch[e];
-              r0.z = off;
-              r0.w = ncp;
-            } else {
-              atomicOr(&P.counters[1], 1u);
-              r0.z = 0;
-              r0.w = 0;
-            }
+            r0.y = zamd::RecWord1(same_pos, byte0, zamd::kRecOverflow);
+            u32 off;
+            const bool claimed = rec_pool_claim(P, ncp, my_scratch, [&](u32 e) __attribute__((always_inline)) { return s_cp[e * M5_THREADS + tid]; }, off);
+            r0.z = claimed ? off : 0u;
+            r0.w = claimed ? ncp : 0u;
           }
           u32* const rec = rec0 + (u64)ti * 8;
           reinterpret_cast<uint4*>(rec)[0] = r0;
@@ -832,14 +817,14 @@ __global__ __launch_bounds__(M5_THREADS, 4) void k_match5(Match5Params Q) {
             //  hops, garbage there, brings it up to 8192: the tests below are signed)
             idx = (Ap.z >> 31) ? 0xC0000000u : 0u;
             if (size_rem < 3) {                      // lz77.c:440-446
-              rec[0] = 0;
-              rec[1] = same_pos | (byte0 << 16);
+              rec[0] = zamd::RecWord0(0, 0);
+              rec[1] = zamd::RecWord1(same_pos, byte0, 0);
             } else {
               limit = size_rem < ZMX_MAX_MATCH ? size_rem : ZMX_MAX_MATCH;  // lz77.c:448-450
               cprev = Ap.x;
               if ((Ap.x & 0xffffu) == 0) {           // empty chain
-                rec[0] = 1;
-                rec[1] = same_pos | (byte0 << 16);
+                rec[0] = zamd::RecWord0(1, 0);
+                rec[1] = zamd::RecWord1(same_pos, byte0, 0);
               } else {
                 plv0 = Ap.w; plv1 = Bp.x; plv2 = Bp.y; plv3 = Bp.z; plv4 = Bp.w;
                 pbyte = P0.x; foff = 0; fmask = 0xffffu;   // bestlength 1: bytes 0 and 1
@@ -971,8 +956,8 @@ __global__ __launch_bounds__(M5_THREADS, 4) void k_match5(Match5Params Q) {
           } else {
             idx += hops;
             if (cur >= 3) {
-              if (ncp < 8) s_cp[ncp * M5_THREADS + tid] = cur | (xd << 16);
-              else if (ncp < SCRATCH_CPS) my_scratch[ncp] = cur | (xd << 16);
+              if (ncp < zamd::kRecInlineCps) s_cp[ncp * M5_THREADS + tid] = zamd::RecPoolEntry(cur, xd);
+              else if (ncp < SCRATCH_CPS) my_scratch[ncp] = zamd::RecPoolEntry(cur, xd);
               ++ncp;
             }
             bestlen = cur;

@@ -162,17 +162,17 @@ extern "C" __global__ __launch_bounds__(256) void k_rec_digest(const BlockDesc* 
     const u32* r = recs + (bd.pos_off + i) * 8;
     u64 h = dg_mix((u64)blockIdx.y * 0x100000001B3ull, i);
     h = dg_mix(h, r[0]);
-    const u32 d1 = r[1];
-    const u32 ncpf = d1 >> 24;
-    h = dg_mix(h, d1 & 0xffffffu);
-    if (ncpf != 0xffu) {
-      const u8* b = reinterpret_cast<const u8*>(r) + 8;
+    h = dg_mix(h, zamd::RecWord1(zamd::RecSame(r[1]), zamd::RecLiteral(r[1]), 0));
+    // (the number of change points in front of them: the walk's two halves)
+    auto mix = [&](u32 len, u32 dist) { h = dg_mix(h, zamd::RecPoolEntry(len, dist)); };
+    const u32 ncpf = zamd::RecCount(r[1]);
+    if (ncpf != zamd::kRecOverflow) {
       h = dg_mix(h, ncpf);
-      for (u32 e = 0; e < ncpf; ++e) h = dg_mix(h, ((u32)b[3 * e] + 3u) | (((u32)b[3 * e + 1] | ((u32)b[3 * e + 2] << 8)) << 16));
+      zamd::RecWalkInlineCps(r, ncpf, mix);
     } else {
-      const u32 off = r[2], n = r[3] & 0xffffu;
+      const u32 off = zamd::RecPoolOffset(r[2]), n = zamd::RecPoolCount(r[3]);
       h = dg_mix(h, n);
-      for (u32 e = 0; e < n; ++e) h = dg_mix(h, pool[off + e]);
+      zamd::RecWalkPoolCps(pool, off, n, mix);
     }
     s0 += h;
     s1 += (h >> 17 | h << 47) * 0x94D049BB133111EBull;

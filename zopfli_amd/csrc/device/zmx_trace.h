@@ -48,15 +48,6 @@ __device__ __forceinline__ void ts_bounds(u32 B, u32 s, u32& lo, u32& hi) {
   lo = hi > TS_SEG ? hi - TS_SEG : 0u;
 }
 
-__device__ __forceinline__ u32 ts_find_block(const u32* seg_off, u32 nb, u32 seg) {
-  u32 lo = 0, hi = nb;
-  while (hi - lo > 1) {
-    const u32 mid = (lo + hi) >> 1;
-    if (seg_off[mid] <= seg) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // Pointer jumping: J[h] = (where a run of steps from cell h ends, how many steps it is).  After
 // TS_ROUNDS rounds of J[h] = J[h] o J[end of J[h]] over all cells every entry is 2^TS_ROUNDS steps
 // per lookup away from its exit, instead of one dependent LDS read per symbol.  Updates are
@@ -67,7 +58,7 @@ __device__ __forceinline__ u32 ts_find_block(const u32* seg_off, u32 nb, u32 seg
 __global__ __launch_bounds__(TS_THREADS) void k_trace_exits(TraceSegParams P) {
   __shared__ u32 s_j[TS_SEG + 1];   // index h - lo: cell code (inside: h' - lo; left: 0x8000 | lo - h') | steps << 16
   const u32 seg = P.seg0 + blockIdx.x;
-  const u32 b = ts_find_block(P.seg_off, P.nb_total, seg);
+  const u32 b = find_block(P.seg_off, P.nb_total, seg);
   const BlockDesc bd = P.blocks[b];
   const u32 B = (u32)(bd.inend - bd.instart);
   u32 lo, hi;
@@ -135,7 +126,7 @@ __global__ __launch_bounds__(64) void k_trace_emit(TraceSegParams P) {
   __shared__ u32 s_hist[320];
 
   const u32 seg = P.seg0 + blockIdx.x;
-  const u32 b = ts_find_block(P.seg_off, P.nb_total, seg);
+  const u32 b = find_block(P.seg_off, P.nb_total, seg);
   const BlockDesc bd = P.blocks[b];
   const u32 B = (u32)(bd.inend - bd.instart);
   const u32 lane = threadIdx.x;
@@ -211,30 +202,24 @@ __global__ __launch_bounds__(64) void k_trace_emit(TraceSegParams P) {
         u32 e;
         const u32 d1 = pend_ra.y;
         if (pend_len >= 3) {
-          const u32 ncpf = d1 >> 24;
+          const u32 ncpf = zamd::RecCount(d1);
           u32 dist = 0;
-          if (ncpf != 0xffu) {
+          if (ncpf != zamd::kRecOverflow) {
             const u32 w[6] = {pend_ra.z, pend_ra.w, pend_rb.x, pend_rb.y, pend_rb.z, pend_rb.w};
 #pragma unroll
             for (int k = 7; k >= 0; --k) {
-              const u32 bit = 24u * k;
-              const u32 lo32 = w[bit >> 5] >> (bit & 31);
-              const u32 v = (bit & 31) > 8 ? (lo32 | (w[(bit >> 5) + 1 > 5 ? 5 : (bit >> 5) + 1] << (32 - (bit & 31)))) : lo32;
-              if ((u32)k < ncpf && (v & 255u) + 3u >= pend_len) dist = (v >> 8) & 0xffffu;
+              const u32 v = zamd::RecCpFieldOfWords(w, (u32)k);
+              if ((u32)k < ncpf && zamd::RecCpLength(v) >= pend_len) dist = zamd::RecCpDist(v);
             }
           } else {
-            const u32 off = pend_ra.z, cnt = pend_ra.w & 0xffffu;
-            u32 plo = 0, phi = cnt;   // first entry with len >= pend_len
-            while (plo < phi) {
-              const u32 mid = (plo + phi) >> 1;
-              if ((P.pool[off + mid] & 0xffffu) < pend_len) plo = mid + 1; else phi = mid;
-            }
-            if (plo < cnt) dist = P.pool[off + plo] >> 16;
+            const u32 off = zamd::RecPoolOffset(pend_ra.z), cnt = zamd::RecPoolCount(pend_ra.w);
+            const u32 plo = zamd::RecPoolFind(P.pool, off, cnt, pend_len);   // first entry with len >= pend_len
+            if (plo < cnt) dist = zamd::RecPoolDist(P.pool[off + plo]);
           }
           e = pend_len | (dist << 16);
           if (dist == 0) atomicOr(&P.flags[1], 4u);
         } else {
-          e = (d1 >> 16) & 255u;
+          e = zamd::RecLiteral(d1);
         }
         sbase[B - 1 - (pend_total + lane)] = e;
         hist_add_symbol(s_hist, e & 0xffffu, e >> 16);
