@@ -331,6 +331,26 @@ int zmx_hash_links_download(zmx_ctx* ctx, zmx_tables* tables, size_t block, uint
 /* Parity probe: length_array[0..blocksize] of the last zmx_squeeze_run. */
 int zmx_length_array_download(zmx_ctx* ctx, zmx_tables* tables, size_t block, uint16_t* out);
 
+/* Parity probe: what the table build lays out once for every squeeze run of one block of B positions (tables with DP
+ * rows, untrimmed).  *block_edges is always set: the slots the block's rows take in codes[].  Every array may be null
+ * (not copied), so a first call with all of them null asks for the size of `codes`:
+ *   dph      2 B words: per position the row's offset in the block's codes, then kend | shortcut << 16 | run row << 17 |
+ *            literal byte << 18 | codeless << 26 (kend = min(length, B - j), 1 below 3: squeeze.c:286; shortcut:
+ *            squeeze.c:251-258; run row = length >= 3, best distance 1, one change point; codeless = a run row of 64
+ *            or more edges, which takes no slots, unless ZOPFLI_AMD_RUN_CODES=1)
+ *   codes    *block_edges weight codes, times 8: slot 0 of a row (1 + byte), slot 1 zero, slot k - 1 for k = 3..kend
+ *            257 + 30 (length symbol of k - 257) + distance symbol of sublen[k]
+ *   winflag, winroff   W = (B + 31) / 32 + 1 words each: the kind and the first row's offset of every 32-position window
+ *            (aligned to the block start), then one closing record: kind 0, where the block's rows end
+ *   wmeta    40 W words: per window, words 0..31 = (row offset - the window's first + 32 - (u + 1)) << 16 | kend of
+ *            position u (0 for the padding of a last partial window), 32 / 33 = where the window's rows start / end,
+ *            34 = the kind; 35..39 are not defined.  Kind: 1 = 32 positions inside the block, none shortcut-flagged,
+ *            kend + u < 64 for all; else 0 = a position outside the block, a shortcut flag or a run row of 64 or more
+ *            edges; else 2 = kend + u < 128 for all; else 3.  | 0x100: a row of the window is codeless.
+ * Nothing is defined for an empty block beyond *block_edges = 0. */
+int zmx_dp_rows_download(zmx_ctx* ctx, zmx_tables* tables, size_t block, uint64_t* block_edges, uint32_t* dph,
+                         uint16_t* codes, uint32_t* winflag, uint32_t* winroff, uint32_t* wmeta);
+
 /* Test entry: TraceBackwards + FollowPath (squeeze.c:317, :338) over length arrays the CALLER hands in — the tail of
  * zmx_squeeze_run (k_trace_exits, k_trace_link, k_trace_emit and the result copy: the same code) without the DP in
  * front of it.  length_arrays[b] has entries[b] = blocksize + 1 cells, as zmx_length_array_download returns them; they

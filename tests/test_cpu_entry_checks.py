@@ -1,6 +1,6 @@
 """The entry checks of test_gpu_entry_checks.py against the host test library: its stand-in for the device layer
 (tests/hostlib/zmx_oracle_backend.cc) runs the device layer's own rules (csrc/host/entry_checks.h) on its own tables,
-for every entry it has (it has no hash links): the same requests are refused, with the same texts and class.  CPU only."""
+for every entry it has (it has no hash links and no DP rows): the same requests are refused, with the same texts and class.  CPU only."""
 import pytest
 
 import oracle_lib as ol
@@ -20,8 +20,8 @@ def test_store_refs_checked_host_backend(host_ctx):
 
 
 def test_trimmed_tables_refuse_host_backend(host_ctx):
-    ec.trimmed_tables_refuse(host_ctx, hash_links=False)
+    ec.trimmed_tables_refuse(host_ctx, hash_links=False, dp_rows=False)
 
 
 def test_matches_only_tables_refuse_host_backend(host_ctx):
-    ec.matches_only_tables_refuse(host_ctx)
+    ec.matches_only_tables_refuse(host_ctx, dp_rows=False)

@@ -105,7 +105,7 @@ def store_refs_checked(ctx):
         t.free()
 
 
-def trimmed_tables_refuse(ctx, hash_links=True):
+def trimmed_tables_refuse(ctx, hash_links=True, dp_rows=True):
     """After zmx_tables_trim the stores are still served; everything that needs more says so."""
     t, counts, model = entry_case(ctx)
     try:
@@ -121,6 +121,8 @@ def trimmed_tables_refuse(ctx, hash_links=True):
         }
         if hash_links:
             calls["zmx_hash_links_download"] = lambda: t.hash_links(0)
+        if dp_rows:
+            calls["zmx_dp_rows_download"] = lambda: t.dp_rows(0)
         for who, call in calls.items():
             _refused(ctx, call, f"{who}: {TRIMMED}")
         for b in range(len(BLOCKS)):
@@ -129,13 +131,26 @@ def trimmed_tables_refuse(ctx, hash_links=True):
         t.free()
 
 
-def matches_only_tables_refuse(ctx):
+def matches_only_tables_refuse(ctx, dp_rows=True):
     t, counts, model = entry_case(ctx, matches_only=True)
     try:
         las = [np.zeros(e - s + 1, dtype=np.uint16) for s, e in BLOCKS]
         _refused(ctx, lambda: t.squeeze_run(*model, [1, 1]), f"zmx_squeeze_run: {MATCHES_ONLY}")
         _refused(ctx, lambda: t.trace(las, [0, 0]), f"zmx_trace_length_arrays: {MATCHES_ONLY}")
+        if dp_rows:
+            _refused(ctx, lambda: t.dp_rows(0), f"zmx_dp_rows_download: {MATCHES_ONLY}")
         assert np.array_equal(t.greedy(1)[0], counts[0])
+    finally:
+        t.free()
+
+
+def probe_blocks_checked(ctx):
+    """The probes that name a block alone: block = nb is refused, the last block is served."""
+    t, _, _ = entry_case(ctx)
+    try:
+        nb = len(BLOCKS)
+        _refused(ctx, lambda: t.dp_rows(nb), "zmx_dp_rows_download: bad block")
+        assert len(t.dp_rows(nb - 1)["kend"]) == BLOCKS[-1][1] - BLOCKS[-1][0]
     finally:
         t.free()
 
@@ -154,6 +169,11 @@ def test_trimmed_tables_refuse(gpu_ctx):
 @pytest.mark.gpu
 def test_matches_only_tables_refuse(gpu_ctx):
     matches_only_tables_refuse(gpu_ctx)
+
+
+@pytest.mark.gpu
+def test_probe_blocks_checked(gpu_ctx):
+    probe_blocks_checked(gpu_ctx)
 
 
 @pytest.mark.gpu

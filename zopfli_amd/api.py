@@ -771,3 +771,32 @@ class Tables:
                                                                la.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))),
                         "zmx_length_array_download")
         return la
+
+    def dp_rows(self, block):
+        """zmx_dp_rows_download: the DP row layout of one block as a dict of numpy arrays — "roff" and "flags" (dph's
+        two words per position), "kend", "shortcut", "run_row", "literal", "codeless" (the fields of "flags"),
+        "block_edges" (int), "codes" (uint16[block_edges]), "winflag", "winroff" (uint32[W]) and "wmeta"
+        (uint32[W, 40]), W = (B + 31) // 32 + 1."""
+        import numpy as np
+        fn = self.ctx.lib.zmx_dp_rows_download
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)] + [ctypes.c_void_p] * 5
+        edges = ctypes.c_uint64(0)
+        # (the sizes first; a block or tables that the entry refuses are refused here)
+        self.ctx._check(fn(self.ctx.handle, self.handle, block, ctypes.byref(edges), None, None, None, None, None),
+                        "zmx_dp_rows_download")
+        s, e = self.blocks[block]
+        B = e - s
+        W = (B + 31) // 32 + 1
+        dph = np.zeros((max(B, 1), 2), dtype=np.uint32)
+        codes = np.zeros(max(edges.value, 1), dtype=np.uint16)
+        winflag = np.zeros(W, dtype=np.uint32)
+        winroff = np.zeros(W, dtype=np.uint32)
+        wmeta = np.zeros((W, 40), dtype=np.uint32)
+        self.ctx._check(fn(self.ctx.handle, self.handle, block, ctypes.byref(edges), dph.ctypes.data, codes.ctypes.data,
+                           winflag.ctypes.data, winroff.ctypes.data, wmeta.ctypes.data), "zmx_dp_rows_download")
+        flags = dph[:B, 1].copy()
+        return {"roff": dph[:B, 0].copy(), "flags": flags, "kend": flags & 0xffff, "shortcut": (flags >> 16) & 1,
+                "run_row": (flags >> 17) & 1, "literal": (flags >> 18) & 0xff, "codeless": (flags >> 26) & 1,
+                "block_edges": int(edges.value), "codes": codes[:edges.value], "winflag": winflag, "winroff": winroff,
+                "wmeta": wmeta}

@@ -1,5 +1,5 @@
 // Driver part: the parity probes — zmx_match_digest (its kernel k_rec_digest: zmx_probe.h), zmx_find_longest_match,
-// zmx_hash_links_download, zmx_length_array_download.  Needs drv_context.h (PoolScope) and drv_tables.h (zmx_tables, the checks).
+// zmx_hash_links_download, zmx_length_array_download, zmx_dp_rows_download.  Needs drv_context.h (PoolScope) and drv_tables.h (zmx_tables, the checks).
 #pragma once
 
 extern "C" {
@@ -77,6 +77,27 @@ int zmx_length_array_download(zmx_ctx* c, zmx_tables* t, size_t block, uint16_t*
   DEVICE_ENTRY(c->device);
   HIPCHK(hipMemcpy(out, t->d_la + t->blocks[block].la_off, (static_cast<size_t>(t->bsize[block]) + 1) * sizeof(u16),
                    hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int zmx_dp_rows_download(zmx_ctx* c, zmx_tables* t, size_t block, uint64_t* block_edges, uint32_t* dph, uint16_t* codes,
+                         uint32_t* winflag, uint32_t* winroff, uint32_t* wmeta) {
+  if (const int rc = CheckTables("zmx_dp_rows_download", t, zamd::kWithDp)) return rc;
+  if (const int rc = CheckBlock("zmx_dp_rows_download", t, block)) return rc;
+  DEVICE_ENTRY(c->device);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const BlockDesc& d = t->blocks[block];
+  const size_t B = t->bsize[block];
+  u64 edges = 0, code_base = 0;
+  HIPCHK(hipMemcpy(&edges, t->d_block_edges + block, sizeof(u64), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&code_base, t->d_code_base + block, sizeof(u64), hipMemcpyDeviceToHost));
+  *block_edges = edges;
+  if (dph && B) HIPCHK(hipMemcpy(dph, t->d_dph + d.pos_off, B * sizeof(uint2), hipMemcpyDeviceToHost));
+  if (codes && edges) HIPCHK(hipMemcpy(codes, t->d_codes + code_base, edges * sizeof(u16), hipMemcpyDeviceToHost));
+  const size_t w0 = t->win_off[block], nw = t->win_off[block + 1] - w0;
+  if (winflag) HIPCHK(hipMemcpy(winflag, t->d_winflag + w0, nw * sizeof(u32), hipMemcpyDeviceToHost));
+  if (winroff) HIPCHK(hipMemcpy(winroff, t->d_winroff + w0, nw * sizeof(u32), hipMemcpyDeviceToHost));
+  if (wmeta) HIPCHK(hipMemcpy(wmeta, t->d_wmeta + w0 * D5_WM, nw * D5_WM * sizeof(u32), hipMemcpyDeviceToHost));
   return 0;
 }
 }  // extern "C"

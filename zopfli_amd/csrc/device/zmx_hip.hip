@@ -53,4 +53,4 @@
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
 #include "drv_png.h"         // the two PNG filter entries
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries
-#include "drv_probes.h"      // the parity probes: digest, longest match, hash links, length array
+#include "drv_probes.h"      // the parity probes: digest, longest match, hash links, length array, DP rows
