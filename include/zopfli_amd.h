@@ -269,6 +269,41 @@ typedef struct zmx_enc_job {
 int zmx_encode_blocks(zmx_ctx* ctx, zmx_tables* tables, size_t njobs, const zmx_enc_job* jobs,
                       const uint32_t* codes, unsigned char* const* out);
 
+/* The same bit writer — the same jobs and codes, the same three kernels, the same check of `nbits` — whose bits stay in
+ * device memory: *bits owns one allocation of the context that outlives the call (zmx_bits_free gives it back, on the
+ * same context, once nothing reads it any more); nothing is copied to the host but the flag of the check.
+ * zmx_bits_job: job `job`'s bit string — *d_bits is 8-byte aligned device memory, the symbols are bits
+ * [*bit_start, *bit_start + *nbits) of it, deflate's bit order; bits [0, *bit_start), where the block's header and tree
+ * go, are zero (in zmx_bitjoin_device the header is a piece of its own).  njobs = 0 gives an empty set. */
+typedef struct zmx_bits zmx_bits;
+int zmx_encode_blocks_device(zmx_ctx* ctx, zmx_tables* tables, size_t njobs, const zmx_enc_job* jobs,
+                             const uint32_t* codes, zmx_bits** bits);
+size_t zmx_bits_jobs(const zmx_bits* bits);
+int zmx_bits_job(const zmx_bits* bits, size_t job, const void** d_bits, uint64_t* bit_start, uint64_t* nbits);
+void zmx_bits_free(zmx_ctx* ctx, zmx_bits* bits);
+
+/* A bit-granular gather: n bit strings of device memory joined into the bit string at d_dst in one launch (k_bitjoin,
+ * device/zmx_bitjoin.h: at most 2048 workgroups whatever n and the total).  Bit k of a string at p is
+ * (p[k / 8] >> (k % 8)) & 1, deflate's order.  Piece i is bits [src_bit, src_bit + nbits) of the string at src and
+ * becomes bits [dst_bit, dst_bit + nbits) of the destination.  The pieces are sorted by dst_bit and none, an empty one
+ * included, begins before the one in front of it ends; total_bits is at least the last piece's end.
+ * Every byte of d_dst[0, (total_bits + 7) / 8) is written exactly once, whole; bits that no piece covers — gaps, the tail
+ * of the last byte — are 0; no byte beyond is written, and the destination need not be zeroed first.  Nothing is read
+ * but the aligned 4-byte words that hold a bit of a piece.  d_dst and every src may have any byte alignment.
+ * Refused on the host before any launch (ZMX_ERR_REFUSED; where a piece is at fault the message names it, "piece i"):
+ * a null pointer with bits, host or managed memory, a range that leaves its allocation, a destination that overlaps a
+ * source or is not memory of the context's device, a source on another device, pieces that are unsorted or overlap, a
+ * bit count of 2^60 or more, total_bits below the last piece's end or above 8 * dst_capacity.  total_bits = 0 returns 0
+ * and launches nothing.  Synchronous.  (Timed while kernel timing is on, as zmx_gather_device is.) */
+typedef struct zmx_bit_piece {
+  const void* src;
+  uint64_t src_bit;
+  uint64_t nbits;
+  uint64_t dst_bit;
+} zmx_bit_piece;
+int zmx_bitjoin_device(zmx_ctx* ctx, size_t n, const zmx_bit_piece* pieces, uint64_t total_bits, void* d_dst,
+                       size_t dst_capacity);
+
 /* CRC-32 (gzip_container.c:75, the value ZopfliGzipCompress writes at :107-110) or Adler-32
  * (zlib_container.c:29, written at :71-74) of bytes [begin, end) of the resident input
  * (zmx_set_input), computed on the device; f-2 of SURVEY 8.  `value` is the finished checksum of
@@ -430,6 +465,29 @@ int zmx_compress_device(const ZopfliOptions* options, ZopfliFormat output_type, 
 int zmx_compress_device_batch(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
                               const void* const* d_in, const size_t* insize, unsigned char** out, size_t* outsize);
 
+/* zmx_compress_device whose OUTPUT stays in device memory as well: afterwards d_out[0, *outsize) holds the bytes that
+ * ZopfliCompress(options, output_type, the same bytes on the host, ...) gives from an empty output, byte for byte.  The
+ * stream never visits the host: the blocks' symbols' bits stay where the device's bit writer put them, stored blocks'
+ * bytes are read from d_in, and one launch (zmx_bitjoin_device) joins them with what the host still makes — the
+ * container's header and trailer, every block's header and tree, LEN / NLEN of stored pieces, and the whole of a block
+ * the device could not write (the second split attempt moved its ends, or ZOPFLI_AMD_DEVICE_ENCODE=0) — uploaded in one
+ * small buffer.  What still crosses the bus upward: the parse's histograms and, with block splitting, the symbols the
+ * host's split search reads, as for every entry; no byte of the stream.
+ * d_in is checked as zmx_compress_device checks it, d_out[0, capacity) the same way; d_out may not overlap d_in and lies
+ * on the same device (ZMX_ERR_REFUSED before anything runs).  The stream's size is known on the host before the join: if
+ * it exceeds `capacity` the call fails with ZMX_ERR_REFUSED, *outsize = the size needed, and nothing is written to d_out.
+ * Any failure leaves d_out unwritten, and *outsize means something in the capacity case only.  zmx_compress_bound(format,
+ * insize) is a capacity that always does for blocksplittingmax 1 .. 64 (ZopfliInitOptions: 15; the derivation is in
+ * zopfli_amd/csrc/host/device_output_plan.h).  Synchronous; the caller synchronises the stream that produced d_in.
+ * Limits: a call of more than one round — ZOPFLI_AMD_ROUND_PARTS master blocks, 2000 by default: 2 GB — is refused
+ * (rounds are not joined on the device); the call is dealt over the contexts of the ONE device that holds d_out,
+ * whatever ZOPFLI_AMD_DEVICES names, and that device must be one of the library's; d_in lies on that device too (the
+ * join reads stored blocks' bytes from it); options->verbose prints nothing about the blocks (the reference's lines are
+ * made where the host merges a stream, which this entry never does). */
+int zmx_compress_device_to_device(const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in, size_t insize,
+                                  void* d_out, size_t capacity, size_t* outsize);
+size_t zmx_compress_bound(ZopfliFormat output_type, size_t insize);
+
 /* -------- whole-stream entry points on a resident input (bench, multi-GPU) */
 
 /* ZopfliDeflate (deflate.c:908) of bytes [instart, inend) of the resident input,
@@ -512,6 +570,12 @@ int zmx_last_host_timing(double* out2);
  * [1] device to device [2] device to host.  (A shard's upload includes the 32 KiB window before its first block;
  * zmx_compress_device_batch: [1] counts the gather into the staging buffer and the shards' copies from it.) */
 int zmx_last_input_traffic(double* out3);
+
+/* Where the last call's stream went: [0] its bytes device to host (for the Zopfli* entries and zmx_compress_device: the
+ * whole stream, the other three 0) [1] its bytes host to device — the literals buffer of zmx_compress_device_to_device,
+ * blocks the host wrote included — [2] blocks whose symbols' bits never left the device [3] blocks the host wrote and
+ * uploaded. */
+int zmx_last_output_traffic(double* out4);
 
 /* Match-table builds since the last Zopfli* / zmx_deflate_range call started (HIP events):
  * [0] seconds in the match kernel (k_match2 / k_match5) [1] seconds in k_same +

@@ -254,6 +254,59 @@ def compress_device_batch(srcs, fmt=FORMAT_GZIP, options=None, lib=None):
     return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
 
 
+class CapacityError(RuntimeError):
+    """compress_device_out: the stream does not fit the destination; `needed` is its size in bytes."""
+
+    def __init__(self, message, needed):
+        super().__init__(message)
+        self.needed = needed
+
+
+def compress_device_out(src, dst, fmt=FORMAT_GZIP, options=None, lib=None):
+    """zmx_compress_device_to_device: ZopfliCompress of bytes in device memory into device memory.  `src` is a tensor or
+    an (integer device pointer, nbytes) pair, as compress_device takes them; `dst` a contiguous tensor or an (integer
+    device pointer, capacity) pair on the same device.  Returns the stream's size: its bytes are dst[0, size).  Raises
+    ValueError for a non-contiguous tensor, CapacityError (with the size needed, nothing written) when the stream does not
+    fit, RuntimeError with the library's message when the library refuses a pointer or fails."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    ptr, size = _device_range(int(src[0]), src[1]) if isinstance(src, (tuple, list)) else _device_range(src, None)
+    out, capacity = _device_range(int(dst[0]), dst[1]) if isinstance(dst, (tuple, list)) else _device_range(dst, None)
+    outsize = ctypes.c_size_t(0)
+    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
+    fn = lib.zmx_compress_device_to_device
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), fmt, ptr, size, out, capacity, ctypes.byref(outsize)) != 0:
+        message = "zmx_compress_device_to_device: " + (lib.zmx_last_error() or b"").decode()
+        if outsize.value > capacity:
+            raise CapacityError(message, int(outsize.value))
+        raise RuntimeError(message)
+    return int(outsize.value)
+
+
+def compress_bound(nbytes, fmt=FORMAT_GZIP, lib=None):
+    """zmx_compress_bound: a destination capacity that does for any input of `nbytes` bytes."""
+    lib = lib or library()
+    fn = lib.zmx_compress_bound
+    fn.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    fn.restype = ctypes.c_size_t
+    return int(fn(fmt, nbytes))
+
+
+def last_output_traffic(lib=None):
+    """zmx_last_output_traffic: of this thread's last call, the stream's bytes device to host, its bytes host to device,
+    the blocks whose symbols' bits never left the device, the blocks the host wrote and uploaded."""
+    lib = lib or library()
+    t = (ctypes.c_double * 4)()
+    fn = lib.zmx_last_output_traffic
+    fn.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    fn.restype = ctypes.c_int
+    fn(t)
+    return [float(v) for v in t]
+
+
 def last_input_traffic(lib=None):
     """zmx_last_input_traffic: input bytes of this thread's last call that went host to device, device to device,
     device to host."""
@@ -389,6 +442,22 @@ class Context:
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes), dst),
                     "zmx_gather_device")
+
+    def bitjoin_device(self, pieces, total_bits, dst, capacity=None):
+        """zmx_bitjoin_device: pieces = [(src pointer, src_bit, nbits, dst_bit)] — bits [src_bit, src_bit + nbits) of the
+        bit string at the integer device pointer become bits [dst_bit, dst_bit + nbits) of the one at `dst`, a tensor or
+        an integer pointer with `capacity` bytes, memory of this context's device; bits that no piece covers are 0."""
+        class Piece(ctypes.Structure):
+            _fields_ = [("src", ctypes.c_void_p), ("src_bit", ctypes.c_uint64), ("nbits", ctypes.c_uint64),
+                        ("dst_bit", ctypes.c_uint64)]
+        n = len(pieces)
+        arr = (Piece * max(n, 1))(*[Piece(int(p[0]) if p[0] else None, int(p[1]), int(p[2]), int(p[3])) for p in pieces])
+        dst, capacity = _device_range(dst, capacity)
+        fn = self.lib.zmx_bitjoin_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, n, ctypes.cast(arr, ctypes.c_void_p) if n else None, int(total_bits), dst, capacity),
+                    "zmx_bitjoin_device")
 
     def master_block_costs_device(self):
         """zmx_master_block_costs_device: the dealing costs of the resident input's master blocks, counted on the device."""
@@ -624,6 +693,32 @@ class CostStores:
             self.handle = None
 
 
+class DeviceBits:
+    """The bits of one Tables.encode_blocks_device call, in device memory (zmx_bits)."""
+
+    def __init__(self, ctx, handle, njobs):
+        self.ctx, self.handle, self.njobs = ctx, handle, njobs
+
+    def job(self, j):
+        """(device pointer, bit_start, nbits) of job j: its symbols are bits [bit_start, bit_start + nbits) of the string
+        at the pointer; the bits in front of them are zero."""
+        ptr, start, nbits = ctypes.c_void_p(), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        fn = self.ctx.lib.zmx_bits_job
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
+                       ctypes.POINTER(ctypes.c_uint64)]
+        self.ctx._check(fn(self.handle, j, ctypes.byref(ptr), ctypes.byref(start), ctypes.byref(nbits)), "zmx_bits_job")
+        return int(ptr.value or 0), int(start.value), int(nbits.value)
+
+    def free(self):
+        if self.handle:
+            fn = self.ctx.lib.zmx_bits_free
+            fn.restype = None
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            fn(self.ctx.handle, self.handle)
+            self.handle = ctypes.c_void_p()
+
+
 class Tables:
     def __init__(self, ctx, handle, blocks):
         self.ctx, self.handle, self.blocks = ctx, handle, blocks
@@ -733,6 +828,27 @@ class Tables:
         if slack:
             return [bytes(b) for b in bufs]
         return [bytes(b[:(int(j[3]) + int(j[4]) + 7) // 8]) for b, j in zip(bufs, jobs)]
+
+    def encode_blocks_device(self, jobs, codes):
+        """zmx_encode_blocks_device: encode_blocks whose bits stay in device memory.  Returns a DeviceBits: job j's bit
+        string is at the device pointer ptr(j), its symbols from bit bit_start(j) on, nbits(j) of them; free() it on
+        this context when nothing reads it any more."""
+        import numpy as np
+
+        class Job(ctypes.Structure):
+            _fields_ = [("block", ctypes.c_uint32), ("slot", ctypes.c_int32), ("nsym", ctypes.c_uint32),
+                        ("bit_start", ctypes.c_uint32), ("nbits", ctypes.c_uint64)]
+        n = len(jobs)
+        arr = (Job * max(n, 1))(*[Job(*map(int, j)) for j in jobs])
+        codes = np.ascontiguousarray(codes, dtype=np.uint32).reshape(n, 320)
+        handle = ctypes.c_void_p()
+        fn = self.ctx.lib.zmx_encode_blocks_device
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.POINTER(ctypes.c_void_p)]
+        self.ctx._check(fn(self.ctx.handle, self.handle, n, ctypes.cast(arr, ctypes.c_void_p),
+                           codes.ctypes.data_as(ctypes.c_void_p), ctypes.byref(handle)), "zmx_encode_blocks_device")
+        return DeviceBits(self.ctx, handle, n)
 
     def find_longest_match(self, block, pos):
         import numpy as np

@@ -33,6 +33,8 @@
 #include "zmx_probe.h"       // probe counts, tail runs, the record digest
 #define ZMX_GATHER_KERNELS
 #include "zmx_gather.h"      // many device buffers end to end
+#define ZMX_BITJOIN_KERNELS
+#include "zmx_bitjoin.h"     // many bit strings joined into one
 #include "zmx_knobs.h"       // the ZOPFLI_AMD_* switches
 #include "zopfli_amd.h"
 #include "../host/deal.h"
@@ -50,6 +52,7 @@
 #include "drv_build.h"       // BuildTables phase by phase and the three build entries
 #include "drv_squeeze.h"     // the greedy pass, RunInfo, the squeeze run, the trace test entry
 #include "drv_stores.h"      // store download, verify, encode
+#include "drv_bitjoin.h"     // output that stays on the device: the bit join, the bit writer without the way down
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
 #include "drv_png.h"         // the two PNG filter entries
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries

@@ -98,6 +98,9 @@ double WallMs() {
 // zmx_last_input_traffic: the input bytes of the calling thread's last call that went host to device, device to device,
 // device to host (a call's shard threads hand theirs to the caller's at the join)
 thread_local double g_traffic[3] = {0, 0, 0};
+// zmx_last_output_traffic: the stream's bytes device to host and host to device, the blocks whose symbols' bits stayed on
+// the device and those the host wrote and uploaded
+thread_local double g_out_traffic[4] = {0, 0, 0, 0};
 
 // The stored chunks of an input the host holds no copy of (zmx_set_input_device) take their bytes from the context
 // they were computed on, each its own range only; positions relative to the context's input.
@@ -362,9 +365,16 @@ void RunShard(ShardedCall* call, size_t d, zmx_ctx* ctx, bool retry) {
     explicit SplitOnDevice(bool on) : was(zamd::g_split_on_device) { zamd::g_split_on_device = on || was; }
     ~SplitOnDevice() { zamd::g_split_on_device = was; }
   } split_on_device(hooks && hooks->split_on_device);
+  const bool device_output = call->dev && call->dev->device_output;
+  struct DeviceOutput {
+    bool was;
+    explicit DeviceOutput(bool on) : was(zamd::g_device_output) { zamd::g_device_output = on; }
+    ~DeviceOutput() { zamd::g_device_output = was; }
+  } device_output_mode(device_output);
   sh.rc = RunParts(ctx, call->options, call->btype, mine, &sh.chunks, call->want_part_chunks ? &sh.part_chunks : nullptr,
                    hooks ? hooks->group_bytes : 0);
-  if (!sh.rc && call->dev && FetchStoredBytes(ctx,&sh.chunks, &sh.traffic[2]) != 0) sh.rc = -1;
+  // (output in device memory: the join reads the stored blocks' bytes where the input lies)
+  if (!sh.rc && call->dev && !device_output && FetchStoredBytes(ctx,&sh.chunks, &sh.traffic[2]) != 0) sh.rc = -1;
   if (sh.rc) { sh.err = zmx_last_error(); sh.err_class = zmx_last_error_class(); }
   if (TraceCall()) {
     std::fprintf(stderr, "  shard %zu (%zu parts): start +%.2f ms, wait for turn %.2f, upload %.2f, checksum %.2f, parts %.2f, end +%.2f\n",
@@ -449,7 +459,12 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
   bool runs = false;
   const size_t per_device = ContextsPerDevice(options, btype, in, dev, parts, &runs);
   const double tr_begin = WallMs();
-  const Lease lease(parts.size(), per_device, /*polite=*/parts.size() < 32, /*small=*/parts.size() < 32);
+  const Lease lease(parts.size(), per_device, /*polite=*/parts.size() < 32, /*small=*/parts.size() < 32, dev ? dev->only_device : -1);
+  if (lease.ctxs.empty()) {   // (only_device alone: every other call waits or dies in the pool)
+    dev->error = "device " + std::to_string(dev->only_device) + " is not one of the library's devices (ZOPFLI_AMD_DEVICE, ZOPFLI_AMD_DEVICES)";
+    dev->error_class = ZMX_ERR_REFUSED;
+    return -1;
+  }
   const double tr_lease = WallMs();
   const InlineHostWork inline_host(parts.size() <= 2 && Pool().InFlight() > 1);
   const size_t ndev = std::min(lease.ctxs.size(), parts.size());
@@ -460,7 +475,10 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
   for (const Shard& sh : call.shards) for (int i = 0; i < 3; ++i) g_traffic[i] += sh.traffic[i];
   const double tr_joined = WallMs();
   const int rc = CollectShards(&call, chunks, part_chunks);
-  if (rc) return rc;
+  if (rc) {
+    for (zamd::Chunk& c : *chunks) c.dev_owner.reset();   // (those of the shards before the failed one: while the contexts are still the call's)
+    return rc;
+  }
   if (TraceCall()) {
     std::fprintf(stderr, "RunPartsSharded: lease %.2f ms, shards done +%.2f, chunks moved +%.2f\n", tr_lease - tr_begin,
                  tr_joined - tr_begin, WallMs() - tr_begin);
@@ -470,6 +488,12 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
     for (auto& sh : call.shards) {
       if (sh.sum_bytes) sum->value = zmx_checksum_combine(sum->kind, sum->value, sh.sum, sh.sum_bytes);
     }
+  }
+  if (dev && dev->finish) {
+    const int frc = dev->finish(lease.ctxs[0], chunks, sum ? sum->value : 0);
+    if (frc) { dev->error = zmx_last_error(); dev->error_class = zmx_last_error_class(); }
+    for (zamd::Chunk& c : *chunks) c.dev_owner.reset();   // (while the contexts are still the call's)
+    return frc;
   }
   return 0;
 }
@@ -505,13 +529,16 @@ int RunPartsSharded(const ZopfliOptions& options, int btype, const unsigned char
 // Appends merged chunks at (*out, *outsize, *bp), reference conventions.
 void EmitChunks(const std::vector<zamd::Chunk>& chunks, const unsigned char* in, unsigned char* bp,
                 unsigned char** out, size_t* outsize, bool verbose = false) {
+  const size_t before = *outsize;
   zamd::MergeChunks(chunks, in, bp, out, outsize, verbose);
+  g_out_traffic[0] += static_cast<double>(*outsize - before);
 }
 
 void ResetTiming() {
   zamd::ThreadTiming() = zamd::Timing();
   (void)TakeStats();
   g_traffic[0] = g_traffic[1] = g_traffic[2] = 0;
+  for (double& t : g_out_traffic) t = 0;
 }
 
 void PushByte(unsigned v, unsigned char** out, size_t* outsize) {
@@ -530,6 +557,11 @@ int RunPartsDealt(const ZopfliOptions& options, int btype, const unsigned char* 
 }
 void ResetCallStats() { ResetTiming(); }
 void AddDeviceTraffic(double bytes) { g_traffic[1] += bytes; }
+void SetOutputTraffic(const double* t4) { for (int i = 0; i < 4; ++i) g_out_traffic[i] = t4[i]; }
+int RunPartsToDevice(const ZopfliOptions& options, const std::vector<Part>& parts, ChecksumRequest* sum, DeviceInput* dev) {
+  std::vector<Chunk> chunks;
+  return RunPartsShardedOnce(options, 2, nullptr, parts, &chunks, sum, nullptr, nullptr, dev);
+}
 bool TraceCallOn() { return TraceCall(); }
 double CallWallMs() { return WallMs(); }
 int OnPooledContext(const std::function<int(zmx_ctx*)>& fn) {
@@ -587,6 +619,7 @@ int DeflateWhole(const ZopfliOptions* options, int btype, int final, const Input
     if (const int rc = RunPartsSharded(*options, btype, in, parts, &chunks, sum, input.dev)) return rc;
     const double tr2 = WallMs();
     if (nprefix) zamd::AppendToOutput(prefix, nprefix, out, outsize);
+    g_out_traffic[0] += static_cast<double>(nprefix);
     EmitChunks(chunks, in, bp, out, outsize, options->verbose != 0);
     const double tr3 = WallMs();
     chunks.clear();
@@ -613,6 +646,7 @@ int GzipFrom(const ZopfliOptions* options, const Input& input, size_t insize, un
   const uint32_t crc = sum.value;
   for (int i = 0; i < 4; ++i) PushByte((crc >> (8 * i)) & 255, out, outsize);
   for (int i = 0; i < 4; ++i) PushByte((insize >> (8 * i)) & 255, out, outsize);
+  g_out_traffic[0] += 8;
   if (options->verbose) {
     std::fprintf(stderr, "Original Size: %d, Gzip: %d, Compression: %f%% Removed\n", static_cast<int>(insize),
                  static_cast<int>(*outsize), 100.0 * static_cast<double>(insize - *outsize) / static_cast<double>(insize));
@@ -631,6 +665,7 @@ int ZlibFrom(const ZopfliOptions* options, const Input& input, size_t insize, un
   if (const int rc = DeflateWhole(options, 2, 1, input, insize, header, 2, &bp, out, outsize, &sum)) return rc;
   const uint32_t checksum = sum.value;
   for (int i = 3; i >= 0; --i) PushByte((checksum >> (8 * i)) & 255, out, outsize);
+  g_out_traffic[0] += 4;
   if (options->verbose) {
     std::fprintf(stderr, "Original Size: %d, Zlib: %d, Compression: %f%% Removed\n", static_cast<int>(insize),
                  static_cast<int>(*outsize), 100.0 * static_cast<double>(insize - *outsize) / static_cast<double>(insize));
@@ -763,6 +798,11 @@ int zmx_last_seg_stats(double* out8) {
 
 int zmx_last_input_traffic(double* out3) {
   for (int i = 0; i < 3; ++i) out3[i] = g_traffic[i];
+  return 0;
+}
+
+int zmx_last_output_traffic(double* out4) {
+  for (int i = 0; i < 4; ++i) out4[i] = g_out_traffic[i];
   return 0;
 }
 

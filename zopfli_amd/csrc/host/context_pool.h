@@ -47,8 +47,10 @@ class ContextPool {
   // ZOPFLI_AMD_SMALL_LANES (16) per device — instead of waiting: sixteen callers with 64 KiB files keep eight streams of
   // small kernels and eight host threads' split searches going, where three contexts left thirteen of them waiting.
   // Which slots that makes is ChooseSlots (deal.h).
+  // `only_device` >= 0: contexts of that HIP device alone (a call whose output stays in that device's memory); empty when
+  // it is not one of the pool's live devices.
   std::vector<zmx_ctx*> Acquire(size_t want, size_t per_device = 1, std::vector<int>* device_of = nullptr,
-                                bool polite = false, bool small = false) {
+                                bool polite = false, bool small = false, int only_device = -1) {
     std::unique_lock<std::mutex> lock(mu_);
     Init();
     ++in_flight_;
@@ -59,7 +61,16 @@ class ContextPool {
     const bool may_create_more = !polite || per_device <= 1 || ++polite_wishes_ >= HostSwitches().deal_after;
     for (;;) {
       if (polite && in_flight_ > 1) per_device = 1;
-      std::vector<Slot*> slots = Take(ChooseSlots(Snapshot(), {want, per_device, small, may_create_more, lanes_, small_lanes_}));
+      std::vector<DeviceSlots> snap = Snapshot();
+      if (only_device >= 0) {
+        bool found = false;
+        for (DeviceSlots& d : snap) {
+          if (d.index != only_device) d.dead = true;
+          found |= !d.dead;
+        }
+        if (!found) return {};   // (the call counts as in flight until its Release, like any other)
+      }
+      std::vector<Slot*> slots = Take(ChooseSlots(snap, {want, per_device, small, may_create_more, lanes_, small_lanes_}));
       CreateMissing(&lock, &slots);
       bool any_alive = false;
       for (auto& dev : devices_) any_alive |= !dev.dead;
@@ -209,8 +220,8 @@ inline void ContextPool::OomHook(int device) { Pool().TrimIdle(device); }
 struct Lease {
   std::vector<int> device_of;      // HIP device index of ctxs[i]
   std::vector<zmx_ctx*> ctxs;
-  explicit Lease(size_t want, size_t per_device = 1, bool polite = false, bool small = false)
-      : ctxs(Pool().Acquire(want, per_device, &device_of, polite, small)) {}
+  explicit Lease(size_t want, size_t per_device = 1, bool polite = false, bool small = false, int only_device = -1)
+      : ctxs(Pool().Acquire(want, per_device, &device_of, polite, small, only_device)) {}
   ~Lease() { Pool().Release(ctxs); }
 };
 

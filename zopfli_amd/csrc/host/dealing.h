@@ -51,6 +51,15 @@ struct DeviceInput {
   std::vector<char> runs;     // LooksLikeRuns of every round of `round_parts` parts (ZOPFLI_AMD_ROUND_PARTS)
   size_t round_parts = 1;
   size_t first_part = 0;      // the part of the request that the round being dealt begins with (set by who runs the rounds)
+  // Output that stays in device memory (zmx_compress_device_to_device, device_output.cc; one round only):
+  // the shards run with g_device_output set and leave the bytes of stored blocks where they are; the call is dealt over the
+  // contexts of `only_device` alone; `finish` runs once the shards are collected, on one of the call's contexts and while
+  // the call still holds them all — the chunks' device bits are theirs — with the container's checksum (0 without one);
+  // non-zero = failure, with zmx_last_error / zmx_last_error_class set.  The chunks let go of their device bits before the
+  // contexts go back to the pool, whatever `finish` did with them.
+  bool device_output = false;
+  int only_device = -1;
+  std::function<int(zmx_ctx* ctx, std::vector<Chunk>* chunks, uint32_t sum)> finish;
   // the failure of the request, when it fails
   std::string error;
   int error_class = ZMX_ERR_NONE;
@@ -67,6 +76,10 @@ struct DeviceInput {
 int CompressFromDevice(const ZopfliOptions* options, ZopfliFormat output_type, DeviceInput* dev, size_t insize,
                        unsigned char** out, size_t* outsize);
 
+// dev->cost and dev->runs (dev->round_parts set) of d_in[0, insize), memory of HIP device `device`: MasterBlockCost of every
+// master block and LooksLikeRuns of every round, from one launch of k_probe_counts on a pooled context (device_input.cc)
+int ProbeDeviceInput(const void* d_in, size_t insize, int device, DeviceInput* dev);
+
 // ZopfliDeflate's master blocks of an input of `insize` bytes (deflate.c:916-923): at least one, even when empty
 std::vector<Part> InputMasterBlocks(size_t insize, bool final);
 // the parts of a request dealt over the pool's contexts (one round: the request's bytes plus a window stay below 2^32);
@@ -78,6 +91,12 @@ int RunPartsDealt(const ZopfliOptions& options, int btype, const unsigned char* 
 void ResetCallStats();
 // input bytes the calling thread's call moved device to device outside its shards (zmx_last_input_traffic [1])
 void AddDeviceTraffic(double bytes);
+// what zmx_last_output_traffic reports of the calling thread's call (four numbers)
+void SetOutputTraffic(const double* t4);
+// ZopfliDeflate (btype 2) of the one round of master blocks `parts` of a device input whose output stays in device memory:
+// dealt as RunPartsDealt deals, `sum` taken as a whole-stream call takes it, then dev->finish; on failure dev->error /
+// error_class are set
+int RunPartsToDevice(const ZopfliOptions& options, const std::vector<Part>& parts, ChecksumRequest* sum, DeviceInput* dev);
 // ZOPFLI_AMD_TRACE_CALL=1, and the clock of its lines
 bool TraceCallOn();
 double CallWallMs();

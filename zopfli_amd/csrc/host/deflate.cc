@@ -597,6 +597,33 @@ void ChooseAndEncodeBlock(DeflateCall* call, size_t p, size_t i) {
   s.chunks[i] = std::move(c);
 }
 
+// ---- 5b'. g_device_output: the same jobs by zmx_encode_blocks_device.  The chunks become kDeviceBits: the header stays
+//           on the host, the symbols' bits where the device wrote them, kept alive by the chunks that point at them.
+// (Weak references from THIS file, as api.cc's to zmx_internal_input_fetch: these host sources also load with the host
+//  test library's stand-in for the device layer, which never sets g_device_output.)
+#pragma weak zmx_encode_blocks_device
+#pragma weak zmx_bits_job
+#pragma weak zmx_bits_free
+int LeaveBitsOnDevice(DeflateCall* call, zmx_tables* tables, const std::vector<zmx_enc_job>& jobs,
+                      const std::vector<uint32_t>& codes, const std::vector<std::pair<size_t, size_t>>& owner) {
+  if (!zmx_encode_blocks_device || !zmx_bits_job || !zmx_bits_free) return -1;
+  zmx_bits* raw = nullptr;
+  const int rc = zmx_encode_blocks_device(call->ctx, tables, jobs.size(), jobs.data(), codes.data(), &raw);
+  if (rc) return rc;
+  zmx_ctx* ctx = call->ctx;
+  std::shared_ptr<void> bits(raw, [ctx](void* p) { zmx_bits_free(ctx, static_cast<zmx_bits*>(p)); });
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    DeviceEncode& e = call->st[owner[i].first].enc[owner[i].second];
+    Chunk& c = call->st[owner[i].first].chunks[e.chunk];
+    if (zmx_bits_job(raw, i, &c.dev_bits, nullptr, nullptr) != 0) return -1;
+    c.kind = Chunk::kDeviceBits;
+    c.bits = std::move(e.header);
+    c.header_bits = e.header_bits;
+    c.dev_owner = bits;
+  }
+  return 0;
+}
+
 // ---- 5b. the device writes the symbols of its blocks behind the headers: the blocks of the optimal batch (`fixed` false)
 //          or those of the fixed-tree re-parses
 int WriteBitsOnDevice(DeflateCall* call, bool fixed) {
@@ -623,6 +650,7 @@ int WriteBitsOnDevice(DeflateCall* call, bool fixed) {
     }
   }
   if (jobs.empty()) return 0;
+  if (g_device_output) return LeaveBitsOnDevice(call, kp.tables, jobs, codes, owner);
   // (the chunks' memory — a third of the input's size in all — is allocated and touched by the workers, not by
   //  this thread: first-touch page faults of 30 MB were most of what this phase took)
   outs.resize(jobs.size());

@@ -10,6 +10,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -19,7 +20,7 @@
 namespace zamd {
 
 struct Chunk {
-  enum Kind : uint8_t { kBits = 0, kStored = 1 };
+  enum Kind : uint8_t { kBits = 0, kStored = 1, kDeviceBits = 2 };
   Kind kind = kBits;
   bool final_block = false;     // kStored only: BFINAL of its last piece
   CVec<uint8_t> bits;           // kBits: packed from bit 0 (memory from the library's block cache)
@@ -29,6 +30,13 @@ struct Chunk {
   // A deserialised chunk does not copy: it points into the blob it came from (which must outlive it).
   const uint8_t* view = nullptr;   // kBits: the packed bits; kStored: the raw bytes
   size_t view_bytes = 0;
+  // kDeviceBits (g_device_output): a compressed block whose symbols' bits stayed where the device wrote them.  The
+  // block is `nbits` bits: [0, header_bits) — the 3 header bits and the tree — in `bits`, on the host; the rest are bits
+  // [header_bits, nbits) of the device string at dev_bits (zmx_bits_job), which dev_owner keeps alive.  Only the device
+  // join reads such a chunk (host/device_output.cc): MergeChunks and SerializeChunks never see one.
+  const void* dev_bits = nullptr;
+  size_t header_bits = 0;
+  std::shared_ptr<void> dev_owner;
 
   // ZopfliOptions::verbose: the reference's stderr lines around this block, produced when the chunk
   // is put into the stream (the byte counts it prints depend on the bit position, deflate.c:719-744).
@@ -53,6 +61,10 @@ struct Part {
 // host's search costs per part, and a thousand 64 KiB parts spend 0.7 s in it against 0.1 s on the device.  Both
 // give the same integers.
 inline thread_local bool g_split_on_device = false;
+
+// Set on a thread whose DeflateParts calls leave their output in device memory (zmx_compress_device_to_device): the
+// blocks the device writes become kDeviceBits chunks — their bits do not come down.
+inline thread_local bool g_device_output = false;
 
 // Compresses each part independently (one ZopfliDeflatePart each); chunks come
 // out in stream order.  Positions refer to the input resident in `ctx`.  `part_chunks` (optional): the

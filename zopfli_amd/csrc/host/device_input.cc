@@ -27,7 +27,9 @@ int Refuse(const char* msg) {
 // MasterBlockCost of every master block and LooksLikeRuns of every round of d_in[0, insize), from one launch of
 // k_probe_counts on a pooled context.  On the pointer's own device the kernel reads the caller's buffer; a context of
 // another device takes a copy first (zmx_set_input_device: the runtime's peer copy).
-int ProbeInput(const void* d_in, size_t insize, int device, zamd::DeviceInput* dev) {
+}  // namespace
+
+int zamd::ProbeDeviceInput(const void* d_in, size_t insize, int device, zamd::DeviceInput* dev) {
   const size_t nblocks = (insize + zamd::kMasterBlock - 1) / zamd::kMasterBlock;
   const size_t nrounds = (nblocks + dev->round_parts - 1) / dev->round_parts;
   std::vector<uint64_t> ranges;
@@ -62,8 +64,6 @@ int ProbeInput(const void* d_in, size_t insize, int device, zamd::DeviceInput* d
   return 0;
 }
 
-}  // namespace
-
 extern "C" int zmx_compress_device(const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in, size_t insize,
                                    unsigned char** out, size_t* outsize) {
   if (!options || !out || !outsize) return Refuse("zmx_compress_device: null argument");
@@ -80,7 +80,7 @@ extern "C" int zmx_compress_device(const ZopfliOptions* options, ZopfliFormat ou
     return zmx_set_input_device(ctx, static_cast<const unsigned char*>(d_in) + base, n);
   };
   // (one master block: one shard on one context, whatever its bytes — nothing reads the counts)
-  if (insize > zamd::kMasterBlock && ProbeInput(d_in, insize, device, &dev) != 0) return -1;
+  if (insize > zamd::kMasterBlock && zamd::ProbeDeviceInput(d_in, insize, device, &dev) != 0) return -1;
   if (zamd::CompressFromDevice(options, output_type, &dev, insize, out, outsize) != 0) {
     zmx_internal_set_error(dev.error.c_str(), dev.error_class);
     return -1;

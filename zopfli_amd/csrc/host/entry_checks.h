@@ -69,4 +69,45 @@ inline std::string CheckLengthArrays(const char* who, size_t table_blocks, Block
   return std::string();
 }
 
+// ---- the piece table of zmx_bitjoin_device (device/zmx_bitjoin.h)
+// What needs no runtime: the table itself.  Piece: zmx_bit_piece { src, src_bit, nbits, dst_bit }.  The pieces are sorted by
+// dst_bit and none — an empty one included — begins before the one in front of it ends; no number reaches 2^60 bits, so no
+// sum of two overflows.
+constexpr uint64_t kBitPieceMaxBits = 1ull << 60;
+template <class Piece>
+inline std::string CheckBitPieces(const char* who, size_t n, const Piece* pieces, uint64_t total_bits, uint64_t dst_capacity) {
+  if (n != 0 && pieces == nullptr) return Refusal(who, "null piece table");
+  uint64_t end = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const Piece& q = pieces[i];
+    const std::string piece = "piece " + std::to_string(i);
+    if (q.src_bit >= kBitPieceMaxBits || q.nbits >= kBitPieceMaxBits || q.dst_bit >= kBitPieceMaxBits) {
+      return Refusal(who, piece + ": a bit count of 2^60 or more");
+    }
+    if (q.nbits != 0 && q.src == nullptr) return Refusal(who, piece + ": null pointer with a non-zero size");
+    if (q.dst_bit < end) {
+      return Refusal(who, piece + (i != 0 && q.dst_bit < pieces[i - 1].dst_bit ? ": the pieces are not sorted by dst_bit"
+                                                                                 : ": it overlaps the piece before it"));
+    }
+    end = q.dst_bit + q.nbits;
+  }
+  if (total_bits < end) return Refusal(who, "total_bits " + std::to_string(total_bits) + " is below the last piece's end, " + std::to_string(end));
+  if (total_bits / 8 > dst_capacity || (total_bits / 8 == dst_capacity && total_bits % 8 != 0)) {
+    return Refusal(who, "total_bits " + std::to_string(total_bits) + " is above 8 * dst_capacity, " + std::to_string(dst_capacity) + " bytes");
+  }
+  return std::string();
+}
+// The bytes that hold a bit of a piece, as addresses [*lo, *hi) (nbits != 0).
+template <class Piece>
+inline void BitPieceBytes(const Piece& q, uintptr_t* lo, uintptr_t* hi) {
+  const uintptr_t at = reinterpret_cast<uintptr_t>(q.src);
+  *lo = at + static_cast<uintptr_t>(q.src_bit / 8);
+  *hi = at + static_cast<uintptr_t>((q.src_bit + q.nbits + 7) / 8);
+}
+// The destination dst[0, dst_bytes) may not share a byte with piece i's [src_lo, src_hi).
+inline std::string CheckBitPieceApart(const char* who, size_t i, uintptr_t dst, uint64_t dst_bytes, uintptr_t src_lo, uintptr_t src_hi) {
+  if (src_lo < dst + dst_bytes && dst < src_hi) return Refusal(who, "piece " + std::to_string(i) + ": the destination overlaps this source");
+  return std::string();
+}
+
 }  // namespace zamd

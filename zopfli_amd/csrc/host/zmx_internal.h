@@ -4,7 +4,7 @@
 // layer defines them and includes this header, as every caller does and as the host test library's stand-in for the
 // device layer does (tests/hostlib/zmx_oracle_backend.cc), so a parameter list that changes on one side only does not
 // compile.  Device to host: the statistics, which the host layer owns.
-// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the three
+// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the four
 // functions that tests and tools reach from outside (here and nowhere else).
 #pragma once
 #include <cstddef>
@@ -64,11 +64,20 @@ int zmx_internal_device_alloc(int device, size_t n, void** p);
 // Frees what zmx_internal_device_alloc gave (null: nothing).
 void zmx_internal_device_free(int device, void* p);
 
+// ---- output that stays in device memory
+// zmx_bitjoin_device(ctx, n, pieces, total_bits, d_dst, dst_capacity) whose pieces with is_literal[i] != 0 come from
+// `literals`: their src holds the byte offset in that buffer, which is uploaded once into memory of the context for the
+// time of the join.  `pieces` is rewritten.  0, or -1 with the error set.
+int zmx_internal_bitjoin_literals(zmx_ctx* ctx, const unsigned char* literals, size_t nliterals, size_t n, zmx_bit_piece* pieces,
+                                  const unsigned char* is_literal, uint64_t total_bits, void* d_dst, size_t dst_capacity);
+
 // ---- for tests and tools
 // The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
 // (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing); else 0.  For
 // tools/batch_files.py --device.
 ZMX_INTERNAL_EXPORT double zmx_internal_gather_ms(void);
+// The same for the calling thread's last zmx_bitjoin_device: k_bitjoin alone.  For tools/device_output.py.
+ZMX_INTERNAL_EXPORT double zmx_internal_bitjoin_ms(void);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
 // squeeze run computes them — *wmax, *tiemask —, no device involved.
 ZMX_INTERNAL_EXPORT void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask);
