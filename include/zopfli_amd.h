@@ -304,6 +304,28 @@ typedef struct zmx_bit_piece {
 int zmx_bitjoin_device(zmx_ctx* ctx, size_t n, const zmx_bit_piece* pieces, uint64_t total_bits, void* d_dst,
                        size_t dst_capacity);
 
+/* zmx_bitjoin_device for ndst destinations in ONE launch (k_bitjoin_many: still at most 2048 workgroups, whatever ndst,
+ * npieces and the total) and one synchronisation.  Destination d is the bit string at dests[d].dst, made from pieces
+ * [first_piece, first_piece + npieces) of the one table `pieces`; a piece's dst_bit counts from its own destination, and
+ * within a destination the pieces follow zmx_bitjoin_device's rules.  The piece ranges of consecutive destinations are
+ * consecutive: dests[0].first_piece = 0, and the last range ends at npieces.  capacity[d] is the room at dests[d].dst in
+ * bytes (a null `capacity`: exactly (total_bits + 7) / 8 each).
+ * Every byte of every dst[0, (total_bits + 7) / 8) is written exactly once and no byte outside those ranges, so
+ * destinations may lie back to back at any byte alignment, two of them inside one 16-byte vector; a destination of
+ * total_bits 0 is not touched.  Refused before any upload or launch (ZMX_ERR_REFUSED; the message names "destination d",
+ * and "piece i" counted within it): a null table with a non-zero count, piece ranges that are not consecutive or leave
+ * npieces, whatever zmx_bitjoin_device refuses of a destination and its pieces, two destinations that share a byte, a
+ * piece whose source bytes share a byte with any destination, memory that is not the context's device's.  ndst = 0, or
+ * no destination with a bit, returns 0 and launches nothing.  Synchronous; timed as zmx_bitjoin_device is. */
+typedef struct zmx_bit_dest {
+  void* dst;
+  uint64_t total_bits;
+  uint64_t first_piece;
+  uint64_t npieces;
+} zmx_bit_dest;
+int zmx_bitjoin_many_device(zmx_ctx* ctx, size_t ndst, const zmx_bit_dest* dests, const size_t* capacity, size_t npieces,
+                            const zmx_bit_piece* pieces);
+
 /* CRC-32 (gzip_container.c:75, the value ZopfliGzipCompress writes at :107-110) or Adler-32
  * (zlib_container.c:29, written at :71-74) of bytes [begin, end) of the resident input
  * (zmx_set_input), computed on the device; f-2 of SURVEY 8.  `value` is the finished checksum of
@@ -487,6 +509,40 @@ int zmx_compress_device_batch(const ZopfliOptions* options, ZopfliFormat output_
 int zmx_compress_device_to_device(const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in, size_t insize,
                                   void* d_out, size_t capacity, size_t* outsize);
 size_t zmx_compress_bound(ZopfliFormat output_type, size_t insize);
+
+/* zmx_compress_device_batch whose streams stay in device memory: afterwards d_out[i][0, outsize[i]) holds what
+ * ZopfliCompress(options, output_type, the bytes of d_in[i] on the host, insize[i], ...) gives from an empty output, byte
+ * for byte, for every i.  Everything up to the blocks' bits runs as in zmx_compress_device_batch — the same gather into
+ * the call's staging buffer, the same counts, dealing and shards — and the n streams are then put together as
+ * zmx_compress_device_to_device puts its one: every stream planned as bit pieces from bit 0 with its own container header
+ * and trailer, the plans' small host-made parts uploaded as ONE buffer, and ONE launch (zmx_bitjoin_many_device) for all
+ * destinations.  Stored blocks' bytes are read from the staging buffer, so the inputs may lie on any device.
+ * All sizes are known on the host before anything is written: if any destination is too small the whole call fails with
+ * ZMX_ERR_REFUSED, outsize[i] = the size needed for EVERY i, and nothing is written anywhere.  After any other failure
+ * every outsize[i] is 0 and nothing was written.  zmx_compress_bound(format, insize[i]) is a capacity that always does.
+ * Refused before anything runs (ZMX_ERR_REFUSED): the inputs as zmx_compress_device_batch refuses them; a destination
+ * that is null with a non-zero capacity, is host or managed memory or leaves its allocation; destinations on different
+ * devices; a destination that shares a byte with another destination or with an input.  n = 0 returns 0.
+ * Limits: a batch of more than one round — 2 GB of inputs — is refused before anything is read; the call runs on the
+ * contexts of the one device that holds the destinations, which must be one of the library's; options->verbose prints
+ * nothing about the blocks.  Synchronous; the caller synchronises the streams that produced the inputs.
+ * zmx_last_output_traffic: [0] 0, [1] the uploaded buffer, [2] / [3] the blocks the device and the host wrote, summed over
+ * the batch; zmx_last_input_traffic as for zmx_compress_device_batch with [2] = 0: no stored byte comes down. */
+int zmx_compress_device_batch_to_device(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
+                                        const void* const* d_in, const size_t* insize, void* const* d_out,
+                                        const size_t* capacity, size_t* outsize);
+/* The same streams packed into one arena: stream i lies at d_arena + outoffset[i], outoffset[0] = 0 and outoffset[i] =
+ * the end of stream i - 1 rounded up to `align`, a power of two from 1 to 4096 (1: back to back).  The bytes between
+ * streams are not written, and two streams may share a 16-byte vector: each byte of a stream is still written exactly
+ * once.  The destinations follow from the plans' sizes; otherwise this is the call above, with the arena for its
+ * destinations in every rule.  An arena that is too small: ZMX_ERR_REFUSED, outsize[] and outoffset[] hold what is needed
+ * (the arena must reach outoffset[n - 1] + outsize[n - 1]), nothing written.  zmx_compress_batch_bound(format, n, insize,
+ * align) is a capacity that always does: every input's zmx_compress_bound rounded up to `align`, summed (0 for n = 0 or
+ * an `align` that is not taken). */
+int zmx_compress_device_batch_packed(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
+                                     const void* const* d_in, const size_t* insize, void* d_arena, size_t capacity,
+                                     size_t align, size_t* outoffset, size_t* outsize);
+size_t zmx_compress_batch_bound(ZopfliFormat output_type, size_t n, const size_t* insize, size_t align);
 
 /* -------- whole-stream entry points on a resident input (bench, multi-GPU) */
 

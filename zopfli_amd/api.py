@@ -255,7 +255,8 @@ def compress_device_batch(srcs, fmt=FORMAT_GZIP, options=None, lib=None):
 
 
 class CapacityError(RuntimeError):
-    """compress_device_out: the stream does not fit the destination; `needed` is its size in bytes."""
+    """compress_device_out: the stream does not fit the destination; `needed` is its size in bytes.
+    compress_device_batch_out, compress_device_batch_packed: `needed` is the list of all streams' sizes."""
 
     def __init__(self, message, needed):
         super().__init__(message)
@@ -284,6 +285,76 @@ def compress_device_out(src, dst, fmt=FORMAT_GZIP, options=None, lib=None):
             raise CapacityError(message, int(outsize.value))
         raise RuntimeError(message)
     return int(outsize.value)
+
+
+def _batch_failure(who, lib, outsizes, n):
+    """The error of a failed device-output batch call: CapacityError with the list of sizes needed when the library
+    reported them (a destination was too small; nothing was written), else RuntimeError."""
+    message = who + ": " + (lib.zmx_last_error() or b"").decode()
+    needed = [int(outsizes[i]) for i in range(n)]
+    if any(needed):
+        return CapacityError(message, needed)
+    return RuntimeError(message)
+
+
+def compress_device_batch_out(srcs, dsts, fmt=FORMAT_GZIP, options=None, lib=None):
+    """zmx_compress_device_batch_to_device: one ZopfliCompress stream per input in device memory, each left in device
+    memory.  `srcs` as compress_device_batch takes them; `dsts` a list of as many contiguous tensors or (integer device
+    pointer, capacity) pairs, all on one device.  Returns the list of the streams' sizes: stream i is dsts[i][0, size).
+    Raises ValueError for a non-contiguous tensor or lists of different lengths, CapacityError (`needed`: the list of
+    sizes, nothing written anywhere) when a stream does not fit, RuntimeError with the library's message when the library
+    refuses a pointer or fails."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    if len(srcs) != len(dsts):
+        raise ValueError(f"{len(srcs)} inputs, but {len(dsts)} destinations")
+    ptrs, sizes = _device_ranges(srcs)
+    outs, capacities = _device_ranges(dsts)
+    n = len(ptrs)
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
+    fn = lib.zmx_compress_device_batch_to_device
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p),
+                   ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                   ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), fmt, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes),
+          (ctypes.c_void_p * max(n, 1))(*outs), (ctypes.c_size_t * max(n, 1))(*capacities), outsizes) != 0:
+        raise _batch_failure("zmx_compress_device_batch_to_device", lib, outsizes, n)
+    return [int(outsizes[i]) for i in range(n)]
+
+
+def compress_device_batch_packed(srcs, arena, align=1, fmt=FORMAT_GZIP, options=None, lib=None):
+    """zmx_compress_device_batch_packed: the same streams packed into `arena`, a contiguous tensor or an (integer device
+    pointer, capacity) pair: stream i begins at the end of stream i - 1 rounded up to `align` (a power of two, 1 .. 4096);
+    the bytes between streams are not written.  Returns (offsets, sizes).  Raises as compress_device_batch_out does; a
+    CapacityError's `needed` is the list of sizes, from which compress_batch_bound or the offsets' rule gives the arena."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    ptrs, sizes = _device_ranges(srcs)
+    out, capacity = _device_range(int(arena[0]), arena[1]) if isinstance(arena, (tuple, list)) else _device_range(arena, None)
+    n = len(ptrs)
+    offsets = (ctypes.c_size_t * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    fn = lib.zmx_compress_device_batch_packed
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p),
+                   ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                   ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), fmt, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes),
+          out, capacity, int(align), offsets, outsizes) != 0:
+        raise _batch_failure("zmx_compress_device_batch_packed", lib, outsizes, n)
+    return [int(offsets[i]) for i in range(n)], [int(outsizes[i]) for i in range(n)]
+
+
+def compress_batch_bound(sizes, fmt=FORMAT_GZIP, align=1, lib=None):
+    """zmx_compress_batch_bound: an arena capacity that does for compress_device_batch_packed of inputs of these sizes."""
+    lib = lib or library()
+    fn = lib.zmx_compress_batch_bound
+    fn.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t]
+    fn.restype = ctypes.c_size_t
+    n = len(sizes)
+    return int(fn(fmt, n, (ctypes.c_size_t * max(n, 1))(*[int(s) for s in sizes]), int(align)))
 
 
 def compress_bound(nbytes, fmt=FORMAT_GZIP, lib=None):
@@ -458,6 +529,29 @@ class Context:
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, n, ctypes.cast(arr, ctypes.c_void_p) if n else None, int(total_bits), dst, capacity),
                     "zmx_bitjoin_device")
+
+    def bitjoin_many_device(self, dests, pieces, capacities=None):
+        """zmx_bitjoin_many_device: dests = [(dst pointer, total_bits, first_piece, npieces)], pieces as bitjoin_device
+        takes them with dst_bit counted from the piece's own destination; destination d is made from
+        pieces[first_piece : first_piece + npieces].  `capacities`: the room at every destination in bytes (None: exactly
+        its (total_bits + 7) // 8).  One launch for all of them."""
+        class Piece(ctypes.Structure):
+            _fields_ = [("src", ctypes.c_void_p), ("src_bit", ctypes.c_uint64), ("nbits", ctypes.c_uint64),
+                        ("dst_bit", ctypes.c_uint64)]
+
+        class Dest(ctypes.Structure):
+            _fields_ = [("dst", ctypes.c_void_p), ("total_bits", ctypes.c_uint64), ("first_piece", ctypes.c_uint64),
+                        ("npieces", ctypes.c_uint64)]
+        n, nd = len(pieces), len(dests)
+        parr = (Piece * max(n, 1))(*[Piece(int(p[0]) if p[0] else None, int(p[1]), int(p[2]), int(p[3])) for p in pieces])
+        darr = (Dest * max(nd, 1))(*[Dest(int(d[0]) if d[0] else None, int(d[1]), int(d[2]), int(d[3])) for d in dests])
+        caps = None if capacities is None else (ctypes.c_size_t * max(nd, 1))(*[int(c) for c in capacities])
+        fn = self.lib.zmx_bitjoin_many_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                       ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, nd, ctypes.cast(darr, ctypes.c_void_p) if nd else None, caps, n,
+                       ctypes.cast(parr, ctypes.c_void_p) if n else None), "zmx_bitjoin_many_device")
 
     def master_block_costs_device(self):
         """zmx_master_block_costs_device: the dealing costs of the resident input's master blocks, counted on the device."""

@@ -1,4 +1,5 @@
-// Driver part: output that stays in device memory — zmx_bitjoin_device (k_bitjoin, zmx_bitjoin.h), zmx_encode_blocks_device
+// Driver part: output that stays in device memory — zmx_bitjoin_device (k_bitjoin, zmx_bitjoin.h), zmx_bitjoin_many_device
+// (k_bitjoin_many: many destinations, one launch), zmx_encode_blocks_device
 // with zmx_bits_job / zmx_bits_free (the bit writer of drv_stores.h without the way down).
 // Needs drv_context.h (PoolScope, PoolAllocT), drv_input.h (CheckDevicePointer), drv_tables.h
 // (zmx_tables, CheckTables, CheckStoreRef, Refused).
@@ -7,6 +8,9 @@
 static_assert(sizeof(zmx_bit_piece) == sizeof(zamd::BitPiece) && offsetof(zmx_bit_piece, src_bit) == offsetof(zamd::BitPiece, src_bit) &&
               offsetof(zmx_bit_piece, nbits) == offsetof(zamd::BitPiece, nbits) && offsetof(zmx_bit_piece, dst_bit) == offsetof(zamd::BitPiece, dst_bit),
               "zmx_bit_piece is the kernel's BitPiece");
+static_assert(sizeof(zmx_bit_dest) == sizeof(zamd::BitDest) && offsetof(zmx_bit_dest, total_bits) == offsetof(zamd::BitDest, total_bits) &&
+              offsetof(zmx_bit_dest, first_piece) == offsetof(zamd::BitDest, first_piece) && offsetof(zmx_bit_dest, npieces) == offsetof(zamd::BitDest, npieces),
+              "zmx_bit_dest is the kernel's BitDest");
 static_assert(zamd::kBitPieceMaxBits == zamd::kBitjoinMaxBits, "the entry check's limit is the kernel's");
 
 // The bits of the jobs of one zmx_encode_blocks_device call, where the kernels wrote them.
@@ -23,6 +27,9 @@ struct KnownRanges {
   struct Range { uintptr_t lo; size_t size; int device; };
   std::vector<Range> ranges;
   int Check(size_t piece, const void* p, size_t n, int* device_out) {
+    return Check("zmx_bitjoin_device: piece " + std::to_string(piece), p, n, device_out);
+  }
+  int Check(const std::string& who, const void* p, size_t n, int* device_out) {
     const uintptr_t at = reinterpret_cast<uintptr_t>(p);
     for (const Range& r : ranges) {
       if (at >= r.lo && at - r.lo <= r.size && n <= r.size - (at - r.lo)) {
@@ -32,7 +39,6 @@ struct KnownRanges {
     }
     uintptr_t lo = 0;
     size_t size = 0;
-    const std::string who = "zmx_bitjoin_device: piece " + std::to_string(piece);
     if (const int rc = CheckDevicePointer(who.c_str(), p, n, device_out, &lo, &size)) return rc;
     if (ranges.size() < 64) ranges.push_back({lo, size, *device_out});
     return 0;
@@ -111,6 +117,85 @@ int zmx_internal_bitjoin_literals(zmx_ctx* c, const unsigned char* literals, siz
   }
   const int rc = zmx_bitjoin_device(c, n, pieces, total_bits, d_dst, dst_capacity);
   if (rc) (void)hipStreamSynchronize(c->stream);   // (a refusal launches nothing: the upload may still be on its way)
+  return rc;
+}
+
+int zmx_bitjoin_many_device(zmx_ctx* c, size_t ndst, const zmx_bit_dest* dests, const size_t* capacity, size_t npieces,
+                            const zmx_bit_piece* pieces) {
+  static const char* const kWho = "zmx_bitjoin_many_device";
+  g_bitjoin_ms = 0;
+  if (!c) return FailMsg("zmx_bitjoin_many_device: no context");
+  if (const int rc = Refused(zamd::CheckBitDests(kWho, ndst, dests, capacity, npieces, pieces))) return rc;
+  // ---- every range checked before anything is uploaded or launched; the tiles of every destination
+  KnownRanges known;
+  std::vector<uint64_t> tile_start(ndst + 1, 0);
+  for (size_t d = 0; d < ndst; ++d) {
+    const zmx_bit_dest& e = dests[d];
+    const std::string dest = std::string(kWho) + ": destination " + std::to_string(d);
+    const unsigned char* dst = static_cast<const unsigned char*>(e.dst);
+    tile_start[d + 1] = tile_start[d] + zamd::BitjoinTiles(dst, e.total_bits);
+    if (e.total_bits == 0) continue;     // (its pieces are all empty: nothing is read or written)
+    int device = -1;
+    if (const int rc = known.Check(dest, e.dst, static_cast<size_t>((e.total_bits + 7) / 8), &device)) return rc;
+    if (device != c->device) return FailMsg(dest + " is not memory of the context's device");
+    for (uint64_t i = 0; i < e.npieces; ++i) {
+      const zmx_bit_piece& q = pieces[e.first_piece + i];
+      if (q.nbits == 0) continue;
+      uintptr_t lo = 0, hi = 0;
+      zamd::BitPieceBytes(q, &lo, &hi);
+      const std::string piece = dest + ": piece " + std::to_string(i);
+      if (const int rc = known.Check(piece, q.src, hi - reinterpret_cast<uintptr_t>(q.src), &device)) return rc;
+      if (device != c->device) return FailMsg(piece + ": the source is not memory of the context's device");
+    }
+  }
+  const uint64_t ntiles = tile_start[ndst];
+  if (ntiles == 0) return 0;
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);   // (the tables: held until the stream is drained, on the failing paths too — below)
+  const bool timed = KernelTiming();
+  const auto enqueue = [&]() -> int {
+    zmx_bit_piece* d_pieces = nullptr;
+    zmx_bit_dest* d_dests = nullptr;
+    uint64_t* d_tile_start = nullptr;
+    HIPCHK(tmp.Upload(&d_pieces, pieces, npieces, "bitjoin_pieces"));
+    HIPCHK(tmp.Upload(&d_dests, dests, ndst, "bitjoin_dests"));
+    HIPCHK(tmp.Upload(&d_tile_start, tile_start.data(), ndst + 1, "bitjoin_tile_start"));
+    zamd::BitjoinManyTable M;
+    M.piece = reinterpret_cast<const zamd::BitPiece*>(d_pieces);
+    M.dest = reinterpret_cast<const zamd::BitDest*>(d_dests);
+    M.tile_start = d_tile_start;
+    M.ndst = ndst;
+    const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(ntiles, zamd::kBitjoinMaxBlocks));
+    if (timed) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    hipLaunchKernelGGL(k_bitjoin_many, dim3(grid), dim3(zamd::kBitjoinThreads), 0, c->stream, M, ntiles);
+    KCHK(c, "k_bitjoin_many");
+    if (timed) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    return 0;
+  };
+  if (const int rc = enqueue()) {
+    (void)hipStreamSynchronize(c->stream);   // (what was queued may still read the tables: drained before `tmp` gives them back)
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    g_bitjoin_ms = ms;
+  }
+  return 0;
+}
+
+int zmx_internal_bitjoin_many_literals(zmx_ctx* c, const unsigned char* literals, size_t nliterals, size_t ndst, const zmx_bit_dest* dests,
+                                       const size_t* capacity, size_t npieces, zmx_bit_piece* pieces, const unsigned char* is_literal) {
+  unsigned char* d_literals = nullptr;
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);   // (zmx_bitjoin_many_device drains the stream before it returns, on its failing paths too)
+  HIPCHK(tmp.Upload(&d_literals, literals, nliterals, "bitjoin_literals"));
+  for (size_t i = 0; i < npieces; ++i) {
+    if (is_literal[i]) pieces[i].src = d_literals + reinterpret_cast<uintptr_t>(pieces[i].src);
+  }
+  const int rc = zmx_bitjoin_many_device(c, ndst, dests, capacity, npieces, pieces);
+  (void)hipStreamSynchronize(c->stream);   // (a refusal, or a join of no tile, launches nothing: the upload may still be on its way)
   return rc;
 }
 

@@ -102,6 +102,21 @@ int zmx_internal_device_pointers(const char* who, size_t n, const void* const* p
   return 0;
 }
 
+int zmx_internal_device_pointers_one_device(const char* who, size_t n, const void* const* p, const size_t* nbytes, int* device) {
+  DeviceRangeChecker checker;
+  *device = -1;
+  for (size_t i = 0; i < n; ++i) {
+    const std::string w = std::string(who) + ": range " + std::to_string(i);
+    if (nbytes[i] != 0 && p[i] == nullptr) return FailMsg(w + ": null pointer with a non-zero size");
+    int at = -1;
+    if (const int rc = checker.Check(w.c_str(), p[i], nbytes[i], &at)) return rc;
+    if (at < 0) continue;
+    if (*device >= 0 && at != *device) return FailMsg(w + " lies on another device than the ranges before it");
+    *device = at;
+  }
+  return 0;
+}
+
 int zmx_internal_device_alloc(int device, size_t n, void** p) {
   *p = nullptr;
   DEVICE_ENTRY(device);

@@ -16,8 +16,9 @@
 // Every byte of dst[0, (total_bits + 7) / 8) is written exactly once, whole, and none beyond; nothing is read but the
 // aligned 4-byte words that hold a bit of a piece.  Plain loads and stores only: no atomics, no pre-zeroed destination.
 // The launch is at most kBitjoinMaxBlocks workgroups whatever n and the total.
-// The rules are __host__ __device__ functions, so a CPU program (tests/hostlib/bitjoin_print.cc) runs the very code of
-// the kernel, lanes one after the other.  This header compiles without HIP; the kernel is there for the device layer
+// zmx_bitjoin_many_device / k_bitjoin_many (below): the same join for many destinations in one launch.
+// The rules are __host__ __device__ functions, so a CPU program (tests/hostlib/bitjoin_print.cc, bitjoin_many_print.cc)
+// runs the very code of the kernel, lanes one after the other.  This header compiles without HIP; the kernel is there for the device layer
 // only (ZMX_BITJOIN_KERNELS).
 #ifndef ZMX_BITJOIN_H_
 #define ZMX_BITJOIN_H_
@@ -207,12 +208,75 @@ ZMX_BITJOIN_HD inline void BitjoinTile(const BitjoinTable& T, uint64_t tile, uin
   run(cur, g1, nullptr);
 }
 
+// ---- zmx_bitjoin_many_device: many destinations in one launch (the streams of zmx_compress_device_batch_to_device).
+// Destination d is a join of its own — pieces [first_piece, first_piece + npieces) of one shared table, their dst_bit
+// counted from its own dst — and keeps the tiling of a single join: its tiles are counted from the 16-byte boundary at or
+// below its own dst, BitjoinVectors of them.  The tiles of all destinations are numbered one after the other;
+// tile_start[d] is the number of destination d's first tile (tile_start[ndst]: the number of tiles), made on the host.
+// A workgroup strides over that global number, finds the destination by binary search and runs BitjoinTile on the
+// local tile, so the launch is at most kBitjoinMaxBlocks workgroups whatever ndst, the piece count and the total.  Two
+// destinations may be neighbours inside one 16-byte vector: each join stores only its own bytes of it (BitjoinEdgeVec's
+// byte-by-byte path), so every byte of every destination is still written exactly once and none outside them.
+
+// (the layout of zmx_bit_dest, include/zopfli_amd.h)
+struct BitDest {
+  unsigned char* dst;
+  uint64_t total_bits, first_piece, npieces;
+};
+
+struct BitjoinManyTable {
+  const BitPiece* piece;        // the pieces of all destinations, destination after destination
+  const BitDest* dest;          // [ndst]
+  const uint64_t* tile_start;   // [ndst + 1], ascending; equal neighbours: a destination of no tile
+  uint64_t ndst;
+};
+
+// The tiles of a destination.
+ZMX_BITJOIN_HD inline uint64_t BitjoinTiles(const unsigned char* dst, uint64_t total_bits) {
+  return (BitjoinVectors(dst, total_bits) + kBitjoinTileVecs - 1) / kBitjoinTileVecs;
+}
+
+// The destination that global tile `tile` (< tile_start[ndst]) belongs to — the last d with tile_start[d] <= tile, which
+// has tile_start[d + 1] > tile and so at least one tile: a destination of no tile is never found — and the tile's
+// number within it.
+ZMX_BITJOIN_HD inline uint64_t BitjoinDestOfTile(const uint64_t* tile_start, uint64_t ndst, uint64_t tile, uint64_t* local) {
+  uint64_t lo = 0, hi = ndst;   // tile_start[lo] <= tile < tile_start[hi]
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (tile_start[mid] <= tile) lo = mid; else hi = mid;
+  }
+  *local = tile - tile_start[lo];
+  return lo;
+}
+
+// Destination d as a join of its own.
+ZMX_BITJOIN_HD inline BitjoinTable BitjoinDestTable(const BitjoinManyTable& M, uint64_t d) {
+  const BitDest e = M.dest[d];
+  BitjoinTable T;
+  T.piece = M.piece + e.first_piece;
+  T.n = e.npieces;
+  T.dst = e.dst;
+  T.total_bits = e.total_bits;
+  return T;
+}
+
+// Thread `thread` of a workgroup of `threads` makes its share of global tile `tile`.
+ZMX_BITJOIN_HD inline void BitjoinManyTile(const BitjoinManyTable& M, uint64_t tile, uint32_t thread, uint32_t threads) {
+  uint64_t local = 0;
+  const uint64_t d = BitjoinDestOfTile(M.tile_start, M.ndst, tile, &local);
+  BitjoinTile(BitjoinDestTable(M, d), local, thread, threads);
+}
+
 }  // namespace zamd
 
 #if defined(ZMX_BITJOIN_KERNELS)
 
 __global__ __launch_bounds__(256) void k_bitjoin(zamd::BitjoinTable T, uint64_t ntiles) {
   for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) zamd::BitjoinTile(T, tile, threadIdx.x, blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void k_bitjoin_many(zamd::BitjoinManyTable M, uint64_t ntiles) {
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) zamd::BitjoinManyTile(M, tile, threadIdx.x, blockDim.x);
 }
 
 #endif  // ZMX_BITJOIN_KERNELS

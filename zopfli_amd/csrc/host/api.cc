@@ -564,8 +564,13 @@ int RunPartsToDevice(const ZopfliOptions& options, const std::vector<Part>& part
 }
 bool TraceCallOn() { return TraceCall(); }
 double CallWallMs() { return WallMs(); }
-int OnPooledContext(const std::function<int(zmx_ctx*)>& fn) {
-  Lease lease(1);
+int OnPooledContext(const std::function<int(zmx_ctx*)>& fn, int only_device) {
+  Lease lease(1, 1, false, false, only_device);
+  if (lease.ctxs.empty()) {   // (only_device alone: every other call waits or dies in the pool)
+    const std::string msg = "device " + std::to_string(only_device) + " is not one of the library's devices (ZOPFLI_AMD_DEVICE, ZOPFLI_AMD_DEVICES)";
+    zmx_internal_set_error(msg.c_str(), ZMX_ERR_REFUSED);
+    return -1;
+  }
   return fn(lease.ctxs[0]);
 }
 }  // namespace zamd

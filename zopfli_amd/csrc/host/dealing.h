@@ -51,7 +51,8 @@ struct DeviceInput {
   std::vector<char> runs;     // LooksLikeRuns of every round of `round_parts` parts (ZOPFLI_AMD_ROUND_PARTS)
   size_t round_parts = 1;
   size_t first_part = 0;      // the part of the request that the round being dealt begins with (set by who runs the rounds)
-  // Output that stays in device memory (zmx_compress_device_to_device, device_output.cc; one round only):
+  // Output that stays in device memory (zmx_compress_device_to_device, device_output.cc; zmx_compress_device_batch_to_device,
+  // batch.cc, which takes the chunk counts of RunPartsDealt's `part_chunks` with the chunks; one round only):
   // the shards run with g_device_output set and leave the bytes of stored blocks where they are; the call is dealt over the
   // contexts of `only_device` alone; `finish` runs once the shards are collected, on one of the call's contexts and while
   // the call still holds them all — the chunks' device bits are theirs — with the container's checksum (0 without one);
@@ -100,7 +101,8 @@ int RunPartsToDevice(const ZopfliOptions& options, const std::vector<Part>& part
 // ZOPFLI_AMD_TRACE_CALL=1, and the clock of its lines
 bool TraceCallOn();
 double CallWallMs();
-// `fn` on one of the pool's contexts, held for the call (what the *_pooled entry points outside api.cc use)
-int OnPooledContext(const std::function<int(zmx_ctx*)>& fn);
+// `fn` on one of the pool's contexts, held for the call (what the *_pooled entry points outside api.cc use);
+// `only_device` >= 0: a context of that HIP device — -1 with the error set when it is none of the library's
+int OnPooledContext(const std::function<int(zmx_ctx*)>& fn, int only_device = -1);
 
 }  // namespace zamd

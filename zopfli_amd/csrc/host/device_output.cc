@@ -27,30 +27,14 @@ int Refuse(const std::string& msg) {
   return -1;
 }
 
-std::vector<uint8_t> ContainerHeader(ZopfliFormat format) {
-  if (format == ZOPFLI_FORMAT_GZIP) return {31, 139, 8, 0, 0, 0, 0, 0, 2, 3};   // gzip_container.c:90-101
-  if (format == ZOPFLI_FORMAT_ZLIB) {                                           // zlib_container.c:56-64
-    unsigned cmfflg = 256 * 120 + 3 * 64;   // CM 8, CINFO 7, FLEVEL 3, no dictionary
-    cmfflg += 31 - cmfflg % 31;
-    return {static_cast<uint8_t>(cmfflg / 256), static_cast<uint8_t>(cmfflg % 256)};
-  }
-  return {};
-}
-
-std::vector<uint8_t> ContainerTrailer(ZopfliFormat format, uint32_t sum, size_t insize) {
-  std::vector<uint8_t> t;
-  if (format == ZOPFLI_FORMAT_GZIP) {          // CRC-32, then ISIZE, both little-endian (gzip_container.c:107-116)
-    for (int i = 0; i < 4; ++i) t.push_back(static_cast<uint8_t>(sum >> (8 * i)));
-    for (int i = 0; i < 4; ++i) t.push_back(static_cast<uint8_t>(insize >> (8 * i)));
-  } else if (format == ZOPFLI_FORMAT_ZLIB) {   // Adler-32, big-endian (zlib_container.c:71-74)
-    for (int i = 3; i >= 0; --i) t.push_back(static_cast<uint8_t>(sum >> (8 * i)));
-  }
-  return t;
-}
-
 }  // namespace
 
 extern "C" size_t zmx_compress_bound(ZopfliFormat output_type, size_t insize) { return zamd::CompressBound(output_type, insize); }
+
+extern "C" size_t zmx_compress_batch_bound(ZopfliFormat output_type, size_t n, const size_t* insize, size_t align) {
+  if (n == 0 || !insize || !zamd::PackedAlignOk(align)) return 0;
+  return zamd::CompressBatchBound(output_type, n, insize, align);
+}
 
 extern "C" int zmx_compress_device_to_device(const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in,
                                              size_t insize, void* d_out, size_t capacity, size_t* outsize) {
@@ -87,8 +71,8 @@ extern "C" int zmx_compress_device_to_device(const ZopfliOptions* options, Zopfl
   bool too_small = false;
   size_t written = 0;
   dev.finish = [&](zmx_ctx* ctx, std::vector<zamd::Chunk>* chunks, uint32_t sum) {
-    const zamd::OutputPlan plan = zamd::PlanOutput(ContainerHeader(output_type), *chunks, static_cast<const unsigned char*>(d_in),
-                                                   ContainerTrailer(output_type, sum, insize));
+    const zamd::OutputPlan plan = zamd::PlanOutput(zamd::ContainerHeader(output_type), *chunks, static_cast<const unsigned char*>(d_in),
+                                                   zamd::ContainerTrailer(output_type, sum, insize));
     const size_t need = static_cast<size_t>(plan.total_bits / 8);
     if (need > capacity) {
       too_small = true;

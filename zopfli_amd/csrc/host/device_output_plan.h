@@ -1,5 +1,6 @@
-// zmx_compress_device_to_device, the part that needs no device: zmx_compress_bound's arithmetic and the planner that turns
-// a call's chunk list into the piece table of one zmx_bitjoin_device.  Host code only (tests build it without HIP).
+// zmx_compress_device_to_device and zmx_compress_device_batch_to_device, the part that needs no device: zmx_compress_bound's
+// arithmetic, the packed form's offsets, the containers' bytes and the planner that turns a stream's chunk list into the
+// piece table of a bit join.  Host code only (tests build it without HIP).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -36,6 +37,48 @@ inline size_t CompressBound(ZopfliFormat format, size_t insize) {
   return insize + 6 * pieces + 1 + ContainerBytes(format);
 }
 
+// An arena that does for the streams of n inputs packed as zmx_compress_device_batch_packed packs them: every stream's
+// own bound, rounded up to `align` — stream i then begins at or below the sum of the rounded bounds before it.
+inline size_t AlignUp(size_t v, size_t align) { return (v + align - 1) / align * align; }
+inline size_t CompressBatchBound(ZopfliFormat format, size_t n, const size_t* insize, size_t align) {
+  size_t sum = 0;
+  for (size_t i = 0; i < n; ++i) sum += AlignUp(CompressBound(format, insize[i]), align);
+  return sum;
+}
+// `align` as the packed form takes it: a power of two, 1 .. 4096.
+inline bool PackedAlignOk(size_t align) { return align >= 1 && align <= 4096 && (align & (align - 1)) == 0; }
+// Where the packed form puts n streams of size[i] bytes: offset[i] is the end of stream i - 1 rounded up to `align`
+// (offset[0] = 0; an empty stream takes no room but is aligned like the others).  Returns the end of the last stream.
+inline size_t PackedOffsets(size_t n, const size_t* size, size_t align, size_t* offset) {
+  size_t end = 0;
+  for (size_t i = 0; i < n; ++i) {
+    offset[i] = AlignUp(end, align);
+    end = offset[i] + size[i];
+  }
+  return end;
+}
+
+// The container's bytes around the deflate stream, as the reference writes them.
+inline std::vector<uint8_t> ContainerHeader(ZopfliFormat format) {
+  if (format == ZOPFLI_FORMAT_GZIP) return {31, 139, 8, 0, 0, 0, 0, 0, 2, 3};   // gzip_container.c:90-101
+  if (format == ZOPFLI_FORMAT_ZLIB) {                                           // zlib_container.c:56-64
+    unsigned cmfflg = 256 * 120 + 3 * 64;   // CM 8, CINFO 7, FLEVEL 3, no dictionary
+    cmfflg += 31 - cmfflg % 31;
+    return {static_cast<uint8_t>(cmfflg / 256), static_cast<uint8_t>(cmfflg % 256)};
+  }
+  return {};
+}
+inline std::vector<uint8_t> ContainerTrailer(ZopfliFormat format, uint32_t sum, size_t insize) {
+  std::vector<uint8_t> t;
+  if (format == ZOPFLI_FORMAT_GZIP) {          // CRC-32, then ISIZE, both little-endian (gzip_container.c:107-116)
+    for (int i = 0; i < 4; ++i) t.push_back(static_cast<uint8_t>(sum >> (8 * i)));
+    for (int i = 0; i < 4; ++i) t.push_back(static_cast<uint8_t>(insize >> (8 * i)));
+  } else if (format == ZOPFLI_FORMAT_ZLIB) {   // Adler-32, big-endian (zlib_container.c:71-74)
+    for (int i = 3; i >= 0; --i) t.push_back(static_cast<uint8_t>(sum >> (8 * i)));
+  }
+  return t;
+}
+
 // A piece of the plan: `nbits` bits from bit `src_bit` of the literals buffer at byte `lit` (literal) or of the device
 // string at `dev`, to bit `dst_bit` of the output.
 struct PlanPiece {
@@ -52,10 +95,10 @@ struct OutputPlan {
   size_t host_blocks = 0;          // blocks the host wrote
 };
 
-// The stream of `prefix` (the container's header), the chunks and `trailer`, from bit 0: MergeChunks' placement
-// arithmetic (deflate.cc) with no running bit pointer, the output always beginning byte-aligned.  `d_in`: the device
-// memory the stored chunks' positions refer to.
-inline OutputPlan PlanOutput(const std::vector<uint8_t>& prefix, const std::vector<Chunk>& chunks, const unsigned char* d_in,
+// The stream of `prefix` (the container's header), the chunks [first, last) and `trailer`, from bit 0: MergeChunks'
+// placement arithmetic (deflate.cc) with no running bit pointer, the output always beginning byte-aligned.  `d_in`: the
+// device memory the stored chunks' positions refer to.
+inline OutputPlan PlanOutput(const std::vector<uint8_t>& prefix, const Chunk* first, const Chunk* last, const unsigned char* d_in,
                              const std::vector<uint8_t>& trailer) {
   OutputPlan plan;
   std::vector<uint8_t>& lit = plan.literals;
@@ -66,7 +109,8 @@ inline OutputPlan PlanOutput(const std::vector<uint8_t>& prefix, const std::vect
   };
   literal(prefix.data(), prefix.size(), 8 * prefix.size(), 0);
   uint64_t cur = 8 * prefix.size();
-  for (const Chunk& c : chunks) {
+  for (const Chunk* it = first; it != last; ++it) {
+    const Chunk& c = *it;
     if (c.kind == Chunk::kBits) {
       literal(c.BitData(), (c.nbits + 7) / 8, c.nbits, cur);
       cur += c.nbits;
@@ -102,6 +146,10 @@ inline OutputPlan PlanOutput(const std::vector<uint8_t>& prefix, const std::vect
   literal(trailer.data(), trailer.size(), 8 * trailer.size(), cur);
   plan.total_bits = cur + 8 * trailer.size();
   return plan;
+}
+inline OutputPlan PlanOutput(const std::vector<uint8_t>& prefix, const std::vector<Chunk>& chunks, const unsigned char* d_in,
+                             const std::vector<uint8_t>& trailer) {
+  return PlanOutput(prefix, chunks.data(), chunks.data() + chunks.size(), d_in, trailer);
 }
 
 }  // namespace zamd

@@ -4,9 +4,11 @@
 // `who`, the entry's name, then ": ", then the text — or an empty string when there is nothing to refuse.  Either side
 // turns a message into its own ZMX_ERR_REFUSED.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "symbols.h"
 
@@ -107,6 +109,93 @@ inline void BitPieceBytes(const Piece& q, uintptr_t* lo, uintptr_t* hi) {
 // The destination dst[0, dst_bytes) may not share a byte with piece i's [src_lo, src_hi).
 inline std::string CheckBitPieceApart(const char* who, size_t i, uintptr_t dst, uint64_t dst_bytes, uintptr_t src_lo, uintptr_t src_hi) {
   if (src_lo < dst + dst_bytes && dst < src_hi) return Refusal(who, "piece " + std::to_string(i) + ": the destination overlaps this source");
+  return std::string();
+}
+
+// ---- the destinations of zmx_bitjoin_many_device and of zmx_compress_device_batch_to_device
+// Byte ranges [lo, hi) that may not share a byte, each with the number its owner knows it by.  Sorted once, so that a
+// thousand destinations against ten thousand sources are no product: Add, then Sort, then Overlap and Hit.
+class ApartRanges {
+ public:
+  void Add(uintptr_t lo, uintptr_t hi, size_t id) {
+    if (lo < hi) ranges_.push_back({lo, hi, id});
+  }
+  void Sort() {
+    std::sort(ranges_.begin(), ranges_.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
+  }
+  // two ranges that share a byte (the later one in address order in *b), when there are any
+  bool Overlap(size_t* a, size_t* b) const {
+    for (size_t i = 1; i < ranges_.size(); ++i) {
+      if (ranges_[i].lo < ranges_[i - 1].hi) {
+        *a = ranges_[i - 1].id;
+        *b = ranges_[i].id;
+        return true;
+      }
+    }
+    return false;
+  }
+  // a range that shares a byte with [lo, hi), when there is one (the ranges being apart: Overlap said so)
+  bool Hit(uintptr_t lo, uintptr_t hi, size_t* id) const {
+    if (lo >= hi) return false;
+    // the last range that begins below hi: the ones in front of it end at or below its lo
+    auto it = std::lower_bound(ranges_.begin(), ranges_.end(), hi, [](const Range& r, uintptr_t v) { return r.lo < v; });
+    if (it == ranges_.begin() || (it - 1)->hi <= lo) return false;
+    *id = (it - 1)->id;
+    return true;
+  }
+
+ private:
+  struct Range { uintptr_t lo, hi; size_t id; };
+  std::vector<Range> ranges_;
+};
+
+// What zmx_bitjoin_many_device refuses of its tables without asking the runtime.  Dest: zmx_bit_dest { dst, total_bits,
+// first_piece, npieces }; destination d has capacity[d] bytes (capacity null: exactly (total_bits + 7) / 8).  The piece
+// ranges are consecutive and end at npieces; each destination's pieces follow CheckBitPieces; no two destinations share
+// a byte, and no piece's source bytes share one with any destination.
+template <class Dest, class Piece>
+inline std::string CheckBitDests(const char* who, size_t ndst, const Dest* dests, const size_t* capacity, size_t npieces,
+                                 const Piece* pieces) {
+  if (ndst != 0 && dests == nullptr) return Refusal(who, "null destination table");
+  if (npieces != 0 && pieces == nullptr) return Refusal(who, "null piece table");
+  uint64_t next = 0;
+  for (size_t d = 0; d < ndst; ++d) {
+    const std::string dest = "destination " + std::to_string(d);
+    if (dests[d].first_piece != next) return Refusal(who, dest + ": its pieces do not follow those of the destination before it");
+    if (dests[d].npieces > npieces - next) return Refusal(who, dest + ": its pieces leave the table of " + std::to_string(npieces));
+    next += dests[d].npieces;
+  }
+  if (next != npieces) return Refusal(who, "the destinations take " + std::to_string(next) + " pieces of " + std::to_string(npieces));
+  ApartRanges apart;
+  for (size_t d = 0; d < ndst; ++d) {
+    const Dest& e = dests[d];
+    const std::string dest = std::string(who) + ": destination " + std::to_string(d);
+    if (e.total_bits >= kBitPieceMaxBits) return Refusal(dest.c_str(), "a bit count of 2^60 or more");
+    const uint64_t nbytes = (e.total_bits + 7) / 8;
+    const std::string msg = CheckBitPieces(dest.c_str(), static_cast<size_t>(e.npieces), e.npieces ? pieces + e.first_piece : nullptr,
+                                           e.total_bits, capacity ? capacity[d] : nbytes);
+    if (!msg.empty()) return msg;
+    if (nbytes != 0 && e.dst == nullptr) return Refusal(dest.c_str(), "null pointer with a non-zero size");
+    const uintptr_t at = reinterpret_cast<uintptr_t>(e.dst);
+    apart.Add(at, at + static_cast<uintptr_t>(nbytes), d);
+  }
+  apart.Sort();
+  size_t a = 0, b = 0;
+  if (apart.Overlap(&a, &b)) {
+    return Refusal(who, "destination " + std::to_string(std::max(a, b)) + " overlaps destination " + std::to_string(std::min(a, b)));
+  }
+  for (size_t d = 0; d < ndst; ++d) {
+    for (uint64_t i = 0; i < dests[d].npieces; ++i) {
+      const Piece& q = pieces[dests[d].first_piece + i];
+      if (q.nbits == 0) continue;
+      uintptr_t lo = 0, hi = 0;
+      BitPieceBytes(q, &lo, &hi);
+      if (apart.Hit(lo, hi, &a)) {
+        return Refusal(who, "destination " + std::to_string(d) + ": piece " + std::to_string(i) + ": destination " + std::to_string(a) +
+                                " overlaps this source");
+      }
+    }
+  }
   return std::string();
 }
 

@@ -70,6 +70,14 @@ void zmx_internal_device_free(int device, void* p);
 // time of the join.  `pieces` is rewritten.  0, or -1 with the error set.
 int zmx_internal_bitjoin_literals(zmx_ctx* ctx, const unsigned char* literals, size_t nliterals, size_t n, zmx_bit_piece* pieces,
                                   const unsigned char* is_literal, uint64_t total_bits, void* d_dst, size_t dst_capacity);
+// The same for zmx_bitjoin_many_device(ctx, ndst, dests, capacity, npieces, pieces): one literals buffer for the pieces of
+// all destinations (zmx_compress_device_batch_to_device, batch.cc).
+int zmx_internal_bitjoin_many_literals(zmx_ctx* ctx, const unsigned char* literals, size_t nliterals, size_t ndst, const zmx_bit_dest* dests,
+                                       const size_t* capacity, size_t npieces, zmx_bit_piece* pieces, const unsigned char* is_literal);
+// zmx_internal_device_pointers for ranges that must lie on ONE device (the destinations of a batch): *device is that
+// device, -1 when every range is empty.  Refused (the message starts with `who` and names the range): what
+// zmx_internal_device_pointer refuses of any of them, and a range on another device than the ones before it.
+int zmx_internal_device_pointers_one_device(const char* who, size_t n, const void* const* p, const size_t* nbytes, int* device);
 
 // ---- for tests and tools
 // The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
