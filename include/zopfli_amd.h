@@ -371,6 +371,73 @@ int zmx_png_filter_types_brute(zmx_ctx* ctx, const unsigned char* image, size_t 
 int zmx_png_filter_types_brute_pooled(const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
                                       unsigned windowsize, unsigned char* types);
 
+/* The same row searches on an image that already lies in DEVICE memory, the types left there: d_types[0, height), memory
+ * of the context's device as the image is.  `strategy`: ZMX_PNG_FILTER_ZERO .. _FOUR fill the types with 0 .. 4, _MINSUM
+ * and _ENTROPY run zmx_png_filter_types' kernel, _BRUTE runs zmx_png_filter_types_brute's with window `windowsize`
+ * (read for _BRUTE only).  The numbers are LodePNG's LodePNGFilterStrategy where it has them (lodepng.h:680-698);
+ * _PREDEFINED is for zmx_png_encode_device alone.  Both pointers are checked as zmx_png_filter_rows_device checks its
+ * own; the types may not overlap the image.  height = 0 returns 0.  Synchronous. */
+#define ZMX_PNG_FILTER_ZERO 0
+#define ZMX_PNG_FILTER_ONE 1
+#define ZMX_PNG_FILTER_TWO 2
+#define ZMX_PNG_FILTER_THREE 3
+#define ZMX_PNG_FILTER_FOUR 4
+#define ZMX_PNG_FILTER_MINSUM 5
+#define ZMX_PNG_FILTER_ENTROPY 6
+#define ZMX_PNG_FILTER_BRUTE 7
+#define ZMX_PNG_FILTER_PREDEFINED 8
+int zmx_png_filter_types_device(zmx_ctx* ctx, const void* d_image, size_t linebytes, size_t height, size_t bytewidth,
+                                int strategy, unsigned windowsize, void* d_types);
+
+/* The filtered scanlines of an image in device memory (k_png_rows, device/zmx_png_rows.h: one launch of at most 2048
+ * workgroups): d_out[r * (linebytes + 1)] = d_types[r], and the `linebytes` bytes behind it are row r of d_image filtered
+ * that way (lodepng.cpp:5379-5421 filterScanline: None, Sub, Up, Average, Paeth; `bytewidth` the distance to the left
+ * neighbour, zeros above row 0 and to the left of a row's first `bytewidth` bytes) — the bytes LodePNG's encoder hands to
+ * its deflate.  Every byte of d_out[0, height * (linebytes + 1)) is written exactly once and none outside; d_out may have
+ * any alignment.  Refused before any launch (ZMX_ERR_REFUSED): a null pointer, host or managed memory, a range that
+ * leaves its allocation, memory of another device than the context's, an output that overlaps the image or the types, a
+ * `capacity` below height * (linebytes + 1), linebytes 0 or above 2^31 - 1, a height above 2^31 - 1, a bytewidth that is
+ * not 1 .. 8.  A type byte above 4 is found by the kernel: the call fails (ZMX_ERR_REFUSED), the message names the first
+ * such row ("row N"), and what d_out then holds is not defined.  height = 0 returns 0.  Synchronous; the caller
+ * synchronises the streams that produced the image and the types. */
+int zmx_png_filter_rows_device(zmx_ctx* ctx, const void* d_image, size_t linebytes, size_t height, size_t bytewidth,
+                               const void* d_types, void* d_out, size_t capacity);
+
+/* An image in device memory (a rendered frame, a tensor) as a zopfli-optimised PNG file.  *out, *outsize follow the
+ * reference's append convention, as zmx_compress_device's do, and end holding the file that
+ *   zopflipng --keepcolortype --always_zopflify --filters=<strategy>
+ * writes for a PNG of the same pixels, colour type and bit depth that has no other chunks: the signature, IHDR, ONE
+ * IDAT and IEND, the IDAT's payload being 78 01, ZopfliDeflate(btype 2, final 1) of LodePNG's filtered scanlines and
+ * their Adler-32.  The match is byte for byte when options->numiterations is what zopflipng would take: its rule —
+ * num_iterations (15) for less than 200 000 bytes of scanlines, else num_iterations_large (5), zopflipng_lib.cc:56-58 —
+ * is the caller's business, as is every other field of `options`.
+ * `strategy`: a ZMX_PNG_FILTER_* (zopflipng's --filters= 0 1 2 3 4 m e b); _BRUTE searches with window 32768, as
+ * zopflipng's final encode does (zopflipng_lib.cc:360); _PREDEFINED takes `predefined`, `height` host bytes of at most 4
+ * each (otherwise `predefined` is not read).
+ * No pixel visits the host (zmx_last_input_traffic()[0] is 0): the row search and k_png_rows run on a context of the
+ * image's device into a buffer of the call's own, and zmx_compress_device(ZOPFLI_FORMAT_ZLIB) of that buffer makes the
+ * stream; only the stream comes down, and the container is put around it on the host.
+ * Refused before anything runs (ZMX_ERR_REFUSED), *out and *outsize unchanged: a null argument, width or height 0, a
+ * colour type other than 0, 2, 4, 6, a bit depth other than 8 or 16, an unknown strategy, _PREDEFINED without types or
+ * with a type above 4, and what zmx_png_filter_rows_device refuses of the pixels' pointer.  Any later failure leaves them
+ * unchanged as well.
+ * Out of scope: palette and sub-8-bit images, interlace, colour-type reduction, ancillary chunks, zopflipng's automatic
+ * strategy trial (libzopflipng_amd.so does those, from a file), a PNG left in device memory. */
+typedef struct zmx_png_image {
+  const void* d_pixels;  /* height rows of linebytes bytes, PNG byte order (16-bit samples big-endian), rows back to back */
+  uint32_t width, height, colortype /* 0, 2, 4, 6 */, bitdepth /* 8, 16 */;
+} zmx_png_image;
+int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                          const unsigned char* predefined, unsigned char** out, size_t* outsize);
+/* n images in one call: every out[i], outsize[i] ends as zmx_png_encode_device(options, &images[i], strategy, ...)
+ * leaves it, byte for byte, whatever the other images and their order.  The types and rows are made image by image (two
+ * or three launches each) into ONE buffer, and ONE zmx_compress_device_batch(ZOPFLI_FORMAT_ZLIB) over its slices makes
+ * the streams, so icons and tiles share the table builds and squeeze runs of one large call.  The images lie on one
+ * device.  _PREDEFINED is refused; otherwise the refusals are the single call's, for any image, and no out[i] is changed
+ * by a call that fails.  n = 0 returns 0. */
+int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                unsigned char** out, size_t* outsize);
+
 /* Parity probe over whole tables: two 64-bit sums over all positions of a hash of the logical content of the match
  * records (block, position, length, distance, same, literal, every change point of sublen).  Equal digests of two
  * table sets over the same blocks = the same ZopfliFindLongestMatch results at every position. */

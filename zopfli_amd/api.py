@@ -366,6 +366,91 @@ def compress_bound(nbytes, fmt=FORMAT_GZIP, lib=None):
     return int(fn(fmt, nbytes))
 
 
+class PngImage(ctypes.Structure):
+    """zmx_png_image"""
+    _fields_ = [("d_pixels", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("colortype", ctypes.c_uint32), ("bitdepth", ctypes.c_uint32)]
+
+
+# ZMX_PNG_FILTER_*: zopflipng's --filters= letters, and "p" for predefined types
+PNG_STRATEGIES = {"0": 0, "1": 1, "2": 2, "3": 3, "4": 4, "m": 5, "e": 6, "b": 7, "p": 8}
+PNG_FILTER_MINSUM, PNG_FILTER_ENTROPY, PNG_FILTER_BRUTE, PNG_FILTER_PREDEFINED = 5, 6, 7, 8
+_PNG_COLORTYPE = {1: 0, 2: 4, 3: 2, 4: 6}   # channels -> grey, grey + alpha, RGB, RGBA
+
+
+def _png_strategy(strategy):
+    return PNG_STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)
+
+
+def _png_image(image, sync=True):
+    """The zmx_png_image of a contiguous uint8 tensor (H, W) or (H, W, 2 | 3 | 4), or of a tuple
+    (pointer, width, height, colortype, bitdepth)."""
+    if isinstance(image, (tuple, list)):
+        ptr, width, height, colortype, bitdepth = image
+        return PngImage(int(ptr) or None, int(width), int(height), int(colortype), int(bitdepth))
+    shape = tuple(image.shape)
+    if len(shape) == 2:
+        shape = shape + (1,)
+    if len(shape) != 3 or shape[2] not in _PNG_COLORTYPE or image.element_size() != 1:
+        raise ValueError("an image tensor is uint8 of shape (H, W) or (H, W, 2 | 3 | 4); 16-bit data goes as "
+                         "(pointer, width, height, colortype, bitdepth)")
+    ptr, _ = _device_range(image, None, sync=sync)
+    return PngImage(ptr or None, shape[1], shape[0], _PNG_COLORTYPE[shape[2]], 8)
+
+
+def png_encode_device(image, strategy="e", options=None, predefined=None, lib=None):
+    """zmx_png_encode_device: the image in device memory as the PNG file `zopflipng --keepcolortype --always_zopflify
+    --filters=<strategy>` writes for it (when options.numiterations is zopflipng's: 15 below 200 000 bytes of scanlines,
+    else 5).  `image`: a contiguous uint8 tensor (H, W) grey, (H, W, 2) grey + alpha, (H, W, 3) RGB or (H, W, 4) RGBA — a
+    torch tensor's current stream is synchronised first — or (pointer, width, height, colortype, bitdepth) for any of
+    the colour types 0, 2, 4, 6 at 8 or 16 bits (16-bit samples big-endian).  `strategy`: one of "0" "1" "2" "3" "4" "m"
+    "e" "b", or "p" with `predefined`, a filter type (0 .. 4) for every row.  Returns the file's bytes.  Raises ValueError
+    for a tensor that is no image, RuntimeError with the library's message when the library refuses or fails."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    im = _png_image(image)
+    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
+    if types is not None and len(types) != im.height:
+        raise ValueError(f"{len(types)} predefined types for {im.height} rows")
+    out, outsize = _u8p(), ctypes.c_size_t(0)
+    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
+    fn = lib.zmx_png_encode_device
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p,
+                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, ctypes.byref(out), ctypes.byref(outsize)) != 0:
+        raise RuntimeError("zmx_png_encode_device: " + (lib.zmx_last_error() or b"").decode())
+    return _take(out, outsize)
+
+
+def png_encode_device_batch(images, strategy="e", options=None, lib=None):
+    """zmx_png_encode_device_batch: one PNG file per image, each the one png_encode_device gives, from one call that
+    shares its deflate work among them.  `images`: a list of what png_encode_device takes (the current stream of every
+    torch device among the tensors is synchronised once).  Predefined types are the single call's."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    ims = [_png_image(image, sync=False) for image in images]
+    devices = {}
+    for image in images:
+        if not isinstance(image, (tuple, list)) and type(image).__module__.split(".")[0] == "torch":
+            devices[str(image.device)] = image.device
+    if devices:
+        import torch
+        for device in devices.values():
+            torch.cuda.current_stream(device).synchronize()
+    n = len(ims)
+    arr = (PngImage * max(n, 1))(*ims)
+    outs = (_u8p * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    fn = lib.zmx_png_encode_device_batch
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_int,
+                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), outs, outsizes) != 0:
+        raise RuntimeError("zmx_png_encode_device_batch: " + (lib.zmx_last_error() or b"").decode())
+    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+
+
 def last_output_traffic(lib=None):
     """zmx_last_output_traffic: of this thread's last call, the stream's bytes device to host, its bytes host to device,
     the blocks whose symbols' bits never left the device, the blocks the host wrote and uploaded."""
@@ -513,6 +598,37 @@ class Context:
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes), dst),
                     "zmx_gather_device")
+
+    def png_filter_types_device(self, image, linebytes, height, bytewidth, strategy, types, windowsize=32768):
+        """zmx_png_filter_types_device: the filter type of every row of the image at `image` (a tensor or an integer
+        pointer: `height` rows of `linebytes` bytes in memory of this context's device) under `strategy` (a letter of
+        zopflipng's --filters= or a ZMX_PNG_FILTER_* number; `windowsize` for "b"), into the `height` bytes at `types`,
+        a tensor or an integer pointer into the same device's memory."""
+        img = image if isinstance(image, int) else _device_range(image, None)[0]
+        dst = types if isinstance(types, int) else _device_range(types, None)[0]
+        fn = self.lib.zmx_png_filter_types_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                       ctypes.c_uint, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, img or None, linebytes, height, bytewidth, _png_strategy(strategy), windowsize, dst or None),
+                    "zmx_png_filter_types_device")
+
+    def png_filter_rows_device(self, image, linebytes, height, bytewidth, types, out, capacity=None):
+        """zmx_png_filter_rows_device: the filtered scanlines of the image at `image` — row r is types[r] and then the
+        row filtered that way — into `out`, a tensor or an integer pointer with `capacity` bytes (an integer pointer
+        without one: exactly height * (linebytes + 1)); all three in memory of this context's device."""
+        img = image if isinstance(image, int) else _device_range(image, None)[0]
+        typ = types if isinstance(types, int) else _device_range(types, None)[0]
+        if isinstance(out, int):
+            dst, capacity = out, height * (linebytes + 1) if capacity is None else int(capacity)
+        else:
+            dst, capacity = _device_range(out, capacity)
+        fn = self.lib.zmx_png_filter_rows_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_size_t]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, img or None, linebytes, height, bytewidth, typ or None, dst or None, capacity),
+                    "zmx_png_filter_rows_device")
 
     def bitjoin_device(self, pieces, total_bits, dst, capacity=None):
         """zmx_bitjoin_device: pieces = [(src pointer, src_bit, nbits, dst_bit)] — bits [src_bit, src_bit + nbits) of the

@@ -1,52 +1,38 @@
-// Driver part: LodePNG's filter choices on the device (zmx_png.h, zmx_png_brute.h).  Holds
-// zmx_png_filter_types and zmx_png_filter_types_brute.  Needs drv_context.h (zmx_ctx, PoolScope).
+// Driver part: LodePNG's filter choices on the device (zmx_png.h, zmx_png_brute.h) and the filtered scanlines
+// (zmx_png_rows.h).  Holds zmx_png_filter_types, zmx_png_filter_types_brute, their device-image form
+// zmx_png_filter_types_device, zmx_png_filter_rows_device and the encoder's zmx_internal_png_scanlines.  Needs
+// drv_context.h (zmx_ctx, PoolScope) and drv_input.h (CheckDevicePointer).
 #pragma once
 
-extern "C" {
 // an image the kernels can index with 32 bits: rows of `linebytes`, at most `max_height` of them, pixels of 1 .. 8 bytes
 static bool PngGeometryOk(size_t linebytes, size_t height, size_t max_height, size_t bytewidth) {
   return linebytes != 0 && bytewidth != 0 && linebytes <= 0x7fffffffu && height <= max_height && bytewidth <= 8;
 }
 
-// PNG filter heuristics (zmx_png.h): the filter type LodePNG's MINSUM / ENTROPY strategy picks for every scanline.
-int zmx_png_filter_types(zmx_ctx* c, const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
-                         unsigned char* minsum_types, unsigned char* entropy_types) {
-  if (!c) return FailMsg("zmx_png_filter_types: no context");
-  if (height == 0 || (!minsum_types && !entropy_types)) return 0;
-  if (!PngGeometryOk(linebytes, height, 0x7fffffffu, bytewidth)) return FailMsg("zmx_png_filter_types: bad geometry");
-  DEVICE_ENTRY(c->device);
-  PoolScope tmp(c);
-  u8* d_img = nullptr;
-  u8* d_types = nullptr;
-  HIPCHK(tmp.Upload(&d_img, image, linebytes * height, "d_png_image"));
-  HIPCHK(tmp.AllocT(&d_types, 2 * height, "d_png_types"));
+// k_png_filter_types on an image in memory of the context's device: the types into d_minsum / d_entropy ([height] each,
+// either may be null), queued on the context's stream.
+static int PngHeuristicTypes(zmx_ctx* c, const u8* d_img, size_t linebytes, size_t height, size_t bytewidth, u8* d_minsum,
+                             u8* d_entropy) {
   PngFilterParams pp;
   pp.image = d_img;
   pp.linebytes = static_cast<u32>(linebytes);
   pp.height = static_cast<u32>(height);
   pp.bytewidth = static_cast<u32>(bytewidth);
-  pp.minsum = minsum_types ? d_types : nullptr;
-  pp.entropy = entropy_types ? d_types + height : nullptr;
+  pp.minsum = d_minsum;
+  pp.entropy = d_entropy;
   hipLaunchKernelGGL(k_png_filter_types, dim3(static_cast<unsigned>(height)), dim3(PNGF_THREADS), 0, c->stream, pp);
   KCHK(c, "k_png_filter_types");
-  if (minsum_types) HIPCHK(hipMemcpyAsync(minsum_types, d_types, height, hipMemcpyDeviceToHost, c->stream));
-  if (entropy_types) HIPCHK(hipMemcpyAsync(entropy_types, d_types + height, height, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 
-// LodePNG's brute-force row search (zmx_png_brute.h): the filter type LFS_BRUTE_FORCE picks for every scanline when the
-// rows are deflated with a window of `windowsize`.
-int zmx_png_filter_types_brute(zmx_ctx* c, const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
-                               unsigned windowsize, unsigned char* types) {
-  if (!c) return FailMsg("zmx_png_filter_types_brute: no context");
-  if (windowsize == 0 || windowsize > 32768u || (windowsize & (windowsize - 1u)) != 0) {   // LodePNG's errors 60 / 90
-    return FailMsg("zmx_png_filter_types_brute: the window must be a power of two of at most 32768");
-  }
-  if (height == 0) return 0;
-  if (!types) return FailMsg("zmx_png_filter_types_brute: no output");
-  if (!PngGeometryOk(linebytes, height, 0x7fffffffu / 5u, bytewidth)) return FailMsg("zmx_png_filter_types_brute: bad geometry");
-  DEVICE_ENTRY(c->device);
+static bool PngWindowOk(unsigned windowsize) {   // LodePNG's errors 60 / 90
+  return windowsize != 0 && windowsize <= 32768u && (windowsize & (windowsize - 1u)) == 0;
+}
+
+// k_png_brute + k_png_brute_pick on an image in memory of the context's device: the types into d_types[height], queued on
+// the context's stream; the scratch arrays are `tmp`'s.
+static int PngBruteTypes(zmx_ctx* c, PoolScope* tmp, const u8* d_img, size_t linebytes, size_t height, size_t bytewidth,
+                         unsigned windowsize, u8* d_types) {
   const u32 n = static_cast<u32>(linebytes), jobs = static_cast<u32>(5 * height);
   // the per-position arrays in the dynamic LDS when they fit, else in the scratch beside the head table and the results
   const u64 row_bytes = pngb_row_bytes(n);
@@ -60,15 +46,10 @@ int zmx_png_filter_types_brute(zmx_ctx* c, const unsigned char* image, size_t li
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_png_brute), hipFuncAttributeMaxDynamicSharedMemorySize,
                                static_cast<int>(PNGB_LDS_MAX)));
   }
-  PoolScope tmp(c);
-  u8* d_img = nullptr;
   u8* d_scratch = nullptr;
-  u8* d_types = nullptr;
   u64* d_sizes = nullptr;
-  HIPCHK(tmp.Upload(&d_img, image, linebytes * height, "d_png_image"));
-  HIPCHK(tmp.AllocT(&d_scratch, static_cast<size_t>(stride) * grid, "d_png_brute_scratch"));
-  HIPCHK(tmp.AllocT(&d_sizes, static_cast<size_t>(jobs), "d_png_brute_sizes"));
-  HIPCHK(tmp.AllocT(&d_types, height, "d_png_types"));
+  HIPCHK(tmp->AllocT(&d_scratch, static_cast<size_t>(stride) * grid, "d_png_brute_scratch"));
+  HIPCHK(tmp->AllocT(&d_sizes, static_cast<size_t>(jobs), "d_png_brute_sizes"));
   PngBruteParams pp;
   pp.image = d_img;
   pp.linebytes = n;
@@ -85,8 +66,195 @@ int zmx_png_filter_types_brute(zmx_ctx* c, const unsigned char* image, size_t li
   hipLaunchKernelGGL(k_png_brute_pick, dim3(static_cast<unsigned>((height + 255) / 256)), dim3(256), 0, c->stream,
                      static_cast<const u64*>(d_sizes), static_cast<u32>(height), d_types);
   KCHK(c, "k_png_brute_pick");
+  return 0;
+}
+
+// The types of `strategy` (ZMX_PNG_FILTER_ZERO .. _BRUTE) for an image in memory of the context's device, into
+// d_types[height] (the same device), queued on the context's stream; everything checked by the caller but the strategy
+// and the limits that depend on it.
+static int PngTypesOnDevice(zmx_ctx* c, PoolScope* tmp, const char* who, const u8* d_img, size_t linebytes, size_t height,
+                            size_t bytewidth, int strategy, unsigned windowsize, u8* d_types) {
+  const std::string w(who);
+  if (strategy >= ZMX_PNG_FILTER_ZERO && strategy <= ZMX_PNG_FILTER_FOUR) {
+    HIPCHK(hipMemsetAsync(d_types, strategy, height, c->stream));
+    return 0;
+  }
+  if (strategy == ZMX_PNG_FILTER_MINSUM) return PngHeuristicTypes(c, d_img, linebytes, height, bytewidth, d_types, nullptr);
+  if (strategy == ZMX_PNG_FILTER_ENTROPY) return PngHeuristicTypes(c, d_img, linebytes, height, bytewidth, nullptr, d_types);
+  if (strategy != ZMX_PNG_FILTER_BRUTE) return FailMsg(w + ": unknown strategy " + std::to_string(strategy));
+  if (!PngWindowOk(windowsize)) return FailMsg(w + ": the window must be a power of two of at most 32768");
+  if (!PngGeometryOk(linebytes, height, 0x7fffffffu / 5u, bytewidth)) return FailMsg(w + ": bad geometry");
+  return PngBruteTypes(c, tmp, d_img, linebytes, height, bytewidth, windowsize, d_types);
+}
+
+static bool PngStrategyKnown(int strategy) { return strategy >= ZMX_PNG_FILTER_ZERO && strategy <= ZMX_PNG_FILTER_BRUTE; }
+
+static bool RangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t alo = reinterpret_cast<uintptr_t>(a), blo = reinterpret_cast<uintptr_t>(b);
+  return na != 0 && nb != 0 && alo < blo + nb && blo < alo + na;
+}
+
+static thread_local double g_png_rows_ms = 0;   // (zmx_internal_png_rows_ms)
+
+// k_png_rows, the caller having checked everything: queued on the context's stream, then drained; the flag read.
+static int PngRowsOnDevice(zmx_ctx* c, PoolScope* tmp, const char* who, const u8* d_img, size_t linebytes, size_t height,
+                           size_t bytewidth, const u8* d_types, u8* d_out) {
+  u32* d_bad = nullptr;
+  HIPCHK(tmp->AllocT(&d_bad, 1, "d_png_bad_row"));
+  HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(u32), c->stream));
+  zamd::PngRowsParams P;
+  P.image = d_img;
+  P.types = d_types;
+  P.out = d_out;
+  P.linebytes = linebytes;
+  P.height = height;
+  P.bytewidth = static_cast<u32>(bytewidth);
+  P.bad_row = d_bad;
+  const bool timed = KernelTiming();
+  if (timed) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+  hipLaunchKernelGGL(k_png_rows, dim3(zamd::PngRowsGrid(static_cast<u64>(height) * (linebytes + 1))),
+                     dim3(zamd::kPngRowsThreads), 0, c->stream, P);
+  KCHK(c, "k_png_rows");
+  if (timed) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+  u32 bad = zamd::kPngRowsNoBadRow;
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    g_png_rows_ms = ms;
+  }
+  if (bad != zamd::kPngRowsNoBadRow) {
+    return FailMsg(std::string(who) + ": row " + std::to_string(bad) + " has a filter type above 4");
+  }
+  return 0;
+}
+
+extern "C" {
+double zmx_internal_png_rows_ms(void) { return g_png_rows_ms; }
+
+// PNG filter heuristics (zmx_png.h): the filter type LodePNG's MINSUM / ENTROPY strategy picks for every scanline.
+int zmx_png_filter_types(zmx_ctx* c, const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
+                         unsigned char* minsum_types, unsigned char* entropy_types) {
+  if (!c) return FailMsg("zmx_png_filter_types: no context");
+  if (height == 0 || (!minsum_types && !entropy_types)) return 0;
+  if (!PngGeometryOk(linebytes, height, 0x7fffffffu, bytewidth)) return FailMsg("zmx_png_filter_types: bad geometry");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  u8* d_img = nullptr;
+  u8* d_types = nullptr;
+  HIPCHK(tmp.Upload(&d_img, image, linebytes * height, "d_png_image"));
+  HIPCHK(tmp.AllocT(&d_types, 2 * height, "d_png_types"));
+  if (const int rc = PngHeuristicTypes(c, d_img, linebytes, height, bytewidth, minsum_types ? d_types : nullptr,
+                                       entropy_types ? d_types + height : nullptr)) {
+    return rc;
+  }
+  if (minsum_types) HIPCHK(hipMemcpyAsync(minsum_types, d_types, height, hipMemcpyDeviceToHost, c->stream));
+  if (entropy_types) HIPCHK(hipMemcpyAsync(entropy_types, d_types + height, height, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// LodePNG's brute-force row search (zmx_png_brute.h): the filter type LFS_BRUTE_FORCE picks for every scanline when the
+// rows are deflated with a window of `windowsize`.
+int zmx_png_filter_types_brute(zmx_ctx* c, const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
+                               unsigned windowsize, unsigned char* types) {
+  if (!c) return FailMsg("zmx_png_filter_types_brute: no context");
+  if (!PngWindowOk(windowsize)) return FailMsg("zmx_png_filter_types_brute: the window must be a power of two of at most 32768");
+  if (height == 0) return 0;
+  if (!types) return FailMsg("zmx_png_filter_types_brute: no output");
+  if (!PngGeometryOk(linebytes, height, 0x7fffffffu / 5u, bytewidth)) return FailMsg("zmx_png_filter_types_brute: bad geometry");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  u8* d_img = nullptr;
+  u8* d_types = nullptr;
+  HIPCHK(tmp.Upload(&d_img, image, linebytes * height, "d_png_image"));
+  HIPCHK(tmp.AllocT(&d_types, height, "d_png_types"));
+  if (const int rc = PngBruteTypes(c, &tmp, d_img, linebytes, height, bytewidth, windowsize, d_types)) return rc;
   HIPCHK(hipMemcpyAsync(types, d_types, height, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+// The row searches on an image that lies in device memory; the types stay there.
+int zmx_png_filter_types_device(zmx_ctx* c, const void* d_image, size_t linebytes, size_t height, size_t bytewidth,
+                                int strategy, unsigned windowsize, void* d_types) {
+  const char* who = "zmx_png_filter_types_device";
+  if (!c) return FailMsg(std::string(who) + ": no context");
+  if (!PngStrategyKnown(strategy)) return FailMsg(std::string(who) + ": unknown strategy " + std::to_string(strategy));
+  if (height == 0) return 0;
+  if (!PngGeometryOk(linebytes, height, 0x7fffffffu, bytewidth)) return FailMsg(std::string(who) + ": bad geometry");
+  int img_device = -1, types_device = -1;
+  if (const int rc = CheckDevicePointer(who, d_image, linebytes * height, &img_device)) return rc;
+  if (const int rc = CheckDevicePointer(who, d_types, height, &types_device)) return rc;
+  if (img_device != c->device || types_device != c->device) return FailMsg(std::string(who) + ": memory of another device than the context's");
+  if (RangesOverlap(d_image, linebytes * height, d_types, height)) return FailMsg(std::string(who) + ": the types overlap the image");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  const int rc = PngTypesOnDevice(c, &tmp, who, static_cast<const u8*>(d_image), linebytes, height, bytewidth, strategy,
+                                  windowsize, static_cast<u8*>(d_types));
+  // (what was queued reads the scratch arrays: drained before `tmp` gives them back, on the failing paths too)
+  const hipError_t e = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  HIPCHK(e);
+  return 0;
+}
+
+// The filtered scanlines (zmx_png_rows.h).
+int zmx_png_filter_rows_device(zmx_ctx* c, const void* d_image, size_t linebytes, size_t height, size_t bytewidth,
+                               const void* d_types, void* d_out, size_t capacity) {
+  const char* who = "zmx_png_filter_rows_device";
+  g_png_rows_ms = 0;
+  if (!c) return FailMsg(std::string(who) + ": no context");
+  if (height == 0) return 0;
+  if (!PngGeometryOk(linebytes, height, 0x7fffffffu, bytewidth)) return FailMsg(std::string(who) + ": bad geometry");
+  const size_t total = height * (linebytes + 1);
+  if (capacity < total) {
+    return FailMsg(std::string(who) + ": the output takes " + std::to_string(total) + " bytes, the capacity is " + std::to_string(capacity));
+  }
+  int img_device = -1, types_device = -1, out_device = -1;
+  if (const int rc = CheckDevicePointer(who, d_image, linebytes * height, &img_device)) return rc;
+  if (const int rc = CheckDevicePointer(who, d_types, height, &types_device)) return rc;
+  if (const int rc = CheckDevicePointer(who, d_out, total, &out_device)) return rc;
+  if (img_device != c->device || types_device != c->device || out_device != c->device) {
+    return FailMsg(std::string(who) + ": memory of another device than the context's");
+  }
+  if (RangesOverlap(d_out, total, d_image, linebytes * height)) return FailMsg(std::string(who) + ": the output overlaps the image");
+  if (RangesOverlap(d_out, total, d_types, height)) return FailMsg(std::string(who) + ": the output overlaps the types");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  return PngRowsOnDevice(c, &tmp, who, static_cast<const u8*>(d_image), linebytes, height, bytewidth,
+                         static_cast<const u8*>(d_types), static_cast<u8*>(d_out));
+}
+
+// zmx_png_encode_device's device part (host/png_encode.cc): the types of `strategy` — ZMX_PNG_FILTER_PREDEFINED: the
+// `height` host bytes at `predefined`, checked by the caller — and the scanlines of d_image into d_out, a buffer of the
+// caller's own of height * (linebytes + 1) bytes on the context's device.  The image is checked as the device entries
+// check theirs.
+int zmx_internal_png_scanlines(zmx_ctx* c, const void* d_image, size_t linebytes, size_t height, size_t bytewidth, int strategy,
+                               unsigned windowsize, const unsigned char* predefined, void* d_out) {
+  const char* who = "zmx_png_encode_device";
+  if (!PngGeometryOk(linebytes, height, 0x7fffffffu, bytewidth) || height == 0) return FailMsg(std::string(who) + ": bad geometry");
+  int img_device = -1;
+  if (const int rc = CheckDevicePointer(who, d_image, linebytes * height, &img_device)) return rc;
+  if (img_device != c->device) return FailMsg(std::string(who) + ": the image is memory of another device than the context's");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  u8* d_types = nullptr;
+  int rc = 0;
+  if (strategy == ZMX_PNG_FILTER_PREDEFINED) {
+    const hipError_t e = tmp.Upload(&d_types, predefined, height, "d_png_types");
+    if (e != hipSuccess) rc = Fail("Upload(d_png_types)", e, __FILE__, __LINE__);
+  } else {
+    const hipError_t e = tmp.AllocT(&d_types, height, "d_png_types");
+    if (e != hipSuccess) rc = Fail("AllocT(d_png_types)", e, __FILE__, __LINE__);
+    else rc = PngTypesOnDevice(c, &tmp, who, static_cast<const u8*>(d_image), linebytes, height, bytewidth, strategy, windowsize, d_types);
+  }
+  if (rc == 0) {
+    // (drains the stream whichever way it returns once the kernel is queued)
+    rc = PngRowsOnDevice(c, &tmp, who, static_cast<const u8*>(d_image), linebytes, height, bytewidth, d_types, static_cast<u8*>(d_out));
+  }
+  if (rc != 0) (void)hipStreamSynchronize(c->stream);   // what was queued may still read `tmp`'s arrays
+  return rc;
 }
 }  // extern "C"

@@ -35,6 +35,8 @@
 #include "zmx_gather.h"      // many device buffers end to end
 #define ZMX_BITJOIN_KERNELS
 #include "zmx_bitjoin.h"     // many bit strings joined into one
+#define ZMX_PNG_ROWS_KERNELS
+#include "zmx_png_rows.h"    // the filtered scanlines of a PNG
 #include "zmx_knobs.h"       // the ZOPFLI_AMD_* switches
 #include "zopfli_amd.h"
 #include "../host/deal.h"
@@ -54,6 +56,6 @@
 #include "drv_stores.h"      // store download, verify, encode
 #include "drv_bitjoin.h"     // output that stays on the device: the bit join, the bit writer without the way down
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
-#include "drv_png.h"         // the two PNG filter entries
+#include "drv_png.h"         // the PNG filter entries: row searches on host and device images, the filtered scanlines
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries
 #include "drv_probes.h"      // the parity probes: digest, longest match, hash links, length array, DP rows

@@ -4,7 +4,7 @@
 // layer defines them and includes this header, as every caller does and as the host test library's stand-in for the
 // device layer does (tests/hostlib/zmx_oracle_backend.cc), so a parameter list that changes on one side only does not
 // compile.  Device to host: the statistics, which the host layer owns.
-// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the four
+// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the five
 // functions that tests and tools reach from outside (here and nowhere else).
 #pragma once
 #include <cstddef>
@@ -79,6 +79,14 @@ int zmx_internal_bitjoin_many_literals(zmx_ctx* ctx, const unsigned char* litera
 // zmx_internal_device_pointer refuses of any of them, and a range on another device than the ones before it.
 int zmx_internal_device_pointers_one_device(const char* who, size_t n, const void* const* p, const size_t* nbytes, int* device);
 
+// ---- a PNG from an image in device memory (png_encode.cc)
+// The filter types of `strategy` (a ZMX_PNG_FILTER_*; _BRUTE with window `windowsize`; _PREDEFINED: the `height` host
+// bytes at `predefined`, each at most 4) and then the filtered scanlines of d_image (zmx_png_filter_rows_device) into
+// d_out: height * (linebytes + 1) bytes of the context's device that the caller owns.  The image is checked as
+// zmx_png_filter_rows_device checks its own.  0, or -1 with the error set.
+int zmx_internal_png_scanlines(zmx_ctx* ctx, const void* d_image, size_t linebytes, size_t height, size_t bytewidth, int strategy,
+                               unsigned windowsize, const unsigned char* predefined, void* d_out);
+
 // ---- for tests and tools
 // The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
 // (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing); else 0.  For
@@ -86,6 +94,8 @@ int zmx_internal_device_pointers_one_device(const char* who, size_t n, const voi
 ZMX_INTERNAL_EXPORT double zmx_internal_gather_ms(void);
 // The same for the calling thread's last zmx_bitjoin_device: k_bitjoin alone.  For tools/device_output.py.
 ZMX_INTERNAL_EXPORT double zmx_internal_bitjoin_ms(void);
+// The same for k_png_rows of the calling thread's last zmx_png_filter_rows_device.  For tools/png_device.py.
+ZMX_INTERNAL_EXPORT double zmx_internal_png_rows_ms(void);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
 // squeeze run computes them — *wmax, *tiemask —, no device involved.
 ZMX_INTERNAL_EXPORT void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask);
