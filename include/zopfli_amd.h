@@ -421,8 +421,8 @@ int zmx_png_filter_rows_device(zmx_ctx* ctx, const void* d_image, size_t linebyt
  * colour type other than 0, 2, 4, 6, a bit depth other than 8 or 16, an unknown strategy, _PREDEFINED without types or
  * with a type above 4, and what zmx_png_filter_rows_device refuses of the pixels' pointer.  Any later failure leaves them
  * unchanged as well.
- * Out of scope: palette and sub-8-bit images, interlace, colour-type reduction, ancillary chunks, zopflipng's automatic
- * strategy trial (libzopflipng_amd.so does those, from a file), a PNG left in device memory. */
+ * Out of scope: palette input, interlace, ancillary chunks, zopflipng's automatic strategy trial (libzopflipng_amd.so
+ * does those, from a file), a PNG left in device memory.  Colour-type reduction is zmx_png_optimize_device's. */
 typedef struct zmx_png_image {
   const void* d_pixels;  /* height rows of linebytes bytes, PNG byte order (16-bit samples big-endian), rows back to back */
   uint32_t width, height, colortype /* 0, 2, 4, 6 */, bitdepth /* 8, 16 */;
@@ -437,6 +437,76 @@ int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png_image* ima
  * by a call that fails.  n = 0 returns 0. */
 int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
                                 unsigned char** out, size_t* outsize);
+
+/* -------- colour-type reduction: what zopflipng does to an image without --keepcolortype
+ *
+ * LodePNG's colour statistics (lodepng.cpp lodepng_compute_color_stats) of an image in device memory, every rule stated
+ * on the pixel's RGBA expansion as zopflipng sees it (grey gives r = g = b, no alpha channel gives the maximum):
+ *   colored    some pixel has r != g or r != b
+ *   alpha      some alpha is neither 0 nor the maximum, or the transparent pixels have more than one RGB, or an opaque
+ *              pixel has theirs
+ *   key        otherwise, when some alpha is 0: the transparent pixels' one RGB in key_r, key_g, key_b as 16-bit values
+ *              (an 8-bit value with its byte twice); zeros without a key
+ *   bits       1, 2, 4 or 8: what the grey values need (8 when colored or alpha); 16 for a 16-bit image some sample of
+ *              which has two different bytes — the statistics are then taken on 16-bit values and no colours are counted
+ *              (numcolors 0); a 16-bit image whose bytes are all equal counts as the 8-bit image of its high bytes
+ *   numcolors  the distinct RGBA values, 257 for "more than 256"; palette holds them r, g, b, a in the order of their
+ *              first appearance in raster order (zeros behind them, and all zeros for 257)
+ * k_png_color_stats (device/zmx_png_color.h) reads the image once with at most 2048 workgroups; k_png_color_key reads
+ * it again only when a key is possible.  A few kilobytes come down, no pixel does; the result is the same from run to
+ * run.  The image is refused (ZMX_ERR_REFUSED) as zmx_png_encode_device refuses its own, its pointer as
+ * zmx_png_filter_rows_device refuses one, and an image of 2^32 pixels or more.  Synchronous. */
+typedef struct zmx_png_color_stats {
+  uint32_t colored, key, alpha, numcolors, bits;
+  uint16_t key_r, key_g, key_b, reserved;
+  unsigned char palette[1024];
+} zmx_png_color_stats;
+int zmx_png_color_stats_device(zmx_ctx* ctx, const zmx_png_image* image, zmx_png_color_stats* out);
+
+/* The colour mode LodePNG's auto_choose_color takes for these statistics of an image of `numpixels` pixels: host
+ * arithmetic only.  colortype 0, 2, 3, 4 or 6; bitdepth 1, 2, 4, 8 or 16; for colour type 3 the palette (palettesize
+ * entries r, g, b, a); for 0 and 2 the key where key_defined, masked to the depth.  A key on at most 16 pixels becomes
+ * alpha, a palette is not taken for fewer than two pixels a colour or where grey is no deeper.  -1 (ZMX_ERR_REFUSED) for a
+ * null argument. */
+typedef struct zmx_png_color_mode {
+  uint32_t colortype, bitdepth, palettesize, key_defined;
+  uint16_t key_r, key_g, key_b, reserved;
+  unsigned char palette[1024];
+} zmx_png_color_mode;
+int zmx_png_choose_color(const zmx_png_color_stats* stats, uint64_t numpixels, zmx_png_color_mode* out);
+
+/* The image in another colour mode (lodepng.cpp lodepng_convert), device memory to device memory: d_out gets `height`
+ * rows of (width * bpp + 7) / 8 bytes back to back, bpp = channels * bitdepth (one channel for a palette).  Grey below 8
+ * bits keeps the top bits of r, a palette pixel becomes its colour's rank (of two equal entries the later one), pixels
+ * below 8 bits are packed most significant bits first and every row is padded with zero bits; 8-bit output of a 16-bit
+ * image keeps the high bytes; channels the mode has not are dropped without a look at them (the key is the container's
+ * business).  k_png_convert writes every byte of the output exactly once and none outside; d_out may have any alignment.
+ * Refused before any launch (ZMX_ERR_REFUSED): what zmx_png_color_stats_device refuses of the image, a mode PNG has not, a
+ * palette of 0 or more than 2^bitdepth entries, 16-bit output of an 8-bit image, a `capacity` below the output's size, an
+ * output that is no device memory of the context's device or overlaps the image.  A pixel whose colour the palette lacks
+ * is found by the kernel: the call fails (ZMX_ERR_REFUSED), the message names the first such pixel ("pixel N"), and what
+ * d_out then holds is not defined.  Synchronous. */
+int zmx_png_convert_device(zmx_ctx* ctx, const zmx_png_image* image, const zmx_png_color_mode* mode, void* d_out, size_t capacity);
+
+/* zmx_png_encode_device with the colour mode reduced first: *out, *outsize end holding the file that
+ *   zopflipng --always_zopflify --filters=<strategy>
+ * (no --keepcolortype) writes for a PNG of these pixels that has no other chunks — the signature, IHDR, PLTE for a
+ * palette, tRNS for a palette with alpha or a key, ONE IDAT, IEND — byte for byte under the same conditions.  The mode is
+ * zmx_png_choose_color's of the image's statistics; where that is a palette and the file comes out below 4096 bytes, a
+ * second file is made as RGB or RGBA at 8 bits (zopflipng_lib.cc TryOptimize) and replaces the first when it is strictly
+ * smaller.  The strategy applies to palette and sub-8-bit rows as to any other, with a left neighbour one byte away.
+ * Where the chosen mode is the image's own nothing is converted and the file is zmx_png_encode_device's.  No pixel visits
+ * the host.  Conventions, refusals and failure behaviour are zmx_png_encode_device's; an image of 2^32 pixels or more
+ * is refused as well.
+ * Out of scope: palette INPUT, interlace, --lossy_transparent, --lossy_8bit, ancillary chunks, zopflipng's automatic
+ * strategy trial (libzopflipng_amd.so does those, from a file), a PNG left in device memory. */
+int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                            const unsigned char* predefined, unsigned char** out, size_t* outsize);
+/* n images in one call: every file is the single call's.  Statistics and conversion run image by image on one hold of a
+ * context, ONE zmx_compress_device_batch(ZOPFLI_FORMAT_ZLIB) runs over all scanlines and one more over the second tries,
+ * if any image takes one.  Otherwise as zmx_png_encode_device_batch. */
+int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                  unsigned char** out, size_t* outsize);
 
 /* Parity probe over whole tables: two 64-bit sums over all positions of a hash of the logical content of the match
  * records (block, position, length, distance, same, literal, every change point of sublen).  Equal digests of two

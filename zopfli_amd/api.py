@@ -451,6 +451,88 @@ def png_encode_device_batch(images, strategy="e", options=None, lib=None):
     return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
 
 
+class PngColorStats(ctypes.Structure):
+    """zmx_png_color_stats; `colors()` the palette's numcolors entries (r, g, b, a), none for 0 and 257."""
+    _fields_ = [("colored", ctypes.c_uint32), ("key", ctypes.c_uint32), ("alpha", ctypes.c_uint32), ("numcolors", ctypes.c_uint32),
+                ("bits", ctypes.c_uint32), ("key_r", ctypes.c_uint16), ("key_g", ctypes.c_uint16), ("key_b", ctypes.c_uint16),
+                ("reserved", ctypes.c_uint16), ("palette", ctypes.c_ubyte * 1024)]
+
+    def colors(self):
+        n = self.numcolors if self.numcolors <= 256 else 0
+        return [tuple(self.palette[4 * i:4 * i + 4]) for i in range(n)]
+
+
+class PngColorMode(ctypes.Structure):
+    """zmx_png_color_mode; `colors()` the palettesize entries (r, g, b, a)."""
+    _fields_ = [("colortype", ctypes.c_uint32), ("bitdepth", ctypes.c_uint32), ("palettesize", ctypes.c_uint32),
+                ("key_defined", ctypes.c_uint32), ("key_r", ctypes.c_uint16), ("key_g", ctypes.c_uint16), ("key_b", ctypes.c_uint16),
+                ("reserved", ctypes.c_uint16), ("palette", ctypes.c_ubyte * 1024)]
+
+    def colors(self):
+        return [tuple(self.palette[4 * i:4 * i + 4]) for i in range(min(self.palettesize, 256))]
+
+
+def png_choose_color(stats, numpixels, lib=None):
+    """zmx_png_choose_color: the colour mode LodePNG takes for these statistics (a PngColorStats) of an image of
+    `numpixels` pixels: a PngColorMode.  Host arithmetic only."""
+    lib = lib or library()
+    mode = PngColorMode()
+    fn = lib.zmx_png_choose_color
+    fn.argtypes = [ctypes.POINTER(PngColorStats), ctypes.c_uint64, ctypes.POINTER(PngColorMode)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(stats), int(numpixels), ctypes.byref(mode)) != 0:
+        raise RuntimeError("zmx_png_choose_color: " + (lib.zmx_last_error() or b"").decode())
+    return mode
+
+
+def png_optimize_device(image, strategy="e", options=None, predefined=None, lib=None):
+    """zmx_png_optimize_device: png_encode_device with the colour mode reduced first — the file `zopflipng
+    --always_zopflify --filters=<strategy>` (no --keepcolortype) writes for the image: grey, a palette, a key or fewer
+    bits where the pixels allow it, and RGB or RGBA instead of a palette where that makes a small file smaller.
+    Arguments, result and errors as png_encode_device's."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    im = _png_image(image)
+    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
+    if types is not None and len(types) != im.height:
+        raise ValueError(f"{len(types)} predefined types for {im.height} rows")
+    out, outsize = _u8p(), ctypes.c_size_t(0)
+    fn = lib.zmx_png_optimize_device
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p,
+                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, ctypes.byref(out), ctypes.byref(outsize)) != 0:
+        raise RuntimeError("zmx_png_optimize_device: " + (lib.zmx_last_error() or b"").decode())
+    return _take(out, outsize)
+
+
+def png_optimize_device_batch(images, strategy="e", options=None, lib=None):
+    """zmx_png_optimize_device_batch: one file per image, each the one png_optimize_device gives, from one call.
+    Arguments as png_encode_device_batch's."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    ims = [_png_image(image, sync=False) for image in images]
+    devices = {}
+    for image in images:
+        if not isinstance(image, (tuple, list)) and type(image).__module__.split(".")[0] == "torch":
+            devices[str(image.device)] = image.device
+    if devices:
+        import torch
+        for device in devices.values():
+            torch.cuda.current_stream(device).synchronize()
+    n = len(ims)
+    arr = (PngImage * max(n, 1))(*ims)
+    outs = (_u8p * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    fn = lib.zmx_png_optimize_device_batch
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_int,
+                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), outs, outsizes) != 0:
+        raise RuntimeError("zmx_png_optimize_device_batch: " + (lib.zmx_last_error() or b"").decode())
+    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+
+
 def last_output_traffic(lib=None):
     """zmx_last_output_traffic: of this thread's last call, the stream's bytes device to host, its bytes host to device,
     the blocks whose symbols' bits never left the device, the blocks the host wrote and uploaded."""
@@ -629,6 +711,32 @@ class Context:
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, img or None, linebytes, height, bytewidth, typ or None, dst or None, capacity),
                     "zmx_png_filter_rows_device")
+
+    def png_color_stats_device(self, image):
+        """zmx_png_color_stats_device: LodePNG's colour statistics of an image in memory of this context's device
+        (`image` as png_encode_device takes it): a PngColorStats."""
+        im = _png_image(image)
+        stats = PngColorStats()
+        fn = self.lib.zmx_png_color_stats_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngImage), ctypes.POINTER(PngColorStats)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, ctypes.byref(im), ctypes.byref(stats)), "zmx_png_color_stats_device")
+        return stats
+
+    def png_convert_device(self, image, mode, out, capacity=None):
+        """zmx_png_convert_device: the image in the colour mode `mode` (a PngColorMode, png_choose_color's or the caller's)
+        into `out`, a tensor or an integer pointer with `capacity` bytes (an integer pointer without one: exactly the
+        output's size), memory of this context's device: height rows of (width * bpp + 7) // 8 bytes."""
+        im = _png_image(image)
+        if isinstance(out, int):
+            bpp = (1 if mode.colortype == 3 else {0: 1, 2: 3, 4: 2, 6: 4}.get(mode.colortype, 0)) * mode.bitdepth
+            dst, capacity = out, im.height * ((im.width * bpp + 7) // 8) if capacity is None else int(capacity)
+        else:
+            dst, capacity = _device_range(out, capacity)
+        fn = self.lib.zmx_png_convert_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngImage), ctypes.POINTER(PngColorMode), ctypes.c_void_p, ctypes.c_size_t]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, ctypes.byref(im), ctypes.byref(mode), dst or None, capacity), "zmx_png_convert_device")
 
     def bitjoin_device(self, pieces, total_bits, dst, capacity=None):
         """zmx_bitjoin_device: pieces = [(src pointer, src_bit, nbits, dst_bit)] — bits [src_bit, src_bit + nbits) of the

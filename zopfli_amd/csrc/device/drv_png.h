@@ -130,8 +130,200 @@ static int PngRowsOnDevice(zmx_ctx* c, PoolScope* tmp, const char* who, const u8
   return 0;
 }
 
+// ---- colour statistics and conversion (zmx_png_color.h)
+static_assert(sizeof(zamd::PngColorSummary) == sizeof(zmx_png_color_stats), "PngColorSummary is zmx_png_color_stats");
+
+static thread_local double g_png_color_ms[3] = {0, 0, 0};   // k_png_color_stats, k_png_color_key, k_png_convert (zmx_internal_png_color_ms)
+
+// What every colour entry refuses of an image before its pointer is looked at; *nbytes its size.
+static int PngColorImageOf(const char* who, const zmx_png_image* image, zamd::PngColorImage* I, size_t* nbytes) {
+  const std::string w(who);
+  if (!image) return FailMsg(w + ": no image");
+  if (image->width == 0 || image->height == 0) return FailMsg(w + ": width or height 0");
+  const u32 ct = image->colortype, depth = image->bitdepth;
+  if (!(ct == 0 || ct == 2 || ct == 4 || ct == 6) || !(depth == 8 || depth == 16)) {
+    return FailMsg(w + ": colour type " + std::to_string(ct) + " at " + std::to_string(depth) + " bits is not taken (0, 2, 4, 6 at 8 or 16)");
+  }
+  const u64 linebytes = static_cast<u64>(image->width) * zamd::PngColorPixelBytes(ct, depth);
+  if (!PngGeometryOk(linebytes, image->height, 0x7fffffffu, zamd::PngColorPixelBytes(ct, depth))) return FailMsg(w + ": bad geometry");
+  const u64 numpixels = static_cast<u64>(image->width) * image->height;
+  if (numpixels > 0xffffffffull) return FailMsg(w + ": an image of 2^32 pixels or more");
+  I->pixels = static_cast<const u8*>(image->d_pixels);
+  I->numpixels = numpixels;
+  I->width = image->width;
+  I->height = image->height;
+  I->colortype = ct;
+  I->bitdepth = depth;
+  *nbytes = static_cast<size_t>(linebytes * image->height);
+  return 0;
+}
+
+// The statistics of an image the caller has checked: one launch, the state read, k_png_color_key and a second read where
+// a key is possible.  Drains the context's stream.
+static int PngColorStatsOnDevice(zmx_ctx* c, PoolScope* tmp, const zamd::PngColorImage& I, zmx_png_color_stats* out) {
+  zamd::PngColorState* d_state = nullptr;
+  HIPCHK(tmp->AllocT(&d_state, 1, "d_png_color_state"));
+  u8* const raw = reinterpret_cast<u8*>(d_state);
+  const size_t zeros = offsetof(zamd::PngColorState, key_min);
+  HIPCHK(hipMemsetAsync(raw, 0, zeros, c->stream));
+  HIPCHK(hipMemsetAsync(raw + zeros, 0xff, sizeof(zamd::PngColorState) - zeros, c->stream));
+  const bool timed = KernelTiming();
+  const u32 grid = zamd::PngColorGrid(I);
+  if (timed) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+  hipLaunchKernelGGL(k_png_color_stats, dim3(grid), dim3(zamd::kPngColorThreads), 0, c->stream, I, d_state);
+  KCHK(c, "k_png_color_stats");
+  if (timed) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+  zamd::PngColorState state;
+  HIPCHK(hipMemcpyAsync(&state, d_state, sizeof(state), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    g_png_color_ms[0] = ms;
+  }
+  if (zamd::PngColorWantsKeyPass(state)) {
+    if (timed) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    hipLaunchKernelGGL(k_png_color_key, dim3(grid), dim3(zamd::kPngColorThreads), 0, c->stream, I, state.key_min, d_state);
+    KCHK(c, "k_png_color_key");
+    if (timed) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(hipMemcpyAsync(&state.key_clash, &d_state->key_clash, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (timed) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+      g_png_color_ms[1] = ms;
+    }
+  }
+  zamd::PngColorSummary sum;
+  zamd::PngColorFinish(state, I.bitdepth, &sum);
+  std::memcpy(out, &sum, sizeof(sum));
+  return 0;
+}
+
+// k_png_convert, the caller having checked everything: the image in `mode` into d_out.  Drains the context's stream.
+static int PngConvertOnDevice(zmx_ctx* c, PoolScope* tmp, const char* who, const zamd::PngColorImage& I, const zmx_png_color_mode& mode,
+                              u8* d_out) {
+  u32* d_bad = nullptr;
+  u8* d_palette = nullptr;
+  HIPCHK(tmp->AllocT(&d_bad, 1, "d_png_bad_pixel"));
+  HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(u32), c->stream));
+  if (mode.colortype == 3) HIPCHK(tmp->Upload(&d_palette, mode.palette, 4 * static_cast<size_t>(mode.palettesize), "d_png_palette"));
+  zamd::PngConvParams P;
+  P.in = I;
+  P.out = d_out;
+  P.rowbytes = zamd::PngConvRowBytes(I.width, mode.colortype, mode.bitdepth);
+  P.colortype = mode.colortype;
+  P.bitdepth = mode.bitdepth;
+  P.palettesize = mode.colortype == 3 ? mode.palettesize : 0;
+  P.palette = d_palette;
+  P.bad_pixel = d_bad;
+  const bool timed = KernelTiming();
+  if (timed) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+  hipLaunchKernelGGL(k_png_convert, dim3(zamd::PngConvGrid(P.rowbytes * I.height)), dim3(zamd::kPngColorThreads), 0, c->stream, P);
+  KCHK(c, "k_png_convert");
+  if (timed) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+  u32 bad = zamd::kPngColorNoBadPixel;
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (timed) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    g_png_color_ms[2] = ms;
+  }
+  if (bad != zamd::kPngColorNoBadPixel) {
+    return FailMsg(std::string(who) + ": pixel " + std::to_string(bad) + " has a colour that is not in the palette");
+  }
+  return 0;
+}
+
 extern "C" {
 double zmx_internal_png_rows_ms(void) { return g_png_rows_ms; }
+void zmx_internal_png_color_ms(double out[3]) {
+  for (int k = 0; k < 3; ++k) out[k] = g_png_color_ms[k];
+}
+
+int zmx_png_color_stats_device(zmx_ctx* c, const zmx_png_image* image, zmx_png_color_stats* out) {
+  const char* who = "zmx_png_color_stats_device";
+  g_png_color_ms[0] = g_png_color_ms[1] = 0;
+  if (!c) return FailMsg(std::string(who) + ": no context");
+  if (!out) return FailMsg(std::string(who) + ": no output");
+  zamd::PngColorImage I;
+  size_t nbytes = 0;
+  if (const int rc = PngColorImageOf(who, image, &I, &nbytes)) return rc;
+  int img_device = -1;
+  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (img_device != c->device) return FailMsg(std::string(who) + ": memory of another device than the context's");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  const int rc = PngColorStatsOnDevice(c, &tmp, I, out);
+  if (rc != 0) (void)hipStreamSynchronize(c->stream);   // what was queued may still use `tmp`'s arrays
+  return rc;
+}
+
+int zmx_png_convert_device(zmx_ctx* c, const zmx_png_image* image, const zmx_png_color_mode* mode, void* d_out, size_t capacity) {
+  const char* who = "zmx_png_convert_device";
+  g_png_color_ms[2] = 0;
+  if (!c) return FailMsg(std::string(who) + ": no context");
+  if (!mode) return FailMsg(std::string(who) + ": no mode");
+  zamd::PngColorImage I;
+  size_t nbytes = 0;
+  if (const int rc = PngColorImageOf(who, image, &I, &nbytes)) return rc;
+  if (!zamd::PngModeOk(*mode, I.bitdepth)) {
+    return FailMsg(std::string(who) + ": colour type " + std::to_string(mode->colortype) + " at " + std::to_string(mode->bitdepth) +
+                   " bits with a palette of " + std::to_string(mode->palettesize) + " is no mode this image converts to");
+  }
+  const u64 rowbytes = zamd::PngConvRowBytes(I.width, mode->colortype, mode->bitdepth);
+  if (rowbytes > 0x7fffffffu) return FailMsg(std::string(who) + ": bad geometry");
+  const size_t total = static_cast<size_t>(rowbytes * I.height);
+  if (capacity < total) {
+    return FailMsg(std::string(who) + ": the output takes " + std::to_string(total) + " bytes, the capacity is " + std::to_string(capacity));
+  }
+  int img_device = -1, out_device = -1;
+  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (const int rc = CheckDevicePointer(who, d_out, total, &out_device)) return rc;
+  if (img_device != c->device || out_device != c->device) return FailMsg(std::string(who) + ": memory of another device than the context's");
+  if (RangesOverlap(d_out, total, image->d_pixels, nbytes)) return FailMsg(std::string(who) + ": the output overlaps the image");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  const int rc = PngConvertOnDevice(c, &tmp, who, I, *mode, static_cast<u8*>(d_out));
+  if (rc != 0) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+// zmx_png_optimize_device's device part (host/png_optimize.cc): the image in `mode` (null: as it is) in memory of the
+// context's pool, then the types of `strategy` and the filtered scanlines of that into d_out, a buffer of the caller's
+// own of height * (rowbytes + 1) bytes on the context's device.  The caller has checked the image and the mode.
+int zmx_internal_png_reduced_scanlines(zmx_ctx* c, const zmx_png_image* image, const zmx_png_color_mode* mode, int strategy,
+                                       unsigned windowsize, const unsigned char* predefined, void* d_out) {
+  const char* who = "zmx_png_optimize_device";
+  zamd::PngColorImage I;
+  size_t nbytes = 0;
+  if (const int rc = PngColorImageOf(who, image, &I, &nbytes)) return rc;
+  if (!mode) {
+    return zmx_internal_png_scanlines(c, image->d_pixels, nbytes / I.height, I.height, zamd::PngColorPixelBytes(I.colortype, I.bitdepth),
+                                      strategy, windowsize, predefined, d_out);
+  }
+  if (!zamd::PngModeOk(*mode, I.bitdepth)) return FailMsg(std::string(who) + ": no mode this image converts to");
+  const u64 rowbytes = zamd::PngConvRowBytes(I.width, mode->colortype, mode->bitdepth);
+  const u32 bpp = zamd::PngConvBpp(mode->colortype, mode->bitdepth);
+  int img_device = -1;
+  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (img_device != c->device) return FailMsg(std::string(who) + ": the image is memory of another device than the context's");
+  u8* d_conv = nullptr;
+  {
+    DEVICE_ENTRY(c->device);
+    PoolScope tmp(c);
+    HIPCHK(tmp.AllocT(&d_conv, static_cast<size_t>(rowbytes * I.height), "d_png_converted"));
+    int rc = PngConvertOnDevice(c, &tmp, who, I, *mode, d_conv);
+    if (rc == 0) {
+      rc = zmx_internal_png_scanlines(c, d_conv, static_cast<size_t>(rowbytes), I.height, bpp < 8 ? 1 : bpp / 8, strategy, windowsize,
+                                      predefined, d_out);
+    }
+    if (rc != 0) (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+}
+
 
 // PNG filter heuristics (zmx_png.h): the filter type LodePNG's MINSUM / ENTROPY strategy picks for every scanline.
 int zmx_png_filter_types(zmx_ctx* c, const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,

@@ -37,10 +37,13 @@
 #include "zmx_bitjoin.h"     // many bit strings joined into one
 #define ZMX_PNG_ROWS_KERNELS
 #include "zmx_png_rows.h"    // the filtered scanlines of a PNG
+#define ZMX_PNG_COLOR_KERNELS
+#include "zmx_png_color.h"   // LodePNG's colour statistics and colour conversion
 #include "zmx_knobs.h"       // the ZOPFLI_AMD_* switches
 #include "zopfli_amd.h"
 #include "../host/deal.h"
 #include "../host/entry_checks.h"
+#include "../host/png_color_choose.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
 #include "../host/zmx_internal.h"
@@ -56,6 +59,6 @@
 #include "drv_stores.h"      // store download, verify, encode
 #include "drv_bitjoin.h"     // output that stays on the device: the bit join, the bit writer without the way down
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
-#include "drv_png.h"         // the PNG filter entries: row searches on host and device images, the filtered scanlines
+#include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries
 #include "drv_probes.h"      // the parity probes: digest, longest match, hash links, length array, DP rows

@@ -109,18 +109,78 @@ inline void PngPrefix(uint32_t width, uint32_t height, uint32_t colortype, uint3
 // lodepng_zlib_compress: FLEVEL 0, and the FCHECK that makes 0x7801 a multiple of 31), the IDAT's length is filled in, and
 // `trailer` gets the kPngTrailerBytes bytes that end the file.  False, with nothing changed, when the stream cannot be
 // one (shorter than a header and an Adler-32, or not 78 DA) or does not fit a chunk's 31-bit length.
-inline bool PngClose(unsigned char* file, size_t size, unsigned char* trailer, size_t crc_piece = kPngCrcPiece) {
-  if (size < kPngPrefixBytes + 6) return false;
-  const size_t n = size - kPngPrefixBytes;
-  unsigned char* zlib = file + kPngPrefixBytes;
+// (PngCloseAt: the same behind a prefix of `prefix_bytes` bytes, PngPrefixReduced's)
+inline bool PngCloseAt(unsigned char* file, size_t size, size_t prefix_bytes, unsigned char* trailer, size_t crc_piece = kPngCrcPiece) {
+  if (prefix_bytes < kPngPrefixBytes || size < prefix_bytes + 6) return false;
+  const size_t n = size - prefix_bytes;
+  unsigned char* zlib = file + prefix_bytes;
   if (n > 0x7fffffffu || zlib[0] != 0x78 || zlib[1] != 0xda) return false;
   zlib[1] = 0x01;
-  PngStore32(file + 33, static_cast<uint32_t>(n));
-  PngStore32(trailer, PngCrcJoin(PngCrc32(file + 37, 4), PngCrc32Pieces(zlib, n, crc_piece), n));
+  PngStore32(file + prefix_bytes - 8, static_cast<uint32_t>(n));
+  PngStore32(trailer, PngCrcJoin(PngCrc32(file + prefix_bytes - 4, 4), PngCrc32Pieces(zlib, n, crc_piece), n));
   PngStore32(trailer + 4, 0);
   std::memcpy(trailer + 8, "IEND", 4);
   PngStore32(trailer + 12, PngCrc32(trailer + 8, 4));
   return true;
+}
+inline bool PngClose(unsigned char* file, size_t size, unsigned char* trailer, size_t crc_piece = kPngCrcPiece) {
+  return PngCloseAt(file, size, kPngPrefixBytes, trailer, crc_piece);
+}
+
+// ---- the prefix of a file whose colour mode was reduced (zmx_png_optimize_device, png_optimize.cc): LodePNG's chunk
+// order IHDR, PLTE, tRNS, IDAT (lodepng.cpp lodepng_encode, addChunk_PLTE, addChunk_tRNS)
+// what such a file may be: the modes PNG has
+inline bool PngReducedFormatOk(uint32_t colortype, uint32_t bitdepth) {
+  switch (colortype) {
+    case 0: return bitdepth == 1 || bitdepth == 2 || bitdepth == 4 || bitdepth == 8 || bitdepth == 16;
+    case 3: return bitdepth == 1 || bitdepth == 2 || bitdepth == 4 || bitdepth == 8;
+    case 2: case 4: case 6: return bitdepth == 8 || bitdepth == 16;
+    default: return false;
+  }
+}
+// signature 8, IHDR 25, PLTE up to 12 + 768, tRNS up to 12 + 256, the IDAT's length and type 8
+constexpr size_t kPngMaxPrefixBytes = 8 + 25 + (12 + 768) + (12 + 256) + 8;
+
+// one whole chunk at p; returns its size
+inline size_t PngChunk(unsigned char* p, const char* tag, const unsigned char* data, size_t n) {
+  PngStore32(p, static_cast<uint32_t>(n));
+  std::memcpy(p + 4, tag, 4);
+  if (n) std::memcpy(p + 8, data, n);
+  PngStore32(p + 8 + n, PngCrc32(p + 4, 4 + n));
+  return 12 + n;
+}
+
+// The file up to the IDAT's type, into prefix[kPngMaxPrefixBytes]; returns its size.  Colour type 3: PLTE with the RGB of
+// each of the `palettesize` (1 .. 256) entries r, g, b, a at `palette`, and tRNS with their alphas up to the last that
+// is not 255 (none: no chunk).  Colour types 0 and 2 with `key`: tRNS with the grey value, or the three, as 16-bit numbers.
+inline size_t PngPrefixReduced(uint32_t width, uint32_t height, uint32_t colortype, uint32_t bitdepth, const unsigned char* palette,
+                               uint32_t palettesize, bool key, uint32_t key_r, uint32_t key_g, uint32_t key_b, unsigned char* prefix) {
+  unsigned char plain[kPngPrefixBytes];
+  PngPrefix(width, height, colortype, bitdepth, plain);
+  std::memcpy(prefix, plain, 33);
+  size_t at = 33;
+  if (colortype == 3) {
+    unsigned char rgb[768], alphas[256];
+    size_t amount = 0;
+    for (uint32_t i = 0; i < palettesize; ++i) {
+      std::memcpy(rgb + 3 * i, palette + 4 * i, 3);
+      alphas[i] = palette[4 * i + 3];
+      if (alphas[i] != 255) amount = i + 1;
+    }
+    at += PngChunk(prefix + at, "PLTE", rgb, 3 * static_cast<size_t>(palettesize));
+    if (amount) at += PngChunk(prefix + at, "tRNS", alphas, amount);
+  } else if (key && (colortype == 0 || colortype == 2)) {
+    const uint32_t v[3] = {key_r, key_g, key_b};
+    unsigned char data[6];
+    for (int k = 0; k < 3; ++k) {
+      data[2 * k] = static_cast<unsigned char>(v[k] >> 8);
+      data[2 * k + 1] = static_cast<unsigned char>(v[k] & 255u);
+    }
+    at += PngChunk(prefix + at, "tRNS", data, colortype == 0 ? 2 : 6);
+  }
+  PngStore32(prefix + at, 0);
+  std::memcpy(prefix + at + 4, "IDAT", 4);
+  return at + 8;
 }
 
 // The whole file around a stream that lies elsewhere (`zlib` is not changed).

@@ -4,12 +4,17 @@
 // BEFORE zmx_compress_device(ZLIB) of the buffer runs, which takes contexts itself.  The stream's second byte and the
 // chunks around it are png_container.h's.  (Outside api.cc, as png.cc is: the host-only test library links api.cc
 // against a stand-in for the device layer.)
+// zmx_png_optimize_device and its batch, further down, reduce the colour mode first: the statistics
+// (zmx_png_color_stats_device), LodePNG's choice (png_color_choose.h) and the conversion run on the same hold of the
+// context as the types and the rows; a palette file below 4096 bytes is made a second time as RGB or RGBA, on a second
+// hold, and the smaller file is kept.
 #include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "dealing.h"
 #include "deflate.h"
+#include "png_color_choose.h"
 #include "png_container.h"
 #include "zmx_internal.h"
 #include "zopfli_amd.h"
@@ -63,15 +68,23 @@ struct File {
   File(const File&) = delete;
   File& operator=(const File&) = delete;
   ~File() { std::free(bytes); }
+  size_t prefix_bytes = zamd::kPngPrefixBytes;
   void Begin(const zmx_png_image& im) {
     unsigned char prefix[zamd::kPngPrefixBytes];
     zamd::PngPrefix(im.width, im.height, im.colortype, im.bitdepth, prefix);
     zamd::AppendToOutput(prefix, sizeof(prefix), &bytes, &size);
   }
+  // the file of the image in `mode`: PLTE and tRNS where the mode has them
+  void BeginReduced(const zmx_png_image& im, const zmx_png_color_mode& mode) {
+    unsigned char prefix[zamd::kPngMaxPrefixBytes];
+    prefix_bytes = zamd::PngPrefixReduced(im.width, im.height, mode.colortype, mode.bitdepth, mode.palette, mode.palettesize,
+                                          mode.key_defined != 0, mode.key_r, mode.key_g, mode.key_b, prefix);
+    zamd::AppendToOutput(prefix, prefix_bytes, &bytes, &size);
+  }
   // the stream is in: what depends on it, and the file's end
   bool Close() {
     unsigned char trailer[zamd::kPngTrailerBytes];
-    if (!zamd::PngClose(bytes, size, trailer)) return false;
+    if (!zamd::PngCloseAt(bytes, size, prefix_bytes, trailer)) return false;
     zamd::AppendToOutput(trailer, sizeof(trailer), &bytes, &size);
     return true;
   }
@@ -181,5 +194,227 @@ extern "C" int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t 
     if (!files[i].Close()) return BadStream(w);
   }
   for (size_t i = 0; i < n; ++i) files[i].GiveTo(&out[i], &outsize[i]);
+  return 0;
+}
+
+// ---- zmx_png_optimize_device, zmx_png_optimize_device_batch: the colour mode reduced first (png_color_choose.h)
+extern "C" int zmx_png_choose_color(const zmx_png_color_stats* stats, uint64_t numpixels, zmx_png_color_mode* out) {
+  if (!stats || !out) return Refuse("zmx_png_choose_color: null argument");
+  zamd::PngChooseColor(*stats, numpixels, out);
+  return 0;
+}
+
+namespace {
+
+// What is made of one image: its statistics, the mode of the first file, the scanlines' size in that mode.
+struct Reduced {
+  zmx_png_color_stats stats;
+  zmx_png_color_mode mode;
+  bool as_is = false;      // the mode is the image's own: nothing is converted
+  size_t scanlines = 0;    // height * (row bytes + 1)
+};
+
+bool SameMode(const zmx_png_image& im, const zmx_png_color_mode& mode) {
+  return mode.colortype == im.colortype && mode.bitdepth == im.bitdepth && mode.key_defined == 0;
+}
+
+size_t ScanlinesIn(const zmx_png_image& im, const zmx_png_color_mode& mode) {
+  const size_t bpp = (mode.colortype == 3 ? 1 : zamd::PngChannels(mode.colortype)) * mode.bitdepth;
+  return static_cast<size_t>(im.height) * ((static_cast<size_t>(im.width) * bpp + 7) / 8 + 1);
+}
+
+int CheckReducible(const std::string& w, const zmx_png_image& im, Geometry* g) {
+  if (CheckImage(w, im, g) != 0) return -1;
+  if (static_cast<uint64_t>(im.width) * im.height > 0xffffffffull) return Refuse(w + ": an image of 2^32 pixels or more");
+  return 0;
+}
+
+// on a held context: the statistics and the mode of the first file
+int StatsAndMode(zmx_ctx* ctx, const zmx_png_image& im, Reduced* r) {
+  if (zmx_png_color_stats_device(ctx, &im, &r->stats) != 0) return -1;
+  zamd::PngChooseColor(r->stats, static_cast<uint64_t>(im.width) * im.height, &r->mode);
+  r->as_is = SameMode(im, r->mode);
+  r->scanlines = ScanlinesIn(im, r->mode);
+  return 0;
+}
+
+// Of two closed files of one image the one zopflipng keeps: the second only when it is strictly smaller.
+File& Smaller(File& first, File& second) { return second.size < first.size ? second : first; }
+
+}  // namespace
+
+extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                       const unsigned char* predefined, unsigned char** out, size_t* outsize) {
+  const std::string w = "zmx_png_optimize_device";
+  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
+  Geometry g;
+  if (CheckReducible(w, *image, &g) != 0) return -1;
+  if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
+  if (strategy == ZMX_PNG_FILTER_PREDEFINED) {
+    if (!predefined) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED without types");
+    for (size_t r = 0; r < g.height; ++r) {
+      if (predefined[r] > 4) return Refuse(w + ": predefined type " + std::to_string(predefined[r]) + " of row " + std::to_string(r));
+    }
+  }
+  int device = -1;
+  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, g.linebytes * g.height, &device) != 0) return -1;
+  const uint64_t numpixels = static_cast<uint64_t>(image->width) * image->height;
+  Reduced r;
+  DeviceBuffer scan;
+  scan.device = device;
+  // (the context is held for the statistics, the conversion, the types and the rows only)
+  int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    if (StatsAndMode(ctx, *image, &r) != 0) return -1;
+    if (zmx_internal_device_alloc(device, r.scanlines, &scan.p) != 0) return -1;
+    return zmx_internal_png_reduced_scanlines(ctx, image, r.as_is ? nullptr : &r.mode, strategy, kBruteWindow, predefined, scan.p);
+  }, device);
+  if (rc != 0) return -1;
+  File file;
+  if (r.as_is) file.Begin(*image);
+  else file.BeginReduced(*image, r.mode);
+  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan.p, r.scanlines, &file.bytes, &file.size) != 0) return -1;
+  if (!file.Close()) return BadStream(w);
+  File second;
+  if (r.mode.colortype == 3 && file.size < zamd::kPngRetryBelow) {
+    // zopflipng's second try: without the palette's overhead
+    zmx_png_color_mode retry;
+    zamd::PngRetryMode(r.stats, numpixels, &retry);
+    const bool as_is = SameMode(*image, retry);
+    const size_t scanlines = ScanlinesIn(*image, retry);
+    DeviceBuffer scan2;
+    scan2.device = device;
+    if (zmx_internal_device_alloc(device, scanlines, &scan2.p) != 0) return -1;
+    rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+      return zmx_internal_png_reduced_scanlines(ctx, image, as_is ? nullptr : &retry, strategy, kBruteWindow, predefined, scan2.p);
+    }, device);
+    if (rc != 0) return -1;
+    if (as_is) second.Begin(*image);
+    else second.BeginReduced(*image, retry);
+    if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines, &second.bytes, &second.size) != 0) return -1;
+    if (!second.Close()) return BadStream(w);
+    Smaller(file, second).GiveTo(out, outsize);
+    return 0;
+  }
+  file.GiveTo(out, outsize);
+  return 0;
+}
+
+namespace {
+
+// One zmx_compress_device_batch over the scanlines of the images `which` — image which[k]'s at base + start[k], in
+// modes[k] (as_is[k]: the image's own) — into files[k], closed.
+int CompressInto(const ZopfliOptions* options, const std::string& w, const zmx_png_image* images, const std::vector<size_t>& which,
+                 const std::vector<zmx_png_color_mode>& modes, const std::vector<char>& as_is, const unsigned char* base,
+                 const std::vector<size_t>& start, std::vector<File>* files) {
+  const size_t m = which.size();
+  std::vector<const void*> slices(m);
+  std::vector<size_t> sizes(m), filled(m);
+  std::vector<unsigned char*> bytes(m);
+  for (size_t k = 0; k < m; ++k) {
+    slices[k] = base + start[k];
+    sizes[k] = start[k + 1] - start[k];
+    if (as_is[k]) (*files)[k].Begin(images[which[k]]);
+    else (*files)[k].BeginReduced(images[which[k]], modes[k]);
+    bytes[k] = (*files)[k].bytes;
+    filled[k] = (*files)[k].size;
+  }
+  // (a failed call changes none of them: the files still own their arrays)
+  if (zmx_compress_device_batch(options, ZOPFLI_FORMAT_ZLIB, m, slices.data(), sizes.data(), bytes.data(), filled.data()) != 0) return -1;
+  for (size_t k = 0; k < m; ++k) {
+    (*files)[k].bytes = bytes[k];
+    (*files)[k].size = filled[k];
+  }
+  for (size_t k = 0; k < m; ++k) {
+    if (!(*files)[k].Close()) return BadStream(w);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                             unsigned char** out, size_t* outsize) {
+  const std::string w = "zmx_png_optimize_device_batch";
+  if (n == 0) return 0;
+  if (!options || !images || !out || !outsize) return Refuse(w + ": null argument");
+  if (strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
+  if (!StrategyOk(strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
+  std::vector<const void*> pixels(n);
+  std::vector<size_t> nbytes(n);
+  for (size_t i = 0; i < n; ++i) {
+    Geometry g;
+    if (CheckReducible(w + ": image " + std::to_string(i), images[i], &g) != 0) return -1;
+    pixels[i] = images[i].d_pixels;
+    nbytes[i] = g.linebytes * g.height;
+  }
+  int device = -1;
+  if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &device) != 0) return -1;
+  // the first files: statistics for all, one buffer, conversion and rows image by image, on one hold of a context
+  std::vector<Reduced> r(n);
+  std::vector<size_t> all(n), start(n + 1, 0);
+  std::vector<zmx_png_color_mode> modes(n);
+  std::vector<char> as_is(n);
+  DeviceBuffer scan;
+  scan.device = device;
+  int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    for (size_t i = 0; i < n; ++i) {
+      if (StatsAndMode(ctx, images[i], &r[i]) != 0) return -1;
+      if (r[i].scanlines > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
+      start[i + 1] = start[i] + r[i].scanlines;
+    }
+    if (zmx_internal_device_alloc(device, start[n], &scan.p) != 0) return -1;
+    for (size_t i = 0; i < n; ++i) {
+      if (zmx_internal_png_reduced_scanlines(ctx, &images[i], r[i].as_is ? nullptr : &r[i].mode, strategy, kBruteWindow, nullptr,
+                                             static_cast<unsigned char*>(scan.p) + start[i]) != 0) {
+        return -1;
+      }
+    }
+    return 0;
+  }, device);
+  if (rc != 0) return -1;
+  for (size_t i = 0; i < n; ++i) {
+    all[i] = i;
+    modes[i] = r[i].mode;
+    as_is[i] = r[i].as_is ? 1 : 0;
+  }
+  std::vector<File> files(n);
+  if (CompressInto(options, w, images, all, modes, as_is, static_cast<const unsigned char*>(scan.p), start, &files) != 0) return -1;
+  // zopflipng's second try at the small palette files, all of them in one more batch
+  std::vector<size_t> again;
+  for (size_t i = 0; i < n; ++i) {
+    if (r[i].mode.colortype == 3 && files[i].size < zamd::kPngRetryBelow) again.push_back(i);
+  }
+  std::vector<File> seconds(again.size());
+  if (!again.empty()) {
+    const size_t m = again.size();
+    std::vector<zmx_png_color_mode> modes2(m);
+    std::vector<char> as_is2(m);
+    std::vector<size_t> start2(m + 1, 0);
+    for (size_t k = 0; k < m; ++k) {
+      const zmx_png_image& im = images[again[k]];
+      zamd::PngRetryMode(r[again[k]].stats, static_cast<uint64_t>(im.width) * im.height, &modes2[k]);
+      as_is2[k] = SameMode(im, modes2[k]) ? 1 : 0;
+      start2[k + 1] = start2[k] + ScanlinesIn(im, modes2[k]);
+    }
+    DeviceBuffer scan2;
+    scan2.device = device;
+    if (zmx_internal_device_alloc(device, start2[m], &scan2.p) != 0) return -1;
+    rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+      for (size_t k = 0; k < m; ++k) {
+        if (zmx_internal_png_reduced_scanlines(ctx, &images[again[k]], as_is2[k] ? nullptr : &modes2[k], strategy, kBruteWindow, nullptr,
+                                               static_cast<unsigned char*>(scan2.p) + start2[k]) != 0) {
+          return -1;
+        }
+      }
+      return 0;
+    }, device);
+    if (rc != 0) return -1;
+    if (CompressInto(options, w, images, again, modes2, as_is2, static_cast<const unsigned char*>(scan2.p), start2, &seconds) != 0) return -1;
+  }
+  // every file made before any out[i] is touched
+  std::vector<File*> kept(n);
+  for (size_t i = 0; i < n; ++i) kept[i] = &files[i];
+  for (size_t k = 0; k < again.size(); ++k) kept[again[k]] = &Smaller(files[again[k]], seconds[k]);
+  for (size_t i = 0; i < n; ++i) kept[i]->GiveTo(&out[i], &outsize[i]);
   return 0;
 }

@@ -4,7 +4,7 @@
 // layer defines them and includes this header, as every caller does and as the host test library's stand-in for the
 // device layer does (tests/hostlib/zmx_oracle_backend.cc), so a parameter list that changes on one side only does not
 // compile.  Device to host: the statistics, which the host layer owns.
-// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the five
+// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the six
 // functions that tests and tools reach from outside (here and nowhere else).
 #pragma once
 #include <cstddef>
@@ -87,6 +87,13 @@ int zmx_internal_device_pointers_one_device(const char* who, size_t n, const voi
 int zmx_internal_png_scanlines(zmx_ctx* ctx, const void* d_image, size_t linebytes, size_t height, size_t bytewidth, int strategy,
                                unsigned windowsize, const unsigned char* predefined, void* d_out);
 
+// ---- a PNG with its colour mode reduced (png_encode.cc: zmx_png_optimize_device)
+// zmx_internal_png_scanlines of the image converted to `mode` first (zmx_png_convert_device, into memory of the context's
+// pool); a null `mode`: of the image as it is.  d_out: height * ((width * bpp + 7) / 8 + 1) bytes of the context's device
+// that the caller owns.  0, or -1 with the error set.
+int zmx_internal_png_reduced_scanlines(zmx_ctx* ctx, const zmx_png_image* image, const zmx_png_color_mode* mode, int strategy,
+                                       unsigned windowsize, const unsigned char* predefined, void* d_out);
+
 // ---- for tests and tools
 // The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
 // (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing); else 0.  For
@@ -96,6 +103,9 @@ ZMX_INTERNAL_EXPORT double zmx_internal_gather_ms(void);
 ZMX_INTERNAL_EXPORT double zmx_internal_bitjoin_ms(void);
 // The same for k_png_rows of the calling thread's last zmx_png_filter_rows_device.  For tools/png_device.py.
 ZMX_INTERNAL_EXPORT double zmx_internal_png_rows_ms(void);
+// The same for the calling thread's last zmx_png_color_stats_device and zmx_png_convert_device: k_png_color_stats,
+// k_png_color_key (0: not launched), k_png_convert.  For tools/png_reduce.py.
+ZMX_INTERNAL_EXPORT void zmx_internal_png_color_ms(double out[3]);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
 // squeeze run computes them — *wmax, *tiemask —, no device involved.
 ZMX_INTERNAL_EXPORT void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask);
