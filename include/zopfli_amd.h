@@ -742,7 +742,7 @@ int zmx_master_block_costs_device(zmx_ctx* ctx, double* cost, size_t ncost);
  * Timing breakdown of the last Zopfli* / zmx_deflate_range call on this
  * thread: seconds spent in [0] match tables [1] greedy [2] squeeze runs
  * [3] host cost model [4] block split [5] encode [6] the chain kernels of the squeeze runs (k_dp5_spec,
- * k_dpcheck, k_dpscan, k_dp4_fix: GetBestLengths; HIP events on the launch stream) [7] squeeze runs launched.
+ * k_dp5_stretch, k_dpcheck, k_dprecheck, k_dpscan, k_dp4_fix: GetBestLengths; HIP events on the launch stream) [7] squeeze runs launched.
  * For bench.py's roofline object. */
 int zmx_last_timing(double* out8);
 

@@ -24,12 +24,12 @@ def main(paths):
             out[k]["launches"] = n
             for c, x in v.items():
                 out[k][c] = x / n
-    # the chain of one squeeze run = k_dp5_spec (both passes) + k_dpcheck + k_dpscan + k_dp4_fix: totals over
+    # the chain of one squeeze run = k_dp5_spec + k_dp5_stretch (the redo pass) + k_dpcheck + k_dprecheck + k_dpscan + k_dp4_fix: totals over
     # all their launches divided by the number of squeeze runs (= launches of k_dp4_fix)
     runs = out.get("k_dp4_fix", {}).get("launches", 0)
     if runs:
         chain = collections.defaultdict(float)
-        for k in ("k_dp5_spec", "k_dpcheck", "k_dpscan", "k_dp4_fix"):
+        for k in ("k_dp5_spec", "k_dp5_stretch", "k_dpcheck", "k_dprecheck", "k_dpscan", "k_dp4_fix"):
             for c, x in out.get(k, {}).items():
                 if c != "launches":
                     chain[c] += x * out[k]["launches"] / runs

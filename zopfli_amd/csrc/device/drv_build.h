@@ -13,6 +13,10 @@ extern "C" {
 // (0 = no tasks: the serial chain).
 static unsigned SegL(u64 total_positions) {
   if (Knobs().seg_l_set) return Knobs().seg_l;
+  // (a shard of a dealt call: the call's positions on this device, not the context's share — zamd::CallPositions.  Through
+  //  ZopfliCompress 100 MB of text are three shares of 33 M positions, which took 1024 below: 112.2 ms a step against 107.0
+  //  with 2048, three lines a side, spread 0.2 and 0.8 ms: profiles/chain_stretch.txt)
+  total_positions = std::max<u64>(total_positions, zamd::CallPositions());
   // (with the tasks started at cut points, below, the warm-up is ~70 positions instead of 512 and 2048 beats 4096
   //  for a full batch too: half the positions re-run where a task crosses a binade, 4.17 -> 3.75 ms per run of 100 MB;
   //  1024 loses to the per-task set-up again: 4.2 ms)
@@ -607,7 +611,8 @@ static int BuildChainTasks(zmx_ctx* c, zmx_tables* t) {
   HIPCHK(PoolAlloc(c, &t->d_mid, nt));
   HIPCHK(PoolAlloc(c, &t->d_chk, nt));
   HIPCHK(PoolAlloc(c, &t->d_over, nt * SEG_OVER));
-  HIPCHK(PoolAlloc(c, &t->d_redo, 4 + nt * 4));
+  t->redo_cap = nt;
+  HIPCHK(PoolAlloc(c, &t->d_redo, 4 + nt * 4 + nt * 2));   // counters, k_dpscan's entries, its recheck list
   HIPCHK(hipMemcpyAsync(t->d_tasks, t->tasks.data(), nt * sizeof(SegTask), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(t->d_task_off, t->task_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(t->run.stats(t->d_runout), 0, RunLayout::kStats * sizeof(u32), c->stream));
@@ -677,7 +682,7 @@ static int BuildChainTasks(zmx_ctx* c, zmx_tables* t) {
 // Phase 8: the workgroup lists.
 static int BuildWorkgroupLists(zmx_ctx* c, zmx_tables* t) {
   const size_t nb = t->nb;
-  // k_dp5_spec's workgroups: four tasks of one block each (they share the block's weight table in
+  // k_dp5_spec's workgroups: a stretch of tasks of one block each (they share the block's weight table in
   // LDS); the workgroups that hold a head (several times the length of the other tasks) go first.  Tasks that
   // walk runs of equal bytes (k_taskkind) get workgroups of their own, listed after the others: they are run by the
   // kernel's other variant, beside the rest.
@@ -698,30 +703,41 @@ static int BuildWorkgroupLists(zmx_ctx* c, zmx_tables* t) {
     HIPCHK(hipMemcpyAsync(kind.data(), d_kind, ntk * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
-  std::vector<u32> wg, wg_runs;
-  for (int pass = 0; pass < 2; ++pass) {
-    for (size_t b = 0; b < nb; ++b) {
-      const u32 a0 = t->task_off[b], a1 = t->task_off[b + 1];
-      // pass 0: the group that holds the block's head; pass 1: the others.  Inside a block the tasks of either kind
-      // are grouped four at a time in order.
-      std::vector<u32> grp[2];
-      for (u32 k = a0; k < a1; ++k) grp[kind[k] ? 1 : 0].push_back(k);
-      for (int kd = 0; kd < 2; ++kd) {
-        std::vector<u32>& dst = kd ? wg_runs : wg;
-        for (size_t i = 0; i < grp[kd].size(); i += D5_WG) {
-          const bool has_head = i == 0 && !grp[kd].empty() && grp[kd][0] == a0;
-          if ((pass == 0) != has_head) continue;
-          for (u32 w = 0; w < D5_WG; ++w) dst.push_back(i + w < grp[kd].size() ? grp[kd][i + w] : SEG_NONE);
-        }
+  // The lists: per block and kind the tasks in order, the text tasks' lists first, then the run tasks'.  A workgroup
+  // takes a stretch of ZOPFLI_AMD_SEG_STRETCH consecutive entries of one list (at 4: a task a wave, as before there were
+  // stretches); its descriptor is (first entry, entries).
+  const u32 S = Knobs().seg_stretch;
+  std::vector<u32> list[2];
+  std::vector<uint2> desc[2][2];        // [kind][0: holds the block's head, 1: the others]
+  for (size_t b = 0; b < nb; ++b) {
+    const u32 a0 = t->task_off[b], a1 = t->task_off[b + 1];
+    for (int kd = 0; kd < 2; ++kd) {
+      const u32 l0 = static_cast<u32>(list[kd].size());
+      for (u32 k = a0; k < a1; ++k)
+        if ((kind[k] ? 1 : 0) == kd) list[kd].push_back(k);
+      const u32 l1 = static_cast<u32>(list[kd].size());
+      for (u32 i = l0; i < l1; i += S) {
+        const bool has_head = i == l0 && list[kd][l0] == a0;
+        desc[kd][has_head ? 0 : 1].push_back(make_uint2(i, std::min(S, l1 - i)));
       }
     }
   }
-  t->n_wg = static_cast<u32>(wg.size() / D5_WG);
-  t->n_wg_runs = static_cast<u32>(wg_runs.size() / D5_WG);
-  wg.insert(wg.end(), wg_runs.begin(), wg_runs.end());
-  HIPCHK(PoolAlloc(c, &t->d_wg_tasks, wg.size() + 4));
-  if (!wg.empty()) HIPCHK(hipMemcpyAsync(t->d_wg_tasks, wg.data(), wg.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));   // `wg` is a local
+  // (the run tasks' list lies behind the text tasks' in one array)
+  const u32 shift = static_cast<u32>(list[0].size());
+  std::vector<uint2> wg;
+  for (int kd = 0; kd < 2; ++kd)
+    for (int rest = 0; rest < 2; ++rest)
+      for (uint2 d : desc[kd][rest]) wg.push_back(make_uint2(d.x + (kd ? shift : 0u), d.y));
+  t->n_wg = static_cast<u32>(desc[0][0].size() + desc[0][1].size());
+  t->n_wg_runs = static_cast<u32>(desc[1][0].size() + desc[1][1].size());
+  list[0].insert(list[0].end(), list[1].begin(), list[1].end());
+  HIPCHK(PoolAlloc(c, &t->d_wg_tasks, list[0].size() + 4));
+  HIPCHK(PoolAlloc(c, &t->d_wg_desc, wg.size() + 1));
+  if (!wg.empty()) {
+    HIPCHK(hipMemcpyAsync(t->d_wg_tasks, list[0].data(), list[0].size() * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(t->d_wg_desc, wg.data(), wg.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));   // `list` and `wg` are locals
   return 0;
 }
 
@@ -792,6 +808,9 @@ static void FillTableParams(zmx_tables* t, bool with_dp) {
   cp.wg_tasks = t->d_wg_tasks;
   cp.redo_count = t->d_redo;
   cp.redo_wg = t->d_redo + 4;
+  cp.recheck = t->d_redo + 4 + t->redo_cap * 4;
+  cp.redo_parity = 0;
+  cp.wg_desc = t->d_wg_desc;
   cp.flags = t->run.flags(t->d_runout);
   cp.wmeta = t->d_wmeta;
   cp.winroff = t->d_winroff;

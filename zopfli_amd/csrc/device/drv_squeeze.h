@@ -126,6 +126,14 @@ static int ReportSqueezeProf(zmx_tables* t, const double* ksec, const u32* segst
     for (size_t b = 0; b < nb; ++b) { mx = std::max(mx, static_cast<double>(pr[b * ZMX_PROF_N + 7])); hd = std::max(hd, static_cast<double>(pr[b * ZMX_PROF_N + 8])); }
     std::fprintf(stderr, "  k_dp5_spec: longest task %.0f cycles, longest head task %.0f cycles; %.1f%% of the positions walked by the integer step (cycles per position there: fetch issue %.1f, fetch wait %.1f, gather + chain %.1f)\n", mx, hd, 100.0 * a[10] / (a[4] + 1e-9), a[11] / (a[10] + 1e-9), a[12] / (a[10] + 1e-9), a[13] / (a[10] + 1e-9));
   }
+  // the fixed cost around the tasks, by every pass of k_dp5_spec and k_dp5_stretch: a[54] wave cycles from workgroup (or
+  // entry) start to a wave's first position (a[56] such waves), a[55] wave cycles spent finished in a workgroup that is still
+  // alive, a[57] wave cycles the workgroups were alive for, a[1] in tasks; a[58] tasks listed for the redo pass in a[59] entries
+  if (a[56] > 0 && a[57] > 0) {
+    std::fprintf(stderr, "  k_dp5_spec fixed cost: set-up %.0f cycles a wave (%.0f waves with a task), %.2f%% of the workgroups' wave cycles; finished waves waiting for their workgroup %.2f%%; in tasks %.2f%%\n",
+                 a[54] / a[56], a[56], 100.0 * a[54] / a[57], 100.0 * a[55] / a[57], 100.0 * a[1] / a[57]);
+  }
+  std::fprintf(stderr, "  redo list: %.0f tasks in %.0f entries\n", a[58], a[59]);
   std::fprintf(stderr, "  k_dp5_spec integer windows, cycles per position: class decision %.1f, waiting for the prefetched record and codes %.1f, prefetch issue %.1f\n",
                a[20] / (a[10] + 1e-9), a[21] / (a[10] + 1e-9), a[22] / (a[10] + 1e-9));
   std::fprintf(stderr, "  k_dp5_spec windows: integer %.1f%% of positions at %.0f cycles each, class 1 in doubles %.1f%% at %.0f, class 2 %.1f%% at %.0f, generic %.1f%% at %.0f\n",
@@ -184,11 +192,23 @@ static int TraceAndCollect(zmx_ctx* c, zmx_tables* t, const TraceSegParams& tp, 
   return 0;
 }
 
-// k_dp5_spec over `grid` workgroups of four tasks each: the variant for run tasks or the one for the others, with the
-// profile counters when the run has them
+constexpr unsigned kRedoGrid = 1024;   // the redo pass: 256 CUs x 4 workgroups (LDS-limited)
+// The speculative pass over `grid` workgroups of four waves each: the variant for run tasks or the one for the others, with
+// the profile counters when the run has them.  k_dp5_spec, a task a wave, where no stretch is longer than the four
+// waves, and for the redo pass of a table set with run tasks; k_dp5_stretch, whose waves pull tasks until the stretch is
+// empty, for longer stretches and for the packed redo list.
 static void LaunchSpec(hipStream_t stream, unsigned grid, bool run_tasks, const Dp4Params& p) {
   const dim3 g(grid), b(64 * D5_WG);
-  if (run_tasks) {
+  const bool pull = p.redo_pass ? p.redo_pack > 1 : Knobs().seg_stretch > D5_WG || Knobs().seg_pull;
+  if (pull) {
+    if (run_tasks) {
+      if (p.prof) hipLaunchKernelGGL((k_dp5_stretch<true, 2, true>), g, b, 0, stream, p);
+      else hipLaunchKernelGGL((k_dp5_stretch<false, 2, true>), g, b, 0, stream, p);
+    } else {
+      if (p.prof) hipLaunchKernelGGL((k_dp5_stretch<true, 4, false>), g, b, 0, stream, p);
+      else hipLaunchKernelGGL((k_dp5_stretch<false, 4, false>), g, b, 0, stream, p);
+    }
+  } else if (run_tasks) {
     if (p.prof) hipLaunchKernelGGL((k_dp5_spec<true, 2, true>), g, b, 0, stream, p);
     else hipLaunchKernelGGL((k_dp5_spec<false, 2, true>), g, b, 0, stream, p);
   } else {
@@ -294,18 +314,23 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
       // (ZOPFLI_AMD_SEG_REDO = how many such passes, default 1.  More settle more tasks before the serial pass — class Z:
       //  87 / 92 / 93 % accepted with 1 / 2 / 3 — but every pass waits for its longest task: 1 264 / 1 362 / 1 601 ms)
       for (int pass = 0; pass < knobs.seg_redo; ++pass) {
-        // (the list's counter was zeroed by the k_dpcheck before: zmx_dp4.h)
-        hipLaunchKernelGGL(k_dpscan, dim3(nblk), dim3(64), 0, c->stream, cp);
-        KCHK(c, "k_dpscan");
+        // (the lists' counters were zeroed by the check before: zmx_dp4.h)
         Dp4Params c2 = cp;
         c2.redo_pass = 1;
         c2.est_bits = nullptr;
-        // (one workgroup per listed task; the workgroups beyond the list have nothing to do.  The variant for run tasks
-        //  wherever the set has any: what is run again there is mostly theirs)
-        LaunchSpec(c->stream, ntask, t->n_wg_runs != 0, c2);
-        KCHK(c, "k_dp5_spec");
-        hipLaunchKernelGGL(k_dpcheck, dim3(ntask), dim3(64), 0, c->stream, cp);
-        KCHK(c, "k_dpcheck");
+        c2.redo_parity = pass & 1;
+        c2.redo_pack = t->n_wg_runs != 0 ? 1 : 4;
+        hipLaunchKernelGGL(k_dpscan, dim3(nblk), dim3(64), 0, c->stream, c2);
+        KCHK(c, "k_dpscan");
+        // (text: the list holds up to four tasks of a block per entry — about 1 % of the tasks — and the workgroups stride
+        //  over it: a grid of the device's resident workgroups at most.  A table set with run tasks keeps a task an entry and
+        //  a workgroup a task, by the variant for run tasks: what is run again there is mostly theirs, few and long, and
+        //  packed it measured slower — class Z, profiles/chain_stretch.txt)
+        LaunchSpec(c->stream, c2.redo_pack > 1 ? std::min(ntask, kRedoGrid) : ntask, t->n_wg_runs != 0, c2);
+        KCHK(c, "k_dp5_spec (redo)");
+        // only the checks of the listed tasks and their successors can have changed
+        hipLaunchKernelGGL(k_dprecheck, dim3(std::min(ntask, DPRECHECK_GRID)), dim3(64), 0, c->stream, c2);
+        KCHK(c, "k_dprecheck");
       }
       LaunchFix(c->stream, nblk, cp);
       KCHK(c, "k_dp4_fix");

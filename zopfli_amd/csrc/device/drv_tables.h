@@ -96,7 +96,8 @@ struct zmx_tables {
   std::vector<u32> task_off;  // [nb + 1]
   SegTask* d_tasks = nullptr;
   u32* d_task_off = nullptr;
-  u32* d_wg_tasks = nullptr;       // k_dp5_spec's workgroups: four tasks of one block each
+  u32* d_wg_tasks = nullptr;       // the blocks' task lists per kind, and ...
+  uint2* d_wg_desc = nullptr;      // ... k_dp5_spec's workgroups: a stretch (first entry, entries) of one list each
   u32 n_wg = 0;
   u32 n_wg_runs = 0;               // ... of which the last n_wg_runs hold run tasks (k_taskkind): k_dp5_spec<.., true>
   u32* d_wmeta = nullptr;          // per 32-position window: 40 words, what k_dp5_spec needs to fetch its rows (k_mkdesc)
@@ -110,7 +111,8 @@ struct zmx_tables {
   SegSnap* d_mid = nullptr;      // per task: the state where it first came near the end of its binade (zmx_dp5.h)
   SegCheck* d_chk = nullptr;
   u16* d_over = nullptr;      // [tasks][SEG_OVER]
-  u32* d_redo = nullptr;      // [1 + 3 pad + tasks * 4]: k_dpscan's list of tasks to run a second time
+  u32* d_redo = nullptr;      // [3 counters + 1 pad + redo_cap * 4 + redo_cap * 2]: k_dpscan's entries of tasks to run a second time, its recheck list
+  size_t redo_cap = 0;        // the tasks d_redo was sized for (before any were merged)
   std::vector<u32> h_hist;    // the histograms of the last greedy parse / squeeze run (host copy)
   bool have_hist = false;
   u32 squeeze_runs = 0;
@@ -127,7 +129,7 @@ static void ReleaseTableArrays(zmx_ctx* c, zmx_tables* t, bool keep_stores) {
   rel(t->d_blocks, t->d_tile_off, t->d_same16, t->d_links, t->d_recs, t->d_pool, t->d_la, t->d_dph, t->d_block_edges);
   rel(t->d_badpos, t->d_code_base, t->d_codes, t->d_wtab, t->d_badcodes, t->d_seg_off, t->d_extab, t->d_seginfo);
   rel(t->d_counters, t->d_prof, t->d_tasks, t->d_task_off, t->d_wg_tasks, t->d_wmeta, t->d_runin, t->d_runout);
-  rel(t->d_winroff, t->d_winflag, t->d_win_off, t->d_lvl, t->d_entry, t->d_exit, t->d_mid, t->d_chk, t->d_over, t->d_redo);
+  rel(t->d_winroff, t->d_winflag, t->d_win_off, t->d_lvl, t->d_entry, t->d_exit, t->d_mid, t->d_chk, t->d_over, t->d_redo, t->d_wg_desc);
   PinnedGive(c, &t->h_runin, t->h_runin_cap);
   PinnedGive(c, &t->h_runout, t->h_runout_cap);
   // nothing that pointed into those arrays stays behind (the entries refuse such tables: CheckTables)

@@ -335,19 +335,24 @@ struct Dp4Params {
   const u32* tiemask;      // [nb_total] bit e: a weight of the run can tie in the float rounding of binade e
   u32* stats;              // [8] tasks / accepted / re-run: state, level, tie / positions re-run / re-run: values
   float level_scale;       // test hook (ZOPFLI_AMD_SEG_SCALE): the guessed levels are multiplied by this
-  const u32* wg_tasks;     // k_dp5_spec: [workgroups][4] the tasks of each workgroup (one block each; SEG_NONE = none),
-                           // the workgroups that hold a head first; task0 = first workgroup of the launch
+  const u32* wg_tasks;     // k_dp5_spec: the blocks' task lists, per block and kind (text tasks, run tasks), and ...
+  const uint2* wg_desc;    // ... [workgroups] the stretch of each workgroup: (first entry, entries) of one block's list of one
+                           // kind; the workgroups that hold a head first; task0 = first workgroup of the launch
   const u32* wmeta;        // k_dp5_spec: [windows][40] the record of each 32-position window (k_mkdesc)
   const u32* winroff;      // k_dp5_spec: [windows] first row of each window (k_mkdesc)
   const u32* winflag;      // k_dp5_spec: per 32-position window, 1 = can take the fast path (k_mkdesc)
   const u32* win_off;      // [nb_total] first window of each block in winflag[]
   int debug;               // ZOPFLI_AMD_SEG_DEBUG: k_dp4_fix prints its decisions
   u16* over;               // [tasks][SEG_OVER] lengths of the cells a speculative task computed beyond its pend
-  u32* redo_count;         // k_dpscan: number of tasks to run a second time ...
-  u32* redo_wg;            // ... and their workgroups for k_dp5_spec ([count][4]: the task, then SEG_NONE)
+  u32* redo_count;         // k_dpscan: [0] entries of redo_wg, [1] and [2] entries of recheck by the parity of the pass
+  u32* redo_wg;            // the tasks to run a second time, as entries for k_dp5_spec ([count][4]: up to four tasks of one
+                           // block, then SEG_NONE)
+  u32* recheck;            // ... and the tasks whose check that changes: every listed task and its successor in the block
+  int redo_pack;           // k_dpscan: tasks per entry of redo_wg, 4 or 1 (table sets with run tasks: there a packed list measured slower)
+  int redo_parity;         // k_dpscan, k_dprecheck: which of redo_count[1], [2] counts this pass's recheck entries
   int int_path;            // k_dp5_spec: 1 = clean windows inside the workgroup's binade take the integer chain step (ZOPFLI_AMD_INT_PATH)
   int fix_lean_min;        // k_dp4_fix: a task with this many generic windows is re-run by the lean one-wave job
-  int redo_pass;           // k_dp5_spec: 1 = this launch runs P.redo_wg (workgroups beyond *redo_count have nothing to do)
+  int redo_pass;           // k_dp5_spec: 1 = this launch runs P.redo_wg, its workgroups striding over the *redo_count entries
   int chain_fast;          // run tasks: 1 = chains of long-run shortcuts in a frame that does not move (zmx_dp5.h; ZOPFLI_AMD_SHORTCUT_CHAIN=0: window by window)
   u32* flags;              // [2] the table set's consistency flags
 };
@@ -917,13 +922,29 @@ __device__ __forceinline__ void d4_run_job(const Dp4Params& P, const D4Job& J, u
 
 // exit[t - 1] against entry[t] for every task but the heads: one wave per task
 __global__ __launch_bounds__(64) void k_dpcheck(Dp4Params P) {
-  // (k_dpscan's list of tasks to run again starts empty: every k_dpscan follows a k_dpcheck, and whoever reads the
-  //  counter — the redo pass of k_dp5_spec — has run by the time the next k_dpcheck starts)
-  if (blockIdx.x == 0 && threadIdx.x == 0) *P.redo_count = 0;
+  // (k_dpscan's lists start empty: every k_dpscan follows a k_dpcheck or a k_dprecheck, and whoever reads the
+  //  counter of the tasks to run again — the redo pass of k_dp5_spec — has run by the time the next check starts)
+  if (blockIdx.x == 0 && threadIdx.x < 3) P.redo_count[threadIdx.x] = 0;
   const u32 t = P.task0 + blockIdx.x;
   if (P.tasks[t].pout == 0) return;
   const SegCheck r = d4_check(&P.exit[t - 1], &P.entry[t], threadIdx.x);
   if (threadIdx.x == 0) P.chk[t] = r;
+}
+
+// The check after a redo pass.  That pass rewrote entry[t] and exit[t] of the listed tasks alone, so only chk[t] and
+// chk[t + 1] of a listed t can differ from the first check's: k_dpscan listed those (P.recheck), the workgroups stride
+// over the list, and chk[] of every other task stays what k_dpcheck wrote.  It empties the list of tasks to run again
+// where k_dpcheck does, and the recheck list of the NEXT pass (the other parity: this launch is still reading its own).
+#define DPRECHECK_GRID 1024u
+__global__ __launch_bounds__(64) void k_dprecheck(Dp4Params P) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { P.redo_count[0] = 0; P.redo_count[2 - P.redo_parity] = 0; }
+  const u32 n = P.redo_count[1 + P.redo_parity];
+  for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+    const u32 t = P.recheck[i];
+    if (P.tasks[t].pout == 0) continue;
+    const SegCheck r = d4_check(&P.exit[t - 1], &P.entry[t], threadIdx.x);
+    if (threadIdx.x == 0) P.chk[t] = r;
+  }
 }
 
 // The acceptance test of a task whose entry state matched its predecessor's exit state up to the
@@ -957,6 +978,8 @@ __global__ __launch_bounds__(64) void k_dpscan(Dp4Params P) {
   // order — so the walk is a prefix sum: 64 tasks at a time, a lane each (one lane walking 240 tasks with two
   // dependent loads per task was 0.12 ms a run).
   double carry = 0.0;
+  // the listed tasks go four to an entry of redo_wg: `fill` tasks are in the entry `cur` so far (both the same in every lane)
+  u32 cur = 0, fill = 0;
   for (u32 c0 = t0 + 1; c0 < t1; c0 += 64) {
     const u32 t = c0 + lane;
     const bool act = t < t1;
@@ -971,19 +994,50 @@ __global__ __launch_bounds__(64) void k_dpscan(Dp4Params P) {
       if ((int)lane >= o) incl += up;
     }
     const double delta = carry + incl;
-    if (act) {
-      const bool ok = ck.match == 1 && d4_accept(ck.vmin, (double)vmax, delta, wmax, tiemask) == 0;
-      if (!ok && ck.match != 0) {          // same structure, wrong level: again from the level the chain implies
-        const u32 slot = atomicAdd(P.redo_count, 1u);
-        u32* wg = P.redo_wg + (u64)slot * 4;
+    // same structure, wrong level: again from the level the chain implies
+    const bool again = act && ck.match != 0 && !(ck.match == 1 && d4_accept(ck.vmin, (double)vmax, delta, wmax, tiemask) == 0);
+    const u64 m = __ballot(again);
+    // (PROF, counters 58 and 59 of the block: the tasks listed and the entries they make)
+    if (m && P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + 58], (u64)__popcll(m));
+    if (m && P.redo_pack == 1) {
+      if (P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + 59], (u64)__popcll(m));
+      if (again) {                        // an entry of its own
+        u32* wg = P.redo_wg + (u64)atomicAdd(&P.redo_count[0], 1u) * 4;
         wg[0] = t; wg[1] = SEG_NONE; wg[2] = SEG_NONE; wg[3] = SEG_NONE;
         P.lvl[t] = (float)((double)P.lvl[t] + delta);
+        const u32 k = atomicAdd(&P.redo_count[1 + P.redo_parity], t + 1 < t1 ? 2u : 1u);
+        P.recheck[k] = t;
+        if (t + 1 < t1) P.recheck[k + 1] = t + 1;
       }
+    } else if (m) {
+      const u32 n = (u32)__popcll(m);
+      const u32 fresh = (fill + n + 3u) / 4u - (fill ? 1u : 0u);      // entries this chunk opens
+      u32 base = 0;
+      if (fresh && lane == 0) base = atomicAdd(&P.redo_count[0], fresh);
+      base = (u32)__builtin_amdgcn_readfirstlane((int)base);
+      if (fresh && P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + 59], (u64)fresh);
+      const u32 first = fill ? cur : base;                            // the entry of rank 0 ... 3
+      const u32 after = fill ? base : base + 1u;                      // ... and of rank 4 ... 7
+      if (again) {
+        const u32 r = fill + (u32)__popcll(m & ((1ull << lane) - 1ull));
+        const u32 e = r < 4u ? first : after + (r >> 2) - 1u;
+        P.redo_wg[(u64)e * 4 + (r & 3u)] = t;
+        P.lvl[t] = (float)((double)P.lvl[t] + delta);
+        // chk[t] and chk[t + 1] are the ones the redo pass changes (a listed successor is listed twice: no harm)
+        const u32 k = atomicAdd(&P.redo_count[1 + P.redo_parity], t + 1 < t1 ? 2u : 1u);
+        P.recheck[k] = t;
+        if (t + 1 < t1) P.recheck[k + 1] = t + 1;
+      }
+      const u32 tot = fill + n;
+      cur = tot <= 4u ? first : after + ((tot + 3u) >> 2) - 2u;
+      fill = tot & 3u;
     }
     // (the exit snapshots at hand are those of the first run: whatever becomes of a task, its exit there plus
     //  its shift is the best estimate of the true state the next task starts from)
     carry += __shfl(incl, 63, 64);
   }
+  // the block's last entry, where it is not full
+  if (fill && lane >= fill && lane < 4u) P.redo_wg[(u64)cur * 4 + lane] = SEG_NONE;
 }
 
 // A task of the speculative pass stops at its first window base >= pend and has the lengths of the

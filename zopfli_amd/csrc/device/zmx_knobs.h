@@ -27,6 +27,8 @@ struct DeviceKnobs {
   unsigned seg_warm = 512;       // ZOPFLI_AMD_SEG_WARM: warm-up positions before a task, rounded up to 64, 64 .. 2^20
   unsigned seg_cuts = 1024;      // ZOPFLI_AMD_SEG_CUTS: how far before a task k_cutpoints looks for a cut point; 0 = every task warms up
   bool seg_mid = true;           // ZOPFLI_AMD_SEG_MID: 0 = no mid snapshots (tasks that leave their binade are re-run whole)
+  unsigned seg_stretch = 4;      // ZOPFLI_AMD_SEG_STRETCH: tasks of one block per workgroup of the speculative pass, 1 .. 32; up to 4 a task a wave (k_dp5_spec), beyond the waves pull them (k_dp5_stretch)
+  bool seg_pull = false;         // ZOPFLI_AMD_SEG_PULL: 1 = k_dp5_stretch runs the main pass at stretches of 4 and fewer too (A/B, test hook)
   int seg_redo = 1;              // ZOPFLI_AMD_SEG_REDO: second speculative passes for tasks that only missed their level
   float seg_scale = 1.0f;        // ZOPFLI_AMD_SEG_SCALE: scale of the tasks' level estimates (test hook: wrong binades)
   int seg_debug = 0;             // ZOPFLI_AMD_SEG_DEBUG: per-task trace of the chain kernels
@@ -67,6 +69,8 @@ DeviceKnobs ParseDeviceKnobs(GetEnv get) {
   k.seg_warm = (clamped("ZOPFLI_AMD_SEG_WARM", 512, 64, 1u << 20) + 63u) & ~63u;
   k.seg_cuts = clamped("ZOPFLI_AMD_SEG_CUTS", 1024, 0, 1u << 16);
   k.seg_mid = clamped("ZOPFLI_AMD_SEG_MID", 1, 0, 1) != 0;
+  k.seg_stretch = clamped("ZOPFLI_AMD_SEG_STRETCH", 4, 1, 32);
+  k.seg_pull = on("ZOPFLI_AMD_SEG_PULL", false);
   k.seg_redo = integer("ZOPFLI_AMD_SEG_REDO", 1);
   if (const char* e = get("ZOPFLI_AMD_SEG_SCALE")) k.seg_scale = static_cast<float>(std::atof(e));
   k.seg_debug = integer("ZOPFLI_AMD_SEG_DEBUG", 0);

@@ -64,6 +64,11 @@ zmx_stats& ThreadStats() {
   return stats;
 }
 
+unsigned long long& CallPositions() {
+  static thread_local unsigned long long positions = 0;
+  return positions;
+}
+
 }  // namespace zamd
 
 namespace {
@@ -233,6 +238,7 @@ struct ShardedCall {
   double t_begin;                 // WallMs() when the call asked for its contexts
   std::vector<Shard> shards;
   std::vector<int> priority;      // stream priority of every shard's context
+  std::vector<unsigned long long> device_positions;   // per shard: the bytes of all the call's shards on its device
   UploadOrder order;
 };
 
@@ -287,6 +293,15 @@ void PlanShards(ShardedCall* call, const std::vector<int>& device_of, bool runs)
   const std::vector<size_t> first = zamd::ShardRanges(parts.size(), ndev, cost.empty() ? nullptr : cost.data(), k.shard_weights);
   call->shards = std::vector<Shard>(ndev);
   for (size_t d = 0; d < ndev; ++d) { call->shards[d].first = first[d]; call->shards[d].last = first[d + 1]; }
+  // what the call puts on each shard's device in all: the chain's task length goes by that, not by the shard (RunShard)
+  // (not for data with long runs of equal bytes: a pass of the chain waits for its longest task there, and tasks twice as
+  //  long took class Z from 482 to 673 ms a step)
+  call->device_positions.assign(ndev, 0);
+  for (size_t d = 0; d < ndev && !runs; ++d) {
+    for (size_t e = 0; e < ndev; ++e) {
+      if (device_of[e] == device_of[d] && first[e + 1] > first[e]) call->device_positions[d] += parts[first[e + 1] - 1].inend - parts[first[e]].instart;
+    }
+  }
   // With block splitting the contexts of one device run at three stream priorities — one after the other instead of
   // side by side: their split searches and joins then fall beside the others' kernels (zmx_ctx_set_priority; 100 MB of
   // text 152 -> 145 ms, without block splitting 123 -> 130: there every context stays on its default streams).
@@ -360,6 +375,13 @@ void RunShard(ShardedCall* call, size_t d, zmx_ctx* ctx, bool retry) {
   std::vector<zamd::Part> mine(parts.begin() + static_cast<long>(sh.first), parts.begin() + static_cast<long>(sh.last));
   for (auto& p : mine) { p.instart -= sh.base; p.inend -= sh.base; }
   const double tr3 = WallMs();
+  // A dealt call's table sets take the task length of the whole call on this device (zamd::CallPositions): the contexts
+  // share the device, and a context's third of 100 MB got 1024-position tasks where 2048 are faster (112.2 -> 107.0 ms a
+  // step, profiles/chain_stretch.txt).  A call that is one shard says nothing: the thresholds of small calls stay.
+  struct CallPositionsScope {
+    explicit CallPositionsScope(unsigned long long n) { zamd::CallPositions() = n; }
+    ~CallPositionsScope() { zamd::CallPositions() = 0; }
+  } call_positions(call->shards.size() > 1 ? call->device_positions[d] : 0);
   struct SplitOnDevice {
     bool was;
     explicit SplitOnDevice(bool on) : was(zamd::g_split_on_device) { zamd::g_split_on_device = on || was; }
@@ -468,7 +490,7 @@ int RunPartsShardedOnce(const ZopfliOptions& options, int btype, const unsigned 
   const double tr_lease = WallMs();
   const InlineHostWork inline_host(parts.size() <= 2 && Pool().InFlight() > 1);
   const size_t ndev = std::min(lease.ctxs.size(), parts.size());
-  ShardedCall call{options, btype, in, dev, parts, sum, part_chunks != nullptr, hooks, tr_begin, {}, {}, {}};
+  ShardedCall call{options, btype, in, dev, parts, sum, part_chunks != nullptr, hooks, tr_begin, {}, {}, {}, {}};
   PlanShards(&call, std::vector<int>(lease.device_of.begin(), lease.device_of.begin() + static_cast<long>(ndev)), runs);
   RunShards(&call, lease.ctxs);
   RetryFailedShards(&call, lease.ctxs);

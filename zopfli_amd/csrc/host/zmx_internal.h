@@ -18,7 +18,7 @@
 // reads, takes and adds them (api.cc: zmx_last_*, and a call's shard threads hand theirs to the caller's at the join),
 // so it owns them, as it owns zamd::ThreadTiming; the device layer adds to them where it times its kernels.
 struct zmx_stats {
-  double kernel_seconds[3];  // k_wtab + k_badscan, chain kernels (k_dp5_spec + k_dpcheck + k_dp4_fix), k_trace (HIP events)
+  double kernel_seconds[3];  // k_wtab + k_badscan, chain kernels (k_dp5_spec + k_dp5_stretch + k_dpcheck + k_dprecheck + k_dpscan + k_dp4_fix), k_trace (HIP events)
   double squeeze_launches;
   double match5[3];          // k_match5: entries in flight summed over lanes and iterations, wave iterations, positions it walked
   double match[4];           // match kernel seconds, k_same + k_chain (+ k_levels ...) seconds, table builds, positions matched
@@ -26,6 +26,9 @@ struct zmx_stats {
 };
 namespace zamd {
 zmx_stats& ThreadStats();   // the calling thread's (thread-local: no lock)
+// The positions the call in progress on this thread has on its device in all, 0 = no more than the table set at hand:
+// set around a dealt call's shard (api.cc: RunShard), read where a table set picks its task length (drv_build.h: SegL).
+unsigned long long& CallPositions();
 }
 
 extern "C" {
