@@ -21,7 +21,7 @@ from zopfli_amd import generate
 
 MAX_MATCH = 258
 EG_CAP = 2048            # zmx_kernels.h: edges a wave of k_codes expands at a time
-WM = 40                  # zmx_dp5.h: words per window record
+WM = 40                  # zmx_dp_build.h: words per window record
 WF_CODELESS = 0x100
 CODELESS_FROM = 64       # a run row of this many edges or more takes no codes
 INLINE_CPS = 8           # change points a device record holds itself; more go to the pool

@@ -53,6 +53,11 @@ def test_options_layout():
     assert (o.verbose, o.verbose_more, o.numiterations, o.blocksplitting, o.blocksplittinglast,
             o.blocksplittingmax) == (0, 0, 15, 1, 0, 15)
     assert ctypes.sizeof(ZopfliOptions) == 24
+    # the keys of api.last_seg_stats are the slots of enum zmx_seg_stat, in its order (the host's reading of the last one)
+    with open(os.path.join(ROOT, "zopfli_amd", "csrc", "host", "zmx_internal.h")) as f:
+        body = re.search(r"enum zmx_seg_stat \{(.*?)\n\s*ZMX_SEG_N,", f.read(), flags=re.S).group(1)
+    slots = re.findall(r"^\s*ZMX_SEG_(\w+),", body, flags=re.M)
+    assert [s.lower() for s in slots] == api.SEG_STAT_KEYS and len(slots) == 8
 
 
 def _ref_run_info(cost):

@@ -1,4 +1,4 @@
-"""The speculative pass of the chain by stretches (zmx_dp5.h: k_dp5_spec, a task a wave, for stretches of up to four
+"""The speculative pass of the chain by stretches (zmx_dp5_spec.h: k_dp5_spec, a task a wave, for stretches of up to four
 tasks; k_dp5_stretch, where a workgroup sets up once and its waves pull the tasks of a stretch from a counter, for
 longer ones, for the packed redo list and wherever ZOPFLI_AMD_SEG_PULL=1 asks for it), the packed redo list (zmx_dp4.h
 k_dpscan) and the partial second check (k_dprecheck).  Every case goes through tests/chain_stretch_probe.py in a subprocess — the geometry is read once per
@@ -100,6 +100,20 @@ def test_partial_second_check():
     assert with_redo["digest"] == without["digest"]
     assert without["rerun_level"] + without["rerun_values"] >= with_redo["rerun_level"] + with_redo["rerun_values"], (with_redo, without)
     assert consistent(with_redo) and consistent(without), (with_redo, without)
+
+
+def test_redo_entries_of_one_task():
+    """The redo pass of a table set with run tasks: every level guessed 1.9 times too high on the block of text and long
+    runs, so k_dpscan lists tasks, a task an entry, and k_dp5_spec<.., true> runs them again from their own levels (no
+    scale, through its redo entry path).  The outputs equal those of a process without redo passes."""
+    st = probe("mixed", ZOPFLI_AMD_SEG_SCALE="1.9", ZOPFLI_AMD_PROF="1")
+    print(st)
+    assert consistent(st), st
+    assert st["redo_reports"] == 3, st
+    assert st["redo_tasks"] > 0, st
+    assert st["redo_entries"] == st["redo_tasks"], st
+    without = probe("mixed", ZOPFLI_AMD_SEG_SCALE="1.9", ZOPFLI_AMD_SEG_REDO="0")
+    assert st["digest"] == without["digest"]
 
 
 def test_stretch_edges_guarded():

@@ -422,7 +422,7 @@ def test_chain_tie_rule(int_path):
     """The exactness branch entropy costs never reach: a cost model of dyadic weights (seg_probe.dyadic_costs)
     ties in the float rounding of the binades 2^13 .. 2^21 (squeeze.c:281-299: float cells, double sums), so a
     task there must not be accepted on a shifted entry state (zmx_dp4.h d4_accept -> 2) nor take the integer
-    chain step (zmx_dp5.h: the workgroup's table is refused when the tie mask has its binade).  length_array
+    chain step (zmx_dp5_spec.h: the workgroup's table is refused when the tie mask has its binade).  length_array
     and the stores equal the oracle's, and the statistics show tasks re-run for the tie rule."""
     import subprocess
     import sys

@@ -2,7 +2,7 @@
 
 A position q that no DP edge crosses — p + kend(p) <= q for every p < q, kend(p) = the longest match
 at p (ZopfliFindLongestMatch, lz77.c:407) or 1 for the literal — splits GetBestLengths (squeeze.c:217)
-exactly; k_cutpoints (zopfli_amd/csrc/device/zmx_dp5.h) starts the chain's tasks there.  This prints,
+exactly; k_cutpoints (zopfli_amd/csrc/device/zmx_dp_build.h) starts the chain's tasks there.  This prints,
 per class of tests' synthetic data, the density of such positions: the numbers quoted in DESIGN.md
 section 4 ("Cut points").
 

@@ -598,13 +598,16 @@ def last_timing(lib=None):
     return d
 
 
+# the slots of zmx_last_seg_stats, in the order of enum zmx_seg_stat (csrc/host/zmx_internal.h, the host's reading)
+SEG_STAT_KEYS = ["tasks", "accepted", "rerun_state", "rerun_level", "rerun_tie", "positions_rerun", "rerun_values", "positions"]
+
+
 def last_seg_stats(lib=None):
     """zmx_last_seg_stats: how the chain's tasks of the last call fared."""
     lib = lib or library()
-    t = (ctypes.c_double * 8)()
+    t = (ctypes.c_double * len(SEG_STAT_KEYS))()
     lib.zmx_last_seg_stats(t)
-    keys = ["tasks", "accepted", "rerun_state", "rerun_level", "rerun_tie", "positions_rerun", "rerun_values", "positions"]
-    return dict(zip(keys, list(t)))
+    return dict(zip(SEG_STAT_KEYS, list(t)))
 
 
 class Context:

@@ -616,7 +616,7 @@ static int BuildChainTasks(zmx_ctx* c, zmx_tables* t) {
   HIPCHK(hipMemcpyAsync(t->d_tasks, t->tasks.data(), nt * sizeof(SegTask), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(t->d_task_off, t->task_off.data(), (nb + 1) * sizeof(u32), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(t->run.stats(t->d_runout), 0, RunLayout::kStats * sizeof(u32), c->stream));
-  // start the tasks at cut points of the DP where there is one close enough (zmx_dp5.h: k_cutpoints);
+  // start the tasks at cut points of the DP where there is one close enough (zmx_dp_build.h: k_cutpoints);
   // ZOPFLI_AMD_SEG_CUTS = how far before a task's first owned position to look, 0 = every task warms up
   // (the search costs 1.1 ms per 100 MB at 1024, the configuration the whole GPU suite ran with; 512 would halve
   //  it and finds the same cut point for 99.8 % of the tasks of text)

@@ -118,43 +118,42 @@ static int ReportSqueezeProf(zmx_tables* t, const double* ksec, const u32* segst
   std::fprintf(stderr, "squeeze prof: edges %.2f ms chain %.2f ms trace %.2f ms; chain wave busy %.1f cycles/position, "
                "%.0f steps, fast %.1f%% of %.0f positions walked (%zu in the blocks); tasks %u accepted %u re-run "
                "state %u values %u level %u tie %u (%u positions, %u by the lean job)\n",
-               ksec[0] * 1e3, ksec[1] * 1e3, ksec[2] * 1e3, a[1] / a[4], a[0],
-               100.0 * a[2] / (a[2] + a[3] + 1e-9), a[4], t->total_b, segstats[0], segstats[1], segstats[2],
-               segstats[6], segstats[3], segstats[4], segstats[5], segstats[7]);
+               ksec[0] * 1e3, ksec[1] * 1e3, ksec[2] * 1e3, a[PF_TASK_CYC] / a[PF_POS], a[PF_STEPS],
+               100.0 * a[PF_FAST] / (a[PF_FAST] + a[PF_SLOW] + 1e-9), a[PF_POS], t->total_b, segstats[ZMX_SEG_TASKS], segstats[ZMX_SEG_ACCEPTED], segstats[ZMX_SEG_RERUN_STATE],
+               segstats[ZMX_SEG_RERUN_VALUES], segstats[ZMX_SEG_RERUN_LEVEL], segstats[ZMX_SEG_RERUN_TIE], segstats[ZMX_SEG_POSITIONS_RERUN], segstats[ZMX_SEG_DEV_LEAN]);
   {
     double mx = 0, hd = 0;
-    for (size_t b = 0; b < nb; ++b) { mx = std::max(mx, static_cast<double>(pr[b * ZMX_PROF_N + 7])); hd = std::max(hd, static_cast<double>(pr[b * ZMX_PROF_N + 8])); }
-    std::fprintf(stderr, "  k_dp5_spec: longest task %.0f cycles, longest head task %.0f cycles; %.1f%% of the positions walked by the integer step (cycles per position there: fetch issue %.1f, fetch wait %.1f, gather + chain %.1f)\n", mx, hd, 100.0 * a[10] / (a[4] + 1e-9), a[11] / (a[10] + 1e-9), a[12] / (a[10] + 1e-9), a[13] / (a[10] + 1e-9));
+    for (size_t b = 0; b < nb; ++b) { mx = std::max(mx, static_cast<double>(pr[b * ZMX_PROF_N + PF_D5_LONGEST])); hd = std::max(hd, static_cast<double>(pr[b * ZMX_PROF_N + PF_D5_HEAD])); }
+    std::fprintf(stderr, "  k_dp5_spec: longest task %.0f cycles, longest head task %.0f cycles; %.1f%% of the positions walked by the integer step (cycles per position there: fetch issue %.1f, fetch wait %.1f, gather + chain %.1f)\n", mx, hd, 100.0 * a[PF_D5_INT_POS] / (a[PF_POS] + 1e-9), a[PF_D5_INT_CYC] / (a[PF_D5_INT_POS] + 1e-9), a[PF_D5_INT_CYC + 1] / (a[PF_D5_INT_POS] + 1e-9), a[PF_D5_INT_CYC + 2] / (a[PF_D5_INT_POS] + 1e-9));
   }
-  // the fixed cost around the tasks, by every pass of k_dp5_spec and k_dp5_stretch: a[54] wave cycles from workgroup (or
-  // entry) start to a wave's first position (a[56] such waves), a[55] wave cycles spent finished in a workgroup that is still
-  // alive, a[57] wave cycles the workgroups were alive for, a[1] in tasks; a[58] tasks listed for the redo pass in a[59] entries
-  if (a[56] > 0 && a[57] > 0) {
+  // the fixed cost around the tasks, by every pass of k_dp5_spec and k_dp5_stretch (what a counter means: ZmxProf, zmx_kernels.h)
+  if (a[PF_SETUP_WAVES] > 0 && a[PF_ALIVE_CYC] > 0) {
     std::fprintf(stderr, "  k_dp5_spec fixed cost: set-up %.0f cycles a wave (%.0f waves with a task), %.2f%% of the workgroups' wave cycles; finished waves waiting for their workgroup %.2f%%; in tasks %.2f%%\n",
-                 a[54] / a[56], a[56], 100.0 * a[54] / a[57], 100.0 * a[55] / a[57], 100.0 * a[1] / a[57]);
+                 a[PF_SETUP_CYC] / a[PF_SETUP_WAVES], a[PF_SETUP_WAVES], 100.0 * a[PF_SETUP_CYC] / a[PF_ALIVE_CYC], 100.0 * a[PF_IDLE_CYC] / a[PF_ALIVE_CYC], 100.0 * a[PF_TASK_CYC] / a[PF_ALIVE_CYC]);
   }
-  std::fprintf(stderr, "  redo list: %.0f tasks in %.0f entries\n", a[58], a[59]);
+  std::fprintf(stderr, "  redo list: %.0f tasks in %.0f entries\n", a[PF_REDO_TASKS], a[PF_REDO_ENTRIES]);
   std::fprintf(stderr, "  k_dp5_spec integer windows, cycles per position: class decision %.1f, waiting for the prefetched record and codes %.1f, prefetch issue %.1f\n",
-               a[20] / (a[10] + 1e-9), a[21] / (a[10] + 1e-9), a[22] / (a[10] + 1e-9));
+               a[PF_D5_INTWIN] / (a[PF_D5_INT_POS] + 1e-9), a[PF_D5_INTWIN + 1] / (a[PF_D5_INT_POS] + 1e-9), a[PF_D5_INTWIN + 2] / (a[PF_D5_INT_POS] + 1e-9));
   std::fprintf(stderr, "  k_dp5_spec windows: integer %.1f%% of positions at %.0f cycles each, class 1 in doubles %.1f%% at %.0f, class 2 %.1f%% at %.0f, generic %.1f%% at %.0f\n",
-               100.0 * a[28] / (a[4] + 1e-9), a[24] / (a[28] + 1e-9), 100.0 * a[29] / (a[4] + 1e-9), a[25] / (a[29] + 1e-9),
-               100.0 * a[30] / (a[4] + 1e-9), a[26] / (a[30] + 1e-9), 100.0 * a[31] / (a[4] + 1e-9), a[27] / (a[31] + 1e-9));
+               100.0 * a[PF_D5_CLASS_POS] / (a[PF_POS] + 1e-9), a[PF_D5_CLASS_CYC] / (a[PF_D5_CLASS_POS] + 1e-9), 100.0 * a[PF_D5_CLASS_POS + 1] / (a[PF_POS] + 1e-9), a[PF_D5_CLASS_CYC + 1] / (a[PF_D5_CLASS_POS + 1] + 1e-9),
+               100.0 * a[PF_D5_CLASS_POS + 2] / (a[PF_POS] + 1e-9), a[PF_D5_CLASS_CYC + 2] / (a[PF_D5_CLASS_POS + 2] + 1e-9), 100.0 * a[PF_D5_CLASS_POS + 3] / (a[PF_POS] + 1e-9), a[PF_D5_CLASS_CYC + 3] / (a[PF_D5_CLASS_POS + 3] + 1e-9));
   std::fprintf(stderr, "  k_dp5_spec generic windows, cycles each: shortcut %.0f (%.0f of them), run row integer %.0f (%.0f), run row doubles %.0f (%.0f), other row %.0f (%.0f), window header %.0f (%.0f)\n",
-               a[32] / (a[33] + 1e-9), a[33], a[34] / (a[35] + 1e-9), a[35], a[36] / (a[37] + 1e-9), a[37], a[38] / (a[39] + 1e-9), a[39], a[40] / (a[41] + 1e-9), a[41]);
+               a[PF_D5_GEN] / (a[PF_D5_GEN + 1] + 1e-9), a[PF_D5_GEN + 1], a[PF_D5_GEN + 2] / (a[PF_D5_GEN + 3] + 1e-9), a[PF_D5_GEN + 3], a[PF_D5_GEN + 4] / (a[PF_D5_GEN + 5] + 1e-9), a[PF_D5_GEN + 5], a[PF_D5_GEN + 6] / (a[PF_D5_GEN + 7] + 1e-9), a[PF_D5_GEN + 7], a[PF_D5_GEN + 8] / (a[PF_D5_GEN + 9] + 1e-9), a[PF_D5_GEN + 9]);
   std::fprintf(stderr, "  k_dp5_spec positions: run interior %.0f in unrolled windows, %.0f in loops with room, %.0f with checks; general step: %.0f run rows, %.0f other rows; class 2: %.0f rows that reach register 2\n",
-               a[42], a[43], a[44], a[45], a[46], a[47]);
+               a[PF_D5_GEN_POS], a[PF_D5_GEN_POS + 1], a[PF_D5_GEN_POS + 2], a[PF_D5_GEN_POS + 3], a[PF_D5_GEN_POS + 4], a[PF_D5_GEN_POS + 5]);
   {
-    const double gen = a[51] - a[49] - a[50] - a[52];     // (the loop over a window's positions, less its stretches)
+    const double gen = a[PF_D5_GEN_CYC + 3] - a[PF_D5_GEN_CYC + 1] - a[PF_D5_GEN_CYC + 2] - a[PF_D5_OTHER_CYC];     // (the loop over a window's positions, less its stretches)
     std::fprintf(stderr, "  k_dp5_spec generic windows, cycles: headers %.3g, run stretches: whole windows %.3g (%.0f per position), others %.3g (%.0f); stretches of other rows %.3g (%.0f); the general step %.3g (%.0f per position incl. shortcuts)\n",
-                 a[48], a[49], a[49] / (a[42] + 1e-9), a[50], a[50] / (a[43] + a[44] + 1e-9), a[52], a[52] / (a[53] + 1e-9), gen, gen / (a[45] + a[46] + a[33] + 1e-9));
+                 a[PF_D5_GEN_CYC], a[PF_D5_GEN_CYC + 1], a[PF_D5_GEN_CYC + 1] / (a[PF_D5_GEN_POS] + 1e-9), a[PF_D5_GEN_CYC + 2], a[PF_D5_GEN_CYC + 2] / (a[PF_D5_GEN_POS + 1] + a[PF_D5_GEN_POS + 2] + 1e-9), a[PF_D5_OTHER_CYC], a[PF_D5_OTHER_CYC] / (a[PF_D5_OTHER_POS] + 1e-9), gen, gen / (a[PF_D5_GEN_POS + 3] + a[PF_D5_GEN_POS + 4] + a[PF_D5_GEN + 1] + 1e-9));
   }
   const char* nm[5] = {"32", "16", "8", "8 (two registers)", "generic"};
   for (int i = 0; i < 5; ++i)
-    std::fprintf(stderr, "  path %-18s %5.1f%% of positions, %6.1f cycles/position\n", nm[i], 100.0 * a[6 + 2 * i] / a[4],
-                 a[5 + 2 * i] / (a[6 + 2 * i] + 1e-9));
+    std::fprintf(stderr, "  path %-18s %5.1f%% of positions, %6.1f cycles/position\n", nm[i], 100.0 * a[PF_D4_PATH + 1 + 2 * i] / a[PF_POS],
+                 a[PF_D4_PATH + 2 * i] / (a[PF_D4_PATH + 1 + 2 * i] + 1e-9));
+  const u32 wave_base[2] = {PF_D4_WAVE1, PF_D4_WAVE2};
   for (int w = 0; w < 2; ++w)
     std::fprintf(stderr, "  producer wave %d, cycles/step: walk %.0f ring %.0f tiles %.0f barrier %.0f\n", w + 1,
-                 a[16 + 8 * w] / a[0], a[17 + 8 * w] / a[0], a[18 + 8 * w] / a[0], a[19 + 8 * w] / a[0]);
+                 a[wave_base[w]] / a[PF_STEPS], a[wave_base[w] + 1] / a[PF_STEPS], a[wave_base[w] + 2] / a[PF_STEPS], a[wave_base[w] + 3] / a[PF_STEPS]);
   return 0;
 }
 
@@ -350,8 +349,8 @@ int zmx_squeeze_run(zmx_ctx* c, zmx_tables* t, const double* cost, const double*
     zmx_stats& ts = zamd::ThreadStats();   // (thread-local: no lock)
     for (int i = 0; i < 3; ++i) ts.kernel_seconds[i] += ksec[i];
     ts.squeeze_launches += 1;
-    for (int i = 0; i < 7; ++i) ts.seg[i] += segstats[i];
-    ts.seg[7] += static_cast<double>(t->total_b);
+    // (the host's last slot is the positions of the blocks, not the device's count of lean jobs: zmx_seg_stat)
+    for (int i = 0; i < ZMX_SEG_N; ++i) ts.seg[i] += i == ZMX_SEG_POSITIONS ? static_cast<double>(t->total_b) : segstats[i];
   }
   if (t->d_prof) return ReportSqueezeProf(t, ksec, segstats);
   return 0;

@@ -7,7 +7,7 @@
 // that says where the parts lie: in = cost | mincost | wmax | tiemask | est | slot, out = hist | nsym | stats | flags.
 // The accessors take the base of either copy, the device's or the pinned one.
 struct RunLayout {
-  static constexpr size_t kStats = 8, kFlags = 4;   // words: the task statistics (k_wtab zeroes them), the consistency flags
+  static constexpr size_t kStats = ZMX_SEG_N, kFlags = 4;   // words: the task statistics (zmx_seg_stat, the device's reading; k_wtab zeroes them), the consistency flags
   size_t in_cost = 0, in_mincost = 0, in_wmax = 0, in_tiemask = 0, in_est = 0, in_slot = 0, in_bytes = 0;
   size_t out_hist = 0, out_nsym = 0, out_stats = 0, out_flags = 0, out_bytes = 0;
   RunLayout() = default;

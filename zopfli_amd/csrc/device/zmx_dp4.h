@@ -28,7 +28,7 @@
 // written.  Any task that fails a test is run again from the true exit state of its predecessor
 // (no guess, no warm-up), which is the serial chain itself.  Nothing unverified is ever used.
 //
-// The speculative pass over all tasks is k_dp5_spec (zmx_dp5.h: one wave per task, built for
+// The speculative pass over all tasks is k_dp5_spec (zmx_dp5_spec.h, its job in zmx_dp5.h: one wave per task, built for
 // throughput).  The serial re-runs of k_dp4_fix below use the round-1 k_dp3 pipeline, built for the
 // latency of ONE chain: one workgroup of four waves (one per SIMD), with one
 // s_barrier per STEP (a run of positions of one 64-position group whose edge rows span at most
@@ -707,9 +707,9 @@ __device__ __forceinline__ void d4_run_job(const Dp4Params& P, const D4Job& J, u
     }
     if (PROF && P.prof && lane == 0) {
       u64* o = P.prof + (u64)b * ZMX_PROF_N;
-      atomicAdd(&o[0], n_steps); atomicAdd(&o[1], t_work); atomicAdd(&o[2], n_fast); atomicAdd(&o[3], n_slow);
-      atomicAdd(&o[4], n_fast + n_slow);
-      for (int i = 0; i < 5; ++i) { atomicAdd(&o[5 + 2 * i], tp[i]); atomicAdd(&o[6 + 2 * i], np[i]); }
+      atomicAdd(&o[PF_STEPS], n_steps); atomicAdd(&o[PF_TASK_CYC], t_work); atomicAdd(&o[PF_FAST], n_fast); atomicAdd(&o[PF_SLOW], n_slow);
+      atomicAdd(&o[PF_POS], n_fast + n_slow);
+      for (int i = 0; i < 5; ++i) { atomicAdd(&o[PF_D4_PATH + 2 * i], tp[i]); atomicAdd(&o[PF_D4_PATH + 1 + 2 * i], np[i]); }
     }
   } else if (wave == 1) {
     // =================================================================== wave 1: the walk and the ring
@@ -795,7 +795,7 @@ __device__ __forceinline__ void d4_run_job(const Dp4Params& P, const D4Job& J, u
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA in flight when the ring is reused
     if (J.exit && lane == 0) { J.exit->base = W.base; J.exit->noshort = W.noshort ? 1u : 0u; J.exit->skip = 0u; }
     if (PROF && P.prof && lane == 0) {
-      u64* o = P.prof + (u64)b * ZMX_PROF_N + 16;
+      u64* o = P.prof + (u64)b * ZMX_PROF_N + PF_D4_WAVE1;
       for (int i = 0; i < 4; ++i) atomicAdd(&o[i], tq[i]);
     }
   } else {
@@ -908,7 +908,7 @@ __device__ __forceinline__ void d4_run_job(const Dp4Params& P, const D4Job& J, u
     }
     __syncthreads();         // the chain wave's last step
     if (PROF && P.prof && wave == 2 && lane == 0) {
-      u64* o = P.prof + (u64)b * ZMX_PROF_N + 24;
+      u64* o = P.prof + (u64)b * ZMX_PROF_N + PF_D4_WAVE2;
       for (int i = 0; i < 4; ++i) atomicAdd(&o[i], tq[i]);
     }
   }
@@ -997,10 +997,10 @@ __global__ __launch_bounds__(64) void k_dpscan(Dp4Params P) {
     // same structure, wrong level: again from the level the chain implies
     const bool again = act && ck.match != 0 && !(ck.match == 1 && d4_accept(ck.vmin, (double)vmax, delta, wmax, tiemask) == 0);
     const u64 m = __ballot(again);
-    // (PROF, counters 58 and 59 of the block: the tasks listed and the entries they make)
-    if (m && P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + 58], (u64)__popcll(m));
+    // (PROF: the tasks listed and the entries they make)
+    if (m && P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + PF_REDO_TASKS], (u64)__popcll(m));
     if (m && P.redo_pack == 1) {
-      if (P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + 59], (u64)__popcll(m));
+      if (P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + PF_REDO_ENTRIES], (u64)__popcll(m));
       if (again) {                        // an entry of its own
         u32* wg = P.redo_wg + (u64)atomicAdd(&P.redo_count[0], 1u) * 4;
         wg[0] = t; wg[1] = SEG_NONE; wg[2] = SEG_NONE; wg[3] = SEG_NONE;
@@ -1015,7 +1015,7 @@ __global__ __launch_bounds__(64) void k_dpscan(Dp4Params P) {
       u32 base = 0;
       if (fresh && lane == 0) base = atomicAdd(&P.redo_count[0], fresh);
       base = (u32)__builtin_amdgcn_readfirstlane((int)base);
-      if (fresh && P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + 59], (u64)fresh);
+      if (fresh && P.prof && lane == 0) atomicAdd(&P.prof[(u64)b * ZMX_PROF_N + PF_REDO_ENTRIES], (u64)fresh);
       const u32 first = fill ? cur : base;                            // the entry of rank 0 ... 3
       const u32 after = fill ? base : base + 1u;                      // ... and of rank 4 ... 7
       if (again) {
@@ -1052,4 +1052,4 @@ __device__ __forceinline__ void d4_copy_over(const Dp4Params& P, u32 t, u32 B, u
   for (u32 i = threadIdx.x; pend + i < stop && pend + i <= B; i += blockDim.x) la[pend + i] = over[i];
 }
 
-// (k_dp4_fix, the serial pass, is at the end of zmx_dp5.h: it uses the jobs of both files)
+// (k_dp4_fix, the serial pass, is in zmx_dp4_fix.h: it uses the jobs of this file and of zmx_dp5.h)

@@ -1,7 +1,8 @@
-// k_dp5_spec: the speculative pass over the chain's tasks (see zmx_dp4.h for what a task is and why
-// its result can be trusted) written for THROUGHPUT: one wave per task, no LDS staging, no helper
-// waves, so that a CU runs a dozen tasks at once and the waves of a SIMD fill each other's stalls.
-// Included only by zmx_hip.hip, after zmx_dp4.h (same jobs, snapshots, cell registers, arithmetic).
+// d5_run_job: one task of the chain (see zmx_dp4.h for what a task is and why its result can be trusted) walked by
+// ONE wave, written for THROUGHPUT: no LDS staging by helper waves, so that a CU runs a dozen tasks at once and the
+// waves of a SIMD fill each other's stalls.  The speculative kernels (zmx_dp5_spec.h) run it a task a wave, k_dp4_fix
+// (zmx_dp4_fix.h) as its lean serial re-run.  Included only by zmx_hip.hip, after zmx_dp4.h (same jobs, snapshots,
+// cell registers, arithmetic) and zmx_dp_build.h (the window records it reads).
 //
 // k_dp4's four-wave pipeline is built for the latency of ONE chain (one workgroup per CU, 142 KB of
 // LDS): right for the stretches k_dp4_fix has to run serially, wasteful when 50 000 independent tasks
@@ -43,78 +44,8 @@ typedef u32 d5_u32x4 __attribute__((ext_vector_type(4)));
 typedef u32 d5_u32x2 __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(4))) d5_u32x4* d5_cdscp;
 
-// What k_dp5_spec needs to fetch the rows of a 32-position window (aligned to the block start).  The rows of
-// consecutive positions are consecutive in codes[] (dph's offsets are a running sum of the row lengths), so the
-// wave copies the window's codes into LDS in one piece and lane l finds code l - u - 1 of row u at index
-// rel[u] + l of the copy.  Everything a window needs besides the codes is ONE 40-word record (wmeta), fetched by
-// ONE vector load a window ahead: words 0..31 = (rel[u] + 32) << 16 | kend[u], 32 / 33 = where the window's rows
-// start / end in the block's codes, 34 = the window's class (1 = 32 positions, none flagged for the long-run
-// shortcut, no edge beyond cell register 0; 2 = none flagged, edges of any length; 0 = neither).
-//
-// Why this shape — what round 2 measured on the way (all bit-exact, profiles/): a 16-byte buffer descriptor per
-// position and a buffer_load per row: the CU's address unit is busy 16 cycles per wave-wide load whatever the
-// lanes do, 256 cycles per position with 16 waves; descriptors built by SALU from packed row lengths: 30
-// instructions per position around a chain step of six, and a wave issues one instruction per four cycles at
-// best; s_load for the per-window words: SMEM shares its counter with LDS, so nothing scalar can be in flight
-// across a window; and, throughout, three dependent memory round trips per window that four waves per SIMD do
-// not hide (95 % of a window's 9 000 cycles were waiting).
-#define D5_WM 40u          // words per window in wmeta[]
-#define D5_WF_CODELESS 0x100u   // winflag / wmeta word 34, beside the window's kind in the low byte: a row without codes (k_rowscan)
 #define D5_STAGE_BYTES 4352u    // a wave's staging area: >= 4096 + 16, >= 6 DP_XN
 #define D5_STAGE_HALF 2176u     // two halves of >= 2048 + 16 for the LDS-DMA double buffer
-struct MkDescParams {
-  const BlockDesc* blocks;
-  const uint2* dph;
-  u32* wmeta;           // [windows + 1 per block][D5_WM]
-  u32* winroff;         // [windows + 1 per block] = wmeta word 32 (the scalar path of windows nobody prefetched)
-  const u32* win_off;   // [nb] first window of each block in winflag[] / winroff[] / wmeta[]
-  u32* winflag;         // [windows + 1 per block] = wmeta word 34
-};
-
-__global__ __launch_bounds__(256) void k_mkdesc(MkDescParams P) {
-  const BlockDesc bd = P.blocks[blockIdx.y];
-  const u32 B = (u32)(bd.inend - bd.instart);
-  const u32 p = blockIdx.x * 256u + threadIdx.x;
-  const u32 lane = threadIdx.x & 63;
-  uint2 dhw = make_uint2(0, 0);
-  if (p < B) dhw = P.dph[bd.pos_off + p];
-  // (whole waves take part in the ballots and the shuffle; a wave covers two windows)
-  const bool flagged = p >= B || ((dhw.y >> 16) & 1u) != 0;
-  const u64 not1 = __ballot(flagged || (dhw.y & 0xffffu) + (lane & 31u) >= 64u);    // an edge beyond cell register 0
-  // flagged for the shortcut, or short — or a wide run row (k_rowscan): those go position by position, where their
-  // weights come from the run-row table instead of six scattered code loads (d5_run_job)
-  const u64 not2 = __ballot(flagged || (((dhw.y >> 17) & 1u) != 0 && (dhw.y & 0xffffu) >= 64u));
-  // a row that reaches beyond cell register 1: kind 3 = kind 2 with such rows.  The text variant of the job takes it as
-  // kind 2 (the rest of such a row on demand: rare there); the run variant position by position with staged codes
-  // (the last 257 positions of every run of class Z are such rows: 1 800 cycles a position as kind 2)
-  const u64 far3 = __ballot(p < B && (dhw.y & 0xffffu) + (lane & 31u) >= 128u);
-  const u32 first = (u32)__shfl((int)dhw.x, (int)(lane & 32u), 64);                  // row offset of the window's first position
-  const u32 w = P.win_off[blockIdx.y] + (p >> 5);
-  u32* wm = P.wmeta + (u64)w * D5_WM;
-  const u32 kend = dhw.y & 0xffffu;
-  const u32 klay = dph_layout_len(dhw.y);      // (what the row takes in codes[]: nothing for a wide run row)
-  const u64 nocodes = __ballot(p < B && (dhw.y & DPH_CODELESS) != 0);
-  if (p < ((B + 31u) & ~31u)) wm[p & 31u] = p < B ? ((dhw.x - first + 32u - ((p & 31u) + 1u)) << 16) | kend : 0u;
-  if ((lane & 31u) == 0 && p < B) {
-    const u32 sh = lane & 32u;
-    // (bit 8, D5_WF_CODELESS: a row of the window has no codes — such a window is of kind 0, and a task that holds one is
-    //  re-run by the lean one-wave job, never by k_dp4's pipeline, whose ring expects every row's codes)
-    const u32 f = ((u32)(not1 >> sh) == 0 ? 1u : (u32)(not2 >> sh) != 0 ? 0u : (u32)(far3 >> sh) == 0 ? 2u : 3u) |
-                  ((u32)(nocodes >> sh) != 0 ? D5_WF_CODELESS : 0u);
-    P.winflag[w] = f;
-    P.winroff[w] = dhw.x;
-    wm[32] = dhw.x;
-    wm[34] = f;
-  }
-  if (p < B && ((p & 31u) == 31u || p + 1 == B)) wm[33] = dhw.x + klay;           // where the window's rows end
-  if (p + 1 == B) {      // one record past the last window: where the block's rows end, class 0
-    P.winroff[w + 1] = dhw.x + klay;
-    P.winflag[w + 1] = 0;
-    wm[D5_WM + 32] = dhw.x + klay;
-    wm[D5_WM + 33] = dhw.x + klay;
-    wm[D5_WM + 34] = 0;
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
 // The chain step in INTEGER arithmetic, exact inside one binade.
@@ -159,24 +90,19 @@ __device__ __forceinline__ u64 d5_rne_scaled(double w, int e) {
 }
 
 // max / min over the 64 lanes of a wave (four DPP rows), the result uniform
-__device__ __forceinline__ u32 d5_max64(u32 v) {
-#define D5_DPP_STEP(CTRL) { const u32 t_ = (u32)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false); v = v > t_ ? v : t_; }
-  D5_DPP_STEP(0x111) D5_DPP_STEP(0x112) D5_DPP_STEP(0x114) D5_DPP_STEP(0x118)
+#define D5_DPP_STEP(CTRL, OP) { const u32 t_ = (u32)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false); v = v OP t_ ? v : t_; }
+#define D5_REDUCE64(NAME, OP)                                                                                             \
+  __device__ __forceinline__ u32 NAME(u32 v) {                                                                            \
+    D5_DPP_STEP(0x111, OP) D5_DPP_STEP(0x112, OP) D5_DPP_STEP(0x114, OP) D5_DPP_STEP(0x118, OP)                           \
+    const u32 a = (u32)__builtin_amdgcn_readlane((int)v, 15), b2 = (u32)__builtin_amdgcn_readlane((int)v, 31);            \
+    const u32 a3 = (u32)__builtin_amdgcn_readlane((int)v, 47), a4 = (u32)__builtin_amdgcn_readlane((int)v, 63);           \
+    const u32 m1 = a OP b2 ? a : b2, m2 = a3 OP a4 ? a3 : a4;                                                             \
+    return m1 OP m2 ? m1 : m2;                                                                                            \
+  }
+D5_REDUCE64(d5_max64, >)
+D5_REDUCE64(d5_min64, <)
+#undef D5_REDUCE64
 #undef D5_DPP_STEP
-  const u32 a = (u32)__builtin_amdgcn_readlane((int)v, 15), b2 = (u32)__builtin_amdgcn_readlane((int)v, 31);
-  const u32 a3 = (u32)__builtin_amdgcn_readlane((int)v, 47), a4 = (u32)__builtin_amdgcn_readlane((int)v, 63);
-  const u32 m1 = a > b2 ? a : b2, m2 = a3 > a4 ? a3 : a4;
-  return m1 > m2 ? m1 : m2;
-}
-__device__ __forceinline__ u32 d5_min64(u32 v) {
-#define D5_DPP_STEP(CTRL) { const u32 t_ = (u32)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false); v = v < t_ ? v : t_; }
-  D5_DPP_STEP(0x111) D5_DPP_STEP(0x112) D5_DPP_STEP(0x114) D5_DPP_STEP(0x118)
-#undef D5_DPP_STEP
-  const u32 a = (u32)__builtin_amdgcn_readlane((int)v, 15), b2 = (u32)__builtin_amdgcn_readlane((int)v, 31);
-  const u32 a3 = (u32)__builtin_amdgcn_readlane((int)v, 47), a4 = (u32)__builtin_amdgcn_readlane((int)v, 63);
-  const u32 m1 = a < b2 ? a : b2, m2 = a3 < a4 ? a3 : a4;
-  return m1 < m2 ? m1 : m2;
-}
 
 // The workgroup builds the table of binade `e` from the run's weights (s_wtab is in place); returns false
 // (every thread alike) when the binade is out of range or a weight can tie there.
@@ -1201,634 +1127,20 @@ __device__ __forceinline__ void d5_run_job(const Dp4Params& P, const D4Job& J, u
   }
   if (PROF && P.prof && lane == 0) {
     u64* o = P.prof + (u64)b * ZMX_PROF_N;
-    atomicAdd(&o[1], (u64)__builtin_readcyclecounter() - t_begin);
-    atomicAdd(&o[2], n_fast); atomicAdd(&o[3], n_slow); atomicAdd(&o[4], n_fast + n_slow);
-    atomicAdd(&o[5], (u64)__builtin_readcyclecounter() - t_begin); atomicAdd(&o[6], n_fast);
-    atomicAdd(&o[14], n_slow);
-    atomicAdd(&o[10], n_int);
-    for (int i = 0; i < 3; ++i) atomicAdd(&o[20 + i], pw[i]);
-    for (int i = 0; i < 4; ++i) { atomicAdd(&o[24 + i], kc[i]); atomicAdd(&o[28 + i], kn[i]); }
-    atomicAdd(&o[11], pq[0]); atomicAdd(&o[12], pq[1]); atomicAdd(&o[13], pq[2]);
-    for (int i = 0; i < 10; ++i) atomicAdd(&o[32 + i], gq[i]);
-    for (int i = 0; i < 6; ++i) atomicAdd(&o[42 + i], gr[i]);
-    for (int i = 0; i < 4; ++i) atomicAdd(&o[48 + i], gt[i]);
-    atomicAdd(&o[52], go[0]); atomicAdd(&o[53], go[1]);
+    atomicAdd(&o[PF_TASK_CYC], (u64)__builtin_readcyclecounter() - t_begin);
+    atomicAdd(&o[PF_FAST], n_fast); atomicAdd(&o[PF_SLOW], n_slow); atomicAdd(&o[PF_POS], n_fast + n_slow);
+    atomicAdd(&o[PF_D5_CYC], (u64)__builtin_readcyclecounter() - t_begin); atomicAdd(&o[PF_D5_FAST], n_fast);
+    atomicAdd(&o[PF_D5_SLOW], n_slow);
+    atomicAdd(&o[PF_D5_INT_POS], n_int);
+    for (int i = 0; i < 3; ++i) atomicAdd(&o[PF_D5_INTWIN + i], pw[i]);
+    for (int i = 0; i < 4; ++i) { atomicAdd(&o[PF_D5_CLASS_CYC + i], kc[i]); atomicAdd(&o[PF_D5_CLASS_POS + i], kn[i]); }
+    atomicAdd(&o[PF_D5_INT_CYC], pq[0]); atomicAdd(&o[PF_D5_INT_CYC + 1], pq[1]); atomicAdd(&o[PF_D5_INT_CYC + 2], pq[2]);
+    for (int i = 0; i < 10; ++i) atomicAdd(&o[PF_D5_GEN + i], gq[i]);
+    for (int i = 0; i < 6; ++i) atomicAdd(&o[PF_D5_GEN_POS + i], gr[i]);
+    for (int i = 0; i < 4; ++i) atomicAdd(&o[PF_D5_GEN_CYC + i], gt[i]);
+    atomicAdd(&o[PF_D5_OTHER_CYC], go[0]); atomicAdd(&o[PF_D5_OTHER_POS], go[1]);
     const u64 dt = (u64)__builtin_readcyclecounter() - t_begin;
-    atomicMax(&o[7], dt);                               // the longest task of the block
-    if (J.la_lo == 1) atomicAdd(&o[8], dt);             // the head task
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// CUT POINTS.  A position q that no DP edge crosses — p + kend(p) <= q for every p < q (kend: the longest
-// match at p, or 1 for the literal: dph[p].y) — splits GetBestLengths exactly: every cell beyond q gets its
-// value through cell q alone, so a chain started at q from ONE cell is the true chain shifted by a constant,
-// with no warm-up and nothing left to chance (a long-run shortcut cannot span a cut either: the run's own
-// matches would cross it).  Text has one every ~25 positions (largest gap seen: 688), data made of long runs
-// almost none.  One wave per task looks for the last cut point at most `depth` positions before the task's
-// pout and makes it the task's start (SegTask.q, which then need not be a multiple of 32: k_dp5_spec starts
-// at the window that holds it, with the level in that window's cell); tasks without one keep the warm-up.
-// ---------------------------------------------------------------------------------------------
-struct CutParams {
-  const BlockDesc* blocks;
-  const uint2* dph;
-  SegTask* tasks;
-  u32 depth;
-  u32 warm;        // the warm-up a task without a cut point would get
-  u32* found;      // [2]: tasks that got a cut point, sum of (pout - q) over them
-  u32* wide;       // [tasks]: 1 = no cut point, and the warm-up stretch holds long-run material (see below)
-};
-
-// A task that finds no cut point has to rely on coalescence (zmx_dp4.h) over its warm-up stretch.  Inside and
-// behind runs of equal bytes that does not happen: the long-run shortcut (squeeze.c:251-271) copies 258 cells
-// unmixed, and where every row is 258 edges of one distance the paths run side by side — measured on class Z,
-// 90 % of such tasks were re-run serially.  So a task whose warm-up stretch holds a shortcut position or a run row
-// of 64+ edges is not started at all: the host merges it into its predecessor (BuildTables), whose own start IS a
-// cut point (or the block's head) — tasks become the stretches between cut points there, every one exact by
-// construction, and the only thing left to verify is the level.
-__global__ __launch_bounds__(64) void k_cutpoints(CutParams P) {
-  const u32 t = blockIdx.x;
-  const SegTask K = P.tasks[t];
-  if (K.pout == 0) return;      // the head of a block starts from the block's true state
-  const BlockDesc bd = P.blocks[K.block];
-  const uint2* dph = P.dph + bd.pos_off;
-  const u32 lane = threadIdx.x;
-  const u32 lo = K.pout > P.depth + ZMX_MAX_MATCH ? K.pout - P.depth - ZMX_MAX_MATCH : 0u;
-  const u32 wlo = K.pout > P.warm ? K.pout - P.warm : 0u;
-  // the prefix maximum from lo on is the true one for q >= lo + 258 (no edge is longer), and for every q if lo = 0
-  const u32 q_min = lo == 0 ? 1u : lo + ZMX_MAX_MATCH;
-  u32 carry = 0, best = SEG_NONE;
-  bool wide = false;
-  for (u32 p0 = lo; p0 < K.pout; p0 += 64) {
-    const u32 p = p0 + lane;
-    const u32 y = p < K.pout ? dph[p].y : 0u;
-    const u32 r = p < K.pout ? p + (y & 0xffffu) : 0u;
-    wide |= p >= wlo && (((y >> 16) & 1u) != 0 || (((y >> 17) & 1u) != 0 && (y & 0xffffu) >= 64u));
-    u32 incl = wave_scan_max(r);
-    incl = incl > carry ? incl : carry;
-    // q = p + 1 is a cut point; not pout itself: the start cell has no source, and the cells from pout on are
-    // compared with the predecessor's, sources included
-    const u64 ok = __ballot(p + 1 < K.pout && p + 1 >= q_min && incl <= p + 1);
-    if (ok) best = p0 + (63u - (u32)__builtin_clzll(ok)) + 1u;
-    carry = rdlane_u32(incl, 63);
-  }
-  const bool any_wide = __any(wide);
-  if (lane == 0) {
-    P.wide[t] = best == SEG_NONE && any_wide ? 1u : 0u;
-    if (best != SEG_NONE) {
-      P.tasks[t].q = best;
-      atomicAdd(&P.found[0], 1u);
-      atomicAdd(&P.found[1], K.pout - best);
-    }
-  }
-}
-
-// Which of the two k_dp5_spec variants a task is for: 1 = at least a quarter of its 32-position windows are of the
-// generic kind (shortcut positions, wide run rows: k_mkdesc), i.e. it walks runs of equal bytes.  One wave per task.
-struct TaskKindParams {
-  const SegTask* tasks;
-  const BlockDesc* blocks;
-  const u32* winflag;
-  const u32* win_off;
-  u32* kind;
-};
-__global__ __launch_bounds__(64) void k_taskkind(TaskKindParams P) {
-  const u32 t = blockIdx.x;
-  const SegTask K = P.tasks[t];
-  const BlockDesc bd = P.blocks[K.block];
-  const u32 B = (u32)(bd.inend - bd.instart);
-  const u32* wf = P.winflag + P.win_off[K.block];
-  const u32 w0 = K.q >> 5, w1 = ((K.pend < B ? K.pend : B) + 31u) >> 5;
-  u32 g = 0;
-  for (u32 w = w0 + threadIdx.x; w < w1; w += 64) g += (wf[w] & 0xffu) == 0 || (wf[w] & 0xffu) == 3 ? 1u : 0u;
-  g = wave_scan_add(g);
-  if (threadIdx.x == 63) P.kind[t] = 4u * g >= (w1 - w0) && g >= 4u ? 1u : 0u;
-}
-
-// k_dp5_spec: a workgroup = four waves = up to four tasks of ONE block and one kind — a stretch (P.wg_desc) of at most
-// four entries of the block's task list (P.wg_tasks), a task a wave —, sharing the run's weight table in LDS; after the
-// table is in place the waves go their own ways.  This is the form the main pass runs by default: the window loop of
-// d5_run_job is at the edge of its register budget, and a loop over tasks around it (k_dp5_stretch, below) costs it 7 %.
-#define D5_WG 4u
-template <bool PROF, int WAVES, bool RUNS>
-__global__ __launch_bounds__(64 * D5_WG, WAVES) void k_dp5_spec(Dp4Params P) {
-  __shared__ __align__(16) double s_wtab[ZMX_WTAB];
-  // per wave: the staged codes of a window (4 KB + the alignment slack), or the cells of a long-run shortcut
-  __shared__ __align__(16) unsigned char s_buf[D5_WG][D5_STAGE_BYTES];
-  __shared__ __align__(8) uint2 s_itab[ZMX_WTAB];
-  __shared__ __align__(8) double s_w1[D5_W1];
-  __shared__ u8 s_sym1[D5_W1];
-  __shared__ __align__(8) uint2 s_ri[D5_WG][32];
-  __shared__ __align__(8) uint2 s_rk[RUNS ? D5_WG : 1u][RUNS ? D5_RKN : 1u];
-  __shared__ u32 s_rmax;
-  // PROF: when the waves of the workgroup finished (sum, latest, how many)
-  __shared__ unsigned long long s_pf_sum, s_pf_max;
-  __shared__ u32 s_pf_done;
-  const u64 t_wg0 = PROF ? (u64)__builtin_readcyclecounter() : 0ull;
-  const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  // (the redo pass of a table set with run tasks: k_dpscan's entries of one task each, a workgroup per entry)
-  if (P.redo_pass && blockIdx.x >= *P.redo_count) return;
-  const uint2 wd = P.redo_pass ? make_uint2(0u, 1u) : P.wg_desc[P.task0 + blockIdx.x];
-  const u32* wg = P.redo_pass ? P.redo_wg + (u64)blockIdx.x * D5_WG : P.wg_tasks + wd.x;
-  const u32 t0 = wg[0];
-  const u32 b0 = P.tasks[t0].block;
-  for (u32 i = threadIdx.x; i < ZMX_WTAB; i += 64 * D5_WG) s_wtab[i] = P.wtab[(u64)b0 * ZMX_WTAB + i];
-  if (threadIdx.x == 0) { s_rmax = 0; if (PROF) { s_pf_sum = 0; s_pf_max = 0; s_pf_done = 0; } }
-  __syncthreads();
-  d5_build_w1(s_wtab, s_w1, s_sym1);
-  // PROF, the fixed cost around the tasks (counters 54 .. 57 of the block): a wave is done — with its task, or without one.
-  // The last of the four adds, for all of them, (latest finish) - (own finish): wave cycles spent finished in a live workgroup.
-  auto prof_done = [&]() {
-    if (PROF && P.prof && (threadIdx.x & 63u) == 0) {
-      const unsigned long long te = (unsigned long long)((u64)__builtin_readcyclecounter() - t_wg0);
-      atomicAdd(&s_pf_sum, te);
-      atomicMax(&s_pf_max, te);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      if (atomicAdd(&s_pf_done, 1u) == D5_WG - 1u) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        atomicAdd(&P.prof[(u64)b0 * ZMX_PROF_N + 55], (u64)(D5_WG * s_pf_max - s_pf_sum));
-        atomicAdd(&P.prof[(u64)b0 * ZMX_PROF_N + 57], (u64)(D5_WG * s_pf_max));
-      }
-    }
-  };
-  // the level a speculative task starts from
-  auto task_level = [&](u32 tt) -> float {
-    const SegTask K = P.tasks[tt];
-    float lv = P.est_bits ? P.est_bits[K.block] * ((float)K.q / (float)(u32)(P.blocks[K.block].inend - P.blocks[K.block].instart)) : P.lvl[tt];
-    if (!P.redo_pass) lv *= P.level_scale;
-    return lv >= 16.0f ? lv : 16.0f;
-  };
-  // the binade of the workgroup's integer table (zmx_dp5.h, D5IntTab): that of its first speculative task
-  D5IntTab IT;
-  IT.on = false; IT.lo = 0; IT.span = 0;
-  {
-    const u32 tl = P.tasks[t0].pout != 0 ? t0 : wd.y > 1u ? wg[1] : SEG_NONE;
-    if (tl != SEG_NONE && P.int_path) {
-      const u32 lb = __float_as_uint(task_level(tl));
-      const int e = (int)(lb >> 23) - 127;
-      if (e >= 4 && e < 31 && ((P.tiemask[b0] >> (e & 31)) & 1u) == 0) {
-        d5_build_inttab(s_wtab, s_itab, s_rmax, e);
-        __syncthreads();
-        const u32 rm = s_rmax;
-        IT.on = true;
-        IT.lo = lb & 0x7f800000u;
-        IT.span = rm < 0x100000u ? 33u * rm : 0x40000000u;
-      }
-    }
-  }
-  if (wave >= wd.y) { prof_done(); return; }
-  const u32 t = wg[wave];
-  const SegTask T = P.tasks[t];
-  const BlockDesc bd = P.blocks[T.block];
-  const u32 B = (u32)(bd.inend - bd.instart);
-  if (B == 0) { prof_done(); return; }
-  D4Job J;
-  J.start = T.q & ~31u;       // windows lie at multiples of 32 from the block start
-  J.cell = T.q & 31u;
-  J.noshort = 0;
-  J.pout = T.pout;
-  J.pend = T.pend;
-  J.load = false;
-  J.delta = 0;
-  J.init = nullptr;
-  J.entry = &P.entry[t];
-  J.exit = &P.exit[t];
-  // (round 3: run tasks only — the long ones, tens of thousands of positions between two cut points; round 5: text tasks
-  //  too: a block has a binade boundary per doubling of its cost whatever its size, and in a SMALL call the serial re-runs
-  //  of the tasks that cross one were most of k_dp4_fix: 0.66 ms per run of a 1 MB call)
-  J.mid = T.pout != 0 && P.mid != nullptr ? &P.mid[t] : nullptr;
-  J.over_lo = T.pend <= B ? T.pend : SEG_NONE;
-  J.over = P.over + (u64)t * SEG_OVER;
-  if (T.pout == 0) {       // the head of the block
-    J.spec = false;
-    J.la_lo = 1;
-    J.level = 0.0f;
-  } else {
-    J.spec = true;
-    J.la_lo = SEG_NONE;
-    J.level = task_level(t);
-    if (P.est_bits && (threadIdx.x & 63) == 0) P.lvl[t] = J.level;
-  }
-  if (PROF && P.prof && (threadIdx.x & 63u) == 0) {      // from workgroup start to the wave's first position
-    atomicAdd(&P.prof[(u64)b0 * ZMX_PROF_N + 54], (u64)__builtin_readcyclecounter() - t_wg0);
-    atomicAdd(&P.prof[(u64)b0 * ZMX_PROF_N + 56], 1ull);
-  }
-  d5_run_job<PROF, RUNS>(P, J, T.block, bd, s_wtab, reinterpret_cast<float*>(s_buf[wave]), reinterpret_cast<u16*>(s_buf[wave] + 4u * DP_XN),
-                   reinterpret_cast<u16*>(s_buf[wave]), s_itab, IT, s_w1, s_sym1, s_ri[wave], s_rk[RUNS ? wave : 0u]);
-  prof_done();
-}
-
-// k_dp5_stretch: one workgroup = four waves = a STRETCH of tasks of ONE block and one kind: `count` consecutive entries of the block's
-// task list (P.wg_desc, P.wg_tasks), sharing the run's weight table in LDS.  The set-up — the weight table, the run-row
-// weights, the integer table, the tasks' records and levels — is done once per stretch; after it the waves go their own
-// ways: each pulls the next entry from a counter in LDS and walks it, until the stretch is empty.  Which wave walks a
-// task, and when, does not enter the task's output.  NO workgroup barrier lies behind the set-up in the main pass: a
-// wave that finds the stretch empty leaves while the others work.
-// The redo pass (P.redo_pass) runs k_dpscan's list instead: entries of up to four tasks of one block, the workgroups
-// striding over them; every wave stays for every entry there, so the barriers between two entries are met by all four.
-#define D5_STRETCH_MAX 32u   // entries of a stretch at most (ZOPFLI_AMD_SEG_STRETCH): their records are held in LDS
-template <bool PROF, int WAVES, bool RUNS>
-__global__ __launch_bounds__(64 * D5_WG, WAVES) void k_dp5_stretch(Dp4Params P) {
-  __shared__ __align__(16) double s_wtab[ZMX_WTAB];
-  // per wave: the staged codes of a window (4 KB + the alignment slack), or the cells of a long-run shortcut
-  __shared__ __align__(16) unsigned char s_buf[D5_WG][D5_STAGE_BYTES];
-  __shared__ __align__(8) uint2 s_itab[ZMX_WTAB];
-  __shared__ __align__(8) double s_w1[D5_W1];
-  __shared__ u8 s_sym1[D5_W1];
-  __shared__ __align__(8) uint2 s_ri[D5_WG][32];
-  __shared__ __align__(8) uint2 s_rk[RUNS ? D5_WG : 1u][RUNS ? D5_RKN : 1u];
-  __shared__ u32 s_rmax;
-  // the stretch: its next entry, and per entry the task's id, record and starting level
-  __shared__ u32 s_next;
-  __shared__ u32 s_hdr[4];         // the stretch's block, entries (0 for an empty block), integer table: built, binade
-  __shared__ u32 s_tid[D5_STRETCH_MAX];
-  __shared__ __align__(16) SegTask s_task[D5_STRETCH_MAX];
-  __shared__ float s_lvl[D5_STRETCH_MAX];
-  // PROF: when the waves of the workgroup finished (sum, latest, how many)
-  __shared__ unsigned long long s_pf_sum, s_pf_max;
-  __shared__ u32 s_pf_done;
-  const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const u32 lane = threadIdx.x & 63u;
-  u32 item = P.redo_pass ? blockIdx.x : P.task0 + blockIdx.x;
-  const u32 n_items = P.redo_pass ? *P.redo_count : item + 1u;
-  for (; item < n_items; item += gridDim.x) {
-    const u64 t_wg0 = PROF ? (u64)__builtin_readcyclecounter() : 0ull;     // (PROF counts per entry: each has its set-up)
-    const u32* list;
-    u32 count = 0;
-    if (P.redo_pass) {
-      list = P.redo_wg + (u64)item * D5_WG;
-      while (count < D5_WG && list[count] != SEG_NONE) ++count;
-    } else {
-      const uint2 d = P.wg_desc[item];
-      list = P.wg_tasks + d.x;
-      count = d.y < D5_STRETCH_MAX ? d.y : D5_STRETCH_MAX;
-    }
-    if (count == 0) continue;          // (every thread alike; no list holds such an entry)
-    const u32 b0 = P.tasks[list[0]].block;
-    const BlockDesc bd = P.blocks[b0];
-    const u32 B = (u32)(bd.inend - bd.instart);
-    for (u32 i = threadIdx.x; i < ZMX_WTAB; i += 64 * D5_WG) s_wtab[i] = P.wtab[(u64)b0 * ZMX_WTAB + i];
-    // the entries' records, and the level a speculative task starts from
-    for (u32 i = threadIdx.x; i < count; i += 64 * D5_WG) {
-      const u32 tt = list[i];
-      const SegTask K = P.tasks[tt];
-      float lv = 0.0f;
-      if (K.pout != 0) {
-        lv = P.est_bits ? P.est_bits[b0] * ((float)K.q / (float)B) : P.lvl[tt];
-        if (!P.redo_pass) lv *= P.level_scale;
-        lv = lv >= 16.0f ? lv : 16.0f;
-        if (P.est_bits) P.lvl[tt] = lv;
-      }
-      s_tid[i] = tt;
-      s_task[i] = K;
-      s_lvl[i] = lv;
-    }
-    if (threadIdx.x == 0) { s_rmax = 0; s_next = 0; if (PROF) { s_pf_sum = 0; s_pf_max = 0; s_pf_done = 0; } }
-    __syncthreads();
-    d5_build_w1(s_wtab, s_w1, s_sym1);
-    // the binade of the workgroup's integer table (zmx_dp5.h, D5IntTab): that of the stretch's first speculative task;
-    // a task of the stretch in another binade walks in doubles
-    {
-      const u32 il = s_task[0].pout != 0 ? 0u : 1u;
-      bool on = false;
-      u32 lb = 0;
-      if (il < count && P.int_path) {
-        lb = __float_as_uint(s_lvl[il]);
-        const int e = (int)(lb >> 23) - 127;
-        if (e >= 4 && e < 31 && ((P.tiemask[b0] >> (e & 31)) & 1u) == 0) {
-          d5_build_inttab(s_wtab, s_itab, s_rmax, e);
-          on = true;
-        }
-      }
-      // what the waves need per task goes through LDS: held in registers across the tasks it cost the window loop its own
-      if (threadIdx.x == 0) { s_hdr[0] = b0; s_hdr[1] = B != 0 ? count : 0u; s_hdr[2] = on ? 1u : 0u; s_hdr[3] = lb & 0x7f800000u; }
-      __syncthreads();
-    }
-    bool first_job = true;
-    for (;;) {
-      u32 i = 0;
-      if (lane == 0) i = atomicAdd(&s_next, 1u);
-      i = (u32)__builtin_amdgcn_readfirstlane((int)i);
-      if (i >= (u32)__builtin_amdgcn_readfirstlane((int)s_hdr[1])) break;
-      // The parameters a task needs only on its way into the window loop are read again from the kernel's argument
-      // segment, task by task (scalar loads that hit the constant cache).  Read once at the kernel's start they would
-      // have to stay in scalar registers across the loop over the tasks, and the window loop paid for them in spills.
-      typedef const __attribute__((address_space(4))) unsigned char* kargp;
-      kargp kq = (kargp)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(kq));
-      Dp4Params Pj = P;                 // (a member that is not listed below stays the kernel's own copy: right, only dearer)
-#define D5_KARG(F) Pj.F = *reinterpret_cast<const __attribute__((address_space(4))) decltype(Dp4Params::F)*>(kq + offsetof(Dp4Params, F));
-      D5_KARG(blocks) D5_KARG(dph) D5_KARG(cost) D5_KARG(mincost) D5_KARG(codes) D5_KARG(code_base) D5_KARG(la) D5_KARG(prof)
-      D5_KARG(badpos) D5_KARG(entry) D5_KARG(exit) D5_KARG(mid) D5_KARG(wmax) D5_KARG(tiemask) D5_KARG(wmeta) D5_KARG(winroff)
-      D5_KARG(winflag) D5_KARG(win_off) D5_KARG(over) D5_KARG(int_path) D5_KARG(chain_fast) D5_KARG(debug) D5_KARG(flags)
-#undef D5_KARG
-      const Dp4Params& P = Pj;
-      const u32 b0 = (u32)__builtin_amdgcn_readfirstlane((int)s_hdr[0]);
-      const BlockDesc bd = P.blocks[b0];
-      const u32 B = (u32)(bd.inend - bd.instart);
-      D5IntTab IT;
-      IT.on = __builtin_amdgcn_readfirstlane((int)s_hdr[2]) != 0;
-      IT.lo = (u32)__builtin_amdgcn_readfirstlane((int)s_hdr[3]);
-      {
-        const u32 rm = (u32)__builtin_amdgcn_readfirstlane((int)s_rmax);
-        IT.span = !IT.on ? 0u : rm < 0x100000u ? 33u * rm : 0x40000000u;
-      }
-      const u32 t = (u32)__builtin_amdgcn_readfirstlane((int)s_tid[i]);
-      SegTask T;
-      T.block = b0;
-      T.q = (u32)__builtin_amdgcn_readfirstlane((int)s_task[i].q);
-      T.pout = (u32)__builtin_amdgcn_readfirstlane((int)s_task[i].pout);
-      T.pend = (u32)__builtin_amdgcn_readfirstlane((int)s_task[i].pend);
-      D4Job J;
-      J.start = T.q & ~31u;       // windows lie at multiples of 32 from the block start
-      J.cell = T.q & 31u;
-      J.noshort = 0;
-      J.pout = T.pout;
-      J.pend = T.pend;
-      J.load = false;
-      J.delta = 0;
-      J.init = nullptr;
-      J.entry = &P.entry[t];
-      J.exit = &P.exit[t];
-      // (round 3: run tasks only — the long ones, tens of thousands of positions between two cut points; round 5: text tasks
-      //  too: a block has a binade boundary per doubling of its cost whatever its size, and in a SMALL call the serial re-runs
-      //  of the tasks that cross one were most of k_dp4_fix: 0.66 ms per run of a 1 MB call)
-      J.mid = T.pout != 0 && P.mid != nullptr ? &P.mid[t] : nullptr;
-      J.over_lo = T.pend <= B ? T.pend : SEG_NONE;
-      J.over = P.over + (u64)t * SEG_OVER;
-      if (T.pout == 0) {       // the head of the block
-        J.spec = false;
-        J.la_lo = 1;
-        J.level = 0.0f;
-      } else {
-        J.spec = true;
-        J.la_lo = SEG_NONE;
-        J.level = __uint_as_float((u32)__builtin_amdgcn_readfirstlane((int)__float_as_uint(s_lvl[i])));
-      }
-      if (PROF && P.prof && first_job && lane == 0) {
-        atomicAdd(&P.prof[(u64)b0 * ZMX_PROF_N + 54], (u64)__builtin_readcyclecounter() - t_wg0);
-        atomicAdd(&P.prof[(u64)b0 * ZMX_PROF_N + 56], 1ull);
-      }
-      first_job = false;
-      d5_run_job<PROF, RUNS>(P, J, b0, bd, s_wtab, reinterpret_cast<float*>(s_buf[wave]), reinterpret_cast<u16*>(s_buf[wave] + 4u * DP_XN),
-                       reinterpret_cast<u16*>(s_buf[wave]), s_itab, IT, s_w1, s_sym1, s_ri[wave], s_rk[RUNS ? wave : 0u]);
-      // the wave's staging area, s_ri and s_rk are the next job's: nothing of this one — LDS-DMA, stores, LDS reads — is
-      // still on its way
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    }
-    if (PROF && P.prof && lane == 0) {
-      // cycles this wave is finished while the workgroup is alive: the last wave to finish adds, for all four,
-      // (latest finish) - (own finish)
-      const unsigned long long te = (unsigned long long)((u64)__builtin_readcyclecounter() - t_wg0);
-      atomicAdd(&s_pf_sum, te);
-      atomicMax(&s_pf_max, te);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      if (atomicAdd(&s_pf_done, 1u) == D5_WG - 1u) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        atomicAdd(&P.prof[(u64)b0 * ZMX_PROF_N + 55], (u64)(D5_WG * s_pf_max - s_pf_sum));
-        atomicAdd(&P.prof[(u64)b0 * ZMX_PROF_N + 57], (u64)(D5_WG * s_pf_max));
-      }
-    }
-    if (!P.redo_pass) return;
-    __syncthreads();     // the tables in LDS are the next entry's
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// FIX: one workgroup per block walks the block's tasks in order, accepts every task whose entry
-// state is the true state up to a shift that keeps the task inside its binade, and runs the others
-// again from the true state — the serial chain, for exactly the stretches that need it.  A re-run uses
-// k_dp4's four-wave pipeline (d4_run_job: 57 cycles per position on text, but a ring restart and two
-// bubble steps per long-run shortcut and 14 positions per step where rows are 258 wide), or, for a
-// task with at least P.fix_lean_min windows of the generic kind (shortcut flags, long rows), the lean
-// one-wave job of k_dp5_spec (d5_run_job in load mode: a shortcut is a handful of LDS operations).
-// ---------------------------------------------------------------------------------------------
-#define FIX_CH 256u       // tasks whose summaries k_dp4_fix holds in LDS at a time
-template <bool PROF>
-__global__ __launch_bounds__(64 * (D3_NB + 2)) void k_dp4_fix(Dp4Params P) {
-  D4_LDS_DECL
-  const u32 b = P.block0 + blockIdx.x;
-  const BlockDesc bd = P.blocks[b];
-  const u32 B = (u32)(bd.inend - bd.instart);
-  if (B == 0) return;
-  const u32 t0 = P.task_off[b], t1 = P.task_off[b + 1];
-  const u32 lane = threadIdx.x & 63;
-  const bool lead = threadIdx.x == 0;
-  const double wmax = (double)P.wmax[b] + 1.0;
-  const u32 tiemask = P.tiemask[b];
-  for (u32 i = threadIdx.x; i < ZMX_WTAB; i += blockDim.x) s_wtab[i] = P.wtab[(u64)b * ZMX_WTAB + i];
-  __syncthreads();
-  __shared__ __align__(8) double s_w1[D5_W1];
-  __shared__ u8 s_sym1[D5_W1];
-  __shared__ __align__(8) uint2 s_ri[32];
-  d5_build_w1(s_wtab, s_w1, s_sym1);
-  u16* la_block = P.la + bd.la_off;
-  d4_copy_over(P, t0, B, la_block);   // the head is exact
-  double delta_prev = 0.0;     // what has to be added to exit[t - 1] to get the true values
-  bool rerun_prev = false;     // exit[t - 1] was rewritten by this workgroup: P.chk[t] is stale
-  u32 n_ok = 0, n_state = 0, n_level = 0, n_tie = 0, n_pos = 0, n_values = 0, n_lean = 0, n_mid = 0;
-  const u32* winflag = P.winflag + P.win_off[b];
-  const u64 cyc0 = __builtin_readcyclecounter();
-  u64 cyc_run = 0;
-  // The walk reads a few words per task and almost always just accepts it: with a dependent global load or two
-  // per task, 240 tasks a block, the walk — not the re-runs — was most of this kernel's 0.75 ms.  So: the tasks'
-  // summaries come into LDS FIX_CH at a time in one sweep, and what an accepted task leaves to do (its overshoot
-  // cells into length_array, its level for the next run) is done for the whole chunk afterwards, all threads at once.
-  __shared__ double s_ck_d[FIX_CH], s_dl[FIX_CH];
-  __shared__ float s_ck_vmin[FIX_CH], s_vmax[FIX_CH];
-  __shared__ u32 s_ck_match[FIX_CH], s_xbase[FIX_CH], s_pend[FIX_CH], s_acc[FIX_CH];
-  __shared__ double s_wsum[4], s_dprev;
-  __shared__ u32 s_wfail[4];
-  static_assert(FIX_CH == 64 * (D3_NB + 2), "the sweep judges a chunk's tasks a thread each");
-  for (u32 c0 = t0 + 1; c0 < t1; c0 += FIX_CH) {
-  const u32 cn = t1 - c0 < FIX_CH ? t1 - c0 : FIX_CH;
-  for (u32 i = threadIdx.x; i < cn; i += blockDim.x) {
-    const SegCheck k = P.chk[c0 + i];
-    s_ck_d[i] = k.d; s_ck_vmin[i] = k.vmin; s_ck_match[i] = k.match;
-    s_vmax[i] = P.exit[c0 + i].vmax;
-    s_xbase[i] = P.exit[c0 + i].base + P.exit[c0 + i].skip;   // (where the task's own cells end: d4_copy_over)
-    s_pend[i] = P.tasks[c0 + i].pend;
-    s_acc[i] = 0;
-    s_dl[i] = 0.0;
-  }
-  __syncthreads();
-  for (u32 t = c0; t < c0 + cn; ++t) {
-    // The walk, a SWEEP at a time (round 5): nearly every task is simply accepted, and deciding so one task after the
-    // other — four waves doing the same dozen double-precision operations — was 1 200 cycles a task, 0.25 ms of this
-    // kernel's 0.43 per 1 MB block.  All tasks of the chunk from t on are judged at once, a thread each: their shifts are a
-    // prefix sum of the checks' differences (sums of multiples of float ulps: exact in any order, as in k_dpscan), the
-    // acceptance test is the one below with that shift; everything up to the first task that fails is accepted, and
-    // that task takes the serial step — which re-runs it — as before.  (Not behind a re-run: the next task's check is stale.)
-    if (!rerun_prev) {
-      const u32 ti0 = t - c0;
-      const u32 i = threadIdx.x;                       // (FIX_CH = the workgroup's threads: a thread per task of the chunk)
-      const bool act = i >= ti0 && i < cn;
-      double incl = act ? s_ck_d[i] : 0.0;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const double up = __shfl_up(incl, o, 64);
-        if ((int)lane >= o) incl += up;
-      }
-      if (lane == 63) s_wsum[threadIdx.x >> 6] = incl;
-      __syncthreads();
-      double before = 0.0;
-      for (u32 w = 0; w < (threadIdx.x >> 6); ++w) before += s_wsum[w];
-      const double delta_i = delta_prev + before + incl;
-      const bool ok_i = act && s_ck_match[i] == 1 && d4_accept(s_ck_vmin[i], (double)s_vmax[i], delta_i, wmax, tiemask) == 0;
-      const u64 failm = __ballot(act && !ok_i);
-      if (lane == 0) s_wfail[threadIdx.x >> 6] = failm ? (threadIdx.x & ~63u) + (u32)__ffsll((long long)failm) - 1u : 0xffffffffu;
-      __syncthreads();
-      u32 first_fail = cn;
-      for (u32 w = 0; w < (blockDim.x >> 6); ++w) first_fail = s_wfail[w] < first_fail ? s_wfail[w] : first_fail;
-      if (act && i < first_fail) { s_acc[i] = 1; s_dl[i] = delta_i; }
-      if (first_fail > ti0 && i == first_fail - 1u) s_dprev = delta_i;
-      __syncthreads();
-      if (first_fail > ti0) { delta_prev = s_dprev; n_ok += first_fail - ti0; }
-      t = c0 + first_fail;
-      if (t >= c0 + cn) break;
-    }
-    const u32 ti = t - c0;
-    SegCheck ck;
-    if (rerun_prev) ck = d4_check(&P.exit[t - 1], &P.entry[t], lane);   // every wave computes the same
-    else { ck.d = s_ck_d[ti]; ck.vmin = s_ck_vmin[ti]; ck.match = s_ck_match[ti]; }
-    const double delta = delta_prev + ck.d;
-    // the guess to start the next run of this task from
-    if (lead) s_dl[ti] = delta;
-    bool ok = ck.match == 1;
-    u32 why = 0;
-    if (ok) {
-      why = d4_accept(ck.vmin, (double)s_vmax[ti], delta, wmax, tiemask);
-      ok = why == 0;
-    }
-    if (P.debug == 6 && ck.match == 0 && threadIdx.x < 64) {
-      // where the two states differ: the first cell whose reach, source or value shape is not the same
-      const SegSnap* E = &P.exit[t - 1];
-      const SegSnap* N = &P.entry[t];
-      u32 first = 0xffffffffu;
-      for (int s6 = 0; s6 < 6; ++s6) {
-        const u32 i = 64u * s6 + lane;
-        const bool ef = E->c[i] < 1e29f, nf = N->c[i] < 1e29f;
-        if ((ef != nf || E->l[i] != N->l[i]) && i < first) first = i;
-      }
-      for (int o = 32; o >= 1; o >>= 1) { const u32 v = __shfl_xor(first, o, 64); first = v < first ? v : first; }
-      if (lane == 0) {
-        const u32 i = first < SEG_CELLS ? first : 0;
-        printf("diff b %u t %u pout %u base %u/%u noshort %u/%u skip %u/%u first cell %u: exit c %.4f l %u | entry c %.4f l %u | q %u\n", b, t - t0, P.tasks[t].pout,
-               E->base, N->base, E->noshort, N->noshort, E->skip, N->skip, first, (double)E->c[i], E->l[i], (double)N->c[i], N->l[i], P.tasks[t].q);
-      }
-    }
-    if (P.debug == 1 && lead) {
-      printf("fix b %u t %u pout %u: match %u d %.6f delta %.6f vmin %.4f vmax %.4f why %u ok %d entry base %u exit-1 base %u\n", b,
-             t - t0, P.tasks[t].pout, ck.match, ck.d, delta, (double)ck.vmin, (double)P.exit[t].vmax, why, ok ? 1 : 0,
-             P.entry[t].base, P.exit[t - 1].base);
-    }
-    if (ok) {
-      if (lead) s_acc[ti] = 1;
-      delta_prev = delta;
-      rerun_prev = false;
-      ++n_ok;
-      continue;
-    }
-    if (ck.match == 0) ++n_state; else if (ck.match == 2) ++n_values; else if (why == 1) ++n_level; else ++n_tie;
-    const SegTask T = P.tasks[t];
-    D4Job J;
-    J.start = P.exit[t - 1].base;
-    J.noshort = P.exit[t - 1].noshort;
-    J.pout = 0;
-    J.pend = T.pend;
-    J.over_lo = SEG_NONE;    // (this workgroup is the only writer of the block's length_array now)
-    J.spec = false;
-    J.load = true;
-    J.level = 0.0f;
-    J.delta = delta_prev;
-    J.init = &P.exit[t - 1];
-    J.entry = nullptr;
-    J.exit = &P.exit[t];
-    J.over = nullptr;
-    // The task matched its predecessor and only grew out of its binade: if what it did up to its mid snapshot passes the
-    // test (the same test, with the largest source value of that prefix), the prefix stands — its lengths are in
-    // length_array already — and the re-run starts at the snapshot, from the task's own cells plus the shift.
-    bool from_mid = false;
-    if (ck.match == 1 && why == 1 && P.mid != nullptr) {
-      const u32 mb_ = P.mid[t].base;
-      if (mb_ != SEG_NONE && mb_ > P.entry[t].base && mb_ < (T.pend < B ? T.pend : B) &&
-          d4_accept(ck.vmin, (double)P.mid[t].vmax, delta, wmax, tiemask) == 0) {
-        from_mid = true;
-        J.start = mb_;
-        J.noshort = P.mid[t].noshort;
-        J.delta = delta;
-        J.init = &P.mid[t];
-        ++n_mid;
-      }
-    }
-    J.la_lo = J.start;
-    n_pos += (T.pend < B ? T.pend : B) - (J.start < B ? J.start : B);
-    // windows of the task that k_dp5_spec's fast paths cannot take (k_mkdesc)
-    const u32 w0 = J.start >> 5, w1 = ((T.pend < B ? T.pend : B) + 31u) >> 5;
-    u32 generic = 0, mine = 0, nocodes = 0;
-    for (u32 w = w0 + threadIdx.x; w < w1; w += blockDim.x) {
-      generic += (winflag[w] & 0xffu) == 0 ? 1u : 0u;
-      nocodes |= winflag[w] & D5_WF_CODELESS;
-      ++mine;
-    }
-    // (the barriers also mean: every wave has read the old exit[t] / exit[t - 1])
-    // (automatic, P.fix_lean_min < 0: the lean job where most of the windows are of the generic kind — runs of equal
-    //  bytes: its run-row path reads no codes, the pipeline's ring would restart at every shortcut.  Counted per
-    //  thread: a merged task has thousands of windows)
-    const int n_generic = __syncthreads_count((int)generic);
-    const int n_major = __syncthreads_count(mine > 0 && 2 * generic >= mine ? 1 : 0);
-    const int n_have = __syncthreads_count(mine > 0 ? 1 : 0);
-    const int n_nocodes = __syncthreads_count(nocodes != 0 ? 1 : 0);   // (a wide run row without codes: only the lean job's tables know its weights)
-    // (a predecessor that stopped inside a shortcut's window — skip — can only be continued by the job that knows
-    //  about it)
-    const bool lean = (!from_mid && P.exit[t - 1].skip != 0) || n_nocodes > 0 || (P.fix_lean_min >= 0 ? n_generic >= P.fix_lean_min : 2 * n_major >= n_have);
-    const u64 cr0 = __builtin_readcyclecounter();
-    if (lean) {
-      ++n_lean;
-      D5IntTab IT;
-      IT.on = false; IT.lo = 0; IT.span = 0;
-      if (threadIdx.x < 64) {
-        d5_run_job<PROF, true>(P, J, b, bd, s_wtab, s_xc, s_xl, s_ring, *reinterpret_cast<const uint2 (*)[ZMX_WTAB]>(&s_t1[0][0]), IT, s_w1, s_sym1, s_ri,
-                               reinterpret_cast<uint2*>(&s_t2[0][0]));   // (s_rk: the pipeline's tiles are idle in this job)
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      __syncthreads();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    } else {
-      d4_run_job<PROF>(P, J, b, bd, s_ring, s_wtab, s_t1, s_t2, s_tab, s_desc, s_tabc, s_xc, s_xl, s_lout);
-    }
-    cyc_run += __builtin_readcyclecounter() - cr0;
-    delta_prev = 0.0;
-    rerun_prev = true;
-  }
-  __syncthreads();
-  // the chunk's accepted tasks: their cells beyond pend (d4_copy_over), one task per wave at a time; and every
-  // task's level for the next run
-  // (sixteen lanes a task, sixteen tasks at a time: a task's copy is one or two dependent global round trips of a few dozen
-  //  cells, and with a wave per task — four in flight — those round trips were a third of this kernel on text)
-  for (u32 i = threadIdx.x >> 4; i < cn; i += blockDim.x >> 4) {
-    if (!s_acc[i]) continue;
-    const u32 pend = s_pend[i], stop = s_xbase[i];
-    if (pend > B) continue;                   // the last task of the block runs to the end
-    const u16* over = P.over + (u64)(c0 + i) * SEG_OVER;
-    for (u32 k = threadIdx.x & 15u; pend + k < stop && pend + k <= B; k += 16) la_block[pend + k] = over[k];
-  }
-  for (u32 i = threadIdx.x; i < cn; i += blockDim.x) P.lvl[c0 + i] = (float)((double)P.lvl[c0 + i] + s_dl[i]);
-  __syncthreads();
-  }
-  if (P.debug >= 2 && lead) {
-    printf("fix b %u: %u tasks ok %u state %u values %u level %u (%u of them from their mid snapshot) tie %u lean %u, %u positions re-run, %llu cycles in all, %llu in re-runs\n", b,
-           t1 - t0, n_ok, n_state, n_values, n_level, n_mid, n_tie, n_lean, n_pos, (unsigned long long)(__builtin_readcyclecounter() - cyc0),
-           (unsigned long long)cyc_run);
-  }
-  if (lead && P.stats) {
-    atomicAdd(&P.stats[0], t1 - t0);
-    atomicAdd(&P.stats[1], n_ok);
-    atomicAdd(&P.stats[2], n_state);
-    atomicAdd(&P.stats[3], n_level);
-    atomicAdd(&P.stats[4], n_tie);
-    atomicAdd(&P.stats[5], n_pos);
-    atomicAdd(&P.stats[6], n_values);
-    atomicAdd(&P.stats[7], n_lean);
+    atomicMax(&o[PF_D5_LONGEST], dt);                   // the longest task of the block
+    if (J.la_lo == 1) atomicAdd(&o[PF_D5_HEAD], dt);    // the head task
   }
 }

@@ -16,12 +16,17 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../host/zmx_internal.h"   // the seam to the host layer; its statistics slots are k_wtab's and k_dp4_fix's too
+
 // ---- the kernels (the order is the order of the code object)
 #include "zmx_kernels.h"     // types, BlockDesc, hash links, rows, codes, record copies, verify
 #include "zmx_match2.h"      // k_match2: the match table, a lane per position
 #include "zmx_match5.h"      // k_match5: the exact skip-walk for long chains
-#include "zmx_dp4.h"         // the chain's tasks: check, scan, the serial fix
-#include "zmx_dp5.h"         // k_dp5_spec: the speculative tasks; k_cutpoints
+#include "zmx_dp4.h"         // the chain's tasks: snapshots, the four-wave job, k_dpcheck, k_dprecheck, k_dpscan
+#include "zmx_dp_build.h"    // once per table set: k_mkdesc (window records), k_cutpoints, k_taskkind
+#include "zmx_dp5.h"         // d5_run_job: a task walked by one wave, the integer chain step
+#include "zmx_dp5_spec.h"    // k_dp5_spec, k_dp5_stretch: the speculative pass, and the set-up the two share
+#include "zmx_dp4_fix.h"     // k_dp4_fix: the serial pass, which runs the jobs of zmx_dp4.h and zmx_dp5.h
 #include "zmx_encode.h"      // the bit writer
 #include "zmx_checksum.h"    // CRC-32 / Adler-32 pieces
 #include "zmx_trace.h"       // the walk back over length_array, in segments
@@ -46,7 +51,6 @@
 #include "../host/png_color_choose.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
-#include "../host/zmx_internal.h"
 
 // ---- the driver
 #include "drv_errors.h"      // the thread's error state, HIPCHK, KCHK, DeviceGuard and DEVICE_ENTRY

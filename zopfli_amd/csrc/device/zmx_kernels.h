@@ -619,7 +619,7 @@ __global__ __launch_bounds__(256) void k_wtab(WtabParams P) {
   __shared__ u32 s_bad[40];
   const u32 b = blockIdx.x, tid = threadIdx.x;
   if (tid < 40) s_bad[tid] = 0;
-  if (b == 0 && tid < 8 && P.stats) P.stats[tid] = 0;
+  if (b == 0 && tid < ZMX_SEG_N && P.stats) P.stats[tid] = 0;
   __syncthreads();
   const double* ll = P.cost + (u64)b * 320;
   const double* d = ll + 288;
@@ -692,6 +692,34 @@ __global__ __launch_bounds__(256) void k_badscan(BadScanParams P) {
 
 // ------------------------------------------- shared by the chain kernels (zmx_dp4.h)
 #define ZMX_PROF_N 60u                // u64 profiling counters per block (ZOPFLI_AMD_PROF)
+// The counters by slot, as ReportSqueezeProf (drv_squeeze.h) reads them; a name with a range is the range's first slot.
+// The pipeline (d4_run_job) and the one-wave job (d5_run_job) share the slots 5 .. 14 and 24 .. 27, each its own way.
+enum ZmxProf : u32 {
+  PF_STEPS = 0,            // d4_run_job: steps of the pipeline
+  PF_TASK_CYC = 1,         // wave cycles inside jobs (d4_run_job: the consumer wave's; d5_run_job: start to end)
+  PF_FAST = 2, PF_SLOW = 3, PF_POS = 4,   // positions on a fast path, on the generic path, and walked (their sum)
+  PF_D4_PATH = 5,          // 5 .. 14, d4_run_job: {cycles, positions} of its paths 32, 16, 8, 8 (two registers), generic
+  PF_D5_CYC = 5, PF_D5_FAST = 6,         // d5_run_job into the same slots: its cycles and fast positions (the report's "32" line),
+  PF_D5_LONGEST = 7, PF_D5_HEAD = 8,     // the longest task of the block (a maximum: the report takes the largest), the head task's cycles,
+  PF_D5_INT_POS = 10,      // positions walked by the integer step,
+  PF_D5_INT_CYC = 11,      // 11 .. 13, cycles of the integer windows: issuing the row fetches, waiting for them, gather + chain,
+  PF_D5_SLOW = 14,         // and its generic positions (the "generic" line)
+  PF_D4_WAVE1 = 16,        // 16 .. 19, d4_run_job's producer wave 1, cycles: walk, ring, tiles, barrier
+  PF_D5_INTWIN = 20,       // 20 .. 22, integer windows, cycles: class decision, wait for the prefetched record and codes, prefetch issue
+  PF_D4_WAVE2 = 24,        // 24 .. 27, producer wave 2, as PF_D4_WAVE1
+  PF_D5_CLASS_CYC = 24,    // 24 .. 27, d5_run_job: cycles by window class: integer, class 1 in doubles, class 2, generic
+  PF_D5_CLASS_POS = 28,    // 28 .. 31: positions by window class
+  PF_D5_GEN = 32,          // 32 .. 41, generic windows, {cycles, count} of: shortcuts, run rows integer, run rows doubles, other rows, window headers
+  PF_D5_GEN_POS = 42,      // 42 .. 47, positions: run interior in unrolled windows, in loops with room, with checks; the general step's run rows, other rows; class-2 rows that reach register 2
+  PF_D5_GEN_CYC = 48,      // 48 .. 51, cycles of generic windows: headers, run stretches in whole windows, in loops, the loop over a window's positions
+  PF_D5_OTHER_CYC = 52, PF_D5_OTHER_POS = 53,   // stretches of other rows: cycles and positions
+  PF_SETUP_CYC = 54,       // k_dp5_spec, k_dp5_stretch: wave cycles from workgroup (or entry) start to a wave's first position
+  PF_IDLE_CYC = 55,        // wave cycles spent finished in a workgroup that is still alive
+  PF_SETUP_WAVES = 56,     // the waves PF_SETUP_CYC counts: those with a task
+  PF_ALIVE_CYC = 57,       // wave cycles the workgroups were alive for
+  PF_REDO_TASKS = 58, PF_REDO_ENTRIES = 59,   // k_dpscan: tasks listed for the redo pass, and the entries they make
+};
+static_assert(PF_REDO_ENTRIES + 1u == ZMX_PROF_N, "the last named counter is the last slot");
 #define DP_RING 16384u                // weight codes in the LDS ring (32 KB)
 #define DP_PIECE 512u                 // codes per LDS-DMA instruction (64 lanes x 16 B)
 #define DP_XN 704u                    // long-run shortcut staging: 384 cells

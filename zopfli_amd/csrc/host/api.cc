@@ -85,7 +85,7 @@ void AddStats(const zmx_stats& s) {
   t.squeeze_launches += s.squeeze_launches;
   for (int i = 0; i < 3; ++i) t.match5[i] += s.match5[i];
   for (int i = 0; i < 4; ++i) t.match[i] += s.match[i];
-  for (int i = 0; i < 8; ++i) t.seg[i] += s.seg[i];
+  for (int i = 0; i < ZMX_SEG_N; ++i) t.seg[i] += s.seg[i];
 }
 
 using zamd::Die;
@@ -819,7 +819,7 @@ int zmx_last_match_walk(double* out3) {
 
 int zmx_last_seg_stats(double* out8) {
   const zmx_stats& s = zamd::ThreadStats();
-  for (int i = 0; i < 8; ++i) out8[i] = s.seg[i];
+  for (int i = 0; i < ZMX_SEG_N; ++i) out8[i] = s.seg[i];   // (ZMX_SEG_N = the 8 of the public header)
   return 0;
 }
 

@@ -14,6 +14,26 @@
 
 #define ZMX_INTERNAL_EXPORT __attribute__((visibility("default")))
 
+// How the chain's tasks of a run fared, by slot: what k_dp4_fix adds up on the device (RunLayout::kStats words of the
+// run's output), what zmx_stats::seg sums per thread and what zmx_last_seg_stats hands out, in the order of the keys of
+// zopfli_amd/api.py (SEG_STAT_KEYS; tests/test_cpu_abi.py holds the two against each other).
+// The last slot is two things.  On the DEVICE it is ZMX_SEG_DEV_LEAN, the serial re-runs the lean one-wave job took:
+// ReportSqueezeProf reads that, from the run's own words.  On the HOST it is ZMX_SEG_POSITIONS, the positions of the
+// run's blocks, which zmx_squeeze_run puts there in the device's count's place: AddStats, zmx_last_seg_stats and
+// api.py read that.
+enum zmx_seg_stat {
+  ZMX_SEG_TASKS,            // tasks of the run's blocks, heads included
+  ZMX_SEG_ACCEPTED,         // accepted as the speculative pass left them
+  ZMX_SEG_RERUN_STATE,      // run again serially: the entry state was not the predecessor's exit state
+  ZMX_SEG_RERUN_LEVEL,      // ... the shift takes the task out of its binade
+  ZMX_SEG_RERUN_TIE,        // ... a weight can tie in the task's binade
+  ZMX_SEG_POSITIONS_RERUN,  // positions of the tasks run again
+  ZMX_SEG_RERUN_VALUES,     // run again: same structure, other values
+  ZMX_SEG_POSITIONS,        // (host) positions in the blocks
+  ZMX_SEG_N,
+  ZMX_SEG_DEV_LEAN = ZMX_SEG_POSITIONS   // (device) re-runs by the lean one-wave job
+};
+
 // Kernel, match and task statistics, summed per calling THREAD since the start of its call.  Only the host layer
 // reads, takes and adds them (api.cc: zmx_last_*, and a call's shard threads hand theirs to the caller's at the join),
 // so it owns them, as it owns zamd::ThreadTiming; the device layer adds to them where it times its kernels.
@@ -22,7 +42,7 @@ struct zmx_stats {
   double squeeze_launches;
   double match5[3];          // k_match5: entries in flight summed over lanes and iterations, wave iterations, positions it walked
   double match[4];           // match kernel seconds, k_same + k_chain (+ k_levels ...) seconds, table builds, positions matched
-  double seg[8];             // tasks, accepted, re-run: state / level / tie, positions re-run, re-run: values, positions
+  double seg[ZMX_SEG_N];     // by zmx_seg_stat, the host's reading of the last slot
 };
 namespace zamd {
 zmx_stats& ThreadStats();   // the calling thread's (thread-local: no lock)
