@@ -545,6 +545,21 @@ int zmx_length_array_download(zmx_ctx* ctx, zmx_tables* tables, size_t block, ui
 int zmx_dp_rows_download(zmx_ctx* ctx, zmx_tables* tables, size_t block, uint64_t* block_edges, uint32_t* dph,
                          uint16_t* codes, uint32_t* winflag, uint32_t* winroff, uint32_t* wmeta);
 
+/* Parity probe: how the table build cut the DP chain of the whole table set into tasks and packed them for the
+ * speculative pass (tables with DP rows, untrimmed), read from the device copies the kernels see.  counts4 is always
+ * set: tasks after the merge, tasks merged into their predecessors, workgroups of text tasks, workgroups of run tasks.
+ * Every array may be null (not copied), so a first call with all of them null asks for the sizes:
+ *   tasks     4 words per task: block, q (first position walked: a cut point of the DP, or pout - warm-up), pout,
+ *             pend (blocksize + 1 for a block's last task); the tasks of a block are consecutive and tile it
+ *   task_off  nblocks + 1 words: the first task of every block
+ *   wg_tasks  one word per task: the text tasks' list (per block the task indices in order), then the run tasks'.
+ *             A task's kind is stored nowhere else: it is the list that holds it
+ *   wg_desc   2 words per workgroup (counts4[2] + counts4[3] of them): first entry in wg_tasks, entries; at most
+ *             ZOPFLI_AMD_SEG_STRETCH entries of one block and one list, the text workgroups first and among those of
+ *             a kind the ones that hold a block's first task first */
+int zmx_chain_tasks_download(zmx_ctx* ctx, zmx_tables* tables, uint64_t* counts4, uint32_t* tasks, uint32_t* task_off,
+                             uint32_t* wg_tasks, uint32_t* wg_desc);
+
 /* Test entry: TraceBackwards + FollowPath (squeeze.c:317, :338) over length arrays the CALLER hands in — the tail of
  * zmx_squeeze_run (k_trace_exits, k_trace_link, k_trace_emit and the result copy: the same code) without the DP in
  * front of it.  length_arrays[b] has entries[b] = blocksize + 1 cells, as zmx_length_array_download returns them; they

@@ -65,12 +65,10 @@ def case(name):
     raise SystemExit(f"unknown case {name}")
 
 
-def main():
-    data, blocks = case(os.environ["STRETCH_PROBE_CASE"])
-    lib = api.library()
-    ctx = Context(0, lib)
-    ctx.set_input(data)
-    t = ctx.build_tables(blocks)
+def squeeze_runs_against_oracle(t, data, blocks):
+    """Three chained squeeze runs on the tables `t` of `blocks` of `data`, each held to the CPU oracle (length_array,
+    stores, histograms, symbol counts; the first mismatch is printed and ends the process with status 1).  -> the
+    digest of everything the runs produced."""
     nb = len(blocks)
     nsym, hist = t.greedy(0)
     tables = [ol.OracleTable(data, s, e) for (s, e) in blocks]
@@ -105,11 +103,21 @@ def main():
                 sys.exit(1)
             digest.update(np.ascontiguousarray(gll).tobytes() + np.ascontiguousarray(gdd).tobytes())
             digest.update(np.ascontiguousarray(hist[b]).tobytes())
+    return digest.hexdigest()
+
+
+def main():
+    data, blocks = case(os.environ["STRETCH_PROBE_CASE"])
+    lib = api.library()
+    ctx = Context(0, lib)
+    ctx.set_input(data)
+    t = ctx.build_tables(blocks)
+    digest = squeeze_runs_against_oracle(t, data, blocks)
     t.free()
     ctx.close()
     st = api.last_seg_stats(lib)
     st["blocks"] = sum(1 for (s, e) in blocks if e > s)
-    st["digest"] = digest.hexdigest()
+    st["digest"] = digest
     print(json.dumps(st), flush=True)
 
 

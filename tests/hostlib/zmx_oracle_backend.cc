@@ -97,6 +97,7 @@ int zmx_internal_input_fetch(zmx_ctx*, size_t, size_t, unsigned char*) {
 }
 int zmx_hash_links_download(zmx_ctx*, zmx_tables*, size_t, uint16_t*, uint16_t*, uint16_t*) { return Fail("not in the host test library"); }
 int zmx_dp_rows_download(zmx_ctx*, zmx_tables*, size_t, uint64_t*, uint32_t*, uint16_t*, uint32_t*, uint32_t*, uint32_t*) { return Fail("not in the host test library"); }
+int zmx_chain_tasks_download(zmx_ctx*, zmx_tables*, uint64_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*) { return Fail("not in the host test library"); }
 int zmx_match_digest(zmx_ctx*, zmx_tables*, uint64_t*) { return Fail("not in the host test library"); }
 int zmx_set_match_kernel(int) { return 0; }   // (no kernels here)
 void zmx_set_oom_hook(zmx_oom_hook_t) {}

@@ -123,6 +123,7 @@ def trimmed_tables_refuse(ctx, hash_links=True, dp_rows=True):
             calls["zmx_hash_links_download"] = lambda: t.hash_links(0)
         if dp_rows:
             calls["zmx_dp_rows_download"] = lambda: t.dp_rows(0)
+            calls["zmx_chain_tasks_download"] = lambda: t.chain_tasks()
         for who, call in calls.items():
             _refused(ctx, call, f"{who}: {TRIMMED}")
         for b in range(len(BLOCKS)):
@@ -139,6 +140,7 @@ def matches_only_tables_refuse(ctx, dp_rows=True):
         _refused(ctx, lambda: t.trace(las, [0, 0]), f"zmx_trace_length_arrays: {MATCHES_ONLY}")
         if dp_rows:
             _refused(ctx, lambda: t.dp_rows(0), f"zmx_dp_rows_download: {MATCHES_ONLY}")
+            _refused(ctx, lambda: t.chain_tasks(), f"zmx_chain_tasks_download: {MATCHES_ONLY}")
         assert np.array_equal(t.greedy(1)[0], counts[0])
     finally:
         t.free()
@@ -151,6 +153,14 @@ def probe_blocks_checked(ctx):
         nb = len(BLOCKS)
         _refused(ctx, lambda: t.dp_rows(nb), "zmx_dp_rows_download: bad block")
         assert len(t.dp_rows(nb - 1)["kend"]) == BLOCKS[-1][1] - BLOCKS[-1][0]
+        # zmx_chain_tasks_download names no block; its sizes-first call: the arrays have the sizes it reported, every
+        # block has a first task, and the tasks are those of the two lists
+        ct = t.chain_tasks()
+        nt = len(ct["tasks"])
+        assert nt >= nb and len(ct["task_off"]) == nb + 1 and int(ct["task_off"][-1]) == nt
+        assert len(ct["wg_desc"]) == ct["n_wg"] + ct["n_wg_runs"] > 0
+        assert sorted(map(int, ct["wg_tasks"])) == list(range(nt)) and int(ct["wg_desc"][:, 1].sum()) == nt
+        assert [int(ct["tasks"][int(k), 2]) for k in ct["task_off"][:-1]] == [0] * nb
     finally:
         t.free()
 

@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_lib as ol  # noqa: E402
+from chain_task_cases import cut_points  # noqa: E402  (the one statement of the definition: the reference of the GPU tests)
 from zopfli_amd import generate  # noqa: E402
 
 
@@ -31,8 +32,7 @@ def density(cls, n):
         t.lib.zo_find_longest_match(t.h, p, sub.ctypes.data_as(ol._u16p), ctypes.byref(d), ctypes.byref(l))
         if l.value >= 3:
             kend[p] = min(l.value, n - p)        # squeeze.c:286
-    reach = np.maximum.accumulate(np.arange(n) + kend)      # reach[q - 1] = furthest cell an edge from below q gets to
-    cuts = np.flatnonzero(reach <= np.arange(1, n + 1)) + 1
+    cuts = np.flatnonzero(cut_points(kend))
     gaps = np.diff(np.concatenate(([0], cuts)))
     return len(cuts), gaps
 

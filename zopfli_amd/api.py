@@ -1237,3 +1237,29 @@ class Tables:
                 "run_row": (flags >> 17) & 1, "literal": (flags >> 18) & 0xff, "codeless": (flags >> 26) & 1,
                 "block_edges": int(edges.value), "codes": codes[:edges.value], "winflag": winflag, "winroff": winroff,
                 "wmeta": wmeta}
+
+    def chain_tasks(self):
+        """zmx_chain_tasks_download: the chain's task set-up of the whole table set as a dict — "tasks" (uint32
+        [ntasks, 4]: block, q, pout, pend, after the merge), "task_off" (uint32[nb + 1]), "merged" (int), "wg_tasks"
+        (uint32[ntasks]: the text list, then the run list), "wg_desc" (uint32[n_wg + n_wg_runs, 2]: first entry,
+        entries), "n_wg", "n_wg_runs" (int) and "kind" (uint32[ntasks]: 1 for the tasks of the run list)."""
+        import numpy as np
+        fn = self.ctx.lib.zmx_chain_tasks_download
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)] + [ctypes.c_void_p] * 4
+        counts = (ctypes.c_uint64 * 4)()
+        # (the sizes first; tables that the entry refuses are refused here)
+        self.ctx._check(fn(self.ctx.handle, self.handle, counts, None, None, None, None), "zmx_chain_tasks_download")
+        nt, merged, n_wg, n_wg_runs = (int(v) for v in counts)
+        tasks = np.zeros((max(nt, 1), 4), dtype=np.uint32)
+        task_off = np.zeros(len(self.blocks) + 1, dtype=np.uint32)
+        wg_tasks = np.zeros(max(nt, 1), dtype=np.uint32)
+        wg_desc = np.zeros((max(n_wg + n_wg_runs, 1), 2), dtype=np.uint32)
+        self.ctx._check(fn(self.ctx.handle, self.handle, counts, tasks.ctypes.data, task_off.ctypes.data, wg_tasks.ctypes.data,
+                           wg_desc.ctypes.data), "zmx_chain_tasks_download")
+        wg_desc = wg_desc[:n_wg + n_wg_runs]
+        kind = np.zeros(nt, dtype=np.uint32)
+        for first, n in wg_desc[n_wg:]:
+            kind[wg_tasks[int(first):int(first) + int(n)]] = 1
+        return {"tasks": tasks[:nt], "task_off": task_off, "merged": merged, "wg_tasks": wg_tasks[:nt], "wg_desc": wg_desc,
+                "n_wg": n_wg, "n_wg_runs": n_wg_runs, "kind": kind}

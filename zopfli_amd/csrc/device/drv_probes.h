@@ -1,5 +1,5 @@
 // Driver part: the parity probes — zmx_match_digest (its kernel k_rec_digest: zmx_probe.h), zmx_find_longest_match,
-// zmx_hash_links_download, zmx_length_array_download, zmx_dp_rows_download.  Needs drv_context.h (PoolScope) and drv_tables.h (zmx_tables, the checks).
+// zmx_hash_links_download, zmx_length_array_download, zmx_dp_rows_download, zmx_chain_tasks_download.  Needs drv_context.h (PoolScope) and drv_tables.h (zmx_tables, the checks).
 #pragma once
 
 extern "C" {
@@ -98,6 +98,25 @@ int zmx_dp_rows_download(zmx_ctx* c, zmx_tables* t, size_t block, uint64_t* bloc
   if (winflag) HIPCHK(hipMemcpy(winflag, t->d_winflag + w0, nw * sizeof(u32), hipMemcpyDeviceToHost));
   if (winroff) HIPCHK(hipMemcpy(winroff, t->d_winroff + w0, nw * sizeof(u32), hipMemcpyDeviceToHost));
   if (wmeta) HIPCHK(hipMemcpy(wmeta, t->d_wmeta + w0 * D5_WM, nw * D5_WM * sizeof(u32), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int zmx_chain_tasks_download(zmx_ctx* c, zmx_tables* t, uint64_t* counts4, uint32_t* tasks, uint32_t* task_off, uint32_t* wg_tasks,
+                             uint32_t* wg_desc) {
+  if (const int rc = CheckTables("zmx_chain_tasks_download", t, zamd::kWithDp)) return rc;
+  DEVICE_ENTRY(c->device);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  // (every task is in exactly one of the two lists: BuildWorkgroupLists)
+  const size_t nt = t->tasks.size(), nwg = static_cast<size_t>(t->n_wg) + t->n_wg_runs;
+  counts4[0] = nt;
+  counts4[1] = t->merged_tasks;
+  counts4[2] = t->n_wg;
+  counts4[3] = t->n_wg_runs;
+  static_assert(sizeof(SegTask) == 4 * sizeof(u32) && sizeof(uint2) == 2 * sizeof(u32), "the caller's rows");
+  if (tasks && nt) HIPCHK(hipMemcpy(tasks, t->d_tasks, nt * sizeof(SegTask), hipMemcpyDeviceToHost));
+  if (task_off && t->nb) HIPCHK(hipMemcpy(task_off, t->d_task_off, (t->nb + 1) * sizeof(u32), hipMemcpyDeviceToHost));
+  if (wg_tasks && nwg) HIPCHK(hipMemcpy(wg_tasks, t->d_wg_tasks, nt * sizeof(u32), hipMemcpyDeviceToHost));
+  if (wg_desc && nwg) HIPCHK(hipMemcpy(wg_desc, t->d_wg_desc, nwg * sizeof(uint2), hipMemcpyDeviceToHost));
   return 0;
 }
 }  // extern "C"

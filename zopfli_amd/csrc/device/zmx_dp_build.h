@@ -80,9 +80,11 @@ __global__ __launch_bounds__(256) void k_mkdesc(MkDescParams P) {
 // value through cell q alone, so a chain started at q from ONE cell is the true chain shifted by a constant,
 // with no warm-up and nothing left to chance (a long-run shortcut cannot span a cut either: the run's own
 // matches would cross it).  Text has one every ~25 positions (largest gap seen: 688), data made of long runs
-// almost none.  One wave per task looks for the last cut point at most `depth` positions before the task's
-// pout and makes it the task's start (SegTask.q, which then need not be a multiple of 32: k_dp5_spec starts
-// at the window that holds it, with the level in that window's cell); tasks without one keep the warm-up.
+// almost none.  One wave per task looks for the last cut point q in [pout - depth, pout) — in [1, pout) where
+// pout <= depth + 258: the scan then starts at the block's first position, its prefix maximum is the true one
+// everywhere, and an older cut point is as exact and still cheaper than a warm-up — and makes it the task's
+// start (SegTask.q, which then need not be a multiple of 32: k_dp5_spec starts at the window that holds it,
+// with the level in that window's cell); tasks without one keep the warm-up.
 // ---------------------------------------------------------------------------------------------
 struct CutParams {
   const BlockDesc* blocks;
@@ -112,9 +114,12 @@ __global__ __launch_bounds__(64) void k_cutpoints(CutParams P) {
   const u32 wlo = K.pout > P.warm ? K.pout - P.warm : 0u;
   // the prefix maximum from lo on is the true one for q >= lo + 258 (no edge is longer), and for every q if lo = 0
   const u32 q_min = lo == 0 ? 1u : lo + ZMX_MAX_MATCH;
+  // the whole warm-up stretch is looked at for long-run material, also where it begins before lo (a warm-up longer than
+  // depth + 258): a prefix maximum from an earlier start is as true from q_min on
+  const u32 scan_lo = wlo < lo ? wlo : lo;
   u32 carry = 0, best = SEG_NONE;
   bool wide = false;
-  for (u32 p0 = lo; p0 < K.pout; p0 += 64) {
+  for (u32 p0 = scan_lo; p0 < K.pout; p0 += 64) {
     const u32 p = p0 + lane;
     const u32 y = p < K.pout ? dph[p].y : 0u;
     const u32 r = p < K.pout ? p + (y & 0xffffu) : 0u;
