@@ -498,8 +498,9 @@ int zmx_png_convert_device(zmx_ctx* ctx, const zmx_png_image* image, const zmx_p
  * Where the chosen mode is the image's own nothing is converted and the file is zmx_png_encode_device's.  No pixel visits
  * the host.  Conventions, refusals and failure behaviour are zmx_png_encode_device's; an image of 2^32 pixels or more
  * is refused as well.
- * Out of scope: palette INPUT, interlace, --lossy_transparent, --lossy_8bit, ancillary chunks, zopflipng's automatic
- * strategy trial (libzopflipng_amd.so does those, from a file), a PNG left in device memory. */
+ * Out of scope: palette INPUT, interlace, ancillary chunks, zopflipng's automatic strategy trial (libzopflipng_amd.so
+ * does those, from a file), a PNG left in device memory.  --lossy_transparent and --lossy_8bit are the _lossy entries'
+ * further down. */
 int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
                             const unsigned char* predefined, unsigned char** out, size_t* outsize);
 /* n images in one call: every file is the single call's.  Statistics and conversion run image by image on one hold of a
@@ -507,6 +508,65 @@ int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* i
  * if any image takes one.  Otherwise as zmx_png_encode_device_batch. */
 int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
                                   unsigned char** out, size_t* outsize);
+
+/* -------- zopflipng's --lossy_transparent and --lossy_8bit on an image in device memory
+ *
+ * zopflipng's rewrite of the pixels nobody sees (zopflipng_lib.cc LossyOptimizeTransparent), device memory to device
+ * memory.  Every pixel is read as 8-bit r, g, b, a (grey + alpha gives r = g = b), the N = width * height pixels in
+ * raster order, rows back to back:
+ *   key      no pixel has 0 < a < 255
+ *   palette  at most 256 colours, every pixel with a = 0 counting as one colour
+ *   mode 1   (key or palette) every pixel with a = 0 gets the RGB of the FIRST pixel with a = 0
+ *   mode 2   (otherwise) a pixel with a = 0 gets the RGB of the last pixel before it — in the whole image, not its row —
+ *            that had a > 0, and (0, 0, 0) where there was none
+ *   mode 0   no pixel has a = 0, or the colour type is 0 or 2 (no statistics are taken for those: partial_alpha and
+ *            numcolors are 0): d_out gets a copy of the image
+ * Alpha and the pixels with a > 0 never change.  d_out gets `height` rows of `linebytes` in the image's own format, in
+ * every mode; d_out == image->d_pixels rewrites in place.  For a 16-bit image the call takes the caller at their word:
+ * the pixels are read through their HIGH bytes, and the high bytes of r, g, b of a pixel whose alpha's high byte is 0 are
+ * rewritten, the low bytes left — something zopflipng never does (it leaves a 16-bit image alone) and the entries below
+ * never ask for.
+ * k_png_lossy_stats, k_png_lossy_carry (mode 2 only) and k_png_lossy_fill (device/zmx_png_lossy.h) run one after the
+ * other on the context's stream, at most 2048 workgroups each, none waiting for another; a few words come down, no pixel
+ * does.  Refused before any launch (ZMX_ERR_REFUSED): what zmx_png_color_stats_device refuses of the image, a `capacity`
+ * below the image's size, an output that is no device memory of the context's device, an output that overlaps the image
+ * without being the image.  Synchronous; the caller synchronises the stream that produced the image. */
+#define ZMX_PNG_LOSSY_TRANSPARENT 1u
+#define ZMX_PNG_LOSSY_8BIT 2u
+typedef struct zmx_png_lossy_info {
+  uint32_t mode;            /* 0 no transparent pixel (d_out = the image), 1 fixed, 2 carry */
+  uint32_t partial_alpha;   /* some 0 < a < 255 */
+  uint32_t numcolors;       /* transparent pixels as one colour; 257 = more than 256 */
+  uint32_t fill_r, fill_g, fill_b;   /* mode 1: the colour; else 0 */
+  uint64_t first_transparent;        /* pixel index, UINT64_MAX without one */
+} zmx_png_lossy_info;
+int zmx_png_lossy_transparent_device(zmx_ctx* ctx, const zmx_png_image* image, void* d_out, size_t capacity,
+                                     zmx_png_lossy_info* info /* may be null */);
+
+/* zmx_png_encode_device and zmx_png_optimize_device with zopflipng's lossy options: `lossy` is 0 or an OR of
+ * ZMX_PNG_LOSSY_*, anything else is refused.  The encode entry ends holding the file
+ *   zopflipng --keepcolortype --always_zopflify --filters=<strategy> [--lossy_transparent] [--lossy_8bit]
+ * writes, the optimize entry the same without --keepcolortype, byte for byte under the conditions of the entries above.
+ * The flags mean what they mean to zopflipng (zopflipng_lib.cc:415-428), the combinations that do nothing included:
+ *   _8BIT         a 16-bit image is encoded as the 8-bit image of its high bytes (same colour type, made by
+ *                 k_png_convert) — for the optimize entry; the encode entry accepts and ignores it
+ *   _TRANSPARENT  zmx_png_lossy_transparent_device's rewrite of an image that is 8-bit by then; nothing happens to a
+ *                 16-bit image unless the optimize entry has _8BIT as well
+ * lossy = 0 gives zmx_png_encode_device's / zmx_png_optimize_device's file.  The caller's image is never written: the
+ * rewritten and the 8-bit image go to a buffer of the call's own, on the hold of the context that makes the statistics
+ * and the rows, and everything after is the entries' path on that buffer — the choice of the mode, the second try below
+ * 4096 bytes, the row search, one zmx_compress_device[_batch](ZLIB).  No pixel visits the host.  The batches rewrite image
+ * by image with the batch's flags.  Conventions, refusals, failure behaviour and _PREDEFINED are the entries' above; the
+ * encode entries refuse as well, before anything runs, an image of 2^32 pixels or more that _TRANSPARENT would rewrite
+ * (grey + alpha or RGBA at 8 bits), as the optimize entries refuse any such image. */
+int zmx_png_encode_device_lossy(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_optimize_device_lossy(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                  const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_encode_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                      unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_optimize_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                        unsigned lossy, unsigned char** out, size_t* outsize);
 
 /* Parity probe over whole tables: two 64-bit sums over all positions of a hash of the logical content of the match
  * records (block, position, length, distance, same, literal, every change point of sublen).  Equal digests of two

@@ -382,6 +382,30 @@ def _png_strategy(strategy):
     return PNG_STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)
 
 
+PNG_LOSSY_TRANSPARENT, PNG_LOSSY_8BIT = 1, 2   # ZMX_PNG_LOSSY_*
+
+
+def _png_lossy(lossy_transparent, lossy_8bit):
+    return (PNG_LOSSY_TRANSPARENT if lossy_transparent else 0) | (PNG_LOSSY_8BIT if lossy_8bit else 0)
+
+
+def _png_entry(lib, name, lossy, batch):
+    """(function, the arguments behind the strategy or the types) of a PNG entry: the _lossy symbol with its flags where
+    flags are set, else the plain one — a library from before the flags still loads and serves lossy = 0."""
+    fn = getattr(lib, name + "_lossy" if lossy else name)
+    head = ([ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_int] if batch else
+            [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p])
+    fn.argtypes = head + ([ctypes.c_uint] if lossy else []) + [ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    return fn, ((lossy,) if lossy else ())
+
+
+class PngLossyInfo(ctypes.Structure):
+    """zmx_png_lossy_info; first_transparent is 2^64 - 1 without a transparent pixel."""
+    _fields_ = [("mode", ctypes.c_uint32), ("partial_alpha", ctypes.c_uint32), ("numcolors", ctypes.c_uint32), ("fill_r", ctypes.c_uint32),
+                ("fill_g", ctypes.c_uint32), ("fill_b", ctypes.c_uint32), ("first_transparent", ctypes.c_uint64)]
+
+
 def _png_image(image, sync=True):
     """The zmx_png_image of a contiguous uint8 tensor (H, W) or (H, W, 2 | 3 | 4), or of a tuple
     (pointer, width, height, colortype, bitdepth)."""
@@ -398,14 +422,16 @@ def _png_image(image, sync=True):
     return PngImage(ptr or None, shape[1], shape[0], _PNG_COLORTYPE[shape[2]], 8)
 
 
-def png_encode_device(image, strategy="e", options=None, predefined=None, lib=None):
+def png_encode_device(image, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_encode_device: the image in device memory as the PNG file `zopflipng --keepcolortype --always_zopflify
     --filters=<strategy>` writes for it (when options.numiterations is zopflipng's: 15 below 200 000 bytes of scanlines,
     else 5).  `image`: a contiguous uint8 tensor (H, W) grey, (H, W, 2) grey + alpha, (H, W, 3) RGB or (H, W, 4) RGBA — a
     torch tensor's current stream is synchronised first — or (pointer, width, height, colortype, bitdepth) for any of
     the colour types 0, 2, 4, 6 at 8 or 16 bits (16-bit samples big-endian).  `strategy`: one of "0" "1" "2" "3" "4" "m"
-    "e" "b", or "p" with `predefined`, a filter type (0 .. 4) for every row.  Returns the file's bytes.  Raises ValueError
-    for a tensor that is no image, RuntimeError with the library's message when the library refuses or fails."""
+    "e" "b", or "p" with `predefined`, a filter type (0 .. 4) for every row.  `lossy_transparent`, `lossy_8bit`: zopflipng's
+    --lossy_transparent and --lossy_8bit (zmx_png_encode_device_lossy; under --keepcolortype the second does nothing and
+    the first nothing to a 16-bit image).  Returns the file's bytes.  Raises ValueError for a tensor that is no image,
+    RuntimeError with the library's message when the library refuses or fails."""
     lib = lib or library()
     options = options or ZopfliOptions()
     im = _png_image(image)
@@ -414,16 +440,13 @@ def png_encode_device(image, strategy="e", options=None, predefined=None, lib=No
         raise ValueError(f"{len(types)} predefined types for {im.height} rows")
     out, outsize = _u8p(), ctypes.c_size_t(0)
     # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
-    fn = lib.zmx_png_encode_device
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p,
-                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, ctypes.byref(out), ctypes.byref(outsize)) != 0:
+    fn, flags = _png_entry(lib, "zmx_png_encode_device", _png_lossy(lossy_transparent, lossy_8bit), False)
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, *flags, ctypes.byref(out), ctypes.byref(outsize)) != 0:
         raise RuntimeError("zmx_png_encode_device: " + (lib.zmx_last_error() or b"").decode())
     return _take(out, outsize)
 
 
-def png_encode_device_batch(images, strategy="e", options=None, lib=None):
+def png_encode_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_encode_device_batch: one PNG file per image, each the one png_encode_device gives, from one call that
     shares its deflate work among them.  `images`: a list of what png_encode_device takes (the current stream of every
     torch device among the tensors is synchronised once).  Predefined types are the single call's."""
@@ -442,11 +465,8 @@ def png_encode_device_batch(images, strategy="e", options=None, lib=None):
     arr = (PngImage * max(n, 1))(*ims)
     outs = (_u8p * max(n, 1))()
     outsizes = (ctypes.c_size_t * max(n, 1))()
-    fn = lib.zmx_png_encode_device_batch
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_int,
-                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), outs, outsizes) != 0:
+    fn, flags = _png_entry(lib, "zmx_png_encode_device_batch", _png_lossy(lossy_transparent, lossy_8bit), True)
+    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), *flags, outs, outsizes) != 0:
         raise RuntimeError("zmx_png_encode_device_batch: " + (lib.zmx_last_error() or b"").decode())
     return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
 
@@ -485,11 +505,13 @@ def png_choose_color(stats, numpixels, lib=None):
     return mode
 
 
-def png_optimize_device(image, strategy="e", options=None, predefined=None, lib=None):
+def png_optimize_device(image, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_optimize_device: png_encode_device with the colour mode reduced first — the file `zopflipng
     --always_zopflify --filters=<strategy>` (no --keepcolortype) writes for the image: grey, a palette, a key or fewer
     bits where the pixels allow it, and RGB or RGBA instead of a palette where that makes a small file smaller.
-    Arguments, result and errors as png_encode_device's."""
+    `lossy_8bit` encodes a 16-bit image as the 8-bit image of its high bytes, `lossy_transparent` gives the pixels with
+    alpha 0 of an image that is 8-bit by then the RGB zopflipng gives them (zmx_png_optimize_device_lossy).  Arguments,
+    result and errors as png_encode_device's."""
     lib = lib or library()
     options = options or ZopfliOptions()
     im = _png_image(image)
@@ -497,16 +519,14 @@ def png_optimize_device(image, strategy="e", options=None, predefined=None, lib=
     if types is not None and len(types) != im.height:
         raise ValueError(f"{len(types)} predefined types for {im.height} rows")
     out, outsize = _u8p(), ctypes.c_size_t(0)
-    fn = lib.zmx_png_optimize_device
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p,
-                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, ctypes.byref(out), ctypes.byref(outsize)) != 0:
+    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
+    fn, flags = _png_entry(lib, "zmx_png_optimize_device", _png_lossy(lossy_transparent, lossy_8bit), False)
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, *flags, ctypes.byref(out), ctypes.byref(outsize)) != 0:
         raise RuntimeError("zmx_png_optimize_device: " + (lib.zmx_last_error() or b"").decode())
     return _take(out, outsize)
 
 
-def png_optimize_device_batch(images, strategy="e", options=None, lib=None):
+def png_optimize_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_optimize_device_batch: one file per image, each the one png_optimize_device gives, from one call.
     Arguments as png_encode_device_batch's."""
     lib = lib or library()
@@ -524,11 +544,8 @@ def png_optimize_device_batch(images, strategy="e", options=None, lib=None):
     arr = (PngImage * max(n, 1))(*ims)
     outs = (_u8p * max(n, 1))()
     outsizes = (ctypes.c_size_t * max(n, 1))()
-    fn = lib.zmx_png_optimize_device_batch
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_int,
-                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), outs, outsizes) != 0:
+    fn, flags = _png_entry(lib, "zmx_png_optimize_device_batch", _png_lossy(lossy_transparent, lossy_8bit), True)
+    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), *flags, outs, outsizes) != 0:
         raise RuntimeError("zmx_png_optimize_device_batch: " + (lib.zmx_last_error() or b"").decode())
     return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
 
@@ -740,6 +757,24 @@ class Context:
         fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngImage), ctypes.POINTER(PngColorMode), ctypes.c_void_p, ctypes.c_size_t]
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, ctypes.byref(im), ctypes.byref(mode), dst or None, capacity), "zmx_png_convert_device")
+
+    def png_lossy_transparent_device(self, image, out, capacity=None):
+        """zmx_png_lossy_transparent_device: zopflipng's --lossy_transparent rewrite of the image (`image` as
+        png_encode_device takes it) into `out`, a tensor or an integer pointer with `capacity` bytes (an integer pointer
+        without one: exactly the image's size), memory of this context's device; `out` may be the image itself.  Returns
+        the PngLossyInfo."""
+        im = _png_image(image)
+        if isinstance(out, int):
+            nbytes = im.height * im.width * {0: 1, 2: 3, 4: 2, 6: 4}.get(im.colortype, 0) * (im.bitdepth // 8)
+            dst, capacity = out, nbytes if capacity is None else int(capacity)
+        else:
+            dst, capacity = _device_range(out, capacity)
+        info = PngLossyInfo()
+        fn = self.lib.zmx_png_lossy_transparent_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngImage), ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(PngLossyInfo)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, ctypes.byref(im), dst or None, capacity, ctypes.byref(info)), "zmx_png_lossy_transparent_device")
+        return info
 
     def bitjoin_device(self, pieces, total_bits, dst, capacity=None):
         """zmx_bitjoin_device: pieces = [(src pointer, src_bit, nbits, dst_bit)] — bits [src_bit, src_bit + nbits) of the

@@ -1,6 +1,7 @@
 // Driver part: LodePNG's filter choices on the device (zmx_png.h, zmx_png_brute.h) and the filtered scanlines
 // (zmx_png_rows.h).  Holds zmx_png_filter_types, zmx_png_filter_types_brute, their device-image form
-// zmx_png_filter_types_device, zmx_png_filter_rows_device and the encoder's zmx_internal_png_scanlines.  Needs
+// zmx_png_filter_types_device, zmx_png_filter_rows_device and the encoder's zmx_internal_png_scanlines; the colour
+// statistics and conversion (zmx_png_color.h); zopflipng's --lossy_transparent (zmx_png_lossy.h).  Needs
 // drv_context.h (zmx_ctx, PoolScope) and drv_input.h (CheckDevicePointer).
 #pragma once
 
@@ -236,10 +237,98 @@ static int PngConvertOnDevice(zmx_ctx* c, PoolScope* tmp, const char* who, const
   return 0;
 }
 
+// ---- zopflipng's --lossy_transparent (zmx_png_lossy.h)
+static thread_local double g_png_lossy_ms[3] = {0, 0, 0};   // k_png_lossy_stats, k_png_lossy_carry, k_png_lossy_fill (zmx_internal_png_lossy_ms)
+
+// One kernel's time where kernel timing is on: between Begin and End on the context's stream; End drains it.
+struct PngLossyTimer {
+  zmx_ctx* c;
+  bool timed;
+  hipError_t Begin() { return timed ? hipEventRecord(c->ev[0], c->stream) : hipSuccess; }
+  hipError_t End(double* ms) {
+    if (!timed) return hipSuccess;
+    hipError_t e = hipEventRecord(c->ev[1], c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    float f = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&f, c->ev[0], c->ev[1]);
+    *ms = f;
+    return e;
+  }
+};
+
+// The rewrite of an image the caller has checked (colour type 4 or 6), into d_out — the image's own pixels: in place.
+// Statistics, the state read, then the carry scan (mode 2) and the fill, or with `copy_when_none` a copy where no pixel is
+// transparent.  *info is filled.  Drains the context's stream.
+static int PngLossyOnDevice(zmx_ctx* c, PoolScope* tmp, const zamd::PngColorImage& I, size_t nbytes, u8* d_out, bool copy_when_none,
+                            zmx_png_lossy_info* info) {
+  const u64 tiles = zamd::PngLossyTiles(I);
+  const u32 grid = zamd::PngLossyGrid(I);
+  zamd::PngLossyState* d_state = nullptr;
+  u32* d_summaries = nullptr;
+  HIPCHK(tmp->AllocT(&d_state, 1, "d_png_lossy_state"));
+  HIPCHK(tmp->AllocT(&d_summaries, static_cast<size_t>(tiles), "d_png_lossy_summaries"));
+  u8* const raw = reinterpret_cast<u8*>(d_state);
+  HIPCHK(hipMemsetAsync(raw, 0xff, sizeof(zamd::PngLossyState), c->stream));
+  HIPCHK(hipMemsetAsync(raw + offsetof(zamd::PngLossyState, color), 0, offsetof(zamd::PngColorState, key_min), c->stream));
+  PngLossyTimer timer{c, KernelTiming()};
+  HIPCHK(timer.Begin());
+  hipLaunchKernelGGL(k_png_lossy_stats, dim3(grid), dim3(zamd::kPngLossyThreads), 0, c->stream, I, d_state, d_summaries);
+  KCHK(c, "k_png_lossy_stats");
+  HIPCHK(timer.End(&g_png_lossy_ms[0]));
+  zamd::PngLossyState state;   // (all of it but the table)
+  HIPCHK(hipMemcpyAsync(&state, d_state, offsetof(zamd::PngLossyState, color) + offsetof(zamd::PngColorState, table), hipMemcpyDeviceToHost,
+                        c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const zamd::PngLossyDecision d = zamd::PngLossyDecide(state);
+  *info = zmx_png_lossy_info();
+  info->mode = d.mode;
+  info->partial_alpha = d.partial_alpha;
+  info->numcolors = d.numcolors;
+  info->first_transparent = state.first_transparent == zamd::kPngLossyNoIndex ? UINT64_MAX : state.first_transparent;
+  if (d.mode == zamd::kPngLossyModeNone) {
+    if (copy_when_none && d_out != I.pixels) {
+      HIPCHK(hipMemcpyAsync(d_out, I.pixels, nbytes, hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+  }
+  zamd::PngLossyParams P;
+  P.in = I;
+  P.out = d_out;
+  P.mode = d.mode;
+  P.first_transparent = state.first_transparent;
+  P.carry_in = nullptr;
+  P.state = d_state;
+  if (d.mode == zamd::kPngLossyModeCarry) {
+    u32* d_carry = nullptr;
+    HIPCHK(tmp->AllocT(&d_carry, static_cast<size_t>(tiles), "d_png_lossy_carry"));
+    HIPCHK(timer.Begin());
+    hipLaunchKernelGGL(k_png_lossy_carry, dim3(1), dim3(zamd::kPngLossyThreads), 0, c->stream, static_cast<const u32*>(d_summaries), d_carry,
+                       tiles);
+    KCHK(c, "k_png_lossy_carry");
+    HIPCHK(timer.End(&g_png_lossy_ms[1]));
+    P.carry_in = d_carry;
+  }
+  HIPCHK(timer.Begin());
+  hipLaunchKernelGGL(k_png_lossy_fill, dim3(grid), dim3(zamd::kPngLossyThreads), 0, c->stream, P);
+  KCHK(c, "k_png_lossy_fill");
+  HIPCHK(timer.End(&g_png_lossy_ms[2]));
+  u32 fill = 0;
+  if (d.mode == zamd::kPngLossyModeFixed) HIPCHK(hipMemcpyAsync(&fill, &d_state->fill, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  info->fill_r = fill & 255u;
+  info->fill_g = (fill >> 8) & 255u;
+  info->fill_b = (fill >> 16) & 255u;
+  return 0;
+}
+
 extern "C" {
 double zmx_internal_png_rows_ms(void) { return g_png_rows_ms; }
 void zmx_internal_png_color_ms(double out[3]) {
   for (int k = 0; k < 3; ++k) out[k] = g_png_color_ms[k];
+}
+void zmx_internal_png_lossy_ms(double out[3]) {
+  for (int k = 0; k < 3; ++k) out[k] = g_png_lossy_ms[k];
 }
 
 int zmx_png_color_stats_device(zmx_ctx* c, const zmx_png_image* image, zmx_png_color_stats* out) {
@@ -286,6 +375,75 @@ int zmx_png_convert_device(zmx_ctx* c, const zmx_png_image* image, const zmx_png
   DEVICE_ENTRY(c->device);
   PoolScope tmp(c);
   const int rc = PngConvertOnDevice(c, &tmp, who, I, *mode, static_cast<u8*>(d_out));
+  if (rc != 0) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+int zmx_png_lossy_transparent_device(zmx_ctx* c, const zmx_png_image* image, void* d_out, size_t capacity, zmx_png_lossy_info* info) {
+  const char* who = "zmx_png_lossy_transparent_device";
+  g_png_lossy_ms[0] = g_png_lossy_ms[1] = g_png_lossy_ms[2] = 0;
+  if (!c) return FailMsg(std::string(who) + ": no context");
+  zamd::PngColorImage I;
+  size_t nbytes = 0;
+  if (const int rc = PngColorImageOf(who, image, &I, &nbytes)) return rc;
+  if (capacity < nbytes) {
+    return FailMsg(std::string(who) + ": the output takes " + std::to_string(nbytes) + " bytes, the capacity is " + std::to_string(capacity));
+  }
+  int img_device = -1, out_device = -1;
+  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (const int rc = CheckDevicePointer(who, d_out, nbytes, &out_device)) return rc;
+  if (img_device != c->device || out_device != c->device) return FailMsg(std::string(who) + ": memory of another device than the context's");
+  if (d_out != image->d_pixels && RangesOverlap(d_out, nbytes, image->d_pixels, nbytes)) {
+    return FailMsg(std::string(who) + ": the output overlaps the image without being the image");
+  }
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  zmx_png_lossy_info got = zmx_png_lossy_info();
+  got.first_transparent = UINT64_MAX;
+  int rc = 0;
+  if (I.colortype == 4 || I.colortype == 6) {
+    rc = PngLossyOnDevice(c, &tmp, I, nbytes, static_cast<u8*>(d_out), true, &got);
+  } else if (d_out != image->d_pixels) {
+    // (no alpha channel: nothing is transparent)
+    const hipError_t e = hipMemcpyAsync(d_out, image->d_pixels, nbytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) rc = Fail("hipMemcpyAsync(image)", e, __FILE__, __LINE__);
+  }
+  const hipError_t e = hipStreamSynchronize(c->stream);   // what was queued may still use `tmp`'s arrays
+  if (rc != 0) return rc;
+  HIPCHK(e);
+  if (info) *info = got;
+  return 0;
+}
+
+// The _lossy entries' device part (host/png_encode.cc; zmx_internal.h says what it makes).
+int zmx_internal_png_lossy_image(zmx_ctx* c, const char* who, const zmx_png_image* image, int to8, int transparent, void* d_buf,
+                                 zmx_png_image* work) {
+  zamd::PngColorImage I;
+  size_t nbytes = 0;
+  if (const int rc = PngColorImageOf(who, image, &I, &nbytes)) return rc;
+  int img_device = -1;
+  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (img_device != c->device) return FailMsg(std::string(who) + ": the image is memory of another device than the context's");
+  *work = *image;
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  int rc = 0;
+  if (to8 && I.bitdepth == 16) {
+    zmx_png_color_mode mode = zmx_png_color_mode();
+    mode.colortype = I.colortype;
+    mode.bitdepth = 8;
+    rc = PngConvertOnDevice(c, &tmp, who, I, mode, static_cast<u8*>(d_buf));
+    I.pixels = static_cast<const u8*>(d_buf);
+    I.bitdepth = 8;
+    nbytes /= 2;
+    work->d_pixels = d_buf;
+    work->bitdepth = 8;
+  }
+  if (rc == 0 && transparent && I.bitdepth == 8 && (I.colortype == 4 || I.colortype == 6)) {
+    zmx_png_lossy_info info;
+    rc = PngLossyOnDevice(c, &tmp, I, nbytes, static_cast<u8*>(d_buf), false, &info);
+    if (rc == 0 && info.mode != zamd::kPngLossyModeNone) work->d_pixels = d_buf;
+  }
   if (rc != 0) (void)hipStreamSynchronize(c->stream);
   return rc;
 }

@@ -44,6 +44,8 @@
 #include "zmx_png_rows.h"    // the filtered scanlines of a PNG
 #define ZMX_PNG_COLOR_KERNELS
 #include "zmx_png_color.h"   // LodePNG's colour statistics and colour conversion
+#define ZMX_PNG_LOSSY_KERNELS
+#include "zmx_png_lossy.h"   // zopflipng's --lossy_transparent: statistics, the carry scan, the rewrite
 #include "zmx_knobs.h"       // the ZOPFLI_AMD_* switches
 #include "zopfli_amd.h"
 #include "../host/deal.h"

@@ -8,6 +8,9 @@
 // (zmx_png_color_stats_device), LodePNG's choice (png_color_choose.h) and the conversion run on the same hold of the
 // context as the types and the rows; a palette file below 4096 bytes is made a second time as RGB or RGBA, on a second
 // hold, and the smaller file is kept.
+// The _lossy entries put zopflipng's --lossy_8bit and --lossy_transparent in front (zmx_internal_png_lossy_image, on the
+// first hold of the context): the 8-bit and the rewritten image go to a buffer of the call's own, and everything after
+// runs on that instead of the caller's pixels.  The entries without the suffix are these with lossy = 0.
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -100,6 +103,32 @@ struct File {
   }
 };
 
+// What a _lossy entry makes of an image before anything else (zopflipng_lib.cc:415-428): its 8-bit image where the
+// optimize entry has _8BIT and the image is 16 bits deep, the rewrite of the transparent pixels where it has _TRANSPARENT
+// and the image is 8-bit by then and has an alpha channel.  bytes: the buffer either takes, 0 where nothing is made.
+struct LossyPlan {
+  bool to8 = false, transparent = false;
+  size_t bytes = 0;
+};
+
+LossyPlan PlanLossy(const zmx_png_image& im, const Geometry& g, unsigned lossy, bool optimize) {
+  LossyPlan p;
+  p.to8 = optimize && (lossy & ZMX_PNG_LOSSY_8BIT) != 0 && im.bitdepth == 16;
+  p.transparent = (lossy & ZMX_PNG_LOSSY_TRANSPARENT) != 0 && (im.bitdepth == 8 || p.to8) && (im.colortype == 4 || im.colortype == 6);
+  if (p.to8 || p.transparent) p.bytes = g.linebytes / (p.to8 ? 2 : 1) * g.height;
+  return p;
+}
+
+// The rewrite's kernels index pixels with 32 bits, as the colour statistics do.
+int CheckRewritable(const std::string& w, const zmx_png_image& im, const LossyPlan& plan) {
+  if (plan.transparent && static_cast<uint64_t>(im.width) * im.height > 0xffffffffull) {
+    return Refuse(w + ": an image of 2^32 pixels or more with ZMX_PNG_LOSSY_TRANSPARENT");
+  }
+  return 0;
+}
+
+bool LossyOk(unsigned lossy) { return (lossy & ~(ZMX_PNG_LOSSY_TRANSPARENT | ZMX_PNG_LOSSY_8BIT)) == 0; }
+
 int BadStream(const std::string& w) {
   zmx_internal_set_error((w + ": the zlib stream does not fit an IDAT chunk").c_str(), ZMX_ERR_DEVICE);
   return -1;
@@ -107,10 +136,12 @@ int BadStream(const std::string& w) {
 
 }  // namespace
 
-extern "C" int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                                     const unsigned char* predefined, unsigned char** out, size_t* outsize) {
-  const std::string w = "zmx_png_encode_device";
+namespace {
+
+int EncodeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
+              unsigned lossy, unsigned char** out, size_t* outsize) {
   if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
   Geometry g;
   if (CheckImage(w, *image, &g) != 0) return -1;
   if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
@@ -120,13 +151,18 @@ extern "C" int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png
       if (predefined[r] > 4) return Refuse(w + ": predefined type " + std::to_string(predefined[r]) + " of row " + std::to_string(r));
     }
   }
-  DeviceBuffer scan;
+  const LossyPlan plan = PlanLossy(*image, g, lossy, false);
+  if (CheckRewritable(w, *image, plan) != 0) return -1;
+  DeviceBuffer scan, rewritten;
   if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, g.linebytes * g.height, &scan.device) != 0) return -1;
   if (zmx_internal_device_alloc(scan.device, g.scanlines, &scan.p) != 0) return -1;
-  // (the context is held for the types and the rows only)
+  rewritten.device = scan.device;
+  if (plan.bytes != 0 && zmx_internal_device_alloc(scan.device, plan.bytes, &rewritten.p) != 0) return -1;
+  zmx_png_image work = *image;
+  // (the context is held for the rewrite, the types and the rows only)
   const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    return zmx_internal_png_scanlines(ctx, image->d_pixels, g.linebytes, g.height, g.bytewidth, strategy, kBruteWindow,
-                                      predefined, scan.p);
+    if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), image, 0, 1, rewritten.p, &work) != 0) return -1;
+    return zmx_internal_png_scanlines(ctx, work.d_pixels, g.linebytes, g.height, g.bytewidth, strategy, kBruteWindow, predefined, scan.p);
   }, scan.device);
   if (rc != 0) return -1;
   File file;
@@ -137,15 +173,17 @@ extern "C" int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png
   return 0;
 }
 
-extern "C" int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
-                                           unsigned char** out, size_t* outsize) {
-  const std::string w = "zmx_png_encode_device_batch";
+int EncodeBatch(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy, unsigned lossy,
+                unsigned char** out, size_t* outsize) {
   if (n == 0) return 0;
   if (!options || !images || !out || !outsize) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
   if (strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
   if (!StrategyOk(strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
   std::vector<Geometry> g(n);
   std::vector<size_t> start(n + 1, 0);   // where image i's scanlines begin in the one buffer
+  std::vector<size_t> rstart(n + 1, 0);  // and its rewritten pixels in theirs
+  std::vector<LossyPlan> plan(n);
   std::vector<const void*> pixels(n);
   std::vector<size_t> nbytes(n);
   for (size_t i = 0; i < n; ++i) {
@@ -153,17 +191,27 @@ extern "C" int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t 
     if (CheckImage(wi, images[i], &g[i]) != 0) return -1;
     if (g[i].scanlines > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
     start[i + 1] = start[i] + g[i].scanlines;
+    plan[i] = PlanLossy(images[i], g[i], lossy, false);
+    if (CheckRewritable(wi, images[i], plan[i]) != 0) return -1;
+    rstart[i + 1] = rstart[i] + ((plan[i].bytes + 15) & ~static_cast<size_t>(15));
     pixels[i] = images[i].d_pixels;
     nbytes[i] = g[i].linebytes * g[i].height;
   }
-  DeviceBuffer scan;
+  DeviceBuffer scan, rewritten;
   if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &scan.device) != 0) return -1;
   if (zmx_internal_device_alloc(scan.device, start[n], &scan.p) != 0) return -1;
+  rewritten.device = scan.device;
+  if (rstart[n] != 0 && zmx_internal_device_alloc(scan.device, rstart[n], &rewritten.p) != 0) return -1;
   unsigned char* const base = static_cast<unsigned char*>(scan.p);
   // (one hold of a context for all images; a launch set per image: tools/png_device.py measures what that costs)
   const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
     for (size_t i = 0; i < n; ++i) {
-      if (zmx_internal_png_scanlines(ctx, pixels[i], g[i].linebytes, g[i].height, g[i].bytewidth, strategy, kBruteWindow, nullptr,
+      zmx_png_image work = images[i];
+      if (plan[i].bytes != 0 &&
+          zmx_internal_png_lossy_image(ctx, w.c_str(), &images[i], 0, 1, static_cast<unsigned char*>(rewritten.p) + rstart[i], &work) != 0) {
+        return -1;
+      }
+      if (zmx_internal_png_scanlines(ctx, work.d_pixels, g[i].linebytes, g[i].height, g[i].bytewidth, strategy, kBruteWindow, nullptr,
                                      base + start[i]) != 0) {
         return -1;
       }
@@ -195,6 +243,25 @@ extern "C" int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t 
   }
   for (size_t i = 0; i < n; ++i) files[i].GiveTo(&out[i], &outsize[i]);
   return 0;
+}
+
+}  // namespace
+
+extern "C" int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                     const unsigned char* predefined, unsigned char** out, size_t* outsize) {
+  return EncodeOne("zmx_png_encode_device", options, image, strategy, predefined, 0, out, outsize);
+}
+extern "C" int zmx_png_encode_device_lossy(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                           const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  return EncodeOne("zmx_png_encode_device_lossy", options, image, strategy, predefined, lossy, out, outsize);
+}
+extern "C" int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                           unsigned char** out, size_t* outsize) {
+  return EncodeBatch("zmx_png_encode_device_batch", options, n, images, strategy, 0, out, outsize);
+}
+extern "C" int zmx_png_encode_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                                 unsigned lossy, unsigned char** out, size_t* outsize) {
+  return EncodeBatch("zmx_png_encode_device_batch_lossy", options, n, images, strategy, lossy, out, outsize);
 }
 
 // ---- zmx_png_optimize_device, zmx_png_optimize_device_batch: the colour mode reduced first (png_color_choose.h)
@@ -243,10 +310,12 @@ File& Smaller(File& first, File& second) { return second.size < first.size ? sec
 
 }  // namespace
 
-extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                                       const unsigned char* predefined, unsigned char** out, size_t* outsize) {
-  const std::string w = "zmx_png_optimize_device";
+namespace {
+
+int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
+                unsigned lossy, unsigned char** out, size_t* outsize) {
   if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
   Geometry g;
   if (CheckReducible(w, *image, &g) != 0) return -1;
   if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
@@ -259,19 +328,23 @@ extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_p
   int device = -1;
   if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, g.linebytes * g.height, &device) != 0) return -1;
   const uint64_t numpixels = static_cast<uint64_t>(image->width) * image->height;
+  const LossyPlan plan = PlanLossy(*image, g, lossy, true);
   Reduced r;
-  DeviceBuffer scan;
-  scan.device = device;
-  // (the context is held for the statistics, the conversion, the types and the rows only)
+  DeviceBuffer scan, rewritten;
+  scan.device = rewritten.device = device;
+  if (plan.bytes != 0 && zmx_internal_device_alloc(device, plan.bytes, &rewritten.p) != 0) return -1;
+  zmx_png_image work = *image;   // what is encoded: the caller's image, or its 8-bit or rewritten image in `rewritten`
+  // (the context is held for the rewrite, the statistics, the conversion, the types and the rows only)
   int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    if (StatsAndMode(ctx, *image, &r) != 0) return -1;
+    if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), image, plan.to8, plan.transparent, rewritten.p, &work) != 0) return -1;
+    if (StatsAndMode(ctx, work, &r) != 0) return -1;
     if (zmx_internal_device_alloc(device, r.scanlines, &scan.p) != 0) return -1;
-    return zmx_internal_png_reduced_scanlines(ctx, image, r.as_is ? nullptr : &r.mode, strategy, kBruteWindow, predefined, scan.p);
+    return zmx_internal_png_reduced_scanlines(ctx, &work, r.as_is ? nullptr : &r.mode, strategy, kBruteWindow, predefined, scan.p);
   }, device);
   if (rc != 0) return -1;
   File file;
-  if (r.as_is) file.Begin(*image);
-  else file.BeginReduced(*image, r.mode);
+  if (r.as_is) file.Begin(work);
+  else file.BeginReduced(work, r.mode);
   if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan.p, r.scanlines, &file.bytes, &file.size) != 0) return -1;
   if (!file.Close()) return BadStream(w);
   File second;
@@ -279,17 +352,17 @@ extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_p
     // zopflipng's second try: without the palette's overhead
     zmx_png_color_mode retry;
     zamd::PngRetryMode(r.stats, numpixels, &retry);
-    const bool as_is = SameMode(*image, retry);
-    const size_t scanlines = ScanlinesIn(*image, retry);
+    const bool as_is = SameMode(work, retry);
+    const size_t scanlines = ScanlinesIn(work, retry);
     DeviceBuffer scan2;
     scan2.device = device;
     if (zmx_internal_device_alloc(device, scanlines, &scan2.p) != 0) return -1;
     rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-      return zmx_internal_png_reduced_scanlines(ctx, image, as_is ? nullptr : &retry, strategy, kBruteWindow, predefined, scan2.p);
+      return zmx_internal_png_reduced_scanlines(ctx, &work, as_is ? nullptr : &retry, strategy, kBruteWindow, predefined, scan2.p);
     }, device);
     if (rc != 0) return -1;
-    if (as_is) second.Begin(*image);
-    else second.BeginReduced(*image, retry);
+    if (as_is) second.Begin(work);
+    else second.BeginReduced(work, retry);
     if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines, &second.bytes, &second.size) != 0) return -1;
     if (!second.Close()) return BadStream(w);
     Smaller(file, second).GiveTo(out, outsize);
@@ -297,6 +370,17 @@ extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_p
   }
   file.GiveTo(out, outsize);
   return 0;
+}
+
+}  // namespace
+
+extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                       const unsigned char* predefined, unsigned char** out, size_t* outsize) {
+  return OptimizeOne("zmx_png_optimize_device", options, image, strategy, predefined, 0, out, outsize);
+}
+extern "C" int zmx_png_optimize_device_lossy(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                             const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  return OptimizeOne("zmx_png_optimize_device_lossy", options, image, strategy, predefined, lossy, out, outsize);
 }
 
 namespace {
@@ -332,23 +416,35 @@ int CompressInto(const ZopfliOptions* options, const std::string& w, const zmx_p
 
 }  // namespace
 
-extern "C" int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
-                                             unsigned char** out, size_t* outsize) {
-  const std::string w = "zmx_png_optimize_device_batch";
+namespace {
+
+int OptimizeBatch(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* callers, int strategy, unsigned lossy,
+                  unsigned char** out, size_t* outsize) {
   if (n == 0) return 0;
-  if (!options || !images || !out || !outsize) return Refuse(w + ": null argument");
+  if (!options || !callers || !out || !outsize) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
   if (strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
   if (!StrategyOk(strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
   std::vector<const void*> pixels(n);
   std::vector<size_t> nbytes(n);
+  std::vector<LossyPlan> plan(n);
+  std::vector<size_t> rstart(n + 1, 0);   // where image i's 8-bit or rewritten pixels begin in their buffer
   for (size_t i = 0; i < n; ++i) {
     Geometry g;
-    if (CheckReducible(w + ": image " + std::to_string(i), images[i], &g) != 0) return -1;
-    pixels[i] = images[i].d_pixels;
+    if (CheckReducible(w + ": image " + std::to_string(i), callers[i], &g) != 0) return -1;
+    pixels[i] = callers[i].d_pixels;
     nbytes[i] = g.linebytes * g.height;
+    plan[i] = PlanLossy(callers[i], g, lossy, true);
+    rstart[i + 1] = rstart[i] + ((plan[i].bytes + 15) & ~static_cast<size_t>(15));
   }
   int device = -1;
   if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &device) != 0) return -1;
+  DeviceBuffer rewritten;
+  rewritten.device = device;
+  if (rstart[n] != 0 && zmx_internal_device_alloc(device, rstart[n], &rewritten.p) != 0) return -1;
+  // what is encoded: the callers' images, or their 8-bit or rewritten images in `rewritten`
+  std::vector<zmx_png_image> work(callers, callers + n);
+  const zmx_png_image* const images = work.data();
   // the first files: statistics for all, one buffer, conversion and rows image by image, on one hold of a context
   std::vector<Reduced> r(n);
   std::vector<size_t> all(n), start(n + 1, 0);
@@ -358,6 +454,10 @@ extern "C" int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_
   scan.device = device;
   int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
     for (size_t i = 0; i < n; ++i) {
+      if (plan[i].bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), &callers[i], plan[i].to8, plan[i].transparent,
+                                                             static_cast<unsigned char*>(rewritten.p) + rstart[i], &work[i]) != 0) {
+        return -1;
+      }
       if (StatsAndMode(ctx, images[i], &r[i]) != 0) return -1;
       if (r[i].scanlines > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
       start[i + 1] = start[i] + r[i].scanlines;
@@ -417,4 +517,15 @@ extern "C" int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_
   for (size_t k = 0; k < again.size(); ++k) kept[again[k]] = &Smaller(files[again[k]], seconds[k]);
   for (size_t i = 0; i < n; ++i) kept[i]->GiveTo(&out[i], &outsize[i]);
   return 0;
+}
+
+}  // namespace
+
+extern "C" int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                             unsigned char** out, size_t* outsize) {
+  return OptimizeBatch("zmx_png_optimize_device_batch", options, n, images, strategy, 0, out, outsize);
+}
+extern "C" int zmx_png_optimize_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                                   unsigned lossy, unsigned char** out, size_t* outsize) {
+  return OptimizeBatch("zmx_png_optimize_device_batch_lossy", options, n, images, strategy, lossy, out, outsize);
 }

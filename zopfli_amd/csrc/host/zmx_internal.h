@@ -117,6 +117,16 @@ int zmx_internal_png_scanlines(zmx_ctx* ctx, const void* d_image, size_t linebyt
 int zmx_internal_png_reduced_scanlines(zmx_ctx* ctx, const zmx_png_image* image, const zmx_png_color_mode* mode, int strategy,
                                        unsigned windowsize, const unsigned char* predefined, void* d_out);
 
+// ---- zopflipng's lossy options in front of the two (png_encode.cc: the _lossy entries)
+// What the entries encode instead of `image`: with `to8` (a 16-bit image) its 8-bit image in the same colour type
+// (k_png_convert), with `transparent` zmx_png_lossy_transparent_device's rewrite of that, or of the image itself — both into
+// d_buf, height * width * channels * (to8 ? 1 : bitdepth / 8) bytes of the context's device that the caller owns.  *work
+// is `image` with the pointer and the depth of what was made; where nothing had to be rewritten (no transparent pixel) it
+// still points at the caller's pixels.  The image is checked as zmx_png_color_stats_device checks its own.  0, or -1 with
+// the error set, its message starting with `who`, the entry's name.
+int zmx_internal_png_lossy_image(zmx_ctx* ctx, const char* who, const zmx_png_image* image, int to8, int transparent, void* d_buf,
+                                 zmx_png_image* work);
+
 // ---- for tests and tools
 // The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
 // (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing); else 0.  For
@@ -129,6 +139,9 @@ ZMX_INTERNAL_EXPORT double zmx_internal_png_rows_ms(void);
 // The same for the calling thread's last zmx_png_color_stats_device and zmx_png_convert_device: k_png_color_stats,
 // k_png_color_key (0: not launched), k_png_convert.  For tools/png_reduce.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_png_color_ms(double out[3]);
+// The same for the calling thread's last zmx_png_lossy_transparent_device: k_png_lossy_stats, k_png_lossy_carry,
+// k_png_lossy_fill (0: not launched).  For tools/png_lossy.py.
+ZMX_INTERNAL_EXPORT void zmx_internal_png_lossy_ms(double out[3]);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
 // squeeze run computes them — *wmax, *tiemask —, no device involved.
 ZMX_INTERNAL_EXPORT void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask);
