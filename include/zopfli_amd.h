@@ -421,8 +421,14 @@ int zmx_png_filter_rows_device(zmx_ctx* ctx, const void* d_image, size_t linebyt
  * colour type other than 0, 2, 4, 6, a bit depth other than 8 or 16, an unknown strategy, _PREDEFINED without types or
  * with a type above 4, and what zmx_png_filter_rows_device refuses of the pixels' pointer.  Any later failure leaves them
  * unchanged as well.
- * Out of scope: palette input, interlace, ancillary chunks, zopflipng's automatic strategy trial (libzopflipng_amd.so
- * does those, from a file), a PNG left in device memory.  Colour-type reduction is zmx_png_optimize_device's. */
+ * `strategy` may also be ZMX_PNG_FILTER_AUTO (further down): zopflipng's own choice, made by
+ * zmx_png_choose_strategy_device(reduce_color = 0) on the same hold of the context, after the lossy rewrite where one is
+ * asked for; the file is then the one zopflipng --keepcolortype --always_zopflify writes with NO --filters for an input
+ * whose rows carry filter type 0 — or, where `predefined` is given, the types at `predefined` (the eighth trial; if it
+ * wins, the file is _PREDEFINED's).
+ * Out of scope: palette input, interlace, ancillary chunks (libzopflipng_amd.so does those, from a file — its own strategy
+ * trials still run LodePNG on host threads), a PNG left in device memory.  Colour-type reduction is
+ * zmx_png_optimize_device's. */
 typedef struct zmx_png_image {
   const void* d_pixels;  /* height rows of linebytes bytes, PNG byte order (16-bit samples big-endian), rows back to back */
   uint32_t width, height, colortype /* 0, 2, 4, 6 */, bitdepth /* 8, 16 */;
@@ -434,9 +440,47 @@ int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png_image* ima
  * or three launches each) into ONE buffer, and ONE zmx_compress_device_batch(ZOPFLI_FORMAT_ZLIB) over its slices makes
  * the streams, so icons and tiles share the table builds and squeeze runs of one large call.  The images lie on one
  * device.  _PREDEFINED is refused; otherwise the refusals are the single call's, for any image, and no out[i] is changed
- * by a call that fails.  n = 0 returns 0. */
+ * by a call that fails.  n = 0 returns 0.  ZMX_PNG_FILTER_AUTO chooses image by image (seven trials each: a batch passes
+ * no predefined types) before the one zmx_compress_device_batch. */
 int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
                                 unsigned char** out, size_t* outsize);
+
+/* -------- zopflipng's automatic filter-strategy choice (its default: no --filters)
+ *
+ * The length lodepng_zlib_compress returns for each of n buffers in device memory under LodePNG's default settings
+ * (btype 2, use_lz77 1, minmatch 3, nicematch 128, lazymatching 1) with window `windowsize`: zlib_bytes[i] is
+ * 2 + ceil(deflate bits / 8) + 4 for d_in[i][0, insize[i]).  Only the size is made, never the stream.  The kernels of
+ * device/zmx_png_lodeflate.h parse all buffers of the call side by side — LodePNG's deflate blocks of insize / 8 + 8 bytes
+ * within [65536, 262144], its hash chains with their stale slots, its lazy matching — and bring every block down to its
+ * 286 + 30 symbol counts and extra bits; host/png_lodeflate_size.h makes LodePNG's dynamic trees of those and adds up the
+ * bits.  A few KB per deflate block come down, no byte of the buffers does.  The scratch is 12 bytes per input byte and
+ * 257 KiB per 262144 bytes (and per buffer).
+ * Refused before any launch (ZMX_ERR_REFUSED), zlib_bytes untouched: a null argument, n = 0, a buffer of 0 bytes, a window
+ * LodePNG refuses (0, not a power of two, above 32768), more than 2^40 bytes in all, and what zmx_png_filter_rows_device
+ * refuses of a pointer.  Any later failure leaves zlib_bytes untouched as well.  Synchronous; the caller synchronises the
+ * streams that produced the buffers. */
+int zmx_png_deflate_sizes_device(zmx_ctx* ctx, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize,
+                                 uint64_t* zlib_bytes);
+
+/* zopflipng's AutoChooseFilterStrategy (zopflipng_lib.cc:270-305) for an image in device memory: the PNG file LodePNG's
+ * own encoder would write (its deflate at window 8192) is sized under the strategies 0, 1, 2, 3, 4, MINSUM, ENTROPY and
+ * PREDEFINED in that order — never BRUTE — and *strategy is the ZMX_PNG_FILTER_* of the first strictly smallest file;
+ * file_bytes[k] is trial k's file size.  The rows of all trials go into one buffer of the call's own
+ * (zmx_png_filter_types_device's and zmx_png_filter_rows_device's kernels) and ONE zmx_png_deflate_sizes_device sizes
+ * them; the container's bytes for the mode are added on the host.
+ *   reduce_color = 0  the image's own colour type and depth (zopflipng --keepcolortype)
+ *   reduce_color = 1  zmx_png_choose_color's mode of the image's statistics; as in zopflipng's TryOptimize, a palette
+ *                     trial whose file is below 4096 bytes is sized as RGB / RGBA at 8 bits as well and counts with the
+ *                     smaller of its two sizes
+ *   predefined        `height` host bytes of at most 4 each: the eighth trial.  Null: that trial is skipped and
+ *                     file_bytes[7] = 0 — zopflipng's answer for an input PNG whose rows all carry filter type 0, whose
+ *                     predefined trial repeats trial 0 and cannot win.
+ * Refusals are zmx_png_optimize_device's of the image (with reduce_color = 0: zmx_png_encode_device's), a null context,
+ * strategy or file_bytes, a predefined type above 4; *strategy and file_bytes are written by a call that succeeds only.
+ * Synchronous; no pixel visits the host. */
+#define ZMX_PNG_FILTER_AUTO 10 /* (9 is no strategy and stays refused) */
+int zmx_png_choose_strategy_device(zmx_ctx* ctx, const zmx_png_image* image, int reduce_color,
+                                   const unsigned char* predefined /* may be null */, int* strategy, uint64_t file_bytes[8]);
 
 /* -------- colour-type reduction: what zopflipng does to an image without --keepcolortype
  *
@@ -498,9 +542,11 @@ int zmx_png_convert_device(zmx_ctx* ctx, const zmx_png_image* image, const zmx_p
  * Where the chosen mode is the image's own nothing is converted and the file is zmx_png_encode_device's.  No pixel visits
  * the host.  Conventions, refusals and failure behaviour are zmx_png_encode_device's; an image of 2^32 pixels or more
  * is refused as well.
- * Out of scope: palette INPUT, interlace, ancillary chunks, zopflipng's automatic strategy trial (libzopflipng_amd.so
- * does those, from a file), a PNG left in device memory.  --lossy_transparent and --lossy_8bit are the _lossy entries'
- * further down. */
+ * ZMX_PNG_FILTER_AUTO: zmx_png_choose_strategy_device(reduce_color = 1) chooses on the same hold of the context, with the
+ * statistics the entry has taken; both tries of a small palette file are made with the chosen strategy, as zopflipng's
+ * are.  The file is the one zopflipng --always_zopflify writes with no --filters.
+ * Out of scope: palette INPUT, interlace, ancillary chunks (libzopflipng_amd.so does those, from a file), a PNG left in
+ * device memory.  --lossy_transparent and --lossy_8bit are the _lossy entries' further down. */
 int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
                             const unsigned char* predefined, unsigned char** out, size_t* outsize);
 /* n images in one call: every file is the single call's.  Statistics and conversion run image by image on one hold of a

@@ -372,9 +372,10 @@ class PngImage(ctypes.Structure):
                 ("colortype", ctypes.c_uint32), ("bitdepth", ctypes.c_uint32)]
 
 
-# ZMX_PNG_FILTER_*: zopflipng's --filters= letters, and "p" for predefined types
-PNG_STRATEGIES = {"0": 0, "1": 1, "2": 2, "3": 3, "4": 4, "m": 5, "e": 6, "b": 7, "p": 8}
+# ZMX_PNG_FILTER_*: zopflipng's --filters= letters, "p" for predefined types, "auto" for zopflipng's own choice
+PNG_STRATEGIES = {"0": 0, "1": 1, "2": 2, "3": 3, "4": 4, "m": 5, "e": 6, "b": 7, "p": 8, "auto": 10}
 PNG_FILTER_MINSUM, PNG_FILTER_ENTROPY, PNG_FILTER_BRUTE, PNG_FILTER_PREDEFINED = 5, 6, 7, 8
+PNG_FILTER_AUTO = 10   # zopflipng without --filters: the strategy of its trials (Context.png_choose_strategy_device)
 _PNG_COLORTYPE = {1: 0, 2: 4, 3: 2, 4: 6}   # channels -> grey, grey + alpha, RGB, RGBA
 
 
@@ -428,7 +429,8 @@ def png_encode_device(image, strategy="e", options=None, predefined=None, lib=No
     else 5).  `image`: a contiguous uint8 tensor (H, W) grey, (H, W, 2) grey + alpha, (H, W, 3) RGB or (H, W, 4) RGBA — a
     torch tensor's current stream is synchronised first — or (pointer, width, height, colortype, bitdepth) for any of
     the colour types 0, 2, 4, 6 at 8 or 16 bits (16-bit samples big-endian).  `strategy`: one of "0" "1" "2" "3" "4" "m"
-    "e" "b", or "p" with `predefined`, a filter type (0 .. 4) for every row.  `lossy_transparent`, `lossy_8bit`: zopflipng's
+    "e" "b", "p" with `predefined`, a filter type (0 .. 4) for every row, or "auto" (PNG_FILTER_AUTO): zopflipng's own
+    choice, the file it writes without --filters (`predefined`, where given, is the eighth trial).  `lossy_transparent`, `lossy_8bit`: zopflipng's
     --lossy_transparent and --lossy_8bit (zmx_png_encode_device_lossy; under --keepcolortype the second does nothing and
     the first nothing to a 16-bit image).  Returns the file's bytes.  Raises ValueError for a tensor that is no image,
     RuntimeError with the library's message when the library refuses or fails."""
@@ -731,6 +733,39 @@ class Context:
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, img or None, linebytes, height, bytewidth, typ or None, dst or None, capacity),
                     "zmx_png_filter_rows_device")
+
+    def png_deflate_sizes_device(self, bufs, windowsize=8192):
+        """zmx_png_deflate_sizes_device: the length LodePNG's own zlib encoder (default settings, window `windowsize`)
+        gives for every buffer of `bufs` (tensors or (pointer, nbytes) pairs in memory of this context's device), all
+        sized in one pass over the device: a list of integers."""
+        ptrs, sizes = _device_ranges(bufs)
+        n = len(ptrs)
+        out = (ctypes.c_uint64 * max(n, 1))()
+        fn = self.lib.zmx_png_deflate_sizes_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint,
+                       ctypes.POINTER(ctypes.c_uint64)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes), int(windowsize), out),
+                    "zmx_png_deflate_sizes_device")
+        return [int(out[i]) for i in range(n)]
+
+    def png_choose_strategy_device(self, image, reduce_color=False, predefined=None):
+        """zmx_png_choose_strategy_device: zopflipng's choice of the filter strategy for the image (`image` as
+        png_encode_device takes it; `reduce_color`: without --keepcolortype; `predefined`: a type per row for the eighth
+        trial): (the ZMX_PNG_FILTER_* number, the eight trial file sizes, 0 for a trial that was not run)."""
+        im = _png_image(image)
+        types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
+        if types is not None and len(types) != im.height:
+            raise ValueError(f"{len(types)} predefined types for {im.height} rows")
+        strategy = ctypes.c_int(-1)
+        sizes = (ctypes.c_uint64 * 8)()
+        fn = self.lib.zmx_png_choose_strategy_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int),
+                       ctypes.POINTER(ctypes.c_uint64)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, ctypes.byref(im), 1 if reduce_color else 0, types, ctypes.byref(strategy), sizes),
+                    "zmx_png_choose_strategy_device")
+        return int(strategy.value), [int(v) for v in sizes]
 
     def png_color_stats_device(self, image):
         """zmx_png_color_stats_device: LodePNG's colour statistics of an image in memory of this context's device

@@ -1,8 +1,9 @@
 // Driver part: LodePNG's filter choices on the device (zmx_png.h, zmx_png_brute.h) and the filtered scanlines
 // (zmx_png_rows.h).  Holds zmx_png_filter_types, zmx_png_filter_types_brute, their device-image form
 // zmx_png_filter_types_device, zmx_png_filter_rows_device and the encoder's zmx_internal_png_scanlines; the colour
-// statistics and conversion (zmx_png_color.h); zopflipng's --lossy_transparent (zmx_png_lossy.h).  Needs
-// drv_context.h (zmx_ctx, PoolScope) and drv_input.h (CheckDevicePointer).
+// statistics and conversion (zmx_png_color.h); zopflipng's --lossy_transparent (zmx_png_lossy.h); LodePNG's zlib size of
+// device buffers and the rows of zopflipng's strategy trials (zmx_png_lodeflate.h).  Needs drv_context.h (zmx_ctx,
+// PoolScope) and drv_input.h (CheckDevicePointer).
 #pragma once
 
 // an image the kernels can index with 32 bits: rows of `linebytes`, at most `max_height` of them, pixels of 1 .. 8 bytes
@@ -605,6 +606,163 @@ int zmx_internal_png_scanlines(zmx_ctx* c, const void* d_image, size_t linebytes
     rc = PngRowsOnDevice(c, &tmp, who, static_cast<const u8*>(d_image), linebytes, height, bytewidth, d_types, static_cast<u8*>(d_out));
   }
   if (rc != 0) (void)hipStreamSynchronize(c->stream);   // what was queued may still read `tmp`'s arrays
+  return rc;
+}
+}  // extern "C"
+
+// ---- LodePNG's zlib size of device buffers (zmx_png_lodeflate.h, host/png_lodeflate_size.h)
+static thread_local double g_png_lo_ms[6] = {0, 0, 0, 0, 0, 0};   // k_png_lo_hash, _links, _ask, _keep, _search, _parse (zmx_internal_png_lodeflate_ms)
+
+// The six kernels over buffers the caller has checked, the counts read, the sizes made.  Drains the context's stream.
+static int PngLoSizesOnDevice(zmx_ctx* c, PoolScope* tmp, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize,
+                              uint64_t* zlib_bytes) {
+  const zamd::LoPlan plan = zamd::LoMakePlan(n, d_in, insize, zamd::kLoTileLen);
+  const size_t ntiles = plan.tiles.size(), nblocks = plan.blocks.size();
+  if (ntiles > 0x7fffffffu || nblocks > 0x7fffffffu) return FailMsg("zmx_png_deflate_sizes_device: too many tiles in one call");
+  zamd::LoBuf* d_bufs = nullptr;
+  zamd::LoTile* d_tiles = nullptr;
+  zamd::LoTile* d_blocks = nullptr;
+  zamd::LoParams P;
+  HIPCHK(tmp->Upload(&d_bufs, plan.bufs.data(), n, "d_png_lo_bufs"));
+  HIPCHK(tmp->Upload(&d_tiles, plan.tiles.data(), ntiles, "d_png_lo_tiles"));
+  HIPCHK(tmp->Upload(&d_blocks, plan.blocks.data(), nblocks, "d_png_lo_blocks"));
+  HIPCHK(tmp->AllocT(&P.HC, static_cast<size_t>(plan.positions), "d_png_lo_hc"));
+  HIPCHK(tmp->AllocT(&P.ZC, static_cast<size_t>(plan.positions), "d_png_lo_zc"));
+  HIPCHK(tmp->AllocT(&P.LD, static_cast<size_t>(plan.positions), "d_png_lo_ld"));
+  HIPCHK(tmp->AllocT(&P.tables, ntiles * static_cast<size_t>(zamd::kLoTableLen), "d_png_lo_tables"));
+  HIPCHK(tmp->AllocT(&P.counts, nblocks * static_cast<size_t>(zamd::kLoCountWords), "d_png_lo_counts"));
+  P.bufs = d_bufs;
+  P.tiles = d_tiles;
+  P.blocks = d_blocks;
+  P.window = windowsize;
+  P.ntiles = static_cast<u32>(ntiles);
+  P.nblocks = static_cast<u32>(nblocks);
+  P.tile_len = zamd::kLoTileLen;
+  HIPCHK(hipMemsetAsync(P.tables, 0, ntiles * static_cast<size_t>(zamd::kLoTableLen) * sizeof(u32), c->stream));
+  PngLossyTimer timer{c, KernelTiming()};
+  const u32 gx = (plan.longest_tile + zamd::kLoThreads - 1) / zamd::kLoThreads;
+  // a per-position kernel over all tiles, at most 65535 rows of workgroups a launch
+#define PNG_LO_PER_POSITION(kernel, slot)                                                                                       \
+  do {                                                                                                                           \
+    HIPCHK(timer.Begin());                                                                                                       \
+    for (size_t t0 = 0; t0 < ntiles; t0 += 65535) {                                                                              \
+      const u32 rows = static_cast<u32>(std::min<size_t>(65535, ntiles - t0));                                                   \
+      hipLaunchKernelGGL(kernel, dim3(gx, rows), dim3(zamd::kLoThreads), 0, c->stream, P, static_cast<u32>(t0));                 \
+      KCHK(c, #kernel);                                                                                                          \
+    }                                                                                                                            \
+    HIPCHK(timer.End(&g_png_lo_ms[slot]));                                                                                       \
+  } while (0)
+  PNG_LO_PER_POSITION(k_png_lo_hash, 0);
+  HIPCHK(timer.Begin());
+  hipLaunchKernelGGL(k_png_lo_links, dim3(static_cast<u32>(ntiles)), dim3(zamd::kLoThreads), 0, c->stream, P);
+  KCHK(c, "k_png_lo_links");
+  HIPCHK(timer.End(&g_png_lo_ms[1]));
+  PNG_LO_PER_POSITION(k_png_lo_ask, 2);
+  PNG_LO_PER_POSITION(k_png_lo_keep, 3);
+  PNG_LO_PER_POSITION(k_png_lo_search, 4);
+#undef PNG_LO_PER_POSITION
+  HIPCHK(timer.Begin());
+  hipLaunchKernelGGL(k_png_lo_parse, dim3(static_cast<u32>(nblocks)), dim3(64), 0, c->stream, P);
+  KCHK(c, "k_png_lo_parse");
+  HIPCHK(timer.End(&g_png_lo_ms[5]));
+  std::vector<u32> counts(nblocks * static_cast<size_t>(zamd::kLoCountWords));
+  HIPCHK(hipMemcpyAsync(counts.data(), P.counts, counts.size() * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  std::vector<zamd::LoBlockCounts> blocks(nblocks);
+  for (size_t b = 0; b < nblocks; ++b) {
+    const u32* w = counts.data() + b * zamd::kLoCountWords;
+    std::memcpy(blocks[b].ll, w, sizeof(blocks[b].ll));
+    std::memcpy(blocks[b].d, w + zamd::kLoNumLl, sizeof(blocks[b].d));
+    blocks[b].extra_bits = static_cast<uint64_t>(w[316]) | (static_cast<uint64_t>(w[317]) << 32);
+  }
+  for (size_t i = 0; i < n; ++i) {
+    zlib_bytes[i] = zamd::LoZlibBytes(blocks.data() + plan.first_block[i], plan.first_block[i + 1] - plan.first_block[i]);
+  }
+  return 0;
+}
+
+extern "C" {
+void zmx_internal_png_lodeflate_ms(double out[6]) {
+  for (int k = 0; k < 6; ++k) out[k] = g_png_lo_ms[k];
+}
+
+int zmx_png_deflate_sizes_device(zmx_ctx* c, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize,
+                                 uint64_t* zlib_bytes) {
+  const char* who = "zmx_png_deflate_sizes_device";
+  const std::string w(who);
+  for (double& ms : g_png_lo_ms) ms = 0;
+  if (!c) return FailMsg(w + ": no context");
+  if (n == 0 || !d_in || !insize || !zlib_bytes) return FailMsg(w + ": a null argument or no buffer");
+  if (!PngWindowOk(windowsize)) return FailMsg(w + ": the window must be a power of two of at most 32768");
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (insize[i] == 0) return FailMsg(w + ": buffer " + std::to_string(i) + " has no bytes");
+    if (!d_in[i]) return FailMsg(w + ": buffer " + std::to_string(i) + " is a null pointer");
+    total += insize[i];
+    if (total > (1ull << 40)) return FailMsg(w + ": more than 2^40 bytes in one call");
+  }
+  for (size_t i = 0; i < n; ++i) {
+    int device = -1;
+    if (const int rc = CheckDevicePointer(who, d_in[i], insize[i], &device)) return rc;
+    if (device != c->device) return FailMsg(w + ": memory of another device than the context's");
+  }
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  std::vector<uint64_t> sizes(n);
+  const int rc = PngLoSizesOnDevice(c, &tmp, n, d_in, insize, windowsize, sizes.data());
+  // (what was queued uses the scratch arrays: drained before `tmp` gives them back, on the failing paths too)
+  const hipError_t e = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  HIPCHK(e);
+  std::copy(sizes.begin(), sizes.end(), zlib_bytes);
+  return 0;
+}
+
+// zmx_png_choose_strategy_device's device part (host/png_encode.cc): the image in `mode` (null: as it is), converted
+// once, then the rows of trial k = 0 .. ntrials - 1 at d_out + k * scanlines — zopflipng's order: the types 0 .. 4, MINSUM,
+// ENTROPY, and for ntrials = 8 the `height` host bytes at `predefined` (checked by the caller).  d_out is a buffer of the
+// caller's own on the context's device.  The image is checked as the device entries check theirs.
+int zmx_internal_png_trial_scanlines(zmx_ctx* c, const char* who, const zmx_png_image* image, const zmx_png_color_mode* mode,
+                                     const unsigned char* predefined, int ntrials, void* d_out) {
+  zamd::PngColorImage I;
+  size_t nbytes = 0;
+  if (const int rc = PngColorImageOf(who, image, &I, &nbytes)) return rc;
+  if (mode && !zamd::PngModeOk(*mode, I.bitdepth)) return FailMsg(std::string(who) + ": no mode this image converts to");
+  int img_device = -1;
+  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (img_device != c->device) return FailMsg(std::string(who) + ": the image is memory of another device than the context's");
+  const u64 rowbytes = mode ? zamd::PngConvRowBytes(I.width, mode->colortype, mode->bitdepth) : nbytes / I.height;
+  const u32 bpp = mode ? zamd::PngConvBpp(mode->colortype, mode->bitdepth) : 8u * zamd::PngColorPixelBytes(I.colortype, I.bitdepth);
+  const size_t bytewidth = bpp < 8 ? 1 : bpp / 8, height = I.height;
+  if (!PngGeometryOk(rowbytes, height, 0x7fffffffu, bytewidth)) return FailMsg(std::string(who) + ": bad geometry");
+  const size_t scanlines = height * (static_cast<size_t>(rowbytes) + 1);
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  const u8* d_img = static_cast<const u8*>(image->d_pixels);
+  int rc = 0;
+  if (mode) {
+    u8* d_conv = nullptr;
+    HIPCHK(tmp.AllocT(&d_conv, static_cast<size_t>(rowbytes) * height, "d_png_converted"));
+    rc = PngConvertOnDevice(c, &tmp, who, I, *mode, d_conv);
+    d_img = d_conv;
+  }
+  u8* d_types = nullptr;
+  if (rc == 0) {
+    const hipError_t e = tmp.AllocT(&d_types, height, "d_png_types");
+    if (e != hipSuccess) rc = Fail("AllocT(d_png_types)", e, __FILE__, __LINE__);
+  }
+  for (int k = 0; rc == 0 && k < ntrials; ++k) {
+    if (k == 7) {
+      const hipError_t e = hipMemcpyAsync(d_types, predefined, height, hipMemcpyHostToDevice, c->stream);
+      if (e != hipSuccess) rc = Fail("hipMemcpyAsync(d_png_types)", e, __FILE__, __LINE__);
+    } else {
+      rc = PngTypesOnDevice(c, &tmp, who, d_img, static_cast<size_t>(rowbytes), height, bytewidth, k, 0, d_types);
+    }
+    // (drains the stream whichever way it returns once the kernel is queued: d_types is free for the next trial)
+    if (rc == 0) rc = PngRowsOnDevice(c, &tmp, who, d_img, static_cast<size_t>(rowbytes), height, bytewidth, d_types,
+                                      static_cast<u8*>(d_out) + static_cast<size_t>(k) * scanlines);
+  }
+  if (rc != 0) (void)hipStreamSynchronize(c->stream);
   return rc;
 }
 }  // extern "C"

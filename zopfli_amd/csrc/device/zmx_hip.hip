@@ -46,11 +46,14 @@
 #include "zmx_png_color.h"   // LodePNG's colour statistics and colour conversion
 #define ZMX_PNG_LOSSY_KERNELS
 #include "zmx_png_lossy.h"   // zopflipng's --lossy_transparent: statistics, the carry scan, the rewrite
+#define ZMX_PNG_LODEFLATE_KERNELS
+#include "zmx_png_lodeflate.h"   // LodePNG's own deflate, sized: hash, links over tiles, search, the lazy parse per block
 #include "zmx_knobs.h"       // the ZOPFLI_AMD_* switches
 #include "zopfli_amd.h"
 #include "../host/deal.h"
 #include "../host/entry_checks.h"
 #include "../host/png_color_choose.h"
+#include "../host/png_lodeflate_size.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
 
@@ -65,6 +68,6 @@
 #include "drv_stores.h"      // store download, verify, encode
 #include "drv_bitjoin.h"     // output that stays on the device: the bit join, the bit writer without the way down
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
-#include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion
+#include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion, LodePNG's zlib sizes
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries
 #include "drv_probes.h"      // the parity probes: digest, longest match, hash links, length array, DP rows

@@ -11,6 +11,9 @@
 // The _lossy entries put zopflipng's --lossy_8bit and --lossy_transparent in front (zmx_internal_png_lossy_image, on the
 // first hold of the context): the 8-bit and the rewritten image go to a buffer of the call's own, and everything after
 // runs on that instead of the caller's pixels.  The entries without the suffix are these with lossy = 0.
+// ZMX_PNG_FILTER_AUTO is zopflipng's own choice of the strategy (zmx_png_choose_strategy_device, further down): made on the
+// first hold of the context, after the rewrite and the 8-bit conversion, image by image in the batches; everything after
+// is the entry's path with the strategy chosen.
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -58,8 +61,18 @@ int CheckImage(const std::string& w, const zmx_png_image& im, Geometry* g) {
 }
 
 bool StrategyOk(int strategy, bool predefined_allowed) {
-  return (strategy >= ZMX_PNG_FILTER_ZERO && strategy <= ZMX_PNG_FILTER_BRUTE) ||
+  return (strategy >= ZMX_PNG_FILTER_ZERO && strategy <= ZMX_PNG_FILTER_BRUTE) || strategy == ZMX_PNG_FILTER_AUTO ||
          (predefined_allowed && strategy == ZMX_PNG_FILTER_PREDEFINED);
+}
+
+// _PREDEFINED's types, and the ones _AUTO may be given for its eighth trial
+int CheckPredefined(const std::string& w, int strategy, const unsigned char* predefined, size_t height) {
+  if (strategy == ZMX_PNG_FILTER_PREDEFINED && !predefined) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED without types");
+  if (strategy != ZMX_PNG_FILTER_PREDEFINED && strategy != ZMX_PNG_FILTER_AUTO) return 0;
+  for (size_t r = 0; predefined && r < height; ++r) {
+    if (predefined[r] > 4) return Refuse(w + ": predefined type " + std::to_string(predefined[r]) + " of row " + std::to_string(r));
+  }
+  return 0;
 }
 
 // A file in the making: a malloc'ed array under the reference's convention that begins with PngPrefix's bytes, for
@@ -138,6 +151,134 @@ int BadStream(const std::string& w) {
 
 namespace {
 
+// What is made of one image: its statistics, the mode of the first file, the scanlines' size in that mode.
+struct Reduced {
+  zmx_png_color_stats stats;
+  zmx_png_color_mode mode;
+  bool as_is = false;      // the mode is the image's own: nothing is converted
+  size_t scanlines = 0;    // height * (row bytes + 1)
+};
+
+bool SameMode(const zmx_png_image& im, const zmx_png_color_mode& mode) {
+  return mode.colortype == im.colortype && mode.bitdepth == im.bitdepth && mode.key_defined == 0;
+}
+
+size_t ScanlinesIn(const zmx_png_image& im, const zmx_png_color_mode& mode) {
+  const size_t bpp = (mode.colortype == 3 ? 1 : zamd::PngChannels(mode.colortype)) * mode.bitdepth;
+  return static_cast<size_t>(im.height) * ((static_cast<size_t>(im.width) * bpp + 7) / 8 + 1);
+}
+
+int CheckReducible(const std::string& w, const zmx_png_image& im, Geometry* g) {
+  if (CheckImage(w, im, g) != 0) return -1;
+  if (static_cast<uint64_t>(im.width) * im.height > 0xffffffffull) return Refuse(w + ": an image of 2^32 pixels or more");
+  return 0;
+}
+
+// on a held context: the statistics and the mode of the first file
+int StatsAndMode(zmx_ctx* ctx, const zmx_png_image& im, Reduced* r) {
+  if (zmx_png_color_stats_device(ctx, &im, &r->stats) != 0) return -1;
+  zamd::PngChooseColor(r->stats, static_cast<uint64_t>(im.width) * im.height, &r->mode);
+  r->as_is = SameMode(im, r->mode);
+  r->scanlines = ScanlinesIn(im, r->mode);
+  return 0;
+}
+
+// ---- zopflipng's choice of the filter strategy (zopflipng_lib.cc AutoChooseFilterStrategy)
+constexpr unsigned kTrialWindow = 8192;
+constexpr int kTrialStrategies[8] = {ZMX_PNG_FILTER_ZERO, ZMX_PNG_FILTER_ONE,    ZMX_PNG_FILTER_TWO,     ZMX_PNG_FILTER_THREE,
+                                     ZMX_PNG_FILTER_FOUR, ZMX_PNG_FILTER_MINSUM, ZMX_PNG_FILTER_ENTROPY, ZMX_PNG_FILTER_PREDEFINED};
+
+// The file sizes of the trials of `im` in `mode` (null: as it is) on a held context: the rows of all trials in one buffer,
+// one zmx_png_deflate_sizes_device, the container's bytes around each stream.
+int TrialFileSizes(zmx_ctx* ctx, const std::string& w, int device, const zmx_png_image& im, const zmx_png_color_mode* mode,
+                   const unsigned char* predefined, int ntrials, uint64_t* file_bytes) {
+  zmx_png_color_mode own = zmx_png_color_mode();
+  own.colortype = im.colortype;
+  own.bitdepth = im.bitdepth;
+  const size_t scanlines = ScanlinesIn(im, mode ? *mode : own);
+  if (scanlines > SIZE_MAX / 8) return Refuse(w + ": the sizes overflow");
+  DeviceBuffer rows;
+  rows.device = device;
+  if (zmx_internal_device_alloc(device, scanlines * ntrials, &rows.p) != 0) return -1;
+  if (zmx_internal_png_trial_scanlines(ctx, w.c_str(), &im, mode, predefined, ntrials, rows.p) != 0) return -1;
+  const void* ptrs[8];
+  size_t sizes[8];
+  uint64_t zlib_bytes[8];
+  for (int k = 0; k < ntrials; ++k) {
+    ptrs[k] = static_cast<const unsigned char*>(rows.p) + static_cast<size_t>(k) * scanlines;
+    sizes[k] = scanlines;
+  }
+  if (zmx_png_deflate_sizes_device(ctx, static_cast<size_t>(ntrials), ptrs, sizes, kTrialWindow, zlib_bytes) != 0) return -1;
+  size_t prefix_bytes = zamd::kPngPrefixBytes;
+  if (mode) {
+    unsigned char prefix[zamd::kPngMaxPrefixBytes];
+    prefix_bytes = zamd::PngPrefixReduced(im.width, im.height, mode->colortype, mode->bitdepth, mode->palette, mode->palettesize,
+                                          mode->key_defined != 0, mode->key_r, mode->key_g, mode->key_b, prefix);
+  }
+  for (int k = 0; k < ntrials; ++k) file_bytes[k] = prefix_bytes + zlib_bytes[k] + zamd::kPngTrailerBytes;
+  return 0;
+}
+
+// The choice for an image the caller has checked, on a held context.  `known`: its statistics and mode where the caller
+// has them (reduce_color only); else they are taken here.
+int ChooseStrategy(zmx_ctx* ctx, const std::string& w, int device, const zmx_png_image& im, bool reduce_color, const Reduced* known,
+                   const unsigned char* predefined, int* strategy, uint64_t* file_bytes) {
+  const int ntrials = predefined ? 8 : 7;
+  uint64_t bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (!reduce_color) {
+    if (TrialFileSizes(ctx, w, device, im, nullptr, predefined, ntrials, bytes) != 0) return -1;
+  } else {
+    Reduced mine;
+    if (!known) {
+      if (StatsAndMode(ctx, im, &mine) != 0) return -1;
+      known = &mine;
+    }
+    if (TrialFileSizes(ctx, w, device, im, known->as_is ? nullptr : &known->mode, predefined, ntrials, bytes) != 0) return -1;
+    bool small = false;
+    for (int k = 0; k < ntrials; ++k) small = small || bytes[k] < zamd::kPngRetryBelow;
+    if (known->mode.colortype == 3 && small) {
+      // TryOptimize's second try sits inside every trial: a small palette file competes with its RGB / RGBA file
+      zmx_png_color_mode retry;
+      zamd::PngRetryMode(known->stats, static_cast<uint64_t>(im.width) * im.height, &retry);
+      uint64_t second[8];
+      if (TrialFileSizes(ctx, w, device, im, SameMode(im, retry) ? nullptr : &retry, predefined, ntrials, second) != 0) return -1;
+      for (int k = 0; k < ntrials; ++k) {
+        if (bytes[k] < zamd::kPngRetryBelow && second[k] < bytes[k]) bytes[k] = second[k];
+      }
+    }
+  }
+  int best = 0;
+  for (int k = 1; k < ntrials; ++k) {
+    if (bytes[k] < bytes[best]) best = k;
+  }
+  *strategy = kTrialStrategies[best];
+  if (file_bytes) {
+    for (int k = 0; k < 8; ++k) file_bytes[k] = bytes[k];
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int zmx_png_choose_strategy_device(zmx_ctx* ctx, const zmx_png_image* image, int reduce_color, const unsigned char* predefined,
+                                              int* strategy, uint64_t file_bytes[8]) {
+  const std::string w = "zmx_png_choose_strategy_device";
+  if (!ctx || !image || !strategy || !file_bytes) return Refuse(w + ": null argument");
+  Geometry g;
+  if ((reduce_color ? CheckReducible(w, *image, &g) : CheckImage(w, *image, &g)) != 0) return -1;
+  if (CheckPredefined(w, ZMX_PNG_FILTER_AUTO, predefined, g.height) != 0) return -1;
+  int device = -1;
+  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, g.linebytes * g.height, &device) != 0) return -1;
+  int chosen = 0;
+  uint64_t bytes[8];
+  if (ChooseStrategy(ctx, w, device, *image, reduce_color != 0, nullptr, predefined, &chosen, bytes) != 0) return -1;
+  *strategy = chosen;
+  for (int k = 0; k < 8; ++k) file_bytes[k] = bytes[k];
+  return 0;
+}
+
+namespace {
+
 int EncodeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
               unsigned lossy, unsigned char** out, size_t* outsize) {
   if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
@@ -145,12 +286,7 @@ int EncodeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_
   Geometry g;
   if (CheckImage(w, *image, &g) != 0) return -1;
   if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
-  if (strategy == ZMX_PNG_FILTER_PREDEFINED) {
-    if (!predefined) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED without types");
-    for (size_t r = 0; r < g.height; ++r) {
-      if (predefined[r] > 4) return Refuse(w + ": predefined type " + std::to_string(predefined[r]) + " of row " + std::to_string(r));
-    }
-  }
+  if (CheckPredefined(w, strategy, predefined, g.height) != 0) return -1;
   const LossyPlan plan = PlanLossy(*image, g, lossy, false);
   if (CheckRewritable(w, *image, plan) != 0) return -1;
   DeviceBuffer scan, rewritten;
@@ -162,6 +298,7 @@ int EncodeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_
   // (the context is held for the rewrite, the types and the rows only)
   const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
     if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), image, 0, 1, rewritten.p, &work) != 0) return -1;
+    if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, scan.device, work, false, nullptr, predefined, &strategy, nullptr) != 0) return -1;
     return zmx_internal_png_scanlines(ctx, work.d_pixels, g.linebytes, g.height, g.bytewidth, strategy, kBruteWindow, predefined, scan.p);
   }, scan.device);
   if (rc != 0) return -1;
@@ -211,7 +348,9 @@ int EncodeBatch(const std::string& w, const ZopfliOptions* options, size_t n, co
           zmx_internal_png_lossy_image(ctx, w.c_str(), &images[i], 0, 1, static_cast<unsigned char*>(rewritten.p) + rstart[i], &work) != 0) {
         return -1;
       }
-      if (zmx_internal_png_scanlines(ctx, work.d_pixels, g[i].linebytes, g[i].height, g[i].bytewidth, strategy, kBruteWindow, nullptr,
+      int chosen = strategy;
+      if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, scan.device, work, false, nullptr, nullptr, &chosen, nullptr) != 0) return -1;
+      if (zmx_internal_png_scanlines(ctx, work.d_pixels, g[i].linebytes, g[i].height, g[i].bytewidth, chosen, kBruteWindow, nullptr,
                                      base + start[i]) != 0) {
         return -1;
       }
@@ -273,38 +412,6 @@ extern "C" int zmx_png_choose_color(const zmx_png_color_stats* stats, uint64_t n
 
 namespace {
 
-// What is made of one image: its statistics, the mode of the first file, the scanlines' size in that mode.
-struct Reduced {
-  zmx_png_color_stats stats;
-  zmx_png_color_mode mode;
-  bool as_is = false;      // the mode is the image's own: nothing is converted
-  size_t scanlines = 0;    // height * (row bytes + 1)
-};
-
-bool SameMode(const zmx_png_image& im, const zmx_png_color_mode& mode) {
-  return mode.colortype == im.colortype && mode.bitdepth == im.bitdepth && mode.key_defined == 0;
-}
-
-size_t ScanlinesIn(const zmx_png_image& im, const zmx_png_color_mode& mode) {
-  const size_t bpp = (mode.colortype == 3 ? 1 : zamd::PngChannels(mode.colortype)) * mode.bitdepth;
-  return static_cast<size_t>(im.height) * ((static_cast<size_t>(im.width) * bpp + 7) / 8 + 1);
-}
-
-int CheckReducible(const std::string& w, const zmx_png_image& im, Geometry* g) {
-  if (CheckImage(w, im, g) != 0) return -1;
-  if (static_cast<uint64_t>(im.width) * im.height > 0xffffffffull) return Refuse(w + ": an image of 2^32 pixels or more");
-  return 0;
-}
-
-// on a held context: the statistics and the mode of the first file
-int StatsAndMode(zmx_ctx* ctx, const zmx_png_image& im, Reduced* r) {
-  if (zmx_png_color_stats_device(ctx, &im, &r->stats) != 0) return -1;
-  zamd::PngChooseColor(r->stats, static_cast<uint64_t>(im.width) * im.height, &r->mode);
-  r->as_is = SameMode(im, r->mode);
-  r->scanlines = ScanlinesIn(im, r->mode);
-  return 0;
-}
-
 // Of two closed files of one image the one zopflipng keeps: the second only when it is strictly smaller.
 File& Smaller(File& first, File& second) { return second.size < first.size ? second : first; }
 
@@ -319,12 +426,7 @@ int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_pn
   Geometry g;
   if (CheckReducible(w, *image, &g) != 0) return -1;
   if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
-  if (strategy == ZMX_PNG_FILTER_PREDEFINED) {
-    if (!predefined) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED without types");
-    for (size_t r = 0; r < g.height; ++r) {
-      if (predefined[r] > 4) return Refuse(w + ": predefined type " + std::to_string(predefined[r]) + " of row " + std::to_string(r));
-    }
-  }
+  if (CheckPredefined(w, strategy, predefined, g.height) != 0) return -1;
   int device = -1;
   if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, g.linebytes * g.height, &device) != 0) return -1;
   const uint64_t numpixels = static_cast<uint64_t>(image->width) * image->height;
@@ -338,6 +440,7 @@ int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_pn
   int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
     if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), image, plan.to8, plan.transparent, rewritten.p, &work) != 0) return -1;
     if (StatsAndMode(ctx, work, &r) != 0) return -1;
+    if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, device, work, true, &r, predefined, &strategy, nullptr) != 0) return -1;
     if (zmx_internal_device_alloc(device, r.scanlines, &scan.p) != 0) return -1;
     return zmx_internal_png_reduced_scanlines(ctx, &work, r.as_is ? nullptr : &r.mode, strategy, kBruteWindow, predefined, scan.p);
   }, device);
@@ -447,6 +550,7 @@ int OptimizeBatch(const std::string& w, const ZopfliOptions* options, size_t n, 
   const zmx_png_image* const images = work.data();
   // the first files: statistics for all, one buffer, conversion and rows image by image, on one hold of a context
   std::vector<Reduced> r(n);
+  std::vector<int> chosen(n, strategy);   // (_AUTO: the strategy of each image's own trials)
   std::vector<size_t> all(n), start(n + 1, 0);
   std::vector<zmx_png_color_mode> modes(n);
   std::vector<char> as_is(n);
@@ -459,12 +563,13 @@ int OptimizeBatch(const std::string& w, const ZopfliOptions* options, size_t n, 
         return -1;
       }
       if (StatsAndMode(ctx, images[i], &r[i]) != 0) return -1;
+      if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, device, images[i], true, &r[i], nullptr, &chosen[i], nullptr) != 0) return -1;
       if (r[i].scanlines > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
       start[i + 1] = start[i] + r[i].scanlines;
     }
     if (zmx_internal_device_alloc(device, start[n], &scan.p) != 0) return -1;
     for (size_t i = 0; i < n; ++i) {
-      if (zmx_internal_png_reduced_scanlines(ctx, &images[i], r[i].as_is ? nullptr : &r[i].mode, strategy, kBruteWindow, nullptr,
+      if (zmx_internal_png_reduced_scanlines(ctx, &images[i], r[i].as_is ? nullptr : &r[i].mode, chosen[i], kBruteWindow, nullptr,
                                              static_cast<unsigned char*>(scan.p) + start[i]) != 0) {
         return -1;
       }
@@ -501,7 +606,7 @@ int OptimizeBatch(const std::string& w, const ZopfliOptions* options, size_t n, 
     if (zmx_internal_device_alloc(device, start2[m], &scan2.p) != 0) return -1;
     rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
       for (size_t k = 0; k < m; ++k) {
-        if (zmx_internal_png_reduced_scanlines(ctx, &images[again[k]], as_is2[k] ? nullptr : &modes2[k], strategy, kBruteWindow, nullptr,
+        if (zmx_internal_png_reduced_scanlines(ctx, &images[again[k]], as_is2[k] ? nullptr : &modes2[k], chosen[again[k]], kBruteWindow, nullptr,
                                                static_cast<unsigned char*>(scan2.p) + start2[k]) != 0) {
           return -1;
         }

@@ -127,6 +127,14 @@ int zmx_internal_png_reduced_scanlines(zmx_ctx* ctx, const zmx_png_image* image,
 int zmx_internal_png_lossy_image(zmx_ctx* ctx, const char* who, const zmx_png_image* image, int to8, int transparent, void* d_buf,
                                  zmx_png_image* work);
 
+// ---- zopflipng's filter-strategy trials (png_encode.cc: zmx_png_choose_strategy_device, ZMX_PNG_FILTER_AUTO)
+// The image converted to `mode` once (null: as it is), then the scanlines of trial k = 0 .. ntrials - 1 at
+// d_out + k * height * (rowbytes + 1), in zopflipng's order: the types 0 .. 4, MINSUM, ENTROPY and, for ntrials = 8, the
+// `height` host bytes at `predefined`, each at most 4.  d_out is memory of the context's device that the caller owns.
+// 0, or -1 with the error set, its message starting with `who`.
+int zmx_internal_png_trial_scanlines(zmx_ctx* ctx, const char* who, const zmx_png_image* image, const zmx_png_color_mode* mode,
+                                     const unsigned char* predefined, int ntrials, void* d_out);
+
 // ---- for tests and tools
 // The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
 // (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing); else 0.  For
@@ -142,6 +150,9 @@ ZMX_INTERNAL_EXPORT void zmx_internal_png_color_ms(double out[3]);
 // The same for the calling thread's last zmx_png_lossy_transparent_device: k_png_lossy_stats, k_png_lossy_carry,
 // k_png_lossy_fill (0: not launched).  For tools/png_lossy.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_png_lossy_ms(double out[3]);
+// The same for the calling thread's last zmx_png_deflate_sizes_device: k_png_lo_hash, k_png_lo_links, k_png_lo_ask,
+// k_png_lo_keep, k_png_lo_search, k_png_lo_parse.  For tools/png_auto.py.
+ZMX_INTERNAL_EXPORT void zmx_internal_png_lodeflate_ms(double out[6]);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
 // squeeze run computes them — *wmax, *tiemask —, no device involved.
 ZMX_INTERNAL_EXPORT void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask);
