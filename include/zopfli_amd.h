@@ -340,6 +340,16 @@ int zmx_checksum(zmx_ctx* ctx, int kind, size_t begin, size_t end, uint32_t* val
  * inputs (zmx_compress_batch). */
 int zmx_checksums(zmx_ctx* ctx, int kind, size_t n, const uint64_t* begin, const uint64_t* end, uint32_t* values);
 uint32_t zmx_checksum_combine(int kind, uint32_t a, uint32_t b, uint64_t len_b);
+/* The same for n ranges of ARBITRARY device memory: values[i] = the checksum of d_ptr[i][0, nbytes[i]) on its own.  A range
+ * may start at any byte address, have any length and lie in any allocation of the context's device; no byte outside a
+ * range is read.  k_checksum_pieces (k_checksum's geometry: 256 KiB pieces counted from the range's end) and
+ * k_checksum_finish (device/zmx_checksum_device.h) follow each other on the context's stream, each ONE launch for any n:
+ * the pieces are combined and the checksum finished on the device, and only 4 * n bytes come down.  An empty range gives
+ * the initial value (CRC-32 0, Adler-32 1); n = 0 returns 0 and launches nothing.  Refused before any launch
+ * (ZMX_ERR_REFUSED), `values` untouched: a null array, an unknown kind, and — the message naming "range i" — a null
+ * pointer with bytes, host or managed memory, a range that leaves its allocation, memory of another device than the
+ * context's.  Synchronous; the caller synchronises the streams that produced the bytes. */
+int zmx_checksum_device(zmx_ctx* ctx, int kind, size_t n, const void* const* d_ptr, const size_t* nbytes, uint32_t* values);
 
 /* Parity probe: the ZopfliFindLongestMatch result for one position of one
  * block, expanded to the reference's sublen[259] convention. */
@@ -427,8 +437,8 @@ int zmx_png_filter_rows_device(zmx_ctx* ctx, const void* d_image, size_t linebyt
  * whose rows carry filter type 0 — or, where `predefined` is given, the types at `predefined` (the eighth trial; if it
  * wins, the file is _PREDEFINED's).
  * Out of scope: palette input, interlace, ancillary chunks (libzopflipng_amd.so does those, from a file — its own strategy
- * trials still run LodePNG on host threads), a PNG left in device memory.  Colour-type reduction is
- * zmx_png_optimize_device's. */
+ * trials still run LodePNG on host threads).  Colour-type reduction is zmx_png_optimize_device's; the file left in device
+ * memory is zmx_png_encode_device_to_device's, further down. */
 typedef struct zmx_png_image {
   const void* d_pixels;  /* height rows of linebytes bytes, PNG byte order (16-bit samples big-endian), rows back to back */
   uint32_t width, height, colortype /* 0, 2, 4, 6 */, bitdepth /* 8, 16 */;
@@ -545,8 +555,9 @@ int zmx_png_convert_device(zmx_ctx* ctx, const zmx_png_image* image, const zmx_p
  * ZMX_PNG_FILTER_AUTO: zmx_png_choose_strategy_device(reduce_color = 1) chooses on the same hold of the context, with the
  * statistics the entry has taken; both tries of a small palette file are made with the chosen strategy, as zopflipng's
  * are.  The file is the one zopflipng --always_zopflify writes with no --filters.
- * Out of scope: palette INPUT, interlace, ancillary chunks (libzopflipng_amd.so does those, from a file), a PNG left in
- * device memory.  --lossy_transparent and --lossy_8bit are the _lossy entries' further down. */
+ * Out of scope: palette INPUT, interlace, ancillary chunks (libzopflipng_amd.so does those, from a file).
+ * --lossy_transparent and --lossy_8bit are the _lossy entries' further down, the file left in device memory is
+ * zmx_png_optimize_device_to_device's. */
 int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
                             const unsigned char* predefined, unsigned char** out, size_t* outsize);
 /* n images in one call: every file is the single call's.  Statistics and conversion run image by image on one hold of a
@@ -613,6 +624,48 @@ int zmx_png_encode_device_batch_lossy(const ZopfliOptions* options, size_t n, co
                                       unsigned lossy, unsigned char** out, size_t* outsize);
 int zmx_png_optimize_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
                                         unsigned lossy, unsigned char** out, size_t* outsize);
+
+/* -------- the PNG entries with the file LEFT IN DEVICE MEMORY
+ *
+ * d_out[0, *outsize) ends holding, byte for byte, the file that zmx_png_encode_device_lossy / zmx_png_optimize_device_lossy
+ * appends to an empty output for the same options, image, strategy, predefined types and `lossy` (an argument here: these
+ * entries have no _lossy twins) — every strategy, _AUTO and _PREDEFINED included, both lossy flags and their no-op
+ * combinations.  No byte of the file, the stream or the pixels visits the host (zmx_last_input_traffic()[0] and
+ * zmx_last_output_traffic()[0] are 0; [1] of the latter: the uploaded literals, as for zmx_compress_device_to_device).
+ * d_out may have any byte alignment; every byte of the file is written and no byte outside it.
+ * Everything in front of the compression is the host-output entries' first hold of the context.  The stream then goes
+ * zmx_compress_device_to_device's way with a FRAME around it: in front of the stream's first bit the file's prefix with the
+ * IDAT's length filled in and LodePNG's 78 01, behind the Adler-32 four placeholder bytes and IEND — all literals of the one
+ * bit join.  After the join, while the call still holds its contexts, zmx_checksum_device's two kernels run over the
+ * IDAT's type and payload where they lie and seal the CRC-32 into the placeholder.
+ * The plan gives the file's size before anything is written: a `capacity` that is too small, or a stream that does not fit
+ * the 31 bits of a chunk's length, returns -1 (ZMX_ERR_REFUSED) with *outsize = the size needed and d_out untouched.
+ * zmx_png_bound(width, height, colortype, bitdepth) — the INPUT's mode — is always enough for both single entries
+ * (host/device_output_plan.h derives it); 0 for a mode the entries refuse.
+ * zmx_png_optimize_device_to_device, palette files: which of the two tries is kept is known only once the first is made, so
+ * a palette file is made into a buffer of the call's own, the second try of one below 4096 bytes into another, and one
+ * device-to-device copy puts the kept file into d_out; `capacity` is held against the kept file's size.
+ * zmx_png_encode_device_batch_packed: zmx_png_encode_device_batch's front half, then zmx_compress_device_batch_packed's plan
+ * with a frame per stream — ONE k_bitjoin_many launch writes all files, ONE k_checksum_pieces and ONE k_checksum_finish
+ * launch seal all n.  File i lies at d_arena + outoffset[i], outoffset[i] = the end of file i - 1 rounded up to `align`
+ * (a power of two, 1 .. 4096); the bytes between files are not written.  An arena that is too small: outoffset[] and
+ * outsize[] report what is needed and nothing is written.  zmx_png_batch_bound = every image's bound rounded up to
+ * `align`, summed.  _PREDEFINED is refused, as in the host-output batch; n = 0 returns 0.
+ * Limits, inherited from the to-device compress entries: one round (ZOPFLI_AMD_ROUND_PARTS master blocks of scanlines for
+ * the single entries, 2 000 000 000 bytes for the batch); the image(s) and the destination on ONE device of the library's;
+ * the destination overlapping neither an image nor anything made from it.  Refused as well, before anything runs: what
+ * the host-output entries refuse, a destination that is not plain device memory or leaves its allocation.
+ * Out of scope: a to-device batch form of OPTIMIZE — its second tries need a second packed pass and a gather of the kept
+ * files. */
+size_t zmx_png_bound(uint32_t width, uint32_t height, uint32_t colortype, uint32_t bitdepth);
+int zmx_png_encode_device_to_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                    const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize);
+int zmx_png_optimize_device_to_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                      const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize);
+size_t zmx_png_batch_bound(size_t n, const zmx_png_image* images, size_t align);
+int zmx_png_encode_device_batch_packed(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                       unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
+                                       size_t* outsize);
 
 /* Parity probe over whole tables: two 64-bit sums over all positions of a hash of the logical content of the match
  * records (block, position, length, distance, same, literal, every change point of sublen).  Equal digests of two

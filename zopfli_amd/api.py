@@ -256,7 +256,8 @@ def compress_device_batch(srcs, fmt=FORMAT_GZIP, options=None, lib=None):
 
 class CapacityError(RuntimeError):
     """compress_device_out: the stream does not fit the destination; `needed` is its size in bytes.
-    compress_device_batch_out, compress_device_batch_packed: `needed` is the list of all streams' sizes."""
+    compress_device_batch_out, compress_device_batch_packed: `needed` is the list of all streams' sizes.
+    png_encode_device_out, png_optimize_device_out: the file's size; png_encode_device_batch_packed: the list of the files'."""
 
     def __init__(self, message, needed):
         super().__init__(message)
@@ -550,6 +551,96 @@ def png_optimize_device_batch(images, strategy="e", options=None, lib=None, loss
     if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), *flags, outs, outsizes) != 0:
         raise RuntimeError("zmx_png_optimize_device_batch: " + (lib.zmx_last_error() or b"").decode())
     return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+
+
+def png_bound(width, height, colortype, bitdepth, lib=None):
+    """zmx_png_bound: a destination capacity that does for png_encode_device_out and png_optimize_device_out of any image
+    of this width, height, colour type and bit depth (0 for a mode the entries refuse)."""
+    lib = lib or library()
+    fn = lib.zmx_png_bound
+    fn.argtypes = [ctypes.c_uint32] * 4
+    fn.restype = ctypes.c_size_t
+    return int(fn(int(width), int(height), int(colortype), int(bitdepth)))
+
+
+def png_batch_bound(images, align=1, lib=None):
+    """zmx_png_batch_bound: an arena capacity that does for png_encode_device_batch_packed of these images (what
+    png_encode_device takes, or bare (None, width, height, colortype, bitdepth) tuples: the pixels are not looked at)."""
+    lib = lib or library()
+    ims = [_png_image(image, sync=False) for image in images]
+    n = len(ims)
+    fn = lib.zmx_png_batch_bound
+    fn.argtypes = [ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_size_t]
+    fn.restype = ctypes.c_size_t
+    return int(fn(n, (PngImage * max(n, 1))(*ims), int(align)))
+
+
+def _png_device_out(name, image, dst, strategy, options, predefined, lib, lossy):
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    im = _png_image(image)
+    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
+    if types is not None and len(types) != im.height:
+        raise ValueError(f"{len(types)} predefined types for {im.height} rows")
+    out, capacity = _device_range(int(dst[0]), dst[1]) if isinstance(dst, (tuple, list)) else _device_range(dst, None)
+    outsize = ctypes.c_size_t(0)
+    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
+    fn = getattr(lib, name)
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint, ctypes.c_void_p,
+                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, lossy, out, capacity, ctypes.byref(outsize)) != 0:
+        message = name + ": " + (lib.zmx_last_error() or b"").decode()
+        if outsize.value > capacity:
+            raise CapacityError(message, int(outsize.value))
+        raise RuntimeError(message)
+    return int(outsize.value)
+
+
+def png_encode_device_out(image, dst, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, lossy_8bit=False):
+    """zmx_png_encode_device_to_device: png_encode_device's file left in device memory.  `dst`: a contiguous tensor or an
+    (integer device pointer, capacity) pair on the image's device, of any byte alignment.  Returns the file's size: its
+    bytes are dst[0, size), and no byte behind them is written.  Raises CapacityError (with the size needed, nothing
+    written) when the file does not fit — png_bound gives a capacity that always does —, otherwise as png_encode_device."""
+    return _png_device_out("zmx_png_encode_device_to_device", image, dst, strategy, options, predefined, lib,
+                           _png_lossy(lossy_transparent, lossy_8bit))
+
+
+def png_optimize_device_out(image, dst, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, lossy_8bit=False):
+    """zmx_png_optimize_device_to_device: png_optimize_device's file left in device memory; arguments, result and errors as
+    png_encode_device_out's."""
+    return _png_device_out("zmx_png_optimize_device_to_device", image, dst, strategy, options, predefined, lib,
+                           _png_lossy(lossy_transparent, lossy_8bit))
+
+
+def png_encode_device_batch_packed(images, arena, align=1, strategy="e", options=None, lib=None, lossy_transparent=False, lossy_8bit=False):
+    """zmx_png_encode_device_batch_packed: png_encode_device_batch's files packed into `arena`, a contiguous tensor or an
+    (integer device pointer, capacity) pair: file i begins at the end of file i - 1 rounded up to `align` (a power of two,
+    1 .. 4096); the bytes between files are not written.  Returns (offsets, sizes).  Raises CapacityError (`needed`: the
+    list of sizes, nothing written) when the arena is too small — png_batch_bound gives one that does."""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    ims = [_png_image(image, sync=False) for image in images]
+    devices = {}
+    for image in images:
+        if not isinstance(image, (tuple, list)) and type(image).__module__.split(".")[0] == "torch":
+            devices[str(image.device)] = image.device
+    if devices:
+        import torch
+        for device in devices.values():
+            torch.cuda.current_stream(device).synchronize()
+    out, capacity = _device_range(int(arena[0]), arena[1]) if isinstance(arena, (tuple, list)) else _device_range(arena, None)
+    n = len(ims)
+    offsets = (ctypes.c_size_t * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    fn = lib.zmx_png_encode_device_batch_packed
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_uint, ctypes.c_void_p,
+                   ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), n, (PngImage * max(n, 1))(*ims), _png_strategy(strategy), _png_lossy(lossy_transparent, lossy_8bit), out,
+          capacity, int(align), offsets, outsizes) != 0:
+        raise _batch_failure("zmx_png_encode_device_batch_packed", lib, outsizes, n)
+    return [int(offsets[i]) for i in range(n)], [int(outsizes[i]) for i in range(n)]
 
 
 def last_output_traffic(lib=None):
@@ -891,6 +982,20 @@ class Context:
                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, kind, n, b, e, v), "zmx_checksums")
+        return [int(v[i]) for i in range(n)]
+
+    def checksum_device(self, kind, ranges):
+        """zmx_checksum_device: CRC-32 / Adler-32 of every range of device memory of the context's device — contiguous
+        tensors or (integer device pointer, nbytes) pairs, at any byte address —, pieces and finish on the device."""
+        ptrs, sizes = _device_ranges(ranges)
+        n = len(ptrs)
+        v = (ctypes.c_uint32 * max(n, 1))()
+        fn = self.lib.zmx_checksum_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                       ctypes.POINTER(ctypes.c_uint32)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, kind, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes), v),
+                    "zmx_checksum_device")
         return [int(v[i]) for i in range(n)]
 
     def build_tables(self, blocks, parent=None, matches_only=False):

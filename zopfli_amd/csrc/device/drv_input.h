@@ -130,6 +130,14 @@ void zmx_internal_device_free(int device, void* p) {
   (void)hipFree(p);
 }
 
+int zmx_internal_device_copy(int device, void* d_dst, const void* d_src, size_t n) {
+  if (n == 0) return 0;
+  DEVICE_ENTRY(device);
+  HIPCHK(hipMemcpy(d_dst, d_src, n, hipMemcpyDeviceToDevice));
+  HIPCHK(hipStreamSynchronize(nullptr));   // (a copy within one device may return before it is done; the source is freed next)
+  return 0;
+}
+
 int zmx_set_input_device(zmx_ctx* c, const void* d_in, size_t insize) {
   int device = -1;
   if (const int rc = CheckDevicePointer("zmx_set_input_device", d_in, insize, &device)) return rc;

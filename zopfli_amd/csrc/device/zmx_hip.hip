@@ -29,6 +29,8 @@
 #include "zmx_dp4_fix.h"     // k_dp4_fix: the serial pass, which runs the jobs of zmx_dp4.h and zmx_dp5.h
 #include "zmx_encode.h"      // the bit writer
 #include "zmx_checksum.h"    // CRC-32 / Adler-32 pieces
+#define ZMX_CHECKSUM_DEVICE_KERNELS
+#include "zmx_checksum_device.h"   // ... of any device memory, finished on the device
 #include "zmx_trace.h"       // the walk back over length_array, in segments
 #include "zmx_greedy.h"      // the greedy parse, same segmentation
 #include "zmx_png.h"         // LodePNG's MINSUM / ENTROPY filter choice
@@ -68,6 +70,7 @@
 #include "drv_stores.h"      // store download, verify, encode
 #include "drv_bitjoin.h"     // output that stays on the device: the bit join, the bit writer without the way down
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
+#include "drv_checksum_device.h"   // zmx_checksum_device, the seal of a PNG left in device memory
 #include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion, LodePNG's zlib sizes
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries
 #include "drv_probes.h"      // the parity probes: digest, longest match, hash links, length array, DP rows

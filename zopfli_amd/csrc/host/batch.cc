@@ -15,6 +15,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "deal.h"
@@ -62,6 +63,7 @@ struct DeviceOut {
   size_t arena_capacity = 0, align = 0;
   size_t* outoffset = nullptr;
   int device = -1;
+  const zamd::PngFrame* frames = nullptr;   // a frame around every stream (device_output_plan.h): PNG files, sealed after the join
 };
 
 // The bytes [lo, lo + size) of the inputs' concatenation in device memory: a plain allocation the call owns, not the
@@ -140,17 +142,22 @@ int JoinStreams(const std::string& w, zmx_ctx* ctx, ZopfliFormat output_type, si
   std::vector<zamd::OutputPlan> plans(n);
   const std::vector<uint8_t> header = zamd::ContainerHeader(output_type);
   zamd::ParallelFor(n, [&](size_t i) {
-    plans[i] = zamd::PlanOutput(header, chunks.data() + first_chunk[first_part[i]], chunks.data() + first_chunk[first_part[i + 1]], d_cat,
-                                zamd::ContainerTrailer(output_type, sum[i], insize[i]));
+    std::vector<uint8_t> trailer = zamd::ContainerTrailer(output_type, sum[i], insize[i]);
+    if (to.frames) trailer = zamd::PngFrameTrailer(std::move(trailer));
+    plans[i] = zamd::PlanOutput(to.frames ? zamd::PngFrameHeader(to.frames[i]) : header, chunks.data() + first_chunk[first_part[i]],
+                                chunks.data() + first_chunk[first_part[i + 1]], d_cat, trailer);
   });
   // ---- the sizes, and with them the destinations, before anything is written
   std::vector<size_t> size(n), offset(n, 0);
   for (size_t i = 0; i < n; ++i) size[i] = static_cast<size_t>(plans[i].total_bits / 8);
   std::string short_of;
+  for (size_t i = 0; to.frames && i < n && short_of.empty(); ++i) {
+    if (!zamd::PngFrameSetLength(to.frames[i], &plans[i])) short_of = "the zlib stream of image " + std::to_string(i) + " does not fit an IDAT chunk";
+  }
   if (to.align != 0) {
     const size_t end = zamd::PackedOffsets(n, size.data(), to.align, offset.data());
     for (size_t i = 0; i < n; ++i) to.outoffset[i] = offset[i];
-    if (end > to.arena_capacity) short_of = "the streams take " + std::to_string(end) + " bytes, the arena has " + std::to_string(to.arena_capacity);
+    if (short_of.empty() && end > to.arena_capacity) short_of = "the streams take " + std::to_string(end) + " bytes, the arena has " + std::to_string(to.arena_capacity);
   } else {
     for (size_t i = 0; i < n && short_of.empty(); ++i) {
       if (size[i] > to.capacity[i]) {
@@ -191,6 +198,20 @@ int JoinStreams(const std::string& w, zmx_ctx* ctx, ZopfliFormat output_type, si
   }
   if (zmx_internal_bitjoin_many_literals(ctx, literals.data(), literals.size(), n, dests.data(), nullptr, pieces.size(), pieces.data(),
                                          is_literal.data()) != 0) return -1;
+  if (to.frames) {
+    // every IDAT's CRC-32 over its type and the joined stream, into the placeholder behind it: two launches for all files
+    std::vector<const void*> from(n);
+    std::vector<size_t> covered(n);
+    std::vector<unsigned char*> seal(n);
+    for (size_t i = 0; i < n; ++i) {
+      unsigned char* const file = static_cast<unsigned char*>(dests[i].dst);
+      const size_t prefix = to.frames[i].file_prefix.size();
+      from[i] = file + prefix - 4;
+      covered[i] = 4 + static_cast<size_t>(zamd::PngFrameIdatBytes(size[i], prefix));
+      seal[i] = file + size[i] - zamd::kPngTrailerBytes;
+    }
+    if (zmx_internal_checksum_seal(ctx, ZMX_CRC32, n, from.data(), covered.data(), seal.data()) != 0) return -1;
+  }
   const double traffic[4] = {0, static_cast<double>(literals.size()), device_blocks, host_blocks};
   zamd::SetOutputTraffic(traffic);
   for (size_t i = 0; i < n; ++i) outsize[i] = size[i];
@@ -477,11 +498,12 @@ extern "C" int zmx_compress_device_batch_to_device(const ZopfliOptions* options,
   return CompressBatch(kWho, options, output_type, n, bytes, insize, nullptr, outsize, &to);
 }
 
-extern "C" int zmx_compress_device_batch_packed(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
-                                                const void* const* d_in, const size_t* insize, void* d_arena, size_t capacity,
-                                                size_t align, size_t* outoffset, size_t* outsize) {
-  static const char* const kWho = "zmx_compress_device_batch_packed";
+namespace {
+
+int BatchPacked(const char* kWho, const ZopfliOptions* options, ZopfliFormat output_type, size_t n, const void* const* d_in, const size_t* insize,
+                const zamd::PngFrame* frames, void* d_arena, size_t capacity, size_t align, size_t* outoffset, size_t* outsize) {
   DeviceOut to;
+  to.frames = frames;
   void* const arena[1] = {d_arena};
   if (const int rc = CheckDeviceOut(kWho, options, output_type, n, d_in, insize, 1, arena, &capacity, outsize, &to.device)) return rc < 0 ? -1 : 0;
   if (!outoffset) return Refuse(std::string(kWho) + ": null array");
@@ -494,4 +516,19 @@ extern "C" int zmx_compress_device_batch_packed(const ZopfliOptions* options, Zo
   BatchBytes bytes;
   bytes.device = d_in;
   return CompressBatch(kWho, options, output_type, n, bytes, insize, nullptr, outsize, &to);
+}
+
+}  // namespace
+
+extern "C" int zmx_compress_device_batch_packed(const ZopfliOptions* options, ZopfliFormat output_type, size_t n,
+                                                const void* const* d_in, const size_t* insize, void* d_arena, size_t capacity,
+                                                size_t align, size_t* outoffset, size_t* outsize) {
+  return BatchPacked("zmx_compress_device_batch_packed", options, output_type, n, d_in, insize, nullptr, d_arena, capacity, align, outoffset,
+                     outsize);
+}
+
+int zamd::CompressDeviceBatchPackedFramed(const char* who, const ZopfliOptions* options, size_t n, const void* const* d_in, const size_t* insize,
+                                          const zamd::PngFrame* frames, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
+                                          size_t* outsize) {
+  return BatchPacked(who, options, ZOPFLI_FORMAT_ZLIB, n, d_in, insize, frames, d_arena, capacity, align, outoffset, outsize);
 }

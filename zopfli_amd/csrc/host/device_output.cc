@@ -8,9 +8,14 @@
 // writer's buffers; stored bytes from the caller's input — and one zmx_bitjoin_device puts it together in d_out, while the
 // call still holds its contexts (the bit buffers are theirs).  The stream's size is known from the plan, before anything
 // is written.
+// zamd::CompressDeviceToDevice is that call with an optional FRAME (device_output_plan.h: PngFrame) for the PNG entries of
+// png_encode.cc: the file's prefix and 78 01 in place of the container's header, a CRC placeholder and IEND behind the
+// trailer, and after the join — on the same hold of the contexts — the IDAT's CRC-32 sealed into the placeholder by
+// zmx_internal_checksum_seal.  Without a frame nothing differs: the same plan, the same launches.
 #include <algorithm>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "dealing.h"
@@ -36,9 +41,8 @@ extern "C" size_t zmx_compress_batch_bound(ZopfliFormat output_type, size_t n, c
   return zamd::CompressBatchBound(output_type, n, insize, align);
 }
 
-extern "C" int zmx_compress_device_to_device(const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in,
-                                             size_t insize, void* d_out, size_t capacity, size_t* outsize) {
-  static const char* const kWho = "zmx_compress_device_to_device";
+int zamd::CompressDeviceToDevice(const char* kWho, const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in, size_t insize,
+                                 void* d_out, size_t capacity, size_t* outsize, const zamd::PngFrame* frame) {
   if (!options || !outsize) return Refuse(std::string(kWho) + ": null argument");
   *outsize = 0;
   if (output_type != ZOPFLI_FORMAT_GZIP && output_type != ZOPFLI_FORMAT_ZLIB && output_type != ZOPFLI_FORMAT_DEFLATE) {
@@ -47,7 +51,7 @@ extern "C" int zmx_compress_device_to_device(const ZopfliOptions* options, Zopfl
   int in_device = -1, out_device = -1;
   if (zmx_internal_device_pointer(kWho, d_in, insize, &in_device) != 0) return -1;
   if (capacity != 0 && d_out == nullptr) return Refuse(std::string(kWho) + ": d_out: null pointer with a non-zero size");
-  if (zmx_internal_device_pointer("zmx_compress_device_to_device: d_out", d_out, capacity, &out_device) != 0) return -1;
+  if (zmx_internal_device_pointer((std::string(kWho) + ": d_out").c_str(), d_out, capacity, &out_device) != 0) return -1;
   if (insize != 0 && capacity != 0) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
     if (a < b + capacity && b < a + insize) return Refuse(std::string(kWho) + ": d_out overlaps d_in");
@@ -71,9 +75,16 @@ extern "C" int zmx_compress_device_to_device(const ZopfliOptions* options, Zopfl
   bool too_small = false;
   size_t written = 0;
   dev.finish = [&](zmx_ctx* ctx, std::vector<zamd::Chunk>* chunks, uint32_t sum) {
-    const zamd::OutputPlan plan = zamd::PlanOutput(zamd::ContainerHeader(output_type), *chunks, static_cast<const unsigned char*>(d_in),
-                                                   zamd::ContainerTrailer(output_type, sum, insize));
+    std::vector<uint8_t> trailer = zamd::ContainerTrailer(output_type, sum, insize);
+    if (frame) trailer = zamd::PngFrameTrailer(std::move(trailer));
+    zamd::OutputPlan plan = zamd::PlanOutput(frame ? zamd::PngFrameHeader(*frame) : zamd::ContainerHeader(output_type), *chunks,
+                                             static_cast<const unsigned char*>(d_in), trailer);
     const size_t need = static_cast<size_t>(plan.total_bits / 8);
+    if (frame && !zamd::PngFrameSetLength(*frame, &plan)) {
+      too_small = true;
+      written = need;
+      return Refuse(std::string(kWho) + ": the zlib stream does not fit an IDAT chunk");
+    }
     if (need > capacity) {
       too_small = true;
       written = need;
@@ -88,6 +99,15 @@ extern "C" int zmx_compress_device_to_device(const ZopfliOptions* options, Zopfl
     }
     if (zmx_internal_bitjoin_literals(ctx, plan.literals.data(), plan.literals.size(), pieces.size(), pieces.data(), is_literal.data(),
                                       plan.total_bits, d_out, capacity) != 0) return -1;
+    if (frame) {
+      // the IDAT's CRC-32 over its type and the joined stream, into the placeholder behind it
+      unsigned char* const file = static_cast<unsigned char*>(d_out);
+      const size_t prefix = frame->file_prefix.size();
+      const void* from = file + prefix - 4;
+      const size_t covered = 4 + static_cast<size_t>(zamd::PngFrameIdatBytes(need, prefix));
+      unsigned char* seal = file + need - zamd::kPngTrailerBytes;
+      if (zmx_internal_checksum_seal(ctx, ZMX_CRC32, 1, &from, &covered, &seal) != 0) return -1;
+    }
     const double traffic[4] = {0, static_cast<double>(plan.literals.size()), static_cast<double>(plan.device_blocks),
                                static_cast<double>(plan.host_blocks)};
     zamd::SetOutputTraffic(traffic);
@@ -105,4 +125,9 @@ extern "C" int zmx_compress_device_to_device(const ZopfliOptions* options, Zopfl
   }
   *outsize = written;
   return 0;
+}
+
+extern "C" int zmx_compress_device_to_device(const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in,
+                                             size_t insize, void* d_out, size_t capacity, size_t* outsize) {
+  return zamd::CompressDeviceToDevice("zmx_compress_device_to_device", options, output_type, d_in, insize, d_out, capacity, outsize, nullptr);
 }

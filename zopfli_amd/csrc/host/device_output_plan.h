@@ -4,9 +4,11 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "deflate.h"
+#include "png_container.h"
 #include "symbols.h"
 #include "zopfli_amd.h"
 
@@ -151,5 +153,84 @@ inline OutputPlan PlanOutput(const std::vector<uint8_t>& prefix, const std::vect
                              const std::vector<uint8_t>& trailer) {
   return PlanOutput(prefix, chunks.data(), chunks.data() + chunks.size(), d_in, trailer);
 }
+
+// ---- a FRAME around the zlib stream: the PNG file left in device memory (zmx_png_encode_device_to_device and its kin)
+// The stream goes the way of zmx_compress_device_to_device(ZOPFLI_FORMAT_ZLIB); the frame replaces the container's header
+// by bytes in front of the stream's first bit and puts bytes behind its Adler-32, all of them literals of the same plan:
+//   in front   `file_prefix` — png_container.h's PngPrefix / PngPrefixReduced, up to and including "IDAT" — and 78 01,
+//              LodePNG's zlib header written straight away (PngCloseAt patches zopfli's 78 DA on the host);
+//   behind     four placeholder bytes where the IDAT's CRC-32 goes, and the 12 bytes of IEND.
+// The plan gives the file's size, and so the IDAT's length (PngFrameSetLength), before anything is written.  What the plan
+// cannot hold is the CRC-32: it covers "IDAT" and the joined stream — [file_prefix.size() - 4, file size - 16) of the file
+// — and is sealed into the placeholder by the device after the join (zmx_internal_checksum_seal).
+struct PngFrame {
+  std::vector<uint8_t> file_prefix;
+};
+inline std::vector<uint8_t> PngFrameHeader(const PngFrame& frame) {
+  std::vector<uint8_t> h = frame.file_prefix;
+  h.push_back(0x78);
+  h.push_back(0x01);
+  return h;
+}
+// `zlib_trailer`: ContainerTrailer(ZOPFLI_FORMAT_ZLIB, ...)
+inline std::vector<uint8_t> PngFrameTrailer(std::vector<uint8_t> zlib_trailer) {
+  unsigned char tail[kPngTrailerBytes];
+  PngStore32(tail, 0);   // the placeholder
+  PngStore32(tail + 4, 0);
+  std::memcpy(tail + 8, "IEND", 4);
+  PngStore32(tail + 12, PngCrc32(tail + 8, 4));
+  zlib_trailer.insert(zlib_trailer.end(), tail, tail + kPngTrailerBytes);
+  return zlib_trailer;
+}
+// The IDAT's length of a file of `file_bytes` bytes behind a prefix of `prefix_bytes`.
+inline uint64_t PngFrameIdatBytes(uint64_t file_bytes, size_t prefix_bytes) { return file_bytes - prefix_bytes - kPngTrailerBytes; }
+constexpr uint64_t kPngMaxChunkBytes = 0x7fffffffu;   // a chunk's length has 31 bits
+// Fills the IDAT's length into a plan made with PngFrameHeader / PngFrameTrailer (the prefix is its first literal);
+// false, with nothing changed, when the stream does not fit a chunk.
+inline bool PngFrameSetLength(const PngFrame& frame, OutputPlan* plan) {
+  const uint64_t n = PngFrameIdatBytes(plan->total_bits / 8, frame.file_prefix.size());
+  if (n > kPngMaxChunkBytes) return false;
+  PngStore32(plan->literals.data() + frame.file_prefix.size() - 8, static_cast<uint32_t>(n));
+  return true;
+}
+
+// An upper bound of the PNG file that zmx_png_encode_device / zmx_png_optimize_device (and their to-device forms) make of
+// an image of height rows in the mode (colortype, bitdepth):
+//   kPngMaxPrefixBytes + CompressBound(ZLIB, height * (linebytes + 1)) + kPngTrailerBytes.
+//  - The IDAT's payload is ZopfliCompress(ZLIB) of the filtered scanlines — the header's second byte differs, its size
+//    does not —, so CompressBound above bounds it, given the scanlines' size S.
+//  - S of the input's mode bounds S of the mode of the FIRST file.  S = height * (ceil(width * bpp / 8) + 1) rises with
+//    bpp, the bits per pixel, and colour reduction (png_color_choose.h, LodePNG's auto_choose_color) only ever picks a
+//    mode whose bpp is at most the input's: it drops channels that say nothing (alpha, colour), halves 16 bits to 8 when
+//    every sample's two bytes are equal, goes below 8 bits for grey, or to a palette of at most 8 bits per pixel where the
+//    input has at least 8 (colour types 0, 2, 4, 6 at 8 or 16 bits) — and otherwise keeps the input's mode.
+//  - The second try of a small palette file (PngRetryMode: RGB or RGBA at 8 bits) may have MORE bits per pixel than the
+//    input (grey + alpha at 8 bits retried as RGBA).  It needs no room of the caller's: it is made into a buffer of the
+//    call's own and replaces the first file only when it is strictly smaller, so the file that is kept is never larger
+//    than the first.
+//  - --lossy_8bit halves the sample width before anything else (16 -> 8 bits, same colour type): bpp halves, S falls.
+//    --lossy_transparent rewrites pixels in place: S is unchanged.
+//  - CompressBound rises with its input size, so the bound of the largest S holds for the S actually used.
+//  - The prefix is at most kPngMaxPrefixBytes (signature, IHDR, a full PLTE and tRNS, the IDAT's length and type).
+inline size_t PngBound(uint32_t width, uint32_t height, uint32_t colortype, uint32_t bitdepth) {
+  const size_t scanlines = static_cast<size_t>(height) * (PngLineBytes(width, colortype, bitdepth) + 1);
+  return kPngMaxPrefixBytes + CompressBound(ZOPFLI_FORMAT_ZLIB, scanlines) + kPngTrailerBytes;
+}
+inline size_t PngBatchBound(size_t n, const zmx_png_image* images, size_t align) {
+  size_t sum = 0;
+  for (size_t i = 0; i < n; ++i) sum += AlignUp(PngBound(images[i].width, images[i].height, images[i].colortype, images[i].bitdepth), align);
+  return sum;
+}
+
+// ---- the two to-device compress entries with a frame (device_output.cc, batch.cc; for png_encode.cc)
+// zmx_compress_device_to_device under the name `who`; `frame` non-null: ZOPFLI_FORMAT_ZLIB with the frame around it, the
+// CRC-32 sealed after the join, while the call still holds its contexts.  A stream that does not fit an IDAT is refused
+// like a capacity that is too small: *outsize = the file's size, d_out untouched.
+int CompressDeviceToDevice(const char* who, const ZopfliOptions* options, ZopfliFormat output_type, const void* d_in, size_t insize,
+                           void* d_out, size_t capacity, size_t* outsize, const PngFrame* frame);
+// zmx_compress_device_batch_packed(ZOPFLI_FORMAT_ZLIB) under the name `who` with frames[i] around stream i: one join for
+// all files, then one seal (two launches) for all of them.
+int CompressDeviceBatchPackedFramed(const char* who, const ZopfliOptions* options, size_t n, const void* const* d_in, const size_t* insize,
+                                    const PngFrame* frames, void* d_arena, size_t capacity, size_t align, size_t* outoffset, size_t* outsize);
 
 }  // namespace zamd

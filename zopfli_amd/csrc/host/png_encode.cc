@@ -14,12 +14,16 @@
 // ZMX_PNG_FILTER_AUTO is zopflipng's own choice of the strategy (zmx_png_choose_strategy_device, further down): made on the
 // first hold of the context, after the rewrite and the 8-bit conversion, image by image in the batches; everything after
 // is the entry's path with the strategy chosen.
+// The _to_device entries and zmx_png_encode_device_batch_packed leave the file in device memory: the same first hold (the
+// *FrontHalf functions, shared with the host-output entries), then the to-device compress path with the file's frame
+// around the stream (device_output_plan.h: PngFrame) and the IDAT's CRC-32 sealed on the device.
 #include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "dealing.h"
 #include "deflate.h"
+#include "device_output_plan.h"
 #include "png_color_choose.h"
 #include "png_container.h"
 #include "zmx_internal.h"
@@ -145,6 +149,47 @@ bool LossyOk(unsigned lossy) { return (lossy & ~(ZMX_PNG_LOSSY_TRANSPARENT | ZMX
 int BadStream(const std::string& w) {
   zmx_internal_set_error((w + ": the zlib stream does not fit an IDAT chunk").c_str(), ZMX_ERR_DEVICE);
   return -1;
+}
+
+// Where a to-device entry leaves its file (or, for the packed batch, all files): null for the host-output entries.
+struct DeviceDest {
+  void* d_out;
+  size_t capacity;
+};
+
+// What a to-device entry refuses of its destination before anything runs: not plain device memory, another device than
+// the images', a byte shared with any of the n images (pixels[i][0, nbytes[i])).
+int CheckDest(const std::string& w, const DeviceDest& dest, int img_device, size_t n, const void* const* pixels, const size_t* nbytes) {
+  if (dest.capacity != 0 && dest.d_out == nullptr) return Refuse(w + ": d_out: null pointer with a non-zero size");
+  int device = -1;
+  if (zmx_internal_device_pointer((w + ": d_out").c_str(), dest.d_out, dest.capacity, &device) != 0) return -1;
+  if (dest.capacity == 0) return 0;
+  if (device != img_device) return Refuse(w + ": the image and d_out lie on different devices");
+  const uintptr_t b = reinterpret_cast<uintptr_t>(dest.d_out);
+  for (size_t i = 0; i < n; ++i) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(pixels[i]);
+    if (a < b + dest.capacity && b < a + nbytes[i]) return Refuse(w + ": d_out overlaps image " + std::to_string(i));
+  }
+  return 0;
+}
+
+// The frame of the file of `im` (device_output_plan.h): in `mode`, or as it is (null)
+zamd::PngFrame FrameOf(const zmx_png_image& im, const zmx_png_color_mode* mode) {
+  zamd::PngFrame frame;
+  if (!mode) {
+    frame.file_prefix.resize(zamd::kPngPrefixBytes);
+    zamd::PngPrefix(im.width, im.height, im.colortype, im.bitdepth, frame.file_prefix.data());
+  } else {
+    frame.file_prefix.resize(zamd::kPngMaxPrefixBytes);
+    frame.file_prefix.resize(zamd::PngPrefixReduced(im.width, im.height, mode->colortype, mode->bitdepth, mode->palette, mode->palettesize,
+                                                    mode->key_defined != 0, mode->key_r, mode->key_g, mode->key_b, frame.file_prefix.data()));
+  }
+  return frame;
+}
+
+// room that does for the file around `scanlines` filtered bytes, whatever its prefix
+size_t FileBound(size_t scanlines) {
+  return zamd::kPngMaxPrefixBytes + zamd::CompressBound(ZOPFLI_FORMAT_ZLIB, scanlines) + zamd::kPngTrailerBytes;
 }
 
 }  // namespace
@@ -279,46 +324,83 @@ extern "C" int zmx_png_choose_strategy_device(zmx_ctx* ctx, const zmx_png_image*
 
 namespace {
 
-int EncodeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
-              unsigned lossy, unsigned char** out, size_t* outsize) {
-  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
-  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+// What zmx_png_encode_device[_lossy] and zmx_png_encode_device_to_device share: the checks (`dest`: the to-device entry's
+// destination, checked with them) and the first hold of a context, which leaves the filtered scanlines in `scan`.
+struct EncodeFront {
   Geometry g;
+  DeviceBuffer scan, rewritten;
+};
+
+int EncodeFrontHalf(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
+                    unsigned lossy, const DeviceDest* dest, EncodeFront* f) {
+  if (!options || !image) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+  Geometry& g = f->g;
   if (CheckImage(w, *image, &g) != 0) return -1;
   if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
   if (CheckPredefined(w, strategy, predefined, g.height) != 0) return -1;
   const LossyPlan plan = PlanLossy(*image, g, lossy, false);
   if (CheckRewritable(w, *image, plan) != 0) return -1;
-  DeviceBuffer scan, rewritten;
-  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, g.linebytes * g.height, &scan.device) != 0) return -1;
+  DeviceBuffer& scan = f->scan;
+  DeviceBuffer& rewritten = f->rewritten;
+  const size_t nbytes = g.linebytes * g.height;
+  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, nbytes, &scan.device) != 0) return -1;
+  if (dest && CheckDest(w, *dest, scan.device, 1, &image->d_pixels, &nbytes) != 0) return -1;
   if (zmx_internal_device_alloc(scan.device, g.scanlines, &scan.p) != 0) return -1;
   rewritten.device = scan.device;
   if (plan.bytes != 0 && zmx_internal_device_alloc(scan.device, plan.bytes, &rewritten.p) != 0) return -1;
   zmx_png_image work = *image;
   // (the context is held for the rewrite, the types and the rows only)
-  const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
     if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), image, 0, 1, rewritten.p, &work) != 0) return -1;
     if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, scan.device, work, false, nullptr, predefined, &strategy, nullptr) != 0) return -1;
     return zmx_internal_png_scanlines(ctx, work.d_pixels, g.linebytes, g.height, g.bytewidth, strategy, kBruteWindow, predefined, scan.p);
   }, scan.device);
-  if (rc != 0) return -1;
+}
+
+int EncodeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
+              unsigned lossy, unsigned char** out, size_t* outsize) {
+  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
+  EncodeFront f;
+  if (EncodeFrontHalf(w, options, image, strategy, predefined, lossy, nullptr, &f) != 0) return -1;
   File file;
   file.Begin(*image);
-  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan.p, g.scanlines, &file.bytes, &file.size) != 0) return -1;
+  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, f.scan.p, f.g.scanlines, &file.bytes, &file.size) != 0) return -1;
   if (!file.Close()) return BadStream(w);
   file.GiveTo(out, outsize);
   return 0;
 }
 
-int EncodeBatch(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy, unsigned lossy,
-                unsigned char** out, size_t* outsize) {
-  if (n == 0) return 0;
-  if (!options || !images || !out || !outsize) return Refuse(w + ": null argument");
+// The file left in device memory: the stream goes zmx_compress_device_to_device's way with the file's frame around it.
+int EncodeOneToDevice(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                      const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
+  if (!options || !image || !outsize) return Refuse(w + ": null argument");
+  *outsize = 0;
+  const DeviceDest dest{d_out, capacity};
+  EncodeFront f;
+  if (EncodeFrontHalf(w, options, image, strategy, predefined, lossy, &dest, &f) != 0) return -1;
+  const zamd::PngFrame frame = FrameOf(*image, nullptr);
+  return zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, f.scan.p, f.g.scanlines, d_out, capacity, outsize, &frame);
+}
+
+// What zmx_png_encode_device_batch[_lossy] and zmx_png_encode_device_batch_packed share (n > 0): the checks (`dest`: the
+// arena, checked with them) and the one hold of a context, which leaves image i's filtered scanlines at scan + start[i].
+struct BatchFront {
+  std::vector<Geometry> g;
+  std::vector<size_t> start;
+  DeviceBuffer scan, rewritten;
+};
+
+int EncodeBatchFrontHalf(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy, unsigned lossy,
+                         const DeviceDest* dest, BatchFront* f) {
+  if (!options || !images) return Refuse(w + ": null argument");
   if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
   if (strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
   if (!StrategyOk(strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
-  std::vector<Geometry> g(n);
-  std::vector<size_t> start(n + 1, 0);   // where image i's scanlines begin in the one buffer
+  std::vector<Geometry>& g = f->g;
+  std::vector<size_t>& start = f->start;   // where image i's scanlines begin in the one buffer
+  g.resize(n);
+  start.assign(n + 1, 0);
   std::vector<size_t> rstart(n + 1, 0);  // and its rewritten pixels in theirs
   std::vector<LossyPlan> plan(n);
   std::vector<const void*> pixels(n);
@@ -334,14 +416,16 @@ int EncodeBatch(const std::string& w, const ZopfliOptions* options, size_t n, co
     pixels[i] = images[i].d_pixels;
     nbytes[i] = g[i].linebytes * g[i].height;
   }
-  DeviceBuffer scan, rewritten;
+  DeviceBuffer& scan = f->scan;
+  DeviceBuffer& rewritten = f->rewritten;
   if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &scan.device) != 0) return -1;
+  if (dest && CheckDest(w, *dest, scan.device, n, pixels.data(), nbytes.data()) != 0) return -1;
   if (zmx_internal_device_alloc(scan.device, start[n], &scan.p) != 0) return -1;
   rewritten.device = scan.device;
   if (rstart[n] != 0 && zmx_internal_device_alloc(scan.device, rstart[n], &rewritten.p) != 0) return -1;
   unsigned char* const base = static_cast<unsigned char*>(scan.p);
   // (one hold of a context for all images; a launch set per image: tools/png_device.py measures what that costs)
-  const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
     for (size_t i = 0; i < n; ++i) {
       zmx_png_image work = images[i];
       if (plan[i].bytes != 0 &&
@@ -357,7 +441,17 @@ int EncodeBatch(const std::string& w, const ZopfliOptions* options, size_t n, co
     }
     return 0;
   }, scan.device);
-  if (rc != 0) return -1;
+}
+
+int EncodeBatch(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy, unsigned lossy,
+                unsigned char** out, size_t* outsize) {
+  if (n == 0) return 0;
+  if (!options || !images || !out || !outsize) return Refuse(w + ": null argument");
+  BatchFront f;
+  if (EncodeBatchFrontHalf(w, options, n, images, strategy, lossy, nullptr, &f) != 0) return -1;
+  const std::vector<Geometry>& g = f.g;
+  const std::vector<size_t>& start = f.start;
+  unsigned char* const base = static_cast<unsigned char*>(f.scan.p);
   std::vector<const void*> slices(n);
   std::vector<size_t> sizes(n);
   std::vector<File> files(n);
@@ -384,7 +478,50 @@ int EncodeBatch(const std::string& w, const ZopfliOptions* options, size_t n, co
   return 0;
 }
 
+// The files left in one arena: zmx_compress_device_batch_packed's plan with a frame per stream.
+int EncodeBatchPacked(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy, unsigned lossy,
+                      void* d_arena, size_t capacity, size_t align, size_t* outoffset, size_t* outsize) {
+  if (n == 0) return 0;
+  if (!options || !images || !outoffset || !outsize) return Refuse(w + ": null argument");
+  if (!zamd::PackedAlignOk(align)) return Refuse(w + ": align " + std::to_string(align) + " is not a power of two from 1 to 4096");
+  const DeviceDest dest{d_arena, capacity};
+  BatchFront f;
+  if (EncodeBatchFrontHalf(w, options, n, images, strategy, lossy, &dest, &f) != 0) return -1;
+  std::vector<const void*> slices(n);
+  std::vector<size_t> sizes(n);
+  std::vector<zamd::PngFrame> frames(n);
+  for (size_t i = 0; i < n; ++i) {
+    slices[i] = static_cast<unsigned char*>(f.scan.p) + f.start[i];
+    sizes[i] = f.g[i].scanlines;
+    frames[i] = FrameOf(images[i], nullptr);
+  }
+  return zamd::CompressDeviceBatchPackedFramed(w.c_str(), options, n, slices.data(), sizes.data(), frames.data(), d_arena, capacity, align,
+                                               outoffset, outsize);
+}
+
 }  // namespace
+
+extern "C" size_t zmx_png_bound(uint32_t width, uint32_t height, uint32_t colortype, uint32_t bitdepth) {
+  if (width == 0 || height == 0 || !zamd::PngFormatOk(colortype, bitdepth)) return 0;
+  return zamd::PngBound(width, height, colortype, bitdepth);
+}
+extern "C" size_t zmx_png_batch_bound(size_t n, const zmx_png_image* images, size_t align) {
+  if (n == 0 || !images || !zamd::PackedAlignOk(align)) return 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (images[i].width == 0 || images[i].height == 0 || !zamd::PngFormatOk(images[i].colortype, images[i].bitdepth)) return 0;
+  }
+  return zamd::PngBatchBound(n, images, align);
+}
+extern "C" int zmx_png_encode_device_to_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                               const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
+  return EncodeOneToDevice("zmx_png_encode_device_to_device", options, image, strategy, predefined, lossy, d_out, capacity, outsize);
+}
+extern "C" int zmx_png_encode_device_batch_packed(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                                  unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
+                                                  size_t* outsize) {
+  return EncodeBatchPacked("zmx_png_encode_device_batch_packed", options, n, images, strategy, lossy, d_arena, capacity, align, outoffset,
+                           outsize);
+}
 
 extern "C" int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
                                      const unsigned char* predefined, unsigned char** out, size_t* outsize) {
@@ -419,51 +556,84 @@ File& Smaller(File& first, File& second) { return second.size < first.size ? sec
 
 namespace {
 
-int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
-                unsigned lossy, unsigned char** out, size_t* outsize) {
-  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
+// What zmx_png_optimize_device[_lossy] and zmx_png_optimize_device_to_device share: the checks (`dest`: the to-device
+// entry's destination, checked with them) and the first hold of a context, which leaves the first file's scanlines in
+// `scan`; and the second try's scanlines, on a second hold.
+struct OptimizeFront {
+  int device = -1;
+  int strategy = 0;         // the one the rows were made with (_AUTO: the chosen one)
+  Reduced r;
+  DeviceBuffer scan, rewritten;
+  zmx_png_image work;       // what is encoded: the caller's image, or its 8-bit or rewritten image in `rewritten`
+};
+
+int OptimizeFrontHalf(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                      const unsigned char* predefined, unsigned lossy, const DeviceDest* dest, OptimizeFront* f) {
+  if (!options || !image) return Refuse(w + ": null argument");
   if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
   Geometry g;
   if (CheckReducible(w, *image, &g) != 0) return -1;
   if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
   if (CheckPredefined(w, strategy, predefined, g.height) != 0) return -1;
-  int device = -1;
-  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, g.linebytes * g.height, &device) != 0) return -1;
-  const uint64_t numpixels = static_cast<uint64_t>(image->width) * image->height;
+  int& device = f->device;
+  const size_t nbytes = g.linebytes * g.height;
+  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, nbytes, &device) != 0) return -1;
+  if (dest && CheckDest(w, *dest, device, 1, &image->d_pixels, &nbytes) != 0) return -1;
   const LossyPlan plan = PlanLossy(*image, g, lossy, true);
-  Reduced r;
-  DeviceBuffer scan, rewritten;
+  Reduced& r = f->r;
+  DeviceBuffer& scan = f->scan;
+  DeviceBuffer& rewritten = f->rewritten;
   scan.device = rewritten.device = device;
   if (plan.bytes != 0 && zmx_internal_device_alloc(device, plan.bytes, &rewritten.p) != 0) return -1;
-  zmx_png_image work = *image;   // what is encoded: the caller's image, or its 8-bit or rewritten image in `rewritten`
+  zmx_png_image& work = f->work;
+  work = *image;
   // (the context is held for the rewrite, the statistics, the conversion, the types and the rows only)
-  int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+  const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
     if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), image, plan.to8, plan.transparent, rewritten.p, &work) != 0) return -1;
     if (StatsAndMode(ctx, work, &r) != 0) return -1;
     if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, device, work, true, &r, predefined, &strategy, nullptr) != 0) return -1;
     if (zmx_internal_device_alloc(device, r.scanlines, &scan.p) != 0) return -1;
     return zmx_internal_png_reduced_scanlines(ctx, &work, r.as_is ? nullptr : &r.mode, strategy, kBruteWindow, predefined, scan.p);
   }, device);
-  if (rc != 0) return -1;
+  f->strategy = strategy;
+  return rc;
+}
+
+// zopflipng's second try — without the palette's overhead — is due: the first file is a palette file of `first_bytes`
+inline bool SecondTryDue(const OptimizeFront& f, size_t first_bytes) { return f.r.mode.colortype == 3 && first_bytes < zamd::kPngRetryBelow; }
+
+// its mode and its scanlines, into scan2
+int SecondTryScanlines(const OptimizeFront& f, const unsigned char* predefined, zmx_png_color_mode* retry, bool* as_is, size_t* scanlines,
+                       DeviceBuffer* scan2) {
+  zamd::PngRetryMode(f.r.stats, static_cast<uint64_t>(f.work.width) * f.work.height, retry);
+  *as_is = SameMode(f.work, *retry);
+  *scanlines = ScanlinesIn(f.work, *retry);
+  scan2->device = f.device;
+  if (zmx_internal_device_alloc(f.device, *scanlines, &scan2->p) != 0) return -1;
+  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    return zmx_internal_png_reduced_scanlines(ctx, &f.work, *as_is ? nullptr : retry, f.strategy, kBruteWindow, predefined, scan2->p);
+  }, f.device);
+}
+
+int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
+                unsigned lossy, unsigned char** out, size_t* outsize) {
+  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
+  OptimizeFront f;
+  if (OptimizeFrontHalf(w, options, image, strategy, predefined, lossy, nullptr, &f) != 0) return -1;
+  const Reduced& r = f.r;
+  const zmx_png_image& work = f.work;
   File file;
   if (r.as_is) file.Begin(work);
   else file.BeginReduced(work, r.mode);
-  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan.p, r.scanlines, &file.bytes, &file.size) != 0) return -1;
+  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, f.scan.p, r.scanlines, &file.bytes, &file.size) != 0) return -1;
   if (!file.Close()) return BadStream(w);
   File second;
-  if (r.mode.colortype == 3 && file.size < zamd::kPngRetryBelow) {
-    // zopflipng's second try: without the palette's overhead
+  if (SecondTryDue(f, file.size)) {
     zmx_png_color_mode retry;
-    zamd::PngRetryMode(r.stats, numpixels, &retry);
-    const bool as_is = SameMode(work, retry);
-    const size_t scanlines = ScanlinesIn(work, retry);
+    bool as_is = false;
+    size_t scanlines = 0;
     DeviceBuffer scan2;
-    scan2.device = device;
-    if (zmx_internal_device_alloc(device, scanlines, &scan2.p) != 0) return -1;
-    rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-      return zmx_internal_png_reduced_scanlines(ctx, &work, as_is ? nullptr : &retry, strategy, kBruteWindow, predefined, scan2.p);
-    }, device);
-    if (rc != 0) return -1;
+    if (SecondTryScanlines(f, predefined, &retry, &as_is, &scanlines, &scan2) != 0) return -1;
     if (as_is) second.Begin(work);
     else second.BeginReduced(work, retry);
     if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines, &second.bytes, &second.size) != 0) return -1;
@@ -475,7 +645,62 @@ int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_pn
   return 0;
 }
 
+// The file left in device memory.  A mode other than a palette: the one file goes straight into d_out, as the encode
+// entry's.  A palette: which file is kept, and so its size, is known only when the first is made — so the first goes into
+// a buffer of the call's own, the second (where one is due) into another, and ONE device-to-device copy puts the kept file
+// into d_out: every byte of the file is written and none outside it, and a capacity of exactly the kept file's size does.
+int OptimizeOneToDevice(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                        const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
+  if (!options || !image || !outsize) return Refuse(w + ": null argument");
+  *outsize = 0;
+  const DeviceDest dest{d_out, capacity};
+  OptimizeFront f;
+  if (OptimizeFrontHalf(w, options, image, strategy, predefined, lossy, &dest, &f) != 0) return -1;
+  const Reduced& r = f.r;
+  const zamd::PngFrame frame = FrameOf(f.work, r.as_is ? nullptr : &r.mode);
+  if (r.mode.colortype != 3) {
+    return zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, f.scan.p, r.scanlines, d_out, capacity, outsize, &frame);
+  }
+  DeviceBuffer first, second;
+  first.device = second.device = f.device;
+  const size_t room = FileBound(r.scanlines);
+  size_t first_bytes = 0, second_bytes = 0;
+  if (zmx_internal_device_alloc(f.device, room, &first.p) != 0) return -1;
+  if (zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, f.scan.p, r.scanlines, first.p, room, &first_bytes, &frame) != 0) {
+    *outsize = first_bytes;   // (a stream that fits no IDAT: the size it would have taken)
+    return -1;
+  }
+  const void* kept = first.p;
+  size_t kept_bytes = first_bytes;
+  if (SecondTryDue(f, first_bytes)) {
+    zmx_png_color_mode retry;
+    bool as_is = false;
+    size_t scanlines = 0;
+    DeviceBuffer scan2;
+    if (SecondTryScanlines(f, predefined, &retry, &as_is, &scanlines, &scan2) != 0) return -1;
+    const zamd::PngFrame frame2 = FrameOf(f.work, as_is ? nullptr : &retry);
+    const size_t room2 = FileBound(scanlines);
+    if (zmx_internal_device_alloc(f.device, room2, &second.p) != 0) return -1;
+    if (zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines, second.p, room2, &second_bytes, &frame2) != 0) return -1;
+    if (second_bytes < first_bytes) {
+      kept = second.p;
+      kept_bytes = second_bytes;
+    }
+  }
+  *outsize = kept_bytes;
+  if (kept_bytes > capacity) {
+    return Refuse(w + ": the file takes " + std::to_string(kept_bytes) + " bytes, d_out has " + std::to_string(capacity));
+  }
+  return zmx_internal_device_copy(f.device, d_out, kept, kept_bytes);
+}
+
 }  // namespace
+
+extern "C" int zmx_png_optimize_device_to_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                                 const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                                 size_t* outsize) {
+  return OptimizeOneToDevice("zmx_png_optimize_device_to_device", options, image, strategy, predefined, lossy, d_out, capacity, outsize);
+}
 
 extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
                                        const unsigned char* predefined, unsigned char** out, size_t* outsize) {

@@ -86,6 +86,9 @@ int zmx_internal_device_pointers(const char* who, size_t n, const void* const* p
 int zmx_internal_device_alloc(int device, size_t n, void** p);
 // Frees what zmx_internal_device_alloc gave (null: nothing).
 void zmx_internal_device_free(int device, void* p);
+// n bytes from d_src to d_dst, both plain memory of `device` that the caller has checked; done when it returns.  0, or -1
+// with the error set.
+int zmx_internal_device_copy(int device, void* d_dst, const void* d_src, size_t n);
 
 // ---- output that stays in device memory
 // zmx_bitjoin_device(ctx, n, pieces, total_bits, d_dst, dst_capacity) whose pieces with is_literal[i] != 0 come from
@@ -101,6 +104,11 @@ int zmx_internal_bitjoin_many_literals(zmx_ctx* ctx, const unsigned char* litera
 // device, -1 when every range is empty.  Refused (the message starts with `who` and names the range): what
 // zmx_internal_device_pointer refuses of any of them, and a range on another device than the ones before it.
 int zmx_internal_device_pointers_one_device(const char* who, size_t n, const void* const* p, const size_t* nbytes, int* device);
+
+// zmx_checksum_device(ctx, kind, n, d_ptr, nbytes, ...) over ranges the caller has checked, whose value i goes to the four
+// bytes at d_seal[i], most significant first, instead of the host: the IDAT's CRC-32 of a PNG left in device memory
+// (device_output.cc, batch.cc).  Two launches for all n, nothing comes down.  0, or -1 with the error set.
+int zmx_internal_checksum_seal(zmx_ctx* ctx, int kind, size_t n, const void* const* d_ptr, const size_t* nbytes, unsigned char* const* d_seal);
 
 // ---- a PNG from an image in device memory (png_encode.cc)
 // The filter types of `strategy` (a ZMX_PNG_FILTER_*; _BRUTE with window `windowsize`; _PREDEFINED: the `height` host
@@ -153,6 +161,9 @@ ZMX_INTERNAL_EXPORT void zmx_internal_png_lossy_ms(double out[3]);
 // The same for the calling thread's last zmx_png_deflate_sizes_device: k_png_lo_hash, k_png_lo_links, k_png_lo_ask,
 // k_png_lo_keep, k_png_lo_search, k_png_lo_parse.  For tools/png_auto.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_png_lodeflate_ms(double out[6]);
+// The same for the calling thread's last zmx_checksum_device (or seal): k_checksum_pieces, k_checksum_finish.  For
+// tools/png_device_output.py.
+ZMX_INTERNAL_EXPORT void zmx_internal_checksum_device_ms(double out[2]);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
 // squeeze run computes them — *wmax, *tiemask —, no device involved.
 ZMX_INTERNAL_EXPORT void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask);
