@@ -436,7 +436,8 @@ int zmx_png_filter_rows_device(zmx_ctx* ctx, const void* d_image, size_t linebyt
  * asked for; the file is then the one zopflipng --keepcolortype --always_zopflify writes with NO --filters for an input
  * whose rows carry filter type 0 — or, where `predefined` is given, the types at `predefined` (the eighth trial; if it
  * wins, the file is _PREDEFINED's).
- * Out of scope: palette input, interlace, ancillary chunks (libzopflipng_amd.so does those, from a file — its own strategy
+ * Palette input: done (zmx_png_index_encode_device, further down).  Out of scope: interlace, ancillary chunks
+ * (libzopflipng_amd.so does those, from a file — its own strategy
  * trials still run LodePNG on host threads).  Colour-type reduction is zmx_png_optimize_device's; the file left in device
  * memory is zmx_png_encode_device_to_device's, further down. */
 typedef struct zmx_png_image {
@@ -555,7 +556,8 @@ int zmx_png_convert_device(zmx_ctx* ctx, const zmx_png_image* image, const zmx_p
  * ZMX_PNG_FILTER_AUTO: zmx_png_choose_strategy_device(reduce_color = 1) chooses on the same hold of the context, with the
  * statistics the entry has taken; both tries of a small palette file are made with the chosen strategy, as zopflipng's
  * are.  The file is the one zopflipng --always_zopflify writes with no --filters.
- * Out of scope: palette INPUT, interlace, ancillary chunks (libzopflipng_amd.so does those, from a file).
+ * Palette input: done (zmx_png_index_optimize_device, further down).  Out of scope: interlace, ancillary chunks
+ * (libzopflipng_amd.so does those, from a file).
  * --lossy_transparent and --lossy_8bit are the _lossy entries' further down, the file left in device memory is
  * zmx_png_optimize_device_to_device's. */
 int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
@@ -666,6 +668,97 @@ size_t zmx_png_batch_bound(size_t n, const zmx_png_image* images, size_t align);
 int zmx_png_encode_device_batch_packed(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
                                        unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
                                        size_t* outsize);
+
+/* -------- palette, 1/2/4-bit grey and index images in device memory
+ *
+ * A label map (one byte a pixel plus a colour map), a binary mask (one bit a pixel), a 2- or 4-bit atlas: `height` rows of
+ * (width * bitdepth + 7) / 8 bytes back to back, the first pixel in a byte's top bits, the bits behind a row's last pixel
+ * anything.  Colour type 3 with a palette of 1 .. 2^bitdepth host entries r, g, b, a at 1, 2, 4 or 8 bits, or colour type
+ * 0 at 1, 2 or 4 bits, which goes through the same code with the grey ramp v * 255 / (2^bitdepth - 1) as its palette.
+ * zopflipng decodes such a PNG to RGBA8 — value i becomes palette[i] — and everything it and LodePNG then do follows from
+ * the palette and ONE fact about the pixels: at which pixel each of the 256 values first appears.  So the device work is
+ * one read of the image and one table-driven rewrite; nothing is expanded to RGBA, and --lossy_transparent is a change of
+ * the host's table.
+ *   zmx_png_index_use_device      first[v] = the smallest raster pixel index (row * width + column) at which value v
+ *                                 occurs, 2^64 - 1 for a value no pixel has.  k_png_index_use (device/zmx_png_index.h)
+ *                                 reads the image once with at most 2048 workgroups; padding bits are no pixels; a
+ *                                 minimum of positions, equal from run to run.  Values at or above palettesize are
+ *                                 reported like any other.
+ *   zmx_png_index_color_stats     host arithmetic (host/png_index.h): the statistics zmx_png_color_stats_device gives for
+ *                                 the RGBA8 expansion of the image — after zopflipng's rewrite of the transparent pixels
+ *                                 where `lossy` has ZMX_PNG_LOSSY_TRANSPARENT (every used entry with alpha 0 gets the RGB of
+ *                                 the first transparent pixel; _8BIT does nothing here).  A colour's first appearance is the
+ *                                 minimum over the values that carry it.  Refused: a value at or above palettesize
+ *                                 that occurs (the message names its first pixel, "pixel N").
+ *   zmx_png_index_table           host arithmetic: the 256 entries that take the image into `mode` (after the same rewrite):
+ *                                 the rank in the mode's palette (of two equal entries the later, as LodePNG's colour tree
+ *                                 keeps it), the grey value's top bits, or the bytes grey alpha / r g b / r g b a, the first
+ *                                 in the entry's low byte.
+ *   zmx_png_index_keep_plan       host arithmetic: the mode of zopflipng --keepcolortype's file — the input's own, with the
+ *                                 whole palette in the input's order, unused entries included; after _TRANSPARENT the
+ *                                 palette shrunk to the entries whose own colour still occurs, as zopflipng_lib.cc:137-155
+ *                                 shrinks it — and the table into it.
+ *   zmx_png_index_convert_device  the image through `table` into `mode`: a palette or grey at 1, 2, 4, 8 bits, grey + alpha,
+ *                                 RGB or RGBA at 8.  d_out gets `height` rows of (width * bpp + 7) / 8 bytes, packed most
+ *                                 significant bits first, rows padded with ZERO bits; k_png_index_convert writes every
+ *                                 byte of the output exactly once and none outside, source and destination at any
+ *                                 alignment.  A pixel whose value is at or above palettesize is found by the kernel: the
+ *                                 call fails (ZMX_ERR_REFUSED), the message names the first such pixel ("pixel N"), and what
+ *                                 d_out then holds is not defined.
+ * The two device steps are synchronous and check their pointers as zmx_png_filter_rows_device checks its own.  Refused
+ * before any launch (ZMX_ERR_REFUSED), by every entry of this section: width or height 0, another colour type or depth,
+ * palettesize 0 or above 2^bitdepth, an image of 2^32 pixels or more; by the convert step a mode outside the list above and
+ * a `capacity` below the output's size.
+ *
+ * zmx_png_index_encode_device: *out, *outsize (zmx_png_encode_device's conventions) end holding the file
+ *   zopflipng --keepcolortype --always_zopflify --filters=<strategy> [--lossy_transparent]
+ * writes for a PNG of this image that has no other chunks; zmx_png_index_optimize_device the file of the same command
+ * WITHOUT --keepcolortype — byte for byte zmx_png_optimize_device_lossy's file of the RGBA8 expansion, second try below
+ * 4096 bytes included, for every strategy and both lossy flags.  One k_png_index_use, the host step, one
+ * k_png_index_convert (two with a second try; one more for each mode ZMX_PNG_FILTER_AUTO's trials need), then the row
+ * search, the filtered scanlines and the compression of the existing entries.  No pixel and no index visits the host
+ * (zmx_last_input_traffic()[0] is 0); the caller's image is never written.  `strategy`, `predefined`, `lossy`, refusals and
+ * failure behaviour are zmx_png_encode_device_lossy's / zmx_png_optimize_device_lossy's, with the image refused as above and
+ * a value at or above palettesize refused once the first kernel has found it (*out, *outsize untouched).
+ * zmx_png_index_choose_strategy_device is zmx_png_choose_strategy_device for such an image, `lossy` applied first.
+ * The _to_device forms leave the file in device memory as zmx_png_encode_device_to_device does — the same frame, one bit
+ * join, the CRC-32 sealed on the device, no byte of the file on the host —; zmx_png_index_bound(width, height, colortype,
+ * bitdepth) is always enough for both (sized for RGBA at 8 bits, which the second try can be; 0 for an image the entries
+ * refuse).  The batches give every out[i], outsize[i] the single entry's file, image by image one k_png_index_use, the host
+ * step and one k_png_index_convert, then ONE zmx_compress_device_batch(ZLIB) over all scanlines and one more for the second
+ * tries; _PREDEFINED is the single call's; n = 0 returns 0.
+ * Out of scope: a packed to-device batch of these, interlace, ancillary chunks, a tRNS key on grey input. */
+typedef struct zmx_png_index_image {
+  const void* d_pixels;        /* height rows of (width * bitdepth + 7) / 8 bytes, first pixel in a byte's top bits, rows back to back */
+  uint32_t width, height;
+  uint32_t colortype;          /* 3 (palette) or 0 (grey) */
+  uint32_t bitdepth;           /* 3: 1, 2, 4, 8    0: 1, 2, 4 */
+  uint32_t palettesize;        /* 3: 1 .. 2^bitdepth    0: not read */
+  unsigned char palette[1024]; /* host memory: r, g, b, a per entry */
+} zmx_png_index_image;
+int zmx_png_index_use_device(zmx_ctx* ctx, const zmx_png_index_image* image, uint64_t first[256]);
+int zmx_png_index_color_stats(const zmx_png_index_image* image, const uint64_t first[256], unsigned lossy, zmx_png_color_stats* out);
+int zmx_png_index_table(const zmx_png_index_image* image, const uint64_t first[256], unsigned lossy, const zmx_png_color_mode* mode,
+                        uint32_t table[256]);
+int zmx_png_index_keep_plan(const zmx_png_index_image* image, const uint64_t first[256], unsigned lossy, zmx_png_color_mode* mode,
+                            uint32_t table[256]);
+int zmx_png_index_convert_device(zmx_ctx* ctx, const zmx_png_index_image* image, const zmx_png_color_mode* mode, const uint32_t table[256],
+                                 void* d_out, size_t capacity);
+int zmx_png_index_choose_strategy_device(zmx_ctx* ctx, const zmx_png_index_image* image, int reduce_color, unsigned lossy,
+                                         const unsigned char* predefined, int* strategy, uint64_t file_bytes[8]);
+int zmx_png_index_encode_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_index_optimize_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                  const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize);
+size_t zmx_png_index_bound(uint32_t width, uint32_t height, uint32_t colortype, uint32_t bitdepth);
+int zmx_png_index_encode_device_to_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                          const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize);
+int zmx_png_index_optimize_device_to_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                            const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize);
+int zmx_png_index_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
+                                      unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_index_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
+                                        unsigned lossy, unsigned char** out, size_t* outsize);
 
 /* Parity probe over whole tables: two 64-bit sums over all positions of a hash of the logical content of the match
  * records (block, position, length, distance, same, literal, every change point of sublen).  Equal digests of two

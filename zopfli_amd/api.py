@@ -643,6 +643,214 @@ def png_encode_device_batch_packed(images, arena, align=1, strategy="e", options
     return [int(offsets[i]) for i in range(n)], [int(outsizes[i]) for i in range(n)]
 
 
+class PngIndexImage(ctypes.Structure):
+    """zmx_png_index_image"""
+    _fields_ = [("d_pixels", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("colortype", ctypes.c_uint32),
+                ("bitdepth", ctypes.c_uint32), ("palettesize", ctypes.c_uint32), ("palette", ctypes.c_ubyte * 1024)]
+
+
+def _png_index_image(image, palette=None, bitdepth=8, sync=True):
+    """The zmx_png_index_image of (tensor or pointer, width, height, colortype, bitdepth, palette) — rows of
+    (width * bitdepth + 7) // 8 bytes, colour type 3 with a palette or 0 (grey at 1, 2, 4 bits; palette None) — or of a
+    2-D uint8 CUDA tensor of indices with `palette` and bitdepth 8.  A palette is n x 4 (r, g, b, a) or n x 3 (opaque)
+    uint8 values, anything numpy.asarray takes."""
+    import numpy as np
+    if isinstance(image, (tuple, list)):
+        src, width, height, colortype, bitdepth, palette = image
+        ptr = int(src) if isinstance(src, int) else _device_range(src, None, sync=sync)[0]
+    else:
+        shape = tuple(image.shape)
+        if len(shape) != 2 or image.element_size() != 1 or int(bitdepth) != 8:
+            raise ValueError("an index tensor is uint8 of shape (H, W) at 8 bits; packed rows go as "
+                             "(tensor_or_pointer, width, height, colortype, bitdepth, palette)")
+        ptr, _ = _device_range(image, None, sync=sync)
+        height, width, colortype = shape[0], shape[1], 3
+    im = PngIndexImage(ptr or None, int(width), int(height), int(colortype), int(bitdepth), 0)
+    if palette is not None:
+        pal = np.asarray(palette, dtype=np.uint8)
+        if pal.ndim != 2 or pal.shape[1] not in (3, 4) or pal.shape[0] > 256:
+            raise ValueError("a palette is at most 256 rows of r, g, b, a or r, g, b")
+        if pal.shape[1] == 3:
+            pal = np.concatenate([pal, np.full((pal.shape[0], 1), 255, dtype=np.uint8)], axis=1)
+        im.palettesize = pal.shape[0]
+        ctypes.memmove(im.palette, np.ascontiguousarray(pal).ctypes.data, 4 * pal.shape[0])
+    elif int(colortype) == 3:
+        raise ValueError("a palette image needs its palette")
+    return im
+
+
+def _png_types(predefined, height):
+    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
+    if types is not None and len(types) != height:
+        raise ValueError(f"{len(types)} predefined types for {height} rows")
+    return types
+
+
+def _png_index_single(name, image, strategy, options, predefined, lib, lossy_transparent, palette, bitdepth):
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    im = _png_index_image(image, palette, bitdepth)
+    types = _png_types(predefined, im.height)
+    out, outsize = _u8p(), ctypes.c_size_t(0)
+    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
+    fn = getattr(lib, name)
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngIndexImage), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint,
+                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, _png_lossy(lossy_transparent, False), ctypes.byref(out),
+          ctypes.byref(outsize)) != 0:
+        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
+    return _take(out, outsize)
+
+
+def png_index_encode_device(image, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, palette=None, bitdepth=8):
+    """zmx_png_index_encode_device: a palette, 1/2/4-bit grey or index image in device memory — a label map with its colour
+    map, a mask, an atlas — as the PNG file `zopflipng --keepcolortype --always_zopflify --filters=<strategy>
+    [--lossy_transparent]` writes for it: the input's colour type, depth and palette, in the input's order.  `image`:
+    (tensor or pointer, width, height, colortype, bitdepth, palette) with rows of (width * bitdepth + 7) // 8 bytes, the
+    first pixel in a byte's top bits — colour type 3 at 1, 2, 4, 8 bits with a palette of n x 4 or n x 3 uint8 values, or
+    colour type 0 at 1, 2, 4 bits with palette None — or a 2-D uint8 CUDA tensor of indices with `palette=` and
+    `bitdepth=8`.  `strategy`, `predefined`, result and errors as png_encode_device's."""
+    return _png_index_single("zmx_png_index_encode_device", image, strategy, options, predefined, lib, lossy_transparent, palette, bitdepth)
+
+
+def png_index_optimize_device(image, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, palette=None, bitdepth=8):
+    """zmx_png_index_optimize_device: the same without --keepcolortype — byte for byte png_optimize_device's file of the
+    image expanded to RGBA8, with no expansion made.  Arguments as png_index_encode_device's."""
+    return _png_index_single("zmx_png_index_optimize_device", image, strategy, options, predefined, lib, lossy_transparent, palette, bitdepth)
+
+
+def _png_index_out(name, image, dst, strategy, options, predefined, lib, lossy_transparent, palette, bitdepth):
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    im = _png_index_image(image, palette, bitdepth)
+    types = _png_types(predefined, im.height)
+    out, capacity = _device_range(int(dst[0]), dst[1]) if isinstance(dst, (tuple, list)) else _device_range(dst, None)
+    outsize = ctypes.c_size_t(0)
+    fn = getattr(lib, name)
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngIndexImage), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint, ctypes.c_void_p,
+                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, _png_lossy(lossy_transparent, False), out, capacity,
+          ctypes.byref(outsize)) != 0:
+        message = name + ": " + (lib.zmx_last_error() or b"").decode()
+        if outsize.value > capacity:
+            raise CapacityError(message, int(outsize.value))
+        raise RuntimeError(message)
+    return int(outsize.value)
+
+
+def png_index_encode_device_out(image, dst, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, palette=None,
+                                bitdepth=8):
+    """zmx_png_index_encode_device_to_device: png_index_encode_device's file left in device memory; `dst`, result and
+    errors as png_encode_device_out's — png_index_bound gives a capacity that always does."""
+    return _png_index_out("zmx_png_index_encode_device_to_device", image, dst, strategy, options, predefined, lib, lossy_transparent, palette,
+                          bitdepth)
+
+
+def png_index_optimize_device_out(image, dst, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, palette=None,
+                                  bitdepth=8):
+    """zmx_png_index_optimize_device_to_device: png_index_optimize_device's file left in device memory."""
+    return _png_index_out("zmx_png_index_optimize_device_to_device", image, dst, strategy, options, predefined, lib, lossy_transparent, palette,
+                          bitdepth)
+
+
+def _png_index_batch(name, images, strategy, options, lib, lossy_transparent):
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    ims = [_png_index_image(image, sync=False) for image in images]
+    devices = {}
+    for image in images:
+        src = image[0] if isinstance(image, (tuple, list)) else image
+        if type(src).__module__.split(".")[0] == "torch":
+            devices[str(src.device)] = src.device
+    if devices:
+        import torch
+        for device in devices.values():
+            torch.cuda.current_stream(device).synchronize()
+    n = len(ims)
+    arr = (PngIndexImage * max(n, 1))(*ims)
+    outs = (_u8p * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    fn = getattr(lib, name)
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngIndexImage), ctypes.c_int, ctypes.c_uint,
+                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), _png_lossy(lossy_transparent, False), outs, outsizes) != 0:
+        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
+    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+
+
+def png_index_encode_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False):
+    """zmx_png_index_encode_device_batch: one file per image, each the one png_index_encode_device gives, from one call
+    that shares its deflate work among them.  `images`: a list of (tensor or pointer, width, height, colortype, bitdepth,
+    palette) tuples.  Predefined types are the single call's."""
+    return _png_index_batch("zmx_png_index_encode_device_batch", images, strategy, options, lib, lossy_transparent)
+
+
+def png_index_optimize_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False):
+    """zmx_png_index_optimize_device_batch: one file per image, each the one png_index_optimize_device gives."""
+    return _png_index_batch("zmx_png_index_optimize_device_batch", images, strategy, options, lib, lossy_transparent)
+
+
+def png_index_bound(width, height, colortype, bitdepth, lib=None):
+    """zmx_png_index_bound: a destination capacity that does for png_index_encode_device_out and
+    png_index_optimize_device_out of any such image (0 for one the entries refuse)."""
+    lib = lib or library()
+    fn = lib.zmx_png_index_bound
+    fn.argtypes = [ctypes.c_uint32] * 4
+    fn.restype = ctypes.c_size_t
+    return int(fn(int(width), int(height), int(colortype), int(bitdepth)))
+
+
+def _png_first(first):
+    return (ctypes.c_uint64 * 256)(*[int(f) for f in first])
+
+
+def png_index_color_stats(image, first, lossy_transparent=False, lib=None):
+    """zmx_png_index_color_stats: the PngColorStats of the image's RGBA8 expansion (after --lossy_transparent where asked)
+    from its first-appearance table (Context.png_index_use_device).  Host arithmetic only; the pixels are not looked at."""
+    lib = lib or library()
+    im = _png_index_image(image, sync=False) if isinstance(image, (tuple, list)) else image
+    stats = PngColorStats()
+    fn = lib.zmx_png_index_color_stats
+    fn.argtypes = [ctypes.POINTER(PngIndexImage), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint, ctypes.POINTER(PngColorStats)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(im), _png_first(first), _png_lossy(lossy_transparent, False), ctypes.byref(stats)) != 0:
+        raise RuntimeError("zmx_png_index_color_stats: " + (lib.zmx_last_error() or b"").decode())
+    return stats
+
+
+def png_index_table(image, first, mode, lossy_transparent=False, lib=None):
+    """zmx_png_index_table: the 256 entries that take the image into `mode` (a PngColorMode), for
+    Context.png_index_convert_device.  Host arithmetic only."""
+    lib = lib or library()
+    im = _png_index_image(image, sync=False) if isinstance(image, (tuple, list)) else image
+    table = (ctypes.c_uint32 * 256)()
+    fn = lib.zmx_png_index_table
+    fn.argtypes = [ctypes.POINTER(PngIndexImage), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint, ctypes.POINTER(PngColorMode),
+                   ctypes.POINTER(ctypes.c_uint32)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(im), _png_first(first), _png_lossy(lossy_transparent, False), ctypes.byref(mode), table) != 0:
+        raise RuntimeError("zmx_png_index_table: " + (lib.zmx_last_error() or b"").decode())
+    return [int(v) for v in table]
+
+
+def png_index_keep_plan(image, first, lossy_transparent=False, lib=None):
+    """zmx_png_index_keep_plan: (the PngColorMode of the --keepcolortype file, the table into it).  Host arithmetic only."""
+    lib = lib or library()
+    im = _png_index_image(image, sync=False) if isinstance(image, (tuple, list)) else image
+    mode = PngColorMode()
+    table = (ctypes.c_uint32 * 256)()
+    fn = lib.zmx_png_index_keep_plan
+    fn.argtypes = [ctypes.POINTER(PngIndexImage), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint, ctypes.POINTER(PngColorMode),
+                   ctypes.POINTER(ctypes.c_uint32)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(im), _png_first(first), _png_lossy(lossy_transparent, False), ctypes.byref(mode), table) != 0:
+        raise RuntimeError("zmx_png_index_keep_plan: " + (lib.zmx_last_error() or b"").decode())
+    return mode, [int(v) for v in table]
+
+
 def last_output_traffic(lib=None):
     """zmx_last_output_traffic: of this thread's last call, the stream's bytes device to host, its bytes host to device,
     the blocks whose symbols' bits never left the device, the blocks the host wrote and uploaded."""
@@ -901,6 +1109,50 @@ class Context:
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, ctypes.byref(im), dst or None, capacity, ctypes.byref(info)), "zmx_png_lossy_transparent_device")
         return info
+
+    def png_index_use_device(self, image, palette=None, bitdepth=8):
+        """zmx_png_index_use_device: for each of the 256 values the smallest raster pixel index at which it occurs in the
+        index image (`image` as png_index_encode_device takes it), 2**64 - 1 for a value no pixel has: a list of 256."""
+        im = _png_index_image(image, palette, bitdepth)
+        first = (ctypes.c_uint64 * 256)()
+        fn = self.lib.zmx_png_index_use_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngIndexImage), ctypes.POINTER(ctypes.c_uint64)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, ctypes.byref(im), first), "zmx_png_index_use_device")
+        return [int(v) for v in first]
+
+    def png_index_convert_device(self, image, mode, table, out, capacity=None, palette=None, bitdepth=8):
+        """zmx_png_index_convert_device: the index image through `table` (256 integers: png_index_table's, png_index_keep_plan's
+        or the caller's) into the colour mode `mode` (a PngColorMode), into `out`, a tensor or an integer pointer with
+        `capacity` bytes (an integer pointer without one: exactly the output's size), memory of this context's device:
+        height rows of (width * bpp + 7) // 8 bytes."""
+        im = _png_index_image(image, palette, bitdepth)
+        if isinstance(out, int):
+            bpp = (1 if mode.colortype == 3 else {0: 1, 2: 3, 4: 2, 6: 4}.get(mode.colortype, 0)) * mode.bitdepth
+            dst, capacity = out, im.height * ((im.width * bpp + 7) // 8) if capacity is None else int(capacity)
+        else:
+            dst, capacity = _device_range(out, capacity)
+        fn = self.lib.zmx_png_index_convert_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngIndexImage), ctypes.POINTER(PngColorMode), ctypes.POINTER(ctypes.c_uint32),
+                       ctypes.c_void_p, ctypes.c_size_t]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, ctypes.byref(im), ctypes.byref(mode), (ctypes.c_uint32 * 256)(*[int(v) for v in table]), dst or None,
+                       capacity), "zmx_png_index_convert_device")
+
+    def png_index_choose_strategy_device(self, image, reduce_color=False, predefined=None, lossy_transparent=False, palette=None, bitdepth=8):
+        """zmx_png_index_choose_strategy_device: png_choose_strategy_device for an index image, --lossy_transparent applied
+        first where asked: (the ZMX_PNG_FILTER_* number, the eight trial file sizes)."""
+        im = _png_index_image(image, palette, bitdepth)
+        types = _png_types(predefined, im.height)
+        strategy = ctypes.c_int(-1)
+        sizes = (ctypes.c_uint64 * 8)()
+        fn = self.lib.zmx_png_index_choose_strategy_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngIndexImage), ctypes.c_int, ctypes.c_uint, ctypes.c_char_p,
+                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, ctypes.byref(im), 1 if reduce_color else 0, _png_lossy(lossy_transparent, False), types,
+                       ctypes.byref(strategy), sizes), "zmx_png_index_choose_strategy_device")
+        return int(strategy.value), [int(v) for v in sizes]
 
     def bitjoin_device(self, pieces, total_bits, dst, capacity=None):
         """zmx_bitjoin_device: pieces = [(src pointer, src_bit, nbits, dst_bit)] — bits [src_bit, src_bit + nbits) of the

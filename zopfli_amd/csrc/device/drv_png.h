@@ -1,7 +1,8 @@
 // Driver part: LodePNG's filter choices on the device (zmx_png.h, zmx_png_brute.h) and the filtered scanlines
 // (zmx_png_rows.h).  Holds zmx_png_filter_types, zmx_png_filter_types_brute, their device-image form
 // zmx_png_filter_types_device, zmx_png_filter_rows_device and the encoder's zmx_internal_png_scanlines; the colour
-// statistics and conversion (zmx_png_color.h); zopflipng's --lossy_transparent (zmx_png_lossy.h); LodePNG's zlib size of
+// statistics and conversion (zmx_png_color.h); zopflipng's --lossy_transparent (zmx_png_lossy.h); index images
+// (zmx_png_index.h: zmx_png_index_use_device, zmx_png_index_convert_device); LodePNG's zlib size of
 // device buffers and the rows of zopflipng's strategy trials (zmx_png_lodeflate.h).  Needs drv_context.h (zmx_ctx,
 // PoolScope) and drv_input.h (CheckDevicePointer).
 #pragma once
@@ -610,6 +611,141 @@ int zmx_internal_png_scanlines(zmx_ctx* c, const void* d_image, size_t linebytes
 }
 }  // extern "C"
 
+// ---- index images: first appearances and the table-driven conversion (zmx_png_index.h)
+static thread_local double g_png_index_ms[2] = {0, 0};   // k_png_index_use, k_png_index_convert (zmx_internal_png_index_ms)
+
+// What every index entry refuses of an image before its pointer is looked at; *nbytes its size.
+static int PngIndexImageOf(const char* who, const zmx_png_index_image* image, zamd::PngIndexImage* I, size_t* nbytes) {
+  const std::string w(who);
+  if (!image) return FailMsg(w + ": no image");
+  if (image->width == 0 || image->height == 0) return FailMsg(w + ": width or height 0");
+  const u32 ct = image->colortype, depth = image->bitdepth;
+  const bool depth_ok = depth == 1 || depth == 2 || depth == 4 || (depth == 8 && ct == 3);
+  if (!(ct == 0 || ct == 3) || !depth_ok) {
+    return FailMsg(w + ": colour type " + std::to_string(ct) + " at " + std::to_string(depth) + " bits is no index image (3 at 1, 2, 4, 8; 0 at 1, 2, 4)");
+  }
+  if (ct == 3 && (image->palettesize == 0 || image->palettesize > (1u << depth))) {
+    return FailMsg(w + ": a palette of " + std::to_string(image->palettesize) + " entries at " + std::to_string(depth) + " bits");
+  }
+  if (static_cast<u64>(image->width) * image->height > 0xffffffffull) return FailMsg(w + ": an image of 2^32 pixels or more");
+  I->pixels = static_cast<const u8*>(image->d_pixels);
+  I->linebytes = zamd::PngIndexLineBytes(image->width, depth);
+  I->width = image->width;
+  I->height = image->height;
+  I->bitdepth = depth;
+  if (!PngGeometryOk(I->linebytes, image->height, 0x7fffffffu, 1)) return FailMsg(w + ": bad geometry");
+  *nbytes = static_cast<size_t>(I->linebytes * image->height);
+  return 0;
+}
+
+// k_png_index_use on an image the caller has checked: the table read.  Drains the context's stream.
+static int PngIndexUseOnDevice(zmx_ctx* c, PoolScope* tmp, const zamd::PngIndexImage& I, size_t nbytes, uint64_t* first) {
+  u32* d_first = nullptr;
+  HIPCHK(tmp->AllocT(&d_first, zamd::kPngIndexValues, "d_png_index_first"));
+  HIPCHK(hipMemsetAsync(d_first, 0xff, zamd::kPngIndexValues * sizeof(u32), c->stream));
+  PngLossyTimer timer{c, KernelTiming()};
+  HIPCHK(timer.Begin());
+  hipLaunchKernelGGL(k_png_index_use, dim3(zamd::PngIndexGrid(nbytes)), dim3(zamd::kPngIndexThreads), 0, c->stream, I, d_first);
+  KCHK(c, "k_png_index_use");
+  HIPCHK(timer.End(&g_png_index_ms[0]));
+  u32 got[zamd::kPngIndexValues];
+  HIPCHK(hipMemcpyAsync(got, d_first, sizeof(got), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (u32 v = 0; v < zamd::kPngIndexValues; ++v) first[v] = got[v] == zamd::kPngIndexNone ? UINT64_MAX : got[v];
+  return 0;
+}
+
+// k_png_index_convert, the caller having checked everything: the image through `table` into d_out in the output mode.
+// Drains the context's stream.
+static int PngIndexConvertOnDevice(zmx_ctx* c, PoolScope* tmp, const char* who, const zamd::PngIndexImage& I, u32 palettesize,
+                                   const zmx_png_color_mode& mode, const uint32_t* table, u8* d_out) {
+  u32* d_bad = nullptr;
+  u32* d_table = nullptr;
+  HIPCHK(tmp->AllocT(&d_bad, 1, "d_png_bad_pixel"));
+  HIPCHK(hipMemsetAsync(d_bad, 0xff, sizeof(u32), c->stream));
+  HIPCHK(tmp->Upload(&d_table, table, zamd::kPngIndexValues, "d_png_index_table"));
+  zamd::PngIndexConvParams P;
+  P.in = I;
+  P.out = d_out;
+  P.rowbytes = zamd::PngConvRowBytes(I.width, mode.colortype, mode.bitdepth);
+  P.colortype = mode.colortype;
+  P.bitdepth = mode.bitdepth;
+  P.palettesize = palettesize;
+  P.table = d_table;
+  P.bad_pixel = d_bad;
+  PngLossyTimer timer{c, KernelTiming()};
+  HIPCHK(timer.Begin());
+  hipLaunchKernelGGL(k_png_index_convert, dim3(zamd::PngIndexGrid(P.rowbytes * I.height)), dim3(zamd::kPngIndexThreads), 0, c->stream, P);
+  KCHK(c, "k_png_index_convert");
+  HIPCHK(timer.End(&g_png_index_ms[1]));
+  u32 bad = zamd::kPngIndexNone;
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (bad != zamd::kPngIndexNone) return FailMsg(std::string(who) + ": pixel " + std::to_string(bad) + " has a value outside the palette");
+  return 0;
+}
+
+extern "C" {
+void zmx_internal_png_index_ms(double out[2]) {
+  for (int k = 0; k < 2; ++k) out[k] = g_png_index_ms[k];
+}
+
+int zmx_png_index_use_device(zmx_ctx* c, const zmx_png_index_image* image, uint64_t first[256]) {
+  const char* who = "zmx_png_index_use_device";
+  g_png_index_ms[0] = 0;
+  if (!c) return FailMsg(std::string(who) + ": no context");
+  if (!first) return FailMsg(std::string(who) + ": no output");
+  zamd::PngIndexImage I;
+  size_t nbytes = 0;
+  if (const int rc = PngIndexImageOf(who, image, &I, &nbytes)) return rc;
+  int img_device = -1;
+  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (img_device != c->device) return FailMsg(std::string(who) + ": memory of another device than the context's");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  uint64_t got[zamd::kPngIndexValues];
+  const int rc = PngIndexUseOnDevice(c, &tmp, I, nbytes, got);
+  if (rc != 0) {
+    (void)hipStreamSynchronize(c->stream);   // what was queued may still use `tmp`'s arrays
+    return rc;
+  }
+  std::copy(got, got + zamd::kPngIndexValues, first);
+  return 0;
+}
+
+int zmx_png_index_convert_device(zmx_ctx* c, const zmx_png_index_image* image, const zmx_png_color_mode* mode, const uint32_t table[256],
+                                 void* d_out, size_t capacity) {
+  const char* who = "zmx_png_index_convert_device";
+  g_png_index_ms[1] = 0;
+  if (!c) return FailMsg(std::string(who) + ": no context");
+  if (!mode || !table) return FailMsg(std::string(who) + ": no mode or no table");
+  zamd::PngIndexImage I;
+  size_t nbytes = 0;
+  if (const int rc = PngIndexImageOf(who, image, &I, &nbytes)) return rc;
+  if (!zamd::PngIndexOutModeOk(mode->colortype, mode->bitdepth)) {
+    return FailMsg(std::string(who) + ": colour type " + std::to_string(mode->colortype) + " at " + std::to_string(mode->bitdepth) +
+                   " bits is no mode an index image converts to");
+  }
+  const u64 rowbytes = zamd::PngConvRowBytes(I.width, mode->colortype, mode->bitdepth);
+  if (rowbytes > 0x7fffffffu) return FailMsg(std::string(who) + ": bad geometry");
+  const size_t total = static_cast<size_t>(rowbytes * I.height);
+  if (capacity < total) {
+    return FailMsg(std::string(who) + ": the output takes " + std::to_string(total) + " bytes, the capacity is " + std::to_string(capacity));
+  }
+  int img_device = -1, out_device = -1;
+  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (const int rc = CheckDevicePointer(who, d_out, total, &out_device)) return rc;
+  if (img_device != c->device || out_device != c->device) return FailMsg(std::string(who) + ": memory of another device than the context's");
+  if (RangesOverlap(d_out, total, image->d_pixels, nbytes)) return FailMsg(std::string(who) + ": the output overlaps the image");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  const u32 palettesize = image->colortype == 3 ? image->palettesize : 1u << image->bitdepth;
+  const int rc = PngIndexConvertOnDevice(c, &tmp, who, I, palettesize, *mode, table, static_cast<u8*>(d_out));
+  if (rc != 0) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+}  // extern "C"
+
 // ---- LodePNG's zlib size of device buffers (zmx_png_lodeflate.h, host/png_lodeflate_size.h)
 static thread_local double g_png_lo_ms[6] = {0, 0, 0, 0, 0, 0};   // k_png_lo_hash, _links, _ask, _keep, _search, _parse (zmx_internal_png_lodeflate_ms)
 
@@ -718,36 +854,24 @@ int zmx_png_deflate_sizes_device(zmx_ctx* c, size_t n, const void* const* d_in, 
   return 0;
 }
 
-// zmx_png_choose_strategy_device's device part (host/png_encode.cc): the image in `mode` (null: as it is), converted
-// once, then the rows of trial k = 0 .. ntrials - 1 at d_out + k * scanlines — zopflipng's order: the types 0 .. 4, MINSUM,
-// ENTROPY, and for ntrials = 8 the `height` host bytes at `predefined` (checked by the caller).  d_out is a buffer of the
-// caller's own on the context's device.  The image is checked as the device entries check theirs.
-int zmx_internal_png_trial_scanlines(zmx_ctx* c, const char* who, const zmx_png_image* image, const zmx_png_color_mode* mode,
+// zmx_png_choose_strategy_device's device part (host/png_encode.cc): the rows of trial k = 0 .. ntrials - 1 of an image
+// that lies converted at d_rows — `height` rows of `rowbytes` bytes — at d_out + k * height * (rowbytes + 1), in zopflipng's
+// order: the types 0 .. 4, MINSUM, ENTROPY, and for ntrials = 8 the `height` host bytes at `predefined` (checked by the
+// caller).  d_out is a buffer of the caller's own on the context's device.  The rows are checked as the device entries
+// check an image.
+int zmx_internal_png_trial_scanlines(zmx_ctx* c, const char* who, const void* d_rows, size_t rowbytes, size_t height, size_t bytewidth,
                                      const unsigned char* predefined, int ntrials, void* d_out) {
-  zamd::PngColorImage I;
-  size_t nbytes = 0;
-  if (const int rc = PngColorImageOf(who, image, &I, &nbytes)) return rc;
-  if (mode && !zamd::PngModeOk(*mode, I.bitdepth)) return FailMsg(std::string(who) + ": no mode this image converts to");
+  if (!PngGeometryOk(rowbytes, height, 0x7fffffffu, bytewidth) || height == 0) return FailMsg(std::string(who) + ": bad geometry");
   int img_device = -1;
-  if (const int rc = CheckDevicePointer(who, image->d_pixels, nbytes, &img_device)) return rc;
+  if (const int rc = CheckDevicePointer(who, d_rows, rowbytes * height, &img_device)) return rc;
   if (img_device != c->device) return FailMsg(std::string(who) + ": the image is memory of another device than the context's");
-  const u64 rowbytes = mode ? zamd::PngConvRowBytes(I.width, mode->colortype, mode->bitdepth) : nbytes / I.height;
-  const u32 bpp = mode ? zamd::PngConvBpp(mode->colortype, mode->bitdepth) : 8u * zamd::PngColorPixelBytes(I.colortype, I.bitdepth);
-  const size_t bytewidth = bpp < 8 ? 1 : bpp / 8, height = I.height;
-  if (!PngGeometryOk(rowbytes, height, 0x7fffffffu, bytewidth)) return FailMsg(std::string(who) + ": bad geometry");
-  const size_t scanlines = height * (static_cast<size_t>(rowbytes) + 1);
+  const size_t scanlines = height * (rowbytes + 1);
   DEVICE_ENTRY(c->device);
   PoolScope tmp(c);
-  const u8* d_img = static_cast<const u8*>(image->d_pixels);
+  const u8* d_img = static_cast<const u8*>(d_rows);
   int rc = 0;
-  if (mode) {
-    u8* d_conv = nullptr;
-    HIPCHK(tmp.AllocT(&d_conv, static_cast<size_t>(rowbytes) * height, "d_png_converted"));
-    rc = PngConvertOnDevice(c, &tmp, who, I, *mode, d_conv);
-    d_img = d_conv;
-  }
   u8* d_types = nullptr;
-  if (rc == 0) {
+  {
     const hipError_t e = tmp.AllocT(&d_types, height, "d_png_types");
     if (e != hipSuccess) rc = Fail("AllocT(d_png_types)", e, __FILE__, __LINE__);
   }
@@ -756,10 +880,10 @@ int zmx_internal_png_trial_scanlines(zmx_ctx* c, const char* who, const zmx_png_
       const hipError_t e = hipMemcpyAsync(d_types, predefined, height, hipMemcpyHostToDevice, c->stream);
       if (e != hipSuccess) rc = Fail("hipMemcpyAsync(d_png_types)", e, __FILE__, __LINE__);
     } else {
-      rc = PngTypesOnDevice(c, &tmp, who, d_img, static_cast<size_t>(rowbytes), height, bytewidth, k, 0, d_types);
+      rc = PngTypesOnDevice(c, &tmp, who, d_img, rowbytes, height, bytewidth, k, 0, d_types);
     }
     // (drains the stream whichever way it returns once the kernel is queued: d_types is free for the next trial)
-    if (rc == 0) rc = PngRowsOnDevice(c, &tmp, who, d_img, static_cast<size_t>(rowbytes), height, bytewidth, d_types,
+    if (rc == 0) rc = PngRowsOnDevice(c, &tmp, who, d_img, rowbytes, height, bytewidth, d_types,
                                       static_cast<u8*>(d_out) + static_cast<size_t>(k) * scanlines);
   }
   if (rc != 0) (void)hipStreamSynchronize(c->stream);

@@ -46,6 +46,8 @@
 #include "zmx_png_rows.h"    // the filtered scanlines of a PNG
 #define ZMX_PNG_COLOR_KERNELS
 #include "zmx_png_color.h"   // LodePNG's colour statistics and colour conversion
+#define ZMX_PNG_INDEX_KERNELS
+#include "zmx_png_index.h"   // index images: where each value first appears, the table-driven conversion
 #define ZMX_PNG_LOSSY_KERNELS
 #include "zmx_png_lossy.h"   // zopflipng's --lossy_transparent: statistics, the carry scan, the rewrite
 #define ZMX_PNG_LODEFLATE_KERNELS
@@ -55,6 +57,7 @@
 #include "../host/deal.h"
 #include "../host/entry_checks.h"
 #include "../host/png_color_choose.h"
+#include "../host/png_index.h"
 #include "../host/png_lodeflate_size.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
@@ -71,6 +74,6 @@
 #include "drv_bitjoin.h"     // output that stays on the device: the bit join, the bit writer without the way down
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
 #include "drv_checksum_device.h"   // zmx_checksum_device, the seal of a PNG left in device memory
-#include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion, LodePNG's zlib sizes
+#include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion, index images, LodePNG's zlib sizes
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries
 #include "drv_probes.h"      // the parity probes: digest, longest match, hash links, length array, DP rows

@@ -216,6 +216,14 @@ inline size_t PngBound(uint32_t width, uint32_t height, uint32_t colortype, uint
   const size_t scanlines = static_cast<size_t>(height) * (PngLineBytes(width, colortype, bitdepth) + 1);
   return kPngMaxPrefixBytes + CompressBound(ZOPFLI_FORMAT_ZLIB, scanlines) + kPngTrailerBytes;
 }
+// The same for the index entries (zmx_png_index_bound): a palette or grey image of 1 .. 8 bits per pixel.
+//  - The --keepcolortype file has the input's own bits per pixel.  LodePNG's choice for the expansion is not bounded by
+//    them: a 1-bit palette of two colours on few pixels comes out as RGB or RGBA at 8 bits (fewer than two pixels a
+//    colour), and the to-device optimize entry writes such a first file straight into d_out.
+//  - No mode that can come out has more than 32 bits per pixel — the expansion has 8-bit samples only, so 16-bit modes
+//    are never chosen, and the second try is RGB or RGBA at 8 bits — and S rises with the bits per pixel.  So S of RGBA at 8
+//    bits bounds S of every file either entry makes, the kept one included.
+inline size_t PngIndexBound(uint32_t width, uint32_t height) { return PngBound(width, height, 6, 8); }
 inline size_t PngBatchBound(size_t n, const zmx_png_image* images, size_t align) {
   size_t sum = 0;
   for (size_t i = 0; i < n; ++i) sum += AlignUp(PngBound(images[i].width, images[i].height, images[i].colortype, images[i].bitdepth), align);

@@ -14,10 +14,15 @@
 // ZMX_PNG_FILTER_AUTO is zopflipng's own choice of the strategy (zmx_png_choose_strategy_device, further down): made on the
 // first hold of the context, after the rewrite and the 8-bit conversion, image by image in the batches; everything after
 // is the entry's path with the strategy chosen.
+// The zmx_png_index_* entries, at the end, take a palette or low-bit grey image: k_png_index_use's table of first
+// appearances, png_index.h's statistics, mode and conversion table, k_png_index_convert, and from there the other entries'
+// path — the trials, the row search, the compression and the tails are shared through RowSource and FinishOptimize*.
 // The _to_device entries and zmx_png_encode_device_batch_packed leave the file in device memory: the same first hold (the
 // *FrontHalf functions, shared with the host-output entries), then the to-device compress path with the file's frame
 // around the stream (device_output_plan.h: PngFrame) and the IDAT's CRC-32 sealed on the device.
+#include <algorithm>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -26,6 +31,7 @@
 #include "device_output_plan.h"
 #include "png_color_choose.h"
 #include "png_container.h"
+#include "png_index.h"
 #include "zmx_internal.h"
 #include "zopfli_amd.h"
 
@@ -95,9 +101,11 @@ struct File {
     zamd::AppendToOutput(prefix, sizeof(prefix), &bytes, &size);
   }
   // the file of the image in `mode`: PLTE and tRNS where the mode has them
-  void BeginReduced(const zmx_png_image& im, const zmx_png_color_mode& mode) {
+  void BeginReduced(const zmx_png_image& im, const zmx_png_color_mode& mode) { BeginIn(im.width, im.height, mode); }
+  // (a mode without a palette and a key gives Begin's bytes)
+  void BeginIn(uint32_t width, uint32_t height, const zmx_png_color_mode& mode) {
     unsigned char prefix[zamd::kPngMaxPrefixBytes];
-    prefix_bytes = zamd::PngPrefixReduced(im.width, im.height, mode.colortype, mode.bitdepth, mode.palette, mode.palettesize,
+    prefix_bytes = zamd::PngPrefixReduced(width, height, mode.colortype, mode.bitdepth, mode.palette, mode.palettesize,
                                           mode.key_defined != 0, mode.key_r, mode.key_g, mode.key_b, prefix);
     zamd::AppendToOutput(prefix, prefix_bytes, &bytes, &size);
   }
@@ -173,17 +181,20 @@ int CheckDest(const std::string& w, const DeviceDest& dest, int img_device, size
   return 0;
 }
 
-// The frame of the file of `im` (device_output_plan.h): in `mode`, or as it is (null)
-zamd::PngFrame FrameOf(const zmx_png_image& im, const zmx_png_color_mode* mode) {
+// The frame of the file of a width x height image in `mode` (device_output_plan.h)
+zamd::PngFrame FrameIn(uint32_t width, uint32_t height, const zmx_png_color_mode& mode) {
   zamd::PngFrame frame;
-  if (!mode) {
-    frame.file_prefix.resize(zamd::kPngPrefixBytes);
-    zamd::PngPrefix(im.width, im.height, im.colortype, im.bitdepth, frame.file_prefix.data());
-  } else {
-    frame.file_prefix.resize(zamd::kPngMaxPrefixBytes);
-    frame.file_prefix.resize(zamd::PngPrefixReduced(im.width, im.height, mode->colortype, mode->bitdepth, mode->palette, mode->palettesize,
-                                                    mode->key_defined != 0, mode->key_r, mode->key_g, mode->key_b, frame.file_prefix.data()));
-  }
+  frame.file_prefix.resize(zamd::kPngMaxPrefixBytes);
+  frame.file_prefix.resize(zamd::PngPrefixReduced(width, height, mode.colortype, mode.bitdepth, mode.palette, mode.palettesize,
+                                                  mode.key_defined != 0, mode.key_r, mode.key_g, mode.key_b, frame.file_prefix.data()));
+  return frame;
+}
+// ... of `im`: in `mode`, or as it is (null)
+zamd::PngFrame FrameOf(const zmx_png_image& im, const zmx_png_color_mode* mode) {
+  if (mode) return FrameIn(im.width, im.height, *mode);
+  zamd::PngFrame frame;
+  frame.file_prefix.resize(zamd::kPngPrefixBytes);
+  zamd::PngPrefix(im.width, im.height, im.colortype, im.bitdepth, frame.file_prefix.data());
   return frame;
 }
 
@@ -208,9 +219,38 @@ bool SameMode(const zmx_png_image& im, const zmx_png_color_mode& mode) {
   return mode.colortype == im.colortype && mode.bitdepth == im.bitdepth && mode.key_defined == 0;
 }
 
-size_t ScanlinesIn(const zmx_png_image& im, const zmx_png_color_mode& mode) {
-  const size_t bpp = (mode.colortype == 3 ? 1 : zamd::PngChannels(mode.colortype)) * mode.bitdepth;
-  return static_cast<size_t>(im.height) * ((static_cast<size_t>(im.width) * bpp + 7) / 8 + 1);
+size_t BitsPerPixel(const zmx_png_color_mode& mode) { return (mode.colortype == 3 ? 1 : zamd::PngChannels(mode.colortype)) * mode.bitdepth; }
+size_t RowBytesIn(uint32_t width, const zmx_png_color_mode& mode) { return (static_cast<size_t>(width) * BitsPerPixel(mode) + 7) / 8; }
+size_t ByteWidthIn(const zmx_png_color_mode& mode) { return BitsPerPixel(mode) < 8 ? 1 : BitsPerPixel(mode) / 8; }
+size_t ScanlinesIn(uint32_t width, uint32_t height, const zmx_png_color_mode& mode) {
+  return static_cast<size_t>(height) * (RowBytesIn(width, mode) + 1);
+}
+size_t ScanlinesIn(const zmx_png_image& im, const zmx_png_color_mode& mode) { return ScanlinesIn(im.width, im.height, mode); }
+
+zmx_png_color_mode OwnMode(const zmx_png_image& im) {
+  zmx_png_color_mode own = zmx_png_color_mode();
+  own.colortype = im.colortype;
+  own.bitdepth = im.bitdepth;
+  return own;
+}
+
+// An image as rows in a colour mode, whatever it is made of (a zmx_png_image: k_png_convert; an index image: its table and
+// k_png_index_convert): on a held context the `height` rows of RowBytesIn(width, mode) bytes go to d_room, memory of the
+// context's device that the caller owns, and *d_rows = d_room — or *d_rows = where the image lies in that mode already.
+struct RowSource {
+  uint32_t width, height;
+  std::function<int(zmx_ctx* ctx, const zmx_png_color_mode& mode, void* d_room, const void** d_rows)> in_mode;
+};
+
+RowSource RowsOf(const zmx_png_image& im) {
+  return RowSource{im.width, im.height, [&im](zmx_ctx* ctx, const zmx_png_color_mode& mode, void* d_room, const void** d_rows) {
+    if (SameMode(im, mode)) {
+      *d_rows = im.d_pixels;
+      return 0;
+    }
+    *d_rows = d_room;
+    return zmx_png_convert_device(ctx, &im, &mode, d_room, RowBytesIn(im.width, mode) * im.height);
+  }};
 }
 
 int CheckReducible(const std::string& w, const zmx_png_image& im, Geometry* g) {
@@ -233,63 +273,52 @@ constexpr unsigned kTrialWindow = 8192;
 constexpr int kTrialStrategies[8] = {ZMX_PNG_FILTER_ZERO, ZMX_PNG_FILTER_ONE,    ZMX_PNG_FILTER_TWO,     ZMX_PNG_FILTER_THREE,
                                      ZMX_PNG_FILTER_FOUR, ZMX_PNG_FILTER_MINSUM, ZMX_PNG_FILTER_ENTROPY, ZMX_PNG_FILTER_PREDEFINED};
 
-// The file sizes of the trials of `im` in `mode` (null: as it is) on a held context: the rows of all trials in one buffer,
-// one zmx_png_deflate_sizes_device, the container's bytes around each stream.
-int TrialFileSizes(zmx_ctx* ctx, const std::string& w, int device, const zmx_png_image& im, const zmx_png_color_mode* mode,
+// The file sizes of the trials of an image in `mode` on a held context: the converted rows and the rows of all trials in
+// one buffer, one zmx_png_deflate_sizes_device, the container's bytes around each stream.
+int TrialFileSizes(zmx_ctx* ctx, const std::string& w, int device, const RowSource& src, const zmx_png_color_mode& mode,
                    const unsigned char* predefined, int ntrials, uint64_t* file_bytes) {
-  zmx_png_color_mode own = zmx_png_color_mode();
-  own.colortype = im.colortype;
-  own.bitdepth = im.bitdepth;
-  const size_t scanlines = ScanlinesIn(im, mode ? *mode : own);
-  if (scanlines > SIZE_MAX / 8) return Refuse(w + ": the sizes overflow");
-  DeviceBuffer rows;
-  rows.device = device;
-  if (zmx_internal_device_alloc(device, scanlines * ntrials, &rows.p) != 0) return -1;
-  if (zmx_internal_png_trial_scanlines(ctx, w.c_str(), &im, mode, predefined, ntrials, rows.p) != 0) return -1;
+  const size_t scanlines = ScanlinesIn(src.width, src.height, mode), rowbytes = RowBytesIn(src.width, mode);
+  if (scanlines > SIZE_MAX / 9) return Refuse(w + ": the sizes overflow");
+  const size_t room = (rowbytes * src.height + 15) & ~static_cast<size_t>(15);
+  DeviceBuffer buf;
+  buf.device = device;
+  if (zmx_internal_device_alloc(device, room + scanlines * ntrials, &buf.p) != 0) return -1;
+  unsigned char* const trials = static_cast<unsigned char*>(buf.p) + room;
+  const void* d_rows = nullptr;
+  if (src.in_mode(ctx, mode, buf.p, &d_rows) != 0) return -1;
+  if (zmx_internal_png_trial_scanlines(ctx, w.c_str(), d_rows, rowbytes, src.height, ByteWidthIn(mode), predefined, ntrials, trials) != 0) return -1;
   const void* ptrs[8];
   size_t sizes[8];
   uint64_t zlib_bytes[8];
   for (int k = 0; k < ntrials; ++k) {
-    ptrs[k] = static_cast<const unsigned char*>(rows.p) + static_cast<size_t>(k) * scanlines;
+    ptrs[k] = trials + static_cast<size_t>(k) * scanlines;
     sizes[k] = scanlines;
   }
   if (zmx_png_deflate_sizes_device(ctx, static_cast<size_t>(ntrials), ptrs, sizes, kTrialWindow, zlib_bytes) != 0) return -1;
-  size_t prefix_bytes = zamd::kPngPrefixBytes;
-  if (mode) {
-    unsigned char prefix[zamd::kPngMaxPrefixBytes];
-    prefix_bytes = zamd::PngPrefixReduced(im.width, im.height, mode->colortype, mode->bitdepth, mode->palette, mode->palettesize,
-                                          mode->key_defined != 0, mode->key_r, mode->key_g, mode->key_b, prefix);
-  }
+  unsigned char prefix[zamd::kPngMaxPrefixBytes];
+  const size_t prefix_bytes = zamd::PngPrefixReduced(src.width, src.height, mode.colortype, mode.bitdepth, mode.palette, mode.palettesize,
+                                                     mode.key_defined != 0, mode.key_r, mode.key_g, mode.key_b, prefix);
   for (int k = 0; k < ntrials; ++k) file_bytes[k] = prefix_bytes + zlib_bytes[k] + zamd::kPngTrailerBytes;
   return 0;
 }
 
-// The choice for an image the caller has checked, on a held context.  `known`: its statistics and mode where the caller
-// has them (reduce_color only); else they are taken here.
-int ChooseStrategy(zmx_ctx* ctx, const std::string& w, int device, const zmx_png_image& im, bool reduce_color, const Reduced* known,
-                   const unsigned char* predefined, int* strategy, uint64_t* file_bytes) {
+// The choice for an image the caller has checked, on a held context: its trials in `mode`.  `stats` non-null: the colour
+// mode was reduced (`mode` is the choice of these statistics), so a small palette file competes with its second try.
+int ChooseStrategy(zmx_ctx* ctx, const std::string& w, int device, const RowSource& src, const zmx_png_color_mode& mode,
+                   const zmx_png_color_stats* stats, const unsigned char* predefined, int* strategy, uint64_t* file_bytes) {
   const int ntrials = predefined ? 8 : 7;
   uint64_t bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (!reduce_color) {
-    if (TrialFileSizes(ctx, w, device, im, nullptr, predefined, ntrials, bytes) != 0) return -1;
-  } else {
-    Reduced mine;
-    if (!known) {
-      if (StatsAndMode(ctx, im, &mine) != 0) return -1;
-      known = &mine;
-    }
-    if (TrialFileSizes(ctx, w, device, im, known->as_is ? nullptr : &known->mode, predefined, ntrials, bytes) != 0) return -1;
-    bool small = false;
-    for (int k = 0; k < ntrials; ++k) small = small || bytes[k] < zamd::kPngRetryBelow;
-    if (known->mode.colortype == 3 && small) {
-      // TryOptimize's second try sits inside every trial: a small palette file competes with its RGB / RGBA file
-      zmx_png_color_mode retry;
-      zamd::PngRetryMode(known->stats, static_cast<uint64_t>(im.width) * im.height, &retry);
-      uint64_t second[8];
-      if (TrialFileSizes(ctx, w, device, im, SameMode(im, retry) ? nullptr : &retry, predefined, ntrials, second) != 0) return -1;
-      for (int k = 0; k < ntrials; ++k) {
-        if (bytes[k] < zamd::kPngRetryBelow && second[k] < bytes[k]) bytes[k] = second[k];
-      }
+  if (TrialFileSizes(ctx, w, device, src, mode, predefined, ntrials, bytes) != 0) return -1;
+  bool small = false;
+  for (int k = 0; k < ntrials; ++k) small = small || bytes[k] < zamd::kPngRetryBelow;
+  if (stats && mode.colortype == 3 && small) {
+    // TryOptimize's second try sits inside every trial: a small palette file competes with its RGB / RGBA file
+    zmx_png_color_mode retry;
+    zamd::PngRetryMode(*stats, static_cast<uint64_t>(src.width) * src.height, &retry);
+    uint64_t second[8];
+    if (TrialFileSizes(ctx, w, device, src, retry, predefined, ntrials, second) != 0) return -1;
+    for (int k = 0; k < ntrials; ++k) {
+      if (bytes[k] < zamd::kPngRetryBelow && second[k] < bytes[k]) bytes[k] = second[k];
     }
   }
   int best = 0;
@@ -301,6 +330,18 @@ int ChooseStrategy(zmx_ctx* ctx, const std::string& w, int device, const zmx_png
     for (int k = 0; k < 8; ++k) file_bytes[k] = bytes[k];
   }
   return 0;
+}
+
+// ... for a zmx_png_image: as it is, or reduced — `known`: its statistics and mode where the caller has them
+int ChooseStrategy(zmx_ctx* ctx, const std::string& w, int device, const zmx_png_image& im, bool reduce_color, const Reduced* known,
+                   const unsigned char* predefined, int* strategy, uint64_t* file_bytes) {
+  if (!reduce_color) return ChooseStrategy(ctx, w, device, RowsOf(im), OwnMode(im), nullptr, predefined, strategy, file_bytes);
+  Reduced mine;
+  if (!known) {
+    if (StatsAndMode(ctx, im, &mine) != 0) return -1;
+    known = &mine;
+  }
+  return ChooseStrategy(ctx, w, device, RowsOf(im), known->mode, &known->stats, predefined, strategy, file_bytes);
 }
 
 }  // namespace
@@ -599,9 +640,6 @@ int OptimizeFrontHalf(const std::string& w, const ZopfliOptions* options, const 
   return rc;
 }
 
-// zopflipng's second try — without the palette's overhead — is due: the first file is a palette file of `first_bytes`
-inline bool SecondTryDue(const OptimizeFront& f, size_t first_bytes) { return f.r.mode.colortype == 3 && first_bytes < zamd::kPngRetryBelow; }
-
 // its mode and its scanlines, into scan2
 int SecondTryScanlines(const OptimizeFront& f, const unsigned char* predefined, zmx_png_color_mode* retry, bool* as_is, size_t* scanlines,
                        DeviceBuffer* scan2) {
@@ -615,28 +653,26 @@ int SecondTryScanlines(const OptimizeFront& f, const unsigned char* predefined, 
   }, f.device);
 }
 
-int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
-                unsigned lossy, unsigned char** out, size_t* outsize) {
-  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
-  OptimizeFront f;
-  if (OptimizeFrontHalf(w, options, image, strategy, predefined, lossy, nullptr, &f) != 0) return -1;
-  const Reduced& r = f.r;
-  const zmx_png_image& work = f.work;
+// zopflipng's second try at a small palette file, made by whoever holds the image: its mode, its scanlines' size and the
+// scanlines, into a buffer allocated here.  0, or -1 with the error set.
+using SecondTry = std::function<int(zmx_png_color_mode* retry, size_t* scanlines, DeviceBuffer* scan2)>;
+
+// What the optimize entries with host output share once the first file's scanlines lie in `scan`: the file in `mode`, the
+// second try where it is a palette file below 4096 bytes, the smaller of the two handed over.
+int FinishOptimize(const std::string& w, const ZopfliOptions* options, uint32_t width, uint32_t height, const zmx_png_color_mode& mode,
+                   const void* d_scan, size_t scanlines, const SecondTry& second_try, unsigned char** out, size_t* outsize) {
   File file;
-  if (r.as_is) file.Begin(work);
-  else file.BeginReduced(work, r.mode);
-  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, f.scan.p, r.scanlines, &file.bytes, &file.size) != 0) return -1;
+  file.BeginIn(width, height, mode);
+  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, d_scan, scanlines, &file.bytes, &file.size) != 0) return -1;
   if (!file.Close()) return BadStream(w);
   File second;
-  if (SecondTryDue(f, file.size)) {
+  if (mode.colortype == 3 && file.size < zamd::kPngRetryBelow) {
     zmx_png_color_mode retry;
-    bool as_is = false;
-    size_t scanlines = 0;
+    size_t scanlines2 = 0;
     DeviceBuffer scan2;
-    if (SecondTryScanlines(f, predefined, &retry, &as_is, &scanlines, &scan2) != 0) return -1;
-    if (as_is) second.Begin(work);
-    else second.BeginReduced(work, retry);
-    if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines, &second.bytes, &second.size) != 0) return -1;
+    if (second_try(&retry, &scanlines2, &scan2) != 0) return -1;
+    second.BeginIn(width, height, retry);
+    if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines2, &second.bytes, &second.size) != 0) return -1;
     if (!second.Close()) return BadStream(w);
     Smaller(file, second).GiveTo(out, outsize);
     return 0;
@@ -645,43 +681,37 @@ int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_pn
   return 0;
 }
 
-// The file left in device memory.  A mode other than a palette: the one file goes straight into d_out, as the encode
-// entry's.  A palette: which file is kept, and so its size, is known only when the first is made — so the first goes into
-// a buffer of the call's own, the second (where one is due) into another, and ONE device-to-device copy puts the kept file
-// into d_out: every byte of the file is written and none outside it, and a capacity of exactly the kept file's size does.
-int OptimizeOneToDevice(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                        const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
-  if (!options || !image || !outsize) return Refuse(w + ": null argument");
-  *outsize = 0;
-  const DeviceDest dest{d_out, capacity};
-  OptimizeFront f;
-  if (OptimizeFrontHalf(w, options, image, strategy, predefined, lossy, &dest, &f) != 0) return -1;
-  const Reduced& r = f.r;
-  const zamd::PngFrame frame = FrameOf(f.work, r.as_is ? nullptr : &r.mode);
-  if (r.mode.colortype != 3) {
-    return zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, f.scan.p, r.scanlines, d_out, capacity, outsize, &frame);
+// The same with the file left in device memory.  A mode other than a palette: the one file goes straight into d_out, as the
+// encode entry's.  A palette: which file is kept, and so its size, is known only when the first is made — so the first goes
+// into a buffer of the call's own, the second (where one is due) into another, and ONE device-to-device copy puts the kept
+// file into d_out: every byte of the file is written and none outside it, and a capacity of exactly the kept file's size does.
+int FinishOptimizeToDevice(const std::string& w, const ZopfliOptions* options, int device, uint32_t width, uint32_t height,
+                           const zmx_png_color_mode& mode, const void* d_scan, size_t scanlines, const SecondTry& second_try, void* d_out,
+                           size_t capacity, size_t* outsize) {
+  const zamd::PngFrame frame = FrameIn(width, height, mode);
+  if (mode.colortype != 3) {
+    return zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, d_scan, scanlines, d_out, capacity, outsize, &frame);
   }
   DeviceBuffer first, second;
-  first.device = second.device = f.device;
-  const size_t room = FileBound(r.scanlines);
+  first.device = second.device = device;
+  const size_t room = FileBound(scanlines);
   size_t first_bytes = 0, second_bytes = 0;
-  if (zmx_internal_device_alloc(f.device, room, &first.p) != 0) return -1;
-  if (zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, f.scan.p, r.scanlines, first.p, room, &first_bytes, &frame) != 0) {
+  if (zmx_internal_device_alloc(device, room, &first.p) != 0) return -1;
+  if (zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, d_scan, scanlines, first.p, room, &first_bytes, &frame) != 0) {
     *outsize = first_bytes;   // (a stream that fits no IDAT: the size it would have taken)
     return -1;
   }
   const void* kept = first.p;
   size_t kept_bytes = first_bytes;
-  if (SecondTryDue(f, first_bytes)) {
+  if (first_bytes < zamd::kPngRetryBelow) {
     zmx_png_color_mode retry;
-    bool as_is = false;
-    size_t scanlines = 0;
+    size_t scanlines2 = 0;
     DeviceBuffer scan2;
-    if (SecondTryScanlines(f, predefined, &retry, &as_is, &scanlines, &scan2) != 0) return -1;
-    const zamd::PngFrame frame2 = FrameOf(f.work, as_is ? nullptr : &retry);
-    const size_t room2 = FileBound(scanlines);
-    if (zmx_internal_device_alloc(f.device, room2, &second.p) != 0) return -1;
-    if (zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines, second.p, room2, &second_bytes, &frame2) != 0) return -1;
+    if (second_try(&retry, &scanlines2, &scan2) != 0) return -1;
+    const zamd::PngFrame frame2 = FrameIn(width, height, retry);
+    const size_t room2 = FileBound(scanlines2);
+    if (zmx_internal_device_alloc(device, room2, &second.p) != 0) return -1;
+    if (zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines2, second.p, room2, &second_bytes, &frame2) != 0) return -1;
     if (second_bytes < first_bytes) {
       kept = second.p;
       kept_bytes = second_bytes;
@@ -691,7 +721,33 @@ int OptimizeOneToDevice(const std::string& w, const ZopfliOptions* options, cons
   if (kept_bytes > capacity) {
     return Refuse(w + ": the file takes " + std::to_string(kept_bytes) + " bytes, d_out has " + std::to_string(capacity));
   }
-  return zmx_internal_device_copy(f.device, d_out, kept, kept_bytes);
+  return zmx_internal_device_copy(device, d_out, kept, kept_bytes);
+}
+
+SecondTry SecondTryOf(const OptimizeFront& f, const unsigned char* predefined) {
+  return [&f, predefined](zmx_png_color_mode* retry, size_t* scanlines, DeviceBuffer* scan2) {
+    bool as_is = false;
+    return SecondTryScanlines(f, predefined, retry, &as_is, scanlines, scan2);
+  };
+}
+
+int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
+                unsigned lossy, unsigned char** out, size_t* outsize) {
+  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
+  OptimizeFront f;
+  if (OptimizeFrontHalf(w, options, image, strategy, predefined, lossy, nullptr, &f) != 0) return -1;
+  return FinishOptimize(w, options, f.work.width, f.work.height, f.r.mode, f.scan.p, f.r.scanlines, SecondTryOf(f, predefined), out, outsize);
+}
+
+int OptimizeOneToDevice(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                        const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
+  if (!options || !image || !outsize) return Refuse(w + ": null argument");
+  *outsize = 0;
+  const DeviceDest dest{d_out, capacity};
+  OptimizeFront f;
+  if (OptimizeFrontHalf(w, options, image, strategy, predefined, lossy, &dest, &f) != 0) return -1;
+  return FinishOptimizeToDevice(w, options, f.device, f.work.width, f.work.height, f.r.mode, f.scan.p, f.r.scanlines,
+                                SecondTryOf(f, predefined), d_out, capacity, outsize);
 }
 
 }  // namespace
@@ -858,4 +914,366 @@ extern "C" int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_
 extern "C" int zmx_png_optimize_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
                                                    unsigned lossy, unsigned char** out, size_t* outsize) {
   return OptimizeBatch("zmx_png_optimize_device_batch_lossy", options, n, images, strategy, lossy, out, outsize);
+}
+
+// ---- palette, 1/2/4-bit grey and index images (png_index.h; device/zmx_png_index.h)
+namespace {
+
+// What is refused of an index image on the host, before its pointer is looked at; *nbytes its size.
+int CheckIndexImage(const std::string& w, const zmx_png_index_image& im, size_t* nbytes) {
+  if (im.width == 0 || im.height == 0) return Refuse(w + ": width or height 0");
+  if (!zamd::PngIndexFormatOk(im.colortype, im.bitdepth)) {
+    return Refuse(w + ": colour type " + std::to_string(im.colortype) + " at " + std::to_string(im.bitdepth) +
+                  " bits is no index image (3 at 1, 2, 4, 8; 0 at 1, 2, 4)");
+  }
+  if (!zamd::PngIndexPaletteSizeOk(im)) {
+    return Refuse(w + ": a palette of " + std::to_string(im.palettesize) + " entries at " + std::to_string(im.bitdepth) + " bits");
+  }
+  if (static_cast<uint64_t>(im.width) * im.height > 0xffffffffull) return Refuse(w + ": an image of 2^32 pixels or more");
+  const uint64_t linebytes = (static_cast<uint64_t>(im.width) * im.bitdepth + 7) / 8;
+  if (linebytes > 0x7fffffffu || im.height > 0x7fffffffu) return Refuse(w + ": bad geometry");
+  *nbytes = static_cast<size_t>(linebytes) * im.height;
+  return 0;
+}
+
+// What the host makes of an image's first appearances: the entries as zopflipng sees them (after --lossy_transparent where
+// asked), the statistics of the expansion, and the mode of the first file — LodePNG's choice, or the input's own.
+struct IndexPlan {
+  uint64_t first[256];
+  zamd::PngIndexPalette seen;
+  zmx_png_color_stats stats;
+  zmx_png_color_mode mode;
+};
+
+int CheckInsidePalette(const std::string& w, const zmx_png_index_image& im, const uint64_t first[256]) {
+  zamd::PngIndexPalette p;
+  zamd::PngIndexPaletteOf(im, &p);
+  const uint64_t outside = zamd::PngIndexFirstOutside(first, p.size);
+  if (outside == zamd::kPngIndexUnused) return 0;
+  return Refuse(w + ": pixel " + std::to_string(outside) + " has a value outside the palette of " + std::to_string(p.size) + " entries");
+}
+
+int PlanIndex(const std::string& w, const zmx_png_index_image& im, unsigned lossy, bool optimize, IndexPlan* plan) {
+  if (CheckInsidePalette(w, im, plan->first) != 0) return -1;
+  zamd::PngIndexPaletteOf(im, &plan->seen);
+  if (lossy & ZMX_PNG_LOSSY_TRANSPARENT) zamd::PngIndexLossyTransparent(&plan->seen, plan->first);
+  zamd::PngIndexColorStats(plan->seen, plan->first, &plan->stats);
+  if (optimize) {
+    zamd::PngChooseColor(plan->stats, static_cast<uint64_t>(im.width) * im.height, &plan->mode);
+  } else {
+    uint32_t table[256];
+    zamd::PngIndexKeepPlan(im, plan->first, (lossy & ZMX_PNG_LOSSY_TRANSPARENT) != 0, &plan->mode, table);
+  }
+  return 0;
+}
+
+RowSource RowsOf(const zmx_png_index_image& im, const zamd::PngIndexPalette& seen) {
+  return RowSource{im.width, im.height, [&im, &seen](zmx_ctx* ctx, const zmx_png_color_mode& mode, void* d_room, const void** d_rows) {
+    uint32_t table[256];
+    zamd::PngIndexTable(seen, mode, table);
+    *d_rows = d_room;
+    return zmx_png_index_convert_device(ctx, &im, &mode, table, d_room, RowBytesIn(im.width, mode) * im.height);
+  }};
+}
+
+// On a held context: the image in `mode` (into d_room, RowBytesIn * height bytes) and the filtered scanlines of that under
+// `strategy` into d_scan, ScanlinesIn bytes; both the caller's.
+int ScanlinesOf(zmx_ctx* ctx, const RowSource& src, const zmx_png_color_mode& mode, int strategy, const unsigned char* predefined, void* d_room,
+                void* d_scan) {
+  const void* d_rows = nullptr;
+  if (src.in_mode(ctx, mode, d_room, &d_rows) != 0) return -1;
+  return zmx_internal_png_scanlines(ctx, d_rows, RowBytesIn(src.width, mode), src.height, ByteWidthIn(mode), strategy, kBruteWindow, predefined,
+                                    d_scan);
+}
+
+// ... with both buffers allocated here; the scanlines stay in *scan
+int ScanlinesOf(zmx_ctx* ctx, int device, const RowSource& src, const zmx_png_color_mode& mode, int strategy, const unsigned char* predefined,
+                DeviceBuffer* scan) {
+  DeviceBuffer room;
+  room.device = scan->device = device;
+  if (zmx_internal_device_alloc(device, RowBytesIn(src.width, mode) * src.height, &room.p) != 0) return -1;
+  if (zmx_internal_device_alloc(device, ScanlinesIn(src.width, src.height, mode), &scan->p) != 0) return -1;
+  return ScanlinesOf(ctx, src, mode, strategy, predefined, room.p, scan->p);
+}
+
+// What the single index entries share: the checks (`dest`: a to-device entry's destination, checked with them) and the
+// first hold of a context, which leaves the first file's scanlines in `scan`.
+struct IndexFront {
+  int device = -1;
+  int strategy = 0;   // the one the rows were made with (_AUTO: the chosen one)
+  IndexPlan plan;
+  size_t scanlines = 0;
+  DeviceBuffer scan;
+};
+
+int IndexFrontHalf(const std::string& w, const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                   const unsigned char* predefined, unsigned lossy, bool optimize, const DeviceDest* dest, IndexFront* f) {
+  if (!options || !image) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+  size_t nbytes = 0;
+  if (CheckIndexImage(w, *image, &nbytes) != 0) return -1;
+  if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
+  if (CheckPredefined(w, strategy, predefined, image->height) != 0) return -1;
+  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, nbytes, &f->device) != 0) return -1;
+  if (dest && CheckDest(w, *dest, f->device, 1, &image->d_pixels, &nbytes) != 0) return -1;
+  IndexPlan& plan = f->plan;
+  // (the context is held for the first appearances, the trials, the conversion, the types and the rows only)
+  const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    if (zmx_png_index_use_device(ctx, image, plan.first) != 0) return -1;
+    if (PlanIndex(w, *image, lossy, optimize, &plan) != 0) return -1;
+    const RowSource src = RowsOf(*image, plan.seen);
+    if (strategy == ZMX_PNG_FILTER_AUTO &&
+        ChooseStrategy(ctx, w, f->device, src, plan.mode, optimize ? &plan.stats : nullptr, predefined, &strategy, nullptr) != 0) {
+      return -1;
+    }
+    f->scanlines = ScanlinesIn(image->width, image->height, plan.mode);
+    return ScanlinesOf(ctx, f->device, src, plan.mode, strategy, predefined, &f->scan);
+  }, f->device);
+  f->strategy = strategy;
+  return rc;
+}
+
+// the second try's mode and scanlines, on a second hold
+SecondTry SecondTryOf(const IndexFront& f, const zmx_png_index_image& image, const unsigned char* predefined) {
+  return [&f, &image, predefined](zmx_png_color_mode* retry, size_t* scanlines, DeviceBuffer* scan2) {
+    zamd::PngRetryMode(f.plan.stats, static_cast<uint64_t>(image.width) * image.height, retry);
+    *scanlines = ScanlinesIn(image.width, image.height, *retry);
+    return zamd::OnPooledContext([&](zmx_ctx* ctx) {
+      return ScanlinesOf(ctx, f.device, RowsOf(image, f.plan.seen), *retry, f.strategy, predefined, scan2);
+    }, f.device);
+  };
+}
+
+int IndexOne(const std::string& w, const ZopfliOptions* options, const zmx_png_index_image* image, int strategy, const unsigned char* predefined,
+             unsigned lossy, bool optimize, unsigned char** out, size_t* outsize) {
+  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
+  IndexFront f;
+  if (IndexFrontHalf(w, options, image, strategy, predefined, lossy, optimize, nullptr, &f) != 0) return -1;
+  if (optimize) {
+    return FinishOptimize(w, options, image->width, image->height, f.plan.mode, f.scan.p, f.scanlines, SecondTryOf(f, *image, predefined), out,
+                          outsize);
+  }
+  File file;
+  file.BeginIn(image->width, image->height, f.plan.mode);
+  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, f.scan.p, f.scanlines, &file.bytes, &file.size) != 0) return -1;
+  if (!file.Close()) return BadStream(w);
+  file.GiveTo(out, outsize);
+  return 0;
+}
+
+int IndexOneToDevice(const std::string& w, const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                     const unsigned char* predefined, unsigned lossy, bool optimize, void* d_out, size_t capacity, size_t* outsize) {
+  if (!options || !image || !outsize) return Refuse(w + ": null argument");
+  *outsize = 0;
+  const DeviceDest dest{d_out, capacity};
+  IndexFront f;
+  if (IndexFrontHalf(w, options, image, strategy, predefined, lossy, optimize, &dest, &f) != 0) return -1;
+  if (optimize) {
+    return FinishOptimizeToDevice(w, options, f.device, image->width, image->height, f.plan.mode, f.scan.p, f.scanlines,
+                                  SecondTryOf(f, *image, predefined), d_out, capacity, outsize);
+  }
+  const zamd::PngFrame frame = FrameIn(image->width, image->height, f.plan.mode);
+  return zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, f.scan.p, f.scanlines, d_out, capacity, outsize, &frame);
+}
+
+// Both batches: image by image one k_png_index_use, the host step and one k_png_index_convert on one hold of a context,
+// ONE zmx_compress_device_batch over all scanlines, and for `optimize` one more hold and one more batch for the second tries.
+int IndexBatch(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy, unsigned lossy,
+               bool optimize, unsigned char** out, size_t* outsize) {
+  if (n == 0) return 0;
+  if (!options || !images || !out || !outsize) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+  if (strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
+  if (!StrategyOk(strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
+  std::vector<const void*> pixels(n);
+  std::vector<size_t> nbytes(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (CheckIndexImage(w + ": image " + std::to_string(i), images[i], &nbytes[i]) != 0) return -1;
+    pixels[i] = images[i].d_pixels;
+  }
+  int device = -1;
+  if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &device) != 0) return -1;
+  // (CompressInto's view of the images: their width and height)
+  std::vector<zmx_png_image> dims(n);
+  for (size_t i = 0; i < n; ++i) dims[i] = zmx_png_image{nullptr, images[i].width, images[i].height, 0, 0};
+  std::vector<IndexPlan> plan(n);
+  std::vector<int> chosen(n, strategy);   // (_AUTO: the strategy of each image's own trials)
+  std::vector<size_t> all(n), start(n + 1, 0);
+  std::vector<zmx_png_color_mode> modes(n);
+  const std::vector<char> converted(n, 0);   // (no file is "the image as it is")
+  DeviceBuffer scan, room;
+  scan.device = room.device = device;
+  int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    size_t most = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const std::string wi = w + ": image " + std::to_string(i);
+      if (zmx_png_index_use_device(ctx, &images[i], plan[i].first) != 0) return -1;
+      if (PlanIndex(wi, images[i], lossy, optimize, &plan[i]) != 0) return -1;
+      if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, device, RowsOf(images[i], plan[i].seen), plan[i].mode,
+                                                            optimize ? &plan[i].stats : nullptr, nullptr, &chosen[i], nullptr) != 0) {
+        return -1;
+      }
+      const size_t scanlines = ScanlinesIn(images[i].width, images[i].height, plan[i].mode);
+      if (scanlines > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
+      start[i + 1] = start[i] + scanlines;
+      most = std::max(most, scanlines);
+    }
+    if (zmx_internal_device_alloc(device, start[n], &scan.p) != 0) return -1;
+    if (zmx_internal_device_alloc(device, most, &room.p) != 0) return -1;
+    for (size_t i = 0; i < n; ++i) {
+      if (ScanlinesOf(ctx, RowsOf(images[i], plan[i].seen), plan[i].mode, chosen[i], nullptr, room.p,
+                      static_cast<unsigned char*>(scan.p) + start[i]) != 0) {
+        return -1;
+      }
+    }
+    return 0;
+  }, device);
+  if (rc != 0) return -1;
+  for (size_t i = 0; i < n; ++i) {
+    all[i] = i;
+    modes[i] = plan[i].mode;
+  }
+  std::vector<File> files(n);
+  if (CompressInto(options, w, dims.data(), all, modes, converted, static_cast<const unsigned char*>(scan.p), start, &files) != 0) return -1;
+  // zopflipng's second try at the small palette files, all of them in one more batch
+  std::vector<size_t> again;
+  for (size_t i = 0; optimize && i < n; ++i) {
+    if (plan[i].mode.colortype == 3 && files[i].size < zamd::kPngRetryBelow) again.push_back(i);
+  }
+  std::vector<File> seconds(again.size());
+  if (!again.empty()) {
+    const size_t m = again.size();
+    std::vector<zmx_png_color_mode> modes2(m);
+    std::vector<size_t> start2(m + 1, 0);
+    size_t most = 0;
+    for (size_t k = 0; k < m; ++k) {
+      const zmx_png_index_image& im = images[again[k]];
+      zamd::PngRetryMode(plan[again[k]].stats, static_cast<uint64_t>(im.width) * im.height, &modes2[k]);
+      start2[k + 1] = start2[k] + ScanlinesIn(im.width, im.height, modes2[k]);
+      most = std::max(most, start2[k + 1] - start2[k]);
+    }
+    DeviceBuffer scan2, room2;
+    scan2.device = room2.device = device;
+    if (zmx_internal_device_alloc(device, start2[m], &scan2.p) != 0) return -1;
+    if (zmx_internal_device_alloc(device, most, &room2.p) != 0) return -1;
+    rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+      for (size_t k = 0; k < m; ++k) {
+        if (ScanlinesOf(ctx, RowsOf(images[again[k]], plan[again[k]].seen), modes2[k], chosen[again[k]], nullptr, room2.p,
+                        static_cast<unsigned char*>(scan2.p) + start2[k]) != 0) {
+          return -1;
+        }
+      }
+      return 0;
+    }, device);
+    if (rc != 0) return -1;
+    const std::vector<char> converted2(m, 0);
+    if (CompressInto(options, w, dims.data(), again, modes2, converted2, static_cast<const unsigned char*>(scan2.p), start2, &seconds) != 0) return -1;
+  }
+  // every file made before any out[i] is touched
+  std::vector<File*> kept(n);
+  for (size_t i = 0; i < n; ++i) kept[i] = &files[i];
+  for (size_t k = 0; k < again.size(); ++k) kept[again[k]] = &Smaller(files[again[k]], seconds[k]);
+  for (size_t i = 0; i < n; ++i) kept[i]->GiveTo(&out[i], &outsize[i]);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int zmx_png_index_color_stats(const zmx_png_index_image* image, const uint64_t first[256], unsigned lossy, zmx_png_color_stats* out) {
+  const std::string w = "zmx_png_index_color_stats";
+  if (!image || !first || !out) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+  size_t nbytes = 0;
+  if (CheckIndexImage(w, *image, &nbytes) != 0) return -1;
+  IndexPlan plan;
+  std::copy(first, first + 256, plan.first);
+  if (PlanIndex(w, *image, lossy, true, &plan) != 0) return -1;
+  *out = plan.stats;
+  return 0;
+}
+
+extern "C" int zmx_png_index_table(const zmx_png_index_image* image, const uint64_t first[256], unsigned lossy, const zmx_png_color_mode* mode,
+                                   uint32_t table[256]) {
+  const std::string w = "zmx_png_index_table";
+  if (!image || !first || !mode || !table) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+  size_t nbytes = 0;
+  if (CheckIndexImage(w, *image, &nbytes) != 0) return -1;
+  if (!zamd::PngIndexOutModeOk(mode->colortype, mode->bitdepth) || (mode->colortype == 3 && (mode->palettesize == 0 || mode->palettesize > 256))) {
+    return Refuse(w + ": colour type " + std::to_string(mode->colortype) + " at " + std::to_string(mode->bitdepth) +
+                  " bits is no mode an index image converts to");
+  }
+  IndexPlan plan;
+  std::copy(first, first + 256, plan.first);
+  if (PlanIndex(w, *image, lossy, true, &plan) != 0) return -1;
+  zamd::PngIndexTable(plan.seen, *mode, table);
+  return 0;
+}
+
+extern "C" int zmx_png_index_keep_plan(const zmx_png_index_image* image, const uint64_t first[256], unsigned lossy, zmx_png_color_mode* mode,
+                                       uint32_t table[256]) {
+  const std::string w = "zmx_png_index_keep_plan";
+  if (!image || !first || !mode || !table) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+  size_t nbytes = 0;
+  if (CheckIndexImage(w, *image, &nbytes) != 0) return -1;
+  if (CheckInsidePalette(w, *image, first) != 0) return -1;
+  zamd::PngIndexKeepPlan(*image, first, (lossy & ZMX_PNG_LOSSY_TRANSPARENT) != 0, mode, table);
+  return 0;
+}
+
+extern "C" int zmx_png_index_choose_strategy_device(zmx_ctx* ctx, const zmx_png_index_image* image, int reduce_color, unsigned lossy,
+                                                    const unsigned char* predefined, int* strategy, uint64_t file_bytes[8]) {
+  const std::string w = "zmx_png_index_choose_strategy_device";
+  if (!ctx || !image || !strategy || !file_bytes) return Refuse(w + ": null argument");
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+  size_t nbytes = 0;
+  if (CheckIndexImage(w, *image, &nbytes) != 0) return -1;
+  if (CheckPredefined(w, ZMX_PNG_FILTER_AUTO, predefined, image->height) != 0) return -1;
+  int device = -1;
+  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, nbytes, &device) != 0) return -1;
+  IndexPlan plan;
+  if (zmx_png_index_use_device(ctx, image, plan.first) != 0) return -1;
+  if (PlanIndex(w, *image, lossy, reduce_color != 0, &plan) != 0) return -1;
+  int chosen = 0;
+  uint64_t bytes[8];
+  if (ChooseStrategy(ctx, w, device, RowsOf(*image, plan.seen), plan.mode, reduce_color ? &plan.stats : nullptr, predefined, &chosen, bytes) != 0) {
+    return -1;
+  }
+  *strategy = chosen;
+  for (int k = 0; k < 8; ++k) file_bytes[k] = bytes[k];
+  return 0;
+}
+
+extern "C" size_t zmx_png_index_bound(uint32_t width, uint32_t height, uint32_t colortype, uint32_t bitdepth) {
+  if (width == 0 || height == 0 || !zamd::PngIndexFormatOk(colortype, bitdepth)) return 0;
+  if (static_cast<uint64_t>(width) * height > 0xffffffffull) return 0;
+  return zamd::PngIndexBound(width, height);
+}
+
+extern "C" int zmx_png_index_encode_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                           const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  return IndexOne("zmx_png_index_encode_device", options, image, strategy, predefined, lossy, false, out, outsize);
+}
+extern "C" int zmx_png_index_optimize_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                             const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  return IndexOne("zmx_png_index_optimize_device", options, image, strategy, predefined, lossy, true, out, outsize);
+}
+extern "C" int zmx_png_index_encode_device_to_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                                     const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                                     size_t* outsize) {
+  return IndexOneToDevice("zmx_png_index_encode_device_to_device", options, image, strategy, predefined, lossy, false, d_out, capacity, outsize);
+}
+extern "C" int zmx_png_index_optimize_device_to_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                                       const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                                       size_t* outsize) {
+  return IndexOneToDevice("zmx_png_index_optimize_device_to_device", options, image, strategy, predefined, lossy, true, d_out, capacity, outsize);
+}
+extern "C" int zmx_png_index_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
+                                                 unsigned lossy, unsigned char** out, size_t* outsize) {
+  return IndexBatch("zmx_png_index_encode_device_batch", options, n, images, strategy, lossy, false, out, outsize);
+}
+extern "C" int zmx_png_index_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
+                                                   unsigned lossy, unsigned char** out, size_t* outsize) {
+  return IndexBatch("zmx_png_index_optimize_device_batch", options, n, images, strategy, lossy, true, out, outsize);
 }

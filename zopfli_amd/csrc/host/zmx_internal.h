@@ -136,11 +136,11 @@ int zmx_internal_png_lossy_image(zmx_ctx* ctx, const char* who, const zmx_png_im
                                  zmx_png_image* work);
 
 // ---- zopflipng's filter-strategy trials (png_encode.cc: zmx_png_choose_strategy_device, ZMX_PNG_FILTER_AUTO)
-// The image converted to `mode` once (null: as it is), then the scanlines of trial k = 0 .. ntrials - 1 at
-// d_out + k * height * (rowbytes + 1), in zopflipng's order: the types 0 .. 4, MINSUM, ENTROPY and, for ntrials = 8, the
-// `height` host bytes at `predefined`, each at most 4.  d_out is memory of the context's device that the caller owns.
-// 0, or -1 with the error set, its message starting with `who`.
-int zmx_internal_png_trial_scanlines(zmx_ctx* ctx, const char* who, const zmx_png_image* image, const zmx_png_color_mode* mode,
+// The scanlines of trial k = 0 .. ntrials - 1 of an image that lies converted at d_rows (`height` rows of `rowbytes` bytes,
+// `bytewidth` the distance to the left neighbour) at d_out + k * height * (rowbytes + 1), in zopflipng's order: the types
+// 0 .. 4, MINSUM, ENTROPY and, for ntrials = 8, the `height` host bytes at `predefined`, each at most 4.  Both are memory of
+// the context's device; d_out the caller owns.  0, or -1 with the error set, its message starting with `who`.
+int zmx_internal_png_trial_scanlines(zmx_ctx* ctx, const char* who, const void* d_rows, size_t rowbytes, size_t height, size_t bytewidth,
                                      const unsigned char* predefined, int ntrials, void* d_out);
 
 // ---- for tests and tools
@@ -158,6 +158,9 @@ ZMX_INTERNAL_EXPORT void zmx_internal_png_color_ms(double out[3]);
 // The same for the calling thread's last zmx_png_lossy_transparent_device: k_png_lossy_stats, k_png_lossy_carry,
 // k_png_lossy_fill (0: not launched).  For tools/png_lossy.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_png_lossy_ms(double out[3]);
+// The same for the calling thread's last zmx_png_index_use_device and zmx_png_index_convert_device: k_png_index_use,
+// k_png_index_convert.  For tools/png_index.py.
+ZMX_INTERNAL_EXPORT void zmx_internal_png_index_ms(double out[2]);
 // The same for the calling thread's last zmx_png_deflate_sizes_device: k_png_lo_hash, k_png_lo_links, k_png_lo_ask,
 // k_png_lo_keep, k_png_lo_search, k_png_lo_parse.  For tools/png_auto.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_png_lodeflate_ms(double out[6]);
