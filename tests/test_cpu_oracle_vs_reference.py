@@ -1,6 +1,9 @@
 """Pins the CPU oracle (oracle/zopfli_oracle.c) to the REAL reference: the functions of
 oracle/_ref/libzopfli_ref.so (compiled from /root/reference by oracle/Makefile) are called
-directly on the same inputs.  CPU only."""
+directly on the same inputs.  CPU only.
+
+The hash state itself — same[], prev1[], prev2[], which the tests here see only through the matches they lead to — is
+compared in test_cpu_hash_link_cases.py, on inputs at the run cap, the window's edge and block ends."""
 import numpy as np
 import pytest
 
