@@ -669,6 +669,70 @@ int zmx_png_encode_device_batch_packed(const ZopfliOptions* options, size_t n, c
                                        unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
                                        size_t* outsize);
 
+/* -------- strided, planar, float and 16-bit sources
+ *
+ * What a GPU program holds instead of a zmx_png_image: a (C, H, W) or (N, C, H, W) tensor, float samples in [0, 1],
+ * native (little-endian) 16-bit ones, a frame with a row pitch, BGRA, bottom-up, a crop or a [::2] view.  A zmx_png_source
+ * says where sample (y, x, c) lies; its PACKED image is the zmx_png_image of colour type 0 / 4 / 2 / 6 for 1 / 2 / 3 / 4
+ * channels at `bitdepth`, rows back to back, PNG channel k of a pixel being source channel order[k].
+ * The value rule is exact:
+ *   U8 -> 8 the byte; U16 -> 16 the value, high byte first; U8 -> 16 and U16 -> 8 are refused (ZMX_PNG_LOSSY_8BIT of the
+ *   optimize entries is the way to 8 bits); F16 and BF16 are widened to fp32 exactly and follow the F32 rule;
+ *   F32 -> 8 or 16, maxv = 255.0f or 65535.0f: q = (uint32) clamp(fl32(fl32(x * maxv) + 0.5f), 0, maxv) — the multiply
+ *   and the add each rounded to fp32, the conversion truncating, a NaN giving 0: torchvision's
+ *   mul(maxv).add_(0.5).clamp_(0, maxv).to(int), what numpy.float32 arithmetic gives.
+ * zmx_png_source_image: host arithmetic — the packed image's mode in *image (d_pixels null) and its size in *nbytes
+ * (either may be null); -1 (ZMX_ERR_REFUSED) for a source the entries refuse without asking the runtime about its memory.
+ * zmx_png_pack_device: the packed images of n sources at d_out[i] (capacity[i] bytes, any byte alignment), by ONE launch
+ * of k_png_pack (device/zmx_png_pack.h) on the context's stream, whatever n: every byte of every packed image is written
+ * exactly once, none outside, no source is written.  Synchronous; n = 0 returns 0.
+ * Refused before any launch (ZMX_ERR_REFUSED), the message naming the source's index: a null argument, width or height 0,
+ * channels outside 1 .. 4, an unknown sample type, a bit depth other than 8 or 16, the two refused conversions, an `order`
+ * that is no permutation of 0 .. channels - 1, d_data or a stride that is no multiple of the sample's size, a row of 2^31
+ * bytes or more, an EXTENT — from the lowest to one past the highest byte any sample touches, by the signs of the three
+ * strides — that overflows 64 bits, is not plain device memory of the context's device or leaves its allocation, a
+ * capacity below the packed size, a destination that is no device memory of that device or overlaps a source's extent or
+ * another destination.
+ * The zmx_png_*_source_* entries: the file, or files, that the entry of the same name without _source gives for the packed
+ * images, byte for byte — every strategy, _AUTO, _PREDEFINED where that entry takes it, both lossy flags; its conventions,
+ * refusals and failure behaviour unchanged, and the refusals above made before anything runs.  All packed images go into
+ * one buffer of the call's own by one k_png_pack launch on the first hold of a context; no pixel visits the host
+ * (zmx_last_input_traffic()[0] stays 0).  The to-device destinations may not overlap a source's extent either.  The bounds
+ * are those of zmx_png_source_image's mode (0 for a refused source). */
+#define ZMX_PNG_SAMPLE_U8 0
+#define ZMX_PNG_SAMPLE_U16 1 /* native, i.e. little-endian */
+#define ZMX_PNG_SAMPLE_F16 2
+#define ZMX_PNG_SAMPLE_BF16 3
+#define ZMX_PNG_SAMPLE_F32 4
+typedef struct zmx_png_source {
+  const void* d_data;                   /* sample (y, x, c) lies at d_data + y*stride_y + x*stride_x + c*stride_c (bytes) */
+  int64_t stride_y, stride_x, stride_c; /* bytes; multiples of the sample's size; any sign; 0 allowed (a broadcast) */
+  uint32_t width, height, channels /* 1 .. 4 */, sample /* ZMX_PNG_SAMPLE_* */;
+  uint32_t bitdepth;                    /* of the PNG: 8 or 16 */
+  uint8_t order[4];                     /* PNG channel k of a pixel is source channel order[k]; a permutation of 0 .. channels-1 */
+} zmx_png_source;
+int zmx_png_source_image(const zmx_png_source* src, zmx_png_image* image /* d_pixels left null */, size_t* nbytes);
+int zmx_png_pack_device(zmx_ctx* ctx, size_t n, const zmx_png_source* sources, void* const* d_out, const size_t* capacity);
+int zmx_png_encode_source_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                                 const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_optimize_source_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                                   const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_encode_source_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
+                                       unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_optimize_source_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
+                                         unsigned lossy, unsigned char** out, size_t* outsize);
+int zmx_png_encode_source_device_to_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                                           const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                           size_t* outsize);
+int zmx_png_optimize_source_device_to_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                                             const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                             size_t* outsize);
+int zmx_png_encode_source_device_batch_packed(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
+                                              unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
+                                              size_t* outsize);
+size_t zmx_png_source_bound(const zmx_png_source* source);
+size_t zmx_png_source_batch_bound(size_t n, const zmx_png_source* sources, size_t align);
+
 /* -------- palette, 1/2/4-bit grey and index images in device memory
  *
  * A label map (one byte a pixel plus a colour map), a binary mask (one bit a pixel), a 2- or 4-bit atlas: `height` rows of

@@ -424,6 +424,168 @@ def _png_image(image, sync=True):
     return PngImage(ptr or None, shape[1], shape[0], _PNG_COLORTYPE[shape[2]], 8)
 
 
+PNG_SAMPLE_U8, PNG_SAMPLE_U16, PNG_SAMPLE_F16, PNG_SAMPLE_BF16, PNG_SAMPLE_F32 = 0, 1, 2, 3, 4   # ZMX_PNG_SAMPLE_*
+_PNG_SAMPLE_OF_DTYPE = {"uint8": PNG_SAMPLE_U8, "uint16": PNG_SAMPLE_U16, "float16": PNG_SAMPLE_F16, "bfloat16": PNG_SAMPLE_BF16,
+                        "float32": PNG_SAMPLE_F32}
+
+
+class PngSourceStruct(ctypes.Structure):
+    """zmx_png_source"""
+    _fields_ = [("d_data", ctypes.c_void_p), ("stride_y", ctypes.c_int64), ("stride_x", ctypes.c_int64), ("stride_c", ctypes.c_int64),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("sample", ctypes.c_uint32),
+                ("bitdepth", ctypes.c_uint32), ("order", ctypes.c_uint8 * 4)]
+
+
+class PngSource:
+    """A zmx_png_source: an image as a GPU program holds it, for the png_* functions in an image's place.
+    `data`: a torch tensor of dtype uint8, uint16, float16, bfloat16 or float32 on the device, contiguous or not — a crop, a
+    [::2] view, a flip, an expand() all do; its strides are taken as they are, in bytes — of shape (H, W, C) or (H, W) with
+    layout "HWC", (C, H, W) or (H, W) with "CHW", C from 1 to 4; or a tuple that spells out the struct: (pointer, stride_y,
+    stride_x, stride_c, width, height, channels, sample, bitdepth[, order]).  Floats are taken as [0, 1] and quantised as
+    torchvision does: mul(maxv).add_(0.5).clamp_(0, maxv).to(int).  `order`: "RGBA" (the channels as they lie), "BGRA" (the
+    first three reversed) or a permutation: PNG channel k is the tensor's channel order[k].  `bitdepth`: of the PNG, 8 or 16;
+    None: 16 for uint16, else 8 (uint8 -> 16 and uint16 -> 8 are refused by the library).  Nothing is copied; the object
+    keeps the tensor alive."""
+
+    def __init__(self, data, layout="HWC", order="RGBA", bitdepth=None):
+        self.tensor = None
+        if isinstance(data, (tuple, list)):
+            ptr, sy, sx, sc, width, height, channels, sample, depth = data[:9]
+            if len(data) > 9:
+                order = data[9]
+            depth = int(depth)
+        else:
+            dtype = str(data.dtype).split(".")[-1]
+            if dtype not in _PNG_SAMPLE_OF_DTYPE:
+                raise ValueError(f"a source tensor is uint8, uint16, float16, bfloat16 or float32, not {dtype}")
+            if layout not in ("HWC", "CHW"):
+                raise ValueError(f'layout is "HWC" or "CHW", not {layout!r}')
+            shape, esize = tuple(data.shape), data.element_size()
+            strides = tuple(int(s) * esize for s in data.stride())
+            if len(shape) == 2:
+                shape, strides = (shape + (1,), strides + (esize,)) if layout == "HWC" else ((1,) + shape, (esize,) + strides)
+            if len(shape) != 3:
+                raise ValueError("a source tensor has two or three dimensions (png_sources takes a batch)")
+            (height, width, channels), (sy, sx, sc) = (shape, strides) if layout == "HWC" else (
+                (shape[1], shape[2], shape[0]), (strides[1], strides[2], strides[0]))
+            if not 1 <= channels <= 4:
+                raise ValueError(f"{channels} channels: an image has 1 to 4")
+            sample = _PNG_SAMPLE_OF_DTYPE[dtype]
+            depth = (16 if sample == PNG_SAMPLE_U16 else 8) if bitdepth is None else int(bitdepth)
+            ptr = data.data_ptr()
+            self.tensor = data
+        channels = int(channels)
+        if isinstance(order, str):
+            if order not in ("RGBA", "BGRA"):
+                raise ValueError(f'order is "RGBA", "BGRA" or a permutation, not {order!r}')
+            order = tuple(range(channels)) if order == "RGBA" or channels < 3 else (2, 1, 0, 3)[:channels]
+        order = tuple(int(k) for k in order)
+        if len(order) < channels or len(order) > 4:
+            raise ValueError(f"order names {len(order)} channels, the image has {channels}")
+        self.struct = PngSourceStruct(int(ptr) or None, int(sy), int(sx), int(sc), int(width), int(height), channels, int(sample), depth,
+                                      (ctypes.c_uint8 * 4)(*(order + (0,) * (4 - len(order)))))
+
+    @property
+    def height(self):
+        return int(self.struct.height)
+
+
+def png_sources(batch, layout="NCHW", order="RGBA", bitdepth=None):
+    """The PngSources of a batch tensor (N, C, H, W) or (N, H, W, C) — layout "NCHW" or "NHWC" —, one per image, views
+    without a copy: for the _batch functions."""
+    if layout not in ("NCHW", "NHWC"):
+        raise ValueError(f'layout is "NCHW" or "NHWC", not {layout!r}')
+    return [PngSource(batch[i], layout[1:], order, bitdepth) for i in range(batch.shape[0])]
+
+
+def _png_are_sources(images):
+    """Whether a list holds PngSources (all of it: a mixed list is an error)."""
+    kinds = {isinstance(image, PngSource) for image in images}
+    if kinds == {True, False}:
+        raise ValueError("a list holds PngSources or images, not both")
+    return kinds == {True}
+
+
+def _png_sync_sources(sources):
+    """The current stream of every distinct torch device among the sources' tensors, synchronised once."""
+    devices = {}
+    for s in sources:
+        if s.tensor is not None and type(s.tensor).__module__.split(".")[0] == "torch":
+            devices[str(s.tensor.device)] = s.tensor.device
+    if devices:
+        import torch
+        for device in devices.values():
+            torch.cuda.current_stream(device).synchronize()
+
+
+def _png_source_array(sources):
+    n = len(sources)
+    return (PngSourceStruct * max(n, 1))(*[s.struct for s in sources])
+
+
+def _png_source_single(name, source, strategy, options, predefined, lib, lossy):
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    types = _png_types(predefined, source.height)
+    _png_sync_sources([source])
+    out, outsize = _u8p(), ctypes.c_size_t(0)
+    fn = getattr(lib, name)
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngSourceStruct), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint,
+                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), ctypes.byref(source.struct), _png_strategy(strategy), types, lossy, ctypes.byref(out), ctypes.byref(outsize)) != 0:
+        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
+    return _take(out, outsize)
+
+
+def _png_source_batch(name, sources, strategy, options, lib, lossy):
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    _png_sync_sources(sources)
+    n = len(sources)
+    outs = (_u8p * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    fn = getattr(lib, name)
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngSourceStruct), ctypes.c_int, ctypes.c_uint,
+                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), n, _png_source_array(sources), _png_strategy(strategy), lossy, outs, outsizes) != 0:
+        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
+    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+
+
+def _png_source_out(name, source, dst, strategy, options, predefined, lib, lossy):
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    types = _png_types(predefined, source.height)
+    _png_sync_sources([source])
+    out, capacity = _device_range(int(dst[0]), dst[1]) if isinstance(dst, (tuple, list)) else _device_range(dst, None)
+    outsize = ctypes.c_size_t(0)
+    fn = getattr(lib, name)
+    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngSourceStruct), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint,
+                   ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(options), ctypes.byref(source.struct), _png_strategy(strategy), types, lossy, out, capacity, ctypes.byref(outsize)) != 0:
+        message = name + ": " + (lib.zmx_last_error() or b"").decode()
+        if outsize.value > capacity:
+            raise CapacityError(message, int(outsize.value))
+        raise RuntimeError(message)
+    return int(outsize.value)
+
+
+def png_source_image(source, lib=None):
+    """zmx_png_source_image: (width, height, colortype, bitdepth, bytes) of the packed image of a PngSource — host
+    arithmetic; RuntimeError for a source the entries refuse without asking the runtime about its memory."""
+    lib = lib or library()
+    im, nbytes = PngImage(), ctypes.c_size_t(0)
+    fn = lib.zmx_png_source_image
+    fn.argtypes = [ctypes.POINTER(PngSourceStruct), ctypes.POINTER(PngImage), ctypes.POINTER(ctypes.c_size_t)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(source.struct), ctypes.byref(im), ctypes.byref(nbytes)) != 0:
+        raise RuntimeError((lib.zmx_last_error() or b"").decode())
+    return int(im.width), int(im.height), int(im.colortype), int(im.bitdepth), int(nbytes.value)
+
+
 def png_encode_device(image, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_encode_device: the image in device memory as the PNG file `zopflipng --keepcolortype --always_zopflify
     --filters=<strategy>` writes for it (when options.numiterations is zopflipng's: 15 below 200 000 bytes of scanlines,
@@ -434,7 +596,11 @@ def png_encode_device(image, strategy="e", options=None, predefined=None, lib=No
     choice, the file it writes without --filters (`predefined`, where given, is the eighth trial).  `lossy_transparent`, `lossy_8bit`: zopflipng's
     --lossy_transparent and --lossy_8bit (zmx_png_encode_device_lossy; under --keepcolortype the second does nothing and
     the first nothing to a 16-bit image).  Returns the file's bytes.  Raises ValueError for a tensor that is no image,
-    RuntimeError with the library's message when the library refuses or fails."""
+    RuntimeError with the library's message when the library refuses or fails.
+    `image` may also be a PngSource — a strided, planar, float or 16-bit tensor as it lies (zmx_png_encode_source_device):
+    the file is the one its packed image gives."""
+    if isinstance(image, PngSource):
+        return _png_source_single("zmx_png_encode_source_device", image, strategy, options, predefined, lib, _png_lossy(lossy_transparent, lossy_8bit))
     lib = lib or library()
     options = options or ZopfliOptions()
     im = _png_image(image)
@@ -452,7 +618,10 @@ def png_encode_device(image, strategy="e", options=None, predefined=None, lib=No
 def png_encode_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_encode_device_batch: one PNG file per image, each the one png_encode_device gives, from one call that
     shares its deflate work among them.  `images`: a list of what png_encode_device takes (the current stream of every
-    torch device among the tensors is synchronised once).  Predefined types are the single call's."""
+    torch device among the tensors is synchronised once).  Predefined types are the single call's.  A list of PngSources
+    (png_sources gives one for a batch tensor) goes to zmx_png_encode_source_device_batch: one launch packs them all."""
+    if _png_are_sources(images):
+        return _png_source_batch("zmx_png_encode_source_device_batch", images, strategy, options, lib, _png_lossy(lossy_transparent, lossy_8bit))
     lib = lib or library()
     options = options or ZopfliOptions()
     ims = [_png_image(image, sync=False) for image in images]
@@ -514,7 +683,9 @@ def png_optimize_device(image, strategy="e", options=None, predefined=None, lib=
     bits where the pixels allow it, and RGB or RGBA instead of a palette where that makes a small file smaller.
     `lossy_8bit` encodes a 16-bit image as the 8-bit image of its high bytes, `lossy_transparent` gives the pixels with
     alpha 0 of an image that is 8-bit by then the RGB zopflipng gives them (zmx_png_optimize_device_lossy).  Arguments,
-    result and errors as png_encode_device's."""
+    result and errors as png_encode_device's, a PngSource included (zmx_png_optimize_source_device)."""
+    if isinstance(image, PngSource):
+        return _png_source_single("zmx_png_optimize_source_device", image, strategy, options, predefined, lib, _png_lossy(lossy_transparent, lossy_8bit))
     lib = lib or library()
     options = options or ZopfliOptions()
     im = _png_image(image)
@@ -531,7 +702,9 @@ def png_optimize_device(image, strategy="e", options=None, predefined=None, lib=
 
 def png_optimize_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_optimize_device_batch: one file per image, each the one png_optimize_device gives, from one call.
-    Arguments as png_encode_device_batch's."""
+    Arguments as png_encode_device_batch's, a list of PngSources included (zmx_png_optimize_source_device_batch)."""
+    if _png_are_sources(images):
+        return _png_source_batch("zmx_png_optimize_source_device_batch", images, strategy, options, lib, _png_lossy(lossy_transparent, lossy_8bit))
     lib = lib or library()
     options = options or ZopfliOptions()
     ims = [_png_image(image, sync=False) for image in images]
@@ -553,10 +726,16 @@ def png_optimize_device_batch(images, strategy="e", options=None, lib=None, loss
     return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
 
 
-def png_bound(width, height, colortype, bitdepth, lib=None):
+def png_bound(width, height=None, colortype=None, bitdepth=None, lib=None):
     """zmx_png_bound: a destination capacity that does for png_encode_device_out and png_optimize_device_out of any image
-    of this width, height, colour type and bit depth (0 for a mode the entries refuse)."""
+    of this width, height, colour type and bit depth (0 for a mode the entries refuse).  png_bound(source) of a PngSource:
+    zmx_png_source_bound, the bound of its packed image's mode."""
     lib = lib or library()
+    if isinstance(width, PngSource):
+        fn = lib.zmx_png_source_bound
+        fn.argtypes = [ctypes.POINTER(PngSourceStruct)]
+        fn.restype = ctypes.c_size_t
+        return int(fn(ctypes.byref(width.struct)))
     fn = lib.zmx_png_bound
     fn.argtypes = [ctypes.c_uint32] * 4
     fn.restype = ctypes.c_size_t
@@ -565,8 +744,14 @@ def png_bound(width, height, colortype, bitdepth, lib=None):
 
 def png_batch_bound(images, align=1, lib=None):
     """zmx_png_batch_bound: an arena capacity that does for png_encode_device_batch_packed of these images (what
-    png_encode_device takes, or bare (None, width, height, colortype, bitdepth) tuples: the pixels are not looked at)."""
+    png_encode_device takes, or bare (None, width, height, colortype, bitdepth) tuples: the pixels are not looked at), or of
+    these PngSources (zmx_png_source_batch_bound)."""
     lib = lib or library()
+    if _png_are_sources(images):
+        fn = lib.zmx_png_source_batch_bound
+        fn.argtypes = [ctypes.c_size_t, ctypes.POINTER(PngSourceStruct), ctypes.c_size_t]
+        fn.restype = ctypes.c_size_t
+        return int(fn(len(images), _png_source_array(images), int(align)))
     ims = [_png_image(image, sync=False) for image in images]
     n = len(ims)
     fn = lib.zmx_png_batch_bound
@@ -601,14 +786,21 @@ def png_encode_device_out(image, dst, strategy="e", options=None, predefined=Non
     """zmx_png_encode_device_to_device: png_encode_device's file left in device memory.  `dst`: a contiguous tensor or an
     (integer device pointer, capacity) pair on the image's device, of any byte alignment.  Returns the file's size: its
     bytes are dst[0, size), and no byte behind them is written.  Raises CapacityError (with the size needed, nothing
-    written) when the file does not fit — png_bound gives a capacity that always does —, otherwise as png_encode_device."""
+    written) when the file does not fit — png_bound gives a capacity that always does —, otherwise as png_encode_device.
+    A PngSource goes to zmx_png_encode_source_device_to_device; `dst` may not overlap the bytes its samples span."""
+    if isinstance(image, PngSource):
+        return _png_source_out("zmx_png_encode_source_device_to_device", image, dst, strategy, options, predefined, lib,
+                               _png_lossy(lossy_transparent, lossy_8bit))
     return _png_device_out("zmx_png_encode_device_to_device", image, dst, strategy, options, predefined, lib,
                            _png_lossy(lossy_transparent, lossy_8bit))
 
 
 def png_optimize_device_out(image, dst, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_optimize_device_to_device: png_optimize_device's file left in device memory; arguments, result and errors as
-    png_encode_device_out's."""
+    png_encode_device_out's (a PngSource: zmx_png_optimize_source_device_to_device)."""
+    if isinstance(image, PngSource):
+        return _png_source_out("zmx_png_optimize_source_device_to_device", image, dst, strategy, options, predefined, lib,
+                               _png_lossy(lossy_transparent, lossy_8bit))
     return _png_device_out("zmx_png_optimize_device_to_device", image, dst, strategy, options, predefined, lib,
                            _png_lossy(lossy_transparent, lossy_8bit))
 
@@ -617,9 +809,24 @@ def png_encode_device_batch_packed(images, arena, align=1, strategy="e", options
     """zmx_png_encode_device_batch_packed: png_encode_device_batch's files packed into `arena`, a contiguous tensor or an
     (integer device pointer, capacity) pair: file i begins at the end of file i - 1 rounded up to `align` (a power of two,
     1 .. 4096); the bytes between files are not written.  Returns (offsets, sizes).  Raises CapacityError (`needed`: the
-    list of sizes, nothing written) when the arena is too small — png_batch_bound gives one that does."""
+    list of sizes, nothing written) when the arena is too small — png_batch_bound gives one that does.  A list of PngSources
+    goes to zmx_png_encode_source_device_batch_packed."""
     lib = lib or library()
     options = options or ZopfliOptions()
+    if _png_are_sources(images):
+        _png_sync_sources(images)
+        out, capacity = _device_range(int(arena[0]), arena[1]) if isinstance(arena, (tuple, list)) else _device_range(arena, None)
+        n = len(images)
+        offsets = (ctypes.c_size_t * max(n, 1))()
+        outsizes = (ctypes.c_size_t * max(n, 1))()
+        fn = lib.zmx_png_encode_source_device_batch_packed
+        fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngSourceStruct), ctypes.c_int, ctypes.c_uint,
+                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+        fn.restype = ctypes.c_int
+        if fn(ctypes.byref(options), n, _png_source_array(images), _png_strategy(strategy), _png_lossy(lossy_transparent, lossy_8bit), out,
+              capacity, int(align), offsets, outsizes) != 0:
+            raise _batch_failure("zmx_png_encode_source_device_batch_packed", lib, outsizes, n)
+        return [int(offsets[i]) for i in range(n)], [int(outsizes[i]) for i in range(n)]
     ims = [_png_image(image, sync=False) for image in images]
     devices = {}
     for image in images:
@@ -1091,6 +1298,23 @@ class Context:
         fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(PngImage), ctypes.POINTER(PngColorMode), ctypes.c_void_p, ctypes.c_size_t]
         fn.restype = ctypes.c_int
         self._check(fn(self.handle, ctypes.byref(im), ctypes.byref(mode), dst or None, capacity), "zmx_png_convert_device")
+
+    def png_pack_device(self, sources, outs):
+        """zmx_png_pack_device: the packed images of `sources` (PngSources: rows back to back, PNG byte order, 16-bit
+        samples big-endian) into `outs`, as many contiguous tensors or (integer device pointer, capacity) pairs on this
+        context's device, of any byte alignment — ONE launch whatever their number.  The tensors' current streams are
+        synchronised once per device."""
+        if len(sources) != len(outs):
+            raise ValueError(f"{len(sources)} sources, but {len(outs)} destinations")
+        _png_sync_sources(sources)
+        ptrs, capacities = _device_ranges(outs)
+        n = len(sources)
+        fn = self.lib.zmx_png_pack_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(PngSourceStruct), ctypes.POINTER(ctypes.c_void_p),
+                       ctypes.POINTER(ctypes.c_size_t)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, n, _png_source_array(sources), (ctypes.c_void_p * max(n, 1))(*ptrs),
+                       (ctypes.c_size_t * max(n, 1))(*capacities)), "zmx_png_pack_device")
 
     def png_lossy_transparent_device(self, image, out, capacity=None):
         """zmx_png_lossy_transparent_device: zopflipng's --lossy_transparent rewrite of the image (`image` as

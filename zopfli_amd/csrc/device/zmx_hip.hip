@@ -48,6 +48,8 @@
 #include "zmx_png_color.h"   // LodePNG's colour statistics and colour conversion
 #define ZMX_PNG_INDEX_KERNELS
 #include "zmx_png_index.h"   // index images: where each value first appears, the table-driven conversion
+#define ZMX_PNG_PACK_KERNELS
+#include "zmx_png_pack.h"    // strided, planar, typed sources into PNG byte order, n of them in one launch
 #define ZMX_PNG_LOSSY_KERNELS
 #include "zmx_png_lossy.h"   // zopflipng's --lossy_transparent: statistics, the carry scan, the rewrite
 #define ZMX_PNG_LODEFLATE_KERNELS
@@ -59,6 +61,7 @@
 #include "../host/png_color_choose.h"
 #include "../host/png_index.h"
 #include "../host/png_lodeflate_size.h"
+#include "../host/png_source.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
 
@@ -75,5 +78,6 @@
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
 #include "drv_checksum_device.h"   // zmx_checksum_device, the seal of a PNG left in device memory
 #include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion, index images, LodePNG's zlib sizes
+#include "drv_png_pack.h"    // zmx_png_pack_device
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries
 #include "drv_probes.h"      // the parity probes: digest, longest match, hash links, length array, DP rows

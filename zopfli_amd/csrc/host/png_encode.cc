@@ -20,6 +20,9 @@
 // The _to_device entries and zmx_png_encode_device_batch_packed leave the file in device memory: the same first hold (the
 // *FrontHalf functions, shared with the host-output entries), then the to-device compress path with the file's frame
 // around the stream (device_output_plan.h: PngFrame) and the IDAT's CRC-32 sealed on the device.
+// The zmx_png_*_source_* entries, last, take strided, planar, float and 16-bit sources (png_source.h): every source
+// checked, one buffer for all packed images, one hold of a context for one k_png_pack launch, then the entry of the same
+// name without _source on zmx_png_images that point into the buffer.
 #include <algorithm>
 #include <cstdlib>
 #include <functional>
@@ -32,6 +35,7 @@
 #include "png_color_choose.h"
 #include "png_container.h"
 #include "png_index.h"
+#include "png_source.h"
 #include "zmx_internal.h"
 #include "zopfli_amd.h"
 
@@ -1276,4 +1280,158 @@ extern "C" int zmx_png_index_encode_device_batch(const ZopfliOptions* options, s
 extern "C" int zmx_png_index_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
                                                    unsigned lossy, unsigned char** out, size_t* outsize) {
   return IndexBatch("zmx_png_index_optimize_device_batch", options, n, images, strategy, lossy, true, out, outsize);
+}
+
+// ---- strided, planar, float and 16-bit sources (png_source.h; device/zmx_png_pack.h)
+namespace {
+
+// The packed images of n sources in ONE buffer of the call's own, slices rounded up to 16 bytes, made by one k_png_pack
+// launch on one hold of a context: images[i] is source i as the other entries take it.
+struct Packed {
+  DeviceBuffer buf;
+  std::vector<zmx_png_image> images;
+};
+
+// Every source checked — with `dest`, the to-device entry's destination, held against the sources' extents — before
+// anything runs; then the buffer and the launch.
+int PackSources(const std::string& w, size_t n, const zmx_png_source* sources, const DeviceDest* dest, Packed* p) {
+  std::vector<size_t> start(n + 1, 0), sizes(n), extent_bytes(n);
+  std::vector<const void*> extent(n);
+  p->images.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    zamd::PngSourcePlan plan;
+    const std::string msg = zamd::CheckPngSource((w + ": source " + std::to_string(i)).c_str(), &sources[i], &plan);
+    if (!msg.empty()) return Refuse(msg);
+    p->images[i] = plan.image;
+    sizes[i] = plan.nbytes;
+    const size_t slice = (plan.nbytes + 15) & ~static_cast<size_t>(15);
+    if (slice > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
+    start[i + 1] = start[i] + slice;
+    extent[i] = reinterpret_cast<const void*>(plan.lo);
+    extent_bytes[i] = plan.hi - plan.lo;
+  }
+  // (the device of the first extent; the pack holds every extent against its context's device)
+  if (zmx_internal_device_pointer((w + ": source 0: the extent").c_str(), extent[0], extent_bytes[0], &p->buf.device) != 0) return -1;
+  if (dest && CheckDest(w, *dest, p->buf.device, n, extent.data(), extent_bytes.data()) != 0) return -1;
+  if (zmx_internal_device_alloc(p->buf.device, start[n], &p->buf.p) != 0) return -1;
+  std::vector<void*> outs(n);
+  for (size_t i = 0; i < n; ++i) {
+    outs[i] = static_cast<unsigned char*>(p->buf.p) + start[i];
+    p->images[i].d_pixels = outs[i];
+  }
+  return zamd::OnPooledContext([&](zmx_ctx* ctx) { return zmx_internal_png_pack(ctx, w.c_str(), n, sources, outs.data(), sizes.data()); },
+                               p->buf.device);
+}
+
+// What the entries behind the pack refuse of their other arguments, held in front of it: nothing runs for a call that is
+// refused anyway.
+int CheckBehindPack(const std::string& w, int strategy, unsigned lossy, bool single, const unsigned char* predefined, const zmx_png_source* source) {
+  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
+  if (!single && strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
+  if (!StrategyOk(strategy, single)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
+  if (single && source && CheckPredefined(w, strategy, predefined, source->height) != 0) return -1;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int zmx_png_source_image(const zmx_png_source* src, zmx_png_image* image, size_t* nbytes) {
+  zamd::PngSourcePlan plan;
+  const std::string msg = zamd::CheckPngSource("zmx_png_source_image", src, &plan);
+  if (!msg.empty()) return Refuse(msg);
+  if (image) *image = plan.image;
+  if (nbytes) *nbytes = plan.nbytes;
+  return 0;
+}
+
+extern "C" size_t zmx_png_source_bound(const zmx_png_source* source) {
+  zamd::PngSourcePlan plan;
+  if (!zamd::CheckPngSource("zmx_png_source_bound", source, &plan).empty()) return 0;
+  return zmx_png_bound(plan.image.width, plan.image.height, plan.image.colortype, plan.image.bitdepth);
+}
+extern "C" size_t zmx_png_source_batch_bound(size_t n, const zmx_png_source* sources, size_t align) {
+  if (n == 0 || !sources) return 0;
+  std::vector<zmx_png_image> images(n);
+  for (size_t i = 0; i < n; ++i) {
+    zamd::PngSourcePlan plan;
+    if (!zamd::CheckPngSource("zmx_png_source_batch_bound", &sources[i], &plan).empty()) return 0;
+    images[i] = plan.image;
+  }
+  return zmx_png_batch_bound(n, images.data(), align);
+}
+
+extern "C" int zmx_png_encode_source_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                                            const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  const std::string w = "zmx_png_encode_source_device";
+  if (!options || !source || !out || !outsize) return Refuse(w + ": null argument");
+  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
+  Packed p;
+  if (PackSources(w, 1, source, nullptr, &p) != 0) return -1;
+  return EncodeOne(w, options, &p.images[0], strategy, predefined, lossy, out, outsize);
+}
+extern "C" int zmx_png_optimize_source_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                                              const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  const std::string w = "zmx_png_optimize_source_device";
+  if (!options || !source || !out || !outsize) return Refuse(w + ": null argument");
+  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
+  Packed p;
+  if (PackSources(w, 1, source, nullptr, &p) != 0) return -1;
+  return OptimizeOne(w, options, &p.images[0], strategy, predefined, lossy, out, outsize);
+}
+extern "C" int zmx_png_encode_source_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
+                                                  unsigned lossy, unsigned char** out, size_t* outsize) {
+  const std::string w = "zmx_png_encode_source_device_batch";
+  if (n == 0) return 0;
+  if (!options || !sources || !out || !outsize) return Refuse(w + ": null argument");
+  if (CheckBehindPack(w, strategy, lossy, false, nullptr, nullptr) != 0) return -1;
+  Packed p;
+  if (PackSources(w, n, sources, nullptr, &p) != 0) return -1;
+  return EncodeBatch(w, options, n, p.images.data(), strategy, lossy, out, outsize);
+}
+extern "C" int zmx_png_optimize_source_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
+                                                    unsigned lossy, unsigned char** out, size_t* outsize) {
+  const std::string w = "zmx_png_optimize_source_device_batch";
+  if (n == 0) return 0;
+  if (!options || !sources || !out || !outsize) return Refuse(w + ": null argument");
+  if (CheckBehindPack(w, strategy, lossy, false, nullptr, nullptr) != 0) return -1;
+  Packed p;
+  if (PackSources(w, n, sources, nullptr, &p) != 0) return -1;
+  return OptimizeBatch(w, options, n, p.images.data(), strategy, lossy, out, outsize);
+}
+extern "C" int zmx_png_encode_source_device_to_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                                                      const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                                      size_t* outsize) {
+  const std::string w = "zmx_png_encode_source_device_to_device";
+  if (!options || !source || !outsize) return Refuse(w + ": null argument");
+  *outsize = 0;
+  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
+  const DeviceDest dest{d_out, capacity};
+  Packed p;
+  if (PackSources(w, 1, source, &dest, &p) != 0) return -1;
+  return EncodeOneToDevice(w, options, &p.images[0], strategy, predefined, lossy, d_out, capacity, outsize);
+}
+extern "C" int zmx_png_optimize_source_device_to_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                                                        const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                                        size_t* outsize) {
+  const std::string w = "zmx_png_optimize_source_device_to_device";
+  if (!options || !source || !outsize) return Refuse(w + ": null argument");
+  *outsize = 0;
+  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
+  const DeviceDest dest{d_out, capacity};
+  Packed p;
+  if (PackSources(w, 1, source, &dest, &p) != 0) return -1;
+  return OptimizeOneToDevice(w, options, &p.images[0], strategy, predefined, lossy, d_out, capacity, outsize);
+}
+extern "C" int zmx_png_encode_source_device_batch_packed(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
+                                                         unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
+                                                         size_t* outsize) {
+  const std::string w = "zmx_png_encode_source_device_batch_packed";
+  if (n == 0) return 0;
+  if (!options || !sources || !outoffset || !outsize) return Refuse(w + ": null argument");
+  if (!zamd::PackedAlignOk(align)) return Refuse(w + ": align " + std::to_string(align) + " is not a power of two from 1 to 4096");
+  if (CheckBehindPack(w, strategy, lossy, false, nullptr, nullptr) != 0) return -1;
+  const DeviceDest dest{d_arena, capacity};
+  Packed p;
+  if (PackSources(w, n, sources, &dest, &p) != 0) return -1;
+  return EncodeBatchPacked(w, options, n, p.images.data(), strategy, lossy, d_arena, capacity, align, outoffset, outsize);
 }

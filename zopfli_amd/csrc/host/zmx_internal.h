@@ -143,6 +143,10 @@ int zmx_internal_png_lossy_image(zmx_ctx* ctx, const char* who, const zmx_png_im
 int zmx_internal_png_trial_scanlines(zmx_ctx* ctx, const char* who, const void* d_rows, size_t rowbytes, size_t height, size_t bytewidth,
                                      const unsigned char* predefined, int ntrials, void* d_out);
 
+// ---- strided, planar and typed sources in front of the PNG entries (png_encode.cc: the _source entries)
+// zmx_png_pack_device(ctx, n, sources, d_out, capacity) whose refusals begin with `who`, the entry's name.
+int zmx_internal_png_pack(zmx_ctx* ctx, const char* who, size_t n, const zmx_png_source* sources, void* const* d_out, const size_t* capacity);
+
 // ---- for tests and tools
 // The copies of the calling thread's last zmx_gather_device — k_gather and the other devices' pieces — in milliseconds
 // (HIP events on the context's stream), taken while kernel timing is on (zmx_set_kernel_timing); else 0.  For
@@ -167,6 +171,8 @@ ZMX_INTERNAL_EXPORT void zmx_internal_png_lodeflate_ms(double out[6]);
 // The same for the calling thread's last zmx_checksum_device (or seal): k_checksum_pieces, k_checksum_finish.  For
 // tools/png_device_output.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_checksum_device_ms(double out[2]);
+// The same for the calling thread's last zmx_png_pack_device: k_png_pack.  For tools/png_source.py.
+ZMX_INTERNAL_EXPORT double zmx_internal_png_pack_ms(void);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
 // squeeze run computes them — *wmax, *tiemask —, no device involved.
 ZMX_INTERNAL_EXPORT void zmx_internal_run_info(const double* cost320, float* wmax, uint32_t* tiemask);
