@@ -2,6 +2,10 @@
 // program: the kernels' lanes one after the other (a barrier of k_png_lo_links is the end of a loop over the lanes),
 // the parse's staging straight from the arrays.
 //   png_lodeflate_print size WINDOW TILE FILE...   the files are the buffers of ONE call: prints a zlib size per file
+//   png_lodeflate_print arrays WINDOW TILE OUT FILE...   the same call; also writes HC, ZC, LD ([positions] each) and counts
+//                                                  ([blocks][kLoCountWords]) as the lanes left them to OUT: raw
+//                                                  little-endian uint32, one array after the other, in the plan's order
+// TILE 0 is the device's tile length.
 //   png_lodeflate_print huff FILE                  every byte a literal (no matches): the size from the bytes' counts per block
 //   png_lodeflate_print lengths MAXBITS COUNT...   LoCodeLengths of the counts
 #include <cstdio>
@@ -26,7 +30,12 @@ std::vector<unsigned char> ReadFile(const char* path) {
   return data;
 }
 
-std::vector<uint64_t> Sizes(const std::vector<std::vector<unsigned char>>& bufs, unsigned window, unsigned tile_len) {
+struct Arrays {   // of one call, as the device's scratch holds them when k_png_lo_parse has ended
+  std::vector<uint32_t> HC, ZC, LD, counts;
+};
+
+std::vector<uint64_t> Sizes(const std::vector<std::vector<unsigned char>>& bufs, unsigned window, unsigned tile_len, Arrays* arrays = nullptr) {
+  if (tile_len == 0) tile_len = zamd::kLoTileLen;
   std::vector<const void*> ptrs;
   std::vector<size_t> sizes;
   for (const auto& b : bufs) { ptrs.push_back(b.data()); sizes.push_back(b.size()); }
@@ -80,10 +89,18 @@ std::vector<uint64_t> Sizes(const std::vector<std::vector<unsigned char>>& bufs,
     for (int i = 0; i < 286; ++i) blocks[b].ll[i] = cnt[i];
     for (int i = 0; i < 30; ++i) blocks[b].d[i] = cnt[286 + i];
     blocks[b].extra_bits = extra;
+    cnt[316] = static_cast<uint32_t>(extra);          // (as k_png_lo_parse leaves them)
+    cnt[317] = static_cast<uint32_t>(extra >> 32);
   }
   std::vector<uint64_t> out;
   for (size_t b = 0; b < bufs.size(); ++b) {
     out.push_back(zamd::LoZlibBytes(blocks.data() + plan.first_block[b], plan.first_block[b + 1] - plan.first_block[b]));
+  }
+  if (arrays) {
+    arrays->HC.swap(HC);
+    arrays->ZC.swap(ZC);
+    arrays->LD.swap(LD);
+    arrays->counts.swap(counts);
   }
   return out;
 }
@@ -97,6 +114,22 @@ int main(int argc, char** argv) {
     for (const uint64_t s : Sizes(bufs, static_cast<unsigned>(atoi(argv[2])), static_cast<unsigned>(atoi(argv[3])))) {
       printf("%llu\n", static_cast<unsigned long long>(s));
     }
+    return 0;
+  }
+  if (argc >= 6 && std::strcmp(argv[1], "arrays") == 0) {
+    std::vector<std::vector<unsigned char>> bufs;
+    for (int i = 5; i < argc; ++i) bufs.push_back(ReadFile(argv[i]));
+    Arrays a;
+    const std::vector<uint64_t> sizes = Sizes(bufs, static_cast<unsigned>(atoi(argv[2])), static_cast<unsigned>(atoi(argv[3])), &a);
+    FILE* fp = fopen(argv[4], "wb");
+    if (!fp) { fprintf(stderr, "cannot write %s\n", argv[4]); return 2; }
+    bool ok = true;
+    for (const std::vector<uint32_t>* v : {&a.HC, &a.ZC, &a.LD, &a.counts}) {   // (the hosts this runs on are little-endian)
+      ok = ok && fwrite(v->data(), sizeof(uint32_t), v->size(), fp) == v->size();
+    }
+    ok = fclose(fp) == 0 && ok;
+    if (!ok) { fprintf(stderr, "cannot write %s\n", argv[4]); return 2; }
+    for (const uint64_t s : sizes) printf("%llu\n", static_cast<unsigned long long>(s));
     return 0;
   }
   if (argc == 3 && std::strcmp(argv[1], "huff") == 0) {
@@ -116,6 +149,6 @@ int main(int argc, char** argv) {
     printf("\n");
     return 0;
   }
-  fprintf(stderr, "usage: png_lodeflate_print size WINDOW TILE FILE... | huff FILE | lengths MAXBITS COUNT...\n");
+  fprintf(stderr, "usage: png_lodeflate_print size WINDOW TILE FILE... | arrays WINDOW TILE OUT FILE... | huff FILE | lengths MAXBITS COUNT...\n");
   return 2;
 }

@@ -3,7 +3,9 @@ length the real LodePNG's zlib encoder gave for every buffer of tests/png_trial_
 window 8192) — one, two, three bytes; the window's edge with copies at 8191, 8192 and 8193; one deflate block against
 two; a copy and a zero run over block ends; eight blocks; the block size's cap; lazy matches taken, beaten and rolled back
 at a block's end; a match of 3 at 4096 and 4097; a match of 258 — eight of them in one call as in eight, other windows
-against the CPU run of the kernels' rules, and the refusals, which leave the output as it was."""
+against the CPU run of the kernels' rules, and the refusals, which leave the output as it was.  Only the size is compared
+here; the per-position arrays and every block's symbol counts at short tile lengths, and windows other than 8192 against
+LodePNG itself, are tests/test_gpu_png_lodeflate_seams.py's."""
 import ctypes
 import os
 import subprocess

@@ -82,3 +82,5 @@ PNG_LIB = os.path.join(REF_DIR, "libzopflipng_amd.so")
 # the reference's zopflipng command line on libzopflipng_amd.so, and LodePNG's own scanline filter behind a C symbol
 PNG_AMD2 = os.path.join(REF_DIR, "zopflipng_amd2")
 PNG_FILTER_REF = os.path.join(REF_DIR, "libpng_filter_ref.so")
+# LodePNG's own LZ77 stage per deflate block and its zlib size behind C symbols (tests/hostlib/png_lodeflate_ref.cc)
+PNG_LODEFLATE_REF = os.path.join(REF_DIR, "libpng_lodeflate_ref.so")

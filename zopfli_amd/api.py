@@ -1255,6 +1255,28 @@ class Context:
                     "zmx_png_deflate_sizes_device")
         return [int(out[i]) for i in range(n)]
 
+    def png_lodeflate_arrays(self, bufs, windowsize=8192, tile_len=0):
+        """zmx_internal_png_lodeflate_arrays (a test hook): png_deflate_sizes_device in tiles of `tile_len` positions
+        (0: the device's own) together with what its kernels left in device memory: (sizes, HC, ZC, LD, counts) — the
+        three per-position arrays over all buffers' positions, one buffer after the other, and the symbol counts as
+        [deflate blocks of all buffers][318], numpy uint32."""
+        import numpy as np
+        ptrs, sizes = _device_ranges(bufs)
+        n = len(ptrs)
+        positions = sum(sizes)
+        nblocks = sum(-(-s // min(262144, max(65536, s // 8 + 8))) for s in sizes)      # lodepng_deflatev's blocks
+        hc, zc, ld = (np.zeros(max(positions, 1), dtype=np.uint32) for _ in range(3))
+        counts = np.zeros((max(nblocks, 1), 318), dtype=np.uint32)
+        out = (ctypes.c_uint64 * max(n, 1))()
+        fn = self.lib.zmx_internal_png_lodeflate_arrays
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint,
+                       ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes), int(windowsize),
+                       int(tile_len), hc.ctypes.data, zc.ctypes.data, ld.ctypes.data, counts.ctypes.data, out),
+                    "zmx_internal_png_lodeflate_arrays")
+        return [int(out[i]) for i in range(n)], hc[:positions], zc[:positions], ld[:positions], counts[:nblocks]
+
     def png_choose_strategy_device(self, image, reduce_color=False, predefined=None):
         """zmx_png_choose_strategy_device: zopflipng's choice of the filter strategy for the image (`image` as
         png_encode_device takes it; `reduce_color`: without --keepcolortype; `predefined`: a type per row for the eighth

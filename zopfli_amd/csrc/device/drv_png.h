@@ -749,10 +749,20 @@ int zmx_png_index_convert_device(zmx_ctx* c, const zmx_png_index_image* image, c
 // ---- LodePNG's zlib size of device buffers (zmx_png_lodeflate.h, host/png_lodeflate_size.h)
 static thread_local double g_png_lo_ms[6] = {0, 0, 0, 0, 0, 0};   // k_png_lo_hash, _links, _ask, _keep, _search, _parse (zmx_internal_png_lodeflate_ms)
 
-// The six kernels over buffers the caller has checked, the counts read, the sizes made.  Drains the context's stream.
+// What a test may take of a call besides the sizes (zmx_internal_png_lodeflate_arrays): host arrays, each null or of
+// [positions] words — `counts` of [blocks][kLoCountWords] —, that receive the device's arrays as the kernels left them.
+struct PngLoArrays {
+  uint32_t* hc = nullptr;
+  uint32_t* zc = nullptr;
+  uint32_t* ld = nullptr;
+  uint32_t* counts = nullptr;
+};
+
+// The six kernels over buffers the caller has checked, in tiles of `tile_len` positions (at most kLoTileLen); the counts
+// read, the sizes made.  Drains the context's stream.
 static int PngLoSizesOnDevice(zmx_ctx* c, PoolScope* tmp, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize,
-                              uint64_t* zlib_bytes) {
-  const zamd::LoPlan plan = zamd::LoMakePlan(n, d_in, insize, zamd::kLoTileLen);
+                              uint32_t tile_len, uint64_t* zlib_bytes, const PngLoArrays& arrays = PngLoArrays()) {
+  const zamd::LoPlan plan = zamd::LoMakePlan(n, d_in, insize, tile_len);
   const size_t ntiles = plan.tiles.size(), nblocks = plan.blocks.size();
   if (ntiles > 0x7fffffffu || nblocks > 0x7fffffffu) return FailMsg("zmx_png_deflate_sizes_device: too many tiles in one call");
   zamd::LoBuf* d_bufs = nullptr;
@@ -773,7 +783,7 @@ static int PngLoSizesOnDevice(zmx_ctx* c, PoolScope* tmp, size_t n, const void* 
   P.window = windowsize;
   P.ntiles = static_cast<u32>(ntiles);
   P.nblocks = static_cast<u32>(nblocks);
-  P.tile_len = zamd::kLoTileLen;
+  P.tile_len = tile_len;
   HIPCHK(hipMemsetAsync(P.tables, 0, ntiles * static_cast<size_t>(zamd::kLoTableLen) * sizeof(u32), c->stream));
   PngLossyTimer timer{c, KernelTiming()};
   const u32 gx = (plan.longest_tile + zamd::kLoThreads - 1) / zamd::kLoThreads;
@@ -804,6 +814,11 @@ static int PngLoSizesOnDevice(zmx_ctx* c, PoolScope* tmp, size_t n, const void* 
   std::vector<u32> counts(nblocks * static_cast<size_t>(zamd::kLoCountWords));
   HIPCHK(hipMemcpyAsync(counts.data(), P.counts, counts.size() * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  const size_t words = static_cast<size_t>(plan.positions);
+  if (arrays.hc) HIPCHK(hipMemcpy(arrays.hc, P.HC, words * sizeof(u32), hipMemcpyDeviceToHost));
+  if (arrays.zc) HIPCHK(hipMemcpy(arrays.zc, P.ZC, words * sizeof(u32), hipMemcpyDeviceToHost));
+  if (arrays.ld) HIPCHK(hipMemcpy(arrays.ld, P.LD, words * sizeof(u32), hipMemcpyDeviceToHost));
+  if (arrays.counts) std::copy(counts.begin(), counts.end(), arrays.counts);
   std::vector<zamd::LoBlockCounts> blocks(nblocks);
   for (size_t b = 0; b < nblocks; ++b) {
     const u32* w = counts.data() + b * zamd::kLoCountWords;
@@ -822,11 +837,10 @@ void zmx_internal_png_lodeflate_ms(double out[6]) {
   for (int k = 0; k < 6; ++k) out[k] = g_png_lo_ms[k];
 }
 
-int zmx_png_deflate_sizes_device(zmx_ctx* c, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize,
-                                 uint64_t* zlib_bytes) {
-  const char* who = "zmx_png_deflate_sizes_device";
+// The checks of a call's arguments, before anything runs; 0, or the refusal.
+static int PngLoCheckCall(const char* who, zmx_ctx* c, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize,
+                          const uint64_t* zlib_bytes) {
   const std::string w(who);
-  for (double& ms : g_png_lo_ms) ms = 0;
   if (!c) return FailMsg(w + ": no context");
   if (n == 0 || !d_in || !insize || !zlib_bytes) return FailMsg(w + ": a null argument or no buffer");
   if (!PngWindowOk(windowsize)) return FailMsg(w + ": the window must be a power of two of at most 32768");
@@ -842,16 +856,48 @@ int zmx_png_deflate_sizes_device(zmx_ctx* c, size_t n, const void* const* d_in, 
     if (const int rc = CheckDevicePointer(who, d_in[i], insize[i], &device)) return rc;
     if (device != c->device) return FailMsg(w + ": memory of another device than the context's");
   }
+  return 0;
+}
+
+// A checked call: the kernels, the stream drained, the sizes handed over when all went well.
+static int PngLoCheckedCall(zmx_ctx* c, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize, uint32_t tile_len,
+                            uint64_t* zlib_bytes, const PngLoArrays& arrays) {
   DEVICE_ENTRY(c->device);
   PoolScope tmp(c);
   std::vector<uint64_t> sizes(n);
-  const int rc = PngLoSizesOnDevice(c, &tmp, n, d_in, insize, windowsize, sizes.data());
+  const int rc = PngLoSizesOnDevice(c, &tmp, n, d_in, insize, windowsize, tile_len, sizes.data(), arrays);
   // (what was queued uses the scratch arrays: drained before `tmp` gives them back, on the failing paths too)
   const hipError_t e = hipStreamSynchronize(c->stream);
   if (rc) return rc;
   HIPCHK(e);
   std::copy(sizes.begin(), sizes.end(), zlib_bytes);
   return 0;
+}
+
+int zmx_png_deflate_sizes_device(zmx_ctx* c, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize,
+                                 uint64_t* zlib_bytes) {
+  for (double& ms : g_png_lo_ms) ms = 0;
+  if (const int rc = PngLoCheckCall("zmx_png_deflate_sizes_device", c, n, d_in, insize, windowsize, zlib_bytes)) return rc;
+  return PngLoCheckedCall(c, n, d_in, insize, windowsize, zamd::kLoTileLen, zlib_bytes, PngLoArrays());
+}
+
+int zmx_internal_png_lodeflate_arrays(zmx_ctx* c, size_t n, const void* const* d_in, const size_t* insize, unsigned windowsize,
+                                      unsigned tile_len, uint32_t* hc, uint32_t* zc, uint32_t* ld, uint32_t* counts, uint64_t* zlib_bytes) {
+  const char* who = "zmx_internal_png_lodeflate_arrays";
+  const std::string w(who);
+  for (double& ms : g_png_lo_ms) ms = 0;
+  if (const int rc = PngLoCheckCall(who, c, n, d_in, insize, windowsize, zlib_bytes)) return rc;
+  if (tile_len == 0) tile_len = zamd::kLoTileLen;
+  if (tile_len > zamd::kLoTileLen) return FailMsg(w + ": a tile of more than " + std::to_string(zamd::kLoTileLen) + " positions");
+  uint64_t ntiles = 0;
+  for (size_t i = 0; i < n; ++i) ntiles += (insize[i] + tile_len - 1) / tile_len;
+  if (ntiles > 1024) return FailMsg(w + ": " + std::to_string(ntiles) + " tiles, more than 1024 (a tile's head table is 263 KB)");
+  PngLoArrays arrays;
+  arrays.hc = hc;
+  arrays.zc = zc;
+  arrays.ld = ld;
+  arrays.counts = counts;
+  return PngLoCheckedCall(c, n, d_in, insize, windowsize, tile_len, zlib_bytes, arrays);
 }
 
 // zmx_png_choose_strategy_device's device part (host/png_encode.cc): the rows of trial k = 0 .. ntrials - 1 of an image

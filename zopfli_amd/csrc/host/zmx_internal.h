@@ -168,6 +168,13 @@ ZMX_INTERNAL_EXPORT void zmx_internal_png_index_ms(double out[2]);
 // The same for the calling thread's last zmx_png_deflate_sizes_device: k_png_lo_hash, k_png_lo_links, k_png_lo_ask,
 // k_png_lo_keep, k_png_lo_search, k_png_lo_parse.  For tools/png_auto.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_png_lodeflate_ms(double out[6]);
+// Test hook (tests/test_gpu_png_lodeflate_seams.py): zmx_png_deflate_sizes_device with the same checks, in tiles of
+// `tile_len` positions (0: the device's own, kLoTileLen; more is refused, and so is a call of more than 1024 tiles), that
+// also hands over what its kernels left in device memory.  hc, zc, ld ([all buffers' positions] words each, the buffers
+// one after the other) and counts ([all buffers' deflate blocks][kLoCountWords]) are host arrays; each may be null.
+ZMX_INTERNAL_EXPORT int zmx_internal_png_lodeflate_arrays(zmx_ctx* ctx, size_t n, const void* const* d_in, const size_t* insize,
+                                                          unsigned windowsize, unsigned tile_len, uint32_t* hc, uint32_t* zc,
+                                                          uint32_t* ld, uint32_t* counts, uint64_t* zlib_bytes);
 // The same for the calling thread's last zmx_checksum_device (or seal): k_checksum_pieces, k_checksum_finish.  For
 // tools/png_device_output.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_checksum_device_ms(double out[2]);
