@@ -84,3 +84,5 @@ PNG_AMD2 = os.path.join(REF_DIR, "zopflipng_amd2")
 PNG_FILTER_REF = os.path.join(REF_DIR, "libpng_filter_ref.so")
 # LodePNG's own LZ77 stage per deflate block and its zlib size behind C symbols (tests/hostlib/png_lodeflate_ref.cc)
 PNG_LODEFLATE_REF = os.path.join(REF_DIR, "libpng_lodeflate_ref.so")
+# LodePNG's fixed-tree deflate of every row under every filter type behind C symbols (tests/hostlib/png_brute_ref.cc)
+PNG_BRUTE_REF = os.path.join(REF_DIR, "libpng_brute_ref.so")

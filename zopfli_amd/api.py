@@ -1277,6 +1277,27 @@ class Context:
                     "zmx_internal_png_lodeflate_arrays")
         return [int(out[i]) for i in range(n)], hc[:positions], zc[:positions], ld[:positions], counts[:nblocks]
 
+    def png_brute_sizes(self, image, linebytes, height, bytewidth, windowsize=32768, force_scratch=False, max_workgroups=0):
+        """zmx_internal_png_brute_sizes (a test hook): zmx_png_filter_types_brute of the host image `image` (bytes or a
+        uint8 array: `height` rows of `linebytes` bytes) together with what k_png_brute computed: (sizes, bits, types) —
+        sizes and bits as numpy uint64 [height][5], the zlib bytes and the fixed-code bit count of every row under
+        every filter type; types numpy uint8 [height].  `force_scratch` keeps the kernel's per-position arrays out of
+        the LDS whatever the row length; `max_workgroups` caps the grid (0: the driver's own choice)."""
+        import numpy as np
+        raw = np.ascontiguousarray(np.frombuffer(image, dtype=np.uint8) if isinstance(image, (bytes, bytearray)) else image, dtype=np.uint8)
+        if raw.size != linebytes * height:
+            raise ValueError(f"{raw.size} bytes for {height} rows of {linebytes}")
+        sizes = np.zeros((max(height, 1), 5), dtype=np.uint64)
+        bits = np.zeros((max(height, 1), 5), dtype=np.uint64)
+        types = np.full(max(height, 1), 255, dtype=np.uint8)
+        fn = self.lib.zmx_internal_png_brute_sizes
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint, ctypes.c_int,
+                       ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, raw.ctypes.data, linebytes, height, bytewidth, int(windowsize), 1 if force_scratch else 0,
+                       int(max_workgroups), sizes.ctypes.data, bits.ctypes.data, types.ctypes.data), "zmx_internal_png_brute_sizes")
+        return sizes[:height], bits[:height], types[:height]
+
     def png_choose_strategy_device(self, image, reduce_color=False, predefined=None):
         """zmx_png_choose_strategy_device: zopflipng's choice of the filter strategy for the image (`image` as
         png_encode_device takes it; `reduce_color`: without --keepcolortype; `predefined`: a type per row for the eighth

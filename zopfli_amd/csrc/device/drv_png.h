@@ -32,20 +32,25 @@ static bool PngWindowOk(unsigned windowsize) {   // LodePNG's errors 60 / 90
   return windowsize != 0 && windowsize <= 32768u && (windowsize & (windowsize - 1u)) == 0;
 }
 
+static_assert(zamd::kPngBruteHeadBytes == PNGB_HEAD_BYTES && zamd::kPngBruteLdsMax == PNGB_LDS_MAX, "host/png_brute_launch.h restates zmx_png_brute.h");
+
+// What a test may take of a search besides the types (zmx_internal_png_brute_sizes): device arrays of `tmp`, [5 * height]
+// each, that live as long as `tmp` does.
+struct PngBruteArrays {
+  u64* d_sizes = nullptr;
+  u64* d_bits = nullptr;
+};
+
 // k_png_brute + k_png_brute_pick on an image in memory of the context's device: the types into d_types[height], queued on
-// the context's stream; the scratch arrays are `tmp`'s.
+// the context's stream; the scratch arrays are `tmp`'s.  The launch is host/png_brute_launch.h's; `knobs` are a test's
+// (the default everywhere else), and so is `arrays`, which makes the kernel keep its bit counts.
 static int PngBruteTypes(zmx_ctx* c, PoolScope* tmp, const u8* d_img, size_t linebytes, size_t height, size_t bytewidth,
-                         unsigned windowsize, u8* d_types) {
+                         unsigned windowsize, u8* d_types, const zamd::PngBruteKnobs& knobs, PngBruteArrays* arrays = nullptr) {
   const u32 n = static_cast<u32>(linebytes), jobs = static_cast<u32>(5 * height);
-  // the per-position arrays in the dynamic LDS when they fit, else in the scratch beside the head table and the results
-  const u64 row_bytes = pngb_row_bytes(n);
-  const bool in_lds = row_bytes <= PNGB_LDS_MAX;
-  const u64 stride = (PNGB_HEAD_BYTES + 4ull * n + (in_lds ? 0 : row_bytes) + 255u) & ~255ull;
-  // two 1024-lane workgroups fill a CU's 32 waves; the LDS may allow fewer
-  const u64 per_cu = in_lds ? std::max<u64>(1, std::min<u64>(2, (160u * 1024u) / (row_bytes + 12u * 1024u))) : 1;
-  const u64 budget = 1ull << 30;
-  const u32 grid = static_cast<u32>(std::max<u64>(1, std::min<u64>({static_cast<u64>(jobs), 256 * per_cu, budget / stride})));
-  if (in_lds && row_bytes > 64u * 1024u) {
+  const zamd::PngBruteLaunch L = zamd::PngBruteMakeLaunch(n, jobs, knobs);
+  const u64 stride = L.stride;
+  const u32 grid = L.grid;
+  if (L.raise_lds_limit) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_png_brute), hipFuncAttributeMaxDynamicSharedMemorySize,
                                static_cast<int>(PNGB_LDS_MAX)));
   }
@@ -62,9 +67,14 @@ static int PngBruteTypes(zmx_ctx* c, PoolScope* tmp, const u8* d_img, size_t lin
   pp.jobs = jobs;
   pp.scratch = d_scratch;
   pp.scratch_stride = stride;
-  pp.in_lds = in_lds ? 1u : 0u;
+  pp.in_lds = L.in_lds ? 1u : 0u;
   pp.sizes = d_sizes;
-  hipLaunchKernelGGL(k_png_brute, dim3(grid), dim3(PNGB_THREADS), in_lds ? static_cast<unsigned>(row_bytes) : 0u, c->stream, pp);
+  if (arrays) {
+    HIPCHK(tmp->AllocT(&pp.bits, static_cast<size_t>(jobs), "d_png_brute_bits"));
+    arrays->d_sizes = d_sizes;
+    arrays->d_bits = pp.bits;
+  }
+  hipLaunchKernelGGL(k_png_brute, dim3(grid), dim3(PNGB_THREADS), L.lds_bytes, c->stream, pp);
   KCHK(c, "k_png_brute");
   hipLaunchKernelGGL(k_png_brute_pick, dim3(static_cast<unsigned>((height + 255) / 256)), dim3(256), 0, c->stream,
                      static_cast<const u64*>(d_sizes), static_cast<u32>(height), d_types);
@@ -87,7 +97,7 @@ static int PngTypesOnDevice(zmx_ctx* c, PoolScope* tmp, const char* who, const u
   if (strategy != ZMX_PNG_FILTER_BRUTE) return FailMsg(w + ": unknown strategy " + std::to_string(strategy));
   if (!PngWindowOk(windowsize)) return FailMsg(w + ": the window must be a power of two of at most 32768");
   if (!PngGeometryOk(linebytes, height, 0x7fffffffu / 5u, bytewidth)) return FailMsg(w + ": bad geometry");
-  return PngBruteTypes(c, tmp, d_img, linebytes, height, bytewidth, windowsize, d_types);
+  return PngBruteTypes(c, tmp, d_img, linebytes, height, bytewidth, windowsize, d_types, zamd::PngBruteKnobs());
 }
 
 static bool PngStrategyKnown(int strategy) { return strategy >= ZMX_PNG_FILTER_ZERO && strategy <= ZMX_PNG_FILTER_BRUTE; }
@@ -522,9 +532,42 @@ int zmx_png_filter_types_brute(zmx_ctx* c, const unsigned char* image, size_t li
   u8* d_types = nullptr;
   HIPCHK(tmp.Upload(&d_img, image, linebytes * height, "d_png_image"));
   HIPCHK(tmp.AllocT(&d_types, height, "d_png_types"));
-  if (const int rc = PngBruteTypes(c, &tmp, d_img, linebytes, height, bytewidth, windowsize, d_types)) return rc;
+  if (const int rc = PngBruteTypes(c, &tmp, d_img, linebytes, height, bytewidth, windowsize, d_types, zamd::PngBruteKnobs())) return rc;
   HIPCHK(hipMemcpyAsync(types, d_types, height, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// Test hook (tests/test_gpu_png_brute_sizes.py): zmx_png_filter_types_brute with the same checks that also hands over the
+// five sizes and bit counts of every row as k_png_brute wrote them, and runs the launch a test asks for.
+int zmx_internal_png_brute_sizes(zmx_ctx* c, const unsigned char* image, size_t linebytes, size_t height, size_t bytewidth,
+                                 unsigned windowsize, int force_scratch, unsigned max_workgroups, uint64_t* sizes, uint64_t* bits,
+                                 unsigned char* types) {
+  const char* who = "zmx_internal_png_brute_sizes";
+  if (!c) return FailMsg(std::string(who) + ": no context");
+  if (!PngWindowOk(windowsize)) return FailMsg(std::string(who) + ": the window must be a power of two of at most 32768");
+  if (force_scratch != 0 && force_scratch != 1) return FailMsg(std::string(who) + ": force_scratch is 0 or 1");
+  if (height == 0) return 0;
+  if (!image || !sizes || !bits || !types) return FailMsg(std::string(who) + ": a null argument");
+  if (!PngGeometryOk(linebytes, height, 0x7fffffffu / 5u, bytewidth)) return FailMsg(std::string(who) + ": bad geometry");
+  DEVICE_ENTRY(c->device);
+  PoolScope tmp(c);
+  u8* d_img = nullptr;
+  u8* d_types = nullptr;
+  HIPCHK(tmp.Upload(&d_img, image, linebytes * height, "d_png_image"));
+  HIPCHK(tmp.AllocT(&d_types, height, "d_png_types"));
+  zamd::PngBruteKnobs knobs;
+  knobs.force_scratch = force_scratch;
+  knobs.max_workgroups = max_workgroups;
+  PngBruteArrays arrays;
+  const int rc = PngBruteTypes(c, &tmp, d_img, linebytes, height, bytewidth, windowsize, d_types, knobs, &arrays);
+  // (what was queued uses the scratch arrays: drained before `tmp` gives them back, on the failing paths too)
+  const hipError_t e = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  HIPCHK(e);
+  HIPCHK(hipMemcpy(sizes, arrays.d_sizes, 5 * height * sizeof(u64), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(bits, arrays.d_bits, 5 * height * sizeof(u64), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(types, d_types, height, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -60,6 +60,7 @@
 #include "../host/entry_checks.h"
 #include "../host/png_color_choose.h"
 #include "../host/png_index.h"
+#include "../host/png_brute_launch.h"
 #include "../host/png_lodeflate_size.h"
 #include "../host/png_source.h"
 #include "../host/symbol_check.h"

@@ -24,7 +24,7 @@
 //   5. one lane replays the lazy parse (:1691-1736) over the per-position (length, offset) and sums the fixed-code bits:
 //      size = 2 + ceil((3 + bits + 7) / 8) + 4.
 // The per-position arrays (F, then H << 16 | C and Z << 16 | CZ packed: one load per chain step gives the hash to check
-// AND the next link) live in the dynamic LDS when the row fits (rows up to ~16.8 KB: 4096 RGBA pixels), else in the
+// AND the next link) live in the dynamic LDS when the row fits (rows of up to 16839 bytes: 4096 RGBA pixels fit), else in the
 // workgroup's slice of the global scratch; the search results (length | offset << 16) go to the scratch and are read
 // back into the LDS (over the packed arrays, dead by then) for the serial scan.  The grid is persistent so that the
 // scratch is bounded.  k_png_brute_pick then takes the first smallest of the five sizes per row.
@@ -43,6 +43,7 @@ struct PngBruteParams {
   u64 scratch_stride;    // bytes per workgroup
   u32 in_lds;            // the per-position arrays live in the dynamic LDS
   u64* sizes;            // [jobs] the zlib size of the row under each type
+  u64* bits = nullptr;   // [jobs] or null: step 5's bit count before it is rounded to bytes (zmx_internal_png_brute_sizes)
 };
 
 // bytes of the per-position arrays of a row of n bytes: F (u8, padded to 4), HC, ZC (u32)
@@ -246,6 +247,7 @@ __global__ __launch_bounds__(PNGB_THREADS) void k_png_brute(PngBruteParams P) {
         }
       }
       P.sizes[job] = 6u + (bits + 7u) / 8u;
+      if (P.bits) P.bits[job] = bits;
     }
     __syncthreads();
   }

@@ -4,7 +4,7 @@
 // layer defines them and includes this header, as every caller does and as the host test library's stand-in for the
 // device layer does (tests/hostlib/zmx_oracle_backend.cc), so a parameter list that changes on one side only does not
 // compile.  Device to host: the statistics, which the host layer owns.
-// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the six
+// The library is built with -fvisibility=hidden, so all this stays inside it; ZMX_INTERNAL_EXPORT marks the
 // functions that tests and tools reach from outside (here and nowhere else).
 #pragma once
 #include <cstddef>
@@ -175,6 +175,14 @@ ZMX_INTERNAL_EXPORT void zmx_internal_png_lodeflate_ms(double out[6]);
 ZMX_INTERNAL_EXPORT int zmx_internal_png_lodeflate_arrays(zmx_ctx* ctx, size_t n, const void* const* d_in, const size_t* insize,
                                                           unsigned windowsize, unsigned tile_len, uint32_t* hc, uint32_t* zc,
                                                           uint32_t* ld, uint32_t* counts, uint64_t* zlib_bytes);
+// Test hook (tests/test_gpu_png_brute_sizes.py): zmx_png_filter_types_brute of a host image with the same checks, which
+// also hands over what k_png_brute computed for every job = row * 5 + type: sizes[5 * height], the zlib bytes it wrote;
+// bits[5 * height], its fixed-code bit count before rounding (3 + data + 7); types[height] from k_png_brute_pick.  Two
+// knobs that no other caller has (host/png_brute_launch.h): force_scratch (0 / 1) puts the per-position arrays into the
+// global scratch whatever the row length; max_workgroups caps the grid (0: the driver's own choice).
+ZMX_INTERNAL_EXPORT int zmx_internal_png_brute_sizes(zmx_ctx* ctx, const unsigned char* image, size_t linebytes, size_t height,
+                                                     size_t bytewidth, unsigned windowsize, int force_scratch, unsigned max_workgroups,
+                                                     uint64_t* sizes, uint64_t* bits, unsigned char* types);
 // The same for the calling thread's last zmx_checksum_device (or seal): k_checksum_pieces, k_checksum_finish.  For
 // tools/png_device_output.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_checksum_device_ms(double out[2]);
