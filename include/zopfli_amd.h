@@ -1148,6 +1148,63 @@ int zmx_set_match_order(int on);
  * [7] block positions of all squeeze runs. */
 int zmx_last_seg_stats(double* out8);
 
+/* ---- Inflate on the device: raw deflate, zlib and gzip streams in device memory decoded into device memory.
+ * What the *_to_device entries leave in HBM, read back where it lies; any conforming stream, not only this library's.
+ * k_inflate (device/zmx_inflate.h): one wavefront a stream, a batch of n streams one launch.  A stream is valid exactly
+ * where inflate() of zlib 1.2.11 accepts it.  Bytes behind the trailer are no error and a second gzip member is not
+ * followed: `consumed` says where it begins.  Preset dictionaries (zlib's FDICT) are not taken.
+ * How a stream ended: */
+#define ZMX_INFLATE_OK 0
+#define ZMX_INFLATE_HEADER 1            /* a zlib or gzip header that is none */
+#define ZMX_INFLATE_DICT 2              /* zlib's FDICT is set */
+#define ZMX_INFLATE_BLOCK_TYPE 3        /* block type 3 */
+#define ZMX_INFLATE_STORED_LEN 4        /* a stored block's LEN is not ~NLEN */
+#define ZMX_INFLATE_TOO_MANY_SYMBOLS 5  /* HLIT > 286 or HDIST > 30 */
+#define ZMX_INFLATE_REPEAT 6            /* a repeat with no previous length, or one that runs past HLIT + HDIST */
+#define ZMX_INFLATE_OVERSUBSCRIBED 7    /* an over-subscribed set of code lengths */
+#define ZMX_INFLATE_INCOMPLETE 8        /* an incomplete set (but a literal/length or distance set of one one-bit code) */
+#define ZMX_INFLATE_NO_END_CODE 9       /* no code for symbol 256 */
+#define ZMX_INFLATE_BAD_CODE 10         /* a bit pattern no code owns */
+#define ZMX_INFLATE_BAD_SYMBOL 11       /* literal/length symbol 286 or 287, distance symbol 30 or 31 */
+#define ZMX_INFLATE_DISTANCE 12         /* a distance behind the first byte of the output */
+#define ZMX_INFLATE_TRUNCATED 13        /* the input ends before the final block or the trailer does */
+#define ZMX_INFLATE_CAPACITY 14         /* the output takes more than `capacity`: outsize says how much */
+#define ZMX_INFLATE_CHECKSUM 15         /* the output's CRC-32 / Adler-32 is not the trailer's (the pooled entries) */
+#define ZMX_INFLATE_SIZE 16             /* gzip's ISIZE is not the output's size mod 2^32 (the pooled entries) */
+/* zmx_last_error_class() after a stream that is no valid stream (every status above but OK and CAPACITY): the data is at
+ * fault, not the request or the device. */
+enum { ZMX_ERR_DATA = 4 };
+
+typedef struct {
+  uint64_t outsize;       /* bytes the stream decodes to (up to where it failed) */
+  uint64_t consumed;      /* bytes of input up to and including the trailer (up to the failing bit) */
+  uint32_t status;        /* a ZMX_INFLATE_* */
+  uint32_t block;         /* the index of the deflate block it stopped in */
+  uint32_t stored_check;  /* the trailer's CRC-32 (gzip) or Adler-32 (zlib) */
+  uint32_t stored_isize;  /* gzip's ISIZE */
+} zmx_inflate_result;
+
+/* The step, on a context the caller holds: stream i is d_in[i][0, insize[i]), its output goes to d_out[i][0, capacity[i]),
+ * all plain memory of the context's device.  A null d_out[i] (or a null d_out) is the size-only mode: the same walk,
+ * nothing stored.  Output beyond capacity[i] is not stored; the stream is walked to its end all the same, so that outsize
+ * is what it takes (ZMX_INFLATE_CAPACITY).  No checksum is compared: the results carry the trailers.  Refused
+ * (ZMX_ERR_REFUSED) before anything is launched: an unknown format, a pointer that is not device memory of the context's
+ * device, a range that leaves its allocation, a destination that shares a byte with an input or with another destination
+ * (the message names the index).  Returns 0 when every stream is ZMX_INFLATE_OK (n = 0: at once); -1 with every result
+ * filled in when one is not: zmx_last_error() names the first failing index and its status (for CAPACITY also outsize),
+ * zmx_last_error_class() is ZMX_ERR_REFUSED for CAPACITY, else ZMX_ERR_DATA. */
+int zmx_inflate_device_ctx(zmx_ctx* ctx, ZopfliFormat format, size_t n, const void* const* d_in, const size_t* insize,
+                           void* const* d_out, const size_t* capacity, zmx_inflate_result* results);
+/* The same on a context from the library's pool, with the checksums verified: after k_inflate the output of every gzip or
+ * zlib stream that ended OK with its output stored goes through zmx_checksum_device's two kernels (one launch pair for the
+ * batch) and the values are compared with the trailers — ZMX_INFLATE_CHECKSUM — and gzip's ISIZE with outsize mod 2^32 —
+ * ZMX_INFLATE_SIZE.  32 n bytes come down and then 4 n; no byte of a stream or of its output visits the host.  All
+ * ranges must lie on one of the library's devices. */
+int zmx_inflate_device_batch(ZopfliFormat format, size_t n, const void* const* d_in, const size_t* insize, void* const* d_out,
+                             const size_t* capacity, zmx_inflate_result* results);
+/* ... of one stream; *outsize as zmx_inflate_result.outsize. */
+int zmx_inflate_device(ZopfliFormat format, const void* d_in, size_t insize, void* d_out, size_t capacity, size_t* outsize);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

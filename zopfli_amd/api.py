@@ -367,6 +367,125 @@ def compress_bound(nbytes, fmt=FORMAT_GZIP, lib=None):
     return int(fn(fmt, nbytes))
 
 
+INFLATE_STATUS = ["OK", "HEADER", "DICT", "BLOCK_TYPE", "STORED_LEN", "TOO_MANY_SYMBOLS", "REPEAT", "OVERSUBSCRIBED", "INCOMPLETE",
+                  "NO_END_CODE", "BAD_CODE", "BAD_SYMBOL", "DISTANCE", "TRUNCATED", "CAPACITY", "CHECKSUM", "SIZE"]   # ZMX_INFLATE_*
+INFLATE_OK, INFLATE_CAPACITY = 0, 14
+ERR_DATA = 4   # ZMX_ERR_DATA
+
+
+class InflateResult(ctypes.Structure):
+    """zmx_inflate_result."""
+    _fields_ = [("outsize", ctypes.c_uint64), ("consumed", ctypes.c_uint64), ("status", ctypes.c_uint32), ("block", ctypes.c_uint32),
+                ("stored_check", ctypes.c_uint32), ("stored_isize", ctypes.c_uint32)]
+
+    def astuple(self):
+        return (int(self.outsize), int(self.consumed), int(self.status), int(self.block), int(self.stored_check), int(self.stored_isize))
+
+
+class InflateError(RuntimeError):
+    """inflate_device_batch, inflate_device, inflate_size_device: stream `index` is no valid stream — `status` (a
+    ZMX_INFLATE_* number; INFLATE_STATUS names it) in deflate block `block`; `needed`: the bytes it decoded to up to
+    there.  `results`: the InflateResult of every stream of the call."""
+
+    def __init__(self, index, status, block, needed, message="", results=None):
+        super().__init__(message or f"stream {index}: ZMX_INFLATE_{INFLATE_STATUS[status] if status < len(INFLATE_STATUS) else status}")
+        self.index, self.status, self.block, self.needed = index, status, block, needed
+        self.results = results or []
+
+
+def _inflate_format(fmt):
+    if isinstance(fmt, str):
+        return {"gzip": FORMAT_GZIP, "zlib": FORMAT_ZLIB, "deflate": FORMAT_DEFLATE}[fmt]
+    return int(fmt)
+
+
+def _inflate_call(lib, fn, who, ctx_args, fmt, streams, outs):
+    """One inflate entry: `outs` None for the size-only mode, else a list of tensors, (pointer, capacity) pairs or None.
+    Returns (rc, results, capacities)."""
+    ptrs, sizes = _device_ranges(streams)
+    n = len(ptrs)
+    if outs is not None and len(outs) != n:
+        raise ValueError(f"{n} streams, but {len(outs)} destinations")
+    out_ptrs, capacities = [None] * n, [0] * n
+    if outs is not None:
+        given = [i for i in range(n) if outs[i] is not None]
+        got_ptrs, got_caps = _device_ranges([outs[i] for i in given])
+        for i, p, c in zip(given, got_ptrs, got_caps):
+            # (a destination of no bytes still asks for the stored mode: any non-null pointer goes with a size of 0)
+            out_ptrs[i], capacities[i] = p or 1, c
+    results = (InflateResult * max(n, 1))()
+    P, sz, vp = ctypes.POINTER, ctypes.c_size_t, ctypes.c_void_p
+    fn.argtypes = [vp] * len(ctx_args) + [ctypes.c_int, sz, P(vp), P(sz), P(vp), P(sz), P(InflateResult)]
+    fn.restype = ctypes.c_int
+    rc = fn(*ctx_args, _inflate_format(fmt), n, (vp * max(n, 1))(*ptrs), (sz * max(n, 1))(*sizes),
+            (vp * max(n, 1))(*out_ptrs) if outs is not None else None, (sz * max(n, 1))(*capacities), results)
+    found = [results[i] for i in range(n)]
+    if rc != 0 and all(r.status == INFLATE_OK for r in found):
+        raise RuntimeError(who + ": " + (lib.zmx_last_error() or b"").decode())
+    return rc, found, capacities
+
+
+def _inflate_raise(lib, who, results, single):
+    """The error of a failed pooled inflate call: CapacityError (`needed`: the size, or the list of all streams' sizes)
+    where the first failing stream only lacks room, else InflateError."""
+    message = who + ": " + (lib.zmx_last_error() or b"").decode()
+    index = next(i for i, r in enumerate(results) if r.status != INFLATE_OK)
+    r = results[index]
+    if r.status == INFLATE_CAPACITY:
+        raise CapacityError(message, int(r.outsize) if single else [int(x.outsize) for x in results])
+    raise InflateError(index, int(r.status), int(r.block), int(r.outsize), message, results)
+
+
+def inflate_size_device(streams, format="gzip", lib=None):
+    """zmx_inflate_device_batch in its size-only mode: the bytes every stream decodes to, nothing stored (and so no checksum
+    compared).  `streams`: uint8 tensors or (integer device pointer, nbytes) pairs.  Raises InflateError."""
+    lib = lib or library()
+    rc, results, _ = _inflate_call(lib, lib.zmx_inflate_device_batch, "zmx_inflate_device_batch", [], format, streams, None)
+    if rc != 0:
+        _inflate_raise(lib, "zmx_inflate_device_batch", results, False)
+    return [int(r.outsize) for r in results]
+
+
+def inflate_device_batch(streams, format="gzip", outs=None, lib=None):
+    """zmx_inflate_device_batch: every deflate / zlib / gzip stream of `streams` (uint8 tensors or (integer device pointer,
+    nbytes) pairs, all on one device) decoded into device memory in one launch, checksums verified on the device.  With
+    `outs` (as many contiguous tensors or (pointer, capacity) pairs) stream i goes to outs[i]; without, a size-only call
+    comes first and the outputs are allocated.  Returns the outputs as uint8 tensors of exactly the decoded sizes (views of
+    `outs` where they are tensors; (pointer, size) pairs where they are pairs).  Raises InflateError for the first stream
+    that is no valid stream (all results in `.results`), CapacityError (`needed`: the list of sizes) where one does not fit,
+    RuntimeError with the library's message for a refused pointer or a device failure."""
+    lib = lib or library()
+    n = len(streams)
+    if outs is None:
+        import torch
+        sizes = inflate_size_device(streams, format, lib)
+        devices = [s.device for s in streams if not isinstance(s, (tuple, list))]
+        outs = [torch.empty(size, dtype=torch.uint8, device=devices[0] if devices else "cuda") for size in sizes]
+    rc, results, _ = _inflate_call(lib, lib.zmx_inflate_device_batch, "zmx_inflate_device_batch", [], format, streams, outs)
+    if rc != 0:
+        _inflate_raise(lib, "zmx_inflate_device_batch", results, False)
+    made = []
+    for i in range(n):
+        size = int(results[i].outsize)
+        made.append((int(outs[i][0]), size) if isinstance(outs[i], (tuple, list)) else outs[i].view(-1)[:size])
+    return made
+
+
+def inflate_device(stream, format="gzip", out=None, size=None, lib=None):
+    """zmx_inflate_device_batch of one stream: a uint8 tensor or an (integer device pointer, nbytes) pair.  `out`: a tensor
+    or (pointer, capacity) pair to decode into; without one the output is allocated — `size` bytes where the caller knows
+    the size, else after a size-only call.  Returns a uint8 tensor of exactly the decoded size.  Raises as
+    inflate_device_batch does; CapacityError's `needed` is the size."""
+    lib = lib or library()
+    if out is None and size is not None:
+        import torch
+        out = torch.empty(int(size), dtype=torch.uint8, device="cuda" if isinstance(stream, (tuple, list)) else stream.device)
+    try:
+        return inflate_device_batch([stream], format, None if out is None else [out], lib)[0]
+    except CapacityError as e:
+        raise CapacityError(str(e), e.needed[0]) from None
+
+
 class PngImage(ctypes.Structure):
     """zmx_png_image"""
     _fields_ = [("d_pixels", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
@@ -1516,6 +1635,13 @@ class Context:
         self._check(fn(self.handle, kind, n, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes), v),
                     "zmx_checksum_device")
         return [int(v[i]) for i in range(n)]
+
+    def inflate_device(self, streams, format="gzip", outs=None):
+        """zmx_inflate_device_ctx: the step on this context — k_inflate over `streams` (uint8 tensors or (integer device
+        pointer, nbytes) pairs in memory of the context's device) into `outs` (tensors, (pointer, capacity) pairs or None
+        entries; None: the size-only mode).  No checksum is compared.  Returns the list of InflateResult, whatever the
+        streams' statuses; raises RuntimeError where the call itself is refused or the device fails."""
+        return _inflate_call(self.lib, self.lib.zmx_inflate_device_ctx, "zmx_inflate_device_ctx", [self.handle], format, streams, outs)[1]
 
     def build_tables(self, blocks, parent=None, matches_only=False):
         """zmx_tables_build, zmx_tables_build_matches (no DP rows: for the greedy pass and as a parent), or

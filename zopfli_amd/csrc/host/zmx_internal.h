@@ -45,6 +45,7 @@ struct zmx_stats {
   double seg[ZMX_SEG_N];     // by zmx_seg_stat, the host's reading of the last slot
 };
 namespace zamd {
+struct InflateJob;          // (device/zmx_inflate.h)
 zmx_stats& ThreadStats();   // the calling thread's (thread-local: no lock)
 // The positions the call in progress on this thread has on its device in all, 0 = no more than the table set at hand:
 // set around a dealt call's shard (api.cc: RunShard), read where a table set picks its task length (drv_build.h: SegL).
@@ -109,6 +110,12 @@ int zmx_internal_device_pointers_one_device(const char* who, size_t n, const voi
 // bytes at d_seal[i], most significant first, instead of the host: the IDAT's CRC-32 of a PNG left in device memory
 // (device_output.cc, batch.cc).  Two launches for all n, nothing comes down.  0, or -1 with the error set.
 int zmx_internal_checksum_seal(zmx_ctx* ctx, int kind, size_t n, const void* const* d_ptr, const size_t* nbytes, unsigned char* const* d_seal);
+
+// ---- inflate on the device (inflate.cc)
+// k_inflate over n <= zamd::kInflateRoundJobs jobs (device/zmx_inflate.h, in the order they are to start) whose ranges the
+// caller has checked: memory of the context's device.  results[jobs[k].index] is job k's.  One launch; 32 n bytes come
+// down.  0, or -1 with the error set (a device failure: a stream's status is no error of the run).
+int zmx_internal_inflate_run(zmx_ctx* ctx, int format, size_t n, const zamd::InflateJob* jobs, zmx_inflate_result* results);
 
 // ---- a PNG from an image in device memory (png_encode.cc)
 // The filter types of `strategy` (a ZMX_PNG_FILTER_*; _BRUTE with window `windowsize`; _PREDEFINED: the `height` host
@@ -186,6 +193,8 @@ ZMX_INTERNAL_EXPORT int zmx_internal_png_brute_sizes(zmx_ctx* ctx, const unsigne
 // The same for the calling thread's last zmx_checksum_device (or seal): k_checksum_pieces, k_checksum_finish.  For
 // tools/png_device_output.py.
 ZMX_INTERNAL_EXPORT void zmx_internal_checksum_device_ms(double out[2]);
+// The same for the calling thread's last k_inflate launch (an inflate call's last round).  For tools/inflate_device.py.
+ZMX_INTERNAL_EXPORT double zmx_internal_inflate_ms(void);
 // The same for the calling thread's last zmx_png_pack_device: k_png_pack.  For tools/png_source.py.
 ZMX_INTERNAL_EXPORT double zmx_internal_png_pack_ms(void);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
