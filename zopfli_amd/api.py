@@ -192,6 +192,24 @@ def _device_range(src, nbytes, sync=True):
     return src.data_ptr(), size
 
 
+def _pair_range(x):
+    """(pointer, bytes) of a contiguous tensor or of an (integer device pointer, nbytes) pair."""
+    return _device_range(int(x[0]), x[1]) if isinstance(x, (tuple, list)) else _device_range(x, None)
+
+
+def _sync_torch(objects):
+    """The current stream of every distinct torch device among the torch tensors in `objects`, synchronised once; anything
+    else in there — None, an integer pointer, a tuple — is passed over."""
+    devices = {}
+    for t in objects:
+        if type(t).__module__.split(".")[0] == "torch":
+            devices[str(t.device)] = t.device
+    if devices:
+        import torch
+        for device in devices.values():
+            torch.cuda.current_stream(device).synchronize()
+
+
 def compress_device(src, nbytes=None, fmt=FORMAT_GZIP, options=None, lib=None):
     """zmx_compress_device: ZopfliCompress of bytes in device memory — `src` is an integer device pointer with `nbytes`,
     or an object with data_ptr(), numel(), element_size() and is_contiguous() (a torch tensor, whose current stream is
@@ -272,8 +290,8 @@ def compress_device_out(src, dst, fmt=FORMAT_GZIP, options=None, lib=None):
     fit, RuntimeError with the library's message when the library refuses a pointer or fails."""
     lib = lib or library()
     options = options or ZopfliOptions()
-    ptr, size = _device_range(int(src[0]), src[1]) if isinstance(src, (tuple, list)) else _device_range(src, None)
-    out, capacity = _device_range(int(dst[0]), dst[1]) if isinstance(dst, (tuple, list)) else _device_range(dst, None)
+    ptr, size = _pair_range(src)
+    out, capacity = _pair_range(dst)
     outsize = ctypes.c_size_t(0)
     # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
     fn = lib.zmx_compress_device_to_device
@@ -333,7 +351,7 @@ def compress_device_batch_packed(srcs, arena, align=1, fmt=FORMAT_GZIP, options=
     lib = lib or library()
     options = options or ZopfliOptions()
     ptrs, sizes = _device_ranges(srcs)
-    out, capacity = _device_range(int(arena[0]), arena[1]) if isinstance(arena, (tuple, list)) else _device_range(arena, None)
+    out, capacity = _pair_range(arena)
     n = len(ptrs)
     offsets = (ctypes.c_size_t * max(n, 1))()
     outsizes = (ctypes.c_size_t * max(n, 1))()
@@ -510,15 +528,86 @@ def _png_lossy(lossy_transparent, lossy_8bit):
     return (PNG_LOSSY_TRANSPARENT if lossy_transparent else 0) | (PNG_LOSSY_8BIT if lossy_8bit else 0)
 
 
-def _png_entry(lib, name, lossy, batch):
-    """(function, the arguments behind the strategy or the types) of a PNG entry: the _lossy symbol with its flags where
-    flags are set, else the plain one — a library from before the flags still loads and serves lossy = 0."""
-    fn = getattr(lib, name + "_lossy" if lossy else name)
-    head = ([ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_int] if batch else
-            [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p])
-    fn.argtypes = head + ([ctypes.c_uint] if lossy else []) + [ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
+_size_p = ctypes.POINTER(ctypes.c_size_t)
+_PNG_TO_HOST = [ctypes.POINTER(_u8p), _size_p]                                     # out, outsize
+_PNG_TO_DEVICE = [ctypes.c_void_p, ctypes.c_size_t, _size_p]                       # d_out, capacity, outsize
+_PNG_PACKED = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, _size_p, _size_p]   # d_arena, capacity, align, outoffset, outsize
+
+
+def _png_entry(lib, name, struct, lossy, batch, tail, suffixed=False):
+    """(function, the arguments between the strategy or the types and `tail`) of a PNG entry on images of type `struct`:
+    its flags.  `suffixed`: the entry has a plain symbol without flags and a _lossy one with them; the _lossy symbol is
+    bound only where flags are set — a library from before the flags still loads and serves lossy = 0.
+    (bound here, at call time, not in bind(): a library without the entry point — the CPU test library — still loads)"""
+    takes_flags = bool(lossy) or not suffixed
+    fn = getattr(lib, name + "_lossy" if suffixed and lossy else name)
+    head = ([ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(struct), ctypes.c_int] if batch else
+            [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(struct), ctypes.c_int, ctypes.c_char_p])
+    fn.argtypes = head + ([ctypes.c_uint] if takes_flags else []) + tail
     fn.restype = ctypes.c_int
-    return fn, ((lossy,) if lossy else ())
+    return fn, ((lossy,) if takes_flags else ())
+
+
+# The four shapes of a PNG entry.  `name`: the symbol (without _lossy); `struct`: PngImage, PngIndexImage or
+# PngSourceStruct; `im` / `ims`: one such struct, or a list of them.
+def _png_single(name, struct, im, strategy, options, types, lib, lossy, suffixed=False):
+    """one image -> the file's bytes"""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    out, outsize = _u8p(), ctypes.c_size_t(0)
+    fn, flags = _png_entry(lib, name, struct, lossy, False, _PNG_TO_HOST, suffixed)
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, *flags, ctypes.byref(out), ctypes.byref(outsize)) != 0:
+        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
+    return _take(out, outsize)
+
+
+def _png_single_out(name, struct, im, dst, strategy, options, types, lib, lossy):
+    """one image -> the file in `dst`; its size"""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    out, capacity = _pair_range(dst)
+    outsize = ctypes.c_size_t(0)
+    fn, flags = _png_entry(lib, name, struct, lossy, False, _PNG_TO_DEVICE)
+    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, *flags, out, capacity, ctypes.byref(outsize)) != 0:
+        message = name + ": " + (lib.zmx_last_error() or b"").decode()
+        if outsize.value > capacity:
+            raise CapacityError(message, int(outsize.value))
+        raise RuntimeError(message)
+    return int(outsize.value)
+
+
+def _png_batch(name, struct, ims, strategy, options, lib, lossy, suffixed=False):
+    """a list of images -> the list of the files' bytes"""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    n = len(ims)
+    outs = (_u8p * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    fn, flags = _png_entry(lib, name, struct, lossy, True, _PNG_TO_HOST, suffixed)
+    if fn(ctypes.byref(options), n, (struct * max(n, 1))(*ims), _png_strategy(strategy), *flags, outs, outsizes) != 0:
+        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
+    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+
+
+def _png_batch_packed(name, struct, ims, arena, align, strategy, options, lib, lossy):
+    """a list of images -> the files packed into `arena`; (offsets, sizes)"""
+    lib = lib or library()
+    options = options or ZopfliOptions()
+    out, capacity = _pair_range(arena)
+    n = len(ims)
+    offsets = (ctypes.c_size_t * max(n, 1))()
+    outsizes = (ctypes.c_size_t * max(n, 1))()
+    fn, flags = _png_entry(lib, name, struct, lossy, True, _PNG_PACKED)
+    if fn(ctypes.byref(options), n, (struct * max(n, 1))(*ims), _png_strategy(strategy), *flags, out, capacity, int(align), offsets, outsizes) != 0:
+        raise _batch_failure(name, lib, outsizes, n)
+    return [int(offsets[i]) for i in range(n)], [int(outsizes[i]) for i in range(n)]
+
+
+def _png_types(predefined, height):
+    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
+    if types is not None and len(types) != height:
+        raise ValueError(f"{len(types)} predefined types for {height} rows")
+    return types
 
 
 class PngLossyInfo(ctypes.Structure):
@@ -625,71 +714,44 @@ def _png_are_sources(images):
     return kinds == {True}
 
 
-def _png_sync_sources(sources):
-    """The current stream of every distinct torch device among the sources' tensors, synchronised once."""
-    devices = {}
-    for s in sources:
-        if s.tensor is not None and type(s.tensor).__module__.split(".")[0] == "torch":
-            devices[str(s.tensor.device)] = s.tensor.device
-    if devices:
-        import torch
-        for device in devices.values():
-            torch.cuda.current_stream(device).synchronize()
-
-
 def _png_source_array(sources):
     n = len(sources)
     return (PngSourceStruct * max(n, 1))(*[s.struct for s in sources])
 
 
-def _png_source_single(name, source, strategy, options, predefined, lib, lossy):
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    types = _png_types(predefined, source.height)
-    _png_sync_sources([source])
-    out, outsize = _u8p(), ctypes.c_size_t(0)
-    fn = getattr(lib, name)
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngSourceStruct), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint,
-                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), ctypes.byref(source.struct), _png_strategy(strategy), types, lossy, ctypes.byref(out), ctypes.byref(outsize)) != 0:
-        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
-    return _take(out, outsize)
+# png_encode_* and png_optimize_* differ in the symbols they call: `name` for images, `source_name` for PngSources.
+def _png_one(name, source_name, image, strategy, options, predefined, lib, lossy):
+    if isinstance(image, PngSource):
+        types = _png_types(predefined, image.height)
+        _sync_torch([image.tensor])
+        return _png_single(source_name, PngSourceStruct, image.struct, strategy, options, types, lib, lossy)
+    im = _png_image(image)
+    return _png_single(name, PngImage, im, strategy, options, _png_types(predefined, im.height), lib, lossy, suffixed=True)
 
 
-def _png_source_batch(name, sources, strategy, options, lib, lossy):
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    _png_sync_sources(sources)
-    n = len(sources)
-    outs = (_u8p * max(n, 1))()
-    outsizes = (ctypes.c_size_t * max(n, 1))()
-    fn = getattr(lib, name)
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngSourceStruct), ctypes.c_int, ctypes.c_uint,
-                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), n, _png_source_array(sources), _png_strategy(strategy), lossy, outs, outsizes) != 0:
-        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
-    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+def _png_one_out(name, source_name, image, dst, strategy, options, predefined, lib, lossy):
+    if isinstance(image, PngSource):
+        types = _png_types(predefined, image.height)
+        _sync_torch([image.tensor])
+        return _png_single_out(source_name, PngSourceStruct, image.struct, dst, strategy, options, types, lib, lossy)
+    im = _png_image(image)
+    return _png_single_out(name, PngImage, im, dst, strategy, options, _png_types(predefined, im.height), lib, lossy)
 
 
-def _png_source_out(name, source, dst, strategy, options, predefined, lib, lossy):
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    types = _png_types(predefined, source.height)
-    _png_sync_sources([source])
-    out, capacity = _device_range(int(dst[0]), dst[1]) if isinstance(dst, (tuple, list)) else _device_range(dst, None)
-    outsize = ctypes.c_size_t(0)
-    fn = getattr(lib, name)
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngSourceStruct), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint,
-                   ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), ctypes.byref(source.struct), _png_strategy(strategy), types, lossy, out, capacity, ctypes.byref(outsize)) != 0:
-        message = name + ": " + (lib.zmx_last_error() or b"").decode()
-        if outsize.value > capacity:
-            raise CapacityError(message, int(outsize.value))
-        raise RuntimeError(message)
-    return int(outsize.value)
+def _png_structs(images):
+    """(whether they are PngSources, the struct type, the structs) of a list of images or of PngSources; the current stream
+    of every torch device among their tensors is synchronised once."""
+    if _png_are_sources(images):
+        _sync_torch(s.tensor for s in images)
+        return True, PngSourceStruct, [s.struct for s in images]
+    ims = [_png_image(image, sync=False) for image in images]
+    _sync_torch(images)
+    return False, PngImage, ims
+
+
+def _png_many(name, source_name, images, strategy, options, lib, lossy):
+    sources, struct, ims = _png_structs(images)
+    return _png_batch(source_name if sources else name, struct, ims, strategy, options, lib, lossy, suffixed=not sources)
 
 
 def png_source_image(source, lib=None):
@@ -718,20 +780,8 @@ def png_encode_device(image, strategy="e", options=None, predefined=None, lib=No
     RuntimeError with the library's message when the library refuses or fails.
     `image` may also be a PngSource — a strided, planar, float or 16-bit tensor as it lies (zmx_png_encode_source_device):
     the file is the one its packed image gives."""
-    if isinstance(image, PngSource):
-        return _png_source_single("zmx_png_encode_source_device", image, strategy, options, predefined, lib, _png_lossy(lossy_transparent, lossy_8bit))
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    im = _png_image(image)
-    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
-    if types is not None and len(types) != im.height:
-        raise ValueError(f"{len(types)} predefined types for {im.height} rows")
-    out, outsize = _u8p(), ctypes.c_size_t(0)
-    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
-    fn, flags = _png_entry(lib, "zmx_png_encode_device", _png_lossy(lossy_transparent, lossy_8bit), False)
-    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, *flags, ctypes.byref(out), ctypes.byref(outsize)) != 0:
-        raise RuntimeError("zmx_png_encode_device: " + (lib.zmx_last_error() or b"").decode())
-    return _take(out, outsize)
+    return _png_one("zmx_png_encode_device", "zmx_png_encode_source_device", image, strategy, options, predefined, lib,
+                    _png_lossy(lossy_transparent, lossy_8bit))
 
 
 def png_encode_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False, lossy_8bit=False):
@@ -739,27 +789,8 @@ def png_encode_device_batch(images, strategy="e", options=None, lib=None, lossy_
     shares its deflate work among them.  `images`: a list of what png_encode_device takes (the current stream of every
     torch device among the tensors is synchronised once).  Predefined types are the single call's.  A list of PngSources
     (png_sources gives one for a batch tensor) goes to zmx_png_encode_source_device_batch: one launch packs them all."""
-    if _png_are_sources(images):
-        return _png_source_batch("zmx_png_encode_source_device_batch", images, strategy, options, lib, _png_lossy(lossy_transparent, lossy_8bit))
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    ims = [_png_image(image, sync=False) for image in images]
-    devices = {}
-    for image in images:
-        if not isinstance(image, (tuple, list)) and type(image).__module__.split(".")[0] == "torch":
-            devices[str(image.device)] = image.device
-    if devices:
-        import torch
-        for device in devices.values():
-            torch.cuda.current_stream(device).synchronize()
-    n = len(ims)
-    arr = (PngImage * max(n, 1))(*ims)
-    outs = (_u8p * max(n, 1))()
-    outsizes = (ctypes.c_size_t * max(n, 1))()
-    fn, flags = _png_entry(lib, "zmx_png_encode_device_batch", _png_lossy(lossy_transparent, lossy_8bit), True)
-    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), *flags, outs, outsizes) != 0:
-        raise RuntimeError("zmx_png_encode_device_batch: " + (lib.zmx_last_error() or b"").decode())
-    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+    return _png_many("zmx_png_encode_device_batch", "zmx_png_encode_source_device_batch", images, strategy, options, lib,
+                     _png_lossy(lossy_transparent, lossy_8bit))
 
 
 class PngColorStats(ctypes.Structure):
@@ -803,46 +834,15 @@ def png_optimize_device(image, strategy="e", options=None, predefined=None, lib=
     `lossy_8bit` encodes a 16-bit image as the 8-bit image of its high bytes, `lossy_transparent` gives the pixels with
     alpha 0 of an image that is 8-bit by then the RGB zopflipng gives them (zmx_png_optimize_device_lossy).  Arguments,
     result and errors as png_encode_device's, a PngSource included (zmx_png_optimize_source_device)."""
-    if isinstance(image, PngSource):
-        return _png_source_single("zmx_png_optimize_source_device", image, strategy, options, predefined, lib, _png_lossy(lossy_transparent, lossy_8bit))
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    im = _png_image(image)
-    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
-    if types is not None and len(types) != im.height:
-        raise ValueError(f"{len(types)} predefined types for {im.height} rows")
-    out, outsize = _u8p(), ctypes.c_size_t(0)
-    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
-    fn, flags = _png_entry(lib, "zmx_png_optimize_device", _png_lossy(lossy_transparent, lossy_8bit), False)
-    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, *flags, ctypes.byref(out), ctypes.byref(outsize)) != 0:
-        raise RuntimeError("zmx_png_optimize_device: " + (lib.zmx_last_error() or b"").decode())
-    return _take(out, outsize)
+    return _png_one("zmx_png_optimize_device", "zmx_png_optimize_source_device", image, strategy, options, predefined, lib,
+                    _png_lossy(lossy_transparent, lossy_8bit))
 
 
 def png_optimize_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_optimize_device_batch: one file per image, each the one png_optimize_device gives, from one call.
     Arguments as png_encode_device_batch's, a list of PngSources included (zmx_png_optimize_source_device_batch)."""
-    if _png_are_sources(images):
-        return _png_source_batch("zmx_png_optimize_source_device_batch", images, strategy, options, lib, _png_lossy(lossy_transparent, lossy_8bit))
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    ims = [_png_image(image, sync=False) for image in images]
-    devices = {}
-    for image in images:
-        if not isinstance(image, (tuple, list)) and type(image).__module__.split(".")[0] == "torch":
-            devices[str(image.device)] = image.device
-    if devices:
-        import torch
-        for device in devices.values():
-            torch.cuda.current_stream(device).synchronize()
-    n = len(ims)
-    arr = (PngImage * max(n, 1))(*ims)
-    outs = (_u8p * max(n, 1))()
-    outsizes = (ctypes.c_size_t * max(n, 1))()
-    fn, flags = _png_entry(lib, "zmx_png_optimize_device_batch", _png_lossy(lossy_transparent, lossy_8bit), True)
-    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), *flags, outs, outsizes) != 0:
-        raise RuntimeError("zmx_png_optimize_device_batch: " + (lib.zmx_last_error() or b"").decode())
-    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+    return _png_many("zmx_png_optimize_device_batch", "zmx_png_optimize_source_device_batch", images, strategy, options, lib,
+                     _png_lossy(lossy_transparent, lossy_8bit))
 
 
 def png_bound(width, height=None, colortype=None, bitdepth=None, lib=None):
@@ -879,49 +879,21 @@ def png_batch_bound(images, align=1, lib=None):
     return int(fn(n, (PngImage * max(n, 1))(*ims), int(align)))
 
 
-def _png_device_out(name, image, dst, strategy, options, predefined, lib, lossy):
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    im = _png_image(image)
-    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
-    if types is not None and len(types) != im.height:
-        raise ValueError(f"{len(types)} predefined types for {im.height} rows")
-    out, capacity = _device_range(int(dst[0]), dst[1]) if isinstance(dst, (tuple, list)) else _device_range(dst, None)
-    outsize = ctypes.c_size_t(0)
-    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
-    fn = getattr(lib, name)
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint, ctypes.c_void_p,
-                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, lossy, out, capacity, ctypes.byref(outsize)) != 0:
-        message = name + ": " + (lib.zmx_last_error() or b"").decode()
-        if outsize.value > capacity:
-            raise CapacityError(message, int(outsize.value))
-        raise RuntimeError(message)
-    return int(outsize.value)
-
-
 def png_encode_device_out(image, dst, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_encode_device_to_device: png_encode_device's file left in device memory.  `dst`: a contiguous tensor or an
     (integer device pointer, capacity) pair on the image's device, of any byte alignment.  Returns the file's size: its
     bytes are dst[0, size), and no byte behind them is written.  Raises CapacityError (with the size needed, nothing
     written) when the file does not fit — png_bound gives a capacity that always does —, otherwise as png_encode_device.
     A PngSource goes to zmx_png_encode_source_device_to_device; `dst` may not overlap the bytes its samples span."""
-    if isinstance(image, PngSource):
-        return _png_source_out("zmx_png_encode_source_device_to_device", image, dst, strategy, options, predefined, lib,
-                               _png_lossy(lossy_transparent, lossy_8bit))
-    return _png_device_out("zmx_png_encode_device_to_device", image, dst, strategy, options, predefined, lib,
-                           _png_lossy(lossy_transparent, lossy_8bit))
+    return _png_one_out("zmx_png_encode_device_to_device", "zmx_png_encode_source_device_to_device", image, dst, strategy, options,
+                        predefined, lib, _png_lossy(lossy_transparent, lossy_8bit))
 
 
 def png_optimize_device_out(image, dst, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, lossy_8bit=False):
     """zmx_png_optimize_device_to_device: png_optimize_device's file left in device memory; arguments, result and errors as
     png_encode_device_out's (a PngSource: zmx_png_optimize_source_device_to_device)."""
-    if isinstance(image, PngSource):
-        return _png_source_out("zmx_png_optimize_source_device_to_device", image, dst, strategy, options, predefined, lib,
-                               _png_lossy(lossy_transparent, lossy_8bit))
-    return _png_device_out("zmx_png_optimize_device_to_device", image, dst, strategy, options, predefined, lib,
-                           _png_lossy(lossy_transparent, lossy_8bit))
+    return _png_one_out("zmx_png_optimize_device_to_device", "zmx_png_optimize_source_device_to_device", image, dst, strategy, options,
+                        predefined, lib, _png_lossy(lossy_transparent, lossy_8bit))
 
 
 def png_encode_device_batch_packed(images, arena, align=1, strategy="e", options=None, lib=None, lossy_transparent=False, lossy_8bit=False):
@@ -930,43 +902,9 @@ def png_encode_device_batch_packed(images, arena, align=1, strategy="e", options
     1 .. 4096); the bytes between files are not written.  Returns (offsets, sizes).  Raises CapacityError (`needed`: the
     list of sizes, nothing written) when the arena is too small — png_batch_bound gives one that does.  A list of PngSources
     goes to zmx_png_encode_source_device_batch_packed."""
-    lib = lib or library()
-    options = options or ZopfliOptions()
-    if _png_are_sources(images):
-        _png_sync_sources(images)
-        out, capacity = _device_range(int(arena[0]), arena[1]) if isinstance(arena, (tuple, list)) else _device_range(arena, None)
-        n = len(images)
-        offsets = (ctypes.c_size_t * max(n, 1))()
-        outsizes = (ctypes.c_size_t * max(n, 1))()
-        fn = lib.zmx_png_encode_source_device_batch_packed
-        fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngSourceStruct), ctypes.c_int, ctypes.c_uint,
-                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
-        fn.restype = ctypes.c_int
-        if fn(ctypes.byref(options), n, _png_source_array(images), _png_strategy(strategy), _png_lossy(lossy_transparent, lossy_8bit), out,
-              capacity, int(align), offsets, outsizes) != 0:
-            raise _batch_failure("zmx_png_encode_source_device_batch_packed", lib, outsizes, n)
-        return [int(offsets[i]) for i in range(n)], [int(outsizes[i]) for i in range(n)]
-    ims = [_png_image(image, sync=False) for image in images]
-    devices = {}
-    for image in images:
-        if not isinstance(image, (tuple, list)) and type(image).__module__.split(".")[0] == "torch":
-            devices[str(image.device)] = image.device
-    if devices:
-        import torch
-        for device in devices.values():
-            torch.cuda.current_stream(device).synchronize()
-    out, capacity = _device_range(int(arena[0]), arena[1]) if isinstance(arena, (tuple, list)) else _device_range(arena, None)
-    n = len(ims)
-    offsets = (ctypes.c_size_t * max(n, 1))()
-    outsizes = (ctypes.c_size_t * max(n, 1))()
-    fn = lib.zmx_png_encode_device_batch_packed
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_uint, ctypes.c_void_p,
-                   ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), n, (PngImage * max(n, 1))(*ims), _png_strategy(strategy), _png_lossy(lossy_transparent, lossy_8bit), out,
-          capacity, int(align), offsets, outsizes) != 0:
-        raise _batch_failure("zmx_png_encode_device_batch_packed", lib, outsizes, n)
-    return [int(offsets[i]) for i in range(n)], [int(outsizes[i]) for i in range(n)]
+    sources, struct, ims = _png_structs(images)
+    name = "zmx_png_encode_source_device_batch_packed" if sources else "zmx_png_encode_device_batch_packed"
+    return _png_batch_packed(name, struct, ims, arena, align, strategy, options, lib, _png_lossy(lossy_transparent, lossy_8bit))
 
 
 class PngIndexImage(ctypes.Structure):
@@ -1005,28 +943,9 @@ def _png_index_image(image, palette=None, bitdepth=8, sync=True):
     return im
 
 
-def _png_types(predefined, height):
-    types = None if predefined is None else bytes(bytearray(int(t) for t in predefined))
-    if types is not None and len(types) != height:
-        raise ValueError(f"{len(types)} predefined types for {height} rows")
-    return types
-
-
 def _png_index_single(name, image, strategy, options, predefined, lib, lossy_transparent, palette, bitdepth):
-    lib = lib or library()
-    options = options or ZopfliOptions()
     im = _png_index_image(image, palette, bitdepth)
-    types = _png_types(predefined, im.height)
-    out, outsize = _u8p(), ctypes.c_size_t(0)
-    # (bound here, not in bind(): a library without the entry point — the CPU test library — still loads)
-    fn = getattr(lib, name)
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngIndexImage), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint,
-                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, _png_lossy(lossy_transparent, False), ctypes.byref(out),
-          ctypes.byref(outsize)) != 0:
-        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
-    return _take(out, outsize)
+    return _png_single(name, PngIndexImage, im, strategy, options, _png_types(predefined, im.height), lib, _png_lossy(lossy_transparent, False))
 
 
 def png_index_encode_device(image, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, palette=None, bitdepth=8):
@@ -1047,23 +966,9 @@ def png_index_optimize_device(image, strategy="e", options=None, predefined=None
 
 
 def _png_index_out(name, image, dst, strategy, options, predefined, lib, lossy_transparent, palette, bitdepth):
-    lib = lib or library()
-    options = options or ZopfliOptions()
     im = _png_index_image(image, palette, bitdepth)
-    types = _png_types(predefined, im.height)
-    out, capacity = _device_range(int(dst[0]), dst[1]) if isinstance(dst, (tuple, list)) else _device_range(dst, None)
-    outsize = ctypes.c_size_t(0)
-    fn = getattr(lib, name)
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.POINTER(PngIndexImage), ctypes.c_int, ctypes.c_char_p, ctypes.c_uint, ctypes.c_void_p,
-                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), ctypes.byref(im), _png_strategy(strategy), types, _png_lossy(lossy_transparent, False), out, capacity,
-          ctypes.byref(outsize)) != 0:
-        message = name + ": " + (lib.zmx_last_error() or b"").decode()
-        if outsize.value > capacity:
-            raise CapacityError(message, int(outsize.value))
-        raise RuntimeError(message)
-    return int(outsize.value)
+    return _png_single_out(name, PngIndexImage, im, dst, strategy, options, _png_types(predefined, im.height), lib,
+                           _png_lossy(lossy_transparent, False))
 
 
 def png_index_encode_device_out(image, dst, strategy="e", options=None, predefined=None, lib=None, lossy_transparent=False, palette=None,
@@ -1082,29 +987,9 @@ def png_index_optimize_device_out(image, dst, strategy="e", options=None, predef
 
 
 def _png_index_batch(name, images, strategy, options, lib, lossy_transparent):
-    lib = lib or library()
-    options = options or ZopfliOptions()
     ims = [_png_index_image(image, sync=False) for image in images]
-    devices = {}
-    for image in images:
-        src = image[0] if isinstance(image, (tuple, list)) else image
-        if type(src).__module__.split(".")[0] == "torch":
-            devices[str(src.device)] = src.device
-    if devices:
-        import torch
-        for device in devices.values():
-            torch.cuda.current_stream(device).synchronize()
-    n = len(ims)
-    arr = (PngIndexImage * max(n, 1))(*ims)
-    outs = (_u8p * max(n, 1))()
-    outsizes = (ctypes.c_size_t * max(n, 1))()
-    fn = getattr(lib, name)
-    fn.argtypes = [ctypes.POINTER(ZopfliOptions), ctypes.c_size_t, ctypes.POINTER(PngIndexImage), ctypes.c_int, ctypes.c_uint,
-                   ctypes.POINTER(_u8p), ctypes.POINTER(ctypes.c_size_t)]
-    fn.restype = ctypes.c_int
-    if fn(ctypes.byref(options), n, arr, _png_strategy(strategy), _png_lossy(lossy_transparent, False), outs, outsizes) != 0:
-        raise RuntimeError(name + ": " + (lib.zmx_last_error() or b"").decode())
-    return [_take(outs[i], ctypes.c_size_t(outsizes[i])) for i in range(n)]
+    _sync_torch(image[0] if isinstance(image, (tuple, list)) else image for image in images)
+    return _png_batch(name, PngIndexImage, ims, strategy, options, lib, _png_lossy(lossy_transparent, False))
 
 
 def png_index_encode_device_batch(images, strategy="e", options=None, lib=None, lossy_transparent=False):
@@ -1468,7 +1353,7 @@ class Context:
         synchronised once per device."""
         if len(sources) != len(outs):
             raise ValueError(f"{len(sources)} sources, but {len(outs)} destinations")
-        _png_sync_sources(sources)
+        _sync_torch(s.tensor for s in sources)
         ptrs, capacities = _device_ranges(outs)
         n = len(sources)
         fn = self.lib.zmx_png_pack_device

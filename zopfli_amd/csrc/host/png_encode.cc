@@ -1,31 +1,32 @@
-// zmx_png_encode_device, zmx_png_encode_device_batch: an image in device memory as the PNG file zopflipng writes for it
-// (include/zopfli_amd.h says which).  The filter types and the filtered scanlines are made on a pooled context of the
-// image's device, into a buffer of the call's own that outlives the context's hold: the context goes back to the pool
-// BEFORE zmx_compress_device(ZLIB) of the buffer runs, which takes contexts itself.  The stream's second byte and the
-// chunks around it are png_container.h's.  (Outside api.cc, as png.cc is: the host-only test library links api.cc
-// against a stand-in for the device layer.)
-// zmx_png_optimize_device and its batch, further down, reduce the colour mode first: the statistics
-// (zmx_png_color_stats_device), LodePNG's choice (png_color_choose.h) and the conversion run on the same hold of the
-// context as the types and the rows; a palette file below 4096 bytes is made a second time as RGB or RGBA, on a second
-// hold, and the smaller file is kept.
-// The _lossy entries put zopflipng's --lossy_8bit and --lossy_transparent in front (zmx_internal_png_lossy_image, on the
-// first hold of the context): the 8-bit and the rewritten image go to a buffer of the call's own, and everything after
-// runs on that instead of the caller's pixels.  The entries without the suffix are these with lossy = 0.
-// ZMX_PNG_FILTER_AUTO is zopflipng's own choice of the strategy (zmx_png_choose_strategy_device, further down): made on the
-// first hold of the context, after the rewrite and the 8-bit conversion, image by image in the batches; everything after
-// is the entry's path with the strategy chosen.
-// The zmx_png_index_* entries, at the end, take a palette or low-bit grey image: k_png_index_use's table of first
-// appearances, png_index.h's statistics, mode and conversion table, k_png_index_convert, and from there the other entries'
-// path — the trials, the row search, the compression and the tails are shared through RowSource and FinishOptimize*.
-// The _to_device entries and zmx_png_encode_device_batch_packed leave the file in device memory: the same first hold (the
-// *FrontHalf functions, shared with the host-output entries), then the to-device compress path with the file's frame
-// around the stream (device_output_plan.h: PngFrame) and the IDAT's CRC-32 sealed on the device.
+// The zmx_png_* entries that make a PNG file of an image in device memory (include/zopfli_amd.h says which file): encode
+// and optimize, plain and _lossy, index, _to_device, _batch, _batch_packed and _source_*.  They are ONE pipeline:
+//
+//   Kind      what the images are made of — ColourKind: zmx_png_images, as they are (encode) or with the colour mode
+//             reduced (optimize), the _lossy rewrite in front; IndexKind: zmx_png_index_images, palette or low-bit grey.
+//             A kind checks image i on the host, and on a held context prepares it and makes its filtered scanlines.
+//   Subject   one prepared image: its rows in any colour mode (RowSource), the first file's mode, the statistics where a
+//             second try competes (null: the encode entries and index-encode), the strategy its rows are made with.
+//   MakeFront the checks of a call of n images, the buffers, and one hold of a pooled context on which every image is
+//             prepared, given its strategy (_AUTO: zopflipng's choice, image by image) and filtered into one scan buffer.
+//             A single call is a front of one image, with _PREDEFINED allowed and no ": image i" in its messages.
+//   Finish*   the files around the streams.  FinishBatch: one zmx_compress_device_batch over the first files, zopflipng's
+//             second try at the palette files below 4096 bytes on one more hold and in one more batch, the smaller kept,
+//             and no out[i] touched before every file is made.  FinishOne / FinishOneToDevice: the same for one file,
+//             through zmx_compress_device or into device memory.  BatchPacked: the first files in one arena.
+//
+// The scanlines go to a buffer of the call's own that outlives the context's hold: the context is back in the pool BEFORE
+// any zmx_compress_device* / CompressDeviceToDevice* call runs — those take contexts themselves, so a hold around them can
+// deadlock the pool.  The stream's second byte and the chunks around it are png_container.h's; the to-device paths put
+// the file's frame around the stream (device_output_plan.h: PngFrame) and seal the IDAT's CRC-32 on the device.
+// ZMX_PNG_FILTER_AUTO is zopflipng's own choice of the strategy (ChooseStrategy; zmx_png_choose_strategy_device).
 // The zmx_png_*_source_* entries, last, take strided, planar, float and 16-bit sources (png_source.h): every source
-// checked, one buffer for all packed images, one hold of a context for one k_png_pack launch, then the entry of the same
-// name without _source on zmx_png_images that point into the buffer.
+// checked, one buffer for all packed images, one hold of a context for one k_png_pack launch, then the pipeline on
+// zmx_png_images that point into the buffer.
+// (Outside api.cc, as png.cc is: the host-only test library links api.cc against a stand-in for the device layer.)
 #include <algorithm>
 #include <cstdlib>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -55,6 +56,8 @@ struct DeviceBuffer {
   ~DeviceBuffer() { zmx_internal_device_free(device, p); }
 };
 
+size_t RoundUp16(size_t n) { return (n + 15) & ~static_cast<size_t>(15); }
+
 struct Geometry {
   size_t linebytes, bytewidth, height, scanlines;   // scanlines = height * (linebytes + 1)
 };
@@ -74,6 +77,12 @@ int CheckImage(const std::string& w, const zmx_png_image& im, Geometry* g) {
   return 0;
 }
 
+int CheckReducible(const std::string& w, const zmx_png_image& im, Geometry* g) {
+  if (CheckImage(w, im, g) != 0) return -1;
+  if (static_cast<uint64_t>(im.width) * im.height > 0xffffffffull) return Refuse(w + ": an image of 2^32 pixels or more");
+  return 0;
+}
+
 bool StrategyOk(int strategy, bool predefined_allowed) {
   return (strategy >= ZMX_PNG_FILTER_ZERO && strategy <= ZMX_PNG_FILTER_BRUTE) || strategy == ZMX_PNG_FILTER_AUTO ||
          (predefined_allowed && strategy == ZMX_PNG_FILTER_PREDEFINED);
@@ -89,8 +98,8 @@ int CheckPredefined(const std::string& w, int strategy, const unsigned char* pre
   return 0;
 }
 
-// A file in the making: a malloc'ed array under the reference's convention that begins with PngPrefix's bytes, for
-// ZopfliCompress to append the stream to.
+// A file in the making: a malloc'ed array under the reference's convention that begins with the file's bytes up to the
+// IDAT's type, for ZopfliCompress to append the stream to.
 struct File {
   unsigned char* bytes = nullptr;
   size_t size = 0;
@@ -99,14 +108,7 @@ struct File {
   File& operator=(const File&) = delete;
   ~File() { std::free(bytes); }
   size_t prefix_bytes = zamd::kPngPrefixBytes;
-  void Begin(const zmx_png_image& im) {
-    unsigned char prefix[zamd::kPngPrefixBytes];
-    zamd::PngPrefix(im.width, im.height, im.colortype, im.bitdepth, prefix);
-    zamd::AppendToOutput(prefix, sizeof(prefix), &bytes, &size);
-  }
-  // the file of the image in `mode`: PLTE and tRNS where the mode has them
-  void BeginReduced(const zmx_png_image& im, const zmx_png_color_mode& mode) { BeginIn(im.width, im.height, mode); }
-  // (a mode without a palette and a key gives Begin's bytes)
+  // the file of a width x height image in `mode`: PLTE and tRNS where the mode has them
   void BeginIn(uint32_t width, uint32_t height, const zmx_png_color_mode& mode) {
     unsigned char prefix[zamd::kPngMaxPrefixBytes];
     prefix_bytes = zamd::PngPrefixReduced(width, height, mode.colortype, mode.bitdepth, mode.palette, mode.palettesize,
@@ -132,19 +134,23 @@ struct File {
   }
 };
 
+// Of two closed files of one image the one zopflipng keeps: the second only when it is strictly smaller.
+File& Smaller(File& first, File& second) { return second.size < first.size ? second : first; }
+
 // What a _lossy entry makes of an image before anything else (zopflipng_lib.cc:415-428): its 8-bit image where the
 // optimize entry has _8BIT and the image is 16 bits deep, the rewrite of the transparent pixels where it has _TRANSPARENT
 // and the image is 8-bit by then and has an alpha channel.  bytes: the buffer either takes, 0 where nothing is made.
+// (of an image that CheckImage has passed)
 struct LossyPlan {
   bool to8 = false, transparent = false;
   size_t bytes = 0;
 };
 
-LossyPlan PlanLossy(const zmx_png_image& im, const Geometry& g, unsigned lossy, bool optimize) {
+LossyPlan PlanLossy(const zmx_png_image& im, unsigned lossy, bool optimize) {
   LossyPlan p;
   p.to8 = optimize && (lossy & ZMX_PNG_LOSSY_8BIT) != 0 && im.bitdepth == 16;
   p.transparent = (lossy & ZMX_PNG_LOSSY_TRANSPARENT) != 0 && (im.bitdepth == 8 || p.to8) && (im.colortype == 4 || im.colortype == 6);
-  if (p.to8 || p.transparent) p.bytes = g.linebytes / (p.to8 ? 2 : 1) * g.height;
+  if (p.to8 || p.transparent) p.bytes = zamd::PngLineBytes(im.width, im.colortype, im.bitdepth) / (p.to8 ? 2 : 1) * im.height;
   return p;
 }
 
@@ -193,32 +199,13 @@ zamd::PngFrame FrameIn(uint32_t width, uint32_t height, const zmx_png_color_mode
                                                   mode.key_defined != 0, mode.key_r, mode.key_g, mode.key_b, frame.file_prefix.data()));
   return frame;
 }
-// ... of `im`: in `mode`, or as it is (null)
-zamd::PngFrame FrameOf(const zmx_png_image& im, const zmx_png_color_mode* mode) {
-  if (mode) return FrameIn(im.width, im.height, *mode);
-  zamd::PngFrame frame;
-  frame.file_prefix.resize(zamd::kPngPrefixBytes);
-  zamd::PngPrefix(im.width, im.height, im.colortype, im.bitdepth, frame.file_prefix.data());
-  return frame;
-}
 
 // room that does for the file around `scanlines` filtered bytes, whatever its prefix
 size_t FileBound(size_t scanlines) {
   return zamd::kPngMaxPrefixBytes + zamd::CompressBound(ZOPFLI_FORMAT_ZLIB, scanlines) + zamd::kPngTrailerBytes;
 }
 
-}  // namespace
-
-namespace {
-
-// What is made of one image: its statistics, the mode of the first file, the scanlines' size in that mode.
-struct Reduced {
-  zmx_png_color_stats stats;
-  zmx_png_color_mode mode;
-  bool as_is = false;      // the mode is the image's own: nothing is converted
-  size_t scanlines = 0;    // height * (row bytes + 1)
-};
-
+// ---- colour modes, and an image as rows in one
 bool SameMode(const zmx_png_image& im, const zmx_png_color_mode& mode) {
   return mode.colortype == im.colortype && mode.bitdepth == im.bitdepth && mode.key_defined == 0;
 }
@@ -229,8 +216,8 @@ size_t ByteWidthIn(const zmx_png_color_mode& mode) { return BitsPerPixel(mode) <
 size_t ScanlinesIn(uint32_t width, uint32_t height, const zmx_png_color_mode& mode) {
   return static_cast<size_t>(height) * (RowBytesIn(width, mode) + 1);
 }
-size_t ScanlinesIn(const zmx_png_image& im, const zmx_png_color_mode& mode) { return ScanlinesIn(im.width, im.height, mode); }
 
+// the mode an image lies in: the first (and only) file's of the encode entries
 zmx_png_color_mode OwnMode(const zmx_png_image& im) {
   zmx_png_color_mode own = zmx_png_color_mode();
   own.colortype = im.colortype;
@@ -257,18 +244,10 @@ RowSource RowsOf(const zmx_png_image& im) {
   }};
 }
 
-int CheckReducible(const std::string& w, const zmx_png_image& im, Geometry* g) {
-  if (CheckImage(w, im, g) != 0) return -1;
-  if (static_cast<uint64_t>(im.width) * im.height > 0xffffffffull) return Refuse(w + ": an image of 2^32 pixels or more");
-  return 0;
-}
-
-// on a held context: the statistics and the mode of the first file
-int StatsAndMode(zmx_ctx* ctx, const zmx_png_image& im, Reduced* r) {
-  if (zmx_png_color_stats_device(ctx, &im, &r->stats) != 0) return -1;
-  zamd::PngChooseColor(r->stats, static_cast<uint64_t>(im.width) * im.height, &r->mode);
-  r->as_is = SameMode(im, r->mode);
-  r->scanlines = ScanlinesIn(im, r->mode);
+// on a held context: the statistics of an image and LodePNG's choice of its mode
+int StatsAndMode(zmx_ctx* ctx, const zmx_png_image& im, zmx_png_color_stats* stats, zmx_png_color_mode* mode) {
+  if (zmx_png_color_stats_device(ctx, &im, stats) != 0) return -1;
+  zamd::PngChooseColor(*stats, static_cast<uint64_t>(im.width) * im.height, mode);
   return 0;
 }
 
@@ -283,7 +262,7 @@ int TrialFileSizes(zmx_ctx* ctx, const std::string& w, int device, const RowSour
                    const unsigned char* predefined, int ntrials, uint64_t* file_bytes) {
   const size_t scanlines = ScanlinesIn(src.width, src.height, mode), rowbytes = RowBytesIn(src.width, mode);
   if (scanlines > SIZE_MAX / 9) return Refuse(w + ": the sizes overflow");
-  const size_t room = (rowbytes * src.height + 15) & ~static_cast<size_t>(15);
+  const size_t room = RoundUp16(rowbytes * src.height);
   DeviceBuffer buf;
   buf.device = device;
   if (zmx_internal_device_alloc(device, room + scanlines * ntrials, &buf.p) != 0) return -1;
@@ -336,18 +315,6 @@ int ChooseStrategy(zmx_ctx* ctx, const std::string& w, int device, const RowSour
   return 0;
 }
 
-// ... for a zmx_png_image: as it is, or reduced — `known`: its statistics and mode where the caller has them
-int ChooseStrategy(zmx_ctx* ctx, const std::string& w, int device, const zmx_png_image& im, bool reduce_color, const Reduced* known,
-                   const unsigned char* predefined, int* strategy, uint64_t* file_bytes) {
-  if (!reduce_color) return ChooseStrategy(ctx, w, device, RowsOf(im), OwnMode(im), nullptr, predefined, strategy, file_bytes);
-  Reduced mine;
-  if (!known) {
-    if (StatsAndMode(ctx, im, &mine) != 0) return -1;
-    known = &mine;
-  }
-  return ChooseStrategy(ctx, w, device, RowsOf(im), known->mode, &known->stats, predefined, strategy, file_bytes);
-}
-
 }  // namespace
 
 extern "C" int zmx_png_choose_strategy_device(zmx_ctx* ctx, const zmx_png_image* image, int reduce_color, const unsigned char* predefined,
@@ -359,192 +326,16 @@ extern "C" int zmx_png_choose_strategy_device(zmx_ctx* ctx, const zmx_png_image*
   if (CheckPredefined(w, ZMX_PNG_FILTER_AUTO, predefined, g.height) != 0) return -1;
   int device = -1;
   if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, g.linebytes * g.height, &device) != 0) return -1;
+  zmx_png_color_stats stats;
+  zmx_png_color_mode mode = OwnMode(*image);
+  if (reduce_color && StatsAndMode(ctx, *image, &stats, &mode) != 0) return -1;
   int chosen = 0;
   uint64_t bytes[8];
-  if (ChooseStrategy(ctx, w, device, *image, reduce_color != 0, nullptr, predefined, &chosen, bytes) != 0) return -1;
+  if (ChooseStrategy(ctx, w, device, RowsOf(*image), mode, reduce_color ? &stats : nullptr, predefined, &chosen, bytes) != 0) return -1;
   *strategy = chosen;
   for (int k = 0; k < 8; ++k) file_bytes[k] = bytes[k];
   return 0;
 }
-
-namespace {
-
-// What zmx_png_encode_device[_lossy] and zmx_png_encode_device_to_device share: the checks (`dest`: the to-device entry's
-// destination, checked with them) and the first hold of a context, which leaves the filtered scanlines in `scan`.
-struct EncodeFront {
-  Geometry g;
-  DeviceBuffer scan, rewritten;
-};
-
-int EncodeFrontHalf(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
-                    unsigned lossy, const DeviceDest* dest, EncodeFront* f) {
-  if (!options || !image) return Refuse(w + ": null argument");
-  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
-  Geometry& g = f->g;
-  if (CheckImage(w, *image, &g) != 0) return -1;
-  if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
-  if (CheckPredefined(w, strategy, predefined, g.height) != 0) return -1;
-  const LossyPlan plan = PlanLossy(*image, g, lossy, false);
-  if (CheckRewritable(w, *image, plan) != 0) return -1;
-  DeviceBuffer& scan = f->scan;
-  DeviceBuffer& rewritten = f->rewritten;
-  const size_t nbytes = g.linebytes * g.height;
-  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, nbytes, &scan.device) != 0) return -1;
-  if (dest && CheckDest(w, *dest, scan.device, 1, &image->d_pixels, &nbytes) != 0) return -1;
-  if (zmx_internal_device_alloc(scan.device, g.scanlines, &scan.p) != 0) return -1;
-  rewritten.device = scan.device;
-  if (plan.bytes != 0 && zmx_internal_device_alloc(scan.device, plan.bytes, &rewritten.p) != 0) return -1;
-  zmx_png_image work = *image;
-  // (the context is held for the rewrite, the types and the rows only)
-  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), image, 0, 1, rewritten.p, &work) != 0) return -1;
-    if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, scan.device, work, false, nullptr, predefined, &strategy, nullptr) != 0) return -1;
-    return zmx_internal_png_scanlines(ctx, work.d_pixels, g.linebytes, g.height, g.bytewidth, strategy, kBruteWindow, predefined, scan.p);
-  }, scan.device);
-}
-
-int EncodeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
-              unsigned lossy, unsigned char** out, size_t* outsize) {
-  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
-  EncodeFront f;
-  if (EncodeFrontHalf(w, options, image, strategy, predefined, lossy, nullptr, &f) != 0) return -1;
-  File file;
-  file.Begin(*image);
-  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, f.scan.p, f.g.scanlines, &file.bytes, &file.size) != 0) return -1;
-  if (!file.Close()) return BadStream(w);
-  file.GiveTo(out, outsize);
-  return 0;
-}
-
-// The file left in device memory: the stream goes zmx_compress_device_to_device's way with the file's frame around it.
-int EncodeOneToDevice(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                      const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
-  if (!options || !image || !outsize) return Refuse(w + ": null argument");
-  *outsize = 0;
-  const DeviceDest dest{d_out, capacity};
-  EncodeFront f;
-  if (EncodeFrontHalf(w, options, image, strategy, predefined, lossy, &dest, &f) != 0) return -1;
-  const zamd::PngFrame frame = FrameOf(*image, nullptr);
-  return zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, f.scan.p, f.g.scanlines, d_out, capacity, outsize, &frame);
-}
-
-// What zmx_png_encode_device_batch[_lossy] and zmx_png_encode_device_batch_packed share (n > 0): the checks (`dest`: the
-// arena, checked with them) and the one hold of a context, which leaves image i's filtered scanlines at scan + start[i].
-struct BatchFront {
-  std::vector<Geometry> g;
-  std::vector<size_t> start;
-  DeviceBuffer scan, rewritten;
-};
-
-int EncodeBatchFrontHalf(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy, unsigned lossy,
-                         const DeviceDest* dest, BatchFront* f) {
-  if (!options || !images) return Refuse(w + ": null argument");
-  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
-  if (strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
-  if (!StrategyOk(strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
-  std::vector<Geometry>& g = f->g;
-  std::vector<size_t>& start = f->start;   // where image i's scanlines begin in the one buffer
-  g.resize(n);
-  start.assign(n + 1, 0);
-  std::vector<size_t> rstart(n + 1, 0);  // and its rewritten pixels in theirs
-  std::vector<LossyPlan> plan(n);
-  std::vector<const void*> pixels(n);
-  std::vector<size_t> nbytes(n);
-  for (size_t i = 0; i < n; ++i) {
-    const std::string wi = w + ": image " + std::to_string(i);
-    if (CheckImage(wi, images[i], &g[i]) != 0) return -1;
-    if (g[i].scanlines > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
-    start[i + 1] = start[i] + g[i].scanlines;
-    plan[i] = PlanLossy(images[i], g[i], lossy, false);
-    if (CheckRewritable(wi, images[i], plan[i]) != 0) return -1;
-    rstart[i + 1] = rstart[i] + ((plan[i].bytes + 15) & ~static_cast<size_t>(15));
-    pixels[i] = images[i].d_pixels;
-    nbytes[i] = g[i].linebytes * g[i].height;
-  }
-  DeviceBuffer& scan = f->scan;
-  DeviceBuffer& rewritten = f->rewritten;
-  if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &scan.device) != 0) return -1;
-  if (dest && CheckDest(w, *dest, scan.device, n, pixels.data(), nbytes.data()) != 0) return -1;
-  if (zmx_internal_device_alloc(scan.device, start[n], &scan.p) != 0) return -1;
-  rewritten.device = scan.device;
-  if (rstart[n] != 0 && zmx_internal_device_alloc(scan.device, rstart[n], &rewritten.p) != 0) return -1;
-  unsigned char* const base = static_cast<unsigned char*>(scan.p);
-  // (one hold of a context for all images; a launch set per image: tools/png_device.py measures what that costs)
-  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    for (size_t i = 0; i < n; ++i) {
-      zmx_png_image work = images[i];
-      if (plan[i].bytes != 0 &&
-          zmx_internal_png_lossy_image(ctx, w.c_str(), &images[i], 0, 1, static_cast<unsigned char*>(rewritten.p) + rstart[i], &work) != 0) {
-        return -1;
-      }
-      int chosen = strategy;
-      if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, scan.device, work, false, nullptr, nullptr, &chosen, nullptr) != 0) return -1;
-      if (zmx_internal_png_scanlines(ctx, work.d_pixels, g[i].linebytes, g[i].height, g[i].bytewidth, chosen, kBruteWindow, nullptr,
-                                     base + start[i]) != 0) {
-        return -1;
-      }
-    }
-    return 0;
-  }, scan.device);
-}
-
-int EncodeBatch(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy, unsigned lossy,
-                unsigned char** out, size_t* outsize) {
-  if (n == 0) return 0;
-  if (!options || !images || !out || !outsize) return Refuse(w + ": null argument");
-  BatchFront f;
-  if (EncodeBatchFrontHalf(w, options, n, images, strategy, lossy, nullptr, &f) != 0) return -1;
-  const std::vector<Geometry>& g = f.g;
-  const std::vector<size_t>& start = f.start;
-  unsigned char* const base = static_cast<unsigned char*>(f.scan.p);
-  std::vector<const void*> slices(n);
-  std::vector<size_t> sizes(n);
-  std::vector<File> files(n);
-  std::vector<unsigned char*> bytes(n);
-  std::vector<size_t> filled(n);
-  for (size_t i = 0; i < n; ++i) {
-    slices[i] = base + start[i];
-    sizes[i] = g[i].scanlines;
-    files[i].Begin(images[i]);
-    bytes[i] = files[i].bytes;
-    filled[i] = files[i].size;
-  }
-  // (a failed call changes none of them: the files still own their arrays)
-  if (zmx_compress_device_batch(options, ZOPFLI_FORMAT_ZLIB, n, slices.data(), sizes.data(), bytes.data(), filled.data()) != 0) return -1;
-  for (size_t i = 0; i < n; ++i) {
-    files[i].bytes = bytes[i];
-    files[i].size = filled[i];
-  }
-  // every file made before any out[i] is touched
-  for (size_t i = 0; i < n; ++i) {
-    if (!files[i].Close()) return BadStream(w);
-  }
-  for (size_t i = 0; i < n; ++i) files[i].GiveTo(&out[i], &outsize[i]);
-  return 0;
-}
-
-// The files left in one arena: zmx_compress_device_batch_packed's plan with a frame per stream.
-int EncodeBatchPacked(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy, unsigned lossy,
-                      void* d_arena, size_t capacity, size_t align, size_t* outoffset, size_t* outsize) {
-  if (n == 0) return 0;
-  if (!options || !images || !outoffset || !outsize) return Refuse(w + ": null argument");
-  if (!zamd::PackedAlignOk(align)) return Refuse(w + ": align " + std::to_string(align) + " is not a power of two from 1 to 4096");
-  const DeviceDest dest{d_arena, capacity};
-  BatchFront f;
-  if (EncodeBatchFrontHalf(w, options, n, images, strategy, lossy, &dest, &f) != 0) return -1;
-  std::vector<const void*> slices(n);
-  std::vector<size_t> sizes(n);
-  std::vector<zamd::PngFrame> frames(n);
-  for (size_t i = 0; i < n; ++i) {
-    slices[i] = static_cast<unsigned char*>(f.scan.p) + f.start[i];
-    sizes[i] = f.g[i].scanlines;
-    frames[i] = FrameOf(images[i], nullptr);
-  }
-  return zamd::CompressDeviceBatchPackedFramed(w.c_str(), options, n, slices.data(), sizes.data(), frames.data(), d_arena, capacity, align,
-                                               outoffset, outsize);
-}
-
-}  // namespace
 
 extern "C" size_t zmx_png_bound(uint32_t width, uint32_t height, uint32_t colortype, uint32_t bitdepth) {
   if (width == 0 || height == 0 || !zamd::PngFormatOk(colortype, bitdepth)) return 0;
@@ -557,367 +348,10 @@ extern "C" size_t zmx_png_batch_bound(size_t n, const zmx_png_image* images, siz
   }
   return zamd::PngBatchBound(n, images, align);
 }
-extern "C" int zmx_png_encode_device_to_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                                               const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
-  return EncodeOneToDevice("zmx_png_encode_device_to_device", options, image, strategy, predefined, lossy, d_out, capacity, outsize);
-}
-extern "C" int zmx_png_encode_device_batch_packed(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
-                                                  unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
-                                                  size_t* outsize) {
-  return EncodeBatchPacked("zmx_png_encode_device_batch_packed", options, n, images, strategy, lossy, d_arena, capacity, align, outoffset,
-                           outsize);
-}
-
-extern "C" int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                                     const unsigned char* predefined, unsigned char** out, size_t* outsize) {
-  return EncodeOne("zmx_png_encode_device", options, image, strategy, predefined, 0, out, outsize);
-}
-extern "C" int zmx_png_encode_device_lossy(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                                           const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
-  return EncodeOne("zmx_png_encode_device_lossy", options, image, strategy, predefined, lossy, out, outsize);
-}
-extern "C" int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
-                                           unsigned char** out, size_t* outsize) {
-  return EncodeBatch("zmx_png_encode_device_batch", options, n, images, strategy, 0, out, outsize);
-}
-extern "C" int zmx_png_encode_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
-                                                 unsigned lossy, unsigned char** out, size_t* outsize) {
-  return EncodeBatch("zmx_png_encode_device_batch_lossy", options, n, images, strategy, lossy, out, outsize);
-}
-
-// ---- zmx_png_optimize_device, zmx_png_optimize_device_batch: the colour mode reduced first (png_color_choose.h)
 extern "C" int zmx_png_choose_color(const zmx_png_color_stats* stats, uint64_t numpixels, zmx_png_color_mode* out) {
   if (!stats || !out) return Refuse("zmx_png_choose_color: null argument");
   zamd::PngChooseColor(*stats, numpixels, out);
   return 0;
-}
-
-namespace {
-
-// Of two closed files of one image the one zopflipng keeps: the second only when it is strictly smaller.
-File& Smaller(File& first, File& second) { return second.size < first.size ? second : first; }
-
-}  // namespace
-
-namespace {
-
-// What zmx_png_optimize_device[_lossy] and zmx_png_optimize_device_to_device share: the checks (`dest`: the to-device
-// entry's destination, checked with them) and the first hold of a context, which leaves the first file's scanlines in
-// `scan`; and the second try's scanlines, on a second hold.
-struct OptimizeFront {
-  int device = -1;
-  int strategy = 0;         // the one the rows were made with (_AUTO: the chosen one)
-  Reduced r;
-  DeviceBuffer scan, rewritten;
-  zmx_png_image work;       // what is encoded: the caller's image, or its 8-bit or rewritten image in `rewritten`
-};
-
-int OptimizeFrontHalf(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                      const unsigned char* predefined, unsigned lossy, const DeviceDest* dest, OptimizeFront* f) {
-  if (!options || !image) return Refuse(w + ": null argument");
-  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
-  Geometry g;
-  if (CheckReducible(w, *image, &g) != 0) return -1;
-  if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
-  if (CheckPredefined(w, strategy, predefined, g.height) != 0) return -1;
-  int& device = f->device;
-  const size_t nbytes = g.linebytes * g.height;
-  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, nbytes, &device) != 0) return -1;
-  if (dest && CheckDest(w, *dest, device, 1, &image->d_pixels, &nbytes) != 0) return -1;
-  const LossyPlan plan = PlanLossy(*image, g, lossy, true);
-  Reduced& r = f->r;
-  DeviceBuffer& scan = f->scan;
-  DeviceBuffer& rewritten = f->rewritten;
-  scan.device = rewritten.device = device;
-  if (plan.bytes != 0 && zmx_internal_device_alloc(device, plan.bytes, &rewritten.p) != 0) return -1;
-  zmx_png_image& work = f->work;
-  work = *image;
-  // (the context is held for the rewrite, the statistics, the conversion, the types and the rows only)
-  const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), image, plan.to8, plan.transparent, rewritten.p, &work) != 0) return -1;
-    if (StatsAndMode(ctx, work, &r) != 0) return -1;
-    if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, device, work, true, &r, predefined, &strategy, nullptr) != 0) return -1;
-    if (zmx_internal_device_alloc(device, r.scanlines, &scan.p) != 0) return -1;
-    return zmx_internal_png_reduced_scanlines(ctx, &work, r.as_is ? nullptr : &r.mode, strategy, kBruteWindow, predefined, scan.p);
-  }, device);
-  f->strategy = strategy;
-  return rc;
-}
-
-// its mode and its scanlines, into scan2
-int SecondTryScanlines(const OptimizeFront& f, const unsigned char* predefined, zmx_png_color_mode* retry, bool* as_is, size_t* scanlines,
-                       DeviceBuffer* scan2) {
-  zamd::PngRetryMode(f.r.stats, static_cast<uint64_t>(f.work.width) * f.work.height, retry);
-  *as_is = SameMode(f.work, *retry);
-  *scanlines = ScanlinesIn(f.work, *retry);
-  scan2->device = f.device;
-  if (zmx_internal_device_alloc(f.device, *scanlines, &scan2->p) != 0) return -1;
-  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    return zmx_internal_png_reduced_scanlines(ctx, &f.work, *as_is ? nullptr : retry, f.strategy, kBruteWindow, predefined, scan2->p);
-  }, f.device);
-}
-
-// zopflipng's second try at a small palette file, made by whoever holds the image: its mode, its scanlines' size and the
-// scanlines, into a buffer allocated here.  0, or -1 with the error set.
-using SecondTry = std::function<int(zmx_png_color_mode* retry, size_t* scanlines, DeviceBuffer* scan2)>;
-
-// What the optimize entries with host output share once the first file's scanlines lie in `scan`: the file in `mode`, the
-// second try where it is a palette file below 4096 bytes, the smaller of the two handed over.
-int FinishOptimize(const std::string& w, const ZopfliOptions* options, uint32_t width, uint32_t height, const zmx_png_color_mode& mode,
-                   const void* d_scan, size_t scanlines, const SecondTry& second_try, unsigned char** out, size_t* outsize) {
-  File file;
-  file.BeginIn(width, height, mode);
-  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, d_scan, scanlines, &file.bytes, &file.size) != 0) return -1;
-  if (!file.Close()) return BadStream(w);
-  File second;
-  if (mode.colortype == 3 && file.size < zamd::kPngRetryBelow) {
-    zmx_png_color_mode retry;
-    size_t scanlines2 = 0;
-    DeviceBuffer scan2;
-    if (second_try(&retry, &scanlines2, &scan2) != 0) return -1;
-    second.BeginIn(width, height, retry);
-    if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines2, &second.bytes, &second.size) != 0) return -1;
-    if (!second.Close()) return BadStream(w);
-    Smaller(file, second).GiveTo(out, outsize);
-    return 0;
-  }
-  file.GiveTo(out, outsize);
-  return 0;
-}
-
-// The same with the file left in device memory.  A mode other than a palette: the one file goes straight into d_out, as the
-// encode entry's.  A palette: which file is kept, and so its size, is known only when the first is made — so the first goes
-// into a buffer of the call's own, the second (where one is due) into another, and ONE device-to-device copy puts the kept
-// file into d_out: every byte of the file is written and none outside it, and a capacity of exactly the kept file's size does.
-int FinishOptimizeToDevice(const std::string& w, const ZopfliOptions* options, int device, uint32_t width, uint32_t height,
-                           const zmx_png_color_mode& mode, const void* d_scan, size_t scanlines, const SecondTry& second_try, void* d_out,
-                           size_t capacity, size_t* outsize) {
-  const zamd::PngFrame frame = FrameIn(width, height, mode);
-  if (mode.colortype != 3) {
-    return zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, d_scan, scanlines, d_out, capacity, outsize, &frame);
-  }
-  DeviceBuffer first, second;
-  first.device = second.device = device;
-  const size_t room = FileBound(scanlines);
-  size_t first_bytes = 0, second_bytes = 0;
-  if (zmx_internal_device_alloc(device, room, &first.p) != 0) return -1;
-  if (zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, d_scan, scanlines, first.p, room, &first_bytes, &frame) != 0) {
-    *outsize = first_bytes;   // (a stream that fits no IDAT: the size it would have taken)
-    return -1;
-  }
-  const void* kept = first.p;
-  size_t kept_bytes = first_bytes;
-  if (first_bytes < zamd::kPngRetryBelow) {
-    zmx_png_color_mode retry;
-    size_t scanlines2 = 0;
-    DeviceBuffer scan2;
-    if (second_try(&retry, &scanlines2, &scan2) != 0) return -1;
-    const zamd::PngFrame frame2 = FrameIn(width, height, retry);
-    const size_t room2 = FileBound(scanlines2);
-    if (zmx_internal_device_alloc(device, room2, &second.p) != 0) return -1;
-    if (zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, scan2.p, scanlines2, second.p, room2, &second_bytes, &frame2) != 0) return -1;
-    if (second_bytes < first_bytes) {
-      kept = second.p;
-      kept_bytes = second_bytes;
-    }
-  }
-  *outsize = kept_bytes;
-  if (kept_bytes > capacity) {
-    return Refuse(w + ": the file takes " + std::to_string(kept_bytes) + " bytes, d_out has " + std::to_string(capacity));
-  }
-  return zmx_internal_device_copy(device, d_out, kept, kept_bytes);
-}
-
-SecondTry SecondTryOf(const OptimizeFront& f, const unsigned char* predefined) {
-  return [&f, predefined](zmx_png_color_mode* retry, size_t* scanlines, DeviceBuffer* scan2) {
-    bool as_is = false;
-    return SecondTryScanlines(f, predefined, retry, &as_is, scanlines, scan2);
-  };
-}
-
-int OptimizeOne(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy, const unsigned char* predefined,
-                unsigned lossy, unsigned char** out, size_t* outsize) {
-  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
-  OptimizeFront f;
-  if (OptimizeFrontHalf(w, options, image, strategy, predefined, lossy, nullptr, &f) != 0) return -1;
-  return FinishOptimize(w, options, f.work.width, f.work.height, f.r.mode, f.scan.p, f.r.scanlines, SecondTryOf(f, predefined), out, outsize);
-}
-
-int OptimizeOneToDevice(const std::string& w, const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                        const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
-  if (!options || !image || !outsize) return Refuse(w + ": null argument");
-  *outsize = 0;
-  const DeviceDest dest{d_out, capacity};
-  OptimizeFront f;
-  if (OptimizeFrontHalf(w, options, image, strategy, predefined, lossy, &dest, &f) != 0) return -1;
-  return FinishOptimizeToDevice(w, options, f.device, f.work.width, f.work.height, f.r.mode, f.scan.p, f.r.scanlines,
-                                SecondTryOf(f, predefined), d_out, capacity, outsize);
-}
-
-}  // namespace
-
-extern "C" int zmx_png_optimize_device_to_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                                                 const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
-                                                 size_t* outsize) {
-  return OptimizeOneToDevice("zmx_png_optimize_device_to_device", options, image, strategy, predefined, lossy, d_out, capacity, outsize);
-}
-
-extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                                       const unsigned char* predefined, unsigned char** out, size_t* outsize) {
-  return OptimizeOne("zmx_png_optimize_device", options, image, strategy, predefined, 0, out, outsize);
-}
-extern "C" int zmx_png_optimize_device_lossy(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
-                                             const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
-  return OptimizeOne("zmx_png_optimize_device_lossy", options, image, strategy, predefined, lossy, out, outsize);
-}
-
-namespace {
-
-// One zmx_compress_device_batch over the scanlines of the images `which` — image which[k]'s at base + start[k], in
-// modes[k] (as_is[k]: the image's own) — into files[k], closed.
-int CompressInto(const ZopfliOptions* options, const std::string& w, const zmx_png_image* images, const std::vector<size_t>& which,
-                 const std::vector<zmx_png_color_mode>& modes, const std::vector<char>& as_is, const unsigned char* base,
-                 const std::vector<size_t>& start, std::vector<File>* files) {
-  const size_t m = which.size();
-  std::vector<const void*> slices(m);
-  std::vector<size_t> sizes(m), filled(m);
-  std::vector<unsigned char*> bytes(m);
-  for (size_t k = 0; k < m; ++k) {
-    slices[k] = base + start[k];
-    sizes[k] = start[k + 1] - start[k];
-    if (as_is[k]) (*files)[k].Begin(images[which[k]]);
-    else (*files)[k].BeginReduced(images[which[k]], modes[k]);
-    bytes[k] = (*files)[k].bytes;
-    filled[k] = (*files)[k].size;
-  }
-  // (a failed call changes none of them: the files still own their arrays)
-  if (zmx_compress_device_batch(options, ZOPFLI_FORMAT_ZLIB, m, slices.data(), sizes.data(), bytes.data(), filled.data()) != 0) return -1;
-  for (size_t k = 0; k < m; ++k) {
-    (*files)[k].bytes = bytes[k];
-    (*files)[k].size = filled[k];
-  }
-  for (size_t k = 0; k < m; ++k) {
-    if (!(*files)[k].Close()) return BadStream(w);
-  }
-  return 0;
-}
-
-}  // namespace
-
-namespace {
-
-int OptimizeBatch(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_image* callers, int strategy, unsigned lossy,
-                  unsigned char** out, size_t* outsize) {
-  if (n == 0) return 0;
-  if (!options || !callers || !out || !outsize) return Refuse(w + ": null argument");
-  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
-  if (strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
-  if (!StrategyOk(strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
-  std::vector<const void*> pixels(n);
-  std::vector<size_t> nbytes(n);
-  std::vector<LossyPlan> plan(n);
-  std::vector<size_t> rstart(n + 1, 0);   // where image i's 8-bit or rewritten pixels begin in their buffer
-  for (size_t i = 0; i < n; ++i) {
-    Geometry g;
-    if (CheckReducible(w + ": image " + std::to_string(i), callers[i], &g) != 0) return -1;
-    pixels[i] = callers[i].d_pixels;
-    nbytes[i] = g.linebytes * g.height;
-    plan[i] = PlanLossy(callers[i], g, lossy, true);
-    rstart[i + 1] = rstart[i] + ((plan[i].bytes + 15) & ~static_cast<size_t>(15));
-  }
-  int device = -1;
-  if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &device) != 0) return -1;
-  DeviceBuffer rewritten;
-  rewritten.device = device;
-  if (rstart[n] != 0 && zmx_internal_device_alloc(device, rstart[n], &rewritten.p) != 0) return -1;
-  // what is encoded: the callers' images, or their 8-bit or rewritten images in `rewritten`
-  std::vector<zmx_png_image> work(callers, callers + n);
-  const zmx_png_image* const images = work.data();
-  // the first files: statistics for all, one buffer, conversion and rows image by image, on one hold of a context
-  std::vector<Reduced> r(n);
-  std::vector<int> chosen(n, strategy);   // (_AUTO: the strategy of each image's own trials)
-  std::vector<size_t> all(n), start(n + 1, 0);
-  std::vector<zmx_png_color_mode> modes(n);
-  std::vector<char> as_is(n);
-  DeviceBuffer scan;
-  scan.device = device;
-  int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    for (size_t i = 0; i < n; ++i) {
-      if (plan[i].bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), &callers[i], plan[i].to8, plan[i].transparent,
-                                                             static_cast<unsigned char*>(rewritten.p) + rstart[i], &work[i]) != 0) {
-        return -1;
-      }
-      if (StatsAndMode(ctx, images[i], &r[i]) != 0) return -1;
-      if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, device, images[i], true, &r[i], nullptr, &chosen[i], nullptr) != 0) return -1;
-      if (r[i].scanlines > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
-      start[i + 1] = start[i] + r[i].scanlines;
-    }
-    if (zmx_internal_device_alloc(device, start[n], &scan.p) != 0) return -1;
-    for (size_t i = 0; i < n; ++i) {
-      if (zmx_internal_png_reduced_scanlines(ctx, &images[i], r[i].as_is ? nullptr : &r[i].mode, chosen[i], kBruteWindow, nullptr,
-                                             static_cast<unsigned char*>(scan.p) + start[i]) != 0) {
-        return -1;
-      }
-    }
-    return 0;
-  }, device);
-  if (rc != 0) return -1;
-  for (size_t i = 0; i < n; ++i) {
-    all[i] = i;
-    modes[i] = r[i].mode;
-    as_is[i] = r[i].as_is ? 1 : 0;
-  }
-  std::vector<File> files(n);
-  if (CompressInto(options, w, images, all, modes, as_is, static_cast<const unsigned char*>(scan.p), start, &files) != 0) return -1;
-  // zopflipng's second try at the small palette files, all of them in one more batch
-  std::vector<size_t> again;
-  for (size_t i = 0; i < n; ++i) {
-    if (r[i].mode.colortype == 3 && files[i].size < zamd::kPngRetryBelow) again.push_back(i);
-  }
-  std::vector<File> seconds(again.size());
-  if (!again.empty()) {
-    const size_t m = again.size();
-    std::vector<zmx_png_color_mode> modes2(m);
-    std::vector<char> as_is2(m);
-    std::vector<size_t> start2(m + 1, 0);
-    for (size_t k = 0; k < m; ++k) {
-      const zmx_png_image& im = images[again[k]];
-      zamd::PngRetryMode(r[again[k]].stats, static_cast<uint64_t>(im.width) * im.height, &modes2[k]);
-      as_is2[k] = SameMode(im, modes2[k]) ? 1 : 0;
-      start2[k + 1] = start2[k] + ScanlinesIn(im, modes2[k]);
-    }
-    DeviceBuffer scan2;
-    scan2.device = device;
-    if (zmx_internal_device_alloc(device, start2[m], &scan2.p) != 0) return -1;
-    rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-      for (size_t k = 0; k < m; ++k) {
-        if (zmx_internal_png_reduced_scanlines(ctx, &images[again[k]], as_is2[k] ? nullptr : &modes2[k], chosen[again[k]], kBruteWindow, nullptr,
-                                               static_cast<unsigned char*>(scan2.p) + start2[k]) != 0) {
-          return -1;
-        }
-      }
-      return 0;
-    }, device);
-    if (rc != 0) return -1;
-    if (CompressInto(options, w, images, again, modes2, as_is2, static_cast<const unsigned char*>(scan2.p), start2, &seconds) != 0) return -1;
-  }
-  // every file made before any out[i] is touched
-  std::vector<File*> kept(n);
-  for (size_t i = 0; i < n; ++i) kept[i] = &files[i];
-  for (size_t k = 0; k < again.size(); ++k) kept[again[k]] = &Smaller(files[again[k]], seconds[k]);
-  for (size_t i = 0; i < n; ++i) kept[i]->GiveTo(&out[i], &outsize[i]);
-  return 0;
-}
-
-}  // namespace
-
-extern "C" int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
-                                             unsigned char** out, size_t* outsize) {
-  return OptimizeBatch("zmx_png_optimize_device_batch", options, n, images, strategy, 0, out, outsize);
-}
-extern "C" int zmx_png_optimize_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
-                                                   unsigned lossy, unsigned char** out, size_t* outsize) {
-  return OptimizeBatch("zmx_png_optimize_device_batch_lossy", options, n, images, strategy, lossy, out, outsize);
 }
 
 // ---- palette, 1/2/4-bit grey and index images (png_index.h; device/zmx_png_index.h)
@@ -990,188 +424,286 @@ int ScanlinesOf(zmx_ctx* ctx, const RowSource& src, const zmx_png_color_mode& mo
                                     d_scan);
 }
 
-// ... with both buffers allocated here; the scanlines stay in *scan
-int ScanlinesOf(zmx_ctx* ctx, int device, const RowSource& src, const zmx_png_color_mode& mode, int strategy, const unsigned char* predefined,
-                DeviceBuffer* scan) {
-  DeviceBuffer room;
-  room.device = scan->device = device;
-  if (zmx_internal_device_alloc(device, RowBytesIn(src.width, mode) * src.height, &room.p) != 0) return -1;
-  if (zmx_internal_device_alloc(device, ScanlinesIn(src.width, src.height, mode), &scan->p) != 0) return -1;
-  return ScanlinesOf(ctx, src, mode, strategy, predefined, room.p, scan->p);
-}
+// ---- the pipeline: Subject, Kind, MakeFront, the finishes
 
-// What the single index entries share: the checks (`dest`: a to-device entry's destination, checked with them) and the
-// first hold of a context, which leaves the first file's scanlines in `scan`.
-struct IndexFront {
-  int device = -1;
-  int strategy = 0;   // the one the rows were made with (_AUTO: the chosen one)
-  IndexPlan plan;
-  size_t scanlines = 0;
-  DeviceBuffer scan;
+// One prepared image.  It is made in place and stays there: `rows` and `stats` point into it.
+struct Subject {
+  uint32_t width = 0, height = 0;
+  RowSource rows;
+  zmx_png_color_mode mode;                       // the first file's
+  const zmx_png_color_stats* stats = nullptr;    // what a second try is made from; null: none competes
+  int strategy = 0;                              // the one the rows are made with (_AUTO: the chosen one)
+  // what the kind keeps alive
+  zmx_png_image work;                            // ColourKind: what is encoded — the caller's image, or its 8-bit or rewritten image
+  zmx_png_color_stats work_stats;                // ... and its statistics, where the mode is reduced
+  std::unique_ptr<IndexPlan> plan;               // IndexKind
+  Subject() = default;
+  Subject(const Subject&) = delete;
+  Subject& operator=(const Subject&) = delete;
 };
 
-int IndexFrontHalf(const std::string& w, const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
-                   const unsigned char* predefined, unsigned lossy, bool optimize, const DeviceDest* dest, IndexFront* f) {
-  if (!options || !image) return Refuse(w + ": null argument");
-  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
-  size_t nbytes = 0;
-  if (CheckIndexImage(w, *image, &nbytes) != 0) return -1;
-  if (!StrategyOk(strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
-  if (CheckPredefined(w, strategy, predefined, image->height) != 0) return -1;
-  if (zmx_internal_device_pointer(w.c_str(), image->d_pixels, nbytes, &f->device) != 0) return -1;
-  if (dest && CheckDest(w, *dest, f->device, 1, &image->d_pixels, &nbytes) != 0) return -1;
-  IndexPlan& plan = f->plan;
-  // (the context is held for the first appearances, the trials, the conversion, the types and the rows only)
-  const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    if (zmx_png_index_use_device(ctx, image, plan.first) != 0) return -1;
-    if (PlanIndex(w, *image, lossy, optimize, &plan) != 0) return -1;
-    const RowSource src = RowsOf(*image, plan.seen);
-    if (strategy == ZMX_PNG_FILTER_AUTO &&
-        ChooseStrategy(ctx, w, f->device, src, plan.mode, optimize ? &plan.stats : nullptr, predefined, &strategy, nullptr) != 0) {
-      return -1;
+// whether zopflipng tries the image a second time, as RGB or RGBA, once its first file has `file_bytes`
+bool SecondTryDue(const Subject& s, size_t file_bytes) { return s.stats && s.mode.colortype == 3 && file_bytes < zamd::kPngRetryBelow; }
+
+// What an entry was asked for, beyond its images.
+struct Call {
+  std::string w;                      // the entry's name
+  const ZopfliOptions* options;
+  int strategy;
+  const unsigned char* predefined;    // the single call's; null in a batch
+  unsigned lossy;
+};
+
+// What a kind's host checks give of image i
+struct Checked {
+  const void* pixels;
+  size_t nbytes;       // the pixels'
+  size_t rewritten;    // of a buffer of the call's own that Prepare fills; 0: none
+  uint32_t height;
+};
+
+// What the images of a call are made of.  `w` is the entry's name, `wi` the same with ": image i" in a batch.
+struct Kind {
+  const void* const given;   // the caller's array of images (null: refused)
+  explicit Kind(const void* images) : given(images) {}
+  virtual ~Kind() = default;
+  // the host checks of image i, before its pointer is looked at
+  virtual int Check(const std::string& wi, unsigned lossy, size_t i, Checked* c) const = 0;
+  // on a held context: image i as a Subject, all but its strategy
+  virtual int Prepare(zmx_ctx* ctx, const std::string& w, const std::string& wi, unsigned lossy, size_t i, void* d_rewritten, Subject* s) const = 0;
+  // whether Scanlines wants d_room: RowBytesIn * height bytes for the image in `mode`
+  virtual bool NeedsRoom() const = 0;
+  // on a held context: the filtered scanlines of `s` in `mode` under s.strategy into d_scan, ScanlinesIn bytes
+  virtual int Scanlines(zmx_ctx* ctx, const Subject& s, const zmx_png_color_mode& mode, const unsigned char* predefined, void* d_room,
+                        void* d_scan) const = 0;
+};
+
+// zmx_png_images: as they are (the encode entries), or with the colour mode reduced (`reduce`: the optimize entries); the
+// _lossy rewrite in front of either.  A conversion goes to the context's pool: no room of the call's own.
+struct ColourKind : Kind {
+  const zmx_png_image* const images;
+  const bool reduce;
+  ColourKind(const zmx_png_image* images_, bool reduce_) : Kind(images_), images(images_), reduce(reduce_) {}
+  int Check(const std::string& wi, unsigned lossy, size_t i, Checked* c) const override {
+    const zmx_png_image& im = images[i];
+    Geometry g;
+    if ((reduce ? CheckReducible(wi, im, &g) : CheckImage(wi, im, &g)) != 0) return -1;
+    const LossyPlan plan = PlanLossy(im, lossy, reduce);
+    if (CheckRewritable(wi, im, plan) != 0) return -1;
+    *c = Checked{im.d_pixels, g.linebytes * g.height, plan.bytes, im.height};
+    return 0;
+  }
+  int Prepare(zmx_ctx* ctx, const std::string& w, const std::string&, unsigned lossy, size_t i, void* d_rewritten, Subject* s) const override {
+    const LossyPlan plan = PlanLossy(images[i], lossy, reduce);
+    s->work = images[i];
+    if (plan.bytes != 0 && zmx_internal_png_lossy_image(ctx, w.c_str(), &images[i], plan.to8, plan.transparent, d_rewritten, &s->work) != 0) return -1;
+    s->width = s->work.width;
+    s->height = s->work.height;
+    s->rows = RowsOf(s->work);
+    s->mode = OwnMode(s->work);
+    if (!reduce) return 0;
+    s->stats = &s->work_stats;
+    return StatsAndMode(ctx, s->work, &s->work_stats, &s->mode);
+  }
+  bool NeedsRoom() const override { return false; }
+  int Scanlines(zmx_ctx* ctx, const Subject& s, const zmx_png_color_mode& mode, const unsigned char* predefined, void*, void* d_scan) const override {
+    if (SameMode(s.work, mode)) {
+      return zmx_internal_png_scanlines(ctx, s.work.d_pixels, RowBytesIn(s.width, mode), s.height, ByteWidthIn(mode), s.strategy, kBruteWindow,
+                                        predefined, d_scan);
     }
-    f->scanlines = ScanlinesIn(image->width, image->height, plan.mode);
-    return ScanlinesOf(ctx, f->device, src, plan.mode, strategy, predefined, &f->scan);
-  }, f->device);
-  f->strategy = strategy;
-  return rc;
-}
-
-// the second try's mode and scanlines, on a second hold
-SecondTry SecondTryOf(const IndexFront& f, const zmx_png_index_image& image, const unsigned char* predefined) {
-  return [&f, &image, predefined](zmx_png_color_mode* retry, size_t* scanlines, DeviceBuffer* scan2) {
-    zamd::PngRetryMode(f.plan.stats, static_cast<uint64_t>(image.width) * image.height, retry);
-    *scanlines = ScanlinesIn(image.width, image.height, *retry);
-    return zamd::OnPooledContext([&](zmx_ctx* ctx) {
-      return ScanlinesOf(ctx, f.device, RowsOf(image, f.plan.seen), *retry, f.strategy, predefined, scan2);
-    }, f.device);
-  };
-}
-
-int IndexOne(const std::string& w, const ZopfliOptions* options, const zmx_png_index_image* image, int strategy, const unsigned char* predefined,
-             unsigned lossy, bool optimize, unsigned char** out, size_t* outsize) {
-  if (!options || !image || !out || !outsize) return Refuse(w + ": null argument");
-  IndexFront f;
-  if (IndexFrontHalf(w, options, image, strategy, predefined, lossy, optimize, nullptr, &f) != 0) return -1;
-  if (optimize) {
-    return FinishOptimize(w, options, image->width, image->height, f.plan.mode, f.scan.p, f.scanlines, SecondTryOf(f, *image, predefined), out,
-                          outsize);
+    return zmx_internal_png_reduced_scanlines(ctx, &s.work, &mode, s.strategy, kBruteWindow, predefined, d_scan);
   }
-  File file;
-  file.BeginIn(image->width, image->height, f.plan.mode);
-  if (zmx_compress_device(options, ZOPFLI_FORMAT_ZLIB, f.scan.p, f.scanlines, &file.bytes, &file.size) != 0) return -1;
-  if (!file.Close()) return BadStream(w);
-  file.GiveTo(out, outsize);
-  return 0;
-}
+};
 
-int IndexOneToDevice(const std::string& w, const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
-                     const unsigned char* predefined, unsigned lossy, bool optimize, void* d_out, size_t capacity, size_t* outsize) {
-  if (!options || !image || !outsize) return Refuse(w + ": null argument");
-  *outsize = 0;
-  const DeviceDest dest{d_out, capacity};
-  IndexFront f;
-  if (IndexFrontHalf(w, options, image, strategy, predefined, lossy, optimize, &dest, &f) != 0) return -1;
-  if (optimize) {
-    return FinishOptimizeToDevice(w, options, f.device, image->width, image->height, f.plan.mode, f.scan.p, f.scanlines,
-                                  SecondTryOf(f, *image, predefined), d_out, capacity, outsize);
+// zmx_png_index_images: one k_png_index_use and the host's plan in place of the statistics — the input's own mode (the
+// index-encode entries) or LodePNG's choice (`optimize`) —, k_png_index_convert into a room of the call's own.
+struct IndexKind : Kind {
+  const zmx_png_index_image* const images;
+  const bool optimize;
+  IndexKind(const zmx_png_index_image* images_, bool optimize_) : Kind(images_), images(images_), optimize(optimize_) {}
+  int Check(const std::string& wi, unsigned, size_t i, Checked* c) const override {
+    size_t nbytes = 0;
+    if (CheckIndexImage(wi, images[i], &nbytes) != 0) return -1;
+    *c = Checked{images[i].d_pixels, nbytes, 0, images[i].height};
+    return 0;
   }
-  const zamd::PngFrame frame = FrameIn(image->width, image->height, f.plan.mode);
-  return zamd::CompressDeviceToDevice(w.c_str(), options, ZOPFLI_FORMAT_ZLIB, f.scan.p, f.scanlines, d_out, capacity, outsize, &frame);
-}
+  int Prepare(zmx_ctx* ctx, const std::string&, const std::string& wi, unsigned lossy, size_t i, void*, Subject* s) const override {
+    const zmx_png_index_image& im = images[i];
+    s->plan.reset(new IndexPlan);
+    if (zmx_png_index_use_device(ctx, &im, s->plan->first) != 0) return -1;
+    if (PlanIndex(wi, im, lossy, optimize, s->plan.get()) != 0) return -1;
+    s->width = im.width;
+    s->height = im.height;
+    s->rows = RowsOf(im, s->plan->seen);
+    s->mode = s->plan->mode;
+    s->stats = optimize ? &s->plan->stats : nullptr;
+    return 0;
+  }
+  bool NeedsRoom() const override { return true; }
+  int Scanlines(zmx_ctx* ctx, const Subject& s, const zmx_png_color_mode& mode, const unsigned char* predefined, void* d_room,
+                void* d_scan) const override {
+    return ScanlinesOf(ctx, s.rows, mode, s.strategy, predefined, d_room, d_scan);
+  }
+};
 
-// Both batches: image by image one k_png_index_use, the host step and one k_png_index_convert on one hold of a context,
-// ONE zmx_compress_device_batch over all scanlines, and for `optimize` one more hold and one more batch for the second tries.
-int IndexBatch(const std::string& w, const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy, unsigned lossy,
-               bool optimize, unsigned char** out, size_t* outsize) {
-  if (n == 0) return 0;
-  if (!options || !images || !out || !outsize) return Refuse(w + ": null argument");
-  if (!LossyOk(lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(lossy));
-  if (strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
-  if (!StrategyOk(strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
+// What the front of a call leaves: every image prepared, image i's filtered scanlines in its first file's mode at
+// scan + start[i] (start[n]: their end).
+struct Front {
+  int device = -1;
+  std::vector<Subject> subjects;
+  std::vector<size_t> start;
+  DeviceBuffer scan, rewritten;
+  const void* Scan(size_t i) const { return static_cast<const unsigned char*>(scan.p) + start[i]; }
+  size_t ScanBytes(size_t i) const { return start[i + 1] - start[i]; }
+};
+
+// The front of a call of n > 0 images, single or batch: the checks (`dest`: a to-device entry's destination, checked with
+// them), the buffers, and the first hold of a context — prepare, the _AUTO choice and the layout image by image, then the
+// rows of all.
+int MakeFront(const Call& c, const Kind& kind, size_t n, bool single, const DeviceDest* dest, Front* f) {
+  const std::string& w = c.w;
+  const auto name = [&](size_t i) { return single ? w : w + ": image " + std::to_string(i); };
+  if (!LossyOk(c.lossy)) return Refuse(w + ": unknown lossy flags " + std::to_string(c.lossy));
+  if (!single) {
+    if (c.strategy == ZMX_PNG_FILTER_PREDEFINED) return Refuse(w + ": ZMX_PNG_FILTER_PREDEFINED is the single call's");
+    if (!StrategyOk(c.strategy, false)) return Refuse(w + ": unknown strategy " + std::to_string(c.strategy));
+  }
   std::vector<const void*> pixels(n);
   std::vector<size_t> nbytes(n);
+  std::vector<size_t> rstart(n + 1, 0);   // where image i's 8-bit or rewritten pixels begin in their buffer
+  uint32_t height = 0;
   for (size_t i = 0; i < n; ++i) {
-    if (CheckIndexImage(w + ": image " + std::to_string(i), images[i], &nbytes[i]) != 0) return -1;
-    pixels[i] = images[i].d_pixels;
+    Checked checked;
+    if (kind.Check(name(i), c.lossy, i, &checked) != 0) return -1;
+    pixels[i] = checked.pixels;
+    nbytes[i] = checked.nbytes;
+    rstart[i + 1] = rstart[i] + RoundUp16(checked.rewritten);
+    height = checked.height;
   }
-  int device = -1;
-  if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &device) != 0) return -1;
-  // (CompressInto's view of the images: their width and height)
-  std::vector<zmx_png_image> dims(n);
-  for (size_t i = 0; i < n; ++i) dims[i] = zmx_png_image{nullptr, images[i].width, images[i].height, 0, 0};
-  std::vector<IndexPlan> plan(n);
-  std::vector<int> chosen(n, strategy);   // (_AUTO: the strategy of each image's own trials)
-  std::vector<size_t> all(n), start(n + 1, 0);
-  std::vector<zmx_png_color_mode> modes(n);
-  const std::vector<char> converted(n, 0);   // (no file is "the image as it is")
-  DeviceBuffer scan, room;
-  scan.device = room.device = device;
-  int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-    size_t most = 0;
+  if (single) {
+    if (!StrategyOk(c.strategy, true)) return Refuse(w + ": unknown strategy " + std::to_string(c.strategy));
+    if (CheckPredefined(w, c.strategy, c.predefined, height) != 0) return -1;
+    if (zmx_internal_device_pointer(w.c_str(), pixels[0], nbytes[0], &f->device) != 0) return -1;
+  } else if (zmx_internal_device_pointers_one_device(w.c_str(), n, pixels.data(), nbytes.data(), &f->device) != 0) {
+    return -1;
+  }
+  const int device = f->device;
+  if (dest && CheckDest(w, *dest, device, n, pixels.data(), nbytes.data()) != 0) return -1;
+  DeviceBuffer room;
+  f->scan.device = f->rewritten.device = room.device = device;
+  if (rstart[n] != 0 && zmx_internal_device_alloc(device, rstart[n], &f->rewritten.p) != 0) return -1;
+  f->subjects = std::vector<Subject>(n);
+  f->start.assign(n + 1, 0);
+  // (one hold of a context for all images, for the device work only; a launch set per image: tools/png_device.py measures
+  // what that costs)
+  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    size_t room_bytes = 0;
     for (size_t i = 0; i < n; ++i) {
-      const std::string wi = w + ": image " + std::to_string(i);
-      if (zmx_png_index_use_device(ctx, &images[i], plan[i].first) != 0) return -1;
-      if (PlanIndex(wi, images[i], lossy, optimize, &plan[i]) != 0) return -1;
-      if (strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, device, RowsOf(images[i], plan[i].seen), plan[i].mode,
-                                                            optimize ? &plan[i].stats : nullptr, nullptr, &chosen[i], nullptr) != 0) {
+      Subject& s = f->subjects[i];
+      if (kind.Prepare(ctx, w, name(i), c.lossy, i, static_cast<unsigned char*>(f->rewritten.p) + rstart[i], &s) != 0) return -1;
+      s.strategy = c.strategy;
+      if (c.strategy == ZMX_PNG_FILTER_AUTO && ChooseStrategy(ctx, w, device, s.rows, s.mode, s.stats, c.predefined, &s.strategy, nullptr) != 0) {
         return -1;
       }
-      const size_t scanlines = ScanlinesIn(images[i].width, images[i].height, plan[i].mode);
-      if (scanlines > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
-      start[i + 1] = start[i] + scanlines;
-      most = std::max(most, scanlines);
+      const size_t scanlines = ScanlinesIn(s.width, s.height, s.mode);
+      if (scanlines > SIZE_MAX - f->start[i]) return Refuse(w + ": the sizes overflow");
+      f->start[i + 1] = f->start[i] + scanlines;
+      room_bytes = std::max(room_bytes, RowBytesIn(s.width, s.mode) * s.height);
     }
-    if (zmx_internal_device_alloc(device, start[n], &scan.p) != 0) return -1;
-    if (zmx_internal_device_alloc(device, most, &room.p) != 0) return -1;
+    if (zmx_internal_device_alloc(device, f->start[n], &f->scan.p) != 0) return -1;
+    if (kind.NeedsRoom() && zmx_internal_device_alloc(device, room_bytes, &room.p) != 0) return -1;
     for (size_t i = 0; i < n; ++i) {
-      if (ScanlinesOf(ctx, RowsOf(images[i], plan[i].seen), plan[i].mode, chosen[i], nullptr, room.p,
-                      static_cast<unsigned char*>(scan.p) + start[i]) != 0) {
-        return -1;
-      }
+      const Subject& s = f->subjects[i];
+      if (kind.Scanlines(ctx, s, s.mode, c.predefined, room.p, static_cast<unsigned char*>(f->scan.p) + f->start[i]) != 0) return -1;
     }
     return 0;
   }, device);
-  if (rc != 0) return -1;
+}
+
+// zopflipng's second try at the small palette files of the subjects `again`: their modes, and on one more hold of a context
+// their scanlines side by side, `again[k]`'s at scan + start[k].
+struct SecondTries {
+  std::vector<zmx_png_color_mode> modes;
+  std::vector<size_t> start;
+  DeviceBuffer scan;
+};
+
+int MakeSecondTries(const Kind& kind, int device, const std::vector<const Subject*>& again, const unsigned char* predefined, SecondTries* t) {
+  const size_t m = again.size();
+  t->modes.resize(m);
+  t->start.assign(m + 1, 0);
+  size_t room_bytes = 0;
+  for (size_t k = 0; k < m; ++k) {
+    const Subject& s = *again[k];
+    zamd::PngRetryMode(*s.stats, static_cast<uint64_t>(s.width) * s.height, &t->modes[k]);
+    t->start[k + 1] = t->start[k] + ScanlinesIn(s.width, s.height, t->modes[k]);
+    room_bytes = std::max(room_bytes, RowBytesIn(s.width, t->modes[k]) * s.height);
+  }
+  DeviceBuffer room;
+  t->scan.device = room.device = device;
+  if (zmx_internal_device_alloc(device, t->start[m], &t->scan.p) != 0) return -1;
+  if (kind.NeedsRoom() && zmx_internal_device_alloc(device, room_bytes, &room.p) != 0) return -1;
+  return zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    for (size_t k = 0; k < m; ++k) {
+      if (kind.Scanlines(ctx, *again[k], t->modes[k], predefined, room.p, static_cast<unsigned char*>(t->scan.p) + t->start[k]) != 0) return -1;
+    }
+    return 0;
+  }, device);
+}
+
+// One zmx_compress_device_batch over the scanlines of the subjects `which` — which[k]'s at base + start[k], in *modes[k] —
+// into files[k], closed.
+int CompressInto(const Call& c, const std::vector<const Subject*>& which, const std::vector<const zmx_png_color_mode*>& modes,
+                 const void* base, const std::vector<size_t>& start, std::vector<File>* files) {
+  const size_t m = which.size();
+  std::vector<const void*> slices(m);
+  std::vector<size_t> sizes(m), filled(m);
+  std::vector<unsigned char*> bytes(m);
+  for (size_t k = 0; k < m; ++k) {
+    slices[k] = static_cast<const unsigned char*>(base) + start[k];
+    sizes[k] = start[k + 1] - start[k];
+    (*files)[k].BeginIn(which[k]->width, which[k]->height, *modes[k]);
+    bytes[k] = (*files)[k].bytes;
+    filled[k] = (*files)[k].size;
+  }
+  // (a failed call changes none of them: the files still own their arrays)
+  if (zmx_compress_device_batch(c.options, ZOPFLI_FORMAT_ZLIB, m, slices.data(), sizes.data(), bytes.data(), filled.data()) != 0) return -1;
+  for (size_t k = 0; k < m; ++k) {
+    (*files)[k].bytes = bytes[k];
+    (*files)[k].size = filled[k];
+  }
+  for (size_t k = 0; k < m; ++k) {
+    if (!(*files)[k].Close()) return BadStream(c.w);
+  }
+  return 0;
+}
+
+// The batch with host output, once the front is made: ONE zmx_compress_device_batch over the first files, one more hold and
+// one more batch for all second tries together (none for a kind without statistics), the smaller of the two handed over.
+int FinishBatch(const Call& c, const Kind& kind, const Front& f, unsigned char** out, size_t* outsize) {
+  const size_t n = f.subjects.size();
+  std::vector<const Subject*> all(n);
+  std::vector<const zmx_png_color_mode*> modes(n);
   for (size_t i = 0; i < n; ++i) {
-    all[i] = i;
-    modes[i] = plan[i].mode;
+    all[i] = &f.subjects[i];
+    modes[i] = &f.subjects[i].mode;
   }
   std::vector<File> files(n);
-  if (CompressInto(options, w, dims.data(), all, modes, converted, static_cast<const unsigned char*>(scan.p), start, &files) != 0) return -1;
+  if (CompressInto(c, all, modes, f.scan.p, f.start, &files) != 0) return -1;
   // zopflipng's second try at the small palette files, all of them in one more batch
   std::vector<size_t> again;
-  for (size_t i = 0; optimize && i < n; ++i) {
-    if (plan[i].mode.colortype == 3 && files[i].size < zamd::kPngRetryBelow) again.push_back(i);
+  for (size_t i = 0; i < n; ++i) {
+    if (SecondTryDue(f.subjects[i], files[i].size)) again.push_back(i);
   }
   std::vector<File> seconds(again.size());
   if (!again.empty()) {
-    const size_t m = again.size();
-    std::vector<zmx_png_color_mode> modes2(m);
-    std::vector<size_t> start2(m + 1, 0);
-    size_t most = 0;
-    for (size_t k = 0; k < m; ++k) {
-      const zmx_png_index_image& im = images[again[k]];
-      zamd::PngRetryMode(plan[again[k]].stats, static_cast<uint64_t>(im.width) * im.height, &modes2[k]);
-      start2[k + 1] = start2[k] + ScanlinesIn(im.width, im.height, modes2[k]);
-      most = std::max(most, start2[k + 1] - start2[k]);
-    }
-    DeviceBuffer scan2, room2;
-    scan2.device = room2.device = device;
-    if (zmx_internal_device_alloc(device, start2[m], &scan2.p) != 0) return -1;
-    if (zmx_internal_device_alloc(device, most, &room2.p) != 0) return -1;
-    rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
-      for (size_t k = 0; k < m; ++k) {
-        if (ScanlinesOf(ctx, RowsOf(images[again[k]], plan[again[k]].seen), modes2[k], chosen[again[k]], nullptr, room2.p,
-                        static_cast<unsigned char*>(scan2.p) + start2[k]) != 0) {
-          return -1;
-        }
-      }
-      return 0;
-    }, device);
-    if (rc != 0) return -1;
-    const std::vector<char> converted2(m, 0);
-    if (CompressInto(options, w, dims.data(), again, modes2, converted2, static_cast<const unsigned char*>(scan2.p), start2, &seconds) != 0) return -1;
+    std::vector<const Subject*> retried(again.size());
+    std::vector<const zmx_png_color_mode*> modes2(again.size());
+    for (size_t k = 0; k < again.size(); ++k) retried[k] = &f.subjects[again[k]];
+    SecondTries t;
+    if (MakeSecondTries(kind, f.device, retried, c.predefined, &t) != 0) return -1;
+    for (size_t k = 0; k < again.size(); ++k) modes2[k] = &t.modes[k];
+    if (CompressInto(c, retried, modes2, t.scan.p, t.start, &seconds) != 0) return -1;
   }
   // every file made before any out[i] is touched
   std::vector<File*> kept(n);
@@ -1181,7 +713,201 @@ int IndexBatch(const std::string& w, const ZopfliOptions* options, size_t n, con
   return 0;
 }
 
+// One file with host output, once the front is made: the file in the subject's mode through zmx_compress_device, the second
+// try where one is due, the smaller of the two handed over.
+int FinishOne(const Call& c, const Kind& kind, const Front& f, unsigned char** out, size_t* outsize) {
+  const Subject& s = f.subjects[0];
+  File file;
+  file.BeginIn(s.width, s.height, s.mode);
+  if (zmx_compress_device(c.options, ZOPFLI_FORMAT_ZLIB, f.Scan(0), f.ScanBytes(0), &file.bytes, &file.size) != 0) return -1;
+  if (!file.Close()) return BadStream(c.w);
+  File second;
+  if (SecondTryDue(s, file.size)) {
+    SecondTries t;
+    if (MakeSecondTries(kind, f.device, {&s}, c.predefined, &t) != 0) return -1;
+    second.BeginIn(s.width, s.height, t.modes[0]);
+    if (zmx_compress_device(c.options, ZOPFLI_FORMAT_ZLIB, t.scan.p, t.start[1], &second.bytes, &second.size) != 0) return -1;
+    if (!second.Close()) return BadStream(c.w);
+    Smaller(file, second).GiveTo(out, outsize);
+    return 0;
+  }
+  file.GiveTo(out, outsize);
+  return 0;
+}
+
+// The same with the file left in device memory: the stream goes zmx_compress_device_to_device's way with the file's frame
+// around it.  Where no second try can be due — no statistics, or a mode other than a palette — the one file goes straight
+// into d_out.  Else which file is kept, and so its size, is known only when the first is made — so the first goes into a
+// buffer of the call's own, the second (where one is due) into another, and ONE device-to-device copy puts the kept file
+// into d_out: every byte of the file is written and none outside it, and a capacity of exactly the kept file's size does.
+int FinishOneToDevice(const Call& c, const Kind& kind, const Front& f, const DeviceDest& dest, size_t* outsize) {
+  const Subject& s = f.subjects[0];
+  const char* const w = c.w.c_str();
+  const int device = f.device;
+  const zamd::PngFrame frame = FrameIn(s.width, s.height, s.mode);
+  if (!SecondTryDue(s, 0)) {
+    return zamd::CompressDeviceToDevice(w, c.options, ZOPFLI_FORMAT_ZLIB, f.Scan(0), f.ScanBytes(0), dest.d_out, dest.capacity, outsize, &frame);
+  }
+  DeviceBuffer first, second;
+  first.device = second.device = device;
+  const size_t room = FileBound(f.ScanBytes(0));
+  size_t first_bytes = 0, second_bytes = 0;
+  if (zmx_internal_device_alloc(device, room, &first.p) != 0) return -1;
+  if (zamd::CompressDeviceToDevice(w, c.options, ZOPFLI_FORMAT_ZLIB, f.Scan(0), f.ScanBytes(0), first.p, room, &first_bytes, &frame) != 0) {
+    *outsize = first_bytes;   // (a stream that fits no IDAT: the size it would have taken)
+    return -1;
+  }
+  const void* kept = first.p;
+  size_t kept_bytes = first_bytes;
+  if (SecondTryDue(s, first_bytes)) {
+    SecondTries t;
+    if (MakeSecondTries(kind, device, {&s}, c.predefined, &t) != 0) return -1;
+    const zamd::PngFrame frame2 = FrameIn(s.width, s.height, t.modes[0]);
+    const size_t room2 = FileBound(t.start[1]);
+    if (zmx_internal_device_alloc(device, room2, &second.p) != 0) return -1;
+    if (zamd::CompressDeviceToDevice(w, c.options, ZOPFLI_FORMAT_ZLIB, t.scan.p, t.start[1], second.p, room2, &second_bytes, &frame2) != 0) return -1;
+    if (second_bytes < first_bytes) {
+      kept = second.p;
+      kept_bytes = second_bytes;
+    }
+  }
+  *outsize = kept_bytes;
+  if (kept_bytes > dest.capacity) {
+    return Refuse(c.w + ": the file takes " + std::to_string(kept_bytes) + " bytes, d_out has " + std::to_string(dest.capacity));
+  }
+  return zmx_internal_device_copy(device, dest.d_out, kept, kept_bytes);
+}
+
+// ---- the four shapes of an entry
+int One(const Call& c, const Kind& kind, unsigned char** out, size_t* outsize) {
+  if (!c.options || !kind.given || !out || !outsize) return Refuse(c.w + ": null argument");
+  Front f;
+  if (MakeFront(c, kind, 1, true, nullptr, &f) != 0) return -1;
+  return FinishOne(c, kind, f, out, outsize);
+}
+
+int OneToDevice(const Call& c, const Kind& kind, void* d_out, size_t capacity, size_t* outsize) {
+  if (!c.options || !kind.given || !outsize) return Refuse(c.w + ": null argument");
+  *outsize = 0;
+  const DeviceDest dest{d_out, capacity};
+  Front f;
+  if (MakeFront(c, kind, 1, true, &dest, &f) != 0) return -1;
+  return FinishOneToDevice(c, kind, f, dest, outsize);
+}
+
+int Batch(const Call& c, const Kind& kind, size_t n, unsigned char** out, size_t* outsize) {
+  if (n == 0) return 0;
+  if (!c.options || !kind.given || !out || !outsize) return Refuse(c.w + ": null argument");
+  Front f;
+  if (MakeFront(c, kind, n, false, nullptr, &f) != 0) return -1;
+  return FinishBatch(c, kind, f, out, outsize);
+}
+
+// The first files left in one arena: zmx_compress_device_batch_packed's plan with a frame per stream.  (For a kind without
+// a second try: the encode entries.)
+int BatchPacked(const Call& c, const Kind& kind, size_t n, void* d_arena, size_t capacity, size_t align, size_t* outoffset, size_t* outsize) {
+  if (n == 0) return 0;
+  if (!c.options || !kind.given || !outoffset || !outsize) return Refuse(c.w + ": null argument");
+  if (!zamd::PackedAlignOk(align)) return Refuse(c.w + ": align " + std::to_string(align) + " is not a power of two from 1 to 4096");
+  const DeviceDest dest{d_arena, capacity};
+  Front f;
+  if (MakeFront(c, kind, n, false, &dest, &f) != 0) return -1;
+  std::vector<const void*> slices(n);
+  std::vector<size_t> sizes(n);
+  std::vector<zamd::PngFrame> frames(n);
+  for (size_t i = 0; i < n; ++i) {
+    slices[i] = f.Scan(i);
+    sizes[i] = f.ScanBytes(i);
+    frames[i] = FrameIn(f.subjects[i].width, f.subjects[i].height, f.subjects[i].mode);
+  }
+  return zamd::CompressDeviceBatchPackedFramed(c.w.c_str(), c.options, n, slices.data(), sizes.data(), frames.data(), d_arena, capacity, align,
+                                               outoffset, outsize);
+}
+
 }  // namespace
+
+// ---- zmx_png_encode_device and its kin: the image's own colour mode
+extern "C" int zmx_png_encode_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                     const unsigned char* predefined, unsigned char** out, size_t* outsize) {
+  return One(Call{"zmx_png_encode_device", options, strategy, predefined, 0}, ColourKind(image, false), out, outsize);
+}
+extern "C" int zmx_png_encode_device_lossy(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                           const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  return One(Call{"zmx_png_encode_device_lossy", options, strategy, predefined, lossy}, ColourKind(image, false), out, outsize);
+}
+extern "C" int zmx_png_encode_device_to_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                               const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
+  return OneToDevice(Call{"zmx_png_encode_device_to_device", options, strategy, predefined, lossy}, ColourKind(image, false), d_out, capacity,
+                     outsize);
+}
+extern "C" int zmx_png_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                           unsigned char** out, size_t* outsize) {
+  return Batch(Call{"zmx_png_encode_device_batch", options, strategy, nullptr, 0}, ColourKind(images, false), n, out, outsize);
+}
+extern "C" int zmx_png_encode_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                                 unsigned lossy, unsigned char** out, size_t* outsize) {
+  return Batch(Call{"zmx_png_encode_device_batch_lossy", options, strategy, nullptr, lossy}, ColourKind(images, false), n, out, outsize);
+}
+extern "C" int zmx_png_encode_device_batch_packed(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                                  unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
+                                                  size_t* outsize) {
+  return BatchPacked(Call{"zmx_png_encode_device_batch_packed", options, strategy, nullptr, lossy}, ColourKind(images, false), n, d_arena,
+                     capacity, align, outoffset, outsize);
+}
+
+// ---- zmx_png_optimize_device and its kin: the colour mode reduced first (png_color_choose.h)
+extern "C" int zmx_png_optimize_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                       const unsigned char* predefined, unsigned char** out, size_t* outsize) {
+  return One(Call{"zmx_png_optimize_device", options, strategy, predefined, 0}, ColourKind(image, true), out, outsize);
+}
+extern "C" int zmx_png_optimize_device_lossy(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                             const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  return One(Call{"zmx_png_optimize_device_lossy", options, strategy, predefined, lossy}, ColourKind(image, true), out, outsize);
+}
+extern "C" int zmx_png_optimize_device_to_device(const ZopfliOptions* options, const zmx_png_image* image, int strategy,
+                                                 const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                                 size_t* outsize) {
+  return OneToDevice(Call{"zmx_png_optimize_device_to_device", options, strategy, predefined, lossy}, ColourKind(image, true), d_out, capacity,
+                     outsize);
+}
+extern "C" int zmx_png_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                             unsigned char** out, size_t* outsize) {
+  return Batch(Call{"zmx_png_optimize_device_batch", options, strategy, nullptr, 0}, ColourKind(images, true), n, out, outsize);
+}
+extern "C" int zmx_png_optimize_device_batch_lossy(const ZopfliOptions* options, size_t n, const zmx_png_image* images, int strategy,
+                                                   unsigned lossy, unsigned char** out, size_t* outsize) {
+  return Batch(Call{"zmx_png_optimize_device_batch_lossy", options, strategy, nullptr, lossy}, ColourKind(images, true), n, out, outsize);
+}
+
+// ---- the index entries, and the host arithmetic they share with tests and tools
+extern "C" int zmx_png_index_encode_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                           const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  return One(Call{"zmx_png_index_encode_device", options, strategy, predefined, lossy}, IndexKind(image, false), out, outsize);
+}
+extern "C" int zmx_png_index_optimize_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                             const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  return One(Call{"zmx_png_index_optimize_device", options, strategy, predefined, lossy}, IndexKind(image, true), out, outsize);
+}
+extern "C" int zmx_png_index_encode_device_to_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                                     const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                                     size_t* outsize) {
+  return OneToDevice(Call{"zmx_png_index_encode_device_to_device", options, strategy, predefined, lossy}, IndexKind(image, false), d_out,
+                     capacity, outsize);
+}
+extern "C" int zmx_png_index_optimize_device_to_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
+                                                       const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
+                                                       size_t* outsize) {
+  return OneToDevice(Call{"zmx_png_index_optimize_device_to_device", options, strategy, predefined, lossy}, IndexKind(image, true), d_out,
+                     capacity, outsize);
+}
+extern "C" int zmx_png_index_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
+                                                 unsigned lossy, unsigned char** out, size_t* outsize) {
+  return Batch(Call{"zmx_png_index_encode_device_batch", options, strategy, nullptr, lossy}, IndexKind(images, false), n, out, outsize);
+}
+extern "C" int zmx_png_index_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
+                                                   unsigned lossy, unsigned char** out, size_t* outsize) {
+  return Batch(Call{"zmx_png_index_optimize_device_batch", options, strategy, nullptr, lossy}, IndexKind(images, true), n, out, outsize);
+}
 
 extern "C" int zmx_png_index_color_stats(const zmx_png_index_image* image, const uint64_t first[256], unsigned lossy, zmx_png_color_stats* out) {
   const std::string w = "zmx_png_index_color_stats";
@@ -1255,33 +981,6 @@ extern "C" size_t zmx_png_index_bound(uint32_t width, uint32_t height, uint32_t 
   return zamd::PngIndexBound(width, height);
 }
 
-extern "C" int zmx_png_index_encode_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
-                                           const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
-  return IndexOne("zmx_png_index_encode_device", options, image, strategy, predefined, lossy, false, out, outsize);
-}
-extern "C" int zmx_png_index_optimize_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
-                                             const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
-  return IndexOne("zmx_png_index_optimize_device", options, image, strategy, predefined, lossy, true, out, outsize);
-}
-extern "C" int zmx_png_index_encode_device_to_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
-                                                     const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
-                                                     size_t* outsize) {
-  return IndexOneToDevice("zmx_png_index_encode_device_to_device", options, image, strategy, predefined, lossy, false, d_out, capacity, outsize);
-}
-extern "C" int zmx_png_index_optimize_device_to_device(const ZopfliOptions* options, const zmx_png_index_image* image, int strategy,
-                                                       const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
-                                                       size_t* outsize) {
-  return IndexOneToDevice("zmx_png_index_optimize_device_to_device", options, image, strategy, predefined, lossy, true, d_out, capacity, outsize);
-}
-extern "C" int zmx_png_index_encode_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
-                                                 unsigned lossy, unsigned char** out, size_t* outsize) {
-  return IndexBatch("zmx_png_index_encode_device_batch", options, n, images, strategy, lossy, false, out, outsize);
-}
-extern "C" int zmx_png_index_optimize_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_index_image* images, int strategy,
-                                                   unsigned lossy, unsigned char** out, size_t* outsize) {
-  return IndexBatch("zmx_png_index_optimize_device_batch", options, n, images, strategy, lossy, true, out, outsize);
-}
-
 // ---- strided, planar, float and 16-bit sources (png_source.h; device/zmx_png_pack.h)
 namespace {
 
@@ -1304,7 +1003,7 @@ int PackSources(const std::string& w, size_t n, const zmx_png_source* sources, c
     if (!msg.empty()) return Refuse(msg);
     p->images[i] = plan.image;
     sizes[i] = plan.nbytes;
-    const size_t slice = (plan.nbytes + 15) & ~static_cast<size_t>(15);
+    const size_t slice = RoundUp16(plan.nbytes);
     if (slice > SIZE_MAX - start[i]) return Refuse(w + ": the sizes overflow");
     start[i + 1] = start[i] + slice;
     extent[i] = reinterpret_cast<const void*>(plan.lo);
@@ -1331,6 +1030,31 @@ int CheckBehindPack(const std::string& w, int strategy, unsigned lossy, bool sin
   if (!StrategyOk(strategy, single)) return Refuse(w + ": unknown strategy " + std::to_string(strategy));
   if (single && source && CheckPredefined(w, strategy, predefined, source->height) != 0) return -1;
   return 0;
+}
+
+// The source entries with host output: `reduce` the optimize ones; `single`: one source, with `predefined`.
+int SourcesToHost(const std::string& w, bool reduce, bool single, const ZopfliOptions* options, size_t n, const zmx_png_source* sources,
+                  int strategy, const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
+  if (n == 0) return 0;
+  if (!options || !sources || !out || !outsize) return Refuse(w + ": null argument");
+  if (CheckBehindPack(w, strategy, lossy, single, predefined, sources) != 0) return -1;
+  Packed p;
+  if (PackSources(w, n, sources, nullptr, &p) != 0) return -1;
+  const Call c{w, options, strategy, predefined, lossy};
+  const ColourKind kind(p.images.data(), reduce);
+  return single ? One(c, kind, out, outsize) : Batch(c, kind, n, out, outsize);
+}
+
+// ... with the file left in device memory
+int SourceToDevice(const std::string& w, bool reduce, const ZopfliOptions* options, const zmx_png_source* source, int strategy,
+                   const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity, size_t* outsize) {
+  if (!options || !source || !outsize) return Refuse(w + ": null argument");
+  *outsize = 0;
+  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
+  const DeviceDest dest{d_out, capacity};
+  Packed p;
+  if (PackSources(w, 1, source, &dest, &p) != 0) return -1;
+  return OneToDevice(Call{w, options, strategy, predefined, lossy}, ColourKind(p.images.data(), reduce), d_out, capacity, outsize);
 }
 
 }  // namespace
@@ -1362,65 +1086,29 @@ extern "C" size_t zmx_png_source_batch_bound(size_t n, const zmx_png_source* sou
 
 extern "C" int zmx_png_encode_source_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
                                             const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
-  const std::string w = "zmx_png_encode_source_device";
-  if (!options || !source || !out || !outsize) return Refuse(w + ": null argument");
-  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
-  Packed p;
-  if (PackSources(w, 1, source, nullptr, &p) != 0) return -1;
-  return EncodeOne(w, options, &p.images[0], strategy, predefined, lossy, out, outsize);
+  return SourcesToHost("zmx_png_encode_source_device", false, true, options, 1, source, strategy, predefined, lossy, out, outsize);
 }
 extern "C" int zmx_png_optimize_source_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
                                               const unsigned char* predefined, unsigned lossy, unsigned char** out, size_t* outsize) {
-  const std::string w = "zmx_png_optimize_source_device";
-  if (!options || !source || !out || !outsize) return Refuse(w + ": null argument");
-  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
-  Packed p;
-  if (PackSources(w, 1, source, nullptr, &p) != 0) return -1;
-  return OptimizeOne(w, options, &p.images[0], strategy, predefined, lossy, out, outsize);
+  return SourcesToHost("zmx_png_optimize_source_device", true, true, options, 1, source, strategy, predefined, lossy, out, outsize);
 }
 extern "C" int zmx_png_encode_source_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
                                                   unsigned lossy, unsigned char** out, size_t* outsize) {
-  const std::string w = "zmx_png_encode_source_device_batch";
-  if (n == 0) return 0;
-  if (!options || !sources || !out || !outsize) return Refuse(w + ": null argument");
-  if (CheckBehindPack(w, strategy, lossy, false, nullptr, nullptr) != 0) return -1;
-  Packed p;
-  if (PackSources(w, n, sources, nullptr, &p) != 0) return -1;
-  return EncodeBatch(w, options, n, p.images.data(), strategy, lossy, out, outsize);
+  return SourcesToHost("zmx_png_encode_source_device_batch", false, false, options, n, sources, strategy, nullptr, lossy, out, outsize);
 }
 extern "C" int zmx_png_optimize_source_device_batch(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
                                                     unsigned lossy, unsigned char** out, size_t* outsize) {
-  const std::string w = "zmx_png_optimize_source_device_batch";
-  if (n == 0) return 0;
-  if (!options || !sources || !out || !outsize) return Refuse(w + ": null argument");
-  if (CheckBehindPack(w, strategy, lossy, false, nullptr, nullptr) != 0) return -1;
-  Packed p;
-  if (PackSources(w, n, sources, nullptr, &p) != 0) return -1;
-  return OptimizeBatch(w, options, n, p.images.data(), strategy, lossy, out, outsize);
+  return SourcesToHost("zmx_png_optimize_source_device_batch", true, false, options, n, sources, strategy, nullptr, lossy, out, outsize);
 }
 extern "C" int zmx_png_encode_source_device_to_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
                                                       const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
                                                       size_t* outsize) {
-  const std::string w = "zmx_png_encode_source_device_to_device";
-  if (!options || !source || !outsize) return Refuse(w + ": null argument");
-  *outsize = 0;
-  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
-  const DeviceDest dest{d_out, capacity};
-  Packed p;
-  if (PackSources(w, 1, source, &dest, &p) != 0) return -1;
-  return EncodeOneToDevice(w, options, &p.images[0], strategy, predefined, lossy, d_out, capacity, outsize);
+  return SourceToDevice("zmx_png_encode_source_device_to_device", false, options, source, strategy, predefined, lossy, d_out, capacity, outsize);
 }
 extern "C" int zmx_png_optimize_source_device_to_device(const ZopfliOptions* options, const zmx_png_source* source, int strategy,
                                                         const unsigned char* predefined, unsigned lossy, void* d_out, size_t capacity,
                                                         size_t* outsize) {
-  const std::string w = "zmx_png_optimize_source_device_to_device";
-  if (!options || !source || !outsize) return Refuse(w + ": null argument");
-  *outsize = 0;
-  if (CheckBehindPack(w, strategy, lossy, true, predefined, source) != 0) return -1;
-  const DeviceDest dest{d_out, capacity};
-  Packed p;
-  if (PackSources(w, 1, source, &dest, &p) != 0) return -1;
-  return OptimizeOneToDevice(w, options, &p.images[0], strategy, predefined, lossy, d_out, capacity, outsize);
+  return SourceToDevice("zmx_png_optimize_source_device_to_device", true, options, source, strategy, predefined, lossy, d_out, capacity, outsize);
 }
 extern "C" int zmx_png_encode_source_device_batch_packed(const ZopfliOptions* options, size_t n, const zmx_png_source* sources, int strategy,
                                                          unsigned lossy, void* d_arena, size_t capacity, size_t align, size_t* outoffset,
@@ -1433,5 +1121,6 @@ extern "C" int zmx_png_encode_source_device_batch_packed(const ZopfliOptions* op
   const DeviceDest dest{d_arena, capacity};
   Packed p;
   if (PackSources(w, n, sources, &dest, &p) != 0) return -1;
-  return EncodeBatchPacked(w, options, n, p.images.data(), strategy, lossy, d_arena, capacity, align, outoffset, outsize);
+  return BatchPacked(Call{w, options, strategy, nullptr, lossy}, ColourKind(p.images.data(), false), n, d_arena, capacity, align, outoffset,
+                     outsize);
 }
