@@ -1205,6 +1205,89 @@ int zmx_inflate_device_batch(ZopfliFormat format, size_t n, const void* const* d
 /* ... of one stream; *outsize as zmx_inflate_result.outsize. */
 int zmx_inflate_device(ZopfliFormat format, const void* d_in, size_t insize, void* d_out, size_t capacity, size_t* outsize);
 
+/* ---- PNG decode on the device: PNG files in device memory decoded into device memory — this library's *_to_device
+ * output, a dataset shard copied up as it lies on disk, tiles from another rank.  Made for many small files in one call:
+ * k_png_chunks walks the chunks of all files in one launch (a lane a file), the IDAT streams go through k_inflate (one
+ * wavefront a stream: a single large image is bound by that kernel's one-wave rate, see README), the chunks' CRC-32s and
+ * the streams' Adler-32s through zmx_checksum_device's kernels, and k_png_unfilter (device/zmx_png_decode.h, one wavefront
+ * an image) undoes the five scanline filters and writes the pixels.  No byte of a file, of its stream or of its pixels
+ * visits the host: what comes down is 88 bytes a file of chunk records, 24 a checked chunk, 32 a stream of inflate
+ * results, 4 a checksum, 8 a file of unfilter results and 1 KiB a file of palettes when a file has a PLTE.
+ * A file is valid exactly where LodePNG's lodepng_decode with default settings accepts it, but:
+ *   - Adam7 files are recognised and not decoded (ZMX_PNG_DECODE_INTERLACE);
+ *   - ancillary chunks other than tRNS are skipped unread, so a file LodePNG refuses only for the CONTENTS (or the CRC) of
+ *     a gAMA, tEXt ... chunk is accepted here;
+ *   - of several tRNS chunks behind one PLTE the last alone holds.
+ * Bytes after IEND are no error; IDATs need not be adjacent and may be empty.
+ * Out of scope: Adam7, the contents of ancillary chunks (gamma, ICC, text), output other than the two modes below (no
+ * 16-bit RGBA, no little-endian samples, no float), APNG, a faster single large stream, and libzopflipng_amd.so, which
+ * keeps LodePNG's decoder.  How a file ended (the order is the order the checks are made in): */
+#define ZMX_PNG_DECODE_OK 0
+#define ZMX_PNG_DECODE_SIGNATURE 1   /* a bad signature, or a file shorter than 33 bytes */
+#define ZMX_PNG_DECODE_IHDR 2        /* not IHDR first or its length not 13; width or height 0; an illegal colour type and
+                                        depth; a compression or filter method not 0; interlace above 1 */
+#define ZMX_PNG_DECODE_INTERLACE 3   /* interlace method 1, in a file whose chunks are in order */
+#define ZMX_PNG_DECODE_CHUNK 4       /* no room for a chunk's 12 bytes before IEND; a length above 2^31 - 1; a chunk that
+                                        runs past the file's end */
+#define ZMX_PNG_DECODE_CRITICAL 5    /* an unknown critical chunk */
+#define ZMX_PNG_DECODE_CRC 6         /* the stored CRC-32 of IHDR, a PLTE, a tRNS, an IDAT or IEND is not its type's and data's */
+#define ZMX_PNG_DECODE_PLTE 7        /* colour type 3 without PLTE; 0 or more than 256 entries */
+#define ZMX_PNG_DECODE_TRNS 8        /* longer than the palette (so also in front of PLTE); not 2 bytes for grey, 6 for RGB;
+                                        present for colour types 4 and 6 */
+#define ZMX_PNG_DECODE_STREAM 9      /* the IDAT bytes are no valid zlib stream (detail: the ZMX_INFLATE_*, CHECKSUM for the
+                                        Adler-32); no IDAT byte at all: ZMX_INFLATE_TRUNCATED */
+#define ZMX_PNG_DECODE_SIZE 10       /* the stream does not decode to exactly height * (1 + linebytes) bytes */
+#define ZMX_PNG_DECODE_FILTER 11     /* a row's filter byte is above 4 (detail: the first such row) */
+#define ZMX_PNG_DECODE_CAPACITY 12   /* the pixels take more than capacity[i]: outsize says how much; nothing is stored */
+
+#define ZMX_PNG_DECODE_OWN 0    /* the file's own colour type and depth, in the layout the encode entries read:
+                                   zmx_png_image.d_pixels for colour types 0, 2, 4, 6 at 8 or 16 bits (16-bit samples
+                                   big-endian), zmx_png_index_image.d_pixels for palette images and grey below 8 bits (rows
+                                   of (width * bitdepth + 7) / 8 bytes, the padding bits of a row's last byte zero) */
+#define ZMX_PNG_DECODE_RGBA8 1  /* 4 * width * height bytes, what lodepng_decode32 gives: the palette with its tRNS alpha
+                                   (an index at or above palettesize: 0, 0, 0, 255), grey replicated, low-bit grey scaled
+                                   by v * 255 / (2^depth - 1), the high byte of 16-bit samples, alpha 0 for a pixel equal to
+                                   the tRNS key at full depth */
+
+typedef struct {
+  uint32_t status;        /* a ZMX_PNG_DECODE_* */
+  uint32_t detail;        /* _STREAM: the ZMX_INFLATE_*; _CRC, _CHUNK, _CRITICAL, _PLTE, _TRNS: the chunk's number in the
+                             file (IHDR is 0); _FILTER: the row */
+  uint32_t width, height, colortype, bitdepth, interlace;
+  uint32_t palettesize;   /* entries of PLTE (0 without one) */
+  uint32_t has_key, key_r, key_g, key_b;   /* tRNS of colour types 0 and 2, at the file's depth */
+  uint64_t outsize;       /* bytes the pixels take in the asked mode (zmx_png_info_device: _OWN) */
+  uint64_t outsize_own, outsize_rgba8;     /* ... in either mode */
+  unsigned char palette[1024];  /* r, g, b, a per entry; alpha from tRNS, 255 where it is short */
+} zmx_png_decode_result;
+
+/* The chunk walk alone: everything of the results but the pixels, for n files d_file[i][0, filesize[i]) on one of the
+ * library's devices.  The chunks' CRCs are compared; the stream is not read.  Returns and refuses as the decode entries. */
+int zmx_png_info_device(size_t n, const void* const* d_file, const size_t* filesize, zmx_png_decode_result* results);
+/* The decode on a context the caller holds: file i's pixels in `mode` go to d_out[i][0, capacity[i]), all plain memory of
+ * the context's device.  A null d_out[i] (or a null d_out) is the size-only mode: the walk, the CRCs and the stream's size
+ * check (k_inflate's size-only mode: the Adler-32 is not compared), nothing stored.  Refused (ZMX_ERR_REFUSED) before
+ * anything runs: an unknown mode, a null array, a pointer that is not device memory of the context's device, a range that
+ * leaves its allocation, a destination that shares a byte with a file or with another destination (the message names the
+ * index); and after the walk, before any stream is read: a header whose scanlines take 2^40 bytes or more.  Returns 0
+ * when every file is ZMX_PNG_DECODE_OK (n = 0: at once); else -1 with every result filled in: zmx_last_error() names the
+ * first failing index and its status, zmx_last_error_class() is ZMX_ERR_REFUSED for _CAPACITY, else ZMX_ERR_DATA.  Files
+ * beside a bad one decode normally.  What was written of an image that ends _FILTER is unspecified, but inside its
+ * destination.  `hooks` may be null; tests use it. */
+typedef struct {
+  int force_wide;          /* every image takes the wide path (the band carry through global memory, a launch a band) */
+  uint32_t idat_capacity;  /* chunk entries a file in the first walk (0: the library's own, 8) */
+} zmx_png_decode_hooks;
+int zmx_png_decode_device_ctx(zmx_ctx* ctx, int mode, size_t n, const void* const* d_file, const size_t* filesize,
+                              void* const* d_out, const size_t* capacity, zmx_png_decode_result* results,
+                              const zmx_png_decode_hooks* hooks);
+/* The same on a context from the library's pool; all ranges must lie on one of the library's devices.
+ * zmx_last_input_traffic()[0] and zmx_last_output_traffic()[0] are 0: nothing of a file or of its pixels crosses. */
+int zmx_png_decode_device_batch(int mode, size_t n, const void* const* d_file, const size_t* filesize, void* const* d_out,
+                                const size_t* capacity, zmx_png_decode_result* results);
+/* ... of one file. */
+int zmx_png_decode_device(int mode, const void* d_file, size_t filesize, void* d_out, size_t capacity, zmx_png_decode_result* result);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -504,6 +504,175 @@ def inflate_device(stream, format="gzip", out=None, size=None, lib=None):
         raise CapacityError(str(e), e.needed[0]) from None
 
 
+PNG_DECODE_STATUS = ["OK", "SIGNATURE", "IHDR", "INTERLACE", "CHUNK", "CRITICAL", "CRC", "PLTE", "TRNS", "STREAM", "SIZE", "FILTER",
+                     "CAPACITY"]   # ZMX_PNG_DECODE_*
+PNG_DECODE_OK, PNG_DECODE_CAPACITY = 0, 12
+PNG_DECODE_OWN, PNG_DECODE_RGBA8 = 0, 1
+
+
+class PngDecodeResult(ctypes.Structure):
+    """zmx_png_decode_result: what a decode or info call says of one file."""
+    _fields_ = [("status", ctypes.c_uint32), ("detail", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("colortype", ctypes.c_uint32), ("bitdepth", ctypes.c_uint32), ("interlace", ctypes.c_uint32), ("palettesize", ctypes.c_uint32),
+                ("has_key", ctypes.c_uint32), ("key_r", ctypes.c_uint32), ("key_g", ctypes.c_uint32), ("key_b", ctypes.c_uint32),
+                ("outsize", ctypes.c_uint64), ("outsize_own", ctypes.c_uint64), ("outsize_rgba8", ctypes.c_uint64),
+                ("palette_bytes", ctypes.c_ubyte * 1024)]
+
+    @property
+    def palette(self):
+        """the palette's r, g, b, a bytes, four an entry (empty without a PLTE)"""
+        return bytes(self.palette_bytes[:4 * int(self.palettesize)])
+
+    @property
+    def key(self):
+        """the tRNS key of colour types 0 and 2 as (r, g, b) at the file's depth, or None"""
+        return (int(self.key_r), int(self.key_g), int(self.key_b)) if self.has_key else None
+
+    @property
+    def linebytes(self):
+        return int(self.outsize_own) // max(int(self.height), 1)
+
+    def astuple(self):
+        return tuple(int(getattr(self, name)) for name, _ in self._fields_[:15]) + (bytes(self.palette_bytes),)
+
+    def own_shape(self):
+        """the shape of the OWN mode's uint8 tensor: (H, linebytes) for palette images and grey below 8 bits, else
+        (H, W, channels * bitdepth / 8)"""
+        if self.colortype == 3 or self.bitdepth < 8:
+            return (int(self.height), self.linebytes)
+        return (int(self.height), int(self.width), self.linebytes // int(self.width))
+
+
+class PngDecodeError(RuntimeError):
+    """png_decode_device*, png_info_device: file `index` is no PNG the library decodes — `status` (a ZMX_PNG_DECODE_* number;
+    PNG_DECODE_STATUS names it) with its `detail`.  `results`: the PngDecodeResult of every file of the call."""
+
+    def __init__(self, index, status, detail, message="", results=None):
+        super().__init__(message or f"file {index}: ZMX_PNG_DECODE_{PNG_DECODE_STATUS[status] if status < len(PNG_DECODE_STATUS) else status}")
+        self.index, self.status, self.detail = index, status, detail
+        self.results = results or []
+
+
+def _png_decode_mode(mode):
+    if isinstance(mode, str):
+        return {"own": PNG_DECODE_OWN, "rgba8": PNG_DECODE_RGBA8}[mode]
+    return int(mode)
+
+
+def _png_decode_call(lib, fn, who, ctx_args, mode, files, outs, tail=()):
+    """One decode entry: `mode` None for the info entry (no mode, no destinations); `outs` None for the size-only mode, else
+    a list of tensors, (pointer, capacity) pairs or None.  Returns (rc, results)."""
+    ptrs, sizes = _device_ranges(files)
+    n = len(ptrs)
+    if outs is not None and len(outs) != n:
+        raise ValueError(f"{n} files, but {len(outs)} destinations")
+    results = (PngDecodeResult * max(n, 1))()
+    P, sz, vp = ctypes.POINTER, ctypes.c_size_t, ctypes.c_void_p
+    args = list(ctx_args)
+    types = [vp] * len(ctx_args)
+    if mode is not None:
+        args.append(_png_decode_mode(mode))
+        types.append(ctypes.c_int)
+    args += [n, (vp * max(n, 1))(*ptrs), (sz * max(n, 1))(*sizes)]
+    types += [sz, P(vp), P(sz)]
+    if mode is not None:
+        out_ptrs, capacities = [None] * n, [0] * n
+        if outs is not None:
+            given = [i for i in range(n) if outs[i] is not None]
+            got_ptrs, got_caps = _device_ranges([outs[i] for i in given])
+            for i, p, c in zip(given, got_ptrs, got_caps):
+                out_ptrs[i], capacities[i] = p or 1, c
+        args += [(vp * max(n, 1))(*out_ptrs) if outs is not None else None, (sz * max(n, 1))(*capacities)]
+        types += [P(vp), P(sz)]
+    fn.argtypes = types + [P(PngDecodeResult)] + [t for t, _ in tail]
+    fn.restype = ctypes.c_int
+    rc = fn(*args, results, *[v for _, v in tail])
+    found = [results[i] for i in range(n)]
+    if rc != 0 and all(r.status == PNG_DECODE_OK for r in found):
+        raise RuntimeError(who + ": " + (lib.zmx_last_error() or b"").decode())
+    return rc, found
+
+
+def _png_decode_raise(lib, who, results, single):
+    """The error of a failed decode call: CapacityError where the first failing file only lacks room, else PngDecodeError."""
+    message = who + ": " + (lib.zmx_last_error() or b"").decode()
+    index = next(i for i, r in enumerate(results) if r.status != PNG_DECODE_OK)
+    r = results[index]
+    if r.status == PNG_DECODE_CAPACITY:
+        raise CapacityError(message, int(r.outsize) if single else [int(x.outsize) for x in results])
+    raise PngDecodeError(index, int(r.status), int(r.detail), message, results)
+
+
+def png_info_device(files, lib=None, check=True):
+    """zmx_png_info_device: the chunk walk of every PNG file of `files` (uint8 tensors or (integer device pointer, nbytes)
+    pairs, all on one device), the chunks' CRCs compared, nothing decoded.  Returns the list of PngDecodeResult — width,
+    height, colortype, bitdepth, interlace, palette, key, status, the sizes of both modes.  Raises PngDecodeError for the
+    first file that is none (`check` False: returns the results whatever their statuses)."""
+    lib = lib or library()
+    rc, results = _png_decode_call(lib, lib.zmx_png_info_device, "zmx_png_info_device", [], None, files, None)
+    if rc != 0 and check:
+        _png_decode_raise(lib, "zmx_png_info_device", results, False)
+    return results
+
+
+def _png_decode_views(mode, results, outs):
+    made = []
+    rgba = _png_decode_mode(mode) == PNG_DECODE_RGBA8
+    for r, out in zip(results, outs):
+        if isinstance(out, (tuple, list)):
+            made.append((int(out[0]), int(r.outsize)))
+            continue
+        shape = (int(r.height), int(r.width), 4) if rgba else r.own_shape()
+        made.append(out.view(-1)[:int(r.outsize)].view(shape))
+    return made
+
+
+def png_decode_device_batch(files, mode="rgba8", outs=None, lib=None):
+    """zmx_png_decode_device_batch: every PNG file of `files` (uint8 tensors or (integer device pointer, nbytes) pairs, all on
+    one device) decoded into device memory: the chunk walk, the inflate and the unfilter on the device, no byte on the host.
+    `mode`: "own" — the file's colour type and depth in the layout the encode entries read — or "rgba8".  With `outs` (as
+    many contiguous tensors or (pointer, capacity) pairs) file i goes to outs[i]; without, one png_info_device round sizes
+    the tensors.  Returns (infos, tensors): uint8 tensors shaped (H, W, 4) for "rgba8"; for "own" (H, linebytes) for palette
+    and low-bit images and (H, W, channels * depth / 8) otherwise ((pointer, size) pairs where `outs` holds pairs).  Raises
+    PngDecodeError for the first bad file (all results in `.results`), CapacityError (`needed`: the list of sizes) where
+    one does not fit, RuntimeError for a refused pointer or a device failure."""
+    lib = lib or library()
+    if outs is None:
+        import torch
+        infos = png_info_device(files, lib)
+        key = "outsize_rgba8" if _png_decode_mode(mode) == PNG_DECODE_RGBA8 else "outsize_own"
+        devices = [f.device for f in files if not isinstance(f, (tuple, list))]
+        outs = [torch.empty(int(getattr(r, key)), dtype=torch.uint8, device=devices[0] if devices else "cuda") for r in infos]
+    rc, results = _png_decode_call(lib, lib.zmx_png_decode_device_batch, "zmx_png_decode_device_batch", [], mode, files, outs)
+    if rc != 0:
+        _png_decode_raise(lib, "zmx_png_decode_device_batch", results, False)
+    return results, _png_decode_views(mode, results, outs)
+
+
+def png_decode_device(file, mode="rgba8", out=None, lib=None):
+    """png_decode_device_batch of one file.  Returns (info, tensor); CapacityError's `needed` is the size."""
+    try:
+        infos, made = png_decode_device_batch([file], mode, None if out is None else [out], lib)
+    except CapacityError as e:
+        raise CapacityError(str(e), e.needed[0]) from None
+    return infos[0], made[0]
+
+
+def png_decode_size_device(files, mode="rgba8", lib=None):
+    """zmx_png_decode_device_batch in its size-only mode: the walk, the CRCs and the stream's size check, nothing stored (the
+    Adler-32 is not compared).  Returns the list of PngDecodeResult; raises PngDecodeError."""
+    lib = lib or library()
+    rc, results = _png_decode_call(lib, lib.zmx_png_decode_device_batch, "zmx_png_decode_device_batch", [], mode, files, None)
+    if rc != 0:
+        _png_decode_raise(lib, "zmx_png_decode_device_batch", results, False)
+    return results
+
+
+class PngDecodeHooks(ctypes.Structure):
+    """zmx_png_decode_hooks."""
+    _fields_ = [("force_wide", ctypes.c_int), ("idat_capacity", ctypes.c_uint32)]
+
+
 class PngImage(ctypes.Structure):
     """zmx_png_image"""
     _fields_ = [("d_pixels", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
@@ -1527,6 +1696,17 @@ class Context:
         entries; None: the size-only mode).  No checksum is compared.  Returns the list of InflateResult, whatever the
         streams' statuses; raises RuntimeError where the call itself is refused or the device fails."""
         return _inflate_call(self.lib, self.lib.zmx_inflate_device_ctx, "zmx_inflate_device_ctx", [self.handle], format, streams, outs)[1]
+
+    def png_decode_device(self, files, mode="rgba8", outs=None, force_wide=False, idat_capacity=None):
+        """zmx_png_decode_device_ctx: the decode on this context — `files` (uint8 tensors or (integer device pointer, nbytes)
+        pairs in memory of the context's device) into `outs` (tensors, (pointer, capacity) pairs or None entries; None: the
+        size-only mode).  Two hooks for tests: `force_wide` sends every image through the wide path (the band carry in
+        global memory, a launch a band), `idat_capacity` sets the chunk entries a file has in the first walk.  Returns the
+        list of PngDecodeResult, whatever the files' statuses; raises RuntimeError where the call itself is refused or the
+        device fails."""
+        hooks = PngDecodeHooks(1 if force_wide else 0, int(idat_capacity or 0))
+        return _png_decode_call(self.lib, self.lib.zmx_png_decode_device_ctx, "zmx_png_decode_device_ctx", [self.handle], mode, files, outs,
+                                tail=[(ctypes.POINTER(PngDecodeHooks), ctypes.byref(hooks))])[1]
 
     def build_tables(self, blocks, parent=None, matches_only=False):
         """zmx_tables_build, zmx_tables_build_matches (no DP rows: for the greedy pass and as a parent), or

@@ -33,6 +33,8 @@
 #include "zmx_checksum_device.h"   // ... of any device memory, finished on the device
 #define ZMX_INFLATE_KERNELS
 #include "zmx_inflate.h"     // k_inflate: deflate, zlib and gzip streams decoded, a wave a stream
+#define ZMX_PNG_DECODE_KERNELS
+#include "zmx_png_decode.h"  // k_png_chunks, k_png_unfilter: a PNG's chunks walked, its scanlines unfiltered, a wave an image
 #include "zmx_trace.h"       // the walk back over length_array, in segments
 #include "zmx_greedy.h"      // the greedy parse, same segmentation
 #include "zmx_png.h"         // LodePNG's MINSUM / ENTROPY filter choice
@@ -61,6 +63,7 @@
 #include "../host/deal.h"
 #include "../host/entry_checks.h"
 #include "../host/inflate_plan.h"
+#include "../host/png_decode_plan.h"
 #include "../host/png_color_choose.h"
 #include "../host/png_index.h"
 #include "../host/png_brute_launch.h"
@@ -82,6 +85,7 @@
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
 #include "drv_checksum_device.h"   // zmx_checksum_device, the seal of a PNG left in device memory
 #include "drv_inflate.h"     // k_inflate's launch, zmx_inflate_device_ctx
+#include "drv_png_decode.h"  // the PNG decode: the run every entry shares, zmx_png_decode_device_ctx
 #include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion, index images, LodePNG's zlib sizes
 #include "drv_png_pack.h"    // zmx_png_pack_device
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries

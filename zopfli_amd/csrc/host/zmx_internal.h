@@ -117,6 +117,16 @@ int zmx_internal_checksum_seal(zmx_ctx* ctx, int kind, size_t n, const void* con
 // down.  0, or -1 with the error set (a device failure: a stream's status is no error of the run).
 int zmx_internal_inflate_run(zmx_ctx* ctx, int format, size_t n, const zamd::InflateJob* jobs, zmx_inflate_result* results);
 
+// ---- PNG decode on the device (png_decode.cc)
+// The whole decode of n <= 2^24 files whose ranges the caller has checked — memory of the context's device, the destinations
+// apart from the files and from each other —: k_png_chunks, the chunks' CRC-32s, the gather of split IDATs, k_inflate, the
+// Adler-32s, k_png_unfilter (device/drv_png_decode.h says what comes down).  info_only: the walk and the CRCs alone.
+// `hooks` may be null.  Every result is filled in; 0, or -1 with the error set, its message starting with `who` (a device
+// failure or a refusal: a file's status is no error of the run).
+int zmx_internal_png_decode_run(zmx_ctx* ctx, const char* who, int mode, int info_only, size_t n, const void* const* d_file,
+                                const size_t* filesize, void* const* d_out, const size_t* capacity, zmx_png_decode_result* results,
+                                const zmx_png_decode_hooks* hooks);
+
 // ---- a PNG from an image in device memory (png_encode.cc)
 // The filter types of `strategy` (a ZMX_PNG_FILTER_*; _BRUTE with window `windowsize`; _PREDEFINED: the `height` host
 // bytes at `predefined`, each at most 4) and then the filtered scanlines of d_image (zmx_png_filter_rows_device) into
@@ -195,6 +205,12 @@ ZMX_INTERNAL_EXPORT int zmx_internal_png_brute_sizes(zmx_ctx* ctx, const unsigne
 ZMX_INTERNAL_EXPORT void zmx_internal_checksum_device_ms(double out[2]);
 // The same for the calling thread's last k_inflate launch (an inflate call's last round).  For tools/inflate_device.py.
 ZMX_INTERNAL_EXPORT double zmx_internal_inflate_ms(void);
+// The same for the calling thread's last PNG decode: k_png_chunks (all its launches), k_png_unfilter (likewise).  For
+// tools/png_decode.py.
+ZMX_INTERNAL_EXPORT void zmx_internal_png_decode_ms(double out[2]);
+// The same call by the host's clock, whether kernel timing is on or not: the walk with its records down, the chunks'
+// CRC-32s, the gather and k_inflate, the Adler-32s, k_png_unfilter with its results down.
+ZMX_INTERNAL_EXPORT void zmx_internal_png_decode_phase_ms(double out[5]);
 // The same for the calling thread's last zmx_png_pack_device: k_png_pack.  For tools/png_source.py.
 ZMX_INTERNAL_EXPORT double zmx_internal_png_pack_ms(void);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
