@@ -1219,9 +1219,10 @@ int zmx_inflate_device(ZopfliFormat format, const void* d_in, size_t insize, voi
  *     a gAMA, tEXt ... chunk is accepted here;
  *   - of several tRNS chunks behind one PLTE the last alone holds.
  * Bytes after IEND are no error; IDATs need not be adjacent and may be empty.
- * Out of scope: Adam7, the contents of ancillary chunks (gamma, ICC, text), output other than the two modes below (no
- * 16-bit RGBA, no little-endian samples, no float), APNG, a faster single large stream, and libzopflipng_amd.so, which
- * keeps LodePNG's decoder.  How a file ended (the order is the order the checks are made in): */
+ * Out of scope: Adam7, the contents of ancillary chunks (gamma, ICC, text), APNG, a faster single large stream, and
+ * libzopflipng_amd.so, which keeps LodePNG's decoder.  These entries write the two modes below; strided, planar, float,
+ * 16-bit and little-endian output is the zmx_png_sink's, further down.  How a file ended (the order is the order the
+ * checks are made in): */
 #define ZMX_PNG_DECODE_OK 0
 #define ZMX_PNG_DECODE_SIGNATURE 1   /* a bad signature, or a file shorter than 33 bytes */
 #define ZMX_PNG_DECODE_IHDR 2        /* not IHDR first or its length not 13; width or height 0; an illegal colour type and
@@ -1239,6 +1240,8 @@ int zmx_inflate_device(ZopfliFormat format, const void* d_in, size_t insize, voi
 #define ZMX_PNG_DECODE_SIZE 10       /* the stream does not decode to exactly height * (1 + linebytes) bytes */
 #define ZMX_PNG_DECODE_FILTER 11     /* a row's filter byte is above 4 (detail: the first such row) */
 #define ZMX_PNG_DECODE_CAPACITY 12   /* the pixels take more than capacity[i]: outsize says how much; nothing is stored */
+#define ZMX_PNG_DECODE_SHAPE 13      /* the sink entries: the file's width or height is not its sink's.  Checked after the walk
+                                        and the CRCs, before the stream is read: nothing is inflated, nothing stored */
 
 #define ZMX_PNG_DECODE_OWN 0    /* the file's own colour type and depth, in the layout the encode entries read:
                                    zmx_png_image.d_pixels for colour types 0, 2, 4, 6 at 8 or 16 bits (16-bit samples
@@ -1287,6 +1290,65 @@ int zmx_png_decode_device_batch(int mode, size_t n, const void* const* d_file, c
                                 const size_t* capacity, zmx_png_decode_result* results);
 /* ... of one file. */
 int zmx_png_decode_device(int mode, const void* d_file, size_t filesize, void* d_out, size_t capacity, zmx_png_decode_result* result);
+
+/* -------- decode into strided, planar, float and 16-bit tensors
+ *
+ * The mirror of zmx_png_source: a zmx_png_sink says where sample (y, x, c) of a decoded image GOES — a (C, H, W) float
+ * plane set, one image of an (N, C, H, W) batch, a pitched BGRA frame, a crop, a bottom-up frame, a [::2] view.  `channels`
+ * 1, 2, 3, 4 ask for grey, grey + alpha, RGB, RGBA (LodePNG's LCT_GREY, LCT_GREY_ALPHA, LCT_RGB, LCT_RGBA) at `bitdepth` 8
+ * or 16; PNG channel k of a pixel goes to sink channel order[k].
+ * The value rule: the integer v of a sample is what LodePNG's lodepng_convert gives from the file's own mode — its
+ * palette with the tRNS alpha, its tRNS key — into the mode (that colour type, bitdepth):
+ *   file depth 16 and bitdepth 16: the file's 16-bit values themselves, grey replicated into R, G, B; alpha 65535, or 0
+ *     for a pixel equal to the key in every channel at full depth;
+ *   every other pair: the RGBA8 value of ZMX_PNG_DECODE_RGBA8 (lodepng_decode32's, see above), at bitdepth 16 the byte
+ *     replicated, v * 257;
+ *   grey from a colour file: the R value (LodePNG's average is commented out);
+ *   a palette index at or above palettesize: 0, 0, 0, 255.
+ * From v to the sample: U8 needs bitdepth 8, the byte; U16 needs bitdepth 16, the value stored native (little-endian);
+ * U8 at 16 and U16 at 8 are refused; F32 is fl32(v) / maxv, maxv = 255.0f or 65535.0f, ONE correctly rounded fp32
+ * division (what numpy.float32(v) / numpy.float32(maxv) gives, never a multiply by a reciprocal); F16 and BF16 are that
+ * quotient rounded to nearest-even into the type.
+ * zmx_png_sink_check: host arithmetic — 0, or -1 (ZMX_ERR_REFUSED) for a sink that is refused without asking the runtime
+ * about its memory.
+ * zmx_png_unpack_device: d_own[i] holds an image's pixels as ZMX_PNG_DECODE_OWN writes them (outsize_own bytes) and
+ * modes[i] says what they are — width, height, colortype, bitdepth, palettesize, palette, the key; a result of
+ * zmx_png_info_device or of a decode serves as it is.  ONE launch of k_png_unpack (device/zmx_png_unpack.h) on the
+ * context's stream stores all n images through their sinks: every byte of every sample of a sink is written exactly
+ * once, no other byte — not the pitch's padding, not the bytes between [::2] samples —, no input is written.
+ * Synchronous; n = 0 returns 0.  Refused besides the list below: a modes[i] that is not ZMX_PNG_DECODE_OK or whose colour
+ * type and depth are not legal, a sink whose width or height is not the mode's, a d_own[i] range that is not memory of
+ * the context's device.
+ * The decode entries: zmx_png_decode_device_ctx / _batch / zmx_png_decode_device with sinks in the destinations' place.
+ * The walk, the CRCs, k_inflate, the Adler-32s and k_png_unfilter run unchanged, the last into _OWN pixels in a buffer of
+ * the call's own; ONE k_png_unpack launch then covers every file that ended OK.  A file whose width or height is not its
+ * sink's ends ZMX_PNG_DECODE_SHAPE — nothing of it is inflated, nothing stored into its sink, its result carries the
+ * header.  Every other status, the return value, zmx_last_error*, files beside a bad one and the traffic counters (both
+ * 0) are as for zmx_png_decode_device_batch; what a sink holds after _FILTER is unspecified but inside its samples.
+ * There is no size-only mode.  `hooks` as in zmx_png_decode_device_ctx.
+ * Refused before anything runs (ZMX_ERR_REFUSED), the message naming the index: a null argument, width or height 0,
+ * channels outside 1 .. 4, an unknown sample type, a bit depth other than 8 or 16, the two refused type/depth pairs, an
+ * `order` that is no permutation, a d_data or a stride that is no multiple of the sample's size, a sink whose samples
+ * can share a byte — of the three dimensions with an extent above 1, sorted by |stride| ascending, each |stride| must be
+ * at least the sample's size plus the sum of |stride_j| * (extent_j - 1) over the smaller ones, so stride 0 is refused
+ * here —, an EXTENT (as a source's) that overflows 64 bits, is not plain device memory of the context's device or leaves
+ * its allocation, or that overlaps a file, the input pixels or another sink's extent.
+ * Out of scope: Adam7, broadcast sinks, a colour-to-grey rule other than LodePNG's, gamma. */
+typedef struct zmx_png_sink {
+  void* d_data;                         /* sample (y, x, c) goes to d_data + y*stride_y + x*stride_x + c*stride_c (bytes) */
+  int64_t stride_y, stride_x, stride_c; /* bytes; multiples of the sample's size; any sign */
+  uint32_t width, height, channels /* 1 .. 4 */, sample /* ZMX_PNG_SAMPLE_* */;
+  uint32_t bitdepth;                    /* of the values: 8 or 16 */
+  uint8_t order[4];                     /* PNG channel k of a pixel goes to sink channel order[k] */
+} zmx_png_sink;
+int zmx_png_sink_check(const zmx_png_sink* sink);
+int zmx_png_unpack_device(zmx_ctx* ctx, size_t n, const zmx_png_decode_result* modes, const void* const* d_own,
+                          const zmx_png_sink* sinks);
+int zmx_png_decode_sink_device_ctx(zmx_ctx* ctx, size_t n, const void* const* d_file, const size_t* filesize,
+                                   const zmx_png_sink* sinks, zmx_png_decode_result* results, const zmx_png_decode_hooks* hooks);
+int zmx_png_decode_sink_device_batch(size_t n, const void* const* d_file, const size_t* filesize, const zmx_png_sink* sinks,
+                                     zmx_png_decode_result* results);
+int zmx_png_decode_sink_device(const void* d_file, size_t filesize, const zmx_png_sink* sink, zmx_png_decode_result* result);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -505,8 +505,8 @@ def inflate_device(stream, format="gzip", out=None, size=None, lib=None):
 
 
 PNG_DECODE_STATUS = ["OK", "SIGNATURE", "IHDR", "INTERLACE", "CHUNK", "CRITICAL", "CRC", "PLTE", "TRNS", "STREAM", "SIZE", "FILTER",
-                     "CAPACITY"]   # ZMX_PNG_DECODE_*
-PNG_DECODE_OK, PNG_DECODE_CAPACITY = 0, 12
+                     "CAPACITY", "SHAPE"]   # ZMX_PNG_DECODE_*
+PNG_DECODE_OK, PNG_DECODE_CAPACITY, PNG_DECODE_SHAPE = 0, 12, 13
 PNG_DECODE_OWN, PNG_DECODE_RGBA8 = 0, 1
 
 
@@ -635,8 +635,16 @@ def png_decode_device_batch(files, mode="rgba8", outs=None, lib=None):
     the tensors.  Returns (infos, tensors): uint8 tensors shaped (H, W, 4) for "rgba8"; for "own" (H, linebytes) for palette
     and low-bit images and (H, W, channels * depth / 8) otherwise ((pointer, size) pairs where `outs` holds pairs).  Raises
     PngDecodeError for the first bad file (all results in `.results`), CapacityError (`needed`: the list of sizes) where
-    one does not fit, RuntimeError for a refused pointer or a device failure."""
+    one does not fit, RuntimeError for a refused pointer or a device failure.
+    `outs` may also hold PngSinks, one per file (zmx_png_decode_sink_device_batch): file i is decoded into the tensor of
+    outs[i] as it lies — strided, planar, float, 16-bit —, `mode` is ignored, and (infos, the sinks' tensors) comes back.
+    A file whose size is not its sink's ends PNG_DECODE_SHAPE.  A list that mixes sinks and tensors is a ValueError."""
     lib = lib or library()
+    if outs is not None and _png_are_sinks(outs):
+        rc, results = _png_decode_sink_call(lib, lib.zmx_png_decode_sink_device_batch, "zmx_png_decode_sink_device_batch", [], files, outs)
+        if rc != 0:
+            _png_decode_raise(lib, "zmx_png_decode_sink_device_batch", results, False)
+        return results, [s.tensor for s in outs]
     if outs is None:
         import torch
         infos = png_info_device(files, lib)
@@ -650,7 +658,21 @@ def png_decode_device_batch(files, mode="rgba8", outs=None, lib=None):
 
 
 def png_decode_device(file, mode="rgba8", out=None, lib=None):
-    """png_decode_device_batch of one file.  Returns (info, tensor); CapacityError's `needed` is the size."""
+    """png_decode_device_batch of one file.  Returns (info, tensor); CapacityError's `needed` is the size.  `out` may be a
+    PngSink (zmx_png_decode_sink_device)."""
+    if isinstance(out, PngSink):
+        lib = lib or library()
+        (ptr,), (size,) = _device_ranges([file])
+        _sync_torch([out.tensor])
+        result = PngDecodeResult()
+        fn = lib.zmx_png_decode_sink_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(PngSinkStruct), ctypes.POINTER(PngDecodeResult)]
+        fn.restype = ctypes.c_int
+        if fn(ptr, size, ctypes.byref(out.struct), ctypes.byref(result)) != 0:
+            if result.status == PNG_DECODE_OK:
+                raise RuntimeError("zmx_png_decode_sink_device: " + (lib.zmx_last_error() or b"").decode())
+            _png_decode_raise(lib, "zmx_png_decode_sink_device", [result], True)
+        return result, out.tensor
     try:
         infos, made = png_decode_device_batch([file], mode, None if out is None else [out], lib)
     except CapacityError as e:
@@ -875,9 +897,105 @@ def png_sources(batch, layout="NCHW", order="RGBA", bitdepth=None):
     return [PngSource(batch[i], layout[1:], order, bitdepth) for i in range(batch.shape[0])]
 
 
+class PngSinkStruct(ctypes.Structure):
+    """zmx_png_sink"""
+    _fields_ = PngSourceStruct._fields_
+
+
+class PngSink(PngSource):
+    """A zmx_png_sink: where a decoded image goes, as a GPU program holds it — for `outs` of png_decode_device_batch and
+    Context.png_decode_device, and for Context.png_unpack_device.  `data`: a writable torch tensor of dtype uint8, uint16,
+    float16, bfloat16 or float32 on the device, contiguous or not, its strides taken as they are, shaped as PngSource's;
+    or the tuple that spells out the struct.  The channels say what is asked for: 1 grey, 2 grey + alpha, 3 RGB, 4 RGBA;
+    PNG channel k goes to the tensor's channel order[k] ("BGRA": the first three reversed).  `bitdepth`: of the values, 8
+    or 16; None: 16 for uint16, else 8.  Integers hold the value, floats value / 255 or value / 65535 (one fp32 division,
+    rounded to nearest-even into float16 and bfloat16).  No two samples may share a byte: an expand() is refused.  The
+    object keeps the tensor alive."""
+
+    def __init__(self, data, layout="HWC", order="RGBA", bitdepth=None):
+        super().__init__(data, layout, order, bitdepth)
+        self.struct = PngSinkStruct.from_buffer_copy(self.struct)
+
+
+def png_sinks(batch, layout="NCHW", order="RGBA", bitdepth=None):
+    """The PngSinks of a batch tensor (N, C, H, W) or (N, H, W, C) — layout "NCHW" or "NHWC" —, one per image, views without
+    a copy: a batch of files decoded into one tensor."""
+    if layout not in ("NCHW", "NHWC"):
+        raise ValueError(f'layout is "NCHW" or "NHWC", not {layout!r}')
+    return [PngSink(batch[i], layout[1:], order, bitdepth) for i in range(batch.shape[0])]
+
+
+def _png_are_sinks(outs):
+    """Whether a list of destinations holds PngSinks (all of it: a mixed list is an error)."""
+    kinds = {isinstance(out, PngSink) for out in outs}
+    if kinds == {True, False}:
+        raise ValueError("a list of destinations holds PngSinks or tensors, not both")
+    return kinds == {True}
+
+
+def _png_sink_array(sinks):
+    n = len(sinks)
+    return (PngSinkStruct * max(n, 1))(*[s.struct for s in sinks])
+
+
+def png_sink_check(sink, lib=None):
+    """zmx_png_sink_check: RuntimeError with the library's message for a PngSink the entries refuse without asking the
+    runtime about its memory — host arithmetic."""
+    lib = lib or library()
+    fn = lib.zmx_png_sink_check
+    fn.argtypes = [ctypes.POINTER(PngSinkStruct)]
+    fn.restype = ctypes.c_int
+    if fn(ctypes.byref(sink.struct)) != 0:
+        raise RuntimeError((lib.zmx_last_error() or b"").decode())
+
+
+def _png_decode_sink_call(lib, fn, who, ctx_args, files, sinks, tail=()):
+    """One decode entry that takes sinks.  Returns (rc, results)."""
+    ptrs, sizes = _device_ranges(files)
+    n = len(ptrs)
+    if len(sinks) != n:
+        raise ValueError(f"{n} files, but {len(sinks)} sinks")
+    _sync_torch(s.tensor for s in sinks)
+    results = (PngDecodeResult * max(n, 1))()
+    P, sz, vp = ctypes.POINTER, ctypes.c_size_t, ctypes.c_void_p
+    fn.argtypes = [vp] * len(ctx_args) + [sz, P(vp), P(sz), P(PngSinkStruct), P(PngDecodeResult)] + [t for t, _ in tail]
+    fn.restype = ctypes.c_int
+    rc = fn(*ctx_args, n, (vp * max(n, 1))(*ptrs), (sz * max(n, 1))(*sizes), _png_sink_array(sinks), results, *[v for _, v in tail])
+    found = [results[i] for i in range(n)]
+    if rc != 0 and all(r.status == PNG_DECODE_OK for r in found):
+        raise RuntimeError(who + ": " + (lib.zmx_last_error() or b"").decode())
+    return rc, found
+
+
+def png_decode_tensors(files, dtype=None, channels=3, layout="NCHW", bitdepth=None, lib=None):
+    """The loader's call: PNG files of ONE size in device memory (what png_decode_device_batch takes) decoded into one batch
+    tensor (N, channels, H, W) — layout "NHWC": (N, H, W, channels) — of `dtype` (default torch.float32): one
+    png_info_device round, one tensor, one decode call with a PngSink per image.  channels 1 .. 4: grey, grey + alpha, RGB,
+    RGBA, whatever the files' own colour types; `bitdepth` as PngSink's.  Returns (infos, tensor).  ValueError names the
+    first file whose size is not the first file's; PngDecodeError as png_decode_device_batch."""
+    import torch
+    lib = lib or library()
+    if layout not in ("NCHW", "NHWC"):
+        raise ValueError(f'layout is "NCHW" or "NHWC", not {layout!r}')
+    dtype = dtype or torch.float32
+    infos = png_info_device(files, lib)
+    devices = [f.device for f in files if not isinstance(f, (tuple, list))]
+    device = devices[0] if devices else "cuda"
+    if not infos:
+        return [], torch.empty((0, channels, 0, 0) if layout == "NCHW" else (0, 0, 0, channels), dtype=dtype, device=device)
+    w, h = int(infos[0].width), int(infos[0].height)
+    for i, r in enumerate(infos):
+        if (int(r.width), int(r.height)) != (w, h):
+            raise ValueError(f"file {i} is {int(r.width)} x {int(r.height)}, file 0 is {w} x {h}: one batch tensor takes one size")
+    n = len(infos)
+    batch = torch.empty((n, channels, h, w) if layout == "NCHW" else (n, h, w, channels), dtype=dtype, device=device)
+    infos, _ = png_decode_device_batch(files, outs=png_sinks(batch, layout, "RGBA", bitdepth), lib=lib)
+    return infos, batch
+
+
 def _png_are_sources(images):
     """Whether a list holds PngSources (all of it: a mixed list is an error)."""
-    kinds = {isinstance(image, PngSource) for image in images}
+    kinds = {isinstance(image, PngSource) and not isinstance(image, PngSink) for image in images}
     if kinds == {True, False}:
         raise ValueError("a list holds PngSources or images, not both")
     return kinds == {True}
@@ -1532,6 +1650,23 @@ class Context:
         self._check(fn(self.handle, n, _png_source_array(sources), (ctypes.c_void_p * max(n, 1))(*ptrs),
                        (ctypes.c_size_t * max(n, 1))(*capacities)), "zmx_png_pack_device")
 
+    def png_unpack_device(self, modes, owns, sinks):
+        """zmx_png_unpack_device: own-mode pixels into sinks — modes[i] (a PngDecodeResult of png_info_device or of a decode)
+        says what owns[i] (a contiguous uint8 tensor or an (integer device pointer, nbytes) pair: the OWN mode's bytes)
+        holds, sinks[i] (a PngSink) where it goes.  ONE launch whatever their number.  The tensors' current streams are
+        synchronised once per device."""
+        if not len(modes) == len(owns) == len(sinks):
+            raise ValueError(f"{len(modes)} modes, {len(owns)} images, {len(sinks)} sinks")
+        _sync_torch(s.tensor for s in sinks)
+        ptrs, _ = _device_ranges(owns)
+        n = len(sinks)
+        fn = self.lib.zmx_png_unpack_device
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(PngDecodeResult), ctypes.POINTER(ctypes.c_void_p),
+                       ctypes.POINTER(PngSinkStruct)]
+        fn.restype = ctypes.c_int
+        self._check(fn(self.handle, n, (PngDecodeResult * max(n, 1))(*modes), (ctypes.c_void_p * max(n, 1))(*ptrs), _png_sink_array(sinks)),
+                    "zmx_png_unpack_device")
+
     def png_lossy_transparent_device(self, image, out, capacity=None):
         """zmx_png_lossy_transparent_device: zopflipng's --lossy_transparent rewrite of the image (`image` as
         png_encode_device takes it) into `out`, a tensor or an integer pointer with `capacity` bytes (an integer pointer
@@ -1705,6 +1840,10 @@ class Context:
         list of PngDecodeResult, whatever the files' statuses; raises RuntimeError where the call itself is refused or the
         device fails."""
         hooks = PngDecodeHooks(1 if force_wide else 0, int(idat_capacity or 0))
+        if outs is not None and _png_are_sinks(outs):
+            # (zmx_png_decode_sink_device_ctx: `mode` is ignored)
+            return _png_decode_sink_call(self.lib, self.lib.zmx_png_decode_sink_device_ctx, "zmx_png_decode_sink_device_ctx", [self.handle], files,
+                                         outs, tail=[(ctypes.POINTER(PngDecodeHooks), ctypes.byref(hooks))])[1]
         return _png_decode_call(self.lib, self.lib.zmx_png_decode_device_ctx, "zmx_png_decode_device_ctx", [self.handle], mode, files, outs,
                                 tail=[(ctypes.POINTER(PngDecodeHooks), ctypes.byref(hooks))])[1]
 

@@ -1,8 +1,11 @@
 // Driver part: PNG decode on the device (zmx_png_decode.h).  Holds the run that every decode entry shares
-// (zmx_internal_png_decode_run: the chunk walk, the CRCs, the gather of split IDATs, k_inflate, the Adler-32s, k_png_unfilter)
-// and zmx_png_decode_device_ctx, the step on a context the caller holds.
+// (zmx_internal_png_decode_run: the chunk walk, the CRCs, the gather of split IDATs, k_inflate, the Adler-32s, k_png_unfilter;
+// with sinks — zmx_internal_png_decode_sink_run — the unfilter writes _OWN pixels into a buffer of the call's own and one
+// k_png_unpack launch stores them through the sinks) and zmx_png_decode_device_ctx and zmx_png_decode_sink_device_ctx, the
+// steps on a context the caller holds.
 // Needs drv_context.h (zmx_ctx, PoolScope, KernelTiming), drv_input.h (DeviceRangeChecker, zmx_gather_device),
-// drv_checksum_device.h (RunChecksumDevice), drv_inflate.h (zmx_internal_inflate_run), host/png_decode_plan.h.
+// drv_checksum_device.h (RunChecksumDevice), drv_inflate.h (zmx_internal_inflate_run), drv_png_unpack.h (PngSinksCheck,
+// PngUnpackAddJob, PngUnpackEnqueue), host/png_decode_plan.h.
 #pragma once
 #include <chrono>
 
@@ -10,7 +13,8 @@ static_assert(zamd::kPngDecOk == ZMX_PNG_DECODE_OK && zamd::kPngDecSignature == 
                   zamd::kPngDecInterlace == ZMX_PNG_DECODE_INTERLACE && zamd::kPngDecChunk == ZMX_PNG_DECODE_CHUNK &&
                   zamd::kPngDecCritical == ZMX_PNG_DECODE_CRITICAL && zamd::kPngDecCrc == ZMX_PNG_DECODE_CRC && zamd::kPngDecPlte == ZMX_PNG_DECODE_PLTE &&
                   zamd::kPngDecTrns == ZMX_PNG_DECODE_TRNS && zamd::kPngDecStream == ZMX_PNG_DECODE_STREAM && zamd::kPngDecSize == ZMX_PNG_DECODE_SIZE &&
-                  zamd::kPngDecFilter == ZMX_PNG_DECODE_FILTER && zamd::kPngDecCapacity == ZMX_PNG_DECODE_CAPACITY,
+                  zamd::kPngDecFilter == ZMX_PNG_DECODE_FILTER && zamd::kPngDecCapacity == ZMX_PNG_DECODE_CAPACITY &&
+                  zamd::kPngDecShape == ZMX_PNG_DECODE_SHAPE,
               "the kernels' statuses are the ABI's");
 static_assert(zamd::kPngDecOwn == ZMX_PNG_DECODE_OWN && zamd::kPngDecRgba8 == ZMX_PNG_DECODE_RGBA8, "the kernels' modes are the ABI's");
 static_assert(sizeof(zamd::PngUnfilterScratch) <= 18 * 1024, "a wave's LDS: eight waves a CU");
@@ -49,22 +53,16 @@ int PngWalkLaunch(zmx_ctx* c, PoolScope* tmp, const std::vector<zamd::PngFileRef
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
 static thread_local double g_png_decode_ms[2] = {0, 0};   // (zmx_internal_png_decode_ms)
-void zmx_internal_png_decode_ms(double out[2]) {
-  out[0] = g_png_decode_ms[0];
-  out[1] = g_png_decode_ms[1];
-}
 // the host's clock at the phases' ends: the walk, the CRCs, the gather and k_inflate, the Adler-32s, the unfilter
 static thread_local double g_png_decode_phase_ms[5] = {0, 0, 0, 0, 0};   // (zmx_internal_png_decode_phase_ms)
-void zmx_internal_png_decode_phase_ms(double out[5]) {
-  for (int i = 0; i < 5; ++i) out[i] = g_png_decode_phase_ms[i];
-}
 
-int zmx_internal_png_decode_run(zmx_ctx* c, const char* who, int mode, int info_only, size_t n, const void* const* d_file, const size_t* filesize,
-                                void* const* d_out, const size_t* capacity, zmx_png_decode_result* results, const zmx_png_decode_hooks* hooks) {
+// The run.  `sinks` null: file i's pixels in `mode` go to d_out[i].  Else (mode _OWN, d_out and capacity null): a file
+// whose size is its sink's is unfiltered into a buffer of the call's own and stored through sinks[i] by k_png_unpack, one
+// launch for all of them behind the unfilter.
+int PngDecodeRun(zmx_ctx* c, const char* who, int mode, int info_only, size_t n, const void* const* d_file, const size_t* filesize,
+                 void* const* d_out, const size_t* capacity, const zmx_png_sink* sinks, zmx_png_decode_result* results,
+                 const zmx_png_decode_hooks* hooks) {
   g_png_decode_ms[0] = g_png_decode_ms[1] = 0;
   for (double& t : g_png_decode_phase_ms) t = 0;
   if (n == 0) return 0;
@@ -74,6 +72,8 @@ int zmx_internal_png_decode_run(zmx_ctx* c, const char* who, int mode, int info_
   const bool timed = KernelTiming();
   const u32 cap0 = hooks && hooks->idat_capacity ? hooks->idat_capacity : zamd::kPngDecEntries;
   const bool force_wide = hooks && hooks->force_wide;
+  std::vector<void*> own_out;        // (sinks: where the unfilter writes, and how much)
+  std::vector<size_t> own_capacity;
   const auto stored = [&](size_t i) { return !info_only && d_out && d_out[i]; };
   auto clock = std::chrono::steady_clock::now();
   const auto phase_done = [&](int phase) {   // (every phase ends with the stream drained)
@@ -154,6 +154,34 @@ int zmx_internal_png_decode_run(zmx_ctx* c, const char* who, int mode, int info_
     }
     phase_done(1);
     if (info_only) return 0;
+    if (sinks) {
+      // ---- a file whose size is not its sink's ends here; the others get their _OWN pixels' room
+      size_t own_total = 0;
+      std::vector<size_t> own_at(n, 0);
+      for (size_t i = 0; i < n; ++i) {
+        if (results[i].status != ZMX_PNG_DECODE_OK) continue;
+        if (results[i].width != sinks[i].width || results[i].height != sinks[i].height) {
+          results[i].status = ZMX_PNG_DECODE_SHAPE;
+          results[i].detail = 0;
+          continue;
+        }
+        own_at[i] = own_total;
+        own_total += PngAlign16(static_cast<size_t>(results[i].outsize_own));
+      }
+      if (own_total > c->code_budget) return FailMsg(std::string(who) + ": the call's pixels are beyond the context's budget");
+      unsigned char* d_own = nullptr;
+      HIPCHK(tmp.AllocT(&d_own, own_total + 16, "png_decode_own"));
+      d_own = reinterpret_cast<unsigned char*>(PngAlign16(reinterpret_cast<uintptr_t>(d_own)));
+      own_out.assign(n, nullptr);
+      own_capacity.assign(n, 0);
+      for (size_t i = 0; i < n; ++i) {
+        if (results[i].status != ZMX_PNG_DECODE_OK) continue;
+        own_out[i] = d_own + own_at[i];
+        own_capacity[i] = static_cast<size_t>(results[i].outsize_own);
+      }
+      d_out = own_out.data();
+      capacity = own_capacity.data();
+    }
     // ---- where each stream lies: one IDAT with bytes is read in place, several are put end to end
     std::vector<size_t> which;                       // the files that have a stream, in the caller's order
     std::vector<const void*> in;                     // (null: gathered, see gather_at)
@@ -321,6 +349,16 @@ int zmx_internal_png_decode_run(zmx_ctx* c, const char* who, int mode, int info_
         results[jobs[w][k].index].detail = unf[w][k].row;
       }
     }
+    if (sinks) {
+      // ---- k_png_unpack: every file that ended OK, one launch
+      std::vector<zamd::PngUnpackJob> unpack;
+      std::vector<uint32_t> unpack_palettes;
+      for (size_t i = 0; i < n; ++i) {
+        if (results[i].status == ZMX_PNG_DECODE_OK) PngUnpackAddJob(sinks[i], results[i], d_out[i], &unpack, &unpack_palettes);
+      }
+      if (const int rc = PngUnpackEnqueue(c, &tmp, unpack, unpack_palettes, false)) return rc;
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
     return 0;
   };
   if (const int rc = run()) {
@@ -328,6 +366,42 @@ int zmx_internal_png_decode_run(zmx_ctx* c, const char* who, int mode, int info_
     return rc;
   }
   return 0;
+}
+
+// What the sink entries refuse of their sinks against their files: PngSinksCheck, and no extent may share a byte with a file.
+int PngDecodeSinksCheck(zmx_ctx* c, const std::string& w, size_t n, const void* const* d_file, const size_t* filesize, const zmx_png_sink* sinks) {
+  zamd::ApartRanges extents;
+  if (const int rc = PngSinksCheck(c, w, n, sinks, &extents)) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    const uintptr_t at = reinterpret_cast<uintptr_t>(d_file[i]);
+    size_t hit = 0;
+    if (extents.Hit(at, at + filesize[i], &hit)) return FailMsg(w + ": sink " + std::to_string(hit) + ": its extent overlaps file " + std::to_string(i));
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+void zmx_internal_png_decode_ms(double out[2]) {
+  out[0] = g_png_decode_ms[0];
+  out[1] = g_png_decode_ms[1];
+}
+void zmx_internal_png_decode_phase_ms(double out[5]) {
+  for (int i = 0; i < 5; ++i) out[i] = g_png_decode_phase_ms[i];
+}
+
+int zmx_internal_png_decode_run(zmx_ctx* c, const char* who, int mode, int info_only, size_t n, const void* const* d_file, const size_t* filesize,
+                                void* const* d_out, const size_t* capacity, zmx_png_decode_result* results, const zmx_png_decode_hooks* hooks) {
+  return PngDecodeRun(c, who, mode, info_only, n, d_file, filesize, d_out, capacity, nullptr, results, hooks);
+}
+
+int zmx_internal_png_decode_sink_run(zmx_ctx* c, const char* who, size_t n, const void* const* d_file, const size_t* filesize,
+                                     const zmx_png_sink* sinks, zmx_png_decode_result* results, const zmx_png_decode_hooks* hooks) {
+  if (n == 0) return 0;
+  if (n > kPngDecodeMaxFiles) return FailMsg(std::string(who) + ": too many files for one call");
+  if (const int rc = PngDecodeSinksCheck(c, who, n, d_file, filesize, sinks)) return rc;
+  return PngDecodeRun(c, who, ZMX_PNG_DECODE_OWN, 0, n, d_file, filesize, nullptr, nullptr, sinks, results, hooks);
 }
 
 int zmx_png_decode_device_ctx(zmx_ctx* c, int mode, size_t n, const void* const* d_file, const size_t* filesize, void* const* d_out,
@@ -357,6 +431,31 @@ int zmx_png_decode_device_ctx(zmx_ctx* c, int mode, size_t n, const void* const*
   std::copy(got.begin(), got.end(), results);
   int error_class = ZMX_ERR_NONE;
   const std::string verdict = zamd::PngDecodeVerdict(kWho, n, results, d_out ? capacity : nullptr, &error_class);
+  if (verdict.empty()) return 0;
+  g_err = verdict;
+  g_err_class = error_class;
+  return -1;
+}
+
+int zmx_png_decode_sink_device_ctx(zmx_ctx* c, size_t n, const void* const* d_file, const size_t* filesize, const zmx_png_sink* sinks,
+                                   zmx_png_decode_result* results, const zmx_png_decode_hooks* hooks) {
+  static const char* const kWho = "zmx_png_decode_sink_device_ctx";
+  if (!c) return FailMsg(std::string(kWho) + ": no context");
+  if (n == 0) return 0;
+  if (!d_file || !filesize || !sinks || !results) return FailMsg(std::string(kWho) + ": null array");
+  DeviceRangeChecker in_checker;
+  for (size_t i = 0; i < n; ++i) {
+    int device = -1;
+    const std::string w = std::string(kWho) + ": file " + std::to_string(i);
+    if (filesize[i] != 0 && !d_file[i]) return FailMsg(w + ": null pointer with a non-zero size");
+    if (const int rc = in_checker.Check(w.c_str(), d_file[i], filesize[i], &device)) return rc;
+    if (device >= 0 && device != c->device) return FailMsg(w + " is not memory of the context's device");
+  }
+  std::vector<zmx_png_decode_result> got(n);
+  if (const int rc = zmx_internal_png_decode_sink_run(c, kWho, n, d_file, filesize, sinks, got.data(), hooks)) return rc;
+  std::copy(got.begin(), got.end(), results);
+  int error_class = ZMX_ERR_NONE;
+  const std::string verdict = zamd::PngDecodeVerdict(kWho, n, results, nullptr, &error_class);
   if (verdict.empty()) return 0;
   g_err = verdict;
   g_err_class = error_class;

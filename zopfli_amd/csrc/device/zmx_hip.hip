@@ -54,6 +54,8 @@
 #include "zmx_png_index.h"   // index images: where each value first appears, the table-driven conversion
 #define ZMX_PNG_PACK_KERNELS
 #include "zmx_png_pack.h"    // strided, planar, typed sources into PNG byte order, n of them in one launch
+#define ZMX_PNG_UNPACK_KERNELS
+#include "zmx_png_unpack.h"  // own-mode pixels into strided, planar, typed sinks, n of them in one launch
 #define ZMX_PNG_LOSSY_KERNELS
 #include "zmx_png_lossy.h"   // zopflipng's --lossy_transparent: statistics, the carry scan, the rewrite
 #define ZMX_PNG_LODEFLATE_KERNELS
@@ -69,6 +71,7 @@
 #include "../host/png_brute_launch.h"
 #include "../host/png_lodeflate_size.h"
 #include "../host/png_source.h"
+#include "../host/png_sink.h"
 #include "../host/symbol_check.h"
 #include "../host/thread_pool.h"
 
@@ -85,7 +88,8 @@
 #include "drv_checksum.h"    // zmx_checksum, zmx_checksums
 #include "drv_checksum_device.h"   // zmx_checksum_device, the seal of a PNG left in device memory
 #include "drv_inflate.h"     // k_inflate's launch, zmx_inflate_device_ctx
-#include "drv_png_decode.h"  // the PNG decode: the run every entry shares, zmx_png_decode_device_ctx
+#include "drv_png_unpack.h"  // zmx_png_unpack_device; the sinks' checks and k_png_unpack's launch
+#include "drv_png_decode.h"  // the PNG decode: the run every entry shares, zmx_png_decode_device_ctx, zmx_png_decode_sink_device_ctx
 #include "drv_png.h"         // the PNG entries: row searches on host and device images, the filtered scanlines, colour statistics and conversion, index images, LodePNG's zlib sizes
 #include "drv_png_pack.h"    // zmx_png_pack_device
 #include "drv_blockcost.h"   // zmx_cost_stores and its five entries

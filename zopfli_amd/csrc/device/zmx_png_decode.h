@@ -66,6 +66,7 @@ enum PngDecodeStatus : uint32_t {
   kPngDecSize,        // (host)
   kPngDecFilter,
   kPngDecCapacity,    // (host)
+  kPngDecShape,       // (host, the sink entries: the file's size is not its sink's)
   kPngDecStatuses
 };
 constexpr uint32_t kPngDecOwn = 0, kPngDecRgba8 = 1;   // (ZMX_PNG_DECODE_OWN, _RGBA8)

@@ -5,11 +5,14 @@
 // zmx_internal_png_decode_run on it (device/drv_png_decode.h): k_png_chunks over all files, the chunks' CRC-32s, split IDATs
 // put end to end, k_inflate into the call's scanline buffer, the Adler-32s, k_png_unfilter into the destinations.  No byte
 // of a file, of its stream or of its pixels visits the host: zmx_last_input_traffic and zmx_last_output_traffic stay 0.
+// The zmx_png_decode_sink_* entries and zmx_png_sink_check: the same run with zmx_png_sinks in the destinations' place
+// (png_sink.h has what is refused of one without a device).
 #include <string>
 #include <vector>
 
 #include "dealing.h"
 #include "png_decode_plan.h"
+#include "png_sink.h"
 #include "zmx_internal.h"
 #include "zopfli_amd.h"
 
@@ -51,7 +54,49 @@ int DecodeBatch(const char* who, int mode, bool info_only, size_t n, const void*
   return -1;
 }
 
+// The decode into sinks: the files' ranges are checked here, the sinks on the context that runs (their extents must be its
+// device's).
+int DecodeSinkBatch(const char* who, size_t n, const void* const* d_file, const size_t* filesize, const zmx_png_sink* sinks,
+                    zmx_png_decode_result* results) {
+  if (n == 0) return 0;
+  if (!d_file || !filesize || !sinks || !results) return Refuse(std::string(who) + ": null array");
+  zamd::ResetCallStats();
+  int in_device = -1;
+  if (zmx_internal_device_pointers_one_device((std::string(who) + ": d_file").c_str(), n, d_file, filesize, &in_device) != 0) return -1;
+  for (size_t i = 0; i < n; ++i) {
+    // (before a context is taken: what needs no runtime)
+    const std::string msg = zamd::CheckPngSink((std::string(who) + ": sink " + std::to_string(i)).c_str(), &sinks[i], nullptr);
+    if (!msg.empty()) return Refuse(msg);
+  }
+  std::vector<zmx_png_decode_result> got(n);
+  const int rc = zamd::OnPooledContext([&](zmx_ctx* ctx) {
+    return zmx_internal_png_decode_sink_run(ctx, who, n, d_file, filesize, sinks, got.data(), nullptr);
+  }, in_device);
+  if (rc != 0) return rc;
+  for (size_t i = 0; i < n; ++i) results[i] = got[i];
+  int error_class = ZMX_ERR_NONE;
+  const std::string verdict = zamd::PngDecodeVerdict(who, n, results, nullptr, &error_class);
+  if (verdict.empty()) return 0;
+  zmx_internal_set_error(verdict.c_str(), error_class);
+  return -1;
+}
+
 }  // namespace
+
+extern "C" int zmx_png_sink_check(const zmx_png_sink* sink) {
+  const std::string msg = zamd::CheckPngSink("zmx_png_sink_check", sink, nullptr);
+  return msg.empty() ? 0 : Refuse(msg);
+}
+
+extern "C" int zmx_png_decode_sink_device_batch(size_t n, const void* const* d_file, const size_t* filesize, const zmx_png_sink* sinks,
+                                                zmx_png_decode_result* results) {
+  return DecodeSinkBatch("zmx_png_decode_sink_device_batch", n, d_file, filesize, sinks, results);
+}
+
+extern "C" int zmx_png_decode_sink_device(const void* d_file, size_t filesize, const zmx_png_sink* sink, zmx_png_decode_result* result) {
+  if (!sink || !result) return Refuse("zmx_png_decode_sink_device: null argument");
+  return DecodeSinkBatch("zmx_png_decode_sink_device", 1, &d_file, &filesize, sink, result);
+}
 
 extern "C" int zmx_png_info_device(size_t n, const void* const* d_file, const size_t* filesize, zmx_png_decode_result* results) {
   return DecodeBatch("zmx_png_info_device", ZMX_PNG_DECODE_OWN, true, n, d_file, filesize, nullptr, nullptr, results);

@@ -20,7 +20,7 @@ inline const char* PngDecodeStatusName(uint32_t status) {
   static const char* const kNames[kPngDecStatuses] = {
       "ZMX_PNG_DECODE_OK", "ZMX_PNG_DECODE_SIGNATURE", "ZMX_PNG_DECODE_IHDR", "ZMX_PNG_DECODE_INTERLACE", "ZMX_PNG_DECODE_CHUNK",
       "ZMX_PNG_DECODE_CRITICAL", "ZMX_PNG_DECODE_CRC", "ZMX_PNG_DECODE_PLTE", "ZMX_PNG_DECODE_TRNS", "ZMX_PNG_DECODE_STREAM",
-      "ZMX_PNG_DECODE_SIZE", "ZMX_PNG_DECODE_FILTER", "ZMX_PNG_DECODE_CAPACITY"};
+      "ZMX_PNG_DECODE_SIZE", "ZMX_PNG_DECODE_FILTER", "ZMX_PNG_DECODE_CAPACITY", "ZMX_PNG_DECODE_SHAPE"};
   return status < kPngDecStatuses ? kNames[status] : "an unknown status";
 }
 

@@ -127,6 +127,12 @@ int zmx_internal_png_decode_run(zmx_ctx* ctx, const char* who, int mode, int inf
                                 const size_t* filesize, void* const* d_out, const size_t* capacity, zmx_png_decode_result* results,
                                 const zmx_png_decode_hooks* hooks);
 
+// The same into sinks (include/zopfli_amd.h: zmx_png_sink): the sinks are checked here — each one, its extent against the
+// runtime, against the other sinks and against the files —, a file whose size is not its sink's ends ZMX_PNG_DECODE_SHAPE
+// before its stream is read, and one k_png_unpack launch stores every file that ended OK.
+int zmx_internal_png_decode_sink_run(zmx_ctx* ctx, const char* who, size_t n, const void* const* d_file, const size_t* filesize,
+                                     const zmx_png_sink* sinks, zmx_png_decode_result* results, const zmx_png_decode_hooks* hooks);
+
 // ---- a PNG from an image in device memory (png_encode.cc)
 // The filter types of `strategy` (a ZMX_PNG_FILTER_*; _BRUTE with window `windowsize`; _PREDEFINED: the `height` host
 // bytes at `predefined`, each at most 4) and then the filtered scanlines of d_image (zmx_png_filter_rows_device) into
@@ -211,6 +217,8 @@ ZMX_INTERNAL_EXPORT void zmx_internal_png_decode_ms(double out[2]);
 // The same call by the host's clock, whether kernel timing is on or not: the walk with its records down, the chunks'
 // CRC-32s, the gather and k_inflate, the Adler-32s, k_png_unfilter with its results down.
 ZMX_INTERNAL_EXPORT void zmx_internal_png_decode_phase_ms(double out[5]);
+// The same for the calling thread's last zmx_png_unpack_device: k_png_unpack.  For tools/png_sink.py.
+ZMX_INTERNAL_EXPORT double zmx_internal_png_unpack_ms(void);
 // The same for the calling thread's last zmx_png_pack_device: k_png_pack.  For tools/png_source.py.
 ZMX_INTERNAL_EXPORT double zmx_internal_png_pack_ms(void);
 // Test hook (tests/test_cpu_abi.py): the acceptance facts of one cost model (320 costs: 288 litlen, 32 distance) as a
